@@ -95,3 +95,20 @@ def row_of(rix, m, r, frac):
     if frac:
         return q * (r + 1) + res if res <= r else None
     return q if res == r else None
+
+
+def llh_live_cases():
+    """The 300 seeded random likelihood problems of test_oracle_ref.py::test_llh_matches_reference_live, as
+    (k, h, th, hist, uc, rho, d); tests/golden/llh_live_ref.json holds the reference's value of each (make_golden.py)."""
+    rng = np.random.default_rng(5)
+    cases = []
+    for _ in range(300):
+        k = int(rng.integers(19, 32))
+        h = int(rng.integers(max(3, k - 16), 16))
+        th = int(rng.integers(0, 7))
+        hist = np.floor(rng.random(th + 1) * 40)
+        uc = float(rng.integers(0, 120))
+        rho = float(rng.uniform(0.01, 1.0))
+        d = float(10 ** rng.uniform(-9, np.log10(0.5)))
+        cases.append((k, h, th, hist, uc, rho, d))
+    return cases

@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -24,7 +25,7 @@ def run_bench(*args):
 
 
 def test_bench_two_ranks_on_one_gpu():
-    out = run_bench("--gpus", "2", "--backend", "gloo", "--ranks-share-device", "--workload", "toy25", "--reads-per-step", "100000",
+    out = run_bench("--full", "--gpus", "2", "--backend", "gloo", "--ranks-share-device", "--workload", "toy25", "--reads-per-step", "100000",
                     "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--check-reads", "3000", "--distinct-batches", "2")
     assert out["n_gpus"] == 2 and out["scaling"] == "weak"
     assert len(out["per_rank_reads_per_s"]) == 2 and min(out["per_rank_reads_per_s"]) > 0
@@ -35,7 +36,7 @@ def test_bench_two_ranks_on_one_gpu():
 
 
 def test_bench_default_line_small():
-    out = run_bench("--workload", "toy25", "--reads-per-step", "200000", "--steps", "3", "--warmup", "1", "--cpu-seconds", "2",
+    out = run_bench("--full", "--workload", "toy25", "--reads-per-step", "200000", "--steps", "3", "--warmup", "1", "--cpu-seconds", "2",
                     "--check-reads", "3000", "--distinct-batches", "2")
     assert out["n_gpus"] == 1 and out["unit"] == "reads/s" and out["vs_baseline"] is None
     rl = out["roofline"]
@@ -67,7 +68,7 @@ def test_bench_one_rank_rccl_replicates_the_index():
     buffers -> dist.broadcast per buffer) on a ONE-rank `nccl` (= RCCL) process group, on the GPU: torch, RCCL and raw
     device pointers meet on hardware here, before the driver's 8-GPU run (src/krepp.cpp:92-106 is the load loop it
     replaces).  The index that went through it still answers like the oracle."""
-    out = run_bench("--force-replicate", "--backend", "nccl", "--workload", "toy25", "--reads-per-step", "100000", "--steps", "2",
+    out = run_bench("--full", "--force-replicate", "--backend", "nccl", "--workload", "toy25", "--reads-per-step", "100000", "--steps", "2",
                     "--warmup", "1", "--no-cpu-baseline", "--no-host-inclusive", "--check-reads", "3000", "--distinct-batches", "1")
     bc = out["index_broadcast"]
     assert bc["backend"] == "nccl" and bc["world"] == 1 and bc["bytes"] == out["config"]["index_device_bytes"] > 1e6
@@ -81,7 +82,7 @@ def test_bench_two_ranks_on_the_10000_genome_index():
     gloo: rank 0 builds, inflates and uploads the index, every flat buffer is broadcast to rank 1 (kr_index_export ->
     kr_index_import), the ranks run their own read shards, rank 0 checks the rows of its last timed launch against the oracle.
     (The driver's SCALE run uses the same command with --backend nccl and one GPU per rank: BASELINE.md.)"""
-    out = run_bench("--gpus", "2", "--backend", "gloo", "--ranks-share-device", "--workload", "syn10000", "--index-gb", "1", "--reads-per-step", "200000",
+    out = run_bench("--full", "--gpus", "2", "--backend", "gloo", "--ranks-share-device", "--workload", "syn10000", "--index-gb", "1", "--reads-per-step", "200000",
                     "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--check-reads", "2000", "--distinct-batches", "1")
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and "10000-genome" in out["config"]["workload"]
     assert len(out["per_rank_reads_per_s"]) == 2 and min(out["per_rank_reads_per_s"]) > 0
@@ -95,7 +96,7 @@ def test_bench_eight_ranks_share_one_gpu():
     kr_index_import + broadcast receptions (gloo carrying the device buffers; the driver's run is this command with
     --backend nccl and a GPU per rank), eight read shards, MAX-over-ranks timing, and the rows of rank 0's last timed
     launch equal to the oracle's (src/krepp.cpp:92-106 is the load loop, :360-387 the batch loop this replaces)."""
-    out = run_bench("--gpus", "8", "--backend", "gloo", "--ranks-share-device", "--workload", "syn10000", "--index-gb", "1",
+    out = run_bench("--full", "--gpus", "8", "--backend", "gloo", "--ranks-share-device", "--workload", "syn10000", "--index-gb", "1",
                     "--reads-per-step", "100000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-host-inclusive",
                     "--check-reads", "2000", "--distinct-batches", "1")
     assert out["n_gpus"] == 8 and out["scaling"] == "weak" and "10000-genome" in out["config"]["workload"]
@@ -117,7 +118,7 @@ def test_bench_eight_ranks_at_the_full_table_size():
     not fit beside eight replicas in ONE GPU's 288 GB; a rank that owns its GPU does not need the cap.)"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env["KR_ACC_SCRATCH_GB"] = "2"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--backend", "gloo", "--ranks-share-device", "--workload", "syn10000",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "8", "--backend", "gloo", "--ranks-share-device", "--workload", "syn10000",
                         "--reads-per-step", "1000000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-host-inclusive", "--check-reads", "2000"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -131,3 +132,28 @@ def test_bench_eight_ranks_at_the_full_table_size():
     assert ck["whole_launch"]["equal_on_an_independent_stream"] and ck["whole_launch"]["rows"] > 10_000_000
     print(f"8 ranks, full table: setup_s {out['setup_s']:.1f} ({out['setup_parts_s']}), {out['value'] / 1e6:.1f} M reads/s whole job")
 
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run times the steps and reports the headline only; `--dump-outputs` writes the rows of the last timed step for a
+    fixed sample of its reads, the same from run to run and with or without `--full` (whose check of that launch against the
+    oracle passes)."""
+    args = ("--workload", "toy25", "--reads-per-step", "100000", "--steps", "3", "--warmup", "1", "--distinct-batches", "2",
+            "--no-cpu-baseline", "--no-host-inclusive", "--check-reads", "3000")
+    plain = run_bench(*args, "--dump-outputs", str(tmp_path / "plain"))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in plain, k
+    assert plain["unit"] == "reads/s" and plain["higher_is_better"] is True and plain["steps"] == 3 and plain["warmup"] == 1
+    assert plain["full"] is False and not {"roofline", "kernel_ms", "check", "cpu_baseline", "value_host_inclusive"} & set(plain)
+    assert abs(plain["value"] * plain["ms_per_step"] / 1e3 - 100000) < 1e-6 * 100000
+    full = run_bench(*args, "--full", "--dump-outputs", str(tmp_path / "full"))
+    assert full["full"] is True and full["check"]["from_timed_launch"] and full["check"]["rows_equal"]
+    names = ("sample_reads", "rows_per_read", "rows_read", "rows_ref", "rows_dist")
+    got = {n: np.load(tmp_path / "plain" / f"{n}.npy") for n in names}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert sum(os.path.getsize(tmp_path / "plain" / f"{n}.npy") for n in names) <= 64 << 20
+    assert len(got["sample_reads"]) == 32768 and np.all(np.diff(got["sample_reads"]) > 0) and got["sample_reads"][-1] < 100000
+    assert got["rows_per_read"].sum() == len(got["rows_read"]) == len(got["rows_ref"]) == len(got["rows_dist"]) > 0
+    assert np.array_equal(np.repeat(got["sample_reads"], got["rows_per_read"].astype(np.int64)), got["rows_read"])
+    assert np.all(got["rows_ref"] >= 0) and np.all(np.isfinite(got["rows_dist"]))
+    for n in names:
+        assert np.array_equal(got[n], np.load(tmp_path / "full" / f"{n}.npy")), n

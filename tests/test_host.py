@@ -223,7 +223,8 @@ def test_steady_batches_of_the_pool_reader_are_one_chunk_each(capi, tmp_path):
     that fits its job): a chunk of 2 * min_bases bytes holds about 0.94 * min_bases bases, which is a batch -- asking for all of
     min_bases took a second chunk for every steady batch, appended by copy (37,736-read batches for a request of 20,000 reads)."""
     rng = np.random.default_rng(3)
-    n, L = 200_000, 150
+    # (the pool's short first chunks take ~142,000 reads at its most threads, 12: the file must reach steady chunks beyond them)
+    n, L = 400_000, 150
     seqs = rng.choice(np.frombuffer(b"ACGT", dtype=np.uint8), size=(n, L))
     with open(tmp_path / "r.fq", "wb") as f:
         for i in range(n):

@@ -1,13 +1,13 @@
 """Pins the oracle against REFERENCE outputs: the committed *_ref.json fixtures were
 produced by the reference's own sources (oracle/ref_drivers/ref_shim.cpp), and, when
-oracle/_ref/libkrepp_ref.so is present, the same calls are repeated live."""
+oracle/_ref/libkrepp_ref.so is present, the calls behind llh_live_ref.json are repeated live."""
 import json
 import os
 
 import numpy as np
-import pytest
 
 from conftest import GOLDEN
+from helpers import llh_live_cases
 
 
 def test_llh_matches_reference_fixture(po):
@@ -22,20 +22,17 @@ def test_llh_matches_reference_fixture(po):
 
 
 def test_llh_matches_reference_live(po):
+    """300 seeded random problems against the reference's own values: called live when oracle/_ref is built, and as
+    recorded from the same calls in llh_live_ref.json (which the live values must equal) in any case."""
     ref = po.ref()
-    if ref is None:
-        pytest.skip("oracle/_ref not built (reference tree absent)")
-    rng = np.random.default_rng(5)
-    for _ in range(300):
-        k = int(rng.integers(19, 32))
-        h = int(rng.integers(max(3, k - 16), 16))
-        th = int(rng.integers(0, 7))
-        hist = np.floor(rng.random(th + 1) * 40)
-        uc = float(rng.integers(0, 120))
-        rho = float(rng.uniform(0.01, 1.0))
-        d = float(10 ** rng.uniform(-9, np.log10(0.5)))
-        hc = np.ascontiguousarray(hist)
-        assert po.llh(k, h, th, hist, uc, rho, d) == ref.ref_llh(k, h, th, hc.ctypes.data, uc, rho, d)
+    want = json.load(open(os.path.join(GOLDEN, "llh_live_ref.json")))
+    cases = llh_live_cases()
+    assert len(want) == len(cases) == 300
+    for (k, h, th, hist, uc, rho, d), w in zip(cases, want):
+        if ref is not None:
+            hc = np.ascontiguousarray(hist)
+            assert float(ref.ref_llh(k, h, th, hc.ctypes.data, uc, rho, d)).hex() == w
+        assert po.llh(k, h, th, hist, uc, rho, d) == float.fromhex(w)
 
 
 def test_murmur_matches_reference(po):
