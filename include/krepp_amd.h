@@ -361,6 +361,10 @@ typedef struct kr_fastx_batch {
   uint32_t more;               /* 0 once the input is exhausted                    */
 } kr_fastx_batch;
 KR_API int kr_fastx_open(const char* path, kr_fastx** out);
+/* The sequential reader (kseq's grammar, no thread pool) on a plain file from byte `offset`, which must be a record start: one byte
+ * past the end of a record, or 0.  kseq's state there is "look for the next '>' / '@'", so the records read from `offset` are the
+ * tail of the records read from the start of the file, byte for byte.  gzip input: KR_ERR_UNSUPPORTED (no byte offsets into it). */
+KR_API int kr_fastx_open_at(const char* path, uint64_t offset, kr_fastx** out);
 KR_API int kr_fastx_next(kr_fastx*, uint64_t min_bases, kr_fastx_batch* out);
 /* The batch kr_fastx_next just returned changes hands (what QSeq gives IBatch by swap, src/query.cpp:32-33): the kr_fastx_batch's
  * pointers stay valid, nothing is copied, until kr_fastx_release hands the buffers back for reuse -- from any thread, before
@@ -406,6 +410,48 @@ KR_API void kr_free(void*);
 /* Page-locked host memory for read batches (KR_BASES_PINNED): what a reader fills instead of a std::string. */
 KR_API void* kr_host_alloc(uint64_t bytes);
 KR_API void kr_host_free(void*);
+
+/* FASTQ records found on the device (csrc/kr_dev_fastq.inc): a batch given as the raw bytes of a plain FASTQ file.  The chunk is
+ * copied to HBM, its newlines are found and every record r (lines 4r .. 4r+3) is checked; the accepted prefix's bases, offsets and
+ * ids are written where kr_batch_submit / kr_batch_submit_text put them, and the batch runs as they run it.  A record is accepted
+ * ("device-clean") iff the host reader's four-line fast path takes it AND its quality line is exactly as long as its sequence line:
+ * '@' header, sequence bytes 33..126 other than '>' '+' '@', a line starting with '+', quality bytes 33..127.  Its name runs from
+ * after the '@' to the first C-locale isspace byte.  The accepted records are then those the sequential reader gives for the same
+ * bytes, with the same names and sequences; the prefix ends at the first record that is not accepted (`status`):
+ *   KR_FASTQ_NOT_CLEAN    anything else (FASTA, CRLF, wrapped lines, odd quality ...): the host reader continues at `consumed`
+ *   KR_FASTQ_INCOMPLETE   bytes behind the last complete record: a record cut by the end of the chunk, or a last line without '\n'
+ *   KR_FASTQ_LONG         more k-mer positions than the stream tiles a sequence from (KR_TILE_MIN_POS): the host path tiles it
+ *   KR_FASTQ_CAPACITY     past max_reads, max_bases or the id buffer: submit again from `consumed` (nreads 0: the record never fits)
+ *   kr_stream_fastq_enable  once per stream: device buffers for chunks of up to max_raw_bytes (< 4 GB: positions are 32-bit)
+ *   kr_batch_submit_fastq   `raw` is page-locked (kr_host_alloc), starts at a record start and stays valid until the batch has been
+ *                           waited for.  Copies it, runs the parse kernels on the stream (beside the previous batch's kernels of other
+ *                           streams), waits for the 64-byte summary only, and with nreads > 0 queues the batch like kr_batch_submit
+ *                           with KR_BASES_DEVICE -- or, on a stream with text enabled and no tap flags, like kr_batch_submit_text with
+ *                           id_sep 0 (the ids are already on the device).  nreads == 0: nothing is queued.  at_eof: `raw` ends where
+ *                           the file does (recorded in the summary; INCOMPLETE there leaves the file's last record to the host reader)
+ *   kr_batch_fastq_names    the accepted records' names as (position in `raw`, length), for the host formatters (kr_format_dist, the
+ *                           KR_ERR_UNSUPPORTED path of kr_batch_collect_text); valid until the next submit on the stream */
+#define KR_FASTQ_OK 0u
+#define KR_FASTQ_NOT_CLEAN 1u
+#define KR_FASTQ_INCOMPLETE 2u
+#define KR_FASTQ_LONG 3u
+#define KR_FASTQ_CAPACITY 4u
+typedef struct kr_fastq_parse { /* 64 bytes, written by the device */
+  uint64_t consumed;  /* the byte just past the last accepted record (0: none)                */
+  uint64_t nbases;    /* bases of the accepted records                                        */
+  uint64_t id_bytes;  /* name bytes of the accepted records (0 without text)                  */
+  uint64_t newlines;  /* '\n' bytes in the chunk                                              */
+  uint32_t nreads;    /* accepted records                                                     */
+  uint32_t status;    /* KR_FASTQ_*                                                           */
+  uint32_t rejected;  /* index of the first record not accepted (== nreads)                   */
+  uint32_t at_eof;    /* the caller's at_eof                                                  */
+  uint32_t reserved[4];
+} kr_fastq_parse;
+KR_API int kr_stream_fastq_enable(kr_stream*, uint64_t max_raw_bytes);
+KR_API int kr_batch_submit_fastq(kr_stream*, const uint8_t* raw, uint64_t nbytes, uint32_t flags, uint32_t at_eof, kr_fastq_parse* out);
+KR_API int kr_batch_fastq_names(kr_stream*, const uint64_t** name_pos, const uint32_t** name_len);
+/* tests: the last kr_batch_submit_fastq's accepted bases [nbases] and offsets [nreads + 1] as the device wrote them */
+KR_API int kr_debug_fastq_batch(kr_stream*, uint8_t* bases, uint64_t* offsets);
 
 /* ------------------------------------------------------------------------- */
 /* `krepp place`: IBatch::place_sequences / report_placement (src/query.cpp:198-333), */

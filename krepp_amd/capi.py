@@ -71,6 +71,15 @@ class KrFastxBatch(C.Structure):
                 ("nreads", C.c_uint32), ("more", C.c_uint32)]
 
 
+KR_FASTQ_OK, KR_FASTQ_NOT_CLEAN, KR_FASTQ_INCOMPLETE, KR_FASTQ_LONG, KR_FASTQ_CAPACITY = 0, 1, 2, 3, 4
+
+
+class KrFastqParse(C.Structure):
+    _fields_ = [("consumed", C.c_uint64), ("nbases", C.c_uint64), ("id_bytes", C.c_uint64), ("newlines", C.c_uint64),
+                ("nreads", C.c_uint32), ("status", C.c_uint32), ("rejected", C.c_uint32), ("at_eof", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
+
+
 class KrMinimizerResult(C.Structure):
     _fields_ = [("keys", u64p), ("nkeys", C.c_uint64), ("n1", C.c_double), ("n2", C.c_double)]
 
@@ -87,11 +96,12 @@ EXPORTS = [
     "kr_host_index_node_label", "kr_host_index_node_parent", "kr_host_index_node_blen",
     "kr_index_upload", "kr_index_free", "kr_index_export", "kr_index_import", "kr_index_device_bytes", "kr_index_slot_words", "kr_index_slot_format", "kr_index_broadcast",
     "kr_params_default", "kr_stream_create", "kr_stream_destroy", "kr_batch_submit", "kr_batch_wait",
-    "kr_batch_collect", "kr_batch_collect_device", "kr_stream_text_enable", "kr_batch_submit_text", "kr_batch_collect_text", "kr_batch_hits", "kr_batch_readtaps",
+    "kr_batch_collect", "kr_batch_collect_device", "kr_stream_text_enable", "kr_batch_submit_text", "kr_batch_collect_text",
+    "kr_stream_fastq_enable", "kr_batch_submit_fastq", "kr_batch_fastq_names", "kr_debug_fastq_batch", "kr_batch_hits", "kr_batch_readtaps",
     "kr_debug_front_end", "kr_debug_stream_move", "kr_debug_stream_addrs", "kr_debug_item_placement", "kr_debug_brent", "kr_debug_colour_classes", "kr_llh_batch", "kr_llh_eval_indexed", "kr_batch_timing",
     "kr_place_tree_create", "kr_place_tree_create_lineage", "kr_place_tree_nnodes", "kr_place_summary_add",
     "kr_place_summary_text", "kr_place_tree_free", "kr_place_tree_kinds", "kr_place_batch", "kr_place_stream", "kr_place_frame", "kr_place_counters",
-    "kr_debug_last_d2h_bytes", "kr_debug_place_fixed5", "kr_place_text_counters", "kr_fastx_open", "kr_fastx_next", "kr_fastx_detach", "kr_fastx_release", "kr_fastx_close", "kr_fastx_parallel_chunks", "kr_fastx_pgz_stats", "kr_format_dist", "kr_debug_fixed5", "kr_free", "kr_host_alloc", "kr_host_free",
+    "kr_debug_last_d2h_bytes", "kr_debug_place_fixed5", "kr_place_text_counters", "kr_fastx_open", "kr_fastx_open_at", "kr_fastx_next", "kr_fastx_detach", "kr_fastx_release", "kr_fastx_close", "kr_fastx_parallel_chunks", "kr_fastx_pgz_stats", "kr_format_dist", "kr_debug_fixed5", "kr_free", "kr_host_alloc", "kr_host_free",
     "kr_build_index", "kr_minimizers_cpu", "kr_minimizers_device", "kr_minimizers_free", "kr_last_error", "kr_version",
 ]
 
@@ -182,6 +192,11 @@ def load():
     lib.kr_place_counters.argtypes = [u64p, u64p, u64p]
     lib.kr_place_counters.restype = None
     lib.kr_fastx_open.argtypes = [C.c_char_p, C.POINTER(vp)]
+    lib.kr_fastx_open_at.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(vp)]
+    lib.kr_stream_fastq_enable.argtypes = [vp, C.c_uint64]
+    lib.kr_batch_submit_fastq.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(KrFastqParse)]
+    lib.kr_batch_fastq_names.argtypes = [vp, C.POINTER(u64p), C.POINTER(u32p)]
+    lib.kr_debug_fastq_batch.argtypes = [vp, vp, vp]
     lib.kr_fastx_next.argtypes = [vp, C.c_uint64, C.POINTER(KrFastxBatch)]
     lib.kr_fastx_detach.argtypes = [vp, C.POINTER(vp)]
     lib.kr_fastx_release.argtypes = [vp, vp]
@@ -518,6 +533,7 @@ class Stream:
     def text_enable(self, host_index, max_text_bytes, max_id_bytes):
         """kr_stream_text_enable: this stream formats its rows-only batches on the device (csrc/kr_dev_text.inc)"""
         check(self.lib.kr_stream_text_enable(self.h, host_index.h, int(max_text_bytes), int(max_id_bytes)))
+        self._text_on = True
 
     def submit_text(self, bases, offsets, names, flags=0, sep=1):
         """kr_batch_submit_text with the reads' ids packed back to back, `sep` NUL bytes behind each"""
@@ -532,6 +548,48 @@ class Stream:
         self._keep = (bases, offsets, ids, id_off)
         self._flags = flags | KR_ROWS_ONLY
         check(self.lib.kr_batch_submit_text(self.h, bases.ctypes.data, offsets.ctypes.data, len(offsets) - 1, flags, ids.ctypes.data, id_off.ctypes.data, sep))
+
+    def fastq_enable(self, max_raw_bytes):
+        """kr_stream_fastq_enable: this stream can be given batches as raw FASTQ bytes (csrc/kr_dev_fastq.inc)"""
+        check(self.lib.kr_stream_fastq_enable(self.h, int(max_raw_bytes)))
+
+    def submit_fastq(self, raw, flags=0, at_eof=1):
+        """kr_batch_submit_fastq on a page-locked copy of `raw` (kept until the next submit): the summary as a dict"""
+        raw = bytes(raw)
+        n = len(raw)
+        if getattr(self, "_pinned_cap", 0) < max(n, 1):
+            if getattr(self, "_pinned", None):
+                self.lib.kr_host_free(self._pinned)
+            self._pinned = self.lib.kr_host_alloc(max(n, 1))
+            if not self._pinned:
+                raise MemoryError("kr_host_alloc failed")
+            self._pinned_cap = max(n, 1)
+        C.memmove(self._pinned, raw, n)
+        self._raw = raw
+        out = KrFastqParse()
+        check(self.lib.kr_batch_submit_fastq(self.h, self._pinned, n, flags, at_eof, C.byref(out)))
+        self._fq_nreads = out.nreads
+        text = getattr(self, "_text_on", False) and not (flags & (KR_TAP_ACCS | KR_TAP_HITS))  # as kr_batch_submit_fastq decides
+        self._flags = flags | KR_BASES_DEVICE | (KR_ROWS_ONLY if text else 0)
+        return {f: getattr(out, f) for f in ("consumed", "nbases", "id_bytes", "newlines", "nreads", "status", "rejected", "at_eof")}
+
+    def fastq_names(self):
+        """kr_batch_fastq_names: the accepted records' names, cut out of the bytes given to submit_fastq"""
+        pos, ln = u64p(), u32p()
+        check(self.lib.kr_batch_fastq_names(self.h, C.byref(pos), C.byref(ln)))
+        n = self._fq_nreads
+        if n == 0:
+            return []
+        p = np.ctypeslib.as_array(pos, shape=(n,))
+        q = np.ctypeslib.as_array(ln, shape=(n,))
+        return [self._raw[int(a):int(a) + int(b)].decode("latin-1") for a, b in zip(p, q)]
+
+    def fastq_batch(self, summary):
+        """(tests) the accepted records' sequences as the record finder wrote them (kr_debug_fastq_batch)"""
+        offs = np.zeros(summary["nreads"] + 1, np.uint64)
+        bases = np.zeros(max(1, summary["nbases"]), np.uint8)
+        check(self.lib.kr_debug_fastq_batch(self.h, bases.ctypes.data, offs.ctypes.data))
+        return [bases[int(offs[i]):int(offs[i + 1])].tobytes() for i in range(summary["nreads"])]
 
     def collect_text(self):
         """kr_batch_collect_text: the batch's report rows as the bytes the device wrote"""
@@ -553,6 +611,9 @@ class Stream:
         if self.h:
             self.lib.kr_stream_destroy(self.h)
             self.h = C.c_void_p()
+        if getattr(self, "_pinned", None):
+            self.lib.kr_host_free(self._pinned)
+            self._pinned, self._pinned_cap = None, 0
 
     def __del__(self):
         try:
@@ -579,15 +640,19 @@ def colour_classes(pse, node_kind):
     return cls, out, lists[: nl.value]
 
 
-def read_fastx(path, min_bases=76800, stats=None, detach=0):
+def read_fastx(path, min_bases=76800, stats=None, detach=0, offset=None):
     """All records of a FASTA/FASTQ(.gz) file via the library's reader: (names, bases, offsets).
     detach = K > 0: every batch is taken over (kr_fastx_detach), read only when K further batches have been parsed, then handed
-    back (kr_fastx_release) -- the way the CLI's workers hold batches in flight."""
+    back (kr_fastx_release) -- the way the CLI's workers hold batches in flight.
+    offset: the sequential reader from that record start of a plain file on (kr_fastx_open_at)."""
     lib = load()
     lib.kr_fastx_parallel_chunks.restype = C.c_uint64
     lib.kr_fastx_parallel_chunks.argtypes = [C.c_void_p]
     h = C.c_void_p()
-    check(lib.kr_fastx_open(os.fsencode(str(path)), C.byref(h)))
+    if offset is None:
+        check(lib.kr_fastx_open(os.fsencode(str(path)), C.byref(h)))
+    else:
+        check(lib.kr_fastx_open_at(os.fsencode(str(path)), int(offset), C.byref(h)))
     names, chunks, lens = [], [], []
 
     def take(b):

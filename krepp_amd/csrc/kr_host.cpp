@@ -1478,6 +1478,43 @@ int kr_fastx_open(const char* path, kr_fastx** out)
   return KR_OK;
 }
 
+// The sequential reader from a record start of a plain file (the host's side of kr_batch_submit_fastq: where the device's accepted
+// prefix ends, this reader takes over).  kseq's state one byte past a record's end is "look for the next marker" (last_char = 0),
+// which is what a fresh reader at that byte starts in.
+int kr_fastx_open_at(const char* path, uint64_t offset, kr_fastx** out)
+{
+  kr::clear_error();
+  if (!path || !out) return kr::fail(KR_ERR_ARG, "kr_fastx_open_at: null argument");
+  struct stat sb;
+  if (stat(path, &sb) != 0) return kr::fail(KR_ERR_IO, std::string("Failed to open the file at ") + path);
+  if (!S_ISREG(sb.st_mode)) return kr::fail(KR_ERR_UNSUPPORTED, std::string("kr_fastx_open_at: not a regular file: ") + path);
+  if (offset > (uint64_t)sb.st_size) return kr::fail(KR_ERR_ARG, "kr_fastx_open_at: offset past the end of the file");
+  int fd = open(path, O_RDONLY);
+  if (fd < 0) return kr::fail(KR_ERR_IO, std::string("Failed to open the file at ") + path);
+  unsigned char magic[2] = {0, 0};
+  const bool gz = pread(fd, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
+  if (gz) {
+    close(fd);
+    return kr::fail(KR_ERR_UNSUPPORTED, std::string("kr_fastx_open_at: gzip input has no record offsets: ") + path);
+  }
+  if (lseek(fd, (off_t)offset, SEEK_SET) < 0) {
+    close(fd);
+    return kr::fail(KR_ERR_IO, std::string("kr_fastx_open_at: seek failed in ") + path);
+  }
+  gzFile f = gzdopen(fd, "rb"); // (plain bytes: zlib reads them through, from the descriptor's position)
+  if (!f) {
+    close(fd);
+    return kr::fail(KR_ERR_IO, std::string("Failed to open the file at ") + path);
+  }
+  gzbuffer(f, 1 << 20);
+  kr_fastx* r = new kr_fastx();
+  r->f = f;
+  r->path = path;
+  r->buf.resize(4 << 20);
+  *out = r;
+  return KR_OK;
+}
+
 // QSeq::read_next_batch (src/rqseq.cpp:180-197): keep reading until the batch holds
 // at least `min_bases` bases (reference: RBATCH_SIZE*DSEQ_LEN = 76,800) or input ends.
 int kr_fastx_next(kr_fastx* r, uint64_t min_bases, kr_fastx_batch* out)

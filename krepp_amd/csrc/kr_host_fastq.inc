@@ -1,0 +1,142 @@
+// kr_host_fastq.inc -- part of kr_device.hip (host side): kr_stream_fastq_enable, kr_batch_submit_fastq, kr_batch_fastq_names.
+// A batch given as the raw bytes of a plain FASTQ file; the records are found by the kernels of kr_dev_fastq.inc, then the batch
+// runs on the submit_batch path with its bases already in HBM.
+
+extern "C" {
+
+int kr_stream_fastq_enable(kr_stream* s, uint64_t max_raw_bytes)
+{
+  kr::clear_error();
+  if (!s || max_raw_bytes == 0) return kr::fail(KR_ERR_ARG, "kr_stream_fastq_enable: bad argument");
+  if (max_raw_bytes >= (1ull << 32)) return kr::fail(KR_ERR_ARG, "kr_stream_fastq_enable: a chunk must stay below 4 GB (positions are 32-bit)");
+  if (s->fq.on) return kr::fail(KR_ERR_STATE, "kr_stream_fastq_enable: already enabled");
+  if (s->max_reads > (1u << 30)) return kr::fail(KR_ERR_ARG, "kr_stream_fastq_enable: more than 2^30 reads per batch (the newline list is indexed by 32 bits)");
+  HIP_TRY(hipSetDevice(s->ix->device));
+  kr_stream::Fastq& f = s->fq;
+  const uint64_t raw_pad = ((max_raw_bytes + 15) & ~15ull) + 16; // (16-byte loads of the last bytes stay inside)
+  const uint64_t ntiles = (max_raw_bytes + kFqTile - 1) / kFqTile + 1, nblk = (uint64_t)s->max_reads / kFqRecBlock + 2;
+  int rc = 0;
+  if ((rc = salloc(s, &f.d_raw, raw_pad)) || (rc = salloc(s, &f.d_tile_nl, ntiles)) || (rc = salloc(s, &f.d_nl, 4ull * s->max_reads)) ||
+      (rc = salloc(s, &f.d_slen, (uint64_t)s->max_reads)) || (rc = salloc(s, &f.d_npos, (uint64_t)s->max_reads)) ||
+      (rc = salloc(s, &f.d_nlen, (uint64_t)s->max_reads)) || (rc = salloc(s, &f.d_id_off, (uint64_t)s->max_reads + 1)) ||
+      (rc = salloc(s, &f.d_bsum_b, nblk)) || (rc = salloc(s, &f.d_bsum_n, nblk)) || (rc = salloc(s, &f.d_ctl, 4)) ||
+      (rc = salloc(s, &f.d_sum, 1)) || (rc = halloc(s, &f.h_sum, 1)))
+    return rc;
+  f.raw_cap = max_raw_bytes;
+  f.on = true;
+  return KR_OK;
+}
+
+int kr_batch_submit_fastq(kr_stream* s, const uint8_t* raw, uint64_t nbytes, uint32_t flags, uint32_t at_eof, kr_fastq_parse* out)
+{
+  kr::clear_error();
+  if (!s || !raw || !out) return kr::fail(KR_ERR_ARG, "kr_batch_submit_fastq: null argument");
+  if (nbytes >= (1ull << 32)) return kr::fail(KR_ERR_ARG, "kr_batch_submit_fastq: a chunk must stay below 4 GB (positions are 32-bit)");
+  if (!s->fq.on) return kr::fail(KR_ERR_STATE, "kr_batch_submit_fastq: kr_stream_fastq_enable first");
+  if (nbytes > s->fq.raw_cap) return kr::fail(KR_ERR_ARG, "kr_batch_submit_fastq: more bytes than kr_stream_fastq_enable sized the stream for");
+  if (flags & (KR_BASES_DEVICE | KR_BASES_PINNED)) return kr::fail(KR_ERR_ARG, "kr_batch_submit_fastq: the bases are the record finder's: no KR_BASES_* flags");
+  memset(out, 0, sizeof(*out));
+  out->at_eof = at_eof ? 1u : 0u;
+  kr_stream::Fastq& f = s->fq;
+  if (nbytes == 0) {
+    f.parsed = true, f.nreads = 0, f.have_names = false;
+    return KR_OK;
+  }
+  const bool text = s->text.on && !(flags & (KR_TAP_ACCS | KR_TAP_HITS));
+  HIP_TRY(hipSetDevice(s->ix->device));
+  (void)hipGetLastError();
+  if (s->submitted && !s->waited) // d_bases, d_offsets and the ids belong to the batch in flight
+    for (uint32_t l = 0; l < s->nlanes; ++l) HIP_TRY(hipStreamSynchronize(s->lanes[l].stream));
+  f.parsed = false, f.have_names = false;
+  hipStream_t st = s->lanes[0].stream; // (the lane of a device-input batch: the parse and the batch are ordered on it)
+  FqIO io;
+  io.raw = f.d_raw, io.nbytes = nbytes;
+  io.tile_nl = f.d_tile_nl, io.nl = f.d_nl, io.nl_cap = 4u * s->max_reads;
+  io.rec_slen = f.d_slen, io.rec_npos = f.d_npos, io.rec_nlen = f.d_nlen;
+  io.bsum_b = f.d_bsum_b, io.bsum_n = f.d_bsum_n, io.ctl = f.d_ctl;
+  io.bases = s->d_bases, io.offsets = s->d_offsets;
+  io.ids = text ? s->text.d_ids : nullptr;
+  io.id_off = text ? s->text.d_id_off : f.d_id_off;
+  io.max_reads = s->max_reads, io.max_bases = s->max_bases, io.id_cap = text ? s->text.id_cap : ~0ull;
+  io.k = s->ix->dix.k, io.tile_min_pos = s->tile_min_pos;
+  io.sum = f.d_sum;
+  // queued before the index's kernel chain is waited for (launch_lane): the copy and the parse overlap other streams' batches
+  HIP_TRY(hipMemcpyAsync(f.d_raw, raw, nbytes, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(f.d_ctl, 0xFF, 32, st));
+  const uint32_t ntiles = (uint32_t)((nbytes + kFqTile - 1) / kFqTile);
+  const uint32_t rgrid = std::min<uint32_t>((s->max_reads + 3) / 4, 8192u), bgrid = std::min<uint32_t>(s->max_reads / kFqRecBlock + 1, 4096u);
+  hipLaunchKernelGGL(kr_fq_nl_count_kernel, dim3(std::min<uint32_t>(ntiles, 16384u)), dim3(256), 0, st, io);
+  hipLaunchKernelGGL(kr_fq_nl_scan_kernel, dim3(1), dim3(1024), 0, st, io);
+  hipLaunchKernelGGL(kr_fq_nl_write_kernel, dim3(std::min<uint32_t>(ntiles, 16384u)), dim3(256), 0, st, io);
+  hipLaunchKernelGGL(kr_fq_rec_kernel, dim3(rgrid), dim3(256), 0, st, io);
+  hipLaunchKernelGGL(kr_fq_bsum_kernel, dim3(bgrid), dim3(256), 0, st, io);
+  hipLaunchKernelGGL(kr_fq_bscan_kernel, dim3(1), dim3(1024), 0, st, io);
+  hipLaunchKernelGGL(kr_fq_off_kernel, dim3(bgrid), dim3(256), 0, st, io);
+  hipLaunchKernelGGL(kr_fq_copy_kernel, dim3(rgrid), dim3(256), 0, st, io);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(f.h_sum, f.d_sum, sizeof(kr_fastq_parse), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  *out = *f.h_sum;
+  out->at_eof = at_eof ? 1u : 0u;
+  f.nreads = out->nreads;
+  f.parsed = true;
+  if (out->nreads == 0) return KR_OK;
+  kr_stream::Text& t = s->text;
+  int rc;
+  if (text) {
+    t.id_bytes = out->id_bytes, t.id_sep = 0;
+    t.req = true, t.ids_on_device = true;
+    rc = submit_batch(s, s->d_bases, s->d_offsets, out->nreads, flags | KR_ROWS_ONLY | KR_BASES_DEVICE);
+    if (rc) t.req = false;
+  } else {
+    t.req = false;
+    rc = submit_batch(s, s->d_bases, s->d_offsets, out->nreads, flags | KR_BASES_DEVICE);
+  }
+  return rc;
+}
+
+int kr_batch_fastq_names(kr_stream* s, const uint64_t** name_pos, const uint32_t** name_len)
+{
+  kr::clear_error();
+  if (!s || !name_pos || !name_len) return kr::fail(KR_ERR_ARG, "kr_batch_fastq_names: null argument");
+  if (!s->fq.on || !s->fq.parsed) return kr::fail(KR_ERR_STATE, "kr_batch_fastq_names: the last submit was not kr_batch_submit_fastq");
+  kr_stream::Fastq& f = s->fq;
+  const uint32_t n = f.nreads;
+  if (!f.have_names && n) {
+    HIP_TRY(hipSetDevice(s->ix->device));
+    if (!f.h_npos) { // page-locked mirrors, made on first use
+      int rc = 0;
+      if ((rc = halloc(s, &f.h_npos, (uint64_t)s->max_reads)) || (rc = halloc(s, &f.h_nlen, (uint64_t)s->max_reads))) return rc;
+    }
+    hipStream_t st = s->lanes[0].stream;
+    HIP_TRY(hipMemcpyAsync(f.h_npos, f.d_npos, (uint64_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(f.h_nlen, f.d_nlen, (uint64_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    f.name_pos.assign(f.h_npos, f.h_npos + n);
+  }
+  if (!n) f.name_pos.clear();
+  f.have_names = true;
+  *name_pos = f.name_pos.data();
+  *name_len = f.h_nlen;
+  return KR_OK;
+}
+
+// (tests) the bases and offsets the record finder wrote for the last kr_batch_submit_fastq: offsets [nreads + 1], bases [nbases]
+int kr_debug_fastq_batch(kr_stream* s, uint8_t* bases, uint64_t* offsets)
+{
+  kr::clear_error();
+  if (!s || !bases || !offsets) return kr::fail(KR_ERR_ARG, "kr_debug_fastq_batch: null argument");
+  if (!s->fq.on || !s->fq.parsed) return kr::fail(KR_ERR_STATE, "kr_debug_fastq_batch: the last submit was not kr_batch_submit_fastq");
+  const uint32_t n = s->fq.nreads;
+  offsets[0] = 0;
+  if (!n) return KR_OK;
+  HIP_TRY(hipSetDevice(s->ix->device));
+  hipStream_t st = s->lanes[0].stream;
+  HIP_TRY(hipMemcpyAsync(offsets, s->d_offsets, ((uint64_t)n + 1) * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (offsets[n]) HIP_TRY(hipMemcpyAsync(bases, s->d_bases, offsets[n], hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return KR_OK;
+}
+
+} // extern "C"

@@ -149,7 +149,24 @@ struct kr_stream {
     uint64_t *d_bsum = nullptr, *d_total = nullptr, *h_total = nullptr;
     char *d_text = nullptr, *h_text = nullptr;
     uint64_t text_cap = 0, id_bytes = 0, h_text_cap = 0; // (h_text: made by the first batch that needs it, as large as that batch's text asks)
+    bool ids_on_device = false; // the batch's ids were written into d_ids / d_id_off by the record finder (kr_batch_submit_fastq)
   } text;
+  // FASTQ records found on the device (kr_dev_fastq.inc; kr_stream_fastq_enable)
+  struct Fastq {
+    bool on = false;
+    uint64_t raw_cap = 0;             // bytes of a chunk
+    uint8_t* d_raw = nullptr;         // [raw_cap rounded up to 16, + 16]
+    uint32_t *d_tile_nl = nullptr, *d_nl = nullptr;
+    uint32_t *d_slen = nullptr, *d_npos = nullptr, *d_nlen = nullptr, *d_id_off = nullptr;
+    uint64_t *d_bsum_b = nullptr, *d_bsum_n = nullptr;
+    unsigned long long* d_ctl = nullptr;
+    kr_fastq_parse *d_sum = nullptr, *h_sum = nullptr;
+    bool parsed = false;              // the last submit on the stream was kr_batch_submit_fastq: its names can be asked for
+    bool have_names = false;          // ... and they are in name_pos / h_nlen
+    uint32_t nreads = 0;
+    uint32_t *h_npos = nullptr, *h_nlen = nullptr;
+    std::vector<uint64_t> name_pos;
+  } fq;
   const uint8_t* sub_bases = nullptr; // the arguments of the submit in flight (host buffers stay valid until wait / collect returns)
   const uint64_t* sub_offsets = nullptr;
   // state
@@ -772,7 +789,7 @@ void kr_stream_destroy(kr_stream* s)
 static int submit_batch(kr_stream* s, const uint8_t* bases, const uint64_t* offsets, uint32_t nreads, uint32_t flags);
 int kr_batch_submit(kr_stream* s, const uint8_t* bases, const uint64_t* offsets, uint32_t nreads, uint32_t flags)
 {
-  if (s) s->text.req = false;
+  if (s) s->text.req = false, s->fq.parsed = false;
   return submit_batch(s, bases, offsets, nreads, flags);
 }
 
@@ -844,7 +861,8 @@ int kr_batch_submit_text(kr_stream* s, const uint8_t* bases, const uint64_t* off
     t.h_id_off[r] = id_off[r] - id_off[0];
   }
   t.id_bytes = nb, t.id_sep = id_sep;
-  t.req = true;
+  t.req = true, t.ids_on_device = false;
+  s->fq.parsed = false;
   const int rc = submit_batch(s, bases, offsets, nreads, flags | KR_ROWS_ONLY);
   if (rc) t.req = false;
   return rc;
@@ -975,7 +993,7 @@ static int submit_batch(kr_stream* s, const uint8_t* bases, const uint64_t* offs
       L.in.bases = s->d_bases;
       L.in.offsets = s->d_offsets + r0 + l;
     }
-    if (s->text.req && !s->tiles.active) { // the reads' ids (staged in page-locked memory by kr_batch_submit_text)
+    if (s->text.req && !s->tiles.active && !s->text.ids_on_device) { // the reads' ids (staged in page-locked memory by kr_batch_submit_text)
       HIP_TRY(hipMemcpyAsync(s->text.d_ids, s->text.h_ids, s->text.id_bytes, hipMemcpyHostToDevice, st));
       HIP_TRY(hipMemcpyAsync(s->text.d_id_off, s->text.h_id_off, ((uint64_t)nreads + 1) * 4, hipMemcpyHostToDevice, st));
     }

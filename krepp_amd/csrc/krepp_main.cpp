@@ -16,6 +16,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <fcntl.h>
 #include <ctime>
 #include <deque>
 #include <malloc.h>
@@ -53,7 +54,7 @@ static const std::map<std::string, std::string> kAlias = {
   {"-i", "--index-dir"}, {"-q", "--query"}, {"-o", "--output-path"}, {"-t", "--nwk-file"}, {"-k", "--kmer-len"},
   {"-w", "--win-len"}, {"-h", "--num-positions"}, {"-m", "--modulo-lsh"}, {"-r", "--residue-lsh"}, {"-l", "--lineage-file"},
 };
-static const char* kFlags[] = {"--multi", "--filter", "--summarize", "--frac", "--verbose", "--gpu-minimizers", "--tabular"};
+static const char* kFlags[] = {"--multi", "--filter", "--summarize", "--frac", "--verbose", "--gpu-minimizers", "--tabular", "--gpu-parse"};
 
 // options as in the reference's CLI (src/krepp.cpp:516-675); the texts are this build's own
 static void print_help(const std::string& sub)
@@ -80,7 +81,8 @@ static void print_help(const std::string& sub)
   printf("krepp (MI355X build, mirrors krepp v0.8.3): dist | place | seek | index | sketch\n");
   if (sub.empty() || sub == "dist")
     printf("\nkrepp dist -i DIR -q READS: distances of every read to the references it matches\n%s%s"
-           "      --filter / --no-filter keep only references not significantly worse than the closest [no-filter]\n",
+           "      --filter / --no-filter keep only references not significantly worse than the closest [no-filter]\n"
+           "      --gpu-parse            FASTQ records found on the GPU (identical output; plain files, others keep the host reader)\n",
            query_opts, index_query_opts);
   if (sub.empty() || sub == "place")
     printf("\nkrepp place -i DIR -q READS: placements on the backbone tree (jplace)\n%s%s"
@@ -156,6 +158,10 @@ struct Job {
   std::vector<kr_placement> pls; // place --summarize: the placements, `read` = global read number
   uint64_t first_read = 0;
   bool done = false;
+  // --gpu-parse: a chunk of the file's raw bytes (page-locked), cut at a guessed record start; its records are found on the device
+  uint8_t* raw = nullptr;
+  uint64_t raw_len = 0, raw_off = 0;
+  bool at_eof = false;
 };
 
 // `dist` and `place` share everything up to the per-batch back end (src/krepp.cpp:347-394, 434-504)
@@ -318,6 +324,32 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
   int workers_ready = 0;
   std::vector<kr_stream*> streams_to_free;
   kr_fastx* fx = nullptr; // (opened before the workers start; they hand batches back to it)
+  // --gpu-parse (`dist` only, plain regular files): the reader only moves bytes into page-locked chunks cut at guessed record starts;
+  // each worker finds the records of its chunks on its GPU (kr_batch_submit_fastq).  The first chunk that stops early (a record
+  // that is not clean four-line FASTQ, a long sequence, a wrong cut, a batch that overflows) names the byte where the host reader
+  // (kr_fastx_open_at) takes over for good; chunks behind it were handed out already and are dropped unwritten (their sequence
+  // numbers are skipped by the writer, in order), as the pool reader's "first surprise -> sequential to the end" (kr_host.cpp).
+  bool gpu_parse = !place && !seek && a.flag.count("--gpu-parse") && a.flag.at("--gpu-parse");
+  int qfd = -1;
+  uint64_t qsize = 0;
+  if (gpu_parse) {
+    struct stat sb;
+    unsigned char mg[2] = {0, 0};
+    qfd = open(a.get("--query").c_str(), O_RDONLY);
+    if (qfd < 0 || fstat(qfd, &sb) != 0 || !S_ISREG(sb.st_mode) || (pread(qfd, mg, 2, 0) == 2 && mg[0] == 0x1f && mg[1] == 0x8b)) {
+      if (qfd >= 0) close(qfd);
+      qfd = -1, gpu_parse = false; // gzip / BGZF / not a regular file: the host reader
+    } else {
+      qsize = (uint64_t)sb.st_size;
+    }
+  }
+  // about one reader batch of ordinary FASTQ per chunk (2 bytes of input per base); KR_CLI_PARSE_CHUNK (bytes): tests
+  const uint64_t chunk_bytes = getenv("KR_CLI_PARSE_CHUNK") ? std::max<uint64_t>(4096, strtoull(getenv("KR_CLI_PARSE_CHUNK"), nullptr, 10))
+                                                            : std::min<uint64_t>(2 * batch_bases + (1u << 16), 3ull << 30);
+  std::vector<uint8_t*> raw_free; // page-locked chunk buffers not in use
+  uint64_t fb_seq = UINT64_MAX, fb_off = 0; // the first (in file order) chunk that stopped early, and the byte the host reader starts at
+  uint64_t gpu_issued = 0, gpu_done = 0;
+  std::atomic<uint64_t> nreads_dev{0};
   auto worker = [&](int g) {
     const int wid = worker_ids++;
     double t_ready = 0, t_first = -1, t_last = 0;
@@ -344,6 +376,13 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
         text_on = true;
       else
         fprintf(stderr, "[krepp_amd] report text on the host: %s\n", kr_last_error());
+    }
+    if (gpu_parse && kr_stream_fastq_enable(st, chunk_bytes)) {
+      std::lock_guard<std::mutex> lk(mu);
+      worker_err = kr_last_error();
+      ++workers_ready;
+      cv_done.notify_all();
+      return;
     }
     t_ready = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_init).count();
     {
@@ -373,6 +412,7 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
       std::vector<kr_placement> pls;
       bool my_turn = false; // this worker holds the output (plain `dist` with device text: rows are written as they arrive)
       bool handed_over = false; // ... and has passed it on already (the job's only piece took its place in the file; `j` is gone)
+      const bool gpu_job = j->raw != nullptr;
       auto emit = [&](const char* p, size_t n, bool whole_job) {
         off_t at_off = -1;
         {
@@ -380,6 +420,7 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
           if (!my_turn) cv_done.wait(lk, [&] { return next_seq == j->seq || !worker_err.empty(); });
           my_turn = true;
           if (!worker_err.empty()) return;
+          if (gpu_job && fb_seq < j->seq) return; // (a chunk behind the first early stop: the host reader covers its bytes)
           if (out_seekable) {
             at_off = file_off;
             file_off += (off_t)n;
@@ -510,7 +551,106 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
         if (!rc && piece != SIZE_MAX && ++streak >= 16) piece = piece > SIZE_MAX / 2 ? SIZE_MAX : piece * 2, streak = 0;
         return rc;
       };
-      const int rc = run(0, job_n);
+      // --gpu-parse: the chunk's records found on the device, submitted again from `consumed` while a batch stops at capacity
+      auto run_chunk = [&]() -> int {
+        {
+          std::lock_guard<std::mutex> lk(mu);
+          if (fb_seq < j->seq) return 0; // (dropped: the host reader covers these bytes)
+        }
+        uint64_t pos = 0;
+        std::vector<double> wc_job(wc_local.size(), 0.0);
+        double tw_job = 0;
+        uint64_t nr_job = 0;
+        bool fell = false;
+        std::string blob;
+        std::vector<const char*> nptr;
+        auto names_of = [&](const uint8_t* raw, uint32_t n) -> int { // the accepted records' names, NUL-terminated, for the host formatter
+          const uint64_t* np = nullptr;
+          const uint32_t* nl = nullptr;
+          const int r = kr_batch_fastq_names(st, &np, &nl);
+          if (r) return r;
+          std::vector<size_t> at_(n);
+          blob.clear();
+          for (uint32_t i = 0; i < n; ++i) at_[i] = blob.size(), blob.append((const char*)raw + np[i], nl[i]), blob.push_back('\0');
+          nptr.resize(n);
+          for (uint32_t i = 0; i < n; ++i) nptr[i] = blob.data() + at_[i];
+          return 0;
+        };
+        while (pos < j->raw_len) {
+          kr_fastq_parse fp;
+          auto t_dev = now();
+          int rc = kr_batch_submit_fastq(st, j->raw + pos, j->raw_len - pos, text_on ? 0u : KR_ROWS_ONLY, j->at_eof ? 1u : 0u, &fp);
+          if (rc) return rc;
+          if (fp.nreads) {
+            const char* dtext = nullptr;
+            uint64_t dlen = 0;
+            kr_result_view rv;
+            bool on_device = false;
+            if (text_on) {
+              rc = kr_batch_collect_text(st, &dtext, &dlen);
+              on_device = rc == 0;
+              if (rc == KR_ERR_UNSUPPORTED) rc = kr_batch_collect(st, &rv);
+            } else {
+              rc = kr_batch_collect(st, &rv);
+            }
+            ns_dev += since(t_dev);
+            if (rc == KR_ERR_CAPACITY) { // more records or text than a batch holds: the host reader takes over at this batch's first record
+              fell = true;
+              break;
+            }
+            if (rc) return rc;
+            auto t_fmt = now();
+            if (on_device) {
+              emit(dtext, dlen, false);
+            } else if (summarize) { // each read shares one unit among the references it keeps (src/query.cpp:168-170)
+              for (uint32_t r = 0; r < rv.nreads; ++r) {
+                uint32_t o = rv.read_off[r], n = rv.read_cnt[r], ns = 0;
+                for (uint32_t i = o; i < o + n; ++i) ns += rv.rec_sel[i];
+                const double w = 1.0 / ns;
+                for (uint32_t i = o; i < o + n; ++i)
+                  if (rv.rec_sel[i]) {
+                    const uint32_t se = rv.rec_key[i] >> 1;
+                    if (se < wc_job.size()) wc_job[se] += w;
+                    tw_job += w;
+                  }
+              }
+            } else {
+              char* txt = nullptr;
+              uint64_t len = 0;
+              rc = names_of(j->raw + pos, fp.nreads);
+              if (!rc) rc = kr_format_dist(hx, &rv, nptr.data(), &txt, &len);
+              if (rc) return rc;
+              emit(txt, len, false);
+              kr_free(txt);
+            }
+            ns_fmt += since(t_fmt);
+            nr_job += fp.nreads;
+          }
+          pos += fp.consumed;
+          if (fp.status == KR_FASTQ_OK) break;
+          if (fp.status == KR_FASTQ_CAPACITY && fp.nreads) continue;
+          fell = true; // not clean, a long sequence, a record cut by the end of the chunk or the file: the host reader from here
+          break;
+        }
+        // in the output's order: only a chunk that no earlier chunk's stop has dropped counts
+        std::unique_lock<std::mutex> lk(mu);
+        if (!my_turn) cv_done.wait(lk, [&] { return next_seq == j->seq || !worker_err.empty(); });
+        my_turn = true;
+        if (fb_seq < j->seq) return 0;
+        for (size_t q = 0; q < wc_job.size(); ++q) wc_local[q] += wc_job[q];
+        tw_local += tw_job;
+        nreads_dev += nr_job;
+        if (fell) fb_seq = j->seq, fb_off = j->raw_off + pos;
+        return 0;
+      };
+      const int rc = gpu_job ? run_chunk() : run(0, job_n);
+      if (gpu_job) {
+        std::lock_guard<std::mutex> lk(mu);
+        raw_free.push_back(j->raw);
+        ++gpu_done;
+        cv_work.notify_all();
+        cv_done.notify_all();
+      }
       if (job_held) kr_fastx_release(fx, job_held); // (the batch's buffers go back to the reader)
       t_last = at(), ++njobs;
       if (t_first < 0) t_first = t_last;
@@ -537,7 +677,13 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
   // with 400,000-read batches through the C ABI a third host thread does pay: DESIGN.md 3.4)
   const int wpg = getenv("KR_CLI_WORKERS_PER_GPU") ? std::max(1, atoi(getenv("KR_CLI_WORKERS_PER_GPU"))) : 2;
   const int nworkers = ngpus * wpg;
-  if (kr_fastx_open(a.get("--query").c_str(), &fx)) error_exit(kr_last_error()); // (before the workers: they hand batches back to it)
+  if (!gpu_parse && kr_fastx_open(a.get("--query").c_str(), &fx)) error_exit(kr_last_error()); // (before the workers: they hand batches back to it)
+  if (gpu_parse) // page-locked chunk buffers: one per worker at work, one being filled, one waiting per worker
+    for (int q = 0; q < 2 * nworkers + 1; ++q) {
+      uint8_t* b_ = (uint8_t*)kr_host_alloc(chunk_bytes + 16);
+      if (!b_) error_exit("cannot allocate page-locked chunk buffers for --gpu-parse");
+      raw_free.push_back(b_);
+    }
   std::vector<std::thread> workers;
   for (int w = 0; w < nworkers; ++w) workers.emplace_back(worker, w % ngpus);
 
@@ -602,7 +748,64 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
     t_loop = std::chrono::steady_clock::now();
   });
   uint64_t nbatches = 0, nreads_total = 0;
+  if (gpu_parse) { // the reader moves bytes only
+    auto t_parse = now();
+    uint64_t off = 0;
+    while (off < qsize) {
+      uint8_t* buf = nullptr;
+      {
+        std::unique_lock<std::mutex> lk(mu);
+        cv_work.wait(lk, [&] { return !raw_free.empty() || fb_seq != UINT64_MAX || !worker_err.empty(); });
+        if (fb_seq != UINT64_MAX || !worker_err.empty()) break; // (an early stop: nothing behind it will be used)
+        buf = raw_free.back();
+        raw_free.pop_back();
+      }
+      const uint64_t want = std::min<uint64_t>(chunk_bytes, qsize - off);
+      uint64_t got = 0;
+      while (got < want) {
+        const ssize_t k = pread(qfd, buf + got, want - got, (off_t)(off + got));
+        if (k <= 0) error_exit("cannot read " + a.get("--query"));
+        got += (uint64_t)k;
+      }
+      const bool last = off + want >= qsize;
+      uint64_t cut = want;
+      if (!last) { // a line starting with '@' whose second next line starts with '+' (the pool reader's rule, kr_host.cpp); none: the
+                   // chunk ends inside a record, its last record stops INCOMPLETE and the host reader takes over there
+        const uint64_t w0 = want > (1u << 20) ? want - (1u << 20) : 0;
+        const uint8_t* nl = (const uint8_t*)memchr(buf + w0, '\n', want - w0);
+        while (nl) {
+          const uint64_t c = (uint64_t)(nl - buf) + 1;
+          const uint8_t* l1 = c < want ? (const uint8_t*)memchr(buf + c, '\n', want - c) : nullptr;
+          const uint8_t* l2 = l1 && (uint64_t)(l1 - buf) + 1 < want ? (const uint8_t*)memchr(l1 + 1, '\n', want - (uint64_t)(l1 - buf) - 1) : nullptr;
+          if (!l2 || (uint64_t)(l2 - buf) + 1 >= want) break;
+          if (buf[c] == '@' && l2[1] == '+') cut = c;
+          nl = l1;
+        }
+      }
+      Job* j = new Job();
+      j->raw = buf, j->raw_len = cut, j->raw_off = off, j->at_eof = last && cut == want;
+      off += cut;
+      {
+        std::unique_lock<std::mutex> lk(mu);
+        j->seq = nbatches++;
+        ++gpu_issued;
+        cv_work.wait(lk, [&] { return todo.size() < (size_t)(2 * nworkers) || !worker_err.empty(); });
+        todo.push_back(j);
+      }
+      cv_work.notify_all();
+    }
+    ns_parse += since(t_parse);
+    { // every chunk handed out is done (an earlier one may still stop early): then the first stop, if any, is final
+      std::unique_lock<std::mutex> lk(mu);
+      cv_done.wait(lk, [&] { return gpu_done == gpu_issued || !worker_err.empty(); });
+    }
+    close(qfd);
+    if (fb_seq != UINT64_MAX && worker_err.empty()) {
+      if (kr_fastx_open_at(a.get("--query").c_str(), fb_off, &fx)) error_exit(kr_last_error());
+    }
+  }
   for (;;) {
+    if (gpu_parse && !fx) break; // (every record went through the device)
     {
       std::lock_guard<std::mutex> lk(mu);
       if (!worker_err.empty()) break; // (a worker without a stream, or one whose batch failed: reported below)
@@ -667,6 +870,7 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
   ready_watch.join();
   writer.join();
   if (!worker_err.empty()) error_exit(worker_err);
+  nreads_total += nreads_dev; // (--gpu-parse: the records found on the device)
   if (summarize && !place) // src/krepp.cpp:388-393 (ascending colour id instead of hash-map order)
     for (uint32_t se = 0; se < wcount.size(); ++se)
       if (wcount[se] != 0) fprintf(out, "%s\t%.5f\t%.5f\n", kr_host_index_node_name(hx, se), wcount[se], wcount[se] / twcount);
