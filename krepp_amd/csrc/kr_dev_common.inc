@@ -91,7 +91,7 @@ struct DevIndex {
 };
 
 struct LlhConst {
-  uint32_t k, h, th, dbg; // dbg: timing experiments only (KR_DEBUG_LLH): 1 no pow, 2 no log(d)/log(1-d), 4 no final log, 8 short loop
+  uint32_t k, h, th, dbg; // dbg (KR_DEBUG_LLH): bit 0 = the device library's pow in place of pown_dd (llh_dpart; tests/test_gpu_llh_numerics.py relies on it)
   double binom_k[32];
   double binom_hnk[kMaxPlanes];
 };

@@ -196,7 +196,12 @@ int salloc(kr_stream* s, T** p, uint64_t n)
   HIP_TRY(hipMalloc((void**)p, std::max<uint64_t>(16, n * sizeof(T))));
   s->dallocs.push_back(*p);
   if (const char* e = getenv("KR_DEBUG_POISON")) { // tests: nothing may depend on what a fresh buffer holds ("all": every buffer; a number: the k-th of the stream)
-    if (!strcmp(e, "all") || (size_t)atoi(e) == s->dallocs.size()) HIP_TRY(hipMemset(*p, 0xA5, std::max<uint64_t>(16, n * sizeof(T))));
+    if (!strcmp(e, "all") || (size_t)atoi(e) == s->dallocs.size()) {
+      HIP_TRY(hipMemset(*p, 0xA5, std::max<uint64_t>(16, n * sizeof(T))));
+      // a device memset may return before it has run, and the lanes' streams do not wait for the null stream: without this the
+      // fill could land AFTER the clear of a buffer that kr_stream_create zeroes on a lane's stream (the spill accumulators)
+      HIP_TRY(hipDeviceSynchronize());
+    }
   }
   return KR_OK;
 }
