@@ -503,6 +503,21 @@ KR_API int kr_place_stream(const kr_host_index*, const kr_index*, const kr_place
 KR_API void kr_place_counters(uint64_t* device_batches, uint64_t* host_batches, uint64_t* heavy_reads);
 /* Ranges of reads whose `place` rows were written on the device / that the host formatted although device text was asked for. */
 KR_API void kr_place_text_counters(uint64_t* device_ranges, uint64_t* fallback_ranges);
+/* Which recovery paths of the device back end ran in this process: the first `n` (at most KR_PLACE_PATHS) of
+ *   [0] ranges run again because the candidate slots ran out (once per rerun)   [1] ... because the kept-candidate slots ran out
+ *   [2] ranges finished with the internal candidates' list incomplete (kr_place_llh_kernel minimised by itself)
+ *   [3] ranges given up: still out of slots after two reruns, or asking for more than a slot index can name (the batch goes to
+ *       the host back end)
+ *   [4..8] ranges whose device text was not taken, by flag: 1 a number out of range, 2 more text than the buffer holds, 4 (not
+ *       raised any more), 8 a rounding tie too close, 16 nothing formatted / a node number out of range; a range counts once
+ *       under every flag it raised
+ *   [9] ranges finished
+ *   of the range finished last, its last attempt: [10] candidate slots asked for  [11] kept-candidate slots handed out  [12]
+ *   entries of the internal candidates' list handed out  [13] bytes of its text (0 without device text)  [14] [15] [16] the
+ *   candidate slots, kept slots and text bytes it ran with  [17] its flag word  [18] its text flags  [19] attempts (1: no rerun).
+ * [0..9] only grow.  For tests (KR_DEBUG_PLACE_CAPS lowers the capacities). */
+#define KR_PLACE_PATHS 20
+KR_API void kr_place_path_counters(uint64_t* out, uint32_t n);
 /* `tabular`: 0 jplace, 1 --tabular, 2 --summarize (no per-read text; feed the placements to
  * kr_place_summary_add).  place --summarize (src/krepp.cpp:466-471,493-497): `wcount` has
  * kr_place_tree_nnodes + 1 doubles, zeroed by the caller before the first batch and indexed by edge + 1. */

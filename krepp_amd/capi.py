@@ -101,7 +101,7 @@ EXPORTS = [
     "kr_debug_front_end", "kr_debug_stream_move", "kr_debug_stream_addrs", "kr_debug_item_placement", "kr_debug_brent", "kr_debug_colour_classes", "kr_llh_batch", "kr_llh_eval_indexed", "kr_batch_timing",
     "kr_place_tree_create", "kr_place_tree_create_lineage", "kr_place_tree_nnodes", "kr_place_summary_add",
     "kr_place_summary_text", "kr_place_tree_free", "kr_place_tree_kinds", "kr_place_batch", "kr_place_stream", "kr_place_frame", "kr_place_counters",
-    "kr_debug_last_d2h_bytes", "kr_debug_place_fixed5", "kr_place_text_counters", "kr_fastx_open", "kr_fastx_open_at", "kr_fastx_next", "kr_fastx_detach", "kr_fastx_release", "kr_fastx_close", "kr_fastx_parallel_chunks", "kr_fastx_pgz_stats", "kr_format_dist", "kr_debug_fixed5", "kr_free", "kr_host_alloc", "kr_host_free",
+    "kr_debug_last_d2h_bytes", "kr_debug_place_fixed5", "kr_place_text_counters", "kr_place_path_counters", "kr_fastx_open", "kr_fastx_open_at", "kr_fastx_next", "kr_fastx_detach", "kr_fastx_release", "kr_fastx_close", "kr_fastx_parallel_chunks", "kr_fastx_pgz_stats", "kr_format_dist", "kr_debug_fixed5", "kr_free", "kr_host_alloc", "kr_host_free",
     "kr_build_index", "kr_minimizers_cpu", "kr_minimizers_device", "kr_minimizers_free", "kr_last_error", "kr_version",
 ]
 
@@ -710,6 +710,23 @@ def place_text_counters():
     load().kr_place_text_counters.restype = None
     load().kr_place_text_counters(C.byref(a), C.byref(b))
     return int(a.value), int(b.value)
+
+
+PLACE_PATHS = ("reruns_cand", "reruns_keep", "list_cut", "given_up", "text_flag_1", "text_flag_2", "text_flag_4", "text_flag_8", "text_flag_16",
+               "ranges", "cnt0", "cnt3", "cnt12", "text_bytes", "cand_cap", "keep_cap", "text_cap", "flags", "text_flags", "attempts")
+
+
+def place_path_counters():
+    """kr_place_path_counters as a dict: which recovery paths of the device back end of `place` ran in this process (reruns for
+    candidate / kept slots, ranges with the internal candidates' list cut, ranges given up to the host back end, text fallbacks by
+    flag, ranges finished: these only grow), and of the range finished last what it asked for (cnt0 candidate slots, cnt3 kept slots,
+    cnt12 list entries, text_bytes) and ran with (cand_cap, keep_cap, text_cap, flags, text_flags, attempts)."""
+    out = (C.c_uint64 * len(PLACE_PATHS))()
+    lib = load()
+    lib.kr_place_path_counters.restype = None
+    lib.kr_place_path_counters.argtypes = [C.POINTER(C.c_uint64), C.c_uint32]
+    lib.kr_place_path_counters(out, len(PLACE_PATHS))
+    return dict(zip(PLACE_PATHS, (int(v) for v in out)))
 
 
 def place_heavy_reads():

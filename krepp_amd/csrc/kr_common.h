@@ -4,6 +4,7 @@
 
 #include "krepp_amd.h"
 
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <functional>
@@ -220,6 +221,14 @@ void place_device_abort(kr_stream* s);
 // the first place_device_launch.  names: the batch's read ids; tabular 0 = jplace rows, 1 = tabular rows.  Off again at the next
 // place_device_begin.
 int place_device_text_begin(kr_stream* s, const PlaceTreeArrays& T, const char* const* names, uint32_t nreads, int tabular, bool multi);
+// Which of the back end's recovery paths ran (kr_place_path_counters, krepp_amd.h: the order of its values): counted where they are
+// taken, in place_device_finish and kr_place_stream.
+enum PlacePath : uint32_t {
+  kPathRerunCand = 0, kPathRerunKeep, kPathListCut, kPathGivenUp, kPathText1, kPathText2, kPathText4, kPathText8, kPathText16, kPathRanges,
+  kPathLastCnt0, kPathLastCnt3, kPathLastCnt12, kPathLastText, kPathLastCandCap, kPathLastKeepCap, kPathLastTextCap, kPathLastFlags,
+  kPathLastTextFlags, kPathLastAttempts, kPathCount
+};
+extern std::atomic<uint64_t> g_place_paths[kPathCount];
 
 } // namespace kr
 

@@ -85,6 +85,7 @@ struct PlaceOut {
   uint32_t big_off, big_min_records, inline_waves;
   double* chain_inline;      // [inline_waves][chain_inline_cap]: the weights of a read such a wave does in global scratch
   uint32_t chain_inline_cap;
+  uint32_t lcap;             // entries of k_se the internal candidates' list may take: kcap (less in tests: KR_DEBUG_PLACE_CAPS)
 };
 
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
@@ -465,7 +466,7 @@ __device__ __forceinline__ bool place_read(const LlhConst& C, const DevIndex& ix
           uint32_t b = 0;
           if (lane == 0) b = atomicAdd(&po.cnt[kPlCnt * (12)], take);
           i_pos = __shfl(b, 0, 64), i_end = i_pos + take;
-          if (i_end > po.kcap) { // (cannot happen with the sizes kr_host_place.inc gives the list: then the likelihood kernel minimises by itself)
+          if (i_end > po.lcap) { // (cannot happen with the sizes kr_host_place.inc gives the list: then the likelihood kernel minimises by itself)
             if (lane == 0) atomicOr(&po.cnt[kPlCnt * (1)], 8u);
             i_pos = i_end = 0;
           }
@@ -623,7 +624,7 @@ __global__ __launch_bounds__(256) void kr_place_brent_kernel(LlhConst C, PlaceOu
   LlhTables LT{(lds_f64*)s_bk, (lds_f64*)s_hnk};
   llh_tables_init(C, LT.bk, LT.hnk);
   if (po.cnt[kPlCnt * (1)] & 8u) return; // the list is incomplete: kr_place_llh_kernel minimises
-  const uint32_t np = NPT ? (uint32_t)NPT : C.th + 1, nlist = min(po.cnt[kPlCnt * (12)], po.kcap);
+  const uint32_t np = NPT ? (uint32_t)NPT : C.th + 1, nlist = min(po.cnt[kPlCnt * (12)], po.lcap);
   for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < nlist; j += gridDim.x * blockDim.x) {
     const uint32_t i = po.k_se[j];
     if (i == 0xFFFFFFFFu) continue;
@@ -746,6 +747,7 @@ __global__ __launch_bounds__(256) void kr_place_compact_kernel(PlaceOut po, Plac
 // lanes -- hundreds of microseconds for the 256 reads a wave got with the `dist` text's 1,024-read blocks, whatever the batch
 // (2.3 ms of a 9 ms call at the CLI's 65,536 reads); 64 reads a block put every CU to work on a batch of that size
 constexpr uint32_t kPlTextBlock = 64;
+constexpr uint32_t kPlTextNoRange = 16; // flag of PlaceText::total[1]: nothing was formatted (a range about to be run again), or a node number was out of range
 struct PlaceText {
   const char* ids;           // ids of the range's reads, back to back
   const uint32_t* id_off;    // [nreads + 1]
@@ -757,7 +759,8 @@ struct PlaceText {
   uint64_t* t_bsum;          // [ceil(nreads / kRowBlock) + 1]
   char* text;
   uint64_t text_cap;
-  uint64_t* total;           // [0] bytes  [1] flags: 1 number out of range, 2 more text than text_cap, 8 a tie too close
+  uint64_t* total;           // [0] bytes  [1] flags: 1 number out of range, 2 more text than text_cap, 8 a tie too close,
+                             // 16 (kPlTextNoRange) the range is not one to format: see kr_place_text_len_kernel
   uint32_t tabular;          // 0 jplace, 1 tabular
   uint32_t multi;
   double chisq;
@@ -831,24 +834,34 @@ __device__ __forceinline__ bool place_cand_keep(const PlaceTree& T, const PlaceT
   if (single) return i == 0u; // a single placement: the read's first candidate as it is (src/query.cpp:233-244)
   return c < tx.chisq && T.parent[se] != 0u;
 }
-__device__ __forceinline__ uint32_t place_read_prepare(const PlaceOut& po, const PlaceTree& T, const PlaceText& tx, uint32_t r, double& total_out, uint32_t& best_out)
+__device__ __forceinline__ uint32_t place_read_prepare(const PlaceOut& po, const PlaceTree& T, const PlaceText& tx, uint32_t r, double& total_out, uint32_t& best_out,
+                                                       uint32_t& flags)
 {
   const uint32_t lane = lane_id();
   const uint32_t info = po.rd_info[r];
   const uint32_t n = info & 0x3FFFFFFFu, c0 = po.rd_c0[r];
   const bool single = ((info >> 30) & 1u) != 0;
+  // A node number taken from the kept-candidate arrays indexes the tree's arrays (parent, card, blen, label_off: pn + 1 entries) here
+  // and in place_tile_rows, which reads it back from s_se: one that is not a node of the tree is replaced by node 0 and raises
+  // kPlTextNoRange, so that nothing is indexed with it and the host formats the range.  (The compaction writes nodes of the tree
+  // only; the check is what stands between a slot it did not write and a load far outside the arrays.)
+  auto node_of = [&](uint32_t raw) -> uint32_t {
+    if (raw == 0x7FFFFFFFu) return 0u; // (node 0 of a single placement: 0 itself marks an unused slot)
+    if (raw > T.pn) {
+      flags |= kPlTextNoRange;
+      return 0u;
+    }
+    return raw;
+  };
   // ---- sorted copy
   for (uint32_t a0 = 0; a0 < n; a0 += 64u) {
     const uint32_t i = a0 + lane;
-    uint32_t se = 0xFFFFFFFFu, raw = 0;
-    if (i < n) raw = po.k_se[c0 + i], se = raw == 0x7FFFFFFFu ? 0u : raw; // (node 0 of a single placement: 0 itself marks an unused slot)
+    uint32_t se = 0xFFFFFFFFu;
+    if (i < n) se = node_of(po.k_se[c0 + i]);
     uint32_t rank = 0;
     for (uint32_t b0 = 0; b0 < n; b0 += 64u) {
       uint32_t sb = 0xFFFFFFFFu;
-      if (b0 + lane < n) {
-        const uint32_t rb_ = po.k_se[c0 + b0 + lane];
-        sb = rb_ == 0x7FFFFFFFu ? 0u : rb_;
-      }
+      if (b0 + lane < n) sb = node_of(po.k_se[c0 + b0 + lane]);
       const uint32_t m = min(64u, n - b0);
       for (uint32_t j = 0; j < m; ++j) {
         const uint32_t sj = (uint32_t)__shfl((int)sb, (int)j);
@@ -983,17 +996,27 @@ __global__ __launch_bounds__(256) void kr_place_text_len_kernel(PlaceOut po, Pla
 {
   __shared__ uint32_t s_sum[4];
   const uint32_t lane = lane_id(), w = threadIdx.x >> 6;
+  // A range that ran out of candidate slots (flag 2 of cnt[1]) or of slots for the kept ones (4) is about to be run again
+  // (place_device_finish), and its per-read words are not the compaction's: a read the compaction skipped for want of slots still
+  // names its slots in the c_* arrays, where k_se holds the Brent list's slot numbers and 0xFFFFFFFF markers, not nodes.  Nothing of
+  // such a range is read: every length is 0, so that kr_text_bscan_kernel finds its sums and total[0] defined, and kPlTextNoRange
+  // in total[1] keeps the writing kernel out and the empty text from being taken for the range's.  (The flag word is final here:
+  // these kernels are queued behind the compaction on the same stream.  The guard stands at the range and not in the compaction --
+  // which could clear bit 31 of a read it skips -- because it also covers the reads that found no candidate slots, and saves the
+  // sort and the logarithms of every other read of an attempt that is thrown away.)
+  const bool discarded = (po.cnt[kPlCnt * (1)] & (2u | 4u)) != 0;
+  if (discarded && blockIdx.x == 0 && threadIdx.x == 0) atomicOr((unsigned long long*)&tx.total[1], (unsigned long long)kPlTextNoRange);
   for (uint32_t b = blockIdx.x; b * kPlTextBlock < nreads; b += gridDim.x) {
     const uint32_t rb = b * kPlTextBlock;
     uint32_t wsum = 0, flags = 0;
     for (uint32_t q = w; q < kPlTextBlock && rb + q < nreads; q += 4u) {
       const uint32_t r = rb + q;
       uint32_t len = 0;
-      if (po.rd_info[r] >> 31) {
+      if (!discarded && (po.rd_info[r] >> 31)) {
         const uint32_t idl = tx.id_off[r + 1] - tx.id_off[r];
         double total;
         uint32_t best;
-        const uint32_t n = place_read_prepare(po, T, tx, r, total, best);
+        const uint32_t n = place_read_prepare(po, T, tx, r, total, best, flags);
         if (lane == 0) tx.rd_total[r] = total, tx.rd_best[r] = best;
         uint32_t nrows = 0, rl = 0;
         for (uint32_t t0 = 0; t0 < n; t0 += 64u) {
@@ -1023,7 +1046,7 @@ __global__ __launch_bounds__(256) void kr_place_text_write_kernel(PlaceOut po, P
 {
   __shared__ uint32_t s_off[kPlTextBlock];
   __shared__ uint32_t s_w[4];
-  if (tx.total[0] > tx.text_cap || (tx.total[1] & ~2ull) != 0) return; // (the host formats this range)
+  if (tx.total[0] > tx.text_cap || (tx.total[1] & ~2ull) != 0) return; // (the host formats this range, or -- kPlTextNoRange -- it is run again)
   const uint32_t lane = lane_id(), w = threadIdx.x >> 6;
   for (uint32_t b = blockIdx.x; b * kPlTextBlock < nreads; b += gridDim.x) {
     const uint32_t rb = b * kPlTextBlock, q0 = 4u * threadIdx.x;

@@ -1,6 +1,23 @@
 // kr_host_place.inc -- part of kr_device.hip (host side): kr::place_on_device, the launch of the place kernels for kr_place_stream.
 
 namespace {
+// KR_DEBUG_POISON=all (tests, as for the stream's own buffers: salloc): nothing may depend on what a new place workspace holds
+int place_poison(void* p, uint64_t bytes)
+{
+  const char* e = getenv("KR_DEBUG_POISON");
+  if (!e || strcmp(e, "all")) return KR_OK;
+  HIP_TRY(hipMemset(p, 0xA5, bytes));
+  HIP_TRY(hipDeviceSynchronize()); // (the lanes' streams do not wait for the null stream)
+  return KR_OK;
+}
+// What the kernels are told the buffers hold: all of it, or what KR_DEBUG_PLACE_CAPS says (never more than there is)
+uint64_t place_cand_slots(const kr_stream::PlaceWs& w) { return w.dbg_cand ? std::min(w.dbg_cand, w.cand_cap) : w.cand_cap; }
+uint64_t place_keep_slots(const kr_stream::PlaceWs& w) { return w.dbg_keep ? std::min(w.dbg_keep, w.keep_cap) : w.keep_cap; }
+uint64_t place_text_bytes(const kr_stream::PlaceWs& w)
+{
+  if (!w.dbg_text) return w.text_cap;
+  return std::min(w.text_cap, w.dbg_sticky ? w.dbg_text : std::max(w.dbg_text, w.text_want_min));
+}
 // candidate slots of a stream's place workspace: a read may need one per leaf and per distinct ancestor while it is worked on, and
 // keeps what it emits; a range that runs out (large trees) is run again with as many as it asked for
 int place_size_candidates(kr_stream* s, uint64_t want)
@@ -9,7 +26,7 @@ int place_size_candidates(kr_stream* s, uint64_t want)
   auto dev_renew = [&](auto*& p, uint64_t n) -> int {
     if (p) (void)hipFree(p), p = nullptr;
     HIP_TRY(hipMalloc((void**)&p, std::max<uint64_t>(16, n * sizeof(*p))));
-    return KR_OK;
+    return place_poison(p, std::max<uint64_t>(16, n * sizeof(*p)));
   };
   int rc2 = 0;
   if (want > w.cand_cap) {
@@ -20,7 +37,7 @@ int place_size_candidates(kr_stream* s, uint64_t want)
   }
   // every candidate, twice: a read that does not fit the rest of its wave's chunk takes a new one and leaves the rest unused (up to
   // total - 1 slots per read), + a partly used chunk per wave of the compaction; a range that still runs out is run again
-  const uint64_t keep_want = std::max<uint64_t>(w.keep_want_min, 2ull * w.cand_cap + 2048ull * 4ull * kPlKeepChunk);
+  const uint64_t keep_want = w.dbg_keep ? w.dbg_keep : std::max<uint64_t>(w.keep_want_min, 2ull * w.cand_cap + 2048ull * 4ull * kPlKeepChunk);
   if (keep_want > w.keep_cap) {
     if ((rc2 = dev_renew(w.d_kse, keep_want)) || (rc2 = dev_renew(w.d_kd, keep_want)) || (rc2 = dev_renew(w.d_kv, keep_want)) || (rc2 = dev_renew(w.d_kchi, keep_want)))
       return rc2;
@@ -73,7 +90,7 @@ int kr::place_device_begin(kr_stream* s, const void* tree_tag, const kr::PlaceTr
   auto dev_renew = [&](auto*& p, uint64_t n) -> int {
     if (p) (void)hipFree(p), p = nullptr;
     HIP_TRY(hipMalloc((void**)&p, std::max<uint64_t>(16, n * sizeof(*p))));
-    return KR_OK;
+    return place_poison(p, std::max<uint64_t>(16, n * sizeof(*p)));
   };
   auto pin_renew = [&](auto*& p, uint64_t n) -> int {
     if (p) (void)hipHostFree(p), p = nullptr;
@@ -111,7 +128,27 @@ int kr::place_device_begin(kr_stream* s, const void* tree_tag, const kr::PlaceTr
   }
   // candidate slots: a read may need one per leaf and per distinct ancestor while it is worked on, and keeps what it
   // emits; a batch that runs out (large trees) is run again with as many as it asked for
-  if ((rc = place_size_candidates(s, std::max<uint64_t>(1u << 20, (uint64_t)n * 24)))) return rc;
+  // KR_DEBUG_PLACE_CAPS="c=SLOTS,k=SLOTS,t=BYTES,l=ENTRIES,sticky" (tests; read per batch, every field optional): the first attempt's
+  // candidate slots, kept-candidate slots and text bytes in place of the floors here, in place_size_candidates and in
+  // place_device_text_begin -- a new stream's buffers are made that small, a larger buffer is used up to there --, so that a small
+  // batch runs out of each; l: what the internal candidates' list may take of the kept slots (a batch of a few hundred reads lists
+  // fewer entries than its compaction takes slots: no kept cap cuts the one and not the other); "sticky": a range that is run
+  // again gets no more than the first time (it ends at the host back end)
+  w.dbg_cand = w.dbg_keep = w.dbg_text = w.dbg_list = 0, w.dbg_sticky = false;
+  if (const char* e = getenv("KR_DEBUG_PLACE_CAPS")) {
+    for (const char* q = e; *q;) {
+      if (q[0] && q[1] == '=' && (q[0] == 'c' || q[0] == 'k' || q[0] == 't' || q[0] == 'l')) {
+        const uint64_t v = std::max<uint64_t>(1, strtoull(q + 2, nullptr, 10));
+        (q[0] == 'c' ? w.dbg_cand : q[0] == 'k' ? w.dbg_keep : q[0] == 't' ? w.dbg_text : w.dbg_list) = v;
+      } else if (!strncmp(q, "sticky", 6)) {
+        w.dbg_sticky = true;
+      }
+      while (*q && *q != ',') ++q;
+      if (*q) ++q;
+    }
+    w.dbg_cand = std::min<uint64_t>(w.dbg_cand, 0x3FFFFFFFull);
+  }
+  if ((rc = place_size_candidates(s, w.dbg_cand ? w.dbg_cand : std::max<uint64_t>(1u << 20, (uint64_t)n * 24)))) return rc;
   // (the device's properties once per stream: the query is a millisecond-class call)
   if (!w.cu_count) {
     hipDeviceProp_t prop0;
@@ -174,12 +211,13 @@ int kr::place_device_launch(kr_stream* s, const kr::PlaceTreeArrays& T, uint32_t
   PlaceTree PT{w.d_parent, w.d_eff, w.d_elig, w.d_lo, w.d_idx_to_pt, w.d_depth, w.d_node, T.pn, T.nidx};
   HIP_TRY(hipMemsetAsync(w.d_cnt, 0, 64 * kPlCnt, st));
   HIP_TRY(hipMemsetAsync(w.d_cse, 0, w.cand_cap * 4, st)); // 0 = unused slot: what the second kernel and the host skip
-  PlaceOut PO{w.d_c0 + r0, w.d_info + r0, w.d_cse, w.d_cread, w.d_cd, w.d_cv, w.d_cchi, w.d_cprob, w.d_rprob, w.d_cnt, (uint32_t)std::min<uint64_t>(w.cand_cap, 0x3FFFFFFFu),
+  PlaceOut PO{w.d_c0 + r0, w.d_info + r0, w.d_cse, w.d_cread, w.d_cd, w.d_cv, w.d_cchi, w.d_cprob, w.d_rprob, w.d_cnt, (uint32_t)std::min<uint64_t>(place_cand_slots(w), 0x3FFFFFFFu),
               w.d_heavy, w.d_heavy_u32, w.d_heavy_f64, w.heavy_leaves, w.heavy_nodes, kPlLeaves, kPlNodes,
-              w.d_kse, w.d_kd, w.d_kv, w.d_kchi, (uint32_t)std::min<uint64_t>(w.keep_cap, 0xFFFFFFFFull), w.d_chain, w.chain_cap,
+              w.d_kse, w.d_kd, w.d_kv, w.d_kchi, (uint32_t)std::min<uint64_t>(place_keep_slots(w), 0xFFFFFFFFull), w.d_chain, w.chain_cap,
               w.chain_cap * std::max<uint32_t>(1u, w.chain_waves / std::max<uint32_t>(1u, w.heavy_waves)), heavy_lds ? 1u : 0u,
               (uint32_t)((uint64_t)n + 8ull * grid), 0u, big_first ? std::min<uint32_t>(std::min<uint32_t>(w.heavy_waves, grid), 1024u) : 0u,
-              w.d_chain + (uint64_t)w.chain_waves * w.chain_cap, 4u * w.chain_cap};
+              w.d_chain + (uint64_t)w.chain_waves * w.chain_cap, 4u * w.chain_cap, 0u};
+  PO.lcap = w.dbg_list ? (uint32_t)std::min<uint64_t>(w.dbg_list, PO.kcap) : PO.kcap;
   if (const char* e = getenv("KR_DEBUG_PLACE_LDS")) { // tests: "leaves,nodes" the LDS launch accepts, so that small trees have heavy reads
     unsigned a = kPlLeaves, b = kPlNodes;
     if (sscanf(e, "%u,%u", &a, &b) >= 1) PO.lds_leaves = std::max(1u, a), PO.lds_nodes = std::max(1u, b);
@@ -205,12 +243,12 @@ int kr::place_device_launch(kr_stream* s, const kr::PlaceTreeArrays& T, uint32_t
   //  for its 200,000 candidates)
   hipLaunchKernelGGL(kr_place_compact_kernel, dim3(std::max<uint32_t>(16u, std::min<uint32_t>(2048u, (n + 255u) / 256u))), dim3(256), 0, st, PO, PT, n, chisq);
   if (w.text_on) { // the range's rows as text (kr_dev_place.inc): lengths, the blocks' first bytes, bytes
-    PlaceText TX{w.d_ids, w.d_id_off + r0, w.d_blen, w.d_card, w.d_labels, w.d_label_off, w.d_tlen + r0, w.d_tbsum, w.d_text, w.text_cap, w.d_ttotal,
+    PlaceText TX{w.d_ids, w.d_id_off + r0, w.d_blen, w.d_card, w.d_labels, w.d_label_off, w.d_tlen + r0, w.d_tbsum, w.d_text, place_text_bytes(w), w.d_ttotal,
                  w.text_tabular, w.text_multi, chisq, w.d_sse, w.d_sd, w.d_sv, w.d_sc, w.d_rtotal + r0, w.d_rbest + r0};
     const uint32_t nblk = (n + kPlTextBlock - 1) / kPlTextBlock;
     HIP_TRY(hipMemsetAsync(w.d_ttotal, 0, 16, st));
     hipLaunchKernelGGL(kr_place_text_len_kernel, dim3(std::min<uint32_t>(nblk, 16384u)), dim3(256), 0, st, PO, PT, TX, n);
-    TextIO tio{nullptr, nullptr, 0u, nullptr, nullptr, nullptr, w.d_tbsum, nullptr, w.text_cap, w.d_ttotal};
+    TextIO tio{nullptr, nullptr, 0u, nullptr, nullptr, nullptr, w.d_tbsum, nullptr, place_text_bytes(w), w.d_ttotal};
     // (the `dist` text's block scan counts its blocks as ceil(reads / kRowBlock): told of nblk x kRowBlock reads it scans these nblk sums)
     hipLaunchKernelGGL(kr_text_bscan_kernel, dim3(1), dim3(1024), 0, st, tio, nblk * kRowBlock);
     hipLaunchKernelGGL(kr_place_text_write_kernel, dim3(std::min<uint32_t>(nblk, 16384u)), dim3(256), 0, st, PO, PT, TX, n);
@@ -242,16 +280,34 @@ int kr::place_device_finish(kr_stream* s, const kr::PlaceTreeArrays& T, uint32_t
     t_mark = now;
   };
   const uint32_t grid = std::min<uint32_t>(n, w.cu_count * 16u);
-  for (int attempt = 0;; ++attempt) {
+  int attempt = 0;
+  for (;; ++attempt) {
     HIP_TRY(hipStreamSynchronize(st));
     if (!(w.h_cnt[kPlCnt * (1)] & (2u | 4u)) || attempt >= 2) break;
     // out of candidate slots (bit 1: counters[0] went on counting what the reads asked for) or out of slots for the kept ones
     // (bit 2: counters[3] went on counting what the compaction handed out)
-    const uint64_t asked = (w.h_cnt[kPlCnt * (1)] & 2u) ? (uint64_t)w.h_cnt[kPlCnt * (0)] + w.h_cnt[kPlCnt * (0)] / 8 + (uint64_t)grid * kPlChunk : w.cand_cap;
+    const uint64_t asked = (w.h_cnt[kPlCnt * (1)] & 2u) ? (uint64_t)w.h_cnt[kPlCnt * (0)] + w.h_cnt[kPlCnt * (0)] / 8 + (uint64_t)grid * kPlChunk : place_cand_slots(w);
     if (asked > 0x3FFFFFFFull) break; // beyond what a slot index can name: the host back end takes the batch
-    if (w.h_cnt[kPlCnt * (1)] & 4u) w.keep_want_min = (uint64_t)w.h_cnt[kPlCnt * (3)] + w.h_cnt[kPlCnt * (3)] / 8 + 2048ull * 4ull * kPlKeepChunk;
+    if (w.h_cnt[kPlCnt * (1)] & 2u) kr::g_place_paths[kr::kPathRerunCand].fetch_add(1, std::memory_order_relaxed);
+    if (w.h_cnt[kPlCnt * (1)] & 4u) {
+      kr::g_place_paths[kr::kPathRerunKeep].fetch_add(1, std::memory_order_relaxed);
+      w.keep_want_min = (uint64_t)w.h_cnt[kPlCnt * (3)] + w.h_cnt[kPlCnt * (3)] / 8 + 2048ull * 4ull * kPlKeepChunk;
+    }
+    if (!w.dbg_sticky) { // (KR_DEBUG_PLACE_CAPS: the rerun gets what it asked for, as it does from the real sizes)
+      if (w.dbg_cand) w.dbg_cand = std::max(w.dbg_cand, asked);
+      if (w.dbg_keep && (w.h_cnt[kPlCnt * (1)] & 4u)) w.dbg_keep = std::max(w.dbg_keep, w.keep_want_min);
+    }
     if ((rc = place_size_candidates(s, asked))) return rc;
     if ((rc = kr::place_device_launch(s, T, r0, n, tau, no_filter, chisq))) return rc;
+  }
+  { // which paths this range took, and what it asked for (kr_place_path_counters)
+    auto set = [](uint32_t k, uint64_t v) { kr::g_place_paths[k].store(v, std::memory_order_relaxed); };
+    kr::g_place_paths[kr::kPathRanges].fetch_add(1, std::memory_order_relaxed);
+    if (w.h_cnt[kPlCnt * (1)] & 8u) kr::g_place_paths[kr::kPathListCut].fetch_add(1, std::memory_order_relaxed);
+    set(kr::kPathLastCnt0, w.h_cnt[kPlCnt * (0)]), set(kr::kPathLastCnt3, w.h_cnt[kPlCnt * (3)]), set(kr::kPathLastCnt12, w.h_cnt[kPlCnt * (12)]);
+    set(kr::kPathLastText, w.text_on ? w.h_ttotal[0] : 0), set(kr::kPathLastCandCap, place_cand_slots(w)), set(kr::kPathLastKeepCap, place_keep_slots(w));
+    set(kr::kPathLastTextCap, w.text_on ? place_text_bytes(w) : 0), set(kr::kPathLastFlags, w.h_cnt[kPlCnt * (1)]);
+    set(kr::kPathLastTextFlags, w.text_on ? w.h_ttotal[1] : 0), set(kr::kPathLastAttempts, (uint64_t)attempt + 1);
   }
   lap("place kernels (both launches, likelihoods, compaction) to their counters on the host");
   HIP_TRY(hipMemcpyAsync(w.h_c0 + r0, w.d_c0 + r0, (uint64_t)n * 4, hipMemcpyDeviceToHost, st));
@@ -268,8 +324,9 @@ int kr::place_device_finish(kr_stream* s, const kr::PlaceTreeArrays& T, uint32_t
   out->text = nullptr, out->text_len = 0, out->text_flags = 0;
   if (w.text_on) {
     out->text_flags = w.h_ttotal[1];
-    if (w.h_ttotal[0] > w.text_cap) w.text_want_min = w.h_ttotal[0] + w.h_ttotal[0] / 4; // (this range goes to the host; the next batch gets the room)
-    if (w.h_ttotal[1] == 0 && w.h_ttotal[0] <= w.text_cap) { // the range's text is complete: it comes back, the candidates stay
+    const uint64_t tcap = place_text_bytes(w); // (what the kernels were told)
+    if (w.h_ttotal[0] > tcap) w.text_want_min = w.h_ttotal[0] + w.h_ttotal[0] / 4; // (this range goes to the host; the next batch gets the room)
+    if (w.h_ttotal[1] == 0 && w.h_ttotal[0] <= tcap) { // the range's text is complete: it comes back, the candidates stay
       const uint64_t tl = w.h_ttotal[0];
       if (tl > w.h_text_cap) {
         if (w.h_text) (void)hipHostFree(w.h_text), w.h_text = nullptr, w.h_text_cap = 0;
@@ -288,7 +345,7 @@ int kr::place_device_finish(kr_stream* s, const kr::PlaceTreeArrays& T, uint32_t
       return KR_OK;
     }
   }
-  const uint64_t used = std::min<uint64_t>(w.h_cnt[kPlCnt * (3)], w.keep_cap); // the candidates kept (compacted)
+  const uint64_t used = std::min<uint64_t>(w.h_cnt[kPlCnt * (3)], place_keep_slots(w)); // the candidates kept (compacted)
   if (kept_base + used > w.h_cand_cap) { // (an earlier range's candidates have been consumed by the time a later one is finished: nothing to carry over)
     const uint64_t cap = kept_base + used + used / 4 + 1024;
     auto pin_renew = [&](auto*& p, uint64_t cnt) -> int {
@@ -325,7 +382,7 @@ int kr::place_device_text_begin(kr_stream* s, const kr::PlaceTreeArrays& T, cons
   auto dev_renew = [&](auto*& p, uint64_t n) -> int {
     if (p) (void)hipFree(p), p = nullptr;
     HIP_TRY(hipMalloc((void**)&p, std::max<uint64_t>(16, n * sizeof(*p))));
-    return KR_OK;
+    return place_poison(p, std::max<uint64_t>(16, n * sizeof(*p)));
   };
   auto pin_renew = [&](auto*& p, uint64_t n) -> int {
     if (p) (void)hipHostFree(p), p = nullptr;
@@ -388,7 +445,7 @@ int kr::place_device_text_begin(kr_stream* s, const kr::PlaceTreeArrays& T, cons
     w.tlen_cap = cap;
   }
   if (!w.d_ttotal && ((rc = dev_renew(w.d_ttotal, 2)) || (rc = pin_renew(w.h_ttotal, 2)))) return rc;
-  const uint64_t want = std::max<uint64_t>(total + (uint64_t)nreads * 512ull + (1u << 20), w.text_want_min); // (text_want_min: what a range that outgrew the buffer asked for)
+  const uint64_t want = std::max<uint64_t>(w.dbg_text ? w.dbg_text : total + (uint64_t)nreads * 512ull + (1u << 20), w.text_want_min); // (text_want_min: what a range that outgrew the buffer asked for)
   if (want > w.text_cap) {
     if ((rc = dev_renew(w.d_text, want))) return rc;
     w.text_cap = want;

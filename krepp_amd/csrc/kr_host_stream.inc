@@ -105,6 +105,10 @@ struct kr_stream {
     uint32_t *d_sse = nullptr, *d_rbest = nullptr; // the kept candidates sorted by node (same slots as d_kse ...), per-read --no-multi choice
     double *d_sd = nullptr, *d_sv = nullptr, *d_sc = nullptr, *d_rtotal = nullptr;
     uint64_t sorted_cap = 0, rtotal_cap = 0;
+    // KR_DEBUG_PLACE_CAPS (tests; place_device_begin reads it per batch): what the kernels are told the candidate slots, the kept
+    // slots and the text buffer hold, 0 = what they do hold; `dbg_sticky`: a range that is run again is given no more
+    uint64_t dbg_cand = 0, dbg_keep = 0, dbg_text = 0, dbg_list = 0; // (dbg_list: entries of the kept slots the internal candidates' list may take)
+    bool dbg_sticky = false;
   } pw;
   // Long sequences across waves (kr_dev_tiles.inc): a host batch with sequences of more than kTileMinPos k-mer positions
   // is submitted as a batch of tiles.  Buffers are made on first use.

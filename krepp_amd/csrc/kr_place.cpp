@@ -125,6 +125,7 @@ char* dup_text(const std::string& s, uint64_t* len)
 // kr_place_stream batches of this process by back end (kr_place_counters): on the device, or sent whole to the host path
 static std::atomic<uint64_t> g_place_device_batches{0}, g_place_host_batches{0}, g_place_heavy_reads{0};
 std::atomic<uint64_t> g_place_text_device{0}, g_place_text_fallback{0};
+std::atomic<uint64_t> kr::g_place_paths[kr::kPathCount] = {};
 
 extern "C" {
 
@@ -1004,6 +1005,7 @@ int kr_place_stream(const kr_host_index* hx, const kr_index* dix, const kr_place
     if (rc) break;
     lap("A-C of a range: aggregation, Brent, chi-square on the device + copy back");
     if (res.overflow) {
+      kr::g_place_paths[kr::kPathGivenUp].fetch_add(1, std::memory_order_relaxed);
       overflow = true;
       break;
     }
@@ -1012,7 +1014,10 @@ int kr_place_stream(const kr_host_index* hx, const kr_index* dix, const kr_place
     if (k + 1 < nranges) // the next range's kernels run beside this range's last phase
       if ((rc = kr::place_device_launch(s, T, r1, r_of(k + 2) - r1, p->tau, p->no_filter != 0, p->chisq))) break;
     if (dev_text) (res.text ? g_place_text_device : g_place_text_fallback).fetch_add(1, std::memory_order_relaxed);
-    if (dev_text && !res.text && timing) fprintf(stderr, "[place/device] the device's text was not taken: flags %llu (1 a number out of range, 2 more text than the buffer holds, 4 more than 64 candidates kept in a read, 8 a rounding tie too close)\n", (unsigned long long)res.text_flags);
+    if (dev_text && !res.text)
+      for (uint32_t b = 0; b < 5; ++b)
+        if (res.text_flags & (1ull << b)) kr::g_place_paths[kr::kPathText1 + b].fetch_add(1, std::memory_order_relaxed);
+    if (dev_text && !res.text && timing) fprintf(stderr, "[place/device] the device's text was not taken: flags %llu (1 a number out of range, 2 more text than the buffer holds, 4 not raised any more: a read's kept candidates are formatted 64 at a time, 8 a rounding tie too close, 16 a node number out of range)\n", (unsigned long long)res.text_flags);
     if (res.text) { // the range's rows, written on the device
       const char* tp = res.text;
       uint64_t tl = res.text_len;
@@ -1105,6 +1110,11 @@ void kr_place_text_counters(uint64_t* device_ranges, uint64_t* fallback_ranges)
 { // ranges of reads whose rows were written on the device / that were formatted by the host although device text was asked for
   if (device_ranges) *device_ranges = g_place_text_device.load(std::memory_order_relaxed);
   if (fallback_ranges) *fallback_ranges = g_place_text_fallback.load(std::memory_order_relaxed);
+}
+
+void kr_place_path_counters(uint64_t* out, uint32_t n)
+{ // (krepp_amd.h: the order of the values)
+  for (uint32_t i = 0; out && i < n && i < kr::kPathCount; ++i) out[i] = kr::g_place_paths[i].load(std::memory_order_relaxed);
 }
 
 void kr_place_counters(uint64_t* device_batches, uint64_t* host_batches, uint64_t* heavy_reads)

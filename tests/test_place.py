@@ -343,8 +343,9 @@ def test_rows_written_on_the_device_equal_the_host_s(capi, po, toy_index_dir, to
 def test_ranges_of_a_batch_give_the_batch_s_output(capi, po, toy_index_dir, toy_reads, toy_genomes, synth, monkeypatch, ranges):
     """kr_place_stream works through a batch in ranges of reads (the host's last phase of one range beside the place kernels of the
     next, round 5): whatever the number of ranges (KR_PLACE_RANGES; 2 by default from 131,072 reads), text -- jplace separators
-    included --, placements and summary equal the host back end's, also when every read of a range exceeds the LDS limits and
-    when the candidate slots run out and a range is run again."""
+    included --, placements and summary equal the host back end's, also when every read of a range exceeds the LDS limits.  (No
+    range runs out of candidate slots here -- the floor of the workspace is a million: a range that does and is run again behind
+    the earlier ranges' candidates is tests/test_gpu_place_capacity.py's, which lowers the capacity and counts the reruns.)"""
     b2, o2, n2 = synth.sample_reads(toy_genomes, 20_000, seed=29)
     hx = capi.HostIndex(toy_index_dir)
     for env in (dict(), dict(KR_DEBUG_PLACE_LDS="3,8")):
