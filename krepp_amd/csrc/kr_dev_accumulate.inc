@@ -330,7 +330,7 @@ __device__ __forceinline__ bool finalize_events(const DevIndex& ix, const BatchO
         else
           plane_pass<PB>(bt, A.np, k0, kn, nev, ev_at);
       }
-      if ((dbg & 512u) && lane == 0) atomicAdd(&out.counters[16], (uint32_t)((__builtin_readcyclecounter() - tl0) >> 6));
+      if ((dbg & 512u) && lane == 0) atomicAdd(&out.counters[kCtCycLevel], (uint32_t)((__builtin_readcyclecounter() - tl0) >> 6));
       // ---- 4. one lane per key of the batch
       for (uint32_t j0 = 0; j0 < kn; j0 += 64) {
         const uint32_t j = j0 + lane;
@@ -392,13 +392,13 @@ __device__ __forceinline__ bool finalize_events(const DevIndex& ix, const BatchO
       WAVE_SYNC();
     }
     if ((dbg & 512u) && lane == 0) { // statistics for tuning
-      atomicAdd(&out.counters[9], nev);
-      atomicAdd(&out.counters[10], nkeys);
-      atomicAdd(&out.counters[11], KB ? (nkeys + KB - 1) / KB : 0u);
-      atomicAdd(&out.counters[12], big ? 1u : 0u);
-      atomicAdd(&out.counters[13], (uint32_t)__popc(lv) * ((nev + 63) / 64));
-      atomicMax(&out.counters[14], nkeys);
-      atomicMax(&out.counters[15], nev);
+      atomicAdd(&out.counters[kCtStEvents], nev);
+      atomicAdd(&out.counters[kCtStKeys], nkeys);
+      atomicAdd(&out.counters[kCtStBatches], KB ? (nkeys + KB - 1) / KB : 0u);
+      atomicAdd(&out.counters[kCtStBig], big ? 1u : 0u);
+      atomicAdd(&out.counters[kCtStLevelTiles], (uint32_t)__popc(lv) * ((nev + 63) / 64));
+      atomicMax(&out.counters[kCtStMaxKeys], nkeys);
+      atomicMax(&out.counters[kCtStMaxEvents], nev);
     }
     if (KR_STATS && (dbg & 512u) && lane == 0) {
       atomicAdd(&g_kr_stats[32u + stat_log2(nkeys)], 1u);
@@ -779,11 +779,11 @@ __device__ __forceinline__ bool finalize_events_fast(const DevIndex& ix, const B
     for (uint32_t q = lane; q < A.bm_words; q += 64) A.bitmap[q] = 0;
   }
   if (KR_STATS && (dbg & 512u) && lane == 0) { // statistics for tuning: the same counters finalize_events keeps
-    atomicAdd(&out.counters[9], nev);
-    atomicAdd(&out.counters[10], nkeys);
-    atomicAdd(&out.counters[11], 1u);
-    atomicMax(&out.counters[14], nkeys);
-    atomicMax(&out.counters[15], nev);
+    atomicAdd(&out.counters[kCtStEvents], nev);
+    atomicAdd(&out.counters[kCtStKeys], nkeys);
+    atomicAdd(&out.counters[kCtStBatches], 1u);
+    atomicMax(&out.counters[kCtStMaxKeys], nkeys);
+    atomicMax(&out.counters[kCtStMaxEvents], nev);
     atomicAdd(&g_kr_stats[32u + stat_log2(nkeys)], 1u);
     atomicAdd(&g_kr_stats[64u + stat_log2(nrec)], 1u);
     atomicAdd(&g_kr_stats[96], 1u);
@@ -846,7 +846,7 @@ __device__ __forceinline__ bool process_read(const DevIndex& ix, const DevParams
   auto set_aside = [&]() {
     if (ws.ll_next == ws.ll_end) {
       uint32_t base = 0;
-      if (lane == 0) base = atomicAdd(&out.counters[25], 16u);
+      if (lane == 0) base = atomicAdd(&out.counters[kCtLongReads], 16u);
       ws.ll_next = __shfl(base, 0);
       ws.ll_end = ws.ll_next + 16u;
     }
@@ -989,7 +989,7 @@ __device__ __forceinline__ bool process_read(const DevIndex& ix, const DevParams
     }
   }
   if (MULTI) segment_done();
-  if (ws.err && lane == 0) atomicOr(&out.counters[1], ws.err);
+  if (ws.err && lane == 0) atomicOr(&out.counters[kCtErr], ws.err);
   ws.err = 0;
   if (MULTI && !ws.evmode) break;
   if (multi) {
@@ -1013,8 +1013,8 @@ __device__ __forceinline__ bool process_read(const DevIndex& ix, const DevParams
                                       finalize_events<false, PB>(ix, out, A, ws, hist_tbl, hist_words, read, onmers, filt0, filt1, P.dbg));
   if ((P.dbg & 512u) && lane == 0) {
     const uint64_t tf1 = __builtin_readcyclecounter();
-    atomicAdd(&out.counters[17], (uint32_t)((tf1 - tf0) >> 6));
-    atomicAdd(&out.counters[18], (uint32_t)((tf1 - tr0) >> 6));
+    atomicAdd(&out.counters[kCtCycFinalize], (uint32_t)((tf1 - tf0) >> 6));
+    atomicAdd(&out.counters[kCtCycRead], (uint32_t)((tf1 - tr0) >> 6));
     if (KR_STATS) atomicAdd(&g_kr_stats[stat_log2(ws.nev)], 1u);
     if (KR_STATS && !fin_ok) atomicAdd(&g_kr_stats[ws.ev_full ? 98 : 99], 1u);
   }
@@ -1226,7 +1226,7 @@ __global__ __launch_bounds__(kWave, (MULTI || PB == 8 ? 4 : KR_ACC_LEAN_WPE)) vo
   ws.gkt_cap = out.kt_spill;
   ReadCursor rc;
   // later launches: the reads the first one set aside (their number is final: kernel boundary)
-  rc.init(out.cursors + (MULTI ? 2u : (PB == 8 ? 3u : 1u)) * kCursors * kCursorStride, LISTED ? out.counters[25] : in.nreads, blockIdx.x, 8u);
+  rc.init(out.cursors + (MULTI ? kCurAccMerge : (PB == 8 ? kCurAcc2 : kCurAcc1)) * kCursors * kCursorStride, LISTED ? out.counters[kCtLongReads] : in.nreads, blockIdx.x, 8u);
   uint32_t r0, r1;
   while (rc.next(r0, r1))
     for (uint32_t r = r0; r < r1; ++r)
@@ -1243,8 +1243,8 @@ __global__ __launch_bounds__(kWave, (MULTI || PB == 8 ? 4 : KR_ACC_LEAN_WPE)) vo
       }
     }
   for (uint32_t q = ws.ll_next + lane_id(); q < ws.ll_end; q += 64) out.long_list[q] = 0xFFFFFFFFu;
-  if (ws.n_l2 && lane_id() == 0) atomicAdd(&out.counters[2], ws.n_l2);
-  if (ws.n_rec && lane_id() == 0) atomicAdd(&out.counters[4], ws.n_rec);
-  if (ws.n_spill && lane_id() == 0) atomicAdd(&out.counters[26], ws.n_spill);
+  if (ws.n_l2 && lane_id() == 0) atomicAdd(&out.counters[kCtL2Reads], ws.n_l2);
+  if (ws.n_rec && lane_id() == 0) atomicAdd(&out.counters[kCtRecords], ws.n_rec);
+  if (ws.n_spill && lane_id() == 0) atomicAdd(&out.counters[kCtStackSpills], ws.n_spill);
 }
 

@@ -106,11 +106,43 @@ struct DevParams {
   double chisq, dist_max;
 };
 
+// Slots of BatchOut::counters: the words a batch's kernels share, one set per lane, cleared before the lane's first kernel and
+// copied to the host behind its last.  Behind every meaning: how kr_batch_wait combines the lanes' values (kCounterRules in
+// kr_host_stream.inc) -- sum, max, or -- or "lane": read per lane, never combined.
+enum CounterSlot : uint32_t {
+  kCtRecSlots = 0,      // record slots handed out, in chunks (beyond rec_cap: the lane is over capacity) -- lane
+  kCtErr = 1,           // error flags (kErr* below) -- or
+  kCtL2Reads = 2,       // reads that used the level-2 (global) accumulator: kr_timing.overflow_reads -- sum
+  kCtTapHits = 3,       // hits written to the tap (KR_TAP_HITS), beyond hit_cap too -- sum
+  kCtRecords = 4,       // records written -- sum
+  kCtLlhCursor = 5,     // chunk cursor of kr_llh_kernel over the distinct problems -- lane
+  kCtItemSlots = 6,     // item slots handed out by the scan -- lane
+  // KR_DEBUG_SKIP=512 statistics of the accumulate kernel ([kr stats])
+  kCtStEvents = 9,      // events -- sum
+  kCtStKeys = 10,       // keys -- sum
+  kCtStBatches = 11,    // key batches -- sum
+  kCtStBig = 12,        // reads beyond the LDS event region -- sum
+  kCtStLevelTiles = 13, // level passes x event tiles -- sum
+  kCtStMaxKeys = 14,    // most keys of a read -- max
+  kCtStMaxEvents = 15,  // most events of a read -- max
+  kCtCycLevel = 16,     // wave cycles / 64 in the level passes -- sum
+  kCtCycFinalize = 17,  // ... in the epilogue of a read -- sum
+  kCtCycRead = 18,      // ... in a whole read -- sum
+  kCtProblems = 22,     // distinct likelihood problems = positions of rep_list handed out, in chunks -- sum
+  kCtLongReads = 25,    // entries of long_list (reads of several segments, set aside by the first accumulate launch) -- lane
+  kCtStackSpills = 26,  // work stacks that outgrew the LDS: kr_timing.stack_spills -- sum
+  kCtRows = 27,         // output rows (rows_mode) -- lane
+  kCtTileHoles = 28,    // records of tiles that became holes (tiled batches) -- sum
+  kCtCount = 29
+};
+constexpr uint32_t kCounterWords = (kCtCount + 31u) & ~31u; // words allocated, cleared and copied per lane: whole 128-byte lines
+// Sets of BatchOut::cursors (kCursors * kCursorStride words each, kr_dev_scan.inc): every launch that hands out reads has its own
+enum CursorSet : uint32_t { kCurScan = 0, kCurAcc1 = 1 /* one segment */, kCurAccMerge = 2 /* several */, kCurAcc2 = 3 /* two segments */, kCurSets = 4 };
+
 // Everything the kernels write for one batch.
 struct BatchOut {
-  uint32_t* counters;    // [0] record slots handed out  [1] error flags  [2] reads that used level 2  [3] nhits(tap)  [4] records
-                         // [5] LLH chunk cursor  [6] item slots handed out  [22] distinct likelihood problems  [27] output rows (rows_mode)
-  uint32_t* cursors;     // read cursors of the scan and the accumulate kernel, [2][kCursors * kCursorStride]
+  uint32_t* counters;    // [kCounterWords] indexed by CounterSlot
+  uint32_t* cursors;     // read cursors of the scan and the accumulate launches, [kCurSets][kCursors * kCursorStride]
   uint32_t* rd_off;
   uint32_t* rd_cnt;
   uint32_t* rd_onmers;
@@ -173,13 +205,13 @@ struct BatchOut {
   // rows-only batch)
   uint32_t rows_indexed;
   uint32_t* row_dix;     // [rec_cap]
-  double* dist_list;     // [counters[22]]
+  double* dist_list;     // [counters[kCtProblems]]
   uint32_t item_cap;
   uint32_t* rd_it_off;
   uint32_t* rd_it_cnt;
   uint32_t rec_chunk;    // record slots a wave takes at a time: kRecChunk for large batches; small ones take less (every
                          // resident wave leaves a partly used chunk behind, and the host copies slots, not records)
-  uint32_t* long_list;   // [max_reads] reads of several segments, set aside by the first accumulate launch (counters[25])
+  uint32_t* long_list;   // [max_reads] reads of several segments, set aside by the first accumulate launch (counters[kCtLongReads])
   // level-2 accumulator scratch, one region per resident wave
   uint32_t* g_planes; // [nwaves][nslots2][np][4]
   uint32_t* g_counts; // [nwaves][nslots2][np]

@@ -408,10 +408,10 @@ __device__ __forceinline__ uint32_t alloc_records(const BatchOut& out, WaveState
 {
   if (ws.rec_next + n > ws.rec_end) {
     uint32_t chunk = max(n, out.rec_chunk), base = 0;
-    if (lane_id() == 0) base = atomicAdd(&out.counters[0], chunk);
+    if (lane_id() == 0) base = atomicAdd(&out.counters[kCtRecSlots], chunk);
     base = __shfl(base, 0);
     if ((uint64_t)base + chunk > out.rec_cap) {
-      if (lane_id() == 0) atomicOr(&out.counters[1], kErrRecCap);
+      if (lane_id() == 0) atomicOr(&out.counters[kCtErr], kErrRecCap);
       return 0xFFFFFFFFu;
     }
     ws.rec_next = base;

@@ -316,7 +316,7 @@ constexpr uint32_t kRepSlack = kDedupBlocks * 4u * kRepChunkMax; // list positio
 #endif
 __device__ __forceinline__ uint32_t dd_mask(const BatchOut& out)
 { // table slots used for this batch: a power of two >= (number of record slots) >> dd_shift, at most dd_slots
-  const uint32_t n = min(out.counters[0], out.rec_cap);
+  const uint32_t n = min(out.counters[kCtRecSlots], out.rec_cap);
   uint32_t m = 1024;
   while (m < out.dd_slots && m < (n >> out.dd_shift)) m <<= 1;
   return m - 1u;
@@ -371,7 +371,7 @@ __global__ __launch_bounds__(256) void kr_dedup_oslot_kernel(BatchOut out, uint3
 }
 __global__ __launch_bounds__(256) void kr_dedup_kernel(BatchOut out)
 {
-  const uint32_t nrec = min(out.counters[0], out.rec_cap);
+  const uint32_t nrec = min(out.counters[kCtRecSlots], out.rec_cap);
   const uint32_t mask = dd_mask(out);
   unsigned long long* tab = reinterpret_cast<unsigned long long*>(out.dd_table);
   // Once the table is half full a wave stops inserting (look-ups only; new problems stand alone).  The wave learns
@@ -395,10 +395,10 @@ __global__ __launch_bounds__(256) void kr_dedup_kernel(BatchOut out)
       for (uint32_t q = lp_next + lane_id(); q < lp_end; q += 64) out.rep_list[q] = 0xFFFFFFFFu;
       const uint32_t size = max(n, rep_chunk);
       uint32_t base = 0;
-      if (lane_id() == 0) base = atomicAdd(&out.counters[22], size);
+      if (lane_id() == 0) base = atomicAdd(&out.counters[kCtProblems], size);
       base = __shfl(base, 0);
       if ((uint64_t)base + size > out.rep_cap) { // (round-5 advice: the slack covers one unused chunk per wave, not every discarded tail)
-        if (lane_id() == 0) atomicOr(&out.counters[1], kErrRecCap); // the batch is reported as over capacity; nothing is written past the slice
+        if (lane_id() == 0) atomicOr(&out.counters[kCtErr], kErrRecCap); // the batch is reported as over capacity; nothing is written past the slice
         base = 0;
       }
       lp_next = base, lp_end = base + size;
@@ -545,8 +545,8 @@ __global__ __launch_bounds__(256) void kr_dedup_direct_kernel(BatchOut out)
     __syncthreads();
     if (threadIdx.x == 0) {
       const uint32_t tot = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-      s_base = tot ? atomicAdd(&out.counters[22], tot) : 0u;
-      if ((uint64_t)s_base + tot > out.rep_cap) atomicOr(&out.counters[1], kErrRecCap), s_base = 0; // (see take_positions)
+      s_base = tot ? atomicAdd(&out.counters[kCtProblems], tot) : 0u;
+      if ((uint64_t)s_base + tot > out.rep_cap) atomicOr(&out.counters[kCtErr], kErrRecCap), s_base = 0; // (see take_positions)
     }
     __syncthreads();
     uint32_t at = s_base + inc - cnt;
@@ -630,7 +630,7 @@ __global__ __launch_bounds__(256) void kr_llh_pre_kernel(LlhConst C, DevIndex ix
   }
   __syncthreads();
   const LlhShared g0{s_g[0][0], s_g[0][1], s_g[0][2]}, g1{s_g[1][0], s_g[1][1], s_g[1][2]};
-  const uint32_t nrep = min(out.counters[22], out.rep_cap); // (beyond the slice: the batch has been flagged, take_positions)
+  const uint32_t nrep = min(out.counters[kCtProblems], out.rep_cap); // (beyond the slice: the batch has been flagged, take_positions)
   for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < nrep; j += gridDim.x * blockDim.x) {
     const uint32_t i = out.rep_list[j];
     if (i == 0xFFFFFFFFu) continue; // hole at the end of a wave's chunk of list positions
@@ -648,7 +648,7 @@ __global__ __launch_bounds__(256) void kr_llh_pre_kernel(LlhConst C, DevIndex ix
 
 // One record per lane, refilled: a lane whose minimisation has converged stores its result and, once
 // kLlhRefill lanes are idle, the idle lanes take the next records of the wave's current chunk (chunks of
-// kLlhChunk records are handed out through counters[5]) together with their first two objective values.
+// kLlhChunk records are handed out through counters[kCtLlhCursor]) together with their first two objective values.
 // Every step evaluates the objective once for all busy lanes.
 #ifndef KR_LLH_REFILL
 #define KR_LLH_REFILL 8
@@ -660,7 +660,7 @@ constexpr uint32_t kLlhChunkMax = 2048, kLlhRefill = KR_LLH_REFILL;
 template <int NPT>
 __device__ __forceinline__ void llh_records(const LlhConst& C, const LlhTables& T, const DevIndex& ix, const BatchOut& out)
 {
-  const uint32_t nrec = min(out.counters[22], out.rep_cap); // distinct problems (rep_list)
+  const uint32_t nrec = min(out.counters[kCtProblems], out.rep_cap); // distinct problems (rep_list)
   const uint32_t lane = lane_id();
   const uint64_t lt = (1ull << lane) - 1ull;
   // chunk size: about four chunks per wave, 64 .. kLlhChunkMax records
@@ -686,7 +686,7 @@ __device__ __forceinline__ void llh_records(const LlhConst& C, const LlhTables& 
     if (idle != 0 && (more || next < end) && ((uint32_t)__popcll(idle) >= kLlhRefill || idle == __ballot(true))) {
       if (next == end) {
         uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(&out.counters[5], kLlhChunk);
+        if (lane == 0) base = atomicAdd(&out.counters[kCtLlhCursor], kLlhChunk);
         base = __shfl(base, 0);
         next = min(base, nrec);
         end = min(base + kLlhChunk, nrec);
@@ -1283,7 +1283,7 @@ __global__ __launch_bounds__(256) void kr_rows_bsum_kernel(BatchOut out, uint32_
   }
 }
 __global__ __launch_bounds__(1024) void kr_rows_bscan_kernel(BatchOut out, uint32_t nreads)
-{ // one workgroup: exclusive prefix of row_bsum in place, the total into counters[27]
+{ // one workgroup: exclusive prefix of row_bsum in place, the total into counters[kCtRows]
   __shared__ uint32_t s_w[16];
   __shared__ uint32_t s_run;
   const uint32_t nb = (nreads + kRowBlock - 1u) / kRowBlock, lane = lane_id(), w = threadIdx.x >> 6;
@@ -1302,13 +1302,13 @@ __global__ __launch_bounds__(1024) void kr_rows_bscan_kernel(BatchOut out, uint3
     if (threadIdx.x == 1023u) s_run = base + inc;
     __syncthreads();
   }
-  if (threadIdx.x == 0) out.counters[27] = s_run;
+  if (threadIdx.x == 0) out.counters[kCtRows] = s_run;
 }
 // INDEXED (KR_ROWS_INDEXED): the row's DIST as the position of its problem in the batch's list of distinct problems
 // (kr_rows_dlist_kernel makes that list dense: dist_list[pos] = rep_dv[pos].x)
 __global__ __launch_bounds__(256) void kr_rows_dlist_kernel(BatchOut out)
 {
-  const uint32_t n = min(out.counters[22], out.rec_cap);
+  const uint32_t n = min(out.counters[kCtProblems], out.rec_cap);
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) out.dist_list[i] = out.rep_dv[i].x;
 }
 template <bool INDEXED>

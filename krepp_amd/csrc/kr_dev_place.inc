@@ -24,15 +24,35 @@
 constexpr uint32_t kPlLeaves = 256;  // leaves of one read the LDS arrays hold (more: the read goes to the second launch, arrays in global scratch)
 constexpr uint32_t kPlNodes = 1024;  // distinct ancestors of one read
 #ifndef KR_PLACE_PROF
-#define KR_PLACE_PROF 0 // 1: cycles / 256 per phase of place_read into cnt[4..9] (experiments)
+#define KR_PLACE_PROF 0 // 1: cycles / 256 per phase of place_read into kPlProf0 .. + 5 (experiments)
 #endif
 constexpr uint32_t kPlBlock = 8;     // leaves of its run an ancestor's lane handles at a time
 constexpr uint32_t kPlCnt = 32;      // words between two of PlaceOut::cnt's counters: a 128-byte line each (atomics on words of ONE line serialise
                                      // in its L2 channel at ~90 M/s, and the first launch makes ~200,000 of them per 400,000 reads)
+enum PlaceCnt : uint32_t { // the counters of PlaceOut::cnt (pl_cnt below), cleared per range and copied to the host behind its kernels
+  kPlCandSlots = 0,    // candidate slots handed out (beyond cap: what the reads asked for)
+  kPlFlags = 1,        // PlaceFlag bits
+  kPlHeavySlots = 2,   // slots of the heavy list handed out, in chunks of 8
+  kPlKept = 3,         // kept candidates' slots handed out by the compaction (beyond kcap likewise)
+  kPlProf0 = 4,        // .. 9: KR_PLACE_PROF cycles / 256 of place_read's six phases (KR_PL_MARK)
+  kPlReadsOut = 10,    // reads handed out to the waves of the first launch
+  kPlBigListed = 11,   // reads with many records, listed by kr_place_big_first_kernel
+  kPlListSlots = 12,   // entries of the internal candidates' list handed out (k_se until the compaction)
+  kPlBigOut = 13,      // ... of the listed big reads handed out
+  kPlInlineReads = 14, // reads beyond the LDS arrays done at once in global scratch by the first launch
+  kPlCntCount = 16     // lines allocated
+};
+enum PlaceFlag : uint32_t {
+  kPlFlagLimits = 1u,  // a read exceeded even the global arrays (cannot happen: they hold the whole tree)
+  kPlFlagCandCap = 2u, // out of candidate slots
+  kPlFlagKeepCap = 4u, // out of slots for the kept candidates
+  kPlFlagListCut = 8u  // the internal candidates' list is incomplete: kr_place_llh_kernel minimises them itself (no error)
+};
+__host__ __device__ __forceinline__ uint32_t& pl_cnt(uint32_t* cnt, uint32_t slot) { return cnt[kPlCnt * slot]; }
 #ifndef KR_PL_READ_CHUNK
 #define KR_PL_READ_CHUNK 4
 #endif
-constexpr uint32_t kPlReadChunk = KR_PL_READ_CHUNK; // reads a wave of the first launch takes at a time (PlaceOut::cnt[10])
+constexpr uint32_t kPlReadChunk = KR_PL_READ_CHUNK; // reads a wave of the first launch takes at a time (kPlReadsOut)
 constexpr uint32_t kPlChain = 8192; // (leaf, ancestor) weights of one read held in the wave's global scratch (more: they are recomputed by walking up)
 constexpr uint32_t kPlChunk = 128;   // candidate slots a wave takes at a time (every wave leaves part of one unused: the host copies slots)
 
@@ -56,9 +76,7 @@ struct PlaceOut {
   double* c_chisq;
   double* c_prob;   // [cap][np + 2] internal candidates: fractional histogram, mismatch count, rho
   double* r_prob;   // [nreads][np + 3] the read's closest leaf: histogram, mismatch count, rho, v_llh
-  uint32_t* cnt;    // [0] candidate slots handed out  [1] flags: 1 = a read exceeded the limits, 2 = out of slots
-                    // [2] slots of the heavy list handed out  [3] kept candidates  [10] reads handed out (first launch)
-                    // [12] entries of the internal candidates' list handed out (k_se until the compaction); flag 8: that list is incomplete
+  uint32_t* cnt;    // [kPlCntCount lines of kPlCnt words] indexed by PlaceCnt through pl_cnt
   uint32_t cap;
   // reads with more leaves / ancestors than the LDS arrays hold: listed by the first launch, done by the second one with its
   // arrays in global scratch (per wave: 4 * heavy_leaves + heavy_nodes words, 2 * heavy_leaves doubles)
@@ -68,7 +86,7 @@ struct PlaceOut {
   uint32_t heavy_leaves, heavy_nodes;
   uint32_t lds_leaves, lds_nodes; // what the first launch accepts (<= kPlLeaves / kPlNodes; smaller in tests: KR_DEBUG_PLACE_LDS)
   // kr_place_compact_kernel: the candidates that pass the chi-square test (src/query.cpp:276-277), read after read, without gaps;
-  // cnt[3] = slots handed out.  These are what the host copies back.
+  // kPlKept = slots handed out.  These are what the host copies back.
   uint32_t* k_se;
   double* k_d;
   double* k_v;
@@ -78,10 +96,10 @@ struct PlaceOut {
   uint32_t chain_cap;
   uint32_t chain_cap_heavy; // the second launch has fewer waves: each takes a larger piece of the same buffer
   uint32_t heavy_in_lds;    // the second launch's arrays are its dynamic LDS (32 * heavy_leaves + 4 * heavy_nodes bytes), not global scratch
-  // reads with many records FIRST (kr_place_big_first_kernel lists them: heavy[big_off ..], cnt[11] entries; cnt[13]: handed out): the
+  // reads with many records FIRST (kr_place_big_first_kernel lists them: heavy[big_off ..], kPlBigListed entries; kPlBigOut: handed out): the
   // waves of the first launch that own a piece of the global scratch (blockIdx.x < inline_waves) start with them and, where a read
   // exceeds the LDS arrays, do it at once in that scratch -- the reads that used to make up the second launch (2.5 ms with a
-  // handful of waves busy) run beside everybody else's ordinary reads.  cnt[14]: reads done that way.
+  // handful of waves busy) run beside everybody else's ordinary reads.  kPlInlineReads: reads done that way.
   uint32_t big_off, big_min_records, inline_waves;
   double* chain_inline;      // [inline_waves][chain_inline_cap]: the weights of a read such a wave does in global scratch
   uint32_t chain_inline_cap;
@@ -141,7 +159,7 @@ __device__ __forceinline__ bool place_read(const LlhConst& C, const DevIndex& ix
   uint32_t info = 0, c0 = 0;
 #if KR_PLACE_PROF
   uint64_t tp = __builtin_readcyclecounter();
-#define KR_PL_MARK(k) do { const uint64_t t_ = __builtin_readcyclecounter(); if (lane == 0) atomicAdd(&po.cnt[kPlCnt * (4 + (k))], (uint32_t)((t_ - tp) >> 8)); tp = t_; } while (0)
+#define KR_PL_MARK(k) do { const uint64_t t_ = __builtin_readcyclecounter(); if (lane == 0) atomicAdd(&pl_cnt(po.cnt, kPlProf0 + (k)), (uint32_t)((t_ - tp) >> 8)); tp = t_; } while (0)
 #else
 #define KR_PL_MARK(k) do {} while (0)
 #endif
@@ -205,11 +223,11 @@ __device__ __forceinline__ bool place_read(const LlhConst& C, const DevIndex& ix
   if (go && nl == 1) { // src/query.cpp:233-244: the placement is the closest leaf
     if (c_pos + 1 > c_end) {
       uint32_t b = 0;
-      if (lane == 0) b = atomicAdd(&po.cnt[kPlCnt * (0)], kPlChunk);
+      if (lane == 0) b = atomicAdd(&pl_cnt(po.cnt, kPlCandSlots), kPlChunk);
       c_pos = __shfl(b, 0, 64), c_end = c_pos + kPlChunk;
     }
     if (c_end > po.cap) {
-      if (lane == 0) atomicOr(&po.cnt[kPlCnt * (1)], 2u);
+      if (lane == 0) atomicOr(&pl_cnt(po.cnt, kPlFlags), kPlFlagCandCap);
     } else {
       c0 = c_pos;
       if (lane == 0)
@@ -341,11 +359,11 @@ __device__ __forceinline__ bool place_read(const LlhConst& C, const DevIndex& ix
     if (c_pos + need > c_end) {
       const uint32_t take = 4u * need > kPlChunk ? 4u * need : kPlChunk; // (a read keeps only what it emits: the rest serves the wave's next reads)
       uint32_t b = 0;
-      if (lane == 0) b = atomicAdd(&po.cnt[kPlCnt * (0)], take);
+      if (lane == 0) b = atomicAdd(&pl_cnt(po.cnt, kPlCandSlots), take);
       c_pos = __shfl(b, 0, 64), c_end = c_pos + take;
     }
     if (c_end > po.cap) {
-      if (lane == 0) atomicOr(&po.cnt[kPlCnt * (1)], 2u);
+      if (lane == 0) atomicOr(&pl_cnt(po.cnt, kPlFlags), kPlFlagCandCap);
       go = false;
     }
   }
@@ -464,10 +482,10 @@ __device__ __forceinline__ bool place_read(const LlhConst& C, const DevIndex& ix
           for (uint32_t q = i_pos + lane; q < i_end; q += kWave) po.k_se[q] = 0xFFFFFFFFu; // the rest of the old chunk: unused
           const uint32_t take = tot > kPlChunk ? tot : kPlChunk;
           uint32_t b = 0;
-          if (lane == 0) b = atomicAdd(&po.cnt[kPlCnt * (12)], take);
+          if (lane == 0) b = atomicAdd(&pl_cnt(po.cnt, kPlListSlots), take);
           i_pos = __shfl(b, 0, 64), i_end = i_pos + take;
           if (i_end > po.lcap) { // (cannot happen with the sizes kr_host_place.inc gives the list: then the likelihood kernel minimises by itself)
-            if (lane == 0) atomicOr(&po.cnt[kPlCnt * (1)], 8u);
+            if (lane == 0) atomicOr(&pl_cnt(po.cnt, kPlFlags), kPlFlagListCut);
             i_pos = i_end = 0;
           }
         }
@@ -503,14 +521,14 @@ __global__ __launch_bounds__(256) void kr_place_big_first_kernel(BatchOut o, uin
     const uint32_t pre = wave_prefix_excl(big, tot);
     if (tot == 0) continue;
     uint32_t b = 0;
-    if (lane_id() == 0) b = atomicAdd(&po.cnt[kPlCnt * (11)], tot);
+    if (lane_id() == 0) b = atomicAdd(&pl_cnt(po.cnt, kPlBigListed), tot);
     b = __shfl(b, 0, 64);
     if (big) po.heavy[po.big_off + b + pre] = r;
   }
 }
 
 // HEAVY = false: every read of the batch, arrays in LDS; a read with more leaves or ancestors than they hold is put on the
-// heavy list (po.heavy, counted in po.cnt[kPlCnt * (2)]).  HEAVY = true (second launch): the listed reads, arrays in the wave's
+// heavy list (po.heavy, counted in pl_cnt(po.cnt, kPlHeavySlots)).  HEAVY = true (second launch): the listed reads, arrays in the wave's
 // global scratch, sized for the whole tree.
 template <bool HEAVY, int NPT>
 __global__ __launch_bounds__(kWave) void kr_place_kernel(LlhConst C, DevIndex ix, BatchOut o, uint32_t nreads, const uint32_t* read_len,
@@ -543,12 +561,12 @@ __global__ __launch_bounds__(kWave) void kr_place_kernel(LlhConst C, DevIndex ix
       if (has_scratch) {
         ++n_inline;
         if (!place_read<PlaceGlobalMem, NPT>(C, ix, o, r, read_len, T, po, tau, no_filter, AG, (lds_u32*)&s_n, c_pos, c_end, i_pos, i_end, po.chain_inline + (uint64_t)blockIdx.x * po.chain_inline_cap, po.chain_inline_cap))
-          if (lane_id() == 0) atomicOr(&po.cnt[kPlCnt * (1)], 1u); // (cannot happen: the arrays hold the whole tree)
+          if (lane_id() == 0) atomicOr(&pl_cnt(po.cnt, kPlFlags), kPlFlagLimits); // (cannot happen: the arrays hold the whole tree)
         return;
       }
       if (h_pos == h_end) {
         uint32_t b = 0;
-        if (lane_id() == 0) b = atomicAdd(&po.cnt[kPlCnt * (2)], 8u);
+        if (lane_id() == 0) b = atomicAdd(&pl_cnt(po.cnt, kPlHeavySlots), 8u);
         h_pos = __shfl(b, 0, 64), h_end = h_pos + 8u;
       }
       if (lane_id() == 0) po.heavy[h_pos] = r;
@@ -556,10 +574,10 @@ __global__ __launch_bounds__(kWave) void kr_place_kernel(LlhConst C, DevIndex ix
     };
     // ---- the reads with many records first (their number is final: kr_place_big_first_kernel ran before this launch)
     if (has_scratch) {
-      const uint32_t nbig = po.cnt[kPlCnt * (11)];
+      const uint32_t nbig = pl_cnt(po.cnt, kPlBigListed);
       for (;;) {
         uint32_t j = 0;
-        if (lane_id() == 0) j = atomicAdd(&po.cnt[kPlCnt * (13)], 1u);
+        if (lane_id() == 0) j = atomicAdd(&pl_cnt(po.cnt, kPlBigOut), 1u);
         j = (uint32_t)__builtin_amdgcn_readfirstlane((int)__shfl(j, 0, 64));
         if (j >= nbig) break;
         one_read((uint32_t)__builtin_amdgcn_readfirstlane((int)po.heavy[po.big_off + j]));
@@ -571,7 +589,7 @@ __global__ __launch_bounds__(kWave) void kr_place_kernel(LlhConst C, DevIndex ix
     for (;;) {
       if (r_pos == r_end) {
         uint32_t b = 0;
-        if (lane_id() == 0) b = atomicAdd(&po.cnt[kPlCnt * (10)], kPlReadChunk);
+        if (lane_id() == 0) b = atomicAdd(&pl_cnt(po.cnt, kPlReadsOut), kPlReadChunk);
         r_pos = (uint32_t)__builtin_amdgcn_readfirstlane((int)__shfl(b, 0, 64)), r_end = min(r_pos + kPlReadChunk, nreads);
         if (r_pos >= nreads) break;
       }
@@ -580,7 +598,7 @@ __global__ __launch_bounds__(kWave) void kr_place_kernel(LlhConst C, DevIndex ix
       one_read(r);
     }
     for (uint32_t q = h_pos + lane_id(); q < h_end; q += 64) po.heavy[q] = 0xFFFFFFFFu; // unused list slots
-    if (n_inline && lane_id() == 0) atomicAdd(&po.cnt[kPlCnt * (14)], n_inline);
+    if (n_inline && lane_id() == 0) atomicAdd(&pl_cnt(po.cnt, kPlInlineReads), n_inline);
   } else if (po.heavy_in_lds) {
     // the whole tree's worth of arrays fits a workgroup's LDS (trees of a few thousand nodes): the same code as the first launch, at
     // LDS latency -- in global scratch a heavy read's passes (the rank-by-counting sort above all: leaves^2 loads) took milliseconds
@@ -589,12 +607,12 @@ __global__ __launch_bounds__(kWave) void kr_place_kernel(LlhConst C, DevIndex ix
     lds_f64* f = (lds_f64*)(KR_LDS uint8_t*)s_hv;
     lds_u32* u = (lds_u32*)(f + 2u * hl);
     PlaceArrays<PlaceLdsMem> A{u, u + hl, u + 2u * hl, u + 3u * hl, f, f + hl, u + 4u * hl, hl, hn};
-    const uint32_t nh = po.cnt[kPlCnt * (2)];
+    const uint32_t nh = pl_cnt(po.cnt, kPlHeavySlots);
     for (uint32_t j = blockIdx.x; j < nh; j += gridDim.x) {
       const uint32_t r = (uint32_t)__builtin_amdgcn_readfirstlane((int)po.heavy[j]);
       if (r == 0xFFFFFFFFu) continue;
       if (!place_read<PlaceLdsMem, NPT>(C, ix, o, r, read_len, T, po, tau, no_filter, A, (lds_u32*)&s_n, c_pos, c_end, i_pos, i_end, po.chain + (uint64_t)blockIdx.x * po.chain_cap_heavy, po.chain_cap_heavy))
-        if (lane_id() == 0) atomicOr(&po.cnt[kPlCnt * (1)], 1u); // (cannot happen: the arrays hold the whole tree)
+        if (lane_id() == 0) atomicOr(&pl_cnt(po.cnt, kPlFlags), kPlFlagLimits); // (cannot happen: the arrays hold the whole tree)
     }
   } else {
     const uint64_t w = blockIdx.x;
@@ -602,12 +620,12 @@ __global__ __launch_bounds__(kWave) void kr_place_kernel(LlhConst C, DevIndex ix
     double* sd = po.heavy_f64 + w * (2ull * po.heavy_leaves);
     PlaceArrays<PlaceGlobalMem> A{su, su + po.heavy_leaves, su + 2ull * po.heavy_leaves, su + 3ull * po.heavy_leaves,
                                   sd, sd + po.heavy_leaves, su + 4ull * po.heavy_leaves, po.heavy_leaves, po.heavy_nodes};
-    const uint32_t nh = po.cnt[kPlCnt * (2)];
+    const uint32_t nh = pl_cnt(po.cnt, kPlHeavySlots);
     for (uint32_t j = blockIdx.x; j < nh; j += gridDim.x) {
       const uint32_t r = (uint32_t)__builtin_amdgcn_readfirstlane((int)po.heavy[j]);
       if (r == 0xFFFFFFFFu) continue;
       if (!place_read<PlaceGlobalMem, NPT>(C, ix, o, r, read_len, T, po, tau, no_filter, A, (lds_u32*)&s_n, c_pos, c_end, i_pos, i_end, po.chain + (uint64_t)blockIdx.x * po.chain_cap_heavy, po.chain_cap_heavy))
-        if (lane_id() == 0) atomicOr(&po.cnt[kPlCnt * (1)], 1u); // (cannot happen: the arrays hold the whole tree)
+        if (lane_id() == 0) atomicOr(&pl_cnt(po.cnt, kPlFlags), kPlFlagLimits); // (cannot happen: the arrays hold the whole tree)
     }
   }
   for (uint32_t q = i_pos + lane_id(); q < i_end; q += kWave) po.k_se[q] = 0xFFFFFFFFu; // unused list entries
@@ -623,8 +641,8 @@ __global__ __launch_bounds__(256) void kr_place_brent_kernel(LlhConst C, PlaceOu
   __shared__ double s_bk[32], s_hnk[kMaxPlanes];
   LlhTables LT{(lds_f64*)s_bk, (lds_f64*)s_hnk};
   llh_tables_init(C, LT.bk, LT.hnk);
-  if (po.cnt[kPlCnt * (1)] & 8u) return; // the list is incomplete: kr_place_llh_kernel minimises
-  const uint32_t np = NPT ? (uint32_t)NPT : C.th + 1, nlist = min(po.cnt[kPlCnt * (12)], po.lcap);
+  if (pl_cnt(po.cnt, kPlFlags) & kPlFlagListCut) return; // the list is incomplete: kr_place_llh_kernel minimises
+  const uint32_t np = NPT ? (uint32_t)NPT : C.th + 1, nlist = min(pl_cnt(po.cnt, kPlListSlots), po.lcap);
   for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < nlist; j += gridDim.x * blockDim.x) {
     const uint32_t i = po.k_se[j];
     if (i == 0xFFFFFFFFu) continue;
@@ -645,14 +663,14 @@ __global__ __launch_bounds__(256) void kr_place_llh_kernel(LlhConst C, PlaceOut 
   __shared__ double s_bk[32], s_hnk[kMaxPlanes];
   LlhTables LT{(lds_f64*)s_bk, (lds_f64*)s_hnk};
   llh_tables_init(C, LT.bk, LT.hnk);
-  const uint32_t np = NPT ? (uint32_t)NPT : C.th + 1, used = min(po.cnt[kPlCnt * (0)], po.cap);
+  const uint32_t np = NPT ? (uint32_t)NPT : C.th + 1, used = min(pl_cnt(po.cnt, kPlCandSlots), po.cap);
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < used; i += gridDim.x * blockDim.x) {
     if (po.c_se[i] == 0) continue;
     const uint32_t rk = po.c_read[i], kind = rk >> 30, r = rk & 0x3FFFFFFFu;
     if (kind == 2u) continue;
     double d = 0, v = 0;
     LlhProblem p;
-    if (kind == 1u && !(po.cnt[kPlCnt * (1)] & 8u)) {
+    if (kind == 1u && !(pl_cnt(po.cnt, kPlFlags) & kPlFlagListCut)) {
       d = po.c_d[i]; // (kr_place_brent_kernel's)
     } else if (kind == 1u) {
       const double* cp = po.c_prob + (uint64_t)i * (np + 2u);
@@ -700,11 +718,11 @@ __global__ __launch_bounds__(256) void kr_place_compact_kernel(PlaceOut po, Plac
     if (k_pos + total > k_end) {
       const uint32_t take = total > kPlKeepChunk ? total : kPlKeepChunk;
       uint32_t b = 0;
-      if (lane == 0) b = atomicAdd(&po.cnt[kPlCnt * (3)], take);
+      if (lane == 0) b = atomicAdd(&pl_cnt(po.cnt, kPlKept), take);
       k_pos = __shfl(b, 0, 64), k_end = k_pos + take;
     }
-    if (k_end > po.kcap) { // out of slots for the kept candidates (flag of its own: the host grows THESE arrays from cnt[3] and runs the batch again)
-      if (lane == 0) atomicOr(&po.cnt[kPlCnt * (1)], 4u);
+    if (k_end > po.kcap) { // out of slots for the kept candidates (flag of its own: the host grows THESE arrays from kPlKept and runs the batch again)
+      if (lane == 0) atomicOr(&pl_cnt(po.cnt, kPlFlags), kPlFlagKeepCap);
       continue;
     }
     uint32_t run = 0;
@@ -747,7 +765,6 @@ __global__ __launch_bounds__(256) void kr_place_compact_kernel(PlaceOut po, Plac
 // lanes -- hundreds of microseconds for the 256 reads a wave got with the `dist` text's 1,024-read blocks, whatever the batch
 // (2.3 ms of a 9 ms call at the CLI's 65,536 reads); 64 reads a block put every CU to work on a batch of that size
 constexpr uint32_t kPlTextBlock = 64;
-constexpr uint32_t kPlTextNoRange = 16; // flag of PlaceText::total[1]: nothing was formatted (a range about to be run again), or a node number was out of range
 struct PlaceText {
   const char* ids;           // ids of the range's reads, back to back
   const uint32_t* id_off;    // [nreads + 1]
@@ -759,8 +776,7 @@ struct PlaceText {
   uint64_t* t_bsum;          // [ceil(nreads / kRowBlock) + 1]
   char* text;
   uint64_t text_cap;
-  uint64_t* total;           // [0] bytes  [1] flags: 1 number out of range, 2 more text than text_cap, 8 a tie too close,
-                             // 16 (kPlTextNoRange) the range is not one to format: see kr_place_text_len_kernel
+  uint64_t* total;           // [0] bytes  [1] TextFlag bits (kr_dev_text.inc); kTextNoRange: see kr_place_text_len_kernel
   uint32_t tabular;          // 0 jplace, 1 tabular
   uint32_t multi;
   double chisq;
@@ -777,7 +793,7 @@ struct PlaceNum { // one "%.5f" number: its rounded magnitude and how it prints
   uint32_t len;   // bytes
   uint8_t neg, nan;
 };
-// flags: 1 = not printable here (magnitude >= 1000, infinite); near_tie: the scaled value lies within 1e-8 of a rounding tie
+// flags: kTextBadNum = not printable here (magnitude >= 1000, infinite); near_tie: the scaled value lies within 1e-8 of a rounding tie
 __device__ __forceinline__ PlaceNum place_num_prep(double v, uint32_t& flags, bool& near_tie)
 {
   PlaceNum p{0u, 0u, 0, 0};
@@ -790,7 +806,7 @@ __device__ __forceinline__ PlaceNum place_num_prep(double v, uint32_t& flags, bo
   p.neg = (uint8_t)((__double_as_longlong(v) >> 63) & 1);
   const double av = fabs(v);
   if (!kr::fixed5_exact(av, &p.nn)) {
-    flags |= 1u;
+    flags |= kTextBadNum;
     p.nn = 0;
   }
   const double sc = av * 100000.0, fr = sc - floor(sc);
@@ -843,12 +859,12 @@ __device__ __forceinline__ uint32_t place_read_prepare(const PlaceOut& po, const
   const bool single = ((info >> 30) & 1u) != 0;
   // A node number taken from the kept-candidate arrays indexes the tree's arrays (parent, card, blen, label_off: pn + 1 entries) here
   // and in place_tile_rows, which reads it back from s_se: one that is not a node of the tree is replaced by node 0 and raises
-  // kPlTextNoRange, so that nothing is indexed with it and the host formats the range.  (The compaction writes nodes of the tree
+  // kTextNoRange, so that nothing is indexed with it and the host formats the range.  (The compaction writes nodes of the tree
   // only; the check is what stands between a slot it did not write and a load far outside the arrays.)
   auto node_of = [&](uint32_t raw) -> uint32_t {
     if (raw == 0x7FFFFFFFu) return 0u; // (node 0 of a single placement: 0 itself marks an unused slot)
     if (raw > T.pn) {
-      flags |= kPlTextNoRange;
+      flags |= kTextNoRange;
       return 0u;
     }
     return raw;
@@ -934,7 +950,7 @@ __device__ __forceinline__ uint32_t place_row_len(const PlaceText& tx, const Pla
   if (tx.tabular) {
     pn[0] = place_num_prep(row.lwr, flags, t0);
     pn[1] = place_num_prep(row.d, flags, t1);
-    if (t0) flags |= 8u; // (LWR went through exp)
+    if (t0) flags |= kTextNearTie; // (LWR went through exp)
     const uint32_t ll = tx.label_off[row.se + 1] - tx.label_off[row.se];
     return idl + 1u + (ll ? ll : 2u) + 1u + place_udigits(edge) + 1u + pn[0].len + 1u + pn[1].len + 1u;
   }
@@ -943,7 +959,7 @@ __device__ __forceinline__ uint32_t place_row_len(const PlaceText& tx, const Pla
   pn[2] = place_num_prep(row.negv, flags, t2);
   pn[3] = place_num_prep(row.lwr, flags, t3);
   pn[4] = place_num_prep(row.d, flags, t4);
-  if (t0 || t3) flags |= 8u; // (pendant length through log, LWR through exp)
+  if (t0 || t3) flags |= kTextNearTie; // (pendant length through log, LWR through exp)
   return 1u + place_udigits(edge) + 2u + pn[0].len + 2u + pn[1].len + 2u + pn[2].len + 2u + pn[3].len + 2u + pn[4].len + 1u;
 }
 __device__ __forceinline__ char* place_row_put(char* q, const PlaceText& tx, const PlaceRow& row, const char* id, uint32_t idl, const PlaceNum (&pn)[5])
@@ -996,16 +1012,16 @@ __global__ __launch_bounds__(256) void kr_place_text_len_kernel(PlaceOut po, Pla
 {
   __shared__ uint32_t s_sum[4];
   const uint32_t lane = lane_id(), w = threadIdx.x >> 6;
-  // A range that ran out of candidate slots (flag 2 of cnt[1]) or of slots for the kept ones (4) is about to be run again
+  // A range that ran out of candidate slots (kPlFlagCandCap) or of slots for the kept ones (kPlFlagKeepCap) is about to be run again
   // (place_device_finish), and its per-read words are not the compaction's: a read the compaction skipped for want of slots still
   // names its slots in the c_* arrays, where k_se holds the Brent list's slot numbers and 0xFFFFFFFF markers, not nodes.  Nothing of
-  // such a range is read: every length is 0, so that kr_text_bscan_kernel finds its sums and total[0] defined, and kPlTextNoRange
+  // such a range is read: every length is 0, so that kr_text_bscan_kernel finds its sums and total[0] defined, and kTextNoRange
   // in total[1] keeps the writing kernel out and the empty text from being taken for the range's.  (The flag word is final here:
   // these kernels are queued behind the compaction on the same stream.  The guard stands at the range and not in the compaction --
   // which could clear bit 31 of a read it skips -- because it also covers the reads that found no candidate slots, and saves the
   // sort and the logarithms of every other read of an attempt that is thrown away.)
-  const bool discarded = (po.cnt[kPlCnt * (1)] & (2u | 4u)) != 0;
-  if (discarded && blockIdx.x == 0 && threadIdx.x == 0) atomicOr((unsigned long long*)&tx.total[1], (unsigned long long)kPlTextNoRange);
+  const bool discarded = (pl_cnt(po.cnt, kPlFlags) & (kPlFlagCandCap | kPlFlagKeepCap)) != 0;
+  if (discarded && blockIdx.x == 0 && threadIdx.x == 0) atomicOr((unsigned long long*)&tx.total[1], (unsigned long long)kTextNoRange);
   for (uint32_t b = blockIdx.x; b * kPlTextBlock < nreads; b += gridDim.x) {
     const uint32_t rb = b * kPlTextBlock;
     uint32_t wsum = 0, flags = 0;
@@ -1046,7 +1062,7 @@ __global__ __launch_bounds__(256) void kr_place_text_write_kernel(PlaceOut po, P
 {
   __shared__ uint32_t s_off[kPlTextBlock];
   __shared__ uint32_t s_w[4];
-  if (tx.total[0] > tx.text_cap || (tx.total[1] & ~2ull) != 0) return; // (the host formats this range, or -- kPlTextNoRange -- it is run again)
+  if (tx.total[0] > tx.text_cap || (tx.total[1] & ~(unsigned long long)kTextOverCap) != 0) return; // (the host formats this range, or -- kTextNoRange -- it is run again)
   const uint32_t lane = lane_id(), w = threadIdx.x >> 6;
   for (uint32_t b = blockIdx.x; b * kPlTextBlock < nreads; b += gridDim.x) {
     const uint32_t rb = b * kPlTextBlock, q0 = 4u * threadIdx.x;

@@ -176,7 +176,7 @@ __device__ __forceinline__ bool item_reserve(const BatchOut& out, ScanWave& sw, 
   const uint32_t have = sw.it_next - sw.rd_start;
   const uint32_t size = (have + n + kItemChunk + 15u) & ~15u; // (chunks start on 128-byte lines)
   uint32_t base = 0;
-  if (lane_id() == 0) base = atomicAdd(&out.counters[6], size);
+  if (lane_id() == 0) base = atomicAdd(&out.counters[kCtItemSlots], size);
   base = __shfl(base, 0);
   if ((uint64_t)base + size > out.item_cap) {
     sw.err |= kErrItemCap;
@@ -236,7 +236,7 @@ __device__ __forceinline__ void emit_hits(const DevIndex& ix, const BatchOut& ou
         sw.filt0 = min(sw.filt0, hd);
       if (TAP) {
         const uint32_t se = get_lib<SL>(ix, tag_lib(tg)).se[idx];
-        const uint32_t hix = atomicAdd(&out.counters[3], 1u);
+        const uint32_t hix = atomicAdd(&out.counters[kCtTapHits], 1u);
         if (hix < out.hit_cap) {
           kr_hit h;
           h.read = read;
@@ -248,7 +248,7 @@ __device__ __forceinline__ void emit_hits(const DevIndex& ix, const BatchOut& ou
           h.se = (se >> 30) == 1u ? ix.leaf_se[se & kColMask] : (se & kColMask);
           out.hits[hix] = h;
         } else {
-          atomicOr(&out.counters[1], kErrHitCap);
+          atomicOr(&out.counters[kCtErr], kErrHitCap);
         }
       }
     }
@@ -555,7 +555,7 @@ __global__ __launch_bounds__(kScanWaves* kWave, (SLOT ? KR_SCAN_WPE_SLOT : KR_SC
   sw.stage = (lds_u64*)s_stage[w];
   sw.filt0 = sw.filt1 = 0xFFFFFFFFu;
   ReadCursor rc;
-  rc.init(out.cursors, in.nreads, blockIdx.x * kScanWaves + w);
+  rc.init(out.cursors + kCurScan * kCursors * kCursorStride, in.nreads, blockIdx.x * kScanWaves + w);
   uint32_t r0, r1;
   lds_u32* meta = (lds_u32*)s_meta[w];
   while (rc.next(r0, r1)) {
@@ -570,6 +570,6 @@ __global__ __launch_bounds__(kScanWaves* kWave, (SLOT ? KR_SCAN_WPE_SLOT : KR_SC
     }
     WAVE_SYNC();
   }
-  if (sw.err && lane_id() == 0) atomicOr(&out.counters[1], sw.err);
+  if (sw.err && lane_id() == 0) atomicOr(&out.counters[kCtErr], sw.err);
 }
 

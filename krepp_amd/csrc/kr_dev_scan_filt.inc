@@ -78,7 +78,7 @@ __device__ __forceinline__ void filt_emit(const DevIndex& ix, const DevParams& P
       const uint2 sv = Lb.sx[idx];
       const uint32_t hd = hd12 + hd_rest8(sv.y, qr);
       if (hd <= P.th) {
-        const uint32_t hix = atomicAdd(&out.counters[3], 1u);
+        const uint32_t hix = atomicAdd(&out.counters[kCtTapHits], 1u);
         if (hix < out.hit_cap) {
           kr_hit h;
           h.read = read;
@@ -90,7 +90,7 @@ __device__ __forceinline__ void filt_emit(const DevIndex& ix, const DevParams& P
           h.se = (sv.x >> 30) == 1u ? ix.leaf_se[sv.x & kColMask] : (sv.x & kColMask);
           out.hits[hix] = h;
         } else {
-          atomicOr(&out.counters[1], kErrHitCap);
+          atomicOr(&out.counters[kCtErr], kErrHitCap);
         }
       }
     }
@@ -235,7 +235,7 @@ __global__ __launch_bounds__(kScanWaves* kWave, WPE) void kr_scan_filt_kernel_t(
   sw.stage = (lds_u64*)s_stage[w];
   sw.filt0 = sw.filt1 = 0xFFFFFFFFu;
   ReadCursor rc;
-  rc.init(out.cursors, in.nreads, blockIdx.x * kScanWaves + w);
+  rc.init(out.cursors + kCurScan * kCursors * kCursorStride, in.nreads, blockIdx.x * kScanWaves + w);
   uint32_t r0v, r1v;
   GroupGen<SL, 0> gen;
   uint4 v[DEPTH * 2];
@@ -304,7 +304,7 @@ __global__ __launch_bounds__(kScanWaves* kWave, WPE) void kr_scan_filt_kernel_t(
     }
     WAVE_SYNC();
   }
-  if (sw.err && lane_id() == 0) atomicOr(&out.counters[1], sw.err);
+  if (sw.err && lane_id() == 0) atomicOr(&out.counters[kCtErr], sw.err);
 }
 
 // ---------------------------------------------------------------------------

@@ -337,7 +337,7 @@ __global__ __launch_bounds__(kScanWaves* kWave, WPE) void kr_scan_pipe_kernel_t(
   sw.stage = (lds_u64*)s_stage[w];
   sw.filt0 = sw.filt1 = 0xFFFFFFFFu;
   ReadCursor rc;
-  rc.init(out.cursors, in.nreads, blockIdx.x * kScanWaves + w);
+  rc.init(out.cursors + kCurScan * kCursors * kCursorStride, in.nreads, blockIdx.x * kScanWaves + w);
   uint32_t r0v, r1v;
   GroupGen<SL, KR_SCAN_PIPE_FE> gen;
   gen.tab = (const lds_u32x4*)s_fetab;
@@ -389,5 +389,5 @@ __global__ __launch_bounds__(kScanWaves* kWave, WPE) void kr_scan_pipe_kernel_t(
     }
     WAVE_SYNC();
   }
-  if (sw.err && lane_id() == 0) atomicOr(&out.counters[1], sw.err);
+  if (sw.err && lane_id() == 0) atomicOr(&out.counters[kCtErr], sw.err);
 }

@@ -15,6 +15,13 @@
 // the host formatter's and to the oracle's.  A DIST outside [0, 1000) (never produced by the minimiser, whose bracket is
 // [1e-10, 0.5]) raises a flag and the caller formats that batch on the host.  The text leaves the device as bytes; the host only
 // writes them.
+// Bits of the text kernels' flag word (TextIO::total[1], PlaceText::total[1]); any of them leaves the text to the host
+enum TextFlag : uint32_t {
+  kTextBadNum = 1u,  // a number outside what the device formats exactly
+  kTextOverCap = 2u, // more text than text_cap
+  kTextNearTie = 8u, // `place`: a value too close to a rounding tie after exp / log
+  kTextNoRange = 16u // `place`: nothing was formatted (a range about to be run again), or a node number was out of range
+};
 struct TextIO {
   const char* ids;          // the reads' ids back to back
   const uint32_t* id_off;   // [nreads + 1] id r = ids[id_off[r] .. id_off[r + 1] - id_sep)
@@ -25,7 +32,7 @@ struct TextIO {
   uint64_t* t_bsum;         // [ceil(nreads / kRowBlock) + 1] bytes per block, then (in place) the blocks' first bytes
   char* text;
   uint64_t text_cap;
-  uint64_t* total;          // [0] bytes of the batch's text  [1] flags: 1 = a DIST outside the exact range, 2 = more text than text_cap
+  uint64_t* total;          // [0] bytes of the batch's text  [1] TextFlag bits
 };
 
 // bytes of "%.5f" of d, and its rounded integer; an unprintable d counts as the 7-byte placeholder that nobody will read
@@ -64,7 +71,7 @@ __global__ __launch_bounds__(256) void kr_text_len_kernel(BatchOut out, TextIO t
       if (lane == 0) t.rd_tlen[r] = len;
       wsum += len;
     }
-    if (__ballot(bad) != 0 && lane == 0) atomicOr((unsigned long long*)&t.total[1], 1ull);
+    if (__ballot(bad) != 0 && lane == 0) atomicOr((unsigned long long*)&t.total[1], (unsigned long long)kTextBadNum);
     if (lane == 0) s_sum[w] = wsum;
     __syncthreads();
     if (threadIdx.x == 0) t.t_bsum[b] = (uint64_t)s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
@@ -99,7 +106,7 @@ __global__ __launch_bounds__(1024) void kr_text_bscan_kernel(TextIO t, uint32_t 
   }
   if (threadIdx.x == 0) {
     t.total[0] = s_run;
-    if (s_run > t.text_cap) atomicOr((unsigned long long*)&t.total[1], 2ull);
+    if (s_run > t.text_cap) atomicOr((unsigned long long*)&t.total[1], (unsigned long long)kTextOverCap);
   }
 }
 

@@ -59,7 +59,7 @@ __global__ __launch_bounds__(kWave) void kr_tile_merge_kernel(DevIndex ix, DevPa
   uint32_t* g_bitmap = out.g_planes + w * (uint64_t)out.nslots2 * np * kPlaneWords; // (EMIT_ONLY: the key bitmap kr_tile_add_kernel made)
   for (uint32_t q = lane; q < out.bm_words; q += kWave) bitmap[q] = 0;
   WAVE_SYNC();
-  uint32_t rec_next = 0, rec_end = 0, n_rec = 0, n_hole = 0; // n_hole: records of tiles that became holes (wave-uniform; summed in counters[28], which kr_batch_wait subtracts before it applies max_records)
+  uint32_t rec_next = 0, rec_end = 0, n_rec = 0, n_hole = 0; // n_hole: records of tiles that became holes (wave-uniform; summed in counters[kCtTileHoles], which kr_batch_wait subtracts before it applies max_records)
   for (uint32_t li = blockIdx.x; li < tb.nlong; li += gridDim.x) {
     const uint32_t v0 = tb.longs[2 * li], nt = tb.longs[2 * li + 1];
     // ---- the sequence's hdist_filt (minimum over its tiles, src/query.cpp:366-368) and valid k-mers (src/query.cpp:66)
@@ -142,10 +142,10 @@ __global__ __launch_bounds__(kWave) void kr_tile_merge_kernel(DevIndex ix, DevPa
       if (rec_next + nrec > rec_end) {
         const uint32_t chunk = max(nrec, out.rec_chunk);
         uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(&out.counters[0], chunk);
+        if (lane == 0) base = atomicAdd(&out.counters[kCtRecSlots], chunk);
         base = __shfl(base, 0);
         if ((uint64_t)base + chunk > out.rec_cap) {
-          if (lane == 0) atomicOr(&out.counters[1], kErrRecCap);
+          if (lane == 0) atomicOr(&out.counters[kCtErr], kErrRecCap);
           room = false;
         } else {
           rec_next = base, rec_end = base + chunk;
@@ -187,8 +187,8 @@ __global__ __launch_bounds__(kWave) void kr_tile_merge_kernel(DevIndex ix, DevPa
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     WAVE_SYNC();
   }
-  if (n_rec && lane == 0) atomicAdd(&out.counters[4], n_rec);
-  if (n_hole && lane == 0) atomicAdd(&out.counters[28], n_hole);
+  if (n_rec && lane == 0) atomicAdd(&out.counters[kCtRecords], n_rec);
+  if (n_hole && lane == 0) atomicAdd(&out.counters[kCtTileHoles], n_hole);
 }
 
 // A batch of FEW long sequences (a genome as the query): one merging wave per sequence is the long pole (1.4 ms per Mb).
@@ -222,7 +222,7 @@ __global__ __launch_bounds__(kWave) void kr_tile_add_kernel(DevIndex ix, DevPara
       }
     }
   }
-  if (n_hole && lane == 0) atomicAdd(&out.counters[28], n_hole);
+  if (n_hole && lane == 0) atomicAdd(&out.counters[kCtTileHoles], n_hole);
 }
 
 // per-read results of the real reads (after the selection kernel)

@@ -18,7 +18,8 @@ struct kr_index {
   // Concurrent batches only slow each other down (DESIGN.md: measured), and a pipeline whose stages take turns
   // keeps the chip busy with two streams.
   mutable std::mutex chain_mu;
-  mutable hipEvent_t chain_ev[16] = {nullptr};
+  static constexpr uint32_t kChainEvents = 16;
+  mutable hipEvent_t chain_ev[kChainEvents] = {nullptr};
   mutable uint32_t chain_n = 0;
   mutable bool chain_off = false;
   mutable std::mutex llh_mu;

@@ -123,7 +123,7 @@ int kr::place_device_begin(kr_stream* s, const void* tree_tag, const kr::PlaceTr
     if ((rc = dev_renew(w.d_len, cap)) || (rc = dev_renew(w.d_c0, cap)) || (rc = dev_renew(w.d_info, cap)) || (rc = pin_renew(w.h_len, cap)) ||
         (rc = pin_renew(w.h_c0, cap)) || (rc = pin_renew(w.h_info, cap)))
       return rc;
-    if (!w.d_cnt && ((rc = dev_renew(w.d_cnt, 16 * kPlCnt)) || (rc = pin_renew(w.h_cnt, 16 * kPlCnt)))) return rc;
+    if (!w.d_cnt && ((rc = dev_renew(w.d_cnt, kPlCntCount * kPlCnt)) || (rc = pin_renew(w.h_cnt, kPlCntCount * kPlCnt)))) return rc;
     w.reads_cap = cap;
   }
   // candidate slots: a read may need one per leaf and per distinct ancestor while it is worked on, and keeps what it
@@ -209,7 +209,7 @@ int kr::place_device_launch(kr_stream* s, const kr::PlaceTreeArrays& T, uint32_t
   const bool big_first = !getenv("KR_PLACE_BIG_FIRST") || atoi(getenv("KR_PLACE_BIG_FIRST")) != 0; // 0: every over-limit read through the second launch
   const bool heavy_lds = !heavy_global && (uint64_t)32 * w.heavy_leaves + 4ull * w.heavy_nodes <= 61440ull;
   PlaceTree PT{w.d_parent, w.d_eff, w.d_elig, w.d_lo, w.d_idx_to_pt, w.d_depth, w.d_node, T.pn, T.nidx};
-  HIP_TRY(hipMemsetAsync(w.d_cnt, 0, 64 * kPlCnt, st));
+  HIP_TRY(hipMemsetAsync(w.d_cnt, 0, kPlCntCount * kPlCnt * 4, st));
   HIP_TRY(hipMemsetAsync(w.d_cse, 0, w.cand_cap * 4, st)); // 0 = unused slot: what the second kernel and the host skip
   PlaceOut PO{w.d_c0 + r0, w.d_info + r0, w.d_cse, w.d_cread, w.d_cd, w.d_cv, w.d_cchi, w.d_cprob, w.d_rprob, w.d_cnt, (uint32_t)std::min<uint64_t>(place_cand_slots(w), 0x3FFFFFFFu),
               w.d_heavy, w.d_heavy_u32, w.d_heavy_f64, w.heavy_leaves, w.heavy_nodes, kPlLeaves, kPlNodes,
@@ -255,7 +255,7 @@ int kr::place_device_launch(kr_stream* s, const kr::PlaceTreeArrays& T, uint32_t
     HIP_TRY(hipMemcpyAsync(w.h_ttotal, w.d_ttotal, 16, hipMemcpyDeviceToHost, st));
   }
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(w.h_cnt, w.d_cnt, 64 * kPlCnt, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(w.h_cnt, w.d_cnt, kPlCntCount * kPlCnt * 4, hipMemcpyDeviceToHost, st));
   return KR_OK;
 }
 
@@ -283,19 +283,19 @@ int kr::place_device_finish(kr_stream* s, const kr::PlaceTreeArrays& T, uint32_t
   int attempt = 0;
   for (;; ++attempt) {
     HIP_TRY(hipStreamSynchronize(st));
-    if (!(w.h_cnt[kPlCnt * (1)] & (2u | 4u)) || attempt >= 2) break;
-    // out of candidate slots (bit 1: counters[0] went on counting what the reads asked for) or out of slots for the kept ones
-    // (bit 2: counters[3] went on counting what the compaction handed out)
-    const uint64_t asked = (w.h_cnt[kPlCnt * (1)] & 2u) ? (uint64_t)w.h_cnt[kPlCnt * (0)] + w.h_cnt[kPlCnt * (0)] / 8 + (uint64_t)grid * kPlChunk : place_cand_slots(w);
+    if (!(pl_cnt(w.h_cnt, kPlFlags) & (kPlFlagCandCap | kPlFlagKeepCap)) || attempt >= 2) break;
+    // out of candidate slots (kPlFlagCandCap: kPlCandSlots went on counting what the reads asked for) or out of slots for the kept ones
+    // (kPlFlagKeepCap: kPlKept went on counting what the compaction handed out)
+    const uint64_t asked = (pl_cnt(w.h_cnt, kPlFlags) & kPlFlagCandCap) ? (uint64_t)pl_cnt(w.h_cnt, kPlCandSlots) + pl_cnt(w.h_cnt, kPlCandSlots) / 8 + (uint64_t)grid * kPlChunk : place_cand_slots(w);
     if (asked > 0x3FFFFFFFull) break; // beyond what a slot index can name: the host back end takes the batch
-    if (w.h_cnt[kPlCnt * (1)] & 2u) kr::g_place_paths[kr::kPathRerunCand].fetch_add(1, std::memory_order_relaxed);
-    if (w.h_cnt[kPlCnt * (1)] & 4u) {
+    if (pl_cnt(w.h_cnt, kPlFlags) & kPlFlagCandCap) kr::g_place_paths[kr::kPathRerunCand].fetch_add(1, std::memory_order_relaxed);
+    if (pl_cnt(w.h_cnt, kPlFlags) & kPlFlagKeepCap) {
       kr::g_place_paths[kr::kPathRerunKeep].fetch_add(1, std::memory_order_relaxed);
-      w.keep_want_min = (uint64_t)w.h_cnt[kPlCnt * (3)] + w.h_cnt[kPlCnt * (3)] / 8 + 2048ull * 4ull * kPlKeepChunk;
+      w.keep_want_min = (uint64_t)pl_cnt(w.h_cnt, kPlKept) + pl_cnt(w.h_cnt, kPlKept) / 8 + 2048ull * 4ull * kPlKeepChunk;
     }
     if (!w.dbg_sticky) { // (KR_DEBUG_PLACE_CAPS: the rerun gets what it asked for, as it does from the real sizes)
       if (w.dbg_cand) w.dbg_cand = std::max(w.dbg_cand, asked);
-      if (w.dbg_keep && (w.h_cnt[kPlCnt * (1)] & 4u)) w.dbg_keep = std::max(w.dbg_keep, w.keep_want_min);
+      if (w.dbg_keep && (pl_cnt(w.h_cnt, kPlFlags) & kPlFlagKeepCap)) w.dbg_keep = std::max(w.dbg_keep, w.keep_want_min);
     }
     if ((rc = place_size_candidates(s, asked))) return rc;
     if ((rc = kr::place_device_launch(s, T, r0, n, tau, no_filter, chisq))) return rc;
@@ -303,10 +303,10 @@ int kr::place_device_finish(kr_stream* s, const kr::PlaceTreeArrays& T, uint32_t
   { // which paths this range took, and what it asked for (kr_place_path_counters)
     auto set = [](uint32_t k, uint64_t v) { kr::g_place_paths[k].store(v, std::memory_order_relaxed); };
     kr::g_place_paths[kr::kPathRanges].fetch_add(1, std::memory_order_relaxed);
-    if (w.h_cnt[kPlCnt * (1)] & 8u) kr::g_place_paths[kr::kPathListCut].fetch_add(1, std::memory_order_relaxed);
-    set(kr::kPathLastCnt0, w.h_cnt[kPlCnt * (0)]), set(kr::kPathLastCnt3, w.h_cnt[kPlCnt * (3)]), set(kr::kPathLastCnt12, w.h_cnt[kPlCnt * (12)]);
+    if (pl_cnt(w.h_cnt, kPlFlags) & kPlFlagListCut) kr::g_place_paths[kr::kPathListCut].fetch_add(1, std::memory_order_relaxed);
+    set(kr::kPathLastCnt0, pl_cnt(w.h_cnt, kPlCandSlots)), set(kr::kPathLastCnt3, pl_cnt(w.h_cnt, kPlKept)), set(kr::kPathLastCnt12, pl_cnt(w.h_cnt, kPlListSlots));
     set(kr::kPathLastText, w.text_on ? w.h_ttotal[0] : 0), set(kr::kPathLastCandCap, place_cand_slots(w)), set(kr::kPathLastKeepCap, place_keep_slots(w));
-    set(kr::kPathLastTextCap, w.text_on ? place_text_bytes(w) : 0), set(kr::kPathLastFlags, w.h_cnt[kPlCnt * (1)]);
+    set(kr::kPathLastTextCap, w.text_on ? place_text_bytes(w) : 0), set(kr::kPathLastFlags, pl_cnt(w.h_cnt, kPlFlags));
     set(kr::kPathLastTextFlags, w.text_on ? w.h_ttotal[1] : 0), set(kr::kPathLastAttempts, (uint64_t)attempt + 1);
   }
   lap("place kernels (both launches, likelihoods, compaction) to their counters on the host");
@@ -315,11 +315,11 @@ int kr::place_device_finish(kr_stream* s, const kr::PlaceTreeArrays& T, uint32_t
   HIP_TRY(hipStreamSynchronize(st));
   out->nreads = n;
 #if KR_PLACE_PROF
-  fprintf(stderr, "[kr place prof] cycles/256 per phase: gather %u, sort %u, ancestors %u, weights %u, leaves %u, accumulate %u\n", w.h_cnt[kPlCnt * (4)], w.h_cnt[kPlCnt * (5)], w.h_cnt[kPlCnt * (6)],
-          w.h_cnt[kPlCnt * (7)], w.h_cnt[kPlCnt * (8)], w.h_cnt[kPlCnt * (9)]);
+  fprintf(stderr, "[kr place prof] cycles/256 per phase: gather %u, sort %u, ancestors %u, weights %u, leaves %u, accumulate %u\n", pl_cnt(w.h_cnt, kPlProf0), pl_cnt(w.h_cnt, kPlProf0 + 1), pl_cnt(w.h_cnt, kPlProf0 + 2),
+          pl_cnt(w.h_cnt, kPlProf0 + 3), pl_cnt(w.h_cnt, kPlProf0 + 4), pl_cnt(w.h_cnt, kPlProf0 + 5));
 #endif
-  out->overflow = (w.h_cnt[kPlCnt * (1)] & ~8u) != 0; // (8: the internal candidates' list was incomplete -- the likelihood kernel did their minimisations itself)
-  out->heavy_reads = w.h_cnt[kPlCnt * (2)] + w.h_cnt[kPlCnt * (14)]; // (list slots handed out, in chunks of 8: an upper bound, 0 when there was none; + reads done in global scratch by the first launch)
+  out->overflow = (pl_cnt(w.h_cnt, kPlFlags) & ~kPlFlagListCut) != 0; // (kPlFlagListCut: the internal candidates' list was incomplete -- the likelihood kernel did their minimisations itself)
+  out->heavy_reads = pl_cnt(w.h_cnt, kPlHeavySlots) + pl_cnt(w.h_cnt, kPlInlineReads); // (list slots handed out, in chunks of 8: an upper bound, 0 when there was none; + reads done in global scratch by the first launch)
   if (out->overflow) return KR_OK;
   out->text = nullptr, out->text_len = 0, out->text_flags = 0;
   if (w.text_on) {
@@ -345,7 +345,7 @@ int kr::place_device_finish(kr_stream* s, const kr::PlaceTreeArrays& T, uint32_t
       return KR_OK;
     }
   }
-  const uint64_t used = std::min<uint64_t>(w.h_cnt[kPlCnt * (3)], place_keep_slots(w)); // the candidates kept (compacted)
+  const uint64_t used = std::min<uint64_t>(pl_cnt(w.h_cnt, kPlKept), place_keep_slots(w)); // the candidates kept (compacted)
   if (kept_base + used > w.h_cand_cap) { // (an earlier range's candidates have been consumed by the time a later one is finished: nothing to carry over)
     const uint64_t cap = kept_base + used + used / 4 + 1024;
     auto pin_renew = [&](auto*& p, uint64_t cnt) -> int {

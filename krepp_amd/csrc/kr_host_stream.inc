@@ -9,10 +9,19 @@
 // rate; accumulate: latency; likelihood: fp64 ALU) of different lanes can share the chip.  Lanes change nothing in any
 // result: reads are independent, and every lane runs the same kernels on its reads.
 constexpr uint32_t kMaxLanes = 8;
+enum LaneEvent { // Lane::ev; kr_batch_timing's intervals lie between them
+  kEvCopyIn = 0,   // before the copies in
+  kEvFirstKernel,  // before the lane's first kernel (behind the index's kernel chain)
+  kEvScanDone,     // scan done
+  kEvAccDone,      // accumulate done
+  kEvLastKernel,   // behind the last kernel
+  kEvAccStart,     // recorded right behind kEvScanDone: start of the accumulate stage
+  kEvLlhStart,     // recorded right behind kEvAccDone: start of the likelihood stage
+  kEvCount
+};
 struct Lane {
   hipStream_t stream = nullptr;
-  hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // [0] before the copies in, [1] first kernel, [2] scan done, [3] accumulate done, [4] last kernel;
-                                                                                       // [5] / [6] are recorded right behind [2] / [3] (start of the accumulate / likelihood stage: kr_batch_timing's intervals)
+  hipEvent_t ev[kEvCount] = {}; // indexed by LaneEvent
   BatchIn in;
   BatchOut out;                // pointers: the lane's private scratch + its slices of the stream's arrays
   uint32_t* d_counters = nullptr;
@@ -25,10 +34,10 @@ struct Lane {
   uint8_t* d_dd_oslot = nullptr;
   uint32_t *d_g_planes = nullptr, *d_g_counts = nullptr, *d_g_list = nullptr;
   uint64_t* d_stk = nullptr;
-  uint32_t* h_counters = nullptr; // pinned [32]
+  uint32_t* h_counters = nullptr; // pinned [kCounterWords]
   // this batch
   uint32_t read0 = 0, nreads = 0, rec_base = 0, rec_cap = 0, nrecs = 0;
-  uint32_t nrows = 0;          // rows-mode batches: output rows of the lane (counters[27])
+  uint32_t nrows = 0;          // rows-mode batches: output rows of the lane (counters[kCtRows])
   uint64_t host_off = 0;       // where the lane's records (rows) start in the compacted host arrays
 };
 
@@ -55,7 +64,7 @@ struct kr_stream {
   // pinned host
   uint8_t* h_bases = nullptr;
   uint64_t* h_offsets = nullptr;
-  uint32_t h_counters[32] = {0}; // aggregate of the lanes' counters
+  uint32_t h_counters[kCounterWords] = {0}; // the lanes' counters combined (kCounterRules)
   uint32_t *h_rd_off = nullptr, *h_rd_cnt = nullptr, *h_rd_onmers = nullptr, *h_rd_filt = nullptr;
   uint8_t* h_rd_na = nullptr;
   uint32_t *h_rec_key = nullptr, *h_rec_hist = nullptr;
@@ -331,218 +340,223 @@ int build_tiles(kr_stream* s, const uint8_t* bases, const uint64_t* offsets, uin
   return KR_OK;
 }
 
-// Queue the kernels of one lane on its stream (everything the lane needs is in L.in / L.out).
+// Runtime flags as template arguments: with_bools(f, b0, b1, ...) calls the generic lambda f with std::bool_constant<b0>{},
+// std::bool_constant<b1>{}, ... so that a kernel family has ONE launch expression whatever its instantiation.
+template <typename F>
+void with_bools(F&& f)
+{
+  f();
+}
+template <typename F, typename... Bs>
+void with_bools(F&& f, bool b, Bs... rest)
+{
+  auto bind = [&](auto c) { with_bools([&](auto... cs) { f(c, cs...); }, rest...); };
+  b ? bind(std::true_type{}) : bind(std::false_type{});
+}
+template <int V>
+using int_c = std::integral_constant<int, V>;
+// The scan's lane-group shape as f(LG, CP, SLOTTED): 2^LG lanes x CP 16-byte chunks per probe.  Slotted tables by slot format; by
+// log_g the packed ones (an index without a slotted copy, or format 9 when its filter slots are not used)
+template <typename F>
+void with_scan_shape(uint32_t slot_log2w, uint32_t log_g, F&& f)
+{
+  switch (slot_log2w) {
+    case 5: return f(int_c<2>{}, int_c<2>{}, std::true_type{}); // 128-byte slots: 4 lanes x 2 chunks
+    case 6: return f(int_c<2>{}, int_c<4>{}, std::true_type{}); // 256-byte slots: 4 lanes x 4 chunks
+    case 7: return f(int_c<3>{}, int_c<4>{}, std::true_type{}); // 512-byte slots: 8 lanes x 4 chunks
+    case 8: return f(int_c<2>{}, int_c<3>{}, std::true_type{}); // 192-byte slots: 4 lanes x 3 chunks
+  }
+  switch (log_g) {
+    case 0: return f(int_c<0>{}, int_c<2>{}, std::false_type{});  // sparse tables: a lane per probe
+    case 2: return f(int_c<2>{}, int_c<3>{}, std::false_type{});  // 4 lanes x 3 chunks = 48 entries per pass
+    default: return f(int_c<3>{}, int_c<3>{}, std::false_type{}); // 8 lanes x 3 chunks = 96 entries per pass
+  }
+}
+
+TileBatch tile_batch(const kr_stream* s)
+{
+  const kr_stream::Tiles& tl = s->tiles;
+  return TileBatch{tl.d_vtile, tl.d_longs, tl.d_rfirst, tl.d_tile_filt, tl.nv, tl.nlong, s->nreads,
+                   tl.d_real_off, tl.d_real_cnt, tl.d_real_onmers, tl.d_real_filt, tl.d_real_na};
+}
+
+// The stages of a lane's batch, each queued on the lane's stream (everything a stage needs is in L.in / L.out); launch_lane calls
+// them in this order.
+void launch_scan(kr_stream* s, Lane& L, bool single, bool tap)
+{
+  hipStream_t st = L.stream;
+  const DevIndex& dix = s->ix->dix;
+  BatchOut& o = L.out;
+  const dim3 block(kScanWaves * kWave);
+  auto grid = [&](uint32_t blocks) { return dim3(std::min<uint32_t>((L.nreads + kScanWaves - 1) / kScanWaves, blocks)); };
+  // slotted tables: the scan as a software pipeline across probe groups (kr_dev_scan_pipe.inc); KR_SCAN_PIPE=0: the
+  // one-group-at-a-time kernel
+  static const bool pipe = !getenv("KR_SCAN_PIPE") || atoi(getenv("KR_SCAN_PIPE")) != 0;
+  with_bools([&](auto SL, auto TAP) {
+    if (s->fk) { // filter slots: one line per probe, candidates verified by the accumulate kernel
+      hipLaunchKernelGGL((kr_scan_filt_kernel_t<KR_SCAN_FILT_DEPTH, KR_SCAN_FILT_WPE, SL.value, TAP.value>), grid(s->scan_filt_blocks), block, 0, st, dix, s->dp, L.in, o);
+      return;
+    }
+    with_scan_shape(s->ix->slot_log2w, s->ix->log_g, [&](auto LG, auto CP, auto SLOTTED) {
+      if constexpr (SLOTTED.value)
+        if (pipe) {
+          hipLaunchKernelGGL((kr_scan_pipe_kernel_t<LG.value, CP.value, KR_SCAN_DEPTH, KR_SCAN_PIPE_WPE, SL.value, TAP.value>), grid(s->scan_pipe_blocks), block, 0, st, dix, s->dp, L.in, o);
+          return;
+        }
+      hipLaunchKernelGGL((kr_scan_kernel_t<LG.value, CP.value, SL.value, TAP.value, SLOTTED.value>), grid(s->scan_blocks), block, 0, st, dix, s->dp, L.in, o);
+    });
+  }, single, tap);
+}
+
+void launch_accumulate(kr_stream* s, Lane& L, bool single)
+{
+  hipStream_t st = L.stream;
+  const DevIndex& dix = s->ix->dix;
+  BatchOut& o = L.out;
+  const uint32_t nreads = L.nreads;
+  const kr_stream::Tiles& tl = s->tiles;
+  const TileBatch tb = tile_batch(s);
+  if (tl.active) // the tiles' hdist_filt moved aside: their keys are judged by the sequence's, in kr_tile_merge_kernel
+    hipLaunchKernelGGL(kr_tile_filt_kernel, dim3(std::min<uint32_t>((tl.nv + 255) / 256, 4096u)), dim3(256), 0, st, o, tb);
+  const uint32_t lds = probe_lds_bytes(s->dp.np, o.bm_words), lds_lean = probe_lds_bytes(s->dp.np, o.bm_words, true);
+  const uint32_t lds_lean2 = probe_lds_bytes(s->dp.np, o.bm_words, true, 2);
+  static const bool no_lean2 = getenv("KR_DEBUG_NO_LEAN2") != nullptr; // (experiments: two-segment reads through the merge instantiation, as before round 3)
+  const uint32_t grid_lean2 = (lds_lean2 <= 65536u && !no_lean2) ? std::min(nreads, s->nwaves_lean2) : 0u; // (very large trees: the two-segment layout does not fit a workgroup's LDS)
+  const uint32_t grid_lean = std::min(nreads, s->nwaves_lean), grid_full = std::min(nreads, s->nwaves_full);
+  const bool np5 = s->dp.np == 5 && !getenv("KR_DEBUG_NP0");
+  with_bools([&](auto SL, auto NP5, auto FK) { // one-segment reads, two-segment reads, then the rest (merge instantiation)
+    constexpr int NPV = NP5.value ? 5 : 0;
+    hipLaunchKernelGGL((kr_acc_kernel_t<SL.value, NPV, false, 7, FK.value>), dim3(grid_lean), dim3(kWave), lds_lean, st, dix, s->dp, L.in, o);
+    if (grid_lean2)
+      hipLaunchKernelGGL((kr_acc_kernel_t<SL.value, NPV, false, 8, FK.value>), dim3(grid_lean2), dim3(kWave), lds_lean2, st, dix, s->dp, L.in, o);
+    hipLaunchKernelGGL((kr_acc_kernel_t<SL.value, NPV, true, 7, FK.value>), dim3(grid_full), dim3(kWave), lds, st, dix, s->dp, L.in, o);
+  }, single, np5, s->fk);
+  if (tl.active) { // the tiles' histograms added per key, the sequence's records at its first tile
+    const uint32_t W = std::min<uint32_t>(32u, s->nwaves / std::max<uint32_t>(1u, tl.nlong)); // adding waves per sequence
+    if (W >= 2 && tl.nlong <= s->nwaves) { // few long sequences: the adding spread over W waves each, then a wave per sequence emits
+      hipLaunchKernelGGL(kr_tile_add_kernel, dim3(tl.nlong * W), dim3(kWave), 0, st, dix, s->dp, o, tb, W);
+      hipLaunchKernelGGL(kr_tile_merge_kernel<true>, dim3(tl.nlong), dim3(kWave), (o.bm_words * 4u + 15u) & ~15u, st, dix, s->dp, o, tb);
+    } else { // many: a wave per sequence does both
+      hipLaunchKernelGGL(kr_tile_merge_kernel<false>, dim3(std::min<uint32_t>(tl.nlong, s->nwaves)), dim3(kWave), (o.bm_words * 4u + 15u) & ~15u, st,
+                         dix, s->dp, o, tb);
+    }
+  }
+}
+
+void launch_likelihood(kr_stream* s, Lane& L)
+{ // the batch's distinct likelihood problems (de-duplication), then their minimisations
+  hipStream_t st = L.stream;
+  const DevIndex& dix = s->ix->dix;
+  BatchOut& o = L.out;
+  const bool np5 = s->llh.th == 4, direct = np5 && o.dd_nodes; // (the direct-mapped part: five planes only)
+  const uint32_t places = kDdOslots * kDdClasses * o.dd_nodes;
+  hipLaunchKernelGGL(kr_dedup_clear_kernel, dim3(4096), dim3(256), 0, st, o);
+  if (o.dd_nodes) hipLaunchKernelGGL(kr_dedup_oslot_kernel, dim3(std::min<uint32_t>((L.nreads + 4095) / 4096, 1024u)), dim3(256), 0, st, o, L.nreads);
+  hipLaunchKernelGGL(kr_dedup_kernel, dim3(kDedupBlocks), dim3(256), 0, st, o);
+  if (direct) hipLaunchKernelGGL(kr_dedup_direct_kernel, dim3(std::min<uint32_t>((places + 4095u) / 4096u, 4096u)), dim3(256), 0, st, o);
+  with_bools([&](auto NP5) {
+    constexpr int NPV = NP5.value ? 5 : 0;
+    hipLaunchKernelGGL(kr_llh_pre_kernel<NPV>, dim3(4096), dim3(256), 0, st, s->llh, dix, o);
+    hipLaunchKernelGGL(kr_llh_kernel<NPV>, dim3(2048), dim3(256), 0, st, s->llh, dix, o);
+  }, np5);
+  if (direct) hipLaunchKernelGGL(kr_dedup_dv_kernel, dim3(std::min<uint32_t>((places + 1023u) / 1024u, 4096u)), dim3(256), 0, st, o);
+}
+
+void launch_select(kr_stream* s, Lane& L)
+{
+  hipStream_t st = L.stream;
+  const DevIndex& dix = s->ix->dix;
+  BatchOut& o = L.out;
+  const uint32_t nreads = L.nreads;
+  const uint32_t sgrid = std::min<uint32_t>((nreads + 7) / 8, 16384u);
+  const bool filt = !s->dp.no_filter && s->dp.multi;
+  // without --filter: a lane per read (kr_select_lane_kernel); KR_SELECT_LANE=0: the wave-per-read kernel for every read
+  static const bool lane_sel = !getenv("KR_SELECT_LANE") || atoi(getenv("KR_SELECT_LANE")) != 0;
+  const uint32_t lgrid = std::min<uint32_t>((nreads + 255) / 256, 8192u);
+  with_bools([&](auto NP5, auto FILT) {
+    constexpr int NPV = NP5.value ? 5 : 0;
+    if (!FILT.value && lane_sel)
+      hipLaunchKernelGGL((kr_select_lane_kernel<NPV>), dim3(lgrid), dim3(256), 0, st, s->llh, dix, s->dp, o, nreads);
+    else
+      hipLaunchKernelGGL((kr_select_kernel<NPV, FILT.value>), dim3(sgrid), dim3(256), 0, st, s->llh, dix, s->dp, o, nreads);
+  }, s->llh.th == 4, filt);
+}
+
+// The output rows of a rows-mode batch, compact: (key, DIST) of the selected records, a read's rows contiguous
+int launch_rows_text(kr_stream* s, Lane& L)
+{
+  hipStream_t st = L.stream;
+  BatchOut& o = L.out;
+  const uint32_t nreads = L.nreads, nblk = (nreads + kRowBlock - 1) / kRowBlock;
+  hipLaunchKernelGGL(kr_rows_bsum_kernel, dim3(std::min<uint32_t>(nblk, 4096u)), dim3(256), 0, st, o, nreads);
+  hipLaunchKernelGGL(kr_rows_bscan_kernel, dim3(1), dim3(1024), 0, st, o, nreads);
+  with_bools([&](auto INDEXED) { hipLaunchKernelGGL(kr_rows_write_kernel<INDEXED.value>, dim3(std::min<uint32_t>(nblk, 8192u)), dim3(256), 0, st, o, nreads); },
+             o.rows_indexed != 0);
+  if (o.rows_indexed) hipLaunchKernelGGL(kr_rows_dlist_kernel, dim3(2048), dim3(256), 0, st, o);
+  if (s->text.req) { // ... and as text (kr_dev_text.inc): lengths, block offsets, bytes
+    kr_stream::Text& tx = s->text;
+    TextIO t{tx.d_ids, tx.d_id_off, tx.id_sep, s->ix->d_names, s->ix->d_name_off, tx.d_tlen, tx.d_bsum, tx.d_text, tx.text_cap, tx.d_total};
+    HIP_TRY(hipMemsetAsync(tx.d_total, 0, 16, st));
+    hipLaunchKernelGGL(kr_text_len_kernel, dim3(std::min<uint32_t>(nblk, 8192u)), dim3(256), 0, st, o, t, nreads);
+    hipLaunchKernelGGL(kr_text_bscan_kernel, dim3(1), dim3(1024), 0, st, t, nreads);
+    hipLaunchKernelGGL(kr_text_write_kernel, dim3(std::min<uint32_t>(nblk, 8192u)), dim3(256), 0, st, o, t, nreads);
+    HIP_TRY(hipMemcpyAsync(tx.h_total, tx.d_total, 16, hipMemcpyDeviceToHost, st));
+    tx.made = true;
+  }
+  return KR_OK;
+}
+
+void launch_gather_rebase(kr_stream* s, Lane& L)
+{
+  hipStream_t st = L.stream;
+  BatchOut& o = L.out;
+  if (s->tiles.active) // per-read results of the real reads, for the views, the copies back and `place`
+    hipLaunchKernelGGL(kr_tile_gather_kernel, dim3(std::min<uint32_t>((s->nreads + 255) / 256, 4096u)), dim3(256), 0, st, o, tile_batch(s));
+  if (L.rec_base) // the result view indexes the stream's arrays, the lane's kernels its slice
+    hipLaunchKernelGGL(kr_rebase_kernel, dim3(std::min<uint32_t>((L.nreads + 255) / 256, 1024u)), dim3(256), 0, st, o.rd_off, o.rd_cnt, L.nreads, L.rec_base);
+}
+
+// Queue the kernels of one lane on its stream.
 int launch_lane(kr_stream* s, Lane& L, uint32_t flags)
 {
   hipStream_t st = L.stream;
-  const uint32_t nreads = L.nreads;
   BatchOut& o = L.out;
   { // about four chunks' worth of reads per wave, between 32 and kRecChunk slots (one shared counter serves ~90 M atomics/s:
     // a million-read batch must not take its slots 32 at a time)
-    uint32_t per_wave = (uint32_t)std::min<uint64_t>(4ull * nreads / std::max<uint32_t>(1u, s->nwaves_lean), kRecChunk), c = 32;
+    uint32_t per_wave = (uint32_t)std::min<uint64_t>(4ull * L.nreads / std::max<uint32_t>(1u, s->nwaves_lean), kRecChunk), c = 32;
     while (c < per_wave) c <<= 1;
     o.rec_chunk = std::min<uint32_t>(c, kRecChunk);
   }
-  HIP_TRY(hipMemsetAsync(o.counters, 0, 128, st));
-  HIP_TRY(hipMemsetAsync(o.cursors, 0, 4 * kCursors * kCursorStride * 4, st));
+  HIP_TRY(hipMemsetAsync(o.counters, 0, kCounterWords * 4, st));
+  HIP_TRY(hipMemsetAsync(o.cursors, 0, kCurSets * kCursors * kCursorStride * 4, st));
   HIP_TRY(hipMemsetAsync(o.rec_key, 0, (uint64_t)o.rec_cap * 4, st));
   HIP_TRY(hipMemsetAsync(o.rec_sel, 0, (uint64_t)o.rec_cap, st));
   // the kernel chain of the index (see kr_index): wait for the previous batch's kernels, record behind ours
   const kr_index* ixp = s->ix;
   std::unique_lock<std::mutex> chain(ixp->chain_mu);
-  if (!ixp->chain_off && ixp->chain_n) HIP_TRY(hipStreamWaitEvent(st, ixp->chain_ev[(ixp->chain_n - 1) % 16], 0));
-  HIP_TRY(hipEventRecord(L.ev[1], st));
-  const DevIndex& dix = s->ix->dix;
-  {
-    const bool tap = (flags & KR_TAP_HITS) != 0;
-    const uint32_t sgrid = std::min<uint32_t>((nreads + kScanWaves - 1) / kScanWaves, s->scan_blocks);
-#define KR_LAUNCH2(LG, CP, SLV, SLT)                                                                                          \
-  do {                                                                                                                   \
-    if (tap)                                                                                                             \
-      hipLaunchKernelGGL((kr_scan_kernel_t<LG, CP, SLV, true, SLT>), dim3(sgrid), dim3(kScanWaves* kWave), 0, st, dix, s->dp, L.in, o); \
-    else                                                                                                                 \
-      hipLaunchKernelGGL((kr_scan_kernel_t<LG, CP, SLV, false, SLT>), dim3(sgrid), dim3(kScanWaves* kWave), 0, st, dix, s->dp, L.in, o); \
-  } while (0)
-#define KR_LAUNCH(LG, CP, SLT)          \
-  do {                                  \
-    if (single)                         \
-      KR_LAUNCH2(LG, CP, true, SLT);    \
-    else                                \
-      KR_LAUNCH2(LG, CP, false, SLT);   \
-  } while (0)
-    const bool single = dix.nlibs == 1 && dix.m <= 64;
-    // slotted tables: the scan as a software pipeline across probe groups (kr_dev_scan_pipe.inc); KR_SCAN_PIPE=0: the
-    // one-group-at-a-time kernel
-    static const bool pipe = !getenv("KR_SCAN_PIPE") || atoi(getenv("KR_SCAN_PIPE")) != 0;
-#define KR_LAUNCHP(LG, CP)                                                                                                                         \
-  do {                                                                                                                                             \
-    const uint32_t pgrid = std::min<uint32_t>((nreads + kScanWaves - 1) / kScanWaves, s->scan_pipe_blocks);                                        \
-    if (tap && single)                                                                                                                             \
-      hipLaunchKernelGGL((kr_scan_pipe_kernel_t<LG, CP, KR_SCAN_DEPTH, KR_SCAN_PIPE_WPE, true, true>), dim3(pgrid), dim3(kScanWaves* kWave), 0, st, dix, s->dp, L.in, o);  \
-    else if (tap)                                                                                                                                  \
-      hipLaunchKernelGGL((kr_scan_pipe_kernel_t<LG, CP, KR_SCAN_DEPTH, KR_SCAN_PIPE_WPE, false, true>), dim3(pgrid), dim3(kScanWaves* kWave), 0, st, dix, s->dp, L.in, o); \
-    else if (single)                                                                                                                               \
-      hipLaunchKernelGGL((kr_scan_pipe_kernel_t<LG, CP, KR_SCAN_DEPTH, KR_SCAN_PIPE_WPE, true, false>), dim3(pgrid), dim3(kScanWaves* kWave), 0, st, dix, s->dp, L.in, o); \
-    else                                                                                                                                           \
-      hipLaunchKernelGGL((kr_scan_pipe_kernel_t<LG, CP, KR_SCAN_DEPTH, KR_SCAN_PIPE_WPE, false, false>), dim3(pgrid), dim3(kScanWaves* kWave), 0, st, dix, s->dp, L.in, o); \
-  } while (0)
-    if (s->fk) { // filter slots: one line per probe, candidates verified by the accumulate kernel
-      const uint32_t fgrid = std::min<uint32_t>((nreads + kScanWaves - 1) / kScanWaves, s->scan_filt_blocks);
-      if (tap && single)
-        hipLaunchKernelGGL((kr_scan_filt_kernel_t<KR_SCAN_FILT_DEPTH, KR_SCAN_FILT_WPE, true, true>), dim3(fgrid), dim3(kScanWaves* kWave), 0, st, dix, s->dp, L.in, o);
-      else if (tap)
-        hipLaunchKernelGGL((kr_scan_filt_kernel_t<KR_SCAN_FILT_DEPTH, KR_SCAN_FILT_WPE, false, true>), dim3(fgrid), dim3(kScanWaves* kWave), 0, st, dix, s->dp, L.in, o);
-      else if (single)
-        hipLaunchKernelGGL((kr_scan_filt_kernel_t<KR_SCAN_FILT_DEPTH, KR_SCAN_FILT_WPE, true, false>), dim3(fgrid), dim3(kScanWaves* kWave), 0, st, dix, s->dp, L.in, o);
-      else
-        hipLaunchKernelGGL((kr_scan_filt_kernel_t<KR_SCAN_FILT_DEPTH, KR_SCAN_FILT_WPE, false, false>), dim3(fgrid), dim3(kScanWaves* kWave), 0, st, dix, s->dp, L.in, o);
-    } else if (pipe && s->ix->slot_log2w == 5)
-      KR_LAUNCHP(2, 2);
-    else if (pipe && s->ix->slot_log2w == 6)
-      KR_LAUNCHP(2, 4);
-    else if (pipe && s->ix->slot_log2w == 7)
-      KR_LAUNCHP(3, 4);
-    else if (pipe && s->ix->slot_log2w == 8)
-      KR_LAUNCHP(2, 3); // 192-byte slots: 4 lanes x 3 chunks
-    else
-    switch (s->ix->slot_log2w) { // (9 without s->fk -- a threshold the candidates' 3-bit hd12 cannot carry -- scans the packed arrays)
-      case 5: KR_LAUNCH(2, 2, true); break; // slotted table, 128-byte slots: 4 lanes x 2 chunks
-      case 6: KR_LAUNCH(2, 4, true); break; // 256-byte slots: 4 lanes x 4 chunks
-      case 7: KR_LAUNCH(3, 4, true); break; // 512-byte slots: 8 lanes x 4 chunks
-      case 8: KR_LAUNCH(2, 3, true); break; // 192-byte slots: 4 lanes x 3 chunks
-      default:
-        switch (s->ix->log_g) {
-          case 0: KR_LAUNCH(0, 2, false); break; // sparse tables: a lane per probe
-          case 2: KR_LAUNCH(2, 3, false); break; // 4 lanes x 3 chunks = 48 entries per pass
-          default: KR_LAUNCH(3, 3, false); break; // 8 lanes x 3 chunks = 96 entries per pass
-        }
-    }
-#undef KR_LAUNCH2
-#undef KR_LAUNCH
-#undef KR_LAUNCHP
-    HIP_TRY(hipEventRecord(L.ev[2], st));
-    HIP_TRY(hipEventRecord(L.ev[5], st));
-    kr_stream::Tiles& tl = s->tiles;
-    TileBatch tb{tl.d_vtile, tl.d_longs, tl.d_rfirst, tl.d_tile_filt, tl.nv, tl.nlong, s->nreads,
-                 tl.d_real_off, tl.d_real_cnt, tl.d_real_onmers, tl.d_real_filt, tl.d_real_na};
-    if (tl.active) // the tiles' hdist_filt moved aside: their keys are judged by the sequence's, in kr_tile_merge_kernel
-      hipLaunchKernelGGL(kr_tile_filt_kernel, dim3(std::min<uint32_t>((tl.nv + 255) / 256, 4096u)), dim3(256), 0, st, o, tb);
-    const uint32_t lds = probe_lds_bytes(s->dp.np, o.bm_words), lds_lean = probe_lds_bytes(s->dp.np, o.bm_words, true);
-    const uint32_t lds_lean2 = probe_lds_bytes(s->dp.np, o.bm_words, true, 2);
-    static const bool no_lean2 = getenv("KR_DEBUG_NO_LEAN2") != nullptr; // (experiments: two-segment reads through the merge instantiation, as before round 3)
-    const uint32_t grid_lean2 = (lds_lean2 <= 65536u && !no_lean2) ? std::min(nreads, s->nwaves_lean2) : 0u; // (very large trees: the two-segment layout does not fit a workgroup's LDS)
-    uint32_t grid_lean = std::min(nreads, s->nwaves_lean), grid_full = std::min(nreads, s->nwaves_full);
-    const bool np5 = s->dp.np == 5 && !getenv("KR_DEBUG_NP0");
-#define KR_ACC2(SLV, NPV, FKV)                                                                                                  \
-  do {                                                                                                                       \
-    hipLaunchKernelGGL((kr_acc_kernel_t<SLV, NPV, false, 7, FKV>), dim3(grid_lean), dim3(kWave), lds_lean, st, dix, s->dp, L.in, o); \
-    if (grid_lean2)                                                                                                            \
-      hipLaunchKernelGGL((kr_acc_kernel_t<SLV, NPV, false, 8, FKV>), dim3(grid_lean2), dim3(kWave), lds_lean2, st, dix, s->dp, L.in, o); \
-    hipLaunchKernelGGL((kr_acc_kernel_t<SLV, NPV, true, 7, FKV>), dim3(grid_full), dim3(kWave), lds, st, dix, s->dp, L.in, o);  \
-  } while (0)
-#define KR_ACC(SLV, NPV)         \
-  do {                           \
-    if (s->fk)                   \
-      KR_ACC2(SLV, NPV, true);   \
-    else                         \
-      KR_ACC2(SLV, NPV, false);  \
-  } while (0)
-    if (single && np5)
-      KR_ACC(true, 5);
-    else if (single)
-      KR_ACC(true, 0);
-    else if (np5)
-      KR_ACC(false, 5);
-    else
-      KR_ACC(false, 0);
-#undef KR_ACC
-#undef KR_ACC2
-    if (tl.active) { // the tiles' histograms added per key, the sequence's records at its first tile
-      const uint32_t W = std::min<uint32_t>(32u, s->nwaves / std::max<uint32_t>(1u, tl.nlong)); // adding waves per sequence
-      if (W >= 2 && tl.nlong <= s->nwaves) { // few long sequences: the adding spread over W waves each, then a wave per sequence emits
-        hipLaunchKernelGGL(kr_tile_add_kernel, dim3(tl.nlong * W), dim3(kWave), 0, st, dix, s->dp, o, tb, W);
-        hipLaunchKernelGGL(kr_tile_merge_kernel<true>, dim3(tl.nlong), dim3(kWave), (o.bm_words * 4u + 15u) & ~15u, st, dix, s->dp, o, tb);
-      } else { // many: a wave per sequence does both
-        hipLaunchKernelGGL(kr_tile_merge_kernel<false>, dim3(std::min<uint32_t>(tl.nlong, s->nwaves)), dim3(kWave), (o.bm_words * 4u + 15u) & ~15u, st,
-                           dix, s->dp, o, tb);
-      }
-    }
-  }
-  HIP_TRY(hipEventRecord(L.ev[3], st));
-  HIP_TRY(hipEventRecord(L.ev[6], st));
-  hipLaunchKernelGGL(kr_dedup_clear_kernel, dim3(4096), dim3(256), 0, st, o);
-  if (o.dd_nodes) hipLaunchKernelGGL(kr_dedup_oslot_kernel, dim3(std::min<uint32_t>((nreads + 4095) / 4096, 1024u)), dim3(256), 0, st, o, nreads);
-  if (s->llh.th == 4) {
-    hipLaunchKernelGGL(kr_dedup_kernel, dim3(kDedupBlocks), dim3(256), 0, st, o);
-    if (o.dd_nodes) hipLaunchKernelGGL(kr_dedup_direct_kernel, dim3(std::min<uint32_t>((kDdOslots * kDdClasses * o.dd_nodes + 4095u) / 4096u, 4096u)), dim3(256), 0, st, o);
-    hipLaunchKernelGGL(kr_llh_pre_kernel<5>, dim3(4096), dim3(256), 0, st, s->llh, dix, o);
-    hipLaunchKernelGGL(kr_llh_kernel<5>, dim3(2048), dim3(256), 0, st, s->llh, dix, o);
-    if (o.dd_nodes) hipLaunchKernelGGL(kr_dedup_dv_kernel, dim3(std::min<uint32_t>((kDdOslots * kDdClasses * o.dd_nodes + 1023u) / 1024u, 4096u)), dim3(256), 0, st, o);
-  } else {
-    hipLaunchKernelGGL(kr_dedup_kernel, dim3(kDedupBlocks), dim3(256), 0, st, o);
-    hipLaunchKernelGGL(kr_llh_pre_kernel<0>, dim3(4096), dim3(256), 0, st, s->llh, dix, o);
-    hipLaunchKernelGGL(kr_llh_kernel<0>, dim3(2048), dim3(256), 0, st, s->llh, dix, o);
-  }
-  {
-    const uint32_t sgrid = std::min<uint32_t>((nreads + 7) / 8, 16384u);
-    const bool filt = !s->dp.no_filter && s->dp.multi;
-    // without --filter: a lane per read (kr_select_lane_kernel); KR_SELECT_LANE=0: the wave-per-read kernel for every read
-    static const bool lane_sel = !getenv("KR_SELECT_LANE") || atoi(getenv("KR_SELECT_LANE")) != 0;
-    const uint32_t lgrid = std::min<uint32_t>((nreads + 255) / 256, 8192u);
-    if (s->llh.th == 4) {
-      if (filt)
-        hipLaunchKernelGGL((kr_select_kernel<5, true>), dim3(sgrid), dim3(256), 0, st, s->llh, dix, s->dp, o, nreads);
-      else if (lane_sel)
-        hipLaunchKernelGGL((kr_select_lane_kernel<5>), dim3(lgrid), dim3(256), 0, st, s->llh, dix, s->dp, o, nreads);
-      else
-        hipLaunchKernelGGL((kr_select_kernel<5, false>), dim3(sgrid), dim3(256), 0, st, s->llh, dix, s->dp, o, nreads);
-    } else {
-      if (filt)
-        hipLaunchKernelGGL((kr_select_kernel<0, true>), dim3(sgrid), dim3(256), 0, st, s->llh, dix, s->dp, o, nreads);
-      else if (lane_sel)
-        hipLaunchKernelGGL((kr_select_lane_kernel<0>), dim3(lgrid), dim3(256), 0, st, s->llh, dix, s->dp, o, nreads);
-      else
-        hipLaunchKernelGGL((kr_select_kernel<0, false>), dim3(sgrid), dim3(256), 0, st, s->llh, dix, s->dp, o, nreads);
-    }
-  }
-  if (o.rows_mode) { // the output rows, compact: (key, DIST) of the selected records, a read's rows contiguous
-    const uint32_t nblk = (nreads + kRowBlock - 1) / kRowBlock;
-    hipLaunchKernelGGL(kr_rows_bsum_kernel, dim3(std::min<uint32_t>(nblk, 4096u)), dim3(256), 0, st, o, nreads);
-    hipLaunchKernelGGL(kr_rows_bscan_kernel, dim3(1), dim3(1024), 0, st, o, nreads);
-    if (o.rows_indexed) {
-      hipLaunchKernelGGL(kr_rows_write_kernel<true>, dim3(std::min<uint32_t>(nblk, 8192u)), dim3(256), 0, st, o, nreads);
-      hipLaunchKernelGGL(kr_rows_dlist_kernel, dim3(2048), dim3(256), 0, st, o);
-    } else {
-      hipLaunchKernelGGL(kr_rows_write_kernel<false>, dim3(std::min<uint32_t>(nblk, 8192u)), dim3(256), 0, st, o, nreads);
-    }
-    if (s->text.req) { // ... and as text (kr_dev_text.inc): lengths, block offsets, bytes
-      kr_stream::Text& tx = s->text;
-      TextIO t{tx.d_ids, tx.d_id_off, tx.id_sep, s->ix->d_names, s->ix->d_name_off, tx.d_tlen, tx.d_bsum, tx.d_text, tx.text_cap, tx.d_total};
-      HIP_TRY(hipMemsetAsync(tx.d_total, 0, 16, st));
-      hipLaunchKernelGGL(kr_text_len_kernel, dim3(std::min<uint32_t>(nblk, 8192u)), dim3(256), 0, st, o, t, nreads);
-      hipLaunchKernelGGL(kr_text_bscan_kernel, dim3(1), dim3(1024), 0, st, t, nreads);
-      hipLaunchKernelGGL(kr_text_write_kernel, dim3(std::min<uint32_t>(nblk, 8192u)), dim3(256), 0, st, o, t, nreads);
-      HIP_TRY(hipMemcpyAsync(tx.h_total, tx.d_total, 16, hipMemcpyDeviceToHost, st));
-      tx.made = true;
-    }
-  }
-  if (s->tiles.active) { // per-read results of the real reads, for the views, the copies back and `place`
-    kr_stream::Tiles& tl = s->tiles;
-    TileBatch tb{tl.d_vtile, tl.d_longs, tl.d_rfirst, tl.d_tile_filt, tl.nv, tl.nlong, s->nreads,
-                 tl.d_real_off, tl.d_real_cnt, tl.d_real_onmers, tl.d_real_filt, tl.d_real_na};
-    hipLaunchKernelGGL(kr_tile_gather_kernel, dim3(std::min<uint32_t>((s->nreads + 255) / 256, 4096u)), dim3(256), 0, st, o, tb);
-  }
-  if (L.rec_base) // the result view indexes the stream's arrays, the lane's kernels its slice
-    hipLaunchKernelGGL(kr_rebase_kernel, dim3(std::min<uint32_t>((nreads + 255) / 256, 1024u)), dim3(256), 0, st, o.rd_off, o.rd_cnt, nreads, L.rec_base);
-  HIP_TRY(hipEventRecord(L.ev[4], st));
+  if (!ixp->chain_off && ixp->chain_n) HIP_TRY(hipStreamWaitEvent(st, ixp->chain_ev[(ixp->chain_n - 1) % kr_index::kChainEvents], 0));
+  HIP_TRY(hipEventRecord(L.ev[kEvFirstKernel], st));
+  const bool single = ixp->dix.nlibs == 1 && ixp->dix.m <= 64;
+  launch_scan(s, L, single, (flags & KR_TAP_HITS) != 0);
+  HIP_TRY(hipEventRecord(L.ev[kEvScanDone], st));
+  HIP_TRY(hipEventRecord(L.ev[kEvAccStart], st));
+  launch_accumulate(s, L, single);
+  HIP_TRY(hipEventRecord(L.ev[kEvAccDone], st));
+  HIP_TRY(hipEventRecord(L.ev[kEvLlhStart], st));
+  launch_likelihood(s, L);
+  launch_select(s, L);
+  if (o.rows_mode)
+    if (int rc = launch_rows_text(s, L)) return rc;
+  launch_gather_rebase(s, L);
+  HIP_TRY(hipEventRecord(L.ev[kEvLastKernel], st));
   if (!ixp->chain_off) {
-    hipEvent_t& ce = ixp->chain_ev[ixp->chain_n % 16];
+    hipEvent_t& ce = ixp->chain_ev[ixp->chain_n % kr_index::kChainEvents];
     if (!ce) HIP_TRY(hipEventCreateWithFlags(&ce, hipEventDisableTiming));
     HIP_TRY(hipEventRecord(ce, st));
     ++ixp->chain_n;
   }
   chain.unlock();
-  HIP_TRY(hipMemcpyAsync(L.h_counters, o.counters, 128, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(L.h_counters, o.counters, kCounterWords * 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipGetLastError());
   return KR_OK;
 }
@@ -721,8 +735,8 @@ int kr_stream_create(const kr_index* ix, const kr_params* p, uint32_t max_reads,
     // GPU_MAX_HW_QUEUES says otherwise): lane 0 has one from the start, the others get theirs when a batch first uses them
     if (l == 0) HT(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
     for (auto& e : L.ev) HT(hipEventCreate(&e));
-    SA(L.d_counters, 32);
-    SA(L.d_cursors, 4 * kCursors * kCursorStride);
+    SA(L.d_counters, kCounterWords);
+    SA(L.d_cursors, kCurSets * kCursors * kCursorStride);
     // lane 0 may be the only lane of a batch; a later lane never holds more than half of one
     const uint32_t lane_recs = l == 0 ? s->rec_cap : s->rec_cap / 2;
     L.dd_slots = std::min<uint32_t>(next_pow2(std::max<uint32_t>(2048u, lane_recs >> o.dd_shift)), 1u << 26);
@@ -741,7 +755,7 @@ int kr_stream_create(const kr_index* ix, const kr_params* p, uint32_t max_reads,
     // multi-GB clear (large trees) would otherwise still be running when the first batch arrives
     HT(hipMemsetAsync(L.d_g_planes, 0, (uint64_t)s->nwaves * nslots2 * np * kPlaneWords * 4, s->lanes[0].stream));
     HT(hipMemsetAsync(L.d_g_counts, 0, (uint64_t)s->nwaves * nslots2 * np * 4, s->lanes[0].stream));
-    HA(L.h_counters, 32);
+    HA(L.h_counters, kCounterWords);
   }
   HT(hipStreamSynchronize(s->lanes[0].stream));
   HA(s->h_bases, max_bases + 256);
@@ -886,8 +900,8 @@ int kr_batch_collect_text(kr_stream* s, const char** text, uint64_t* len)
   if (rc) return rc;
   kr_stream::Text& t = s->text;
   if (!t.made) return kr::fail(KR_ERR_UNSUPPORTED, "kr_batch_collect_text: the batch left the device as record slots (long sequences): kr_batch_collect + kr_format_dist");
-  if (t.h_total[1] & 2ull) return kr::fail(KR_ERR_CAPACITY, "the batch's report text exceeds max_text_bytes: submit fewer reads per batch");
-  if (t.h_total[1] & 1ull) return kr::fail(KR_ERR_UNSUPPORTED, "kr_batch_collect_text: a DIST outside [0, 1000): kr_batch_collect + kr_format_dist");
+  if (t.h_total[1] & kTextOverCap) return kr::fail(KR_ERR_CAPACITY, "the batch's report text exceeds max_text_bytes: submit fewer reads per batch");
+  if (t.h_total[1] & kTextBadNum) return kr::fail(KR_ERR_UNSUPPORTED, "kr_batch_collect_text: a DIST outside [0, 1000): kr_batch_collect + kr_format_dist");
   HIP_TRY(hipSetDevice(s->ix->device));
   const uint64_t n = t.h_total[0];
   if (n) {
@@ -969,7 +983,7 @@ static int submit_batch(kr_stream* s, const uint8_t* bases, const uint64_t* offs
     L.read0 = r0, L.nreads = r1 - r0, L.rec_base = l * lane_rec_cap, L.rec_cap = lane_rec_cap, L.nrecs = 0;
     if (!L.stream) HIP_TRY(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
     hipStream_t st = L.stream;
-    HIP_TRY(hipEventRecord(L.ev[0], st));
+    HIP_TRY(hipEventRecord(L.ev[kEvCopyIn], st));
     if (s->tiles.active) { // the tiled batch: its own bases and offsets, and what the tile kernels need
       kr_stream::Tiles& t = s->tiles;
       HIP_TRY(hipMemcpyAsync(t.d_bases, t.h_bases, t.h_voff[t.nv], hipMemcpyHostToDevice, st));
@@ -1055,6 +1069,20 @@ static int submit_batch(kr_stream* s, const uint8_t* bases, const uint64_t* offs
   return KR_OK;
 }
 
+// How kr_batch_wait combines the lanes' counters into kr_stream::h_counters (CounterSlot, kr_dev_common.inc); a slot that is not
+// listed is read per lane only and stays 0 there
+enum CounterCombine { kSum, kMax, kOr };
+struct CounterRule {
+  CounterSlot slot;
+  CounterCombine how;
+};
+constexpr CounterRule kCounterRules[] = {
+  {kCtErr, kOr}, {kCtL2Reads, kSum}, {kCtTapHits, kSum}, {kCtRecords, kSum},
+  {kCtStEvents, kSum}, {kCtStKeys, kSum}, {kCtStBatches, kSum}, {kCtStBig, kSum}, {kCtStLevelTiles, kSum}, {kCtStMaxKeys, kMax}, {kCtStMaxEvents, kMax},
+  {kCtCycLevel, kSum}, {kCtCycFinalize, kSum}, {kCtCycRead, kSum},
+  {kCtProblems, kSum}, {kCtStackSpills, kSum}, {kCtTileHoles, kSum},
+};
+
 // After a large one-lane batch: how fast did the scan run on the item list in use?  Keep the faster of {the list set aside, the
 // one in use}, and while trials are left put a freshly allocated one in use for the next batch.  KR_ITEM_PLACEMENT_TRIALS
 // allocations per stream, DEFAULT kItemPlacementTrials since round 5 (0 before: the benchmark asked for five and the CLI got none,
@@ -1076,7 +1104,7 @@ int item_placement_step(kr_stream* s)
   float ms = 0;
   for (uint32_t l = 0; l < s->nlanes; ++l) { // (the lanes of a batch work in slices of the one list: their scan times are added)
     float ml = 0;
-    if (hipEventElapsedTime(&ml, s->lanes[l].ev[1], s->lanes[l].ev[2]) != hipSuccess) {
+    if (hipEventElapsedTime(&ml, s->lanes[l].ev[kEvFirstKernel], s->lanes[l].ev[kEvScanDone]) != hipSuccess) {
       (void)hipGetLastError(); // (not this batch's business: leave no sticky error behind)
       return KR_OK;
     }
@@ -1139,29 +1167,28 @@ int kr_batch_wait(kr_stream* s)
   if (s->waited) return s->batch_rc ? kr::fail(s->batch_rc, s->batch_msg) : KR_OK;
   HIP_TRY(hipSetDevice(s->ix->device));
   memset(s->h_counters, 0, sizeof(s->h_counters));
-  uint32_t recs = 0, extent = 0;
+  uint32_t extent = 0;
   bool lane_full = false;
   for (uint32_t l = 0; l < s->nlanes; ++l) {
     Lane& L = s->lanes[l];
     HIP_TRY(hipStreamSynchronize(L.stream)); // kernels done, counters in L.h_counters
     const uint32_t* c = L.h_counters;
-    L.nrecs = std::min(c[0], L.rec_cap);
-    L.nrows = c[27];
+    L.nrecs = std::min(c[kCtRecSlots], L.rec_cap);
+    L.nrows = c[kCtRows];
     extent = std::max(extent, L.nrecs ? L.rec_base + L.nrecs : 0u);
-    recs += c[4];
-    lane_full = lane_full || c[0] > L.rec_cap;
-    s->h_counters[1] |= c[1];
-    for (int i : {2, 3, 4, 9, 10, 11, 12, 13, 16, 17, 18, 19, 20, 21, 22, 26, 28}) s->h_counters[i] += c[i];
-    for (int i : {14, 15}) s->h_counters[i] = std::max(s->h_counters[i], c[i]);
+    lane_full = lane_full || c[kCtRecSlots] > L.rec_cap;
+    for (const CounterRule& r : kCounterRules) {
+      uint32_t& a = s->h_counters[r.slot];
+      a = r.how == kSum ? a + c[r.slot] : (r.how == kMax ? std::max(a, c[r.slot]) : (a | c[r.slot]));
+    }
   }
   s->waited = true;
+  const uint32_t* hc = s->h_counters;
   if (s->dp.dbg & 512u)
     fprintf(stderr, "[kr stats] reads %u events %u keys %u batches %u big %u level-tiles %u max keys %u max events %u records %u distinct likelihood problems (list positions) %u\n", s->nreads,
-            s->h_counters[9], s->h_counters[10], s->h_counters[11], s->h_counters[12], s->h_counters[13], s->h_counters[14],
-            s->h_counters[15], s->h_counters[4], s->h_counters[22]);
+            hc[kCtStEvents], hc[kCtStKeys], hc[kCtStBatches], hc[kCtStBig], hc[kCtStLevelTiles], hc[kCtStMaxKeys], hc[kCtStMaxEvents], hc[kCtRecords], hc[kCtProblems]);
   if (s->dp.dbg & 512u)
-    fprintf(stderr, "[kr stats] wave cycles/64 per launch: level passes %u (zero %u, event passes %u, key passes %u), finalize %u, whole read %u\n",
-            s->h_counters[16], s->h_counters[19], s->h_counters[20], s->h_counters[21], s->h_counters[17], s->h_counters[18]);
+    fprintf(stderr, "[kr stats] wave cycles/64 per launch: level passes %u, finalize %u, whole read %u\n", hc[kCtCycLevel], hc[kCtCycFinalize], hc[kCtCycRead]);
   if (KR_STATS && (s->dp.dbg & 512u)) { // the accumulate kernel's histograms (g_kr_stats), printed and cleared
     uint32_t hs[128], zero[128] = {0};
     if (hipMemcpyFromSymbol(hs, HIP_SYMBOL(g_kr_stats), sizeof(hs)) == hipSuccess && hipMemcpyToSymbol(HIP_SYMBOL(g_kr_stats), zero, sizeof(zero)) == hipSuccess) {
@@ -1180,14 +1207,14 @@ int kr_batch_wait(kr_stream* s)
   }
   if (int prc = item_placement_step(s)) return prc;
   s->nrecs = extent; // record slots of the device view, unused ones (rec_key == 0) included
-  s->nhits = std::min<uint64_t>(s->h_counters[3], s->hit_cap);
-  // (a tiled batch: the tiles' own records became holes when their sequences' records were written: counters[28]; what survives
+  s->nhits = std::min<uint64_t>(hc[kCtTapHits], s->hit_cap);
+  // (a tiled batch: the tiles' own records became holes when their sequences' records were written: kCtTileHoles; what survives
   //  is what the caller's max_records bounds)
-  const uint32_t holes = s->tiles.active ? s->h_counters[28] : 0u;
+  const uint32_t recs = hc[kCtRecords], holes = s->tiles.active ? hc[kCtTileHoles] : 0u;
   if (recs - std::min(recs, holes) > s->rec_user_cap)
     s->batch_rc = kr::fail(KR_ERR_CAPACITY, "the batch produced more records than max_records: submit fewer reads per batch");
   else
-    s->batch_rc = check_errflags(s->h_counters[1] | (lane_full ? kErrRecCap : 0u));
+    s->batch_rc = check_errflags(hc[kCtErr] | (lane_full ? kErrRecCap : 0u));
   if (s->batch_rc) s->batch_msg = kr_last_error();
   if (!s->batch_rc && s->tiles.active && !s->no_tiles && getenv("KR_DEBUG_TILE_OVERFLOW")) s->batch_rc = KR_ERR_CAPACITY; // (tests)
   if (s->batch_rc == KR_ERR_CAPACITY && s->tiles.active && !s->no_tiles) {
@@ -1295,8 +1322,8 @@ int kr_batch_collect(kr_stream* s, kr_result_view* v)
     hipStream_t st = L.stream;
     if (!s->waited) {
       HIP_TRY(hipStreamSynchronize(st));
-      L.nrecs = std::min(L.h_counters[0], L.rec_cap);
-      L.nrows = L.h_counters[27];
+      L.nrecs = std::min(L.h_counters[kCtRecSlots], L.rec_cap);
+      L.nrows = L.h_counters[kCtRows];
       // room for this lane and, by its measure, for the lanes still running; if not, start over once everything is known
       const uint64_t guess = hoff + lane_count(L) * (s->nlanes - l) + lane_count(L) / 8 * (s->nlanes - l - 1);
       if (guess > s->h_rec_cap || (full && !s->h_rec_full)) {
@@ -1323,7 +1350,7 @@ int kr_batch_collect(kr_stream* s, kr_result_view* v)
       HIP_TRY(hipMemcpyAsync(s->h_rd_na + r0, o.rd_na, nr, hipMemcpyDeviceToHost, st));
       s->d2h_bytes += nr * 9;
       if (nc && s->rows_indexed) { // (one lane, waited for: the counters are known)
-        const uint64_t nd = std::min<uint64_t>(L.h_counters[22], L.rec_cap);
+        const uint64_t nd = std::min<uint64_t>(L.h_counters[kCtProblems], L.rec_cap);
         if (nd > s->h_dist_cap) {
           if (s->h_dist_list) {
             s->hallocs.erase(std::remove(s->hallocs.begin(), s->hallocs.end(), (void*)s->h_dist_list), s->hallocs.end());
@@ -1465,7 +1492,7 @@ int kr_debug_stream_move(kr_stream* s, int which)
       MV(o.rd_off, mr); MV(o.rd_cnt, mr); MV(o.rd_onmers, mr); MV(o.rd_filt, 2 * mr); MV(o.rd_na, mr);
       MV(o.rd_it_off, mr); MV(o.rd_it_cnt, mr); MV(o.long_list, mr + 16ull * s->nwaves * ML);
       break;
-    case 2: MV(L.d_counters, 32); MV(L.d_cursors, 4 * kCursors * kCursorStride); break;
+    case 2: MV(L.d_counters, kCounterWords); MV(L.d_cursors, kCurSets * kCursors * kCursorStride); break;
     case 3:
       MV(o.rec_read, s->rec_cap); MV(o.rec_key, s->rec_cap); MV(o.rec_d, s->rec_cap); MV(o.rec_sel, s->rec_cap);
       MV(o.rec_w0, s->rec_cap); MV(o.rec_rep, s->rec_cap); MV(o.rep_list, (uint64_t)s->rec_cap + (uint64_t)kMaxLanes * kRepSlack); MV(o.rep_dv, (uint64_t)s->rec_cap + (uint64_t)kMaxLanes * kRepSlack);
@@ -1515,25 +1542,25 @@ int kr_batch_timing(kr_stream* s, kr_timing* t)
   for (uint32_t l = 0; l < s->nlanes; ++l) {
     Lane& L = s->lanes[l];
     float a = 0;
-    HIP_TRY(hipEventElapsedTime(&a, L.ev[0], L.ev[1]));
+    HIP_TRY(hipEventElapsedTime(&a, L.ev[kEvCopyIn], L.ev[kEvFirstKernel]));
     t->ms_h2d += a;
-    HIP_TRY(hipEventElapsedTime(&a, L.ev[1], L.ev[2]));
+    HIP_TRY(hipEventElapsedTime(&a, L.ev[kEvFirstKernel], L.ev[kEvScanDone]));
     t->ms_scan += a;
-    HIP_TRY(hipEventElapsedTime(&a, L.ev[5], L.ev[3]));
+    HIP_TRY(hipEventElapsedTime(&a, L.ev[kEvAccStart], L.ev[kEvAccDone]));
     t->ms_acc += a;
-    HIP_TRY(hipEventElapsedTime(&a, L.ev[6], L.ev[4]));
+    HIP_TRY(hipEventElapsedTime(&a, L.ev[kEvLlhStart], L.ev[kEvLastKernel]));
     t->ms_llh += a;
     if (l) {
-      HIP_TRY(hipEventElapsedTime(&a, s->lanes[0].ev[1], L.ev[1]));
+      HIP_TRY(hipEventElapsedTime(&a, s->lanes[0].ev[kEvFirstKernel], L.ev[kEvFirstKernel]));
       first = std::min(first, a);
     }
-    HIP_TRY(hipEventElapsedTime(&a, s->lanes[0].ev[1], L.ev[4]));
+    HIP_TRY(hipEventElapsedTime(&a, s->lanes[0].ev[kEvFirstKernel], L.ev[kEvLastKernel]));
     last = std::max(last, a);
   }
   t->ms_total = last - first;
   t->lanes = s->nlanes;
-  t->overflow_reads = s->h_counters[2];
-  t->stack_spills = s->h_counters[26];
+  t->overflow_reads = s->h_counters[kCtL2Reads];
+  t->stack_spills = s->h_counters[kCtStackSpills];
   return KR_OK;
 }
 
