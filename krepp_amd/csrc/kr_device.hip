@@ -101,6 +101,19 @@ namespace {
                       std::string(#expr) + ": " + hipGetErrorString(e__));                                  \
   } while (0)
 
+// KR_DEBUG_POISON (tests): nothing may depend on what a fresh device buffer holds.  "all": every buffer of a stream and of its place
+// workspace is filled; a number: the stream's k-th (`ordinal`, counted by salloc; 0: a buffer that has no number)
+int poison_fresh(void* p, uint64_t bytes, size_t ordinal = 0)
+{
+  const char* e = getenv("KR_DEBUG_POISON");
+  if (!e || (strcmp(e, "all") && (!ordinal || (size_t)atoi(e) != ordinal))) return KR_OK;
+  HIP_TRY(hipMemset(p, 0xA5, bytes));
+  // a device memset may return before it has run, and the lanes' streams do not wait for the null stream: without this the
+  // fill could land AFTER the clear of a buffer that kr_stream_create zeroes on a lane's stream (the spill accumulators)
+  HIP_TRY(hipDeviceSynchronize());
+  return KR_OK;
+}
+
 // dynamic LDS bytes of the probe kernel: stack + probe list + ntouched (+ table)
 uint32_t probe_lds_bytes(uint32_t np, uint32_t bm_words, bool lean = false, uint32_t segs = 1)
 {
@@ -138,6 +151,14 @@ LlhConst make_llh_const(uint32_t k, uint32_t h, uint32_t th)
 #include "kr_host_fastq.inc"
 #include "kr_host_place.inc"
 
+// Room for `need` doubles in the index's likelihood workspace, device and page-locked (under ix->llh_mu); grown with 25 % to spare
+static int llh_workspace(const kr_index* ix, uint64_t need)
+{
+  if (need <= ix->llh_dev.size()) return KR_OK;
+  ix->llh_dev.reset(), ix->llh_pin.reset(); // (both given back before either is asked for again)
+  return reserve_all(need + need / 4, ix->llh_dev, ix->llh_pin) ? KR_OK : alloc_failed("likelihood workspace");
+}
+
 extern "C" {
 
 void* kr_host_alloc(uint64_t bytes)
@@ -161,15 +182,15 @@ int kr_debug_front_end(const kr_index* ix, const uint8_t* bases, const uint64_t*
   if (!ix || !bases || !offsets || !rix || !enc32 || !valid || !pass || !nreads) return kr::fail(KR_ERR_ARG, "kr_debug_front_end: bad argument");
   HIP_TRY(hipSetDevice(ix->device));
   uint64_t nb = offsets[nreads], n = (uint64_t)nreads * stride * 2;
-  uint8_t *d_b = nullptr, *d_valid = nullptr, *d_pass = nullptr;
-  uint64_t* d_o = nullptr;
-  uint32_t *d_rix = nullptr, *d_enc = nullptr;
-  HIP_TRY(hipMalloc((void**)&d_b, nb + 256));
-  HIP_TRY(hipMalloc((void**)&d_o, ((uint64_t)nreads + 1) * 8));
-  HIP_TRY(hipMalloc((void**)&d_rix, n * 4 + 16));
-  HIP_TRY(hipMalloc((void**)&d_enc, n * 4 + 16));
-  HIP_TRY(hipMalloc((void**)&d_valid, n + 16));
-  HIP_TRY(hipMalloc((void**)&d_pass, n + 16));
+  DevBuf<uint8_t> b_b, b_valid, b_pass; // (freed at every return)
+  DevBuf<uint64_t> b_o;
+  DevBuf<uint32_t> b_rix, b_enc;
+  if (!b_b.reserve(nb + 256) || !b_o.reserve((uint64_t)nreads + 1) || !b_rix.reserve(n + 4) || !b_enc.reserve(n + 4) || !b_valid.reserve(n + 16) ||
+      !b_pass.reserve(n + 16))
+    return alloc_failed("kr_debug_front_end");
+  uint8_t *d_b = b_b.get(), *d_valid = b_valid.get(), *d_pass = b_pass.get();
+  uint64_t* d_o = b_o.get();
+  uint32_t *d_rix = b_rix.get(), *d_enc = b_enc.get();
   HIP_TRY(hipMemcpy(d_b, bases, nb, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_o, offsets, ((uint64_t)nreads + 1) * 8, hipMemcpyHostToDevice));
   HIP_TRY(hipMemset(d_rix, 0, n * 4));
@@ -184,7 +205,6 @@ int kr_debug_front_end(const kr_index* ix, const uint8_t* bases, const uint64_t*
   HIP_TRY(hipMemcpy(enc32, d_enc, n * 4, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(valid, d_valid, n, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(pass, d_pass, n, hipMemcpyDeviceToHost));
-  hipFree(d_b), hipFree(d_o), hipFree(d_rix), hipFree(d_enc), hipFree(d_valid), hipFree(d_pass);
   return KR_OK;
 }
 
@@ -200,16 +220,8 @@ int kr_llh_batch(const kr_index* ix, uint32_t th, uint32_t mode, uint64_t n, con
   LlhConst C = make_llh_const(ix->dix.k, ix->dix.h, th);
   const uint64_t np = th + 1, need = n * (np + 5);
   std::lock_guard<std::mutex> lk(ix->llh_mu);
-  if (need > ix->llh_cap) {
-    if (ix->llh_dev) (void)hipFree(ix->llh_dev);
-    if (ix->llh_pin) (void)hipHostFree(ix->llh_pin);
-    ix->llh_dev = ix->llh_pin = nullptr, ix->llh_cap = 0;
-    const uint64_t cap = need + need / 4;
-    HIP_TRY(hipMalloc((void**)&ix->llh_dev, cap * 8));
-    HIP_TRY(hipHostMalloc((void**)&ix->llh_pin, cap * 8, hipHostMallocDefault));
-    ix->llh_cap = cap;
-  }
-  double *pin = ix->llh_pin, *dev = ix->llh_dev;
+  if (int rc = llh_workspace(ix, need)) return rc;
+  double *pin = ix->llh_pin.get(), *dev = ix->llh_dev.get();
   const uint64_t o_uc = n * np, o_rho = o_uc + n, o_di = o_rho + n, o_do = o_di + n, o_v = o_do + n;
   { // stage the inputs in pinned memory (a few threads: tens of MB for a large batch), one H2D copy
     const int nt = n >= (1u << 16) ? 4 : 1;
@@ -250,16 +262,8 @@ int kr_llh_eval_indexed(const kr_index* ix, uint32_t th, uint64_t nprob, const d
   const uint64_t np = th + 1, o_uc = nprob * np, o_rho = o_uc + nprob, o_di = o_rho + nprob, o_v = o_di + n, o_ix = o_v + n,
                  need = o_ix + (n + 1) / 2;
   std::lock_guard<std::mutex> lk(ix->llh_mu);
-  if (need > ix->llh_cap) {
-    if (ix->llh_dev) (void)hipFree(ix->llh_dev);
-    if (ix->llh_pin) (void)hipHostFree(ix->llh_pin);
-    ix->llh_dev = ix->llh_pin = nullptr, ix->llh_cap = 0;
-    const uint64_t cap = need + need / 4;
-    HIP_TRY(hipMalloc((void**)&ix->llh_dev, cap * 8));
-    HIP_TRY(hipHostMalloc((void**)&ix->llh_pin, cap * 8, hipHostMallocDefault));
-    ix->llh_cap = cap;
-  }
-  double *pin = ix->llh_pin, *dev = ix->llh_dev;
+  if (int rc = llh_workspace(ix, need)) return rc;
+  double *pin = ix->llh_pin.get(), *dev = ix->llh_dev.get();
   memcpy(pin, hist, nprob * np * 8);
   memcpy(pin + o_uc, uc, nprob * 8);
   memcpy(pin + o_rho, rho, nprob * 8);
@@ -283,13 +287,11 @@ int kr_debug_brent(const kr_index* ix, uint32_t th, uint32_t n, const uint32_t* 
   if (!ix || !hist || !onmers || !rho || !d_out || !v_out || !n || th > KR_MAX_HDIST_TH) return kr::fail(KR_ERR_ARG, "kr_debug_brent: bad argument");
   HIP_TRY(hipSetDevice(ix->device));
   LlhConst C = make_llh_const(ix->dix.k, ix->dix.h, th);
-  uint32_t *d_h = nullptr, *d_on = nullptr;
-  double *d_rho = nullptr, *d_d = nullptr, *d_v = nullptr;
-  HIP_TRY(hipMalloc((void**)&d_h, (uint64_t)n * (th + 1) * 4));
-  HIP_TRY(hipMalloc((void**)&d_on, (uint64_t)n * 4));
-  HIP_TRY(hipMalloc((void**)&d_rho, (uint64_t)n * 8));
-  HIP_TRY(hipMalloc((void**)&d_d, (uint64_t)n * 8));
-  HIP_TRY(hipMalloc((void**)&d_v, (uint64_t)n * 8));
+  DevBuf<uint32_t> b_h, b_on; // (freed at every return)
+  DevBuf<double> b_rho, b_d, b_v;
+  if (!b_h.reserve((uint64_t)n * (th + 1)) || !reserve_all(n, b_on, b_rho, b_d, b_v)) return alloc_failed("kr_debug_brent");
+  uint32_t *d_h = b_h.get(), *d_on = b_on.get();
+  double *d_rho = b_rho.get(), *d_d = b_d.get(), *d_v = b_v.get();
   HIP_TRY(hipMemcpy(d_h, hist, (uint64_t)n * (th + 1) * 4, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_on, onmers, (uint64_t)n * 4, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_rho, rho, (uint64_t)n * 8, hipMemcpyHostToDevice));
@@ -300,7 +302,6 @@ int kr_debug_brent(const kr_index* ix, uint32_t th, uint32_t n, const uint32_t* 
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(d_out, d_d, (uint64_t)n * 8, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(v_out, d_v, (uint64_t)n * 8, hipMemcpyDeviceToHost));
-  hipFree(d_h), hipFree(d_on), hipFree(d_rho), hipFree(d_d), hipFree(d_v);
   return KR_OK;
 }
 

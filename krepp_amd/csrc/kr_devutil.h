@@ -5,9 +5,43 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <string>
 #include <vector>
 
+#include "kr_buf.h"
+#include "kr_common.h"
+
 namespace {
+
+// Where a Buf (kr_buf.h) takes its memory from: the device in effect (hipSetDevice), or page-locked host memory.  hipFree
+// synchronises the device: a workspace may be renewed while an earlier range's kernels are still queued.
+struct DevMem {
+  static void* alloc(size_t bytes)
+  {
+    void* p = nullptr;
+    return hipMalloc(&p, bytes) == hipSuccess ? p : nullptr;
+  }
+  static void free(void* p) { (void)hipFree(p); }
+};
+struct PinMem {
+  static void* alloc(size_t bytes)
+  {
+    void* p = nullptr;
+    return hipHostMalloc(&p, bytes, hipHostMallocDefault) == hipSuccess ? p : nullptr;
+  }
+  static void free(void* p) { (void)hipHostFree(p); }
+};
+template <class T>
+using DevBuf = Buf<T, DevMem>;
+template <class T>
+using PinBuf = Buf<T, PinMem>;
+// A DevBuf / PinBuf that could not be had: the caller's error, by what the runtime said last
+int alloc_failed(const char* what)
+{
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipErrorOutOfMemory;
+  return kr::fail(e == hipErrorOutOfMemory ? KR_ERR_NOMEM : KR_ERR_NO_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
+}
 
 // Software PEXT for a fixed 32-bit mask (Hacker's Delight 7-4 "compress"): five precomputed
 // move masks; x86's _pext_u64 in LSHF::compute_hash / drop_ppos_lr (src/lshf.cpp:62-69) becomes

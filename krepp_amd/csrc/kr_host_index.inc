@@ -23,12 +23,11 @@ struct kr_index {
   mutable uint32_t chain_n = 0;
   mutable bool chain_off = false;
   mutable std::mutex llh_mu;
-  mutable double* llh_dev = nullptr;
-  mutable double* llh_pin = nullptr;
-  mutable uint64_t llh_cap = 0; // doubles
+  mutable DevBuf<double> llh_dev; // (one capacity, in doubles)
+  mutable PinBuf<double> llh_pin;
   // node names by colour id, for the device-side report text (kr_stream_text_enable; uploaded once, under chain_mu)
-  mutable char* d_names = nullptr;
-  mutable uint32_t* d_name_off = nullptr; // [tree_nnodes + 2]
+  mutable DevBuf<char> d_names;
+  mutable DevBuf<uint32_t> d_name_off; // [tree_nnodes + 2]
 };
 
 namespace {
@@ -387,8 +386,9 @@ int kr_index_upload(const kr_index_view* v, int device, uint32_t flags, kr_index
   const hipMemcpyKind kind = (flags & KR_VIEW_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   HIP_TRY(hipMemcpy((void*)ix->dix.node_info, node_info.data(), node_info.size() * 4, hipMemcpyHostToDevice));
   if (!leaf_se.empty()) HIP_TRY(hipMemcpy((void*)ix->dix.leaf_se, leaf_se.data(), leaf_se.size() * 4, hipMemcpyHostToDevice));
-  uint32_t* d_bad = nullptr;
-  HIP_TRY(hipMalloc(&d_bad, 4));
+  DevBuf<uint32_t> b_bad; // (this and the staging arrays below: freed at every return)
+  if (!b_bad.reserve(1)) return alloc_failed("kr_index_upload");
+  uint32_t* d_bad = b_bad.get();
   HIP_TRY(hipMemset(d_bad, 0, 4));
   for (uint32_t i = 0; i < v->nlibs; ++i) {
     const kr_lib_view& lv = v->libs[i];
@@ -396,20 +396,21 @@ int kr_index_upload(const kr_index_view* v, int device, uint32_t flags, kr_index
     // stage the on-disk arrays, then re-lay them out on the device
     const uint32_t* src_cmer = lv.cmer;
     const uint64_t* src_inc = lv.inc;
-    void *t_cmer = nullptr, *t_inc = nullptr;
+    DevBuf<uint64_t> t_cmer, t_inc;
     if (!(flags & KR_VIEW_DEVICE)) {
-      HIP_TRY(hipMalloc(&t_cmer, lv.nkmers * 8 + 16));
-      HIP_TRY(hipMemcpy(t_cmer, lv.cmer, lv.nkmers * 8, hipMemcpyHostToDevice));
-      HIP_TRY(hipMalloc(&t_inc, (uint64_t)lv.nrows * 8 + 16));
-      HIP_TRY(hipMemcpy(t_inc, lv.inc, (uint64_t)lv.nrows * 8, hipMemcpyHostToDevice));
-      src_cmer = (const uint32_t*)t_cmer;
-      src_inc = (const uint64_t*)t_inc;
+      if (!t_cmer.reserve(lv.nkmers + 2)) return alloc_failed("kr_index_upload: staging");
+      HIP_TRY(hipMemcpy(t_cmer.get(), lv.cmer, lv.nkmers * 8, hipMemcpyHostToDevice));
+      if (!t_inc.reserve((uint64_t)lv.nrows + 2)) return alloc_failed("kr_index_upload: staging");
+      HIP_TRY(hipMemcpy(t_inc.get(), lv.inc, (uint64_t)lv.nrows * 8, hipMemcpyHostToDevice));
+      src_cmer = (const uint32_t*)t_cmer.get();
+      src_inc = t_inc.get();
     }
     HIP_TRY(hipMemset((void*)d.enc, 0xFF, (d.nkmers + 16) * 4));
     HIP_TRY(hipMemset((void*)d.se, 0, (d.nkmers + 16) * 4));
     if (lv.nsubsets > kColMask) return kr::fail(KR_ERR_ARG, "kr_index_upload: more than 2^30 colours is not supported");
-    uint32_t* d_cls = nullptr;
-    HIP_TRY(hipMalloc(&d_cls, (uint64_t)lv.nsubsets * 4 + 16));
+    DevBuf<uint32_t> b_cls;
+    if (!b_cls.reserve((uint64_t)lv.nsubsets + 4)) return alloc_failed("kr_index_upload: staging");
+    uint32_t* d_cls = b_cls.get();
     if (lv.nsubsets) HIP_TRY(hipMemcpy(d_cls, cls[i].data(), (uint64_t)lv.nsubsets * 4, hipMemcpyHostToDevice));
     if (!lists[i].empty()) HIP_TRY(hipMemcpy((void*)d.leaflist, lists[i].data(), lists[i].size() * 4, hipMemcpyHostToDevice));
     if (lv.nkmers)
@@ -422,15 +423,12 @@ int kr_index_upload(const kr_index_view* v, int device, uint32_t flags, kr_index
     } else if (lv.nrows && H.slot_log2w)
       hipLaunchKernelGGL(kr_build_slots, dim3(8192), dim3(256), 0, 0, d.bkt, d.enc, lv.nrows, slot_words(H.slot_log2w), (uint32_t*)d.slots);
     HIP_TRY(hipDeviceSynchronize());
-    if (t_cmer) hipFree(t_cmer);
-    if (t_inc) hipFree(t_inc);
-    hipFree(d_cls);
+    t_cmer.reset(), t_inc.reset(), b_cls.reset(); // (before the copies below, as ever: hipFree synchronises)
     if (lv.nsubsets) HIP_TRY(hipMemcpy((void*)d.pse, hpse[i].data(), (uint64_t)lv.nsubsets * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy((void*)d.rho, lv.rho, (uint64_t)lv.nnodes * 8, kind));
   }
   uint32_t bad = 0;
   HIP_TRY(hipMemcpy(&bad, d_bad, 4, hipMemcpyDeviceToHost));
-  hipFree(d_bad);
   if (bad) {
     kr_index_free(ix.release());
     return kr::fail(KR_ERR_FORMAT, "inc-* is not monotone or a bucket exceeds 2^24 entries / 2^40 offset");
@@ -445,13 +443,9 @@ void kr_index_free(kr_index* ix)
   if (!ix) return;
   (void)hipSetDevice(ix->device);
   for (void* p : ix->allocs) (void)hipFree(p);
-  if (ix->llh_dev) (void)hipFree(ix->llh_dev);
-  if (ix->d_names) (void)hipFree(ix->d_names);
-  if (ix->d_name_off) (void)hipFree(ix->d_name_off);
-  if (ix->llh_pin) (void)hipHostFree(ix->llh_pin);
   for (auto& e : ix->chain_ev)
     if (e) (void)hipEventDestroy(e);
-  delete ix;
+  delete ix; // (the likelihood workspace and the node names free themselves: the device is set)
 }
 
 uint64_t kr_index_device_bytes(const kr_index* ix) { return ix ? ix->bytes : 0; }

@@ -1,61 +1,51 @@
 // kr_host_place.inc -- part of kr_device.hip (host side): kr::place_on_device, the launch of the place kernels for kr_place_stream.
 
 namespace {
-// KR_DEBUG_POISON=all (tests, as for the stream's own buffers: salloc): nothing may depend on what a new place workspace holds
-int place_poison(void* p, uint64_t bytes)
+// Growth of the place workspace.  place_renew: a new block whatever the buffer holds; place_grow: when n exceeds its size;
+// place_grow_all: a group with one capacity -- all of them at least n afterwards, or (a failed allocation) all of them empty, so that
+// the next batch allocates again.  A new device block is poisoned under KR_DEBUG_POISON=all (as the stream's own buffers: salloc).
+template <class T>
+int place_fresh(DevBuf<T>& b) { return poison_fresh(b.get(), b.bytes()); }
+template <class T>
+int place_fresh(PinBuf<T>&) { return KR_OK; }
+template <class B>
+int place_renew(B& b, uint64_t n) { return b.renew(n) ? place_fresh(b) : alloc_failed("place workspace"); }
+template <class B>
+int place_grow(B& b, uint64_t n) { return n <= b.size() ? KR_OK : place_renew(b, n); }
+template <class... B>
+int place_grow_all(uint64_t n, B&... b)
 {
-  const char* e = getenv("KR_DEBUG_POISON");
-  if (!e || strcmp(e, "all")) return KR_OK;
-  HIP_TRY(hipMemset(p, 0xA5, bytes));
-  HIP_TRY(hipDeviceSynchronize()); // (the lanes' streams do not wait for the null stream)
-  return KR_OK;
+  const bool fresh = ((n > b.size()) || ...);
+  if (!reserve_all(n, b...)) return alloc_failed("place workspace");
+  int rc = KR_OK;
+  if (fresh) ((rc = rc ? rc : place_fresh(b)), ...);
+  return rc;
 }
 // What the kernels are told the buffers hold: all of it, or what KR_DEBUG_PLACE_CAPS says (never more than there is)
-uint64_t place_cand_slots(const kr_stream::PlaceWs& w) { return w.dbg_cand ? std::min(w.dbg_cand, w.cand_cap) : w.cand_cap; }
-uint64_t place_keep_slots(const kr_stream::PlaceWs& w) { return w.dbg_keep ? std::min(w.dbg_keep, w.keep_cap) : w.keep_cap; }
+uint64_t place_cand_slots(const kr_stream::PlaceWs& w) { return w.dbg_cand ? std::min<uint64_t>(w.dbg_cand, w.d_cse.size()) : w.d_cse.size(); }
+uint64_t place_keep_slots(const kr_stream::PlaceWs& w) { return w.dbg_keep ? std::min<uint64_t>(w.dbg_keep, w.d_kse.size()) : w.d_kse.size(); }
 uint64_t place_text_bytes(const kr_stream::PlaceWs& w)
 {
-  if (!w.dbg_text) return w.text_cap;
-  return std::min(w.text_cap, w.dbg_sticky ? w.dbg_text : std::max(w.dbg_text, w.text_want_min));
+  const uint64_t cap = w.d_text.size();
+  if (!w.dbg_text) return cap;
+  return std::min(cap, w.dbg_sticky ? w.dbg_text : std::max(w.dbg_text, w.text_want_min));
 }
 // candidate slots of a stream's place workspace: a read may need one per leaf and per distinct ancestor while it is worked on, and
 // keeps what it emits; a range that runs out (large trees) is run again with as many as it asked for
 int place_size_candidates(kr_stream* s, uint64_t want)
 {
   kr_stream::PlaceWs& w = s->pw;
-  auto dev_renew = [&](auto*& p, uint64_t n) -> int {
-    if (p) (void)hipFree(p), p = nullptr;
-    HIP_TRY(hipMalloc((void**)&p, std::max<uint64_t>(16, n * sizeof(*p))));
-    return place_poison(p, std::max<uint64_t>(16, n * sizeof(*p)));
-  };
   int rc2 = 0;
-  if (want > w.cand_cap) {
-    if ((rc2 = dev_renew(w.d_cse, want)) || (rc2 = dev_renew(w.d_cread, want)) || (rc2 = dev_renew(w.d_cd, want)) || (rc2 = dev_renew(w.d_cv, want)) ||
-        (rc2 = dev_renew(w.d_cchi, want)))
-      return rc2;
-    w.cand_cap = want;
-  }
+  if ((rc2 = place_grow_all(want, w.d_cse, w.d_cread, w.d_cd, w.d_cv, w.d_cchi))) return rc2;
+  const uint64_t cand_cap = w.d_cse.size();
   // every candidate, twice: a read that does not fit the rest of its wave's chunk takes a new one and leaves the rest unused (up to
   // total - 1 slots per read), + a partly used chunk per wave of the compaction; a range that still runs out is run again
-  const uint64_t keep_want = w.dbg_keep ? w.dbg_keep : std::max<uint64_t>(w.keep_want_min, 2ull * w.cand_cap + 2048ull * 4ull * kPlKeepChunk);
-  if (keep_want > w.keep_cap) {
-    if ((rc2 = dev_renew(w.d_kse, keep_want)) || (rc2 = dev_renew(w.d_kd, keep_want)) || (rc2 = dev_renew(w.d_kv, keep_want)) || (rc2 = dev_renew(w.d_kchi, keep_want)))
-      return rc2;
-    w.keep_cap = keep_want;
-  }
-  if (w.text_on && w.keep_cap > w.sorted_cap) { // the sorted copy the text kernels work on (kr_dev_place.inc)
-    if ((rc2 = dev_renew(w.d_sse, w.keep_cap)) || (rc2 = dev_renew(w.d_sd, w.keep_cap)) || (rc2 = dev_renew(w.d_sv, w.keep_cap)) || (rc2 = dev_renew(w.d_sc, w.keep_cap))) return rc2;
-    w.sorted_cap = w.keep_cap;
-  }
+  const uint64_t keep_want = w.dbg_keep ? w.dbg_keep : std::max<uint64_t>(w.keep_want_min, 2ull * cand_cap + 2048ull * 4ull * kPlKeepChunk);
+  if ((rc2 = place_grow_all(keep_want, w.d_kse, w.d_kd, w.d_kv, w.d_kchi))) return rc2;
+  // the sorted copy the text kernels work on (kr_dev_place.inc)
+  if (w.text_on && (rc2 = place_grow_all(w.d_kse.size(), w.d_sse, w.d_sd, w.d_sv, w.d_sc))) return rc2;
   const uint64_t np_ = s->dp.np;
-  if (w.cand_cap * (np_ + 2) > w.cprob_cap) {
-    if ((rc2 = dev_renew(w.d_cprob, w.cand_cap * (np_ + 2)))) return rc2;
-    w.cprob_cap = w.cand_cap * (np_ + 2);
-  }
-  if (w.reads_cap * (np_ + 3) > w.rprob_cap) {
-    if ((rc2 = dev_renew(w.d_rprob, w.reads_cap * (np_ + 3)))) return rc2;
-    w.rprob_cap = w.reads_cap * (np_ + 3);
-  }
+  if ((rc2 = place_grow(w.d_cprob, cand_cap * (np_ + 2))) || (rc2 = place_grow(w.d_rprob, w.d_len.size() * (np_ + 3)))) return rc2;
   return KR_OK;
 }
 } // namespace
@@ -87,45 +77,29 @@ int kr::place_device_begin(kr_stream* s, const void* tree_tag, const kr::PlaceTr
   kr_stream::PlaceWs& w = s->pw;
   w.text_on = false; // (place_device_text_begin turns it on for this batch)
   hipStream_t st = s->lanes[0].stream;
-  auto dev_renew = [&](auto*& p, uint64_t n) -> int {
-    if (p) (void)hipFree(p), p = nullptr;
-    HIP_TRY(hipMalloc((void**)&p, std::max<uint64_t>(16, n * sizeof(*p))));
-    return place_poison(p, std::max<uint64_t>(16, n * sizeof(*p)));
-  };
-  auto pin_renew = [&](auto*& p, uint64_t n) -> int {
-    if (p) (void)hipHostFree(p), p = nullptr;
-    HIP_TRY(hipHostMalloc((void**)&p, std::max<uint64_t>(16, n * sizeof(*p)), hipHostMallocDefault));
-    return KR_OK;
-  };
   if (w.tree_tag != tree_tag || w.pn != T.pn || w.nidx != T.nidx) { // the tree as device arrays (once per tree)
     w.tree_tag = nullptr;
     const uint64_t n1 = (uint64_t)T.pn + 1, n2 = (uint64_t)T.nidx + 1;
-    if ((rc = dev_renew(w.d_parent, n1)) || (rc = dev_renew(w.d_eff, n1)) || (rc = dev_renew(w.d_lo, n1)) || (rc = dev_renew(w.d_elig, n1)) ||
-        (rc = dev_renew(w.d_idx_to_pt, n2)) || (rc = dev_renew(w.d_depth, n1)))
+    if ((rc = place_renew(w.d_parent, n1)) || (rc = place_renew(w.d_eff, n1)) || (rc = place_renew(w.d_lo, n1)) || (rc = place_renew(w.d_elig, n1)) ||
+        (rc = place_renew(w.d_idx_to_pt, n2)) || (rc = place_renew(w.d_depth, n1)))
       return rc;
-    HIP_TRY(hipMemcpy(w.d_parent, T.parent, n1 * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(w.d_eff, T.eff, n1 * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(w.d_lo, T.lo, n1 * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(w.d_elig, T.elig, n1, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(w.d_idx_to_pt, T.idx_to_pt, n2 * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(w.d_depth, T.depth, n1 * 4, hipMemcpyHostToDevice));
-    if ((rc = dev_renew(w.d_node, n1))) return rc;
+    HIP_TRY(hipMemcpy(w.d_parent.get(), T.parent, n1 * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(w.d_eff.get(), T.eff, n1 * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(w.d_lo.get(), T.lo, n1 * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(w.d_elig.get(), T.elig, n1, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(w.d_idx_to_pt.get(), T.idx_to_pt, n2 * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(w.d_depth.get(), T.depth, n1 * 4, hipMemcpyHostToDevice));
+    if ((rc = place_renew(w.d_node, n1))) return rc;
     {
       std::vector<uint4> nodes(n1);
       for (uint64_t i = 0; i < n1; ++i) nodes[i] = make_uint4(T.parent[i], T.lo[i], T.eff[i], T.depth[i]);
-      HIP_TRY(hipMemcpy(w.d_node, nodes.data(), n1 * sizeof(uint4), hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(w.d_node.get(), nodes.data(), n1 * sizeof(uint4), hipMemcpyHostToDevice));
     }
     w.tree_tag = tree_tag, w.pn = T.pn, w.nidx = T.nidx;
   }
   const uint32_t n = s->nreads;
-  if (n > w.reads_cap) {
-    const uint64_t cap = (uint64_t)n + n / 4;
-    if ((rc = dev_renew(w.d_len, cap)) || (rc = dev_renew(w.d_c0, cap)) || (rc = dev_renew(w.d_info, cap)) || (rc = pin_renew(w.h_len, cap)) ||
-        (rc = pin_renew(w.h_c0, cap)) || (rc = pin_renew(w.h_info, cap)))
-      return rc;
-    if (!w.d_cnt && ((rc = dev_renew(w.d_cnt, kPlCntCount * kPlCnt)) || (rc = pin_renew(w.h_cnt, kPlCntCount * kPlCnt)))) return rc;
-    w.reads_cap = cap;
-  }
+  if (n > w.d_len.size() && (rc = place_grow_all((uint64_t)n + n / 4, w.d_len, w.d_c0, w.d_info, w.h_len, w.h_c0, w.h_info))) return rc;
+  if ((rc = place_grow_all(kPlCntCount * kPlCnt, w.d_cnt, w.h_cnt))) return rc;
   // candidate slots: a read may need one per leaf and per distinct ancestor while it is worked on, and keeps what it
   // emits; a batch that runs out (large trees) is run again with as many as it asked for
   // KR_DEBUG_PLACE_CAPS="c=SLOTS,k=SLOTS,t=BYTES,l=ENTRIES,sticky" (tests; read per batch, every field optional): the first attempt's
@@ -168,27 +142,24 @@ int kr::place_device_begin(kr_stream* s, const void* tree_tag, const kr::PlaceTr
   const uint32_t grid = std::min<uint32_t>(n, (uint32_t)prop.multiProcessorCount * 16u);
   { // heavy reads (more leaves / ancestors than kr_place_kernel's LDS arrays hold): list + per-wave global scratch of the second launch
     const uint64_t list = 2ull * n + 8ull * grid; // (the reads the first launch sets aside, in chunks of 8 per wave; behind them the reads it starts with)
-    if (list > w.heavy_cap) {
-      if ((rc = dev_renew(w.d_heavy, list + list / 4))) return rc;
-      w.heavy_cap = list + list / 4;
-    }
+    if (list > w.d_heavy.size() && (rc = place_grow(w.d_heavy, list + list / 4))) return rc;
     const uint32_t cwaves = std::max(grid, 1024u);
-    if (!w.d_chain || cwaves > w.chain_waves) { // the weights of every (leaf, ancestor) pair of a read: kPlChain doubles per wave of either launch
+    if (!w.d_chain.get() || cwaves > w.chain_waves) { // the weights of every (leaf, ancestor) pair of a read: kPlChain doubles per wave of either launch
       // (+ a larger piece for each wave that may do an over-limit read itself: PlaceOut::chain_inline)
-      if ((rc = dev_renew(w.d_chain, (uint64_t)cwaves * kPlChain + 1024ull * 4ull * kPlChain))) return rc;
+      if ((rc = place_renew(w.d_chain, (uint64_t)cwaves * kPlChain + 1024ull * 4ull * kPlChain))) return rc;
       w.chain_cap = kPlChain, w.chain_waves = cwaves;
     }
     const uint32_t hl = std::max<uint32_t>(kPlLeaves, s->ix->dix.nleaves), hn = std::max<uint32_t>(kPlNodes, T.pn);
-    if (hl > w.heavy_leaves || hn > w.heavy_nodes || !w.d_heavy_u32) {
+    if (hl > w.heavy_leaves || hn > w.heavy_nodes || !w.d_heavy_u32.get() || !w.d_heavy_f64.get()) {
       const uint64_t per_wave = 32ull * hl + 4ull * hn; // bytes
       const uint32_t waves = (uint32_t)std::max<uint64_t>(64, std::min<uint64_t>(1024, (1ull << 30) / per_wave)); // (<= 1024: the chain scratch above)
-      if ((rc = dev_renew(w.d_heavy_u32, (uint64_t)waves * (4ull * hl + hn))) || (rc = dev_renew(w.d_heavy_f64, (uint64_t)waves * 2ull * hl))) return rc;
+      if ((rc = place_renew(w.d_heavy_u32, (uint64_t)waves * (4ull * hl + hn))) || (rc = place_renew(w.d_heavy_f64, (uint64_t)waves * 2ull * hl))) return rc;
       w.heavy_leaves = hl, w.heavy_nodes = hn, w.heavy_waves = waves;
     }
   }
   lap("workspaces");
-  memcpy(w.h_len, read_len, (uint64_t)n * 4);
-  HIP_TRY(hipMemcpyAsync(w.d_len, w.h_len, (uint64_t)n * 4, hipMemcpyHostToDevice, st));
+  memcpy(w.h_len.get(), read_len, (uint64_t)n * 4);
+  HIP_TRY(hipMemcpyAsync(w.d_len.get(), w.h_len.get(), (uint64_t)n * 4, hipMemcpyHostToDevice, st));
   return KR_OK;
 }
 
@@ -202,21 +173,21 @@ int kr::place_device_launch(kr_stream* s, const kr::PlaceTreeArrays& T, uint32_t
   const uint32_t grid = std::min<uint32_t>(n, cus * 16u);
   BatchOut ro = result_out(s); // the range's reads as reads 0 .. n: the per-read arrays moved by r0 (records are named by rd_off)
   ro.rd_off += r0, ro.rd_cnt += r0, ro.rd_onmers += r0;
-  const uint32_t* d_len = w.d_len + r0;
+  const uint32_t* d_len = w.d_len.get() + r0;
   // the second launch's arrays in LDS where the tree allows it (KR_PLACE_HEAVY_GLOBAL=1: always global scratch, as for large trees)
   const uint32_t heavy_lds_bytes = 32u * w.heavy_leaves + 4u * w.heavy_nodes;
   const bool heavy_global = getenv("KR_PLACE_HEAVY_GLOBAL") != nullptr; // (read per call: tests switch it)
   const bool big_first = !getenv("KR_PLACE_BIG_FIRST") || atoi(getenv("KR_PLACE_BIG_FIRST")) != 0; // 0: every over-limit read through the second launch
   const bool heavy_lds = !heavy_global && (uint64_t)32 * w.heavy_leaves + 4ull * w.heavy_nodes <= 61440ull;
-  PlaceTree PT{w.d_parent, w.d_eff, w.d_elig, w.d_lo, w.d_idx_to_pt, w.d_depth, w.d_node, T.pn, T.nidx};
-  HIP_TRY(hipMemsetAsync(w.d_cnt, 0, kPlCntCount * kPlCnt * 4, st));
-  HIP_TRY(hipMemsetAsync(w.d_cse, 0, w.cand_cap * 4, st)); // 0 = unused slot: what the second kernel and the host skip
-  PlaceOut PO{w.d_c0 + r0, w.d_info + r0, w.d_cse, w.d_cread, w.d_cd, w.d_cv, w.d_cchi, w.d_cprob, w.d_rprob, w.d_cnt, (uint32_t)std::min<uint64_t>(place_cand_slots(w), 0x3FFFFFFFu),
-              w.d_heavy, w.d_heavy_u32, w.d_heavy_f64, w.heavy_leaves, w.heavy_nodes, kPlLeaves, kPlNodes,
-              w.d_kse, w.d_kd, w.d_kv, w.d_kchi, (uint32_t)std::min<uint64_t>(place_keep_slots(w), 0xFFFFFFFFull), w.d_chain, w.chain_cap,
+  PlaceTree PT{w.d_parent.get(), w.d_eff.get(), w.d_elig.get(), w.d_lo.get(), w.d_idx_to_pt.get(), w.d_depth.get(), w.d_node.get(), T.pn, T.nidx};
+  HIP_TRY(hipMemsetAsync(w.d_cnt.get(), 0, kPlCntCount * kPlCnt * 4, st));
+  HIP_TRY(hipMemsetAsync(w.d_cse.get(), 0, w.d_cse.size() * 4, st)); // 0 = unused slot: what the second kernel and the host skip
+  PlaceOut PO{w.d_c0.get() + r0, w.d_info.get() + r0, w.d_cse.get(), w.d_cread.get(), w.d_cd.get(), w.d_cv.get(), w.d_cchi.get(), w.d_cprob.get(), w.d_rprob.get(), w.d_cnt.get(), (uint32_t)std::min<uint64_t>(place_cand_slots(w), 0x3FFFFFFFu),
+              w.d_heavy.get(), w.d_heavy_u32.get(), w.d_heavy_f64.get(), w.heavy_leaves, w.heavy_nodes, kPlLeaves, kPlNodes,
+              w.d_kse.get(), w.d_kd.get(), w.d_kv.get(), w.d_kchi.get(), (uint32_t)std::min<uint64_t>(place_keep_slots(w), 0xFFFFFFFFull), w.d_chain.get(), w.chain_cap,
               w.chain_cap * std::max<uint32_t>(1u, w.chain_waves / std::max<uint32_t>(1u, w.heavy_waves)), heavy_lds ? 1u : 0u,
               (uint32_t)((uint64_t)n + 8ull * grid), 0u, big_first ? std::min<uint32_t>(std::min<uint32_t>(w.heavy_waves, grid), 1024u) : 0u,
-              w.d_chain + (uint64_t)w.chain_waves * w.chain_cap, 4u * w.chain_cap, 0u};
+              w.d_chain.get() + (uint64_t)w.chain_waves * w.chain_cap, 4u * w.chain_cap, 0u};
   PO.lcap = w.dbg_list ? (uint32_t)std::min<uint64_t>(w.dbg_list, PO.kcap) : PO.kcap;
   if (const char* e = getenv("KR_DEBUG_PLACE_LDS")) { // tests: "leaves,nodes" the LDS launch accepts, so that small trees have heavy reads
     unsigned a = kPlLeaves, b = kPlNodes;
@@ -243,19 +214,19 @@ int kr::place_device_launch(kr_stream* s, const kr::PlaceTreeArrays& T, uint32_t
   //  for its 200,000 candidates)
   hipLaunchKernelGGL(kr_place_compact_kernel, dim3(std::max<uint32_t>(16u, std::min<uint32_t>(2048u, (n + 255u) / 256u))), dim3(256), 0, st, PO, PT, n, chisq);
   if (w.text_on) { // the range's rows as text (kr_dev_place.inc): lengths, the blocks' first bytes, bytes
-    PlaceText TX{w.d_ids, w.d_id_off + r0, w.d_blen, w.d_card, w.d_labels, w.d_label_off, w.d_tlen + r0, w.d_tbsum, w.d_text, place_text_bytes(w), w.d_ttotal,
-                 w.text_tabular, w.text_multi, chisq, w.d_sse, w.d_sd, w.d_sv, w.d_sc, w.d_rtotal + r0, w.d_rbest + r0};
+    PlaceText TX{w.d_ids.get(), w.d_id_off.get() + r0, w.d_blen.get(), w.d_card.get(), w.d_labels.get(), w.d_label_off.get(), w.d_tlen.get() + r0, w.d_tbsum.get(), w.d_text.get(), place_text_bytes(w), w.d_ttotal.get(),
+                 w.text_tabular, w.text_multi, chisq, w.d_sse.get(), w.d_sd.get(), w.d_sv.get(), w.d_sc.get(), w.d_rtotal.get() + r0, w.d_rbest.get() + r0};
     const uint32_t nblk = (n + kPlTextBlock - 1) / kPlTextBlock;
-    HIP_TRY(hipMemsetAsync(w.d_ttotal, 0, 16, st));
+    HIP_TRY(hipMemsetAsync(w.d_ttotal.get(), 0, 16, st));
     hipLaunchKernelGGL(kr_place_text_len_kernel, dim3(std::min<uint32_t>(nblk, 16384u)), dim3(256), 0, st, PO, PT, TX, n);
-    TextIO tio{nullptr, nullptr, 0u, nullptr, nullptr, nullptr, w.d_tbsum, nullptr, place_text_bytes(w), w.d_ttotal};
+    TextIO tio{nullptr, nullptr, 0u, nullptr, nullptr, nullptr, w.d_tbsum.get(), nullptr, place_text_bytes(w), w.d_ttotal.get()};
     // (the `dist` text's block scan counts its blocks as ceil(reads / kRowBlock): told of nblk x kRowBlock reads it scans these nblk sums)
     hipLaunchKernelGGL(kr_text_bscan_kernel, dim3(1), dim3(1024), 0, st, tio, nblk * kRowBlock);
     hipLaunchKernelGGL(kr_place_text_write_kernel, dim3(std::min<uint32_t>(nblk, 16384u)), dim3(256), 0, st, PO, PT, TX, n);
-    HIP_TRY(hipMemcpyAsync(w.h_ttotal, w.d_ttotal, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(w.h_ttotal.get(), w.d_ttotal.get(), 16, hipMemcpyDeviceToHost, st));
   }
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(w.h_cnt, w.d_cnt, kPlCntCount * kPlCnt * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(w.h_cnt.get(), w.d_cnt.get(), kPlCntCount * kPlCnt * 4, hipMemcpyDeviceToHost, st));
   return KR_OK;
 }
 
@@ -283,19 +254,19 @@ int kr::place_device_finish(kr_stream* s, const kr::PlaceTreeArrays& T, uint32_t
   int attempt = 0;
   for (;; ++attempt) {
     HIP_TRY(hipStreamSynchronize(st));
-    if (!(pl_cnt(w.h_cnt, kPlFlags) & (kPlFlagCandCap | kPlFlagKeepCap)) || attempt >= 2) break;
+    if (!(pl_cnt(w.h_cnt.get(), kPlFlags) & (kPlFlagCandCap | kPlFlagKeepCap)) || attempt >= 2) break;
     // out of candidate slots (kPlFlagCandCap: kPlCandSlots went on counting what the reads asked for) or out of slots for the kept ones
     // (kPlFlagKeepCap: kPlKept went on counting what the compaction handed out)
-    const uint64_t asked = (pl_cnt(w.h_cnt, kPlFlags) & kPlFlagCandCap) ? (uint64_t)pl_cnt(w.h_cnt, kPlCandSlots) + pl_cnt(w.h_cnt, kPlCandSlots) / 8 + (uint64_t)grid * kPlChunk : place_cand_slots(w);
+    const uint64_t asked = (pl_cnt(w.h_cnt.get(), kPlFlags) & kPlFlagCandCap) ? (uint64_t)pl_cnt(w.h_cnt.get(), kPlCandSlots) + pl_cnt(w.h_cnt.get(), kPlCandSlots) / 8 + (uint64_t)grid * kPlChunk : place_cand_slots(w);
     if (asked > 0x3FFFFFFFull) break; // beyond what a slot index can name: the host back end takes the batch
-    if (pl_cnt(w.h_cnt, kPlFlags) & kPlFlagCandCap) kr::g_place_paths[kr::kPathRerunCand].fetch_add(1, std::memory_order_relaxed);
-    if (pl_cnt(w.h_cnt, kPlFlags) & kPlFlagKeepCap) {
+    if (pl_cnt(w.h_cnt.get(), kPlFlags) & kPlFlagCandCap) kr::g_place_paths[kr::kPathRerunCand].fetch_add(1, std::memory_order_relaxed);
+    if (pl_cnt(w.h_cnt.get(), kPlFlags) & kPlFlagKeepCap) {
       kr::g_place_paths[kr::kPathRerunKeep].fetch_add(1, std::memory_order_relaxed);
-      w.keep_want_min = (uint64_t)pl_cnt(w.h_cnt, kPlKept) + pl_cnt(w.h_cnt, kPlKept) / 8 + 2048ull * 4ull * kPlKeepChunk;
+      w.keep_want_min = (uint64_t)pl_cnt(w.h_cnt.get(), kPlKept) + pl_cnt(w.h_cnt.get(), kPlKept) / 8 + 2048ull * 4ull * kPlKeepChunk;
     }
     if (!w.dbg_sticky) { // (KR_DEBUG_PLACE_CAPS: the rerun gets what it asked for, as it does from the real sizes)
       if (w.dbg_cand) w.dbg_cand = std::max(w.dbg_cand, asked);
-      if (w.dbg_keep && (pl_cnt(w.h_cnt, kPlFlags) & kPlFlagKeepCap)) w.dbg_keep = std::max(w.dbg_keep, w.keep_want_min);
+      if (w.dbg_keep && (pl_cnt(w.h_cnt.get(), kPlFlags) & kPlFlagKeepCap)) w.dbg_keep = std::max(w.dbg_keep, w.keep_want_min);
     }
     if ((rc = place_size_candidates(s, asked))) return rc;
     if ((rc = kr::place_device_launch(s, T, r0, n, tau, no_filter, chisq))) return rc;
@@ -303,71 +274,58 @@ int kr::place_device_finish(kr_stream* s, const kr::PlaceTreeArrays& T, uint32_t
   { // which paths this range took, and what it asked for (kr_place_path_counters)
     auto set = [](uint32_t k, uint64_t v) { kr::g_place_paths[k].store(v, std::memory_order_relaxed); };
     kr::g_place_paths[kr::kPathRanges].fetch_add(1, std::memory_order_relaxed);
-    if (pl_cnt(w.h_cnt, kPlFlags) & kPlFlagListCut) kr::g_place_paths[kr::kPathListCut].fetch_add(1, std::memory_order_relaxed);
-    set(kr::kPathLastCnt0, pl_cnt(w.h_cnt, kPlCandSlots)), set(kr::kPathLastCnt3, pl_cnt(w.h_cnt, kPlKept)), set(kr::kPathLastCnt12, pl_cnt(w.h_cnt, kPlListSlots));
-    set(kr::kPathLastText, w.text_on ? w.h_ttotal[0] : 0), set(kr::kPathLastCandCap, place_cand_slots(w)), set(kr::kPathLastKeepCap, place_keep_slots(w));
-    set(kr::kPathLastTextCap, w.text_on ? place_text_bytes(w) : 0), set(kr::kPathLastFlags, pl_cnt(w.h_cnt, kPlFlags));
-    set(kr::kPathLastTextFlags, w.text_on ? w.h_ttotal[1] : 0), set(kr::kPathLastAttempts, (uint64_t)attempt + 1);
+    if (pl_cnt(w.h_cnt.get(), kPlFlags) & kPlFlagListCut) kr::g_place_paths[kr::kPathListCut].fetch_add(1, std::memory_order_relaxed);
+    set(kr::kPathLastCnt0, pl_cnt(w.h_cnt.get(), kPlCandSlots)), set(kr::kPathLastCnt3, pl_cnt(w.h_cnt.get(), kPlKept)), set(kr::kPathLastCnt12, pl_cnt(w.h_cnt.get(), kPlListSlots));
+    set(kr::kPathLastText, w.text_on ? w.h_ttotal.get()[0] : 0), set(kr::kPathLastCandCap, place_cand_slots(w)), set(kr::kPathLastKeepCap, place_keep_slots(w));
+    set(kr::kPathLastTextCap, w.text_on ? place_text_bytes(w) : 0), set(kr::kPathLastFlags, pl_cnt(w.h_cnt.get(), kPlFlags));
+    set(kr::kPathLastTextFlags, w.text_on ? w.h_ttotal.get()[1] : 0), set(kr::kPathLastAttempts, (uint64_t)attempt + 1);
   }
   lap("place kernels (both launches, likelihoods, compaction) to their counters on the host");
-  HIP_TRY(hipMemcpyAsync(w.h_c0 + r0, w.d_c0 + r0, (uint64_t)n * 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(w.h_info + r0, w.d_info + r0, (uint64_t)n * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(w.h_c0.get() + r0, w.d_c0.get() + r0, (uint64_t)n * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(w.h_info.get() + r0, w.d_info.get() + r0, (uint64_t)n * 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   out->nreads = n;
 #if KR_PLACE_PROF
-  fprintf(stderr, "[kr place prof] cycles/256 per phase: gather %u, sort %u, ancestors %u, weights %u, leaves %u, accumulate %u\n", pl_cnt(w.h_cnt, kPlProf0), pl_cnt(w.h_cnt, kPlProf0 + 1), pl_cnt(w.h_cnt, kPlProf0 + 2),
-          pl_cnt(w.h_cnt, kPlProf0 + 3), pl_cnt(w.h_cnt, kPlProf0 + 4), pl_cnt(w.h_cnt, kPlProf0 + 5));
+  fprintf(stderr, "[kr place prof] cycles/256 per phase: gather %u, sort %u, ancestors %u, weights %u, leaves %u, accumulate %u\n", pl_cnt(w.h_cnt.get(), kPlProf0), pl_cnt(w.h_cnt.get(), kPlProf0 + 1), pl_cnt(w.h_cnt.get(), kPlProf0 + 2),
+          pl_cnt(w.h_cnt.get(), kPlProf0 + 3), pl_cnt(w.h_cnt.get(), kPlProf0 + 4), pl_cnt(w.h_cnt.get(), kPlProf0 + 5));
 #endif
-  out->overflow = (pl_cnt(w.h_cnt, kPlFlags) & ~kPlFlagListCut) != 0; // (kPlFlagListCut: the internal candidates' list was incomplete -- the likelihood kernel did their minimisations itself)
-  out->heavy_reads = pl_cnt(w.h_cnt, kPlHeavySlots) + pl_cnt(w.h_cnt, kPlInlineReads); // (list slots handed out, in chunks of 8: an upper bound, 0 when there was none; + reads done in global scratch by the first launch)
+  out->overflow = (pl_cnt(w.h_cnt.get(), kPlFlags) & ~kPlFlagListCut) != 0; // (kPlFlagListCut: the internal candidates' list was incomplete -- the likelihood kernel did their minimisations itself)
+  out->heavy_reads = pl_cnt(w.h_cnt.get(), kPlHeavySlots) + pl_cnt(w.h_cnt.get(), kPlInlineReads); // (list slots handed out, in chunks of 8: an upper bound, 0 when there was none; + reads done in global scratch by the first launch)
   if (out->overflow) return KR_OK;
   out->text = nullptr, out->text_len = 0, out->text_flags = 0;
   if (w.text_on) {
-    out->text_flags = w.h_ttotal[1];
+    out->text_flags = w.h_ttotal.get()[1];
     const uint64_t tcap = place_text_bytes(w); // (what the kernels were told)
-    if (w.h_ttotal[0] > tcap) w.text_want_min = w.h_ttotal[0] + w.h_ttotal[0] / 4; // (this range goes to the host; the next batch gets the room)
-    if (w.h_ttotal[1] == 0 && w.h_ttotal[0] <= tcap) { // the range's text is complete: it comes back, the candidates stay
-      const uint64_t tl = w.h_ttotal[0];
-      if (tl > w.h_text_cap) {
-        if (w.h_text) (void)hipHostFree(w.h_text), w.h_text = nullptr, w.h_text_cap = 0;
-        const uint64_t cap = tl + tl / 4 + (1u << 20);
-        HIP_TRY(hipHostMalloc((void**)&w.h_text, cap, hipHostMallocDefault));
-        w.h_text_cap = cap;
-      }
+    if (w.h_ttotal.get()[0] > tcap) w.text_want_min = w.h_ttotal.get()[0] + w.h_ttotal.get()[0] / 4; // (this range goes to the host; the next batch gets the room)
+    if (w.h_ttotal.get()[1] == 0 && w.h_ttotal.get()[0] <= tcap) { // the range's text is complete: it comes back, the candidates stay
+      const uint64_t tl = w.h_ttotal.get()[0];
+      if (tl > w.h_text.size() && (rc = place_grow(w.h_text, tl + tl / 4 + (1u << 20)))) return rc;
       if (tl) {
-        HIP_TRY(hipMemcpyAsync(w.h_text, w.d_text, tl, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(w.h_text.get(), w.d_text.get(), tl, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
       }
-      out->text = w.h_text ? w.h_text : "", out->text_len = tl;
+      out->text = w.h_text.get() ? w.h_text.get() : "", out->text_len = tl;
       out->kept = 0;
-      out->rd_c0 = w.h_c0, out->rd_info = w.h_info;
+      out->rd_c0 = w.h_c0.get(), out->rd_info = w.h_info.get();
       lap("the range's rows as text, back on the host");
       return KR_OK;
     }
   }
-  const uint64_t used = std::min<uint64_t>(pl_cnt(w.h_cnt, kPlKept), place_keep_slots(w)); // the candidates kept (compacted)
-  if (kept_base + used > w.h_cand_cap) { // (an earlier range's candidates have been consumed by the time a later one is finished: nothing to carry over)
-    const uint64_t cap = kept_base + used + used / 4 + 1024;
-    auto pin_renew = [&](auto*& p, uint64_t cnt) -> int {
-      if (p) (void)hipHostFree(p), p = nullptr;
-      HIP_TRY(hipHostMalloc((void**)&p, std::max<uint64_t>(16, cnt * sizeof(*p)), hipHostMallocDefault));
-      return KR_OK;
-    };
-    if ((rc = pin_renew(w.h_cse, cap)) || (rc = pin_renew(w.h_cd, cap)) || (rc = pin_renew(w.h_cv, cap)) || (rc = pin_renew(w.h_cchi, cap))) return rc;
-    w.h_cand_cap = cap;
-  }
+  const uint64_t used = std::min<uint64_t>(pl_cnt(w.h_cnt.get(), kPlKept), place_keep_slots(w)); // the candidates kept (compacted)
+  // (an earlier range's candidates have been consumed by the time a later one is finished: nothing to carry over)
+  if (kept_base + used > w.h_cse.size() && (rc = place_grow_all(kept_base + used + used / 4 + 1024, w.h_cse, w.h_cd, w.h_cv, w.h_cchi))) return rc;
   if (used) {
-    HIP_TRY(hipMemcpyAsync(w.h_cse + kept_base, w.d_kse, used * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(w.h_cd + kept_base, w.d_kd, used * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(w.h_cv + kept_base, w.d_kv, used * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(w.h_cchi + kept_base, w.d_kchi, used * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(w.h_cse.get() + kept_base, w.d_kse.get(), used * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(w.h_cd.get() + kept_base, w.d_kd.get(), used * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(w.h_cv.get() + kept_base, w.d_kv.get(), used * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(w.h_cchi.get() + kept_base, w.d_kchi.get(), used * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
   }
   if (kept_base)
-    for (uint32_t r = r0; r < r0 + n; ++r) w.h_c0[r] += (uint32_t)kept_base;
+    for (uint32_t r = r0; r < r0 + n; ++r) w.h_c0.get()[r] += (uint32_t)kept_base;
   out->kept = used;
   lap("candidates kept, back on the host");
-  out->rd_c0 = w.h_c0, out->rd_info = w.h_info, out->c_se = w.h_cse, out->c_d = w.h_cd, out->c_v = w.h_cv, out->c_chisq = w.h_cchi;
+  out->rd_c0 = w.h_c0.get(), out->rd_info = w.h_info.get(), out->c_se = w.h_cse.get(), out->c_d = w.h_cd.get(), out->c_v = w.h_cv.get(), out->c_chisq = w.h_cchi.get();
   return KR_OK;
 }
 
@@ -379,40 +337,27 @@ int kr::place_device_text_begin(kr_stream* s, const kr::PlaceTreeArrays& T, cons
   kr_stream::PlaceWs& w = s->pw;
   HIP_TRY(hipSetDevice(s->device));
   hipStream_t st = s->lanes[0].stream;
-  auto dev_renew = [&](auto*& p, uint64_t n) -> int {
-    if (p) (void)hipFree(p), p = nullptr;
-    HIP_TRY(hipMalloc((void**)&p, std::max<uint64_t>(16, n * sizeof(*p))));
-    return place_poison(p, std::max<uint64_t>(16, n * sizeof(*p)));
-  };
-  auto pin_renew = [&](auto*& p, uint64_t n) -> int {
-    if (p) (void)hipHostFree(p), p = nullptr;
-    HIP_TRY(hipHostMalloc((void**)&p, std::max<uint64_t>(16, n * sizeof(*p)), hipHostMallocDefault));
-    return KR_OK;
-  };
   int rc = 0;
-  if (w.text_tree_tag != w.tree_tag || !w.d_blen) { // the tree's branch lengths, subtree sizes and labels (once per tree)
+  if (w.text_tree_tag != w.tree_tag || !w.d_blen.get()) { // the tree's branch lengths, subtree sizes and labels (once per tree)
     const uint64_t n1 = (uint64_t)T.pn + 1;
     const uint64_t lb = T.label_off[T.pn + 1];
-    if ((rc = dev_renew(w.d_blen, n1)) || (rc = dev_renew(w.d_card, n1)) || (rc = dev_renew(w.d_label_off, n1 + 1)) || (rc = dev_renew(w.d_labels, lb + 16))) return rc;
-    HIP_TRY(hipMemcpy(w.d_blen, T.blen, n1 * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(w.d_card, T.card, n1 * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(w.d_label_off, T.label_off, (n1 + 1) * 4, hipMemcpyHostToDevice));
-    if (lb) HIP_TRY(hipMemcpy(w.d_labels, T.labels, lb, hipMemcpyHostToDevice));
+    w.text_tree_tag = nullptr;
+    if ((rc = place_renew(w.d_blen, n1)) || (rc = place_renew(w.d_card, n1)) || (rc = place_renew(w.d_label_off, n1 + 1)) || (rc = place_renew(w.d_labels, lb + 16))) return rc;
+    HIP_TRY(hipMemcpy(w.d_blen.get(), T.blen, n1 * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(w.d_card.get(), T.card, n1 * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(w.d_label_off.get(), T.label_off, (n1 + 1) * 4, hipMemcpyHostToDevice));
+    if (lb) HIP_TRY(hipMemcpy(w.d_labels.get(), T.labels, lb, hipMemcpyHostToDevice));
     w.text_tree_tag = w.tree_tag;
   }
   // the reads' ids back to back (lengths and copies by the host pool: 400,000 names are 400,000 pointers to chase)
-  if ((uint64_t)nreads + 1 > w.id_off_cap) {
-    const uint64_t cap = (uint64_t)nreads + nreads / 4 + 16;
-    if ((rc = dev_renew(w.d_id_off, cap)) || (rc = pin_renew(w.h_id_off, cap))) return rc;
-    w.id_off_cap = cap;
-  }
+  if ((uint64_t)nreads + 1 > w.d_id_off.size() && (rc = place_grow_all((uint64_t)nreads + nreads / 4 + 16, w.d_id_off, w.h_id_off))) return rc;
   const int nt = std::max(1, std::min(std::min(kr::parallel_width(), 16), (int)(nreads / 8192)));
   std::vector<uint64_t> part((size_t)nt + 1, 0);
   kr::parallel_for(nt, [&](int t) {
     uint64_t sum = 0;
     for (size_t r = (size_t)nreads * t / nt; r < (size_t)nreads * (t + 1) / nt; ++r) {
       const uint32_t l = (uint32_t)strlen(names[r]);
-      w.h_id_off[r + 1] = l; // (lengths first; offsets below)
+      w.h_id_off.get()[r + 1] = l; // (lengths first; offsets below)
       sum += l;
     }
     part[(size_t)t + 1] = sum;
@@ -420,44 +365,29 @@ int kr::place_device_text_begin(kr_stream* s, const kr::PlaceTreeArrays& T, cons
   for (int t = 0; t < nt; ++t) part[(size_t)t + 1] += part[(size_t)t];
   const uint64_t total = part[(size_t)nt];
   if (total >= 0xFFFFFFF0ull) return kr::fail(KR_ERR_CAPACITY, "place: more than 4 GB of read ids in one batch");
-  if (total + 16 > w.ids_cap) {
-    const uint64_t cap = total + total / 4 + 4096;
-    if ((rc = dev_renew(w.d_ids, cap)) || (rc = pin_renew(w.h_ids, cap))) return rc;
-    w.ids_cap = cap;
-  }
-  w.h_id_off[0] = 0;
+  if (total + 16 > w.d_ids.size() && (rc = place_grow_all(total + total / 4 + 4096, w.d_ids, w.h_ids))) return rc;
+  w.h_id_off.get()[0] = 0;
   kr::parallel_for(nt, [&](int t) {
     uint64_t at = part[(size_t)t];
     for (size_t r = (size_t)nreads * t / nt; r < (size_t)nreads * (t + 1) / nt; ++r) {
-      const uint32_t l = w.h_id_off[r + 1];
-      memcpy(w.h_ids + at, names[r], l);
+      const uint32_t l = w.h_id_off.get()[r + 1];
+      memcpy(w.h_ids.get() + at, names[r], l);
       at += l;
-      w.h_id_off[r + 1] = (uint32_t)at;
+      w.h_id_off.get()[r + 1] = (uint32_t)at;
     }
   });
-  HIP_TRY(hipMemcpyAsync(w.d_id_off, w.h_id_off, ((uint64_t)nreads + 1) * 4, hipMemcpyHostToDevice, st));
-  if (total) HIP_TRY(hipMemcpyAsync(w.d_ids, w.h_ids, total, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(w.d_id_off.get(), w.h_id_off.get(), ((uint64_t)nreads + 1) * 4, hipMemcpyHostToDevice, st));
+  if (total) HIP_TRY(hipMemcpyAsync(w.d_ids.get(), w.h_ids.get(), total, hipMemcpyHostToDevice, st));
   // per-read lengths, block sums, the text itself: room for the ids and 512 bytes of rows a read (a range with more comes back
   // with flag 2 and is formatted by the host)
-  if (nreads > w.tlen_cap) {
-    const uint64_t cap = (uint64_t)nreads + nreads / 4 + 16;
-    if ((rc = dev_renew(w.d_tlen, cap)) || (rc = dev_renew(w.d_tbsum, cap / kPlTextBlock + 4))) return rc;
-    w.tlen_cap = cap;
-  }
-  if (!w.d_ttotal && ((rc = dev_renew(w.d_ttotal, 2)) || (rc = pin_renew(w.h_ttotal, 2)))) return rc;
+  if (nreads > w.d_tlen.size() && (rc = place_grow(w.d_tlen, (uint64_t)nreads + nreads / 4 + 16))) return rc;
+  if ((rc = place_grow(w.d_tbsum, w.d_tlen.size() / kPlTextBlock + 4)) || (rc = place_grow_all(2, w.d_ttotal, w.h_ttotal))) return rc; // (the block sums: sized by the lengths' array)
   const uint64_t want = std::max<uint64_t>(w.dbg_text ? w.dbg_text : total + (uint64_t)nreads * 512ull + (1u << 20), w.text_want_min); // (text_want_min: what a range that outgrew the buffer asked for)
-  if (want > w.text_cap) {
-    if ((rc = dev_renew(w.d_text, want))) return rc;
-    w.text_cap = want;
-  }
-  if (nreads > w.rtotal_cap) {
-    const uint64_t cap = (uint64_t)nreads + nreads / 4 + 16;
-    if ((rc = dev_renew(w.d_rtotal, cap)) || (rc = dev_renew(w.d_rbest, cap))) return rc;
-    w.rtotal_cap = cap;
-  }
+  if ((rc = place_grow(w.d_text, want))) return rc;
+  if (nreads > w.d_rtotal.size() && (rc = place_grow_all((uint64_t)nreads + nreads / 4 + 16, w.d_rtotal, w.d_rbest))) return rc;
   w.text_tabular = tabular ? 1u : 0u, w.text_multi = multi ? 1u : 0u;
   w.text_on = true;
-  return place_size_candidates(s, w.cand_cap); // (the sorted copy of the kept candidates: sized with them, now and when a range is run again)
+  return place_size_candidates(s, w.d_cse.size()); // (the sorted copy of the kept candidates: sized with them, now and when a range is run again)
 }
 void kr::place_device_abort(kr_stream* s)
 {

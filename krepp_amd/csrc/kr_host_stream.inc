@@ -60,60 +60,67 @@ struct kr_stream {
   uint8_t* d_bases = nullptr;
   uint64_t* d_offsets = nullptr; // [max_reads + max_lanes]: every lane has its own nreads + 1 entries
   BatchOut out;                  // the stream-wide arrays (and the constants every lane copies)
+  // Who owns what: buffers that live as long as the stream are allocated by salloc / halloc into these two lists and freed in bulk
+  // by kr_stream_destroy -- the lists are append-only, nothing is ever taken out of them; every buffer that grows with the batches
+  // is a DevBuf / PinBuf (kr_buf.h) that frees itself; the structs handed to kernels hold raw pointers filled from get()
   std::vector<void*> dallocs;
+  size_t nfresh = 0;             // device buffers made so far, the item lists included (KR_DEBUG_POISON=<k> names the k-th)
+  DevBuf<uint2> items;           // out.items: the item list in use (ItemPlacement may exchange it for another)
+  DevBuf<kr_hit> d_hits;         // out.hits, made by the first KR_TAP_HITS batch
   // pinned host
   uint8_t* h_bases = nullptr;
   uint64_t* h_offsets = nullptr;
   uint32_t h_counters[kCounterWords] = {0}; // the lanes' counters combined (kCounterRules)
   uint32_t *h_rd_off = nullptr, *h_rd_cnt = nullptr, *h_rd_onmers = nullptr, *h_rd_filt = nullptr;
   uint8_t* h_rd_na = nullptr;
-  uint32_t *h_rec_key = nullptr, *h_rec_hist = nullptr;
-  uint8_t* h_rec_sel = nullptr;
-  double *h_rec_d = nullptr, *h_rec_v = nullptr, *h_rec_chisq = nullptr;
-  kr_hit* h_hits = nullptr;
   std::vector<void*> hallocs;
+  // the records' host arrays grow on demand in kr_batch_collect (all of h_rec_key's size; hist: np times that)
+  PinBuf<uint32_t> h_rec_key, h_rec_hist;
+  PinBuf<uint8_t> h_rec_sel;
+  PinBuf<double> h_rec_d, h_rec_v, h_rec_chisq;
+  PinBuf<kr_hit> h_hits;
   // `place` back end on the device (kr::place_on_device): the placement tree as device arrays (for one tree at a
   // time), per-read / per-candidate outputs and their page-locked mirrors; grown on demand
   struct PlaceWs {
     const void* tree_tag = nullptr;
     uint32_t pn = 0, nidx = 0;
-    uint32_t *d_parent = nullptr, *d_eff = nullptr, *d_lo = nullptr, *d_idx_to_pt = nullptr, *d_depth = nullptr;
+    DevBuf<uint32_t> d_parent, d_eff, d_lo, d_idx_to_pt, d_depth;
     uint32_t cu_count = 0;
-    uint4* d_node = nullptr; // {parent, lo, eff, depth} of every node: one 16-byte load per level of a walk up the tree
-    double* d_chain = nullptr; // per wave of kr_place_kernel: the weights of every (leaf, ancestor) pair of the read in hand
+    DevBuf<uint4> d_node; // {parent, lo, eff, depth} of every node: one 16-byte load per level of a walk up the tree
+    DevBuf<double> d_chain; // per wave of kr_place_kernel: the weights of every (leaf, ancestor) pair of the read in hand
     uint32_t chain_cap = 0, chain_waves = 0;
-    uint8_t* d_elig = nullptr;
-    uint32_t *d_len = nullptr, *d_c0 = nullptr, *d_info = nullptr, *d_cse = nullptr, *d_cread = nullptr, *d_cnt = nullptr;
-    double *d_cd = nullptr, *d_cv = nullptr, *d_cchi = nullptr, *d_cprob = nullptr, *d_rprob = nullptr;
-    uint32_t* d_kse = nullptr; // the candidates that pass the chi-square test, compacted (kr_place_compact_kernel)
-    double *d_kd = nullptr, *d_kv = nullptr, *d_kchi = nullptr;
-    uint64_t keep_cap = 0, keep_want_min = 0; // (keep_want_min: what a batch that ran out of kept-candidate slots asked for)
-    uint64_t cprob_cap = 0, rprob_cap = 0; // doubles
-    uint32_t *d_heavy = nullptr, *d_heavy_u32 = nullptr; // reads beyond the LDS arrays of kr_place_kernel: their list, the second launch's scratch
-    double* d_heavy_f64 = nullptr;
-    uint64_t heavy_cap = 0;                              // list entries
+    DevBuf<uint8_t> d_elig;
+    DevBuf<uint32_t> d_len, d_c0, d_info; // per read: one capacity, with h_len / h_c0 / h_info
+    DevBuf<uint32_t> d_cse, d_cread;      // per candidate slot: one capacity, with d_cd / d_cv / d_cchi
+    DevBuf<uint32_t> d_cnt;
+    DevBuf<double> d_cd, d_cv, d_cchi, d_cprob, d_rprob;
+    DevBuf<uint32_t> d_kse; // the candidates that pass the chi-square test, compacted (kr_place_compact_kernel); one capacity with d_kd / d_kv / d_kchi
+    DevBuf<double> d_kd, d_kv, d_kchi;
+    uint64_t keep_want_min = 0; // what a batch that ran out of kept-candidate slots asked for
+    DevBuf<uint32_t> d_heavy, d_heavy_u32; // reads beyond the LDS arrays of kr_place_kernel: their list, the second launch's scratch
+    DevBuf<double> d_heavy_f64;
     uint32_t heavy_leaves = 0, heavy_nodes = 0, heavy_waves = 0;
-    uint32_t *h_len = nullptr, *h_c0 = nullptr, *h_info = nullptr, *h_cse = nullptr, *h_cnt = nullptr;
-    double *h_cd = nullptr, *h_cv = nullptr, *h_cchi = nullptr;
-    uint64_t reads_cap = 0, cand_cap = 0, h_cand_cap = 0;
+    PinBuf<uint32_t> h_len, h_c0, h_info, h_cse, h_cnt; // (h_cse: one capacity with h_cd / h_cv / h_cchi)
+    PinBuf<double> h_cd, h_cv, h_cchi;
     // rows as text on the device (round 6)
     const void* text_tree_tag = nullptr; // the tree whose branch lengths, subtree sizes and labels are uploaded
-    double* d_blen = nullptr;
-    uint32_t *d_card = nullptr, *d_label_off = nullptr;
-    char* d_labels = nullptr;
+    DevBuf<double> d_blen;
+    DevBuf<uint32_t> d_card, d_label_off;
+    DevBuf<char> d_labels;
     bool text_on = false; // this batch's ranges are formatted on the device
     uint32_t text_tabular = 0, text_multi = 1;
-    char *d_ids = nullptr, *h_ids = nullptr;
-    uint32_t *d_id_off = nullptr, *h_id_off = nullptr;
-    uint64_t ids_cap = 0, id_off_cap = 0;
-    uint32_t* d_tlen = nullptr;
-    uint64_t *d_tbsum = nullptr, *d_ttotal = nullptr, *h_ttotal = nullptr;
-    uint64_t tlen_cap = 0;
-    char *d_text = nullptr, *h_text = nullptr;
-    uint64_t text_cap = 0, h_text_cap = 0, text_want_min = 0;
-    uint32_t *d_sse = nullptr, *d_rbest = nullptr; // the kept candidates sorted by node (same slots as d_kse ...), per-read --no-multi choice
-    double *d_sd = nullptr, *d_sv = nullptr, *d_sc = nullptr, *d_rtotal = nullptr;
-    uint64_t sorted_cap = 0, rtotal_cap = 0;
+    DevBuf<char> d_ids;
+    PinBuf<char> h_ids;
+    DevBuf<uint32_t> d_id_off;
+    PinBuf<uint32_t> h_id_off;
+    DevBuf<uint32_t> d_tlen;
+    DevBuf<uint64_t> d_tbsum, d_ttotal;
+    PinBuf<uint64_t> h_ttotal;
+    DevBuf<char> d_text;
+    PinBuf<char> h_text;
+    uint64_t text_want_min = 0;
+    DevBuf<uint32_t> d_sse, d_rbest; // the kept candidates sorted by node (same slots as d_kse ...), per-read --no-multi choice
+    DevBuf<double> d_sd, d_sv, d_sc, d_rtotal;
     // KR_DEBUG_PLACE_CAPS (tests; place_device_begin reads it per batch): what the kernels are told the candidate slots, the kept
     // slots and the text buffer hold, 0 = what they do hold; `dbg_sticky`: a range that is run again is given no more
     uint64_t dbg_cand = 0, dbg_keep = 0, dbg_text = 0, dbg_list = 0; // (dbg_list: entries of the kept slots the internal candidates' list may take)
@@ -124,14 +131,16 @@ struct kr_stream {
   struct Tiles {
     bool active = false;   // the batch in flight is tiled: `nreads` real reads, `nv` reads on the device
     uint32_t nv = 0, nlong = 0;
-    uint32_t cap = 0;      // reads the arrays below hold (= max_reads)
-    uint64_t bases_cap = 0;
-    uint8_t *h_bases = nullptr, *d_bases = nullptr; // the tiled batch's bases (tiles overlap by k - 1)
-    uint64_t *h_voff = nullptr, *d_voff = nullptr;  // [cap + 1]
-    uint8_t *h_vtile = nullptr, *d_vtile = nullptr; // [cap]
-    uint32_t *h_rfirst = nullptr, *d_rfirst = nullptr, *h_longs = nullptr, *d_longs = nullptr;
-    uint32_t *d_tile_filt = nullptr, *d_real_off = nullptr, *d_real_cnt = nullptr, *d_real_onmers = nullptr, *d_real_filt = nullptr;
-    uint8_t* d_real_na = nullptr;
+    PinBuf<uint8_t> h_bases; // the tiled batch's bases (tiles overlap by k - 1); one capacity with d_bases
+    DevBuf<uint8_t> d_bases;
+    PinBuf<uint64_t> h_voff; // [max_reads + 1]
+    DevBuf<uint64_t> d_voff;
+    PinBuf<uint8_t> h_vtile; // [max_reads], as every array below (h_longs, d_longs and the two filt arrays: two words a read)
+    DevBuf<uint8_t> d_vtile;
+    PinBuf<uint32_t> h_rfirst, h_longs;
+    DevBuf<uint32_t> d_rfirst, d_longs;
+    DevBuf<uint32_t> d_tile_filt, d_real_off, d_real_cnt, d_real_onmers, d_real_filt;
+    DevBuf<uint8_t> d_real_na;
   } tiles;
   bool no_tiles = false;   // (a tiled batch that overflowed a device buffer is run again untiled)
   std::vector<uint8_t> tile_choice; // per read of the batch in hand: submitted as tiles
@@ -142,7 +151,7 @@ struct kr_stream {
   // batches tries a few allocations during its first batches and keeps the one its scan ran fastest on.
   struct ItemPlacement {
     int trials_left = -1;       // -1: KR_ITEM_PLACEMENT_TRIALS not read yet
-    uint2* aside = nullptr;     // the best list so far, set aside while another one is in use
+    DevBuf<uint2> aside;        // the best list so far, set aside while another one is in use (exchanged with kr_stream::items)
     double best_ns = 0;         // its scan time per read
     uint32_t tried = 0, kept_new = 0;
     int settling = 2;           // launches of the list in use that are not measured yet: a list's first launch is ~6 ms slower than its
@@ -160,8 +169,9 @@ struct kr_stream {
     uint32_t id_sep = 0;
     uint32_t* d_tlen = nullptr;
     uint64_t *d_bsum = nullptr, *d_total = nullptr, *h_total = nullptr;
-    char *d_text = nullptr, *h_text = nullptr;
-    uint64_t text_cap = 0, id_bytes = 0, h_text_cap = 0; // (h_text: made by the first batch that needs it, as large as that batch's text asks)
+    char* d_text = nullptr;
+    PinBuf<char> h_text; // (made by the first batch that needs it, as large as that batch's text asks)
+    uint64_t text_cap = 0, id_bytes = 0;
     bool ids_on_device = false; // the batch's ids were written into d_ids / d_id_off by the record finder (kr_batch_submit_fastq)
   } text;
   // FASTQ records found on the device (kr_dev_fastq.inc; kr_stream_fastq_enable)
@@ -183,13 +193,12 @@ struct kr_stream {
   const uint8_t* sub_bases = nullptr; // the arguments of the submit in flight (host buffers stay valid until wait / collect returns)
   const uint64_t* sub_offsets = nullptr;
   // state
-  uint64_t h_rec_cap = 0; // pinned record buffers grow on demand in kr_batch_collect
-  bool h_rec_full = false; // ... and hold v / chisq / hist only once a batch asked for them
+  bool h_rec_full = false; // the pinned record buffers hold v / chisq / hist only once a batch asked for them
   bool rows_mode = false;  // the batch in flight leaves the device as compact rows (KR_ROWS_ONLY, no taps, not tiled)
   bool rows_indexed = false; // ... of 8 bytes: (key, index into the batch's distinct DIST values) -- KR_ROWS_INDEXED
-  uint32_t* h_rec_dix = nullptr; // [h_rec_cap] page-locked, allocated with the first indexed batch
-  double* h_dist_list = nullptr; // [h_dist_cap]
-  uint64_t h_dist_cap = 0, ndist = 0;
+  PinBuf<uint32_t> h_rec_dix; // of h_rec_key's size, allocated with the first indexed batch
+  PinBuf<double> h_dist_list;
+  uint64_t ndist = 0;
   uint64_t d2h_bytes = 0;    // what the last kr_batch_collect copied back
   uint64_t h_sel_ones = 0; // leading entries of h_rec_sel known to hold 1 (rows-mode views: every row is selected)
   bool submitted = false, waited = false, collected = false;
@@ -208,15 +217,13 @@ int salloc(kr_stream* s, T** p, uint64_t n)
 {
   HIP_TRY(hipMalloc((void**)p, std::max<uint64_t>(16, n * sizeof(T))));
   s->dallocs.push_back(*p);
-  if (const char* e = getenv("KR_DEBUG_POISON")) { // tests: nothing may depend on what a fresh buffer holds ("all": every buffer; a number: the k-th of the stream)
-    if (!strcmp(e, "all") || (size_t)atoi(e) == s->dallocs.size()) {
-      HIP_TRY(hipMemset(*p, 0xA5, std::max<uint64_t>(16, n * sizeof(T))));
-      // a device memset may return before it has run, and the lanes' streams do not wait for the null stream: without this the
-      // fill could land AFTER the clear of a buffer that kr_stream_create zeroes on a lane's stream (the spill accumulators)
-      HIP_TRY(hipDeviceSynchronize());
-    }
-  }
-  return KR_OK;
+  return poison_fresh(*p, std::max<uint64_t>(16, n * sizeof(T)), ++s->nfresh);
+}
+// An item list (kr_stream::items, or a trial's): counted and poisoned like the arena's buffers, owned by the caller's Buf
+int new_item_list(kr_stream* s, DevBuf<uint2>& list)
+{
+  if (!list.renew(s->item_cap)) return alloc_failed("item list");
+  return poison_fresh(list.get(), list.bytes(), ++s->nfresh);
 }
 template <typename T>
 int halloc(kr_stream* s, T** p, uint64_t n)
@@ -249,7 +256,7 @@ BatchOut result_out(const kr_stream* s)
   BatchOut o = s->out;
   if (s->tiles.active) {
     const kr_stream::Tiles& t = s->tiles;
-    o.rd_off = t.d_real_off, o.rd_cnt = t.d_real_cnt, o.rd_onmers = t.d_real_onmers, o.rd_filt = t.d_real_filt, o.rd_na = t.d_real_na;
+    o.rd_off = t.d_real_off.get(), o.rd_cnt = t.d_real_cnt.get(), o.rd_onmers = t.d_real_onmers.get(), o.rd_filt = t.d_real_filt.get(), o.rd_na = t.d_real_na.get();
   }
   return o;
 }
@@ -280,61 +287,41 @@ int build_tiles(kr_stream* s, const uint8_t* bases, const uint64_t* offsets, uin
   if (nlong == 0) return KR_OK; // nothing to tile (or no room for a single sequence's tiles)
   kr_stream::Tiles& t = s->tiles;
   HIP_TRY(hipSetDevice(s->device));
-  if (!t.cap) {
+  { // the per-read arrays, made by the first tiled batch.  A group that cannot be had is left empty (the submit reports the error, the
+    // stream stays usable) and the next tiled batch asks again
     const uint64_t c = s->max_reads;
-    // all or nothing: an allocation that fails part-way gives back what the ones before it took (the submit reports the error,
-    // the stream stays usable, and the next tiled batch starts from a clean slate)
-    hipError_t e = hipSuccess;
-    auto host = [&](auto** p, uint64_t bytes) { if (e == hipSuccess) e = hipHostMalloc((void**)p, bytes, hipHostMallocDefault); };
-    auto dev = [&](auto** p, uint64_t bytes) { if (e == hipSuccess) e = hipMalloc((void**)p, bytes); };
-    host(&t.h_voff, (c + 1) * 8), host(&t.h_vtile, c), host(&t.h_rfirst, c * 4), host(&t.h_longs, c * 8);
-    dev(&t.d_voff, (c + 1) * 8), dev(&t.d_vtile, c), dev(&t.d_rfirst, c * 4), dev(&t.d_longs, c * 8), dev(&t.d_tile_filt, c * 8);
-    dev(&t.d_real_off, c * 4), dev(&t.d_real_cnt, c * 4), dev(&t.d_real_onmers, c * 4), dev(&t.d_real_filt, c * 8), dev(&t.d_real_na, c);
-    if (e != hipSuccess) {
-      for (void* p : {(void*)t.h_voff, (void*)t.h_vtile, (void*)t.h_rfirst, (void*)t.h_longs})
-        if (p) (void)hipHostFree(p);
-      for (void* p : {(void*)t.d_voff, (void*)t.d_vtile, (void*)t.d_rfirst, (void*)t.d_longs, (void*)t.d_tile_filt, (void*)t.d_real_off, (void*)t.d_real_cnt,
-                      (void*)t.d_real_onmers, (void*)t.d_real_filt, (void*)t.d_real_na})
-        if (p) (void)hipFree(p);
-      t.h_voff = nullptr, t.h_vtile = nullptr, t.h_rfirst = nullptr, t.h_longs = nullptr;
-      t.d_voff = nullptr, t.d_vtile = nullptr, t.d_rfirst = nullptr, t.d_longs = nullptr, t.d_tile_filt = nullptr, t.d_real_off = nullptr,
-      t.d_real_cnt = nullptr, t.d_real_onmers = nullptr, t.d_real_filt = nullptr, t.d_real_na = nullptr;
-      (void)hipGetLastError();
-      return kr::fail(e == hipErrorOutOfMemory ? KR_ERR_NOMEM : KR_ERR_NO_DEVICE, std::string("build_tiles: ") + hipGetErrorString(e));
-    }
-    t.cap = s->max_reads;
+    if (!reserve_all(c + 1, t.h_voff, t.d_voff) ||
+        !reserve_all(c, t.h_vtile, t.h_rfirst, t.d_vtile, t.d_rfirst, t.d_real_off, t.d_real_cnt, t.d_real_onmers, t.d_real_na) ||
+        !reserve_all(2 * c, t.h_longs, t.d_longs, t.d_tile_filt, t.d_real_filt))
+      return alloc_failed("build_tiles");
   }
-  if (nb + 256 > t.bases_cap) {
-    if (t.h_bases) (void)hipHostFree(t.h_bases), t.h_bases = nullptr;
-    if (t.d_bases) (void)hipFree(t.d_bases), t.d_bases = nullptr;
-    t.bases_cap = 0;
-    const uint64_t c = nb + nb / 4 + 256;
-    HIP_TRY(hipHostMalloc((void**)&t.h_bases, c, hipHostMallocDefault));
-    HIP_TRY(hipMalloc((void**)&t.d_bases, c));
-    t.bases_cap = c;
-  }
+  if (nb + 256 > t.h_bases.size() && !reserve_all(nb + nb / 4 + 256, t.h_bases, t.d_bases)) return alloc_failed("build_tiles");
+  uint8_t* const h_bases = t.h_bases.get();
+  uint64_t* const h_voff = t.h_voff.get();
+  uint8_t* const h_vtile = t.h_vtile.get();
+  uint32_t *const h_rfirst = t.h_rfirst.get(), *const h_longs = t.h_longs.get();
   uint64_t v = 0, pos = 0;
   uint32_t li = 0;
   for (uint32_t r = 0; r < nreads; ++r) {
     const uint8_t* src = bases + offsets[r];
     const uint64_t len = offsets[r + 1] - offsets[r], nkm = len >= k ? len - k + 1 : 0;
-    t.h_rfirst[r] = (uint32_t)v;
+    h_rfirst[r] = (uint32_t)v;
     if (tile_it[r]) {
       const uint64_t nt = (nkm + kSegPos - 1) / kSegPos;
-      t.h_longs[2 * li] = (uint32_t)v, t.h_longs[2 * li + 1] = (uint32_t)nt, ++li;
+      h_longs[2 * li] = (uint32_t)v, h_longs[2 * li + 1] = (uint32_t)nt, ++li;
       for (uint64_t ti = 0; ti < nt; ++ti) { // tile ti: k-mer positions [ti * kSegPos, ...), bases from the first one's start
         const uint64_t b0 = ti * kSegPos, b1 = std::min<uint64_t>(len, b0 + kSegPos + k - 1);
-        memcpy(t.h_bases + pos, src + b0, b1 - b0);
-        t.h_voff[v] = pos, t.h_vtile[v] = 1, ++v;
+        memcpy(h_bases + pos, src + b0, b1 - b0);
+        h_voff[v] = pos, h_vtile[v] = 1, ++v;
         pos += b1 - b0;
       }
     } else {
-      memcpy(t.h_bases + pos, src, len);
-      t.h_voff[v] = pos, t.h_vtile[v] = 0, ++v;
+      memcpy(h_bases + pos, src, len);
+      h_voff[v] = pos, h_vtile[v] = 0, ++v;
       pos += len;
     }
   }
-  t.h_voff[v] = pos;
+  h_voff[v] = pos;
   t.nv = (uint32_t)v, t.nlong = nlong;
   *tiled = true;
   return KR_OK;
@@ -376,8 +363,8 @@ void with_scan_shape(uint32_t slot_log2w, uint32_t log_g, F&& f)
 TileBatch tile_batch(const kr_stream* s)
 {
   const kr_stream::Tiles& tl = s->tiles;
-  return TileBatch{tl.d_vtile, tl.d_longs, tl.d_rfirst, tl.d_tile_filt, tl.nv, tl.nlong, s->nreads,
-                   tl.d_real_off, tl.d_real_cnt, tl.d_real_onmers, tl.d_real_filt, tl.d_real_na};
+  return TileBatch{tl.d_vtile.get(), tl.d_longs.get(), tl.d_rfirst.get(), tl.d_tile_filt.get(), tl.nv, tl.nlong, s->nreads,
+                   tl.d_real_off.get(), tl.d_real_cnt.get(), tl.d_real_onmers.get(), tl.d_real_filt.get(), tl.d_real_na.get()};
 }
 
 // The stages of a lane's batch, each queued on the lane's stream (everything a stage needs is in L.in / L.out); launch_lane calls
@@ -495,7 +482,7 @@ int launch_rows_text(kr_stream* s, Lane& L)
   if (o.rows_indexed) hipLaunchKernelGGL(kr_rows_dlist_kernel, dim3(2048), dim3(256), 0, st, o);
   if (s->text.req) { // ... and as text (kr_dev_text.inc): lengths, block offsets, bytes
     kr_stream::Text& tx = s->text;
-    TextIO t{tx.d_ids, tx.d_id_off, tx.id_sep, s->ix->d_names, s->ix->d_name_off, tx.d_tlen, tx.d_bsum, tx.d_text, tx.text_cap, tx.d_total};
+    TextIO t{tx.d_ids, tx.d_id_off, tx.id_sep, s->ix->d_names.get(), s->ix->d_name_off.get(), tx.d_tlen, tx.d_bsum, tx.d_text, tx.text_cap, tx.d_total};
     HIP_TRY(hipMemsetAsync(tx.d_total, 0, 16, st));
     hipLaunchKernelGGL(kr_text_len_kernel, dim3(std::min<uint32_t>(nblk, 8192u)), dim3(256), 0, st, o, t, nreads);
     hipLaunchKernelGGL(kr_text_bscan_kernel, dim3(1), dim3(1024), 0, st, t, nreads);
@@ -694,7 +681,8 @@ int kr_stream_create(const kr_index* ix, const kr_params* p, uint32_t max_reads,
     s->scan_blocks = s->scan_pipe_blocks = s->scan_filt_blocks = (uint32_t)prop.multiProcessorCount * (uint32_t)std::max(1, atoi(e));
   s->fk = ix->slot_log2w == kSlotFilter && p->hdist_th <= kFiltMaxTh && !getenv("KR_NO_FILTER_SCAN");
   s->item_cap = (uint32_t)std::min<uint64_t>((uint64_t)max_reads * 256u + (uint64_t)ML * std::max(std::max(s->scan_blocks, s->scan_pipe_blocks), s->scan_filt_blocks) * kScanWaves * 2u * kItemChunk, 1ull << 31);
-  SA(o.items, s->item_cap);
+  if ((rc = new_item_list(s.get(), s->items))) { kr_stream_destroy(s.release()); return rc; }
+  o.items = s->items.get();
   SA(o.rd_it_off, max_reads);
   SA(o.rd_it_cnt, max_reads);
   SA(o.long_list, (uint64_t)max_reads + 16ull * s->nwaves * ML);
@@ -778,26 +766,6 @@ void kr_stream_destroy(kr_stream* s)
   (void)hipSetDevice(s->device);
   for (auto& L : s->lanes)
     if (L.stream) (void)hipStreamSynchronize(L.stream);
-  {
-    kr_stream::PlaceWs& w = s->pw;
-    for (void* p : {(void*)w.d_parent, (void*)w.d_eff, (void*)w.d_lo, (void*)w.d_idx_to_pt, (void*)w.d_depth, (void*)w.d_node, (void*)w.d_chain, (void*)w.d_elig, (void*)w.d_len, (void*)w.d_c0,
-                    (void*)w.d_info, (void*)w.d_cse, (void*)w.d_cread, (void*)w.d_cnt, (void*)w.d_cd, (void*)w.d_cv, (void*)w.d_cchi, (void*)w.d_cprob,
-                    (void*)w.d_rprob, (void*)w.d_heavy, (void*)w.d_heavy_u32, (void*)w.d_heavy_f64, (void*)w.d_kse, (void*)w.d_kd, (void*)w.d_kv, (void*)w.d_kchi,
-                    (void*)w.d_blen, (void*)w.d_card, (void*)w.d_label_off, (void*)w.d_labels, (void*)w.d_ids, (void*)w.d_id_off, (void*)w.d_tlen, (void*)w.d_tbsum,
-                    (void*)w.d_ttotal, (void*)w.d_text, (void*)w.d_sse, (void*)w.d_rbest, (void*)w.d_sd, (void*)w.d_sv, (void*)w.d_sc, (void*)w.d_rtotal})
-      if (p) (void)hipFree(p);
-    for (void* p : {(void*)w.h_len, (void*)w.h_c0, (void*)w.h_info, (void*)w.h_cse, (void*)w.h_cnt, (void*)w.h_cd, (void*)w.h_cv, (void*)w.h_cchi, (void*)w.h_ids, (void*)w.h_id_off,
-                    (void*)w.h_ttotal, (void*)w.h_text})
-      if (p) (void)hipHostFree(p);
-  }
-  {
-    kr_stream::Tiles& t = s->tiles;
-    for (void* p : {(void*)t.d_bases, (void*)t.d_voff, (void*)t.d_vtile, (void*)t.d_rfirst, (void*)t.d_longs, (void*)t.d_tile_filt, (void*)t.d_real_off,
-                    (void*)t.d_real_cnt, (void*)t.d_real_onmers, (void*)t.d_real_filt, (void*)t.d_real_na})
-      if (p) (void)hipFree(p);
-    for (void* p : {(void*)t.h_bases, (void*)t.h_voff, (void*)t.h_vtile, (void*)t.h_rfirst, (void*)t.h_longs})
-      if (p) (void)hipHostFree(p);
-  }
   for (void* p : s->dallocs) (void)hipFree(p);
   for (void* p : s->hallocs) (void)hipHostFree(p);
   for (auto& L : s->lanes) {
@@ -806,7 +774,7 @@ void kr_stream_destroy(kr_stream* s)
     if (L.stream) (void)hipStreamDestroy(L.stream);
   }
   for (hipStream_t st : s->moved_streams) (void)hipStreamDestroy(st);
-  delete s;
+  delete s; // (every DevBuf / PinBuf of the stream frees itself here: the device is set, the lanes' streams have been waited for)
 }
 
 static int submit_batch(kr_stream* s, const uint8_t* bases, const uint64_t* offsets, uint32_t nreads, uint32_t flags);
@@ -827,7 +795,7 @@ int kr_stream_text_enable(kr_stream* s, const kr_host_index* h, uint64_t max_tex
   const kr_index* ix = s->ix;
   { // the node names, once per index
     std::lock_guard<std::mutex> lk(ix->chain_mu);
-    if (!ix->d_names) {
+    if (!ix->d_names.get()) {
       const uint32_t nn = ix->dix.tree_nnodes;
       std::vector<uint32_t> off((size_t)nn + 2, 0);
       std::string blob;
@@ -836,17 +804,14 @@ int kr_stream_text_enable(kr_stream* s, const kr_host_index* h, uint64_t max_tex
         blob += kr_host_index_node_name(h, se);
       }
       off[(size_t)nn + 1] = (uint32_t)blob.size();
-      char* dn = nullptr;
-      uint32_t* dofs = nullptr;
-      HIP_TRY(hipMalloc((void**)&dn, std::max<size_t>(16, blob.size())));
-      if (hipMalloc((void**)&dofs, off.size() * 4) != hipSuccess) {
-        (void)hipFree(dn);
-        return kr::fail(KR_ERR_NOMEM, "kr_stream_text_enable: out of device memory");
-      }
-      HIP_TRY(hipMemcpy(dn, blob.data(), blob.size(), hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(dofs, off.data(), off.size() * 4, hipMemcpyHostToDevice));
-      ix->d_name_off = dofs;
-      ix->d_names = dn; // (freed with the index)
+      DevBuf<char> dn; // (local until both are filled: an early return frees them)
+      DevBuf<uint32_t> dofs;
+      if (!dn.reserve(blob.size())) return alloc_failed("kr_stream_text_enable: node names");
+      if (!dofs.reserve(off.size())) return kr::fail(KR_ERR_NOMEM, "kr_stream_text_enable: out of device memory");
+      HIP_TRY(hipMemcpy(dn.get(), blob.data(), blob.size(), hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(dofs.get(), off.data(), off.size() * 4, hipMemcpyHostToDevice));
+      ix->d_name_off.swap(dofs);
+      ix->d_names.swap(dn); // (freed with the index)
     }
   }
   kr_stream::Text& t = s->text;
@@ -905,21 +870,11 @@ int kr_batch_collect_text(kr_stream* s, const char** text, uint64_t* len)
   HIP_TRY(hipSetDevice(s->ix->device));
   const uint64_t n = t.h_total[0];
   if (n) {
-    if (n > t.h_text_cap) {
-      if (t.h_text) {
-        s->hallocs.erase(std::remove(s->hallocs.begin(), s->hallocs.end(), (void*)t.h_text), s->hallocs.end());
-        (void)hipHostFree(t.h_text);
-        t.h_text = nullptr, t.h_text_cap = 0;
-      }
-      const uint64_t cap = std::min<uint64_t>(t.text_cap, n + n / 4 + (1u << 20));
-      int rc2 = halloc(s, &t.h_text, cap);
-      if (rc2) return rc2;
-      t.h_text_cap = cap;
-    }
-    HIP_TRY(hipMemcpyAsync(t.h_text, t.d_text, n, hipMemcpyDeviceToHost, s->lanes[0].stream));
+    if (n > t.h_text.size() && !t.h_text.reserve(std::min<uint64_t>(t.text_cap, n + n / 4 + (1u << 20)))) return alloc_failed("kr_batch_collect_text");
+    HIP_TRY(hipMemcpyAsync(t.h_text.get(), t.d_text, n, hipMemcpyDeviceToHost, s->lanes[0].stream));
     HIP_TRY(hipStreamSynchronize(s->lanes[0].stream));
   }
-  *text = t.h_text ? t.h_text : "";
+  *text = t.h_text.get() ? t.h_text.get() : "";
   *len = n;
   return KR_OK;
 }
@@ -968,12 +923,8 @@ static int submit_batch(kr_stream* s, const uint8_t* bases, const uint64_t* offs
   // no --filter (its select kernel writes rec_v, which the list of values aliases), no device text (its kernels read row_d)
   s->rows_indexed = s->rows_mode && (flags & KR_ROWS_INDEXED) && P == 1 && !(!s->dp.no_filter && s->dp.multi) && !s->text.req;
   if (flags & KR_TAP_HITS) {
-    if (!s->h_hits) {
-      HIP_TRY(hipMalloc((void**)&s->out.hits, (uint64_t)s->hit_cap * sizeof(kr_hit)));
-      s->dallocs.push_back(s->out.hits);
-      HIP_TRY(hipHostMalloc((void**)&s->h_hits, (uint64_t)s->hit_cap * sizeof(kr_hit), hipHostMallocDefault));
-      s->hallocs.push_back(s->h_hits);
-    }
+    if (!reserve_all(s->hit_cap, s->d_hits, s->h_hits)) return alloc_failed("kr_batch_submit: hit tap buffers");
+    s->out.hits = s->d_hits.get();
   }
   const uint32_t lane_rec_cap = P == 1 ? s->rec_cap : (s->rec_cap / P) & ~63u;
   const uint32_t lane_item_cap = s->item_cap / P;
@@ -986,13 +937,13 @@ static int submit_batch(kr_stream* s, const uint8_t* bases, const uint64_t* offs
     HIP_TRY(hipEventRecord(L.ev[kEvCopyIn], st));
     if (s->tiles.active) { // the tiled batch: its own bases and offsets, and what the tile kernels need
       kr_stream::Tiles& t = s->tiles;
-      HIP_TRY(hipMemcpyAsync(t.d_bases, t.h_bases, t.h_voff[t.nv], hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(t.d_voff, t.h_voff, ((uint64_t)t.nv + 1) * 8, hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(t.d_vtile, t.h_vtile, t.nv, hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(t.d_rfirst, t.h_rfirst, (uint64_t)nreads * 4, hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(t.d_longs, t.h_longs, (uint64_t)t.nlong * 8, hipMemcpyHostToDevice, st));
-      L.in.bases = t.d_bases;
-      L.in.offsets = t.d_voff;
+      HIP_TRY(hipMemcpyAsync(t.d_bases.get(), t.h_bases.get(), t.h_voff.get()[t.nv], hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(t.d_voff.get(), t.h_voff.get(), ((uint64_t)t.nv + 1) * 8, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(t.d_vtile.get(), t.h_vtile.get(), t.nv, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(t.d_rfirst.get(), t.h_rfirst.get(), (uint64_t)nreads * 4, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(t.d_longs.get(), t.h_longs.get(), (uint64_t)t.nlong * 8, hipMemcpyHostToDevice, st));
+      L.in.bases = t.d_bases.get();
+      L.in.offsets = t.d_voff.get();
       L.nreads = t.nv;
     } else if (flags & KR_BASES_DEVICE) {
       L.in.bases = bases;
@@ -1039,7 +990,7 @@ static int submit_batch(kr_stream* s, const uint8_t* bases, const uint64_t* offs
     o.rep_cap = (uint32_t)std::min<uint64_t>((uint64_t)lane_rec_cap + kRepSlack, 0xFFFFFFFFull);
     o.keep_v = ((flags & KR_ROWS_ONLY) && !(flags & KR_TAP_ACCS)) ? 0u : 1u;
     o.hist_always = (flags & KR_TAP_ACCS) ? 1u : 0u; // else a record's planes exist only where its packed word cannot describe it
-    o.v_tile = s->tiles.active ? s->tiles.d_vtile : nullptr;
+    o.v_tile = s->tiles.active ? s->tiles.d_vtile.get() : nullptr;
     o.rows_mode = s->rows_mode ? 1u : 0u;
     o.rd_rcnt += r0, o.rd_roff += r0, o.row_bsum += r0 / kRowBlock + 2ull * l;
     o.row_key = o.rec_rep, o.row_d = reinterpret_cast<double*>(o.rep_dv); // (the lane's slices: dead once the select kernel has run)
@@ -1099,7 +1050,7 @@ int item_placement_step(kr_stream* s)
     const char* e = getenv("KR_ITEM_PLACEMENT_TRIALS");
     ip.trials_left = (e && *e) ? std::max(0, atoi(e)) : kItemPlacementTrials;
   }
-  if (ip.trials_left == 0 && !ip.aside) return KR_OK;
+  if (ip.trials_left == 0 && !ip.aside.get()) return KR_OK;
   if (s->tiles.active || s->nreads < 1000000u || (s->flags & KR_TAP_HITS)) return KR_OK; // (small batches: the launch is not what their time is)
   float ms = 0;
   for (uint32_t l = 0; l < s->nlanes; ++l) { // (the lanes of a batch work in slices of the one list: their scan times are added)
@@ -1117,29 +1068,22 @@ int item_placement_step(kr_stream* s)
     if (verbose) fprintf(stderr, "[krepp_amd] item list: early launch %.3f ns per read (not measured)\n", ns);
     return KR_OK;
   }
-  auto forget = [&](void* p) {
-    auto it = std::find(s->dallocs.begin(), s->dallocs.end(), p);
-    if (it != s->dallocs.end()) s->dallocs.erase(it);
-    (void)hipFree(p);
-  };
-  if (ip.aside) { // the list in use was a trial
+  if (ip.aside.get()) { // the list in use was a trial
     const bool better = ns < ip.best_ns * 0.985;
     if (verbose) fprintf(stderr, "[krepp_amd] item list trial %u: %.3f ns per read against %.3f: %s\n", ip.tried, ns, ip.best_ns, better ? "kept" : "dropped");
     if (better) {
-      forget(ip.aside);
       ip.best_ns = ns, ++ip.kept_new;
     } else {
-      forget(s->out.items);
-      s->out.items = ip.aside;
+      s->items.swap(ip.aside);
+      s->out.items = s->items.get();
     }
-    ip.aside = nullptr;
+    ip.aside.reset(); // (the loser)
   } else {
     ip.best_ns = ns;
     if (verbose) fprintf(stderr, "[krepp_amd] item list as allocated: %.3f ns per read\n", ns);
   }
   if (ip.trials_left > 0) {
     --ip.trials_left;
-    uint2* fresh = nullptr;
     const uint64_t bytes = (uint64_t)s->item_cap * sizeof(uint2);
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < 2 * bytes) { // never the last of the memory: somebody else may want it
@@ -1147,14 +1091,13 @@ int item_placement_step(kr_stream* s)
       ip.trials_left = 0;
       return KR_OK;
     }
-    if (hipMalloc((void**)&fresh, bytes) != hipSuccess) {
+    if (!ip.aside.renew(s->item_cap)) {
       (void)hipGetLastError();
       ip.trials_left = 0;
       return KR_OK;
     }
-    s->dallocs.push_back(fresh);
-    ip.aside = s->out.items;
-    s->out.items = fresh;
+    s->items.swap(ip.aside); // the fresh list in use, the best so far aside
+    s->out.items = s->items.get();
     ip.settling = 1;
     ++ip.tried;
   }
@@ -1245,11 +1188,11 @@ static void fill_view(kr_stream* s, kr_result_view* v, bool device)
     v->rec_hist_stride = (s->flags & KR_TAP_ACCS) ? s->rec_cap : 0;
   } else {
     v->read_off = s->h_rd_off, v->read_cnt = s->h_rd_cnt, v->read_onmers = s->h_rd_onmers, v->read_na = s->h_rd_na;
-    v->rec_key = s->h_rec_key, v->rec_sel = s->h_rec_sel, v->rec_d = s->h_rec_d;
-    if (s->rows_indexed) v->rec_d = nullptr, v->rec_dix = s->h_rec_dix, v->dist_list = s->h_dist_list, v->ndist = s->ndist;
-    v->rec_v = rows_only ? nullptr : s->h_rec_v;
-    v->rec_chisq = rows_only ? nullptr : s->h_rec_chisq;
-    v->rec_hist = (s->flags & KR_TAP_ACCS) && !rows_only ? s->h_rec_hist : nullptr;
+    v->rec_key = s->h_rec_key.get(), v->rec_sel = s->h_rec_sel.get(), v->rec_d = s->h_rec_d.get();
+    if (s->rows_indexed) v->rec_d = nullptr, v->rec_dix = s->h_rec_dix.get(), v->dist_list = s->h_dist_list.get(), v->ndist = s->ndist;
+    v->rec_v = rows_only ? nullptr : s->h_rec_v.get();
+    v->rec_chisq = rows_only ? nullptr : s->h_rec_chisq.get();
+    v->rec_hist = (s->flags & KR_TAP_ACCS) && !rows_only ? s->h_rec_hist.get() : nullptr;
     v->rec_hist_stride = s->nrecs;
   }
 }
@@ -1276,30 +1219,22 @@ int kr_batch_collect(kr_stream* s, kr_result_view* v)
   // stream, while later lanes still compute.  The host arrays are compact (no unused slots between lanes), so a lane's
   // records land behind those of the lanes before it.
   auto ensure_host = [&](uint64_t need) -> int {
-    if (need <= s->h_rec_cap && (s->h_rec_full || !full) && (s->h_rec_dix || !s->rows_indexed)) return KR_OK;
-    uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(need + need / 4, s->h_rec_cap), 1u << 16);
-    void** olds[] = {(void**)&s->h_rec_key, (void**)&s->h_rec_hist, (void**)&s->h_rec_sel, (void**)&s->h_rec_d, (void**)&s->h_rec_v, (void**)&s->h_rec_chisq};
-    for (void** o : olds)
-      if (*o) {
-        s->hallocs.erase(std::remove(s->hallocs.begin(), s->hallocs.end(), *o), s->hallocs.end());
-        (void)hipHostFree(*o);
-        *o = nullptr;
-      }
-    s->h_rec_cap = 0;
+    const uint64_t have = s->h_rec_key.size();
+    if (need <= have && (s->h_rec_full || !full) && (s->h_rec_dix.get() || !s->rows_indexed)) return KR_OK;
+    const uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(need + need / 4, have), 1u << 16);
+    // all of them anew, every old one freed first (v / chisq / hist stay empty until a batch asks for them, dix until an indexed one
+    // does); a failure leaves none behind, and the next collect starts over
+    auto drop = [&] { s->h_rec_key.reset(), s->h_rec_sel.reset(), s->h_rec_d.reset(), s->h_rec_hist.reset(), s->h_rec_v.reset(), s->h_rec_chisq.reset(); };
+    drop();
     s->h_sel_ones = 0;
-    int rc2 = 0;
-    if ((rc2 = halloc(s, &s->h_rec_key, cap)) || (rc2 = halloc(s, &s->h_rec_sel, cap)) || (rc2 = halloc(s, &s->h_rec_d, cap))) return rc2;
-    if (s->h_rec_dix) {
-      s->hallocs.erase(std::remove(s->hallocs.begin(), s->hallocs.end(), (void*)s->h_rec_dix), s->hallocs.end());
-      (void)hipHostFree(s->h_rec_dix);
-      s->h_rec_dix = nullptr;
-    }
-    if (s->rows_indexed && (rc2 = halloc(s, &s->h_rec_dix, cap))) return rc2;
-    s->h_rec_full = s->h_rec_full || full;
-    if (s->h_rec_full)
-      if ((rc2 = halloc(s, &s->h_rec_hist, cap * s->dp.np)) || (rc2 = halloc(s, &s->h_rec_v, cap)) || (rc2 = halloc(s, &s->h_rec_chisq, cap))) return rc2;
-    s->h_rec_cap = cap;
-    return KR_OK;
+    bool ok = s->h_rec_key.renew(cap) && s->h_rec_sel.renew(cap) && s->h_rec_d.renew(cap);
+    s->h_rec_dix.reset();
+    if (ok && s->rows_indexed) ok = s->h_rec_dix.renew(cap);
+    if (ok) s->h_rec_full = s->h_rec_full || full;
+    if (ok && s->h_rec_full) ok = s->h_rec_hist.renew(cap * s->dp.np) && s->h_rec_v.renew(cap) && s->h_rec_chisq.renew(cap);
+    if (ok) return KR_OK;
+    drop(), s->h_rec_dix.reset();
+    return alloc_failed("kr_batch_collect: page-locked record arrays");
   };
   if (!pipelined || s->nlanes == 1 || (s->flags & KR_TAP_ACCS)) {
     int rc = kr_batch_wait(s); // (the histogram planes are laid out by the total record count: it must be known first)
@@ -1326,7 +1261,7 @@ int kr_batch_collect(kr_stream* s, kr_result_view* v)
       L.nrows = L.h_counters[kCtRows];
       // room for this lane and, by its measure, for the lanes still running; if not, start over once everything is known
       const uint64_t guess = hoff + lane_count(L) * (s->nlanes - l) + lane_count(L) / 8 * (s->nlanes - l - 1);
-      if (guess > s->h_rec_cap || (full && !s->h_rec_full)) {
+      if (guess > s->h_rec_key.size() || (full && !s->h_rec_full)) {
         for (uint32_t j = 0; j < s->nlanes; ++j) HIP_TRY(hipStreamSynchronize(s->lanes[j].stream));
         int rc = kr_batch_wait(s);
         if (rc) return rc;
@@ -1351,59 +1286,49 @@ int kr_batch_collect(kr_stream* s, kr_result_view* v)
       s->d2h_bytes += nr * 9;
       if (nc && s->rows_indexed) { // (one lane, waited for: the counters are known)
         const uint64_t nd = std::min<uint64_t>(L.h_counters[kCtProblems], L.rec_cap);
-        if (nd > s->h_dist_cap) {
-          if (s->h_dist_list) {
-            s->hallocs.erase(std::remove(s->hallocs.begin(), s->hallocs.end(), (void*)s->h_dist_list), s->hallocs.end());
-            (void)hipHostFree(s->h_dist_list);
-            s->h_dist_list = nullptr, s->h_dist_cap = 0;
-          }
-          const uint64_t cap = nd + nd / 4 + 1024;
-          int rc2 = halloc(s, &s->h_dist_list, cap);
-          if (rc2) return rc2;
-          s->h_dist_cap = cap;
-        }
+        if (nd > s->h_dist_list.size() && !s->h_dist_list.reserve(nd + nd / 4 + 1024)) return alloc_failed("kr_batch_collect: list of distinct DIST values");
         s->ndist = nd;
-        HIP_TRY(hipMemcpyAsync(s->h_rec_key + hoff, o.row_key, nc * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(s->h_rec_dix + hoff, o.row_dix, nc * 4, hipMemcpyDeviceToHost, st));
-        if (nd) HIP_TRY(hipMemcpyAsync(s->h_dist_list, o.dist_list, nd * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(s->h_rec_key.get() + hoff, o.row_key, nc * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(s->h_rec_dix.get() + hoff, o.row_dix, nc * 4, hipMemcpyDeviceToHost, st));
+        if (nd) HIP_TRY(hipMemcpyAsync(s->h_dist_list.get(), o.dist_list, nd * 8, hipMemcpyDeviceToHost, st));
         s->d2h_bytes += nc * 8 + nd * 8;
       } else if (nc) {
-        HIP_TRY(hipMemcpyAsync(s->h_rec_key + hoff, o.row_key, nc * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(s->h_rec_d + hoff, o.row_d, nc * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(s->h_rec_key.get() + hoff, o.row_key, nc * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(s->h_rec_d.get() + hoff, o.row_d, nc * 8, hipMemcpyDeviceToHost, st));
         s->d2h_bytes += nc * 12;
       }
       copies_started = true;
       hoff += nc;
       continue;
     }
-    HIP_TRY(hipMemcpyAsync(s->h_rd_off + r0, tl ? t.d_real_off : o.rd_off, nr * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(s->h_rd_cnt + r0, tl ? t.d_real_cnt : o.rd_cnt, nr * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(s->h_rd_na + r0, tl ? t.d_real_na : o.rd_na, nr, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(s->h_rd_off + r0, tl ? t.d_real_off.get() : o.rd_off, nr * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(s->h_rd_cnt + r0, tl ? t.d_real_cnt.get() : o.rd_cnt, nr * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(s->h_rd_na + r0, tl ? t.d_real_na.get() : o.rd_na, nr, hipMemcpyDeviceToHost, st));
     if (full) {
-      HIP_TRY(hipMemcpyAsync(s->h_rd_onmers + r0, tl ? t.d_real_onmers : o.rd_onmers, nr * 4, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(s->h_rd_filt + 2 * r0, tl ? t.d_real_filt : o.rd_filt, nr * 8, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(s->h_rd_onmers + r0, tl ? t.d_real_onmers.get() : o.rd_onmers, nr * 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(s->h_rd_filt + 2 * r0, tl ? t.d_real_filt.get() : o.rd_filt, nr * 8, hipMemcpyDeviceToHost, st));
     }
     if (nc) {
       s->h_sel_ones = 0; // (real flags from here on)
-      HIP_TRY(hipMemcpyAsync(s->h_rec_key + hoff, o.rec_key, nc * 4, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(s->h_rec_sel + hoff, o.rec_sel, nc, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(s->h_rec_d + hoff, o.rec_d, nc * 8, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(s->h_rec_key.get() + hoff, o.rec_key, nc * 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(s->h_rec_sel.get() + hoff, o.rec_sel, nc, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(s->h_rec_d.get() + hoff, o.rec_d, nc * 8, hipMemcpyDeviceToHost, st));
       if (full) {
-        HIP_TRY(hipMemcpyAsync(s->h_rec_v + hoff, o.rec_v, nc * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(s->h_rec_v.get() + hoff, o.rec_v, nc * 8, hipMemcpyDeviceToHost, st));
         if (!s->dp.no_filter && s->dp.multi)
-          HIP_TRY(hipMemcpyAsync(s->h_rec_chisq + hoff, o.rec_chisq, nc * 8, hipMemcpyDeviceToHost, st));
+          HIP_TRY(hipMemcpyAsync(s->h_rec_chisq.get() + hoff, o.rec_chisq, nc * 8, hipMemcpyDeviceToHost, st));
         else
-          std::fill(s->h_rec_chisq + hoff, s->h_rec_chisq + hoff + nc, std::numeric_limits<double>::quiet_NaN());
+          std::fill(s->h_rec_chisq.get() + hoff, s->h_rec_chisq.get() + hoff + nc, std::numeric_limits<double>::quiet_NaN());
         if (s->flags & KR_TAP_ACCS)
           for (uint32_t x = 0; x < s->dp.np; ++x)
-            HIP_TRY(hipMemcpyAsync(s->h_rec_hist + (uint64_t)x * hist_stride_host + hoff, o.rec_hist + (uint64_t)x * s->rec_cap, nc * 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(s->h_rec_hist.get() + (uint64_t)x * hist_stride_host + hoff, o.rec_hist + (uint64_t)x * s->rec_cap, nc * 4, hipMemcpyDeviceToHost, st));
       }
     }
     copies_started = true;
     hoff += nc;
   }
   if ((s->flags & KR_TAP_HITS) && s->waited && s->nhits)
-    HIP_TRY(hipMemcpyAsync(s->h_hits, s->out.hits, s->nhits * sizeof(kr_hit), hipMemcpyDeviceToHost, s->lanes[0].stream));
+    HIP_TRY(hipMemcpyAsync(s->h_hits.get(), s->out.hits, s->nhits * sizeof(kr_hit), hipMemcpyDeviceToHost, s->lanes[0].stream));
   int rc = kr_batch_wait(s); // (a no-op when it already ran; otherwise every lane is idle by now: aggregates the counters)
   for (uint32_t l = 0; l < s->nlanes; ++l) HIP_TRY(hipStreamSynchronize(s->lanes[l].stream));
   if (rc) return rc;
@@ -1427,7 +1352,7 @@ int kr_batch_collect(kr_stream* s, kr_result_view* v)
       const int nt = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)std::min(kr::parallel_width(), 16), len >> 22));
       kr::parallel_for(nt, [&](int t) {
         const uint64_t a = a0 + len * (uint64_t)t / nt, b = a0 + len * (uint64_t)(t + 1) / nt;
-        memset(s->h_rec_sel + a, 1, b - a);
+        memset(s->h_rec_sel.get() + a, 1, b - a);
       });
       s->h_sel_ones = hoff;
     }
@@ -1435,7 +1360,7 @@ int kr_batch_collect(kr_stream* s, kr_result_view* v)
   } else { // number of output rows: tens of millions of flags for a large batch, summed by the host pool
     const int nt = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)std::min(kr::parallel_width(), 16), hoff >> 20));
     std::vector<uint64_t> part((size_t)nt, 0);
-    const uint8_t* sel = s->h_rec_sel;
+    const uint8_t* sel = s->h_rec_sel.get();
     kr::parallel_for(nt, [&](int t) {
       uint64_t a = hoff * (uint64_t)t / nt, b = hoff * (uint64_t)(t + 1) / nt, c = 0;
       for (uint64_t i = a; i < b; ++i) c += sel[i];
@@ -1462,7 +1387,7 @@ int kr_batch_collect_device(kr_stream* s, kr_result_view* v)
 int kr_batch_hits(kr_stream* s, const kr_hit** hits, uint64_t* nhits)
 {
   if (!s || !hits || !nhits || !s->waited) return kr::fail(KR_ERR_STATE, "kr_batch_hits: collect a KR_TAP_HITS batch first");
-  *hits = s->h_hits;
+  *hits = s->h_hits.get();
   *nhits = s->nhits;
   return KR_OK;
 }

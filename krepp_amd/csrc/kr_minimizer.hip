@@ -218,18 +218,22 @@ extern "C" int kr_minimizers_device(int device, const kr_build_params* bp, const
   std::vector<uint64_t> keys;
   double n1 = 0, n2 = 0;
   if (!tiles.empty()) {
-    uint8_t* d_bases = nullptr;
-    uint64_t *d_off = nullptr, *d_keys = nullptr;
-    uint2* d_tiles = nullptr;
-    uint32_t* d_hll = nullptr;
-    unsigned long long* d_n = nullptr;
+    std::vector<uint32_t> regs((size_t)ncontigs * 8192);
+    { // the device's part; its arrays are freed where this block is left, at an error too
+    DevBuf<uint8_t> b_bases;
+    DevBuf<uint64_t> b_off, b_keys;
+    DevBuf<uint2> b_tiles;
+    DevBuf<uint32_t> b_hll;
+    DevBuf<unsigned long long> b_n;
     const unsigned long long cap = total + 64;
-    HIP_TRY(hipMalloc((void**)&d_bases, total + 64));
-    HIP_TRY(hipMalloc((void**)&d_off, ((uint64_t)ncontigs + 1) * 8));
-    HIP_TRY(hipMalloc((void**)&d_tiles, tiles.size() * sizeof(uint2)));
-    HIP_TRY(hipMalloc((void**)&d_hll, (uint64_t)ncontigs * 8192 * 4));
-    HIP_TRY(hipMalloc((void**)&d_keys, cap * 8));
-    HIP_TRY(hipMalloc((void**)&d_n, 8));
+    if (!b_bases.reserve(total + 64) || !b_off.reserve((uint64_t)ncontigs + 1) || !b_tiles.reserve(tiles.size()) || !b_hll.reserve((uint64_t)ncontigs * 8192) ||
+        !b_keys.reserve(cap) || !b_n.reserve(1))
+      return alloc_failed("kr_minimizers_device");
+    uint8_t* d_bases = b_bases.get();
+    uint64_t *d_off = b_off.get(), *d_keys = b_keys.get();
+    uint2* d_tiles = b_tiles.get();
+    uint32_t* d_hll = b_hll.get();
+    unsigned long long* d_n = b_n.get();
     HIP_TRY(hipMemcpy(d_bases, bases, total, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_off, offsets, ((uint64_t)ncontigs + 1) * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_tiles, tiles.data(), tiles.size() * sizeof(uint2), hipMemcpyHostToDevice));
@@ -244,9 +248,8 @@ extern "C" int kr_minimizers_device(int device, const kr_build_params* bp, const
     if (nk > cap) return kr::fail(KR_ERR_CAPACITY, "kr_minimizers_device: key buffer overflow");
     keys.resize(nk);
     if (nk) HIP_TRY(hipMemcpy(keys.data(), d_keys, nk * 8, hipMemcpyDeviceToHost));
-    std::vector<uint32_t> regs((size_t)ncontigs * 8192);
     HIP_TRY(hipMemcpy(regs.data(), d_hll, regs.size() * 4, hipMemcpyDeviceToHost));
-    (void)hipFree(d_bases), (void)hipFree(d_off), (void)hipFree(d_tiles), (void)hipFree(d_hll), (void)hipFree(d_keys), (void)hipFree(d_n);
+    }
     // contig ends + HyperLogLog estimates, contig by contig as the reference adds them
     std::vector<uint8_t> r8(4096);
     for (uint32_t q : kept) {
