@@ -316,6 +316,12 @@ KR_API int kr_debug_colour_classes(const uint32_t* pse_pairs /*[2*nsubsets]*/, u
 KR_API int kr_debug_brent(const kr_index*, uint32_t hdist_th, uint32_t n, const uint32_t* hist /*[n*(th+1)]*/,
                           const uint32_t* onmers, const double* rho, double* d_out, double* v_out);
 
+/* The prefix-sum helpers of the compacting stages (kr_dev_prefix.inc) on plain numbers, run as those stages run them: sums per
+ * block of `block` values (64 or 1024), one workgroup's scan of the block sums, the exclusive scan inside every block; sums of
+ * `width` bytes (4 or 8; with 4 the caller keeps the total below 2^32).  prefix[i] = values[0] + ... + values[i - 1], *total = the
+ * sum of all n.  n = 0: *total = 0 and nothing is launched.  Runs on the calling thread's current device. */
+KR_API int kr_debug_prefix(const uint32_t* values, uint32_t n, uint32_t block, uint32_t width, uint64_t* prefix /*[n]*/, uint64_t* total);
+
 /* Likelihood kernel on arbitrary problems (the per-edge likelihoods of `krepp place`, whose
  * histograms are fractional: Minfo::add, src/query.hpp:139-152).  One problem per element:
  * hist[n*(th+1)] (doubles), uc[n] = mismatch_count, rho[n].  mode 0: Brent minimisation

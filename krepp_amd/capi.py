@@ -98,7 +98,7 @@ EXPORTS = [
     "kr_params_default", "kr_stream_create", "kr_stream_destroy", "kr_batch_submit", "kr_batch_wait",
     "kr_batch_collect", "kr_batch_collect_device", "kr_stream_text_enable", "kr_batch_submit_text", "kr_batch_collect_text",
     "kr_stream_fastq_enable", "kr_batch_submit_fastq", "kr_batch_fastq_names", "kr_debug_fastq_batch", "kr_batch_hits", "kr_batch_readtaps",
-    "kr_debug_front_end", "kr_debug_stream_move", "kr_debug_stream_addrs", "kr_debug_item_placement", "kr_debug_brent", "kr_debug_colour_classes", "kr_llh_batch", "kr_llh_eval_indexed", "kr_batch_timing",
+    "kr_debug_front_end", "kr_debug_stream_move", "kr_debug_stream_addrs", "kr_debug_item_placement", "kr_debug_brent", "kr_debug_prefix", "kr_debug_colour_classes", "kr_llh_batch", "kr_llh_eval_indexed", "kr_batch_timing",
     "kr_place_tree_create", "kr_place_tree_create_lineage", "kr_place_tree_nnodes", "kr_place_summary_add",
     "kr_place_summary_text", "kr_place_tree_free", "kr_place_tree_kinds", "kr_place_batch", "kr_place_stream", "kr_place_frame", "kr_place_counters",
     "kr_debug_last_d2h_bytes", "kr_debug_place_fixed5", "kr_place_text_counters", "kr_place_path_counters", "kr_fastx_open", "kr_fastx_open_at", "kr_fastx_next", "kr_fastx_detach", "kr_fastx_release", "kr_fastx_close", "kr_fastx_parallel_chunks", "kr_fastx_pgz_stats", "kr_format_dist", "kr_debug_fixed5", "kr_free", "kr_host_alloc", "kr_host_free",
@@ -171,6 +171,7 @@ def load():
     lib.kr_batch_readtaps.argtypes = [vp, C.POINTER(u32p)]
     lib.kr_debug_front_end.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
     lib.kr_debug_brent.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]
+    lib.kr_debug_prefix.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, u64p]
     lib.kr_debug_colour_classes.argtypes = [vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.POINTER(C.c_uint64)]
     lib.kr_batch_timing.argtypes = [vp, C.POINTER(KrTiming)]
     lib.kr_llh_batch.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint64, vp, vp, vp, vp, vp, vp]
@@ -620,6 +621,16 @@ class Stream:
             self.close()
         except Exception:
             pass
+
+
+def debug_prefix(values, block, width):
+    """(tests) the device's prefix-sum helpers on plain numbers (kr_debug_prefix): (exclusive prefix of every value, total), with
+    blocks of `block` values and sums of `width` bytes."""
+    values = np.ascontiguousarray(values, dtype=np.uint32)
+    prefix = np.zeros(len(values), np.uint64)
+    total = C.c_uint64(0)
+    check(load().kr_debug_prefix(values.ctypes.data, len(values), block, width, prefix.ctypes.data, C.byref(total)))
+    return prefix, total.value
 
 
 def colour_classes(pse, node_kind):

@@ -83,6 +83,45 @@ __global__ __launch_bounds__(256) void kr_llh_batch_kernel(LlhConst C, uint32_t 
   }
 }
 
+// kr_debug_prefix: the three steps of kr_dev_prefix.inc as the rows, text and FASTQ kernels run them, on plain numbers.  A block is
+// BLOCK values, thread t owns the values 4t .. 4t+3 of its block (BLOCK = 64: the first 16 threads, as in kr_place_text_write_kernel)
+template <typename T, uint32_t BLOCK>
+__global__ __launch_bounds__(256) void kr_prefix_bsum_kernel(const uint32_t* v, uint32_t n, T* bsum)
+{
+  for (uint32_t b = blockIdx.x; b * BLOCK < n; b += gridDim.x) {
+    T c = 0;
+    for (uint32_t q = 4u * threadIdx.x; q < min(4u * threadIdx.x + 4u, BLOCK); ++q)
+      if (b * BLOCK + q < n) c += v[b * BLOCK + q];
+    const T tot = block_sum(c);
+    if (threadIdx.x == 0) bsum[b] = tot;
+  }
+}
+template <typename T>
+__global__ __launch_bounds__(1024) void kr_prefix_bscan_kernel(T* bsum, uint32_t nblk, uint64_t* total)
+{
+  const T tot = scan_block_sums(bsum, nblk);
+  if (threadIdx.x == 0) *total = tot;
+}
+template <typename T, uint32_t BLOCK>
+__global__ __launch_bounds__(256) void kr_prefix_write_kernel(const uint32_t* v, uint32_t n, const T* bsum, uint64_t* prefix)
+{
+  for (uint32_t b = blockIdx.x; b * BLOCK < n; b += gridDim.x) {
+    const uint32_t i0 = b * BLOCK, q0 = 4u * threadIdx.x;
+    T c[4], tot = 0;
+#pragma unroll
+    for (uint32_t q = 0; q < 4; ++q) {
+      c[q] = (q0 + q < BLOCK && i0 + q0 + q < n) ? v[i0 + q0 + q] : 0u;
+      tot += c[q];
+    }
+    T run = bsum[b] + block_scan_excl(tot);
+#pragma unroll
+    for (uint32_t q = 0; q < 4; ++q) {
+      if (q0 + q < BLOCK && i0 + q0 + q < n) prefix[i0 + q0 + q] = run;
+      run += c[q];
+    }
+  }
+}
+
 // Re-layout kernels used by kr_index_upload.  cls[se] = the tagged form of colour id se (class in the top two bits, see
 // kr_dev_common.inc and colour_classes in kr_host_index.inc); ids the crecord does not define are dropped.
 __global__ void kr_relayout_cmer(const uint32_t* cmer, uint64_t n, uint32_t* enc, uint32_t* se, const uint32_t* cls, uint32_t nsubsets)

@@ -55,65 +55,30 @@ __device__ __forceinline__ uint32_t fq_nl_mask(const uint8_t* raw, uint64_t base
   return m;
 }
 
-__device__ __forceinline__ uint32_t fq_block_sum(uint32_t v, uint32_t* s_w)
-{ // 256 lanes; every lane gets the sum
-  for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
-  __syncthreads();
-  if (lane_id() == 0) s_w[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return s_w[0] + s_w[1] + s_w[2] + s_w[3];
-}
-
 __global__ __launch_bounds__(256) void kr_fq_nl_count_kernel(FqIO f)
 {
-  __shared__ uint32_t s_w[4];
   const uint64_t ntiles = (f.nbytes + kFqTile - 1) / kFqTile;
   for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
     const uint64_t base = t * kFqTile + 16u * threadIdx.x;
     const uint32_t c = base < f.nbytes ? (uint32_t)__popc(fq_nl_mask(f.raw, base, f.nbytes)) : 0u;
-    const uint32_t tot = fq_block_sum(c, s_w);
+    const uint32_t tot = block_sum(c);
     if (threadIdx.x == 0) f.tile_nl[t] = tot;
   }
 }
 
 __global__ __launch_bounds__(1024) void kr_fq_nl_scan_kernel(FqIO f)
 { // one workgroup: exclusive prefix of tile_nl in place (a chunk below 4 GB has fewer than 2^32 newlines)
-  __shared__ uint32_t s_w[16];
-  __shared__ uint32_t s_run;
-  const uint32_t nt = (uint32_t)((f.nbytes + kFqTile - 1) / kFqTile), w = threadIdx.x >> 6;
-  if (threadIdx.x == 0) s_run = 0;
-  __syncthreads();
-  for (uint32_t b0 = 0; b0 < nt; b0 += 1024u) {
-    const uint32_t b = b0 + threadIdx.x;
-    const uint32_t c = b < nt ? f.tile_nl[b] : 0u;
-    const uint32_t inc = wave_scan_incl(c);
-    if (lane_id() == 63u) s_w[w] = inc;
-    __syncthreads();
-    uint32_t base = s_run;
-    for (uint32_t q = 0; q < w; ++q) base += s_w[q];
-    if (b < nt) f.tile_nl[b] = base + inc - c;
-    __syncthreads();
-    if (threadIdx.x == 1023u) s_run = base + inc;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) f.ctl[0] = s_run;
+  const uint32_t newlines = scan_block_sums(f.tile_nl, (uint32_t)((f.nbytes + kFqTile - 1) / kFqTile));
+  if (threadIdx.x == 0) f.ctl[0] = newlines;
 }
 
 __global__ __launch_bounds__(256) void kr_fq_nl_write_kernel(FqIO f)
 {
-  __shared__ uint32_t s_w[4];
   const uint64_t ntiles = (f.nbytes + kFqTile - 1) / kFqTile;
-  const uint32_t w = threadIdx.x >> 6;
   for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
     const uint64_t base = t * kFqTile + 16u * threadIdx.x;
     uint32_t m = base < f.nbytes ? fq_nl_mask(f.raw, base, f.nbytes) : 0u;
-    const uint32_t c = (uint32_t)__popc(m);
-    const uint32_t inc = wave_scan_incl(c);
-    __syncthreads();
-    if (lane_id() == 63u) s_w[w] = inc;
-    __syncthreads();
-    uint32_t idx = f.tile_nl[t] + inc - c;
-    for (uint32_t q = 0; q < w; ++q) idx += s_w[q];
+    uint32_t idx = f.tile_nl[t] + block_scan_excl((uint32_t)__popc(m));
     for (; m; m &= m - 1u, ++idx)
       if (idx < f.nl_cap) f.nl[idx] = (uint32_t)base + (uint32_t)__ffs(m) - 1u;
   }
@@ -167,8 +132,6 @@ __device__ __forceinline__ uint32_t fq_nscan(const FqIO& f) { return (uint32_t)m
 
 __global__ __launch_bounds__(256) void kr_fq_bsum_kernel(FqIO f)
 {
-  __shared__ uint32_t s_w[4];
-  __shared__ uint64_t s_b[4];
   const uint32_t n = fq_nscan(f), nb = n / kFqRecBlock + 1u;
   for (uint32_t b = blockIdx.x; b < nb; b += gridDim.x) {
     uint64_t sb = 0;
@@ -178,48 +141,23 @@ __global__ __launch_bounds__(256) void kr_fq_bsum_kernel(FqIO f)
       const uint32_t r = b * kFqRecBlock + 4u * threadIdx.x + q;
       if (r < n) sb += f.rec_slen[r], sn += f.rec_nlen[r];
     }
-    for (int d = 32; d >= 1; d >>= 1) sb += __shfl_xor(sb, d);
-    __syncthreads();
-    if (lane_id() == 0) s_b[threadIdx.x >> 6] = sb;
-    const uint32_t tn = fq_block_sum(sn, s_w); // (its barriers order s_b too)
-    if (threadIdx.x == 0) f.bsum_b[b] = s_b[0] + s_b[1] + s_b[2] + s_b[3], f.bsum_n[b] = tn;
+    const uint64_t tb = block_sum(sb);
+    const uint32_t tn = block_sum(sn);
+    if (threadIdx.x == 0) f.bsum_b[b] = tb, f.bsum_n[b] = tn;
   }
 }
 
 __global__ __launch_bounds__(1024) void kr_fq_bscan_kernel(FqIO f)
-{ // one workgroup: exclusive prefixes of bsum_b and bsum_n in place; ctl[2] = the records they cover
-  __shared__ uint64_t s_w[2][16];
-  __shared__ uint64_t s_run[2];
-  const uint32_t n = fq_nscan(f), nb = n / kFqRecBlock + 1u, lane = lane_id(), w = threadIdx.x >> 6;
-  if (threadIdx.x < 2) s_run[threadIdx.x] = 0;
-  __syncthreads();
-  for (uint32_t b0 = 0; b0 < nb; b0 += 1024u) {
-    const uint32_t b = b0 + threadIdx.x;
-    uint64_t c[2] = {b < nb ? f.bsum_b[b] : 0ull, b < nb ? f.bsum_n[b] : 0ull}, inc[2] = {c[0], c[1]};
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t up = __shfl_up(inc[a], d);
-        if (lane >= (uint32_t)d) inc[a] += up;
-      }
-    if (lane == 63u) s_w[0][w] = inc[0], s_w[1][w] = inc[1];
-    __syncthreads();
-    uint64_t base[2] = {s_run[0], s_run[1]};
-    for (uint32_t q = 0; q < w; ++q) base[0] += s_w[0][q], base[1] += s_w[1][q];
-    if (b < nb) f.bsum_b[b] = base[0] + inc[0] - c[0], f.bsum_n[b] = base[1] + inc[1] - c[1];
-    __syncthreads();
-    if (threadIdx.x == 1023u) s_run[0] = base[0] + inc[0], s_run[1] = base[1] + inc[1];
-    __syncthreads();
-  }
+{ // one workgroup: exclusive prefixes of bsum_b and bsum_n in place, one after the other; ctl[2] = the records they cover
+  const uint32_t n = fq_nscan(f), nb = n / kFqRecBlock + 1u;
+  scan_block_sums(f.bsum_b, nb);
+  scan_block_sums(f.bsum_n, nb);
   if (threadIdx.x == 0) f.ctl[2] = n;
 }
 
 __global__ __launch_bounds__(256) void kr_fq_off_kernel(FqIO f)
 {
-  __shared__ uint64_t s_b[4];
-  __shared__ uint32_t s_n[4];
-  const uint32_t n = (uint32_t)f.ctl[2], nb = n / kFqRecBlock + 1u, lane = lane_id(), w = threadIdx.x >> 6;
+  const uint32_t n = (uint32_t)f.ctl[2], nb = n / kFqRecBlock + 1u;
   for (uint32_t b = blockIdx.x; b < nb; b += gridDim.x) {
     const uint32_t r0 = b * kFqRecBlock + 4u * threadIdx.x;
     uint64_t cb[4], tb = 0;
@@ -230,17 +168,7 @@ __global__ __launch_bounds__(256) void kr_fq_off_kernel(FqIO f)
       cn[q] = r0 + q < n ? f.rec_nlen[r0 + q] : 0u;
       tb += cb[q], tn += cn[q];
     }
-    uint64_t ib = tb;
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint64_t up = __shfl_up(ib, d);
-      if (lane >= (uint32_t)d) ib += up;
-    }
-    const uint32_t in_ = wave_scan_incl(tn);
-    __syncthreads();
-    if (lane == 63u) s_b[w] = ib, s_n[w] = in_;
-    __syncthreads();
-    uint64_t ob = f.bsum_b[b] + ib - tb, on = f.bsum_n[b] + in_ - tn;
-    for (uint32_t q = 0; q < w; ++q) ob += s_b[q], on += s_n[q];
+    uint64_t ob = f.bsum_b[b] + block_scan_excl(tb), on = f.bsum_n[b] + block_scan_excl(tn);
 #pragma unroll
     for (uint32_t q = 0; q < 4; ++q) {
       const uint32_t r = r0 + q;

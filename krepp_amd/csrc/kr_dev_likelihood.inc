@@ -1267,42 +1267,20 @@ __global__ __launch_bounds__(256, KR_SELECT_WPE) void kr_select_lane_kernel(LlhC
 constexpr uint32_t kRowBlock = 1024;
 __global__ __launch_bounds__(256) void kr_rows_bsum_kernel(BatchOut out, uint32_t nreads)
 {
-  __shared__ uint32_t s_w[4];
   for (uint32_t b = blockIdx.x; b * kRowBlock < nreads; b += gridDim.x) {
     uint32_t c = 0;
     for (uint32_t q = threadIdx.x; q < kRowBlock; q += 256u) {
       const uint32_t r = b * kRowBlock + q;
       if (r < nreads) c += out.rd_rcnt[r];
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) c += (uint32_t)__shfl_xor((int)c, d);
-    if ((threadIdx.x & 63u) == 0) s_w[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) out.row_bsum[b] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-    __syncthreads();
+    const uint32_t tot = block_sum(c);
+    if (threadIdx.x == 0) out.row_bsum[b] = tot;
   }
 }
 __global__ __launch_bounds__(1024) void kr_rows_bscan_kernel(BatchOut out, uint32_t nreads)
 { // one workgroup: exclusive prefix of row_bsum in place, the total into counters[kCtRows]
-  __shared__ uint32_t s_w[16];
-  __shared__ uint32_t s_run;
-  const uint32_t nb = (nreads + kRowBlock - 1u) / kRowBlock, lane = lane_id(), w = threadIdx.x >> 6;
-  if (threadIdx.x == 0) s_run = 0;
-  __syncthreads();
-  for (uint32_t b0 = 0; b0 < nb; b0 += 1024u) {
-    const uint32_t b = b0 + threadIdx.x;
-    const uint32_t c = b < nb ? out.row_bsum[b] : 0u;
-    const uint32_t inc = wave_scan_incl(c);
-    if (lane == 63u) s_w[w] = inc;
-    __syncthreads();
-    uint32_t base = s_run;
-    for (uint32_t q = 0; q < w; ++q) base += s_w[q];
-    if (b < nb) out.row_bsum[b] = base + inc - c;
-    __syncthreads();
-    if (threadIdx.x == 1023u) s_run = base + inc;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out.counters[kCtRows] = s_run;
+  const uint32_t rows = scan_block_sums(out.row_bsum, (nreads + kRowBlock - 1u) / kRowBlock);
+  if (threadIdx.x == 0) out.counters[kCtRows] = rows;
 }
 // INDEXED (KR_ROWS_INDEXED): the row's DIST as the position of its problem in the batch's list of distinct problems
 // (kr_rows_dlist_kernel makes that list dense: dist_list[pos] = rep_dv[pos].x)
@@ -1315,7 +1293,6 @@ template <bool INDEXED>
 __global__ __launch_bounds__(256) void kr_rows_write_kernel(BatchOut out, uint32_t nreads)
 {
   __shared__ uint32_t s_off[kRowBlock];
-  __shared__ uint32_t s_w[4];
   const uint32_t lane = lane_id(), w = threadIdx.x >> 6;
   const uint64_t lt = (1ull << lane) - 1ull;
   for (uint32_t b = blockIdx.x; b * kRowBlock < nreads; b += gridDim.x) {
@@ -1327,11 +1304,7 @@ __global__ __launch_bounds__(256) void kr_rows_write_kernel(BatchOut out, uint32
       c[q] = rb + q0 + q < nreads ? out.rd_rcnt[rb + q0 + q] : 0u;
       tot += c[q];
     }
-    const uint32_t inc = wave_scan_incl(tot);
-    if (lane == 63u) s_w[w] = inc;
-    __syncthreads();
-    uint32_t run = out.row_bsum[b] + inc - tot;
-    for (uint32_t q = 0; q < w; ++q) run += s_w[q];
+    uint32_t run = out.row_bsum[b] + block_scan_excl(tot);
 #pragma unroll
     for (uint32_t q = 0; q < 4; ++q) {
       s_off[q0 + q] = run;

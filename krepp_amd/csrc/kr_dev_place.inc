@@ -773,7 +773,7 @@ struct PlaceText {
   const char* labels;        // node labels back to back
   const uint32_t* label_off; // [pn + 2]
   uint32_t* rd_tlen;         // [nreads] bytes of the read's text
-  uint64_t* t_bsum;          // [ceil(nreads / kRowBlock) + 1]
+  uint64_t* t_bsum;          // [ceil(nreads / kPlTextBlock) + 1] bytes per block, then (in place) the blocks' first bytes
   char* text;
   uint64_t text_cap;
   uint64_t* total;           // [0] bytes  [1] TextFlag bits (kr_dev_text.inc); kTextNoRange: see kr_place_text_len_kernel
@@ -1010,7 +1010,6 @@ __device__ __forceinline__ uint32_t place_read_len(const PlaceText& tx, bool sin
 
 __global__ __launch_bounds__(256) void kr_place_text_len_kernel(PlaceOut po, PlaceTree T, PlaceText tx, uint32_t nreads)
 {
-  __shared__ uint32_t s_sum[4];
   const uint32_t lane = lane_id(), w = threadIdx.x >> 6;
   // A range that ran out of candidate slots (kPlFlagCandCap) or of slots for the kept ones (kPlFlagKeepCap) is about to be run again
   // (place_device_finish), and its per-read words are not the compaction's: a read the compaction skipped for want of slots still
@@ -1042,8 +1041,7 @@ __global__ __launch_bounds__(256) void kr_place_text_len_kernel(PlaceOut po, Pla
           PlaceNum pn[5];
           rl += has ? place_row_len(tx, row, idl, pn, flags) : 0u;
         }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) rl += (uint32_t)__shfl_xor((int)rl, d);
+        rl = wave_sum(rl);
         len = place_read_len(tx, ((po.rd_info[r] >> 30) & 1u) != 0, nrows, rl, idl);
       }
       if (lane == 0) tx.rd_tlen[r] = len;
@@ -1051,17 +1049,14 @@ __global__ __launch_bounds__(256) void kr_place_text_len_kernel(PlaceOut po, Pla
     }
     flags = wave_or(flags);
     if (flags && lane == 0) atomicOr((unsigned long long*)&tx.total[1], (unsigned long long)flags);
-    if (lane == 0) s_sum[w] = wsum;
-    __syncthreads();
-    if (threadIdx.x == 0) tx.t_bsum[b] = (uint64_t)s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
-    __syncthreads();
+    const uint64_t tot = block_sum_waves<uint64_t>(wsum);
+    if (threadIdx.x == 0) tx.t_bsum[b] = tot;
   }
 }
 
 __global__ __launch_bounds__(256) void kr_place_text_write_kernel(PlaceOut po, PlaceTree T, PlaceText tx, uint32_t nreads)
 {
   __shared__ uint32_t s_off[kPlTextBlock];
-  __shared__ uint32_t s_w[4];
   if (tx.total[0] > tx.text_cap || (tx.total[1] & ~(unsigned long long)kTextOverCap) != 0) return; // (the host formats this range, or -- kTextNoRange -- it is run again)
   const uint32_t lane = lane_id(), w = threadIdx.x >> 6;
   for (uint32_t b = blockIdx.x; b * kPlTextBlock < nreads; b += gridDim.x) {
@@ -1072,11 +1067,7 @@ __global__ __launch_bounds__(256) void kr_place_text_write_kernel(PlaceOut po, P
       c[q] = (q0 + q < kPlTextBlock && rb + q0 + q < nreads) ? tx.rd_tlen[rb + q0 + q] : 0u;
       tot += c[q];
     }
-    const uint32_t inc = wave_scan_incl(tot);
-    if (lane == 63u) s_w[w] = inc;
-    __syncthreads();
-    uint32_t run = inc - tot;
-    for (uint32_t q = 0; q < w; ++q) run += s_w[q];
+    uint32_t run = block_scan_excl(tot); // (64 reads: the first 16 threads own them, the totals of the others are 0)
 #pragma unroll
     for (uint32_t q = 0; q < 4; ++q) {
       if (q0 + q < kPlTextBlock) s_off[q0 + q] = run;

@@ -45,7 +45,6 @@ __device__ __forceinline__ uint32_t text_num(double d, uint32_t& n, bool& ok)
 
 __global__ __launch_bounds__(256) void kr_text_len_kernel(BatchOut out, TextIO t, uint32_t nreads)
 {
-  __shared__ uint32_t s_sum[4];
   const uint32_t lane = lane_id(), w = threadIdx.x >> 6;
   for (uint32_t b = blockIdx.x; b * kRowBlock < nreads; b += gridDim.x) {
     const uint32_t rb = b * kRowBlock;
@@ -65,55 +64,30 @@ __global__ __launch_bounds__(256) void kr_text_len_kernel(BatchOut out, TextIO t
           bad = bad || !ok;
         }
       }
-#pragma unroll
-      for (int d = 32; d >= 1; d >>= 1) len += (uint32_t)__shfl_xor((int)len, d);
+      len = wave_sum(len);
       if (out.rd_na[r]) len += idl + 8u; // "\tNA\tNaN\n"
       if (lane == 0) t.rd_tlen[r] = len;
       wsum += len;
     }
     if (__ballot(bad) != 0 && lane == 0) atomicOr((unsigned long long*)&t.total[1], (unsigned long long)kTextBadNum);
-    if (lane == 0) s_sum[w] = wsum;
-    __syncthreads();
-    if (threadIdx.x == 0) t.t_bsum[b] = (uint64_t)s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
-    __syncthreads();
+    const uint64_t tot = block_sum_waves<uint64_t>(wsum);
+    if (threadIdx.x == 0) t.t_bsum[b] = tot;
   }
 }
 
-__global__ __launch_bounds__(1024) void kr_text_bscan_kernel(TextIO t, uint32_t nreads)
+// (the text of `dist` and of `place`, kr_dev_place.inc: nblk is the caller's number of blocks, whatever reads a block holds)
+__global__ __launch_bounds__(1024) void kr_text_bscan_kernel(uint64_t* t_bsum, uint32_t nblk, uint64_t text_cap, uint64_t* total)
 { // one workgroup: exclusive prefix of t_bsum in place (64-bit: an 8 M-read batch on the benchmark index is 7 GB of text)
-  __shared__ uint64_t s_w[16];
-  __shared__ uint64_t s_run;
-  const uint32_t nb = (nreads + kRowBlock - 1u) / kRowBlock, lane = lane_id(), w = threadIdx.x >> 6;
-  if (threadIdx.x == 0) s_run = 0;
-  __syncthreads();
-  for (uint32_t b0 = 0; b0 < nb; b0 += 1024u) {
-    const uint32_t b = b0 + threadIdx.x;
-    const uint64_t c = b < nb ? t.t_bsum[b] : 0ull;
-    uint64_t inc = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint64_t up = __shfl_up(inc, d);
-      if (lane >= (uint32_t)d) inc += up;
-    }
-    if (lane == 63u) s_w[w] = inc;
-    __syncthreads();
-    uint64_t base = s_run;
-    for (uint32_t q = 0; q < w; ++q) base += s_w[q];
-    if (b < nb) t.t_bsum[b] = base + inc - c;
-    __syncthreads();
-    if (threadIdx.x == 1023u) s_run = base + inc;
-    __syncthreads();
-  }
+  const uint64_t bytes = scan_block_sums(t_bsum, nblk);
   if (threadIdx.x == 0) {
-    t.total[0] = s_run;
-    if (s_run > t.text_cap) atomicOr((unsigned long long*)&t.total[1], (unsigned long long)kTextOverCap);
+    total[0] = bytes;
+    if (bytes > text_cap) atomicOr((unsigned long long*)&total[1], (unsigned long long)kTextOverCap);
   }
 }
 
 __global__ __launch_bounds__(256) void kr_text_write_kernel(BatchOut out, TextIO t, uint32_t nreads)
 {
   __shared__ uint32_t s_off[kRowBlock];
-  __shared__ uint32_t s_w[4];
   if (t.total[0] > t.text_cap) return; // (the flag is up: the caller splits the batch)
   const uint32_t lane = lane_id(), w = threadIdx.x >> 6;
   for (uint32_t b = blockIdx.x; b * kRowBlock < nreads; b += gridDim.x) {
@@ -125,11 +99,7 @@ __global__ __launch_bounds__(256) void kr_text_write_kernel(BatchOut out, TextIO
       c[q] = rb + q0 + q < nreads ? t.rd_tlen[rb + q0 + q] : 0u;
       tot += c[q];
     }
-    const uint32_t inc = wave_scan_incl(tot);
-    if (lane == 63u) s_w[w] = inc;
-    __syncthreads();
-    uint32_t run = inc - tot;
-    for (uint32_t q = 0; q < w; ++q) run += s_w[q];
+    uint32_t run = block_scan_excl(tot);
 #pragma unroll
     for (uint32_t q = 0; q < 4; ++q) {
       s_off[q0 + q] = run;

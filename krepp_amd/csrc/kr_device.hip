@@ -36,6 +36,7 @@
 //
 // One translation unit in several files, included below in this order (device code first):
 //   kr_dev_common.inc      constants, device structs and helpers shared by the kernels
+//   kr_dev_prefix.inc      the prefix sums of the stages that compact variable-length output: workgroup sum, workgroup scan, scan of the block sums
 //   kr_dev_scan.inc        kernel 1: probe list, bucket scan, hit items
 //   kr_dev_scan_pipe.inc   kernel 1 for slotted tables as a software pipeline across probe groups
 //   kr_dev_scan_filt.inc   kernel 1 for FILTER slots (format 9): one 128-byte line of 24-bit codes per probe, candidates verified in kernel 2
@@ -78,6 +79,7 @@
 namespace {
 
 #include "kr_dev_common.inc"
+#include "kr_dev_prefix.inc"
 #include "kr_dev_scan.inc"
 #include "kr_dev_scan_pipe.inc"
 #include "kr_dev_scan_filt.inc"
@@ -159,6 +161,26 @@ static int llh_workspace(const kr_index* ix, uint64_t need)
   return reserve_all(need + need / 4, ix->llh_dev, ix->llh_pin) ? KR_OK : alloc_failed("likelihood workspace");
 }
 
+// kr_debug_prefix for sums of type T over blocks of BLOCK values
+template <typename T, uint32_t BLOCK>
+static int debug_prefix(const uint32_t* values, uint32_t n, uint64_t* prefix, uint64_t* total)
+{
+  const uint32_t nblk = (n + BLOCK - 1) / BLOCK, grid = std::min<uint32_t>(nblk, 256u); // (a grid the blocks outnumber: the kernels' loops run)
+  DevBuf<uint32_t> b_v; // (freed at every return)
+  DevBuf<T> b_sum;
+  DevBuf<uint64_t> b_pre;
+  if (!b_v.reserve(n) || !b_sum.reserve(nblk) || !b_pre.reserve((uint64_t)n + 1)) return alloc_failed("kr_debug_prefix");
+  uint64_t* d_total = b_pre.get() + n;
+  HIP_TRY(hipMemcpy(b_v.get(), values, (uint64_t)n * 4, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL((kr_prefix_bsum_kernel<T, BLOCK>), dim3(grid), dim3(256), 0, 0, b_v.get(), n, b_sum.get());
+  hipLaunchKernelGGL((kr_prefix_bscan_kernel<T>), dim3(1), dim3(1024), 0, 0, b_sum.get(), nblk, d_total);
+  hipLaunchKernelGGL((kr_prefix_write_kernel<T, BLOCK>), dim3(grid), dim3(256), 0, 0, b_v.get(), n, b_sum.get(), b_pre.get());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(prefix, b_pre.get(), (uint64_t)n * 8, hipMemcpyDeviceToHost)); // synchronises with the kernels (null stream)
+  HIP_TRY(hipMemcpy(total, d_total, 8, hipMemcpyDeviceToHost));
+  return KR_OK;
+}
+
 extern "C" {
 
 void* kr_host_alloc(uint64_t bytes)
@@ -206,6 +228,17 @@ int kr_debug_front_end(const kr_index* ix, const uint8_t* bases, const uint64_t*
   HIP_TRY(hipMemcpy(valid, d_valid, n, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(pass, d_pass, n, hipMemcpyDeviceToHost));
   return KR_OK;
+}
+
+int kr_debug_prefix(const uint32_t* values, uint32_t n, uint32_t block, uint32_t width, uint64_t* prefix, uint64_t* total)
+{
+  kr::clear_error();
+  if (!total || (n && (!values || !prefix)) || (block != 64u && block != 1024u) || (width != 4u && width != 8u) || n > (1u << 31) /* (the kernels count b * block in 32 bits) */)
+    return kr::fail(KR_ERR_ARG, "kr_debug_prefix: bad argument");
+  *total = 0;
+  if (n == 0) return KR_OK;
+  if (width == 4u) return block == 64u ? debug_prefix<uint32_t, 64u>(values, n, prefix, total) : debug_prefix<uint32_t, 1024u>(values, n, prefix, total);
+  return block == 64u ? debug_prefix<uint64_t, 64u>(values, n, prefix, total) : debug_prefix<uint64_t, 1024u>(values, n, prefix, total);
 }
 
 int kr_llh_batch(const kr_index* ix, uint32_t th, uint32_t mode, uint64_t n, const double* hist, const double* uc, const double* rho,

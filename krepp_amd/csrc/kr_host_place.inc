@@ -219,9 +219,7 @@ int kr::place_device_launch(kr_stream* s, const kr::PlaceTreeArrays& T, uint32_t
     const uint32_t nblk = (n + kPlTextBlock - 1) / kPlTextBlock;
     HIP_TRY(hipMemsetAsync(w.d_ttotal.get(), 0, 16, st));
     hipLaunchKernelGGL(kr_place_text_len_kernel, dim3(std::min<uint32_t>(nblk, 16384u)), dim3(256), 0, st, PO, PT, TX, n);
-    TextIO tio{nullptr, nullptr, 0u, nullptr, nullptr, nullptr, w.d_tbsum.get(), nullptr, place_text_bytes(w), w.d_ttotal.get()};
-    // (the `dist` text's block scan counts its blocks as ceil(reads / kRowBlock): told of nblk x kRowBlock reads it scans these nblk sums)
-    hipLaunchKernelGGL(kr_text_bscan_kernel, dim3(1), dim3(1024), 0, st, tio, nblk * kRowBlock);
+    hipLaunchKernelGGL(kr_text_bscan_kernel, dim3(1), dim3(1024), 0, st, TX.t_bsum, nblk, TX.text_cap, TX.total);
     hipLaunchKernelGGL(kr_place_text_write_kernel, dim3(std::min<uint32_t>(nblk, 16384u)), dim3(256), 0, st, PO, PT, TX, n);
     HIP_TRY(hipMemcpyAsync(w.h_ttotal.get(), w.d_ttotal.get(), 16, hipMemcpyDeviceToHost, st));
   }

@@ -485,7 +485,7 @@ int launch_rows_text(kr_stream* s, Lane& L)
     TextIO t{tx.d_ids, tx.d_id_off, tx.id_sep, s->ix->d_names.get(), s->ix->d_name_off.get(), tx.d_tlen, tx.d_bsum, tx.d_text, tx.text_cap, tx.d_total};
     HIP_TRY(hipMemsetAsync(tx.d_total, 0, 16, st));
     hipLaunchKernelGGL(kr_text_len_kernel, dim3(std::min<uint32_t>(nblk, 8192u)), dim3(256), 0, st, o, t, nreads);
-    hipLaunchKernelGGL(kr_text_bscan_kernel, dim3(1), dim3(1024), 0, st, t, nreads);
+    hipLaunchKernelGGL(kr_text_bscan_kernel, dim3(1), dim3(1024), 0, st, t.t_bsum, nblk, t.text_cap, t.total);
     hipLaunchKernelGGL(kr_text_write_kernel, dim3(std::min<uint32_t>(nblk, 8192u)), dim3(256), 0, st, o, t, nreads);
     HIP_TRY(hipMemcpyAsync(tx.h_total, tx.d_total, 16, hipMemcpyDeviceToHost, st));
     tx.made = true;
