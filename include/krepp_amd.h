@@ -206,6 +206,11 @@ KR_API void kr_stream_destroy(kr_stream*);
                            /* host view is NULL then (a formatter may format each distinct value once). */
                            /* A hint: honoured for batches that run as one lane and are not tiled --     */
                            /* otherwise the view holds rec_d as without it (rec_dix == NULL says which). */
+#define KR_TILE_DEVICE 64u /* with KR_BASES_DEVICE (and for kr_batch_submit_fastq): long sequences of a batch that   */
+                           /* is already in HBM are tiled too -- the tiled batch is laid out by kernels from the       */
+                           /* caller's device bases / offsets (see "Long sequences" below).  The submit then WAITS    */
+                           /* for a 24-byte summary of the layout before it returns.  Ignored for host input (which   */
+                           /* is tiled anyway), with KR_TAP_HITS and while KR_NO_TILES is set                          */
 
 /* Queue one batch: `bases` = concatenated ASCII sequences exactly as the FASTX
  * reader delivers them (QSeq::read_next_batch, src/rqseq.cpp:180-197),
@@ -225,7 +230,18 @@ KR_API void kr_stream_destroy(kr_stream*);
  * the same order).  A tile counts as a read against max_reads: the sequences whose tiles fit the stream are tiled, in order
  * (the others, and every sequence of a batch already in HBM or submitted with KR_TAP_HITS, are one wave's work as before); a
  * tiled batch whose tiles' records overflow the device buffers is run again untiled by kr_batch_wait / kr_batch_collect.  The
- * views always describe the caller's reads. */
+ * views always describe the caller's reads.
+ *
+ * A batch ALREADY IN HBM (KR_BASES_DEVICE) is tiled when it is submitted with KR_TILE_DEVICE: kernels (csrc/kr_dev_tiles.inc) count
+ * the tiles, choose the sequences and lay the tiled batch out from the caller's device arrays -- the batch's bytes are read once
+ * and written once, nothing crosses PCIe -- and the batch then runs exactly as a host batch's tiles do.  Two things differ from
+ * the host's tiling.  The choice is a PREFIX rule: sequence r is tiled iff it is long and the tiles of the long sequences 0 .. r
+ * together fit the stream (sum of nt - 1 <= max_reads - nreads); where the host, taking sequences greedily, may still tile a
+ * shorter sequence behind one that did not fit, the device tiles none behind it.  This only matters when the room runs out, and
+ * never for the results: tiled and untiled sequences give identical records.  And kr_batch_submit does not return before the
+ * layout's summary (tiled reads, long sequences, bases: 24 bytes) has come back -- it waits for the kernels queued so far on the
+ * stream's first lane, as kr_batch_submit_fastq waits for its summary; a batch without a long sequence is then queued as it is.
+ * KR_TILE_MIN_POS is honoured; the caller's bases are read only inside [bases + offsets[0], bases + offsets[nreads]). */
 KR_API int kr_batch_submit(kr_stream*, const uint8_t* bases, const uint64_t* offsets, uint32_t nreads,
                            uint32_t flags);
 KR_API int kr_batch_wait(kr_stream*);
@@ -427,6 +443,10 @@ KR_API void kr_host_free(void*);
  *   KR_FASTQ_NOT_CLEAN    anything else (FASTA, CRLF, wrapped lines, odd quality ...): the host reader continues at `consumed`
  *   KR_FASTQ_INCOMPLETE   bytes behind the last complete record: a record cut by the end of the chunk, or a last line without '\n'
  *   KR_FASTQ_LONG         more k-mer positions than the stream tiles a sequence from (KR_TILE_MIN_POS): the host path tiles it
+ *                         (never raised with KR_TILE_DEVICE in `flags`: the record is accepted like any other, bounded by max_reads,
+ *                         max_bases and the id buffer, and the accepted prefix is submitted with KR_BASES_DEVICE | KR_TILE_DEVICE.
+ *                         A batch that ends up tiled is not formatted on the device: kr_batch_collect_text gives
+ *                         KR_ERR_UNSUPPORTED, kr_batch_collect + kr_format_dist with kr_batch_fastq_names serve it)
  *   KR_FASTQ_CAPACITY     past max_reads, max_bases or the id buffer: submit again from `consumed` (nreads 0: the record never fits)
  *   kr_stream_fastq_enable  once per stream: device buffers for chunks of up to max_raw_bytes (< 4 GB: positions are 32-bit)
  *   kr_batch_submit_fastq   `raw` is page-locked (kr_host_alloc), starts at a record start and stays valid until the batch has been
@@ -458,6 +478,16 @@ KR_API int kr_batch_submit_fastq(kr_stream*, const uint8_t* raw, uint64_t nbytes
 KR_API int kr_batch_fastq_names(kr_stream*, const uint64_t** name_pos, const uint32_t** name_len);
 /* tests: the last kr_batch_submit_fastq's accepted bases [nbases] and offsets [nreads + 1] as the device wrote them */
 KR_API int kr_debug_fastq_batch(kr_stream*, uint8_t* bases, uint64_t* offsets);
+/* tests: the tiled form of the batch last submitted on the stream as it lies on the device, laid out by the host (a host batch)
+ * or by kernels (KR_TILE_DEVICE): reads of the tiled batch and long sequences; voff [nv + 1] where every read of the tiled batch
+ * starts in its bases, vtile [nv] 1 = a tile of a long sequence, rfirst [nreads] the caller's read's first read of the tiled batch,
+ * longs [2 * nlong] (first tile, tiles) of every long sequence, bases [voff[nv]].  *nv == 0: the batch is not tiled (nothing else
+ * is written).  Any array pointer may be NULL. */
+KR_API int kr_debug_tile_layout(kr_stream*, uint32_t* nv, uint32_t* nlong, uint64_t* voff, uint8_t* vtile, uint32_t* rfirst,
+                                uint32_t* longs, uint8_t* bases);
+/* tests (no device needed): a sequence of `len` bases as the tilers see it -- k-mer positions, tiles of 128 positions, and the
+ * bases it takes in a tiled batch (every tile but the first repeats k - 1 bases) */
+KR_API int kr_debug_tile_shape(uint64_t len, uint32_t k, uint64_t* nkm, uint64_t* nt, uint64_t* bytes);
 
 /* ------------------------------------------------------------------------- */
 /* `krepp place`: IBatch::place_sequences / report_placement (src/query.cpp:198-333), */

@@ -20,6 +20,7 @@ KR_ERR_ARG, KR_ERR_IO, KR_ERR_FORMAT, KR_ERR_NO_DEVICE = -1, -2, -3, -4
 KR_ERR_NOMEM, KR_ERR_CAPACITY, KR_ERR_STATE, KR_ERR_UNSUPPORTED = -5, -6, -7, -8
 KR_VIEW_HOST, KR_VIEW_DEVICE = 0, 1
 KR_BASES_HOST, KR_BASES_DEVICE, KR_TAP_ACCS, KR_TAP_HITS, KR_BASES_PINNED, KR_ROWS_ONLY, KR_ROWS_INDEXED = 0, 1, 2, 4, 8, 16, 32
+KR_TILE_DEVICE = 64  # with KR_BASES_DEVICE / submit_fastq: long sequences of a batch in HBM are tiled by kernels
 
 u8p = C.POINTER(C.c_uint8)
 u32p = C.POINTER(C.c_uint32)
@@ -97,7 +98,7 @@ EXPORTS = [
     "kr_index_upload", "kr_index_free", "kr_index_export", "kr_index_import", "kr_index_device_bytes", "kr_index_slot_words", "kr_index_slot_format", "kr_index_broadcast",
     "kr_params_default", "kr_stream_create", "kr_stream_destroy", "kr_batch_submit", "kr_batch_wait",
     "kr_batch_collect", "kr_batch_collect_device", "kr_stream_text_enable", "kr_batch_submit_text", "kr_batch_collect_text",
-    "kr_stream_fastq_enable", "kr_batch_submit_fastq", "kr_batch_fastq_names", "kr_debug_fastq_batch", "kr_batch_hits", "kr_batch_readtaps",
+    "kr_stream_fastq_enable", "kr_batch_submit_fastq", "kr_batch_fastq_names", "kr_debug_fastq_batch", "kr_debug_tile_layout", "kr_debug_tile_shape", "kr_batch_hits", "kr_batch_readtaps",
     "kr_debug_front_end", "kr_debug_stream_move", "kr_debug_stream_addrs", "kr_debug_item_placement", "kr_debug_brent", "kr_debug_prefix", "kr_debug_colour_classes", "kr_llh_batch", "kr_llh_eval_indexed", "kr_batch_timing",
     "kr_place_tree_create", "kr_place_tree_create_lineage", "kr_place_tree_nnodes", "kr_place_summary_add",
     "kr_place_summary_text", "kr_place_tree_free", "kr_place_tree_kinds", "kr_place_batch", "kr_place_stream", "kr_place_frame", "kr_place_counters",
@@ -198,6 +199,8 @@ def load():
     lib.kr_batch_submit_fastq.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(KrFastqParse)]
     lib.kr_batch_fastq_names.argtypes = [vp, C.POINTER(u64p), C.POINTER(u32p)]
     lib.kr_debug_fastq_batch.argtypes = [vp, vp, vp]
+    lib.kr_debug_tile_layout.argtypes = [vp, u32p, u32p, vp, vp, vp, vp, vp]
+    lib.kr_debug_tile_shape.argtypes = [C.c_uint64, C.c_uint32, u64p, u64p, u64p]
     lib.kr_fastx_next.argtypes = [vp, C.c_uint64, C.POINTER(KrFastxBatch)]
     lib.kr_fastx_detach.argtypes = [vp, C.POINTER(vp)]
     lib.kr_fastx_release.argtypes = [vp, vp]
@@ -592,6 +595,23 @@ class Stream:
         check(self.lib.kr_debug_fastq_batch(self.h, bases.ctypes.data, offs.ctypes.data))
         return [bases[int(offs[i]):int(offs[i + 1])].tobytes() for i in range(summary["nreads"])]
 
+    def tile_layout(self, nreads):
+        """(tests) kr_debug_tile_layout: the tiled form of the batch last submitted as it lies on the device, as a dict of
+        nv, nlong and the arrays voff, vtile, rfirst, longs, bases; nv == 0 (and no arrays) when the batch is not tiled"""
+        nv, nl = C.c_uint32(0), C.c_uint32(0)
+        check(self.lib.kr_debug_tile_layout(self.h, C.byref(nv), C.byref(nl), None, None, None, None, None))
+        out = {"nv": int(nv.value), "nlong": int(nl.value)}
+        if out["nv"] == 0:
+            return out
+        voff, vtile = np.zeros(out["nv"] + 1, np.uint64), np.zeros(out["nv"], np.uint8)
+        rfirst, longs = np.zeros(nreads, np.uint32), np.zeros(2 * out["nlong"], np.uint32)
+        check(self.lib.kr_debug_tile_layout(self.h, C.byref(nv), C.byref(nl), voff.ctypes.data, vtile.ctypes.data, rfirst.ctypes.data,
+                                            longs.ctypes.data, None))
+        bases = np.zeros(max(1, int(voff[-1])), np.uint8)
+        check(self.lib.kr_debug_tile_layout(self.h, C.byref(nv), C.byref(nl), None, None, None, None, bases.ctypes.data))
+        out.update(voff=voff, vtile=vtile, rfirst=rfirst, longs=longs.reshape(-1, 2), bases=bases[:int(voff[-1])])
+        return out
+
     def collect_text(self):
         """kr_batch_collect_text: the batch's report rows as the bytes the device wrote"""
         txt = C.c_void_p()
@@ -621,6 +641,13 @@ class Stream:
             self.close()
         except Exception:
             pass
+
+
+def tile_shape(length, k):
+    """(tests) kr_debug_tile_shape: (k-mer positions, tiles of 128 positions, bases in a tiled batch) of a sequence of `length` bases"""
+    a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    check(load().kr_debug_tile_shape(int(length), int(k), C.byref(a), C.byref(b), C.byref(c)))
+    return int(a.value), int(b.value), int(c.value)
 
 
 def debug_prefix(values, block, width):

@@ -17,7 +17,25 @@
 //   * kr_tile_gather_kernel lists the per-read results of the REAL reads (first tile of a long sequence, or the read itself)
 //     for the views, the copies back and `place`.
 // The likelihood and selection kernels run over the tiled batch unchanged: tiles without records are reads without records.
+//
+// Who lays the tiled batch out: build_tiles (kr_host_stream.inc) for a host batch, while it copies the batch into page-locked
+// memory; the kr_tile_lay_* kernels at the end of this file for a batch whose bases are in HBM already (KR_TILE_DEVICE).  Both
+// fill the same arrays and take a sequence's shape from tile_shape below.
 constexpr uint32_t kTileMinPos = 1024; // sequences of more k-mer positions are tiled
+
+// A sequence of `len` bases as tiles: its k-mer positions, its tiles of kSegPos positions (0 for a sequence shorter than k), and
+// the bases it takes in the tiled batch -- every tile but the first repeats the k - 1 bases before it
+struct TileShape {
+  uint64_t nkm, nt, bytes;
+};
+__host__ __device__ inline TileShape tile_shape(uint64_t len, uint32_t k)
+{
+  TileShape t;
+  t.nkm = len >= k ? len - k + 1 : 0;
+  t.nt = (t.nkm + kSegPos - 1) / kSegPos;
+  t.bytes = t.nt ? len + (t.nt - 1) * (k - 1) : len;
+  return t;
+}
 
 struct TileBatch {
   const uint8_t* v_tile;    // [nv] 1: this read of the (tiled) batch is a tile of a long sequence
@@ -235,5 +253,160 @@ __global__ __launch_bounds__(256) void kr_tile_gather_kernel(BatchOut out, TileB
     tb.real_onmers[r] = out.rd_onmers[v];
     tb.real_filt[2 * r] = out.rd_filt[2 * v], tb.real_filt[2 * r + 1] = out.rd_filt[2 * v + 1];
     tb.real_na[r] = out.rd_na[v];
+  }
+}
+
+// ---------------------------------------------------------------------------
+// The tiled batch laid out on the device (KR_BASES_DEVICE | KR_TILE_DEVICE, kr_batch_submit_fastq with KR_TILE_DEVICE): what
+// build_tiles does on the host, from the caller's bases and offsets in HBM.  Blocks of kTileBlock reads, thread t owning the reads
+// 4t .. 4t+3 of its block, and the three steps of kr_dev_prefix.inc twice over:
+//   kr_tile_lay_count_kernel   per block: the reads the long sequences' tiles would ADD to the batch (nt - 1 each)
+//   kr_tile_lay_escan_kernel   one workgroup: the blocks' first values of that sum
+//   kr_tile_lay_choose_kernel  read r is tiled iff it is long and the inclusive prefix of the sum over the reads 0 .. r is at most
+//                              `spare` (max_reads - nreads): a PREFIX of the long sequences, decided by the one scan.  (The host
+//                              takes the sequences greedily and may still tile a shorter one behind one that did not fit; the
+//                              results are the same either way.)  Per block: reads, bases and long sequences of the tiled batch
+//   kr_tile_lay_lscan_kernel   one workgroup: the blocks' first values of the three; the summary {nv, nlong, bases}
+//   kr_tile_lay_reads_kernel   per read: r_first, its place in voff; an untiled read's v_tile and source, a long one's `longs` entry
+//   kr_tile_lay_tiles_kernel   a wave per long sequence: voff, v_tile and source of its nt tiles
+// The host waits for the summary, makes room for the bases, and
+//   kr_tile_lay_copy_kernel    a wave per read of the tiled batch copies its bases: byte loads, so that nothing outside
+//                              [bases + offsets[0], bases + offsets[nreads]) is touched -- the caller's buffer may end there
+// ---------------------------------------------------------------------------
+constexpr uint32_t kTileBlock = 1024; // reads per workgroup of the layout passes: 256 lanes x 4
+
+struct TileLayIO {
+  const uint8_t* bases;    // the caller's
+  const uint64_t* offsets; // [nreads + 1]
+  uint32_t nreads, k, tile_min_pos;
+  uint64_t spare;          // reads the stream has beyond the batch's
+  uint32_t nblk;           // blocks of kTileBlock reads
+  uint64_t *bsum_e, *bsum_v, *bsum_b, *bsum_l; // [nblk] per block, then (in place) the blocks' first values: added reads | reads | bases | long sequences
+  uint8_t* choice;         // [nreads] 1: the read is tiled
+  uint32_t* lread;         // [nlong] the long sequences' reads
+  uint64_t* vsrc;          // [nv] where a read of the tiled batch starts in `bases`
+  uint64_t* voff;          // [nv + 1]  the arrays of TileBatch / the tiled BatchIn
+  uint8_t* vtile;          // [nv]
+  uint32_t* rfirst;        // [nreads]
+  uint32_t* longs;         // [2 * nlong]
+  uint64_t* sum;           // [3] nv, nlong, bases of the tiled batch
+  uint8_t* dst;            // the tiled batch's bases (kr_tile_lay_copy_kernel)
+};
+
+// reads that tiling read r would add to the batch; 0: not a long sequence (tile_min_pos >= kSegPos: a long one has two tiles at least)
+__device__ __forceinline__ uint64_t tile_lay_extra(const TileLayIO& t, uint64_t r)
+{
+  const TileShape sh = tile_shape(t.offsets[r + 1] - t.offsets[r], t.k);
+  return sh.nkm > t.tile_min_pos ? sh.nt - 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void kr_tile_lay_count_kernel(TileLayIO t)
+{
+  for (uint32_t b = blockIdx.x; b < t.nblk; b += gridDim.x) {
+    uint64_t e = 0;
+#pragma unroll
+    for (uint32_t q = 0; q < 4; ++q) {
+      const uint64_t r = (uint64_t)b * kTileBlock + 4u * threadIdx.x + q;
+      if (r < t.nreads) e += tile_lay_extra(t, r);
+    }
+    const uint64_t tot = block_sum(e);
+    if (threadIdx.x == 0) t.bsum_e[b] = tot;
+  }
+}
+
+__global__ __launch_bounds__(1024) void kr_tile_lay_escan_kernel(TileLayIO t) { scan_block_sums(t.bsum_e, t.nblk); }
+
+__global__ __launch_bounds__(256) void kr_tile_lay_choose_kernel(TileLayIO t)
+{
+  for (uint32_t b = blockIdx.x; b < t.nblk; b += gridDim.x) {
+    const uint64_t r0 = (uint64_t)b * kTileBlock + 4u * threadIdx.x;
+    uint64_t e[4], tot = 0;
+#pragma unroll
+    for (uint32_t q = 0; q < 4; ++q) {
+      e[q] = r0 + q < t.nreads ? tile_lay_extra(t, r0 + q) : 0u;
+      tot += e[q];
+    }
+    uint64_t run = t.bsum_e[b] + block_scan_excl(tot), sv = 0, sb = 0, sl = 0;
+#pragma unroll
+    for (uint32_t q = 0; q < 4; ++q) {
+      const uint64_t r = r0 + q;
+      if (r >= t.nreads) break;
+      run += e[q]; // inclusive
+      const bool tiled = e[q] != 0 && run <= t.spare;
+      const uint64_t len = t.offsets[r + 1] - t.offsets[r];
+      const TileShape sh = tile_shape(len, t.k);
+      t.choice[r] = tiled ? 1 : 0;
+      sv += tiled ? sh.nt : 1u, sb += tiled ? sh.bytes : len, sl += tiled ? 1u : 0u;
+    }
+    const uint64_t tv = block_sum(sv), tb = block_sum(sb), tl = block_sum(sl);
+    if (threadIdx.x == 0) t.bsum_v[b] = tv, t.bsum_b[b] = tb, t.bsum_l[b] = tl;
+  }
+}
+
+__global__ __launch_bounds__(1024) void kr_tile_lay_lscan_kernel(TileLayIO t)
+{
+  const uint64_t nv = scan_block_sums(t.bsum_v, t.nblk);
+  const uint64_t nb = scan_block_sums(t.bsum_b, t.nblk);
+  const uint64_t nl = scan_block_sums(t.bsum_l, t.nblk);
+  if (threadIdx.x == 0) t.sum[0] = nv, t.sum[1] = nl, t.sum[2] = nb;
+}
+
+__global__ __launch_bounds__(256) void kr_tile_lay_reads_kernel(TileLayIO t)
+{
+  for (uint32_t b = blockIdx.x; b < t.nblk; b += gridDim.x) {
+    const uint64_t r0 = (uint64_t)b * kTileBlock + 4u * threadIdx.x;
+    uint64_t uv[4], ub[4], tv = 0, tb = 0, tl = 0;
+    bool c[4];
+#pragma unroll
+    for (uint32_t q = 0; q < 4; ++q) {
+      uv[q] = 0, ub[q] = 0, c[q] = false;
+      if (r0 + q < t.nreads) {
+        const uint64_t len = t.offsets[r0 + q + 1] - t.offsets[r0 + q];
+        const TileShape sh = tile_shape(len, t.k);
+        c[q] = t.choice[r0 + q] != 0;
+        uv[q] = c[q] ? sh.nt : 1u, ub[q] = c[q] ? sh.bytes : len;
+      }
+      tv += uv[q], tb += ub[q], tl += c[q] ? 1u : 0u;
+    }
+    uint64_t v = t.bsum_v[b] + block_scan_excl(tv), by = t.bsum_b[b] + block_scan_excl(tb), li = t.bsum_l[b] + block_scan_excl(tl);
+#pragma unroll
+    for (uint32_t q = 0; q < 4; ++q) {
+      const uint64_t r = r0 + q;
+      if (r >= t.nreads) break;
+      t.rfirst[r] = (uint32_t)v;
+      t.voff[v] = by; // (a long sequence: of its first tile; kr_tile_lay_tiles_kernel goes on from here)
+      if (c[q]) {
+        t.longs[2 * li] = (uint32_t)v, t.longs[2 * li + 1] = (uint32_t)uv[q], t.lread[li] = (uint32_t)r;
+        ++li;
+      } else {
+        t.vtile[v] = 0, t.vsrc[v] = t.offsets[r];
+      }
+      v += uv[q], by += ub[q];
+      if (r + 1 == t.nreads) t.voff[v] = by; // the end of the tiled batch
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void kr_tile_lay_tiles_kernel(TileLayIO t)
+{
+  const uint32_t nlong = (uint32_t)t.sum[1], lane = lane_id(), nw = gridDim.x * 4u;
+  const uint64_t step = (uint64_t)kSegPos + t.k - 1; // bases of every tile but a sequence's last
+  for (uint32_t li = blockIdx.x * 4u + (threadIdx.x >> 6); li < nlong; li += nw) {
+    const uint64_t v0 = t.longs[2 * li], nt = t.longs[2 * li + 1], src = t.offsets[t.lread[li]], b0 = t.voff[v0];
+    for (uint64_t ti = lane; ti < nt; ti += kWave) { // tile ti: k-mer positions [ti * kSegPos, ...), bases from the first one's start
+      if (ti) t.voff[v0 + ti] = b0 + ti * step;
+      t.vtile[v0 + ti] = 1, t.vsrc[v0 + ti] = src + ti * kSegPos;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void kr_tile_lay_copy_kernel(TileLayIO t)
+{
+  const uint32_t nv = (uint32_t)t.sum[0], lane = lane_id(), nw = gridDim.x * 4u;
+  for (uint32_t v = blockIdx.x * 4u + (threadIdx.x >> 6); v < nv; v += nw) {
+    const uint64_t d0 = t.voff[v], n = t.voff[v + 1] - d0;
+    const uint8_t* src = t.bases + t.vsrc[v];
+    uint8_t* dst = t.dst + d0;
+    for (uint64_t i = lane; i < n; i += kWave) dst[i] = src[i];
   }
 }

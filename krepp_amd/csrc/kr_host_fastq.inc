@@ -1,6 +1,6 @@
 // kr_host_fastq.inc -- part of kr_device.hip (host side): kr_stream_fastq_enable, kr_batch_submit_fastq, kr_batch_fastq_names.
 // A batch given as the raw bytes of a plain FASTQ file; the records are found by the kernels of kr_dev_fastq.inc, then the batch
-// runs on the submit_batch path with its bases already in HBM.
+// runs on the submit_batch path with its bases already in HBM (with KR_TILE_DEVICE: long records too, tiled by build_tiles_device).
 
 extern "C" {
 
@@ -58,7 +58,8 @@ int kr_batch_submit_fastq(kr_stream* s, const uint8_t* raw, uint64_t nbytes, uin
   io.ids = text ? s->text.d_ids : nullptr;
   io.id_off = text ? s->text.d_id_off : f.d_id_off;
   io.max_reads = s->max_reads, io.max_bases = s->max_bases, io.id_cap = text ? s->text.id_cap : ~0ull;
-  io.k = s->ix->dix.k, io.tile_min_pos = s->tile_min_pos;
+  // KR_TILE_DEVICE: a long record is accepted like any other (no k-mer count exceeds the bound) and tiled on the device below
+  io.k = s->ix->dix.k, io.tile_min_pos = (flags & KR_TILE_DEVICE) ? 0xFFFFFFFFu : s->tile_min_pos;
   io.sum = f.d_sum;
   // queued before the index's kernel chain is waited for (launch_lane): the copy and the parse overlap other streams' batches
   HIP_TRY(hipMemcpyAsync(f.d_raw, raw, nbytes, hipMemcpyHostToDevice, st));

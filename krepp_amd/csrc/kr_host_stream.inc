@@ -127,9 +127,10 @@ struct kr_stream {
     bool dbg_sticky = false;
   } pw;
   // Long sequences across waves (kr_dev_tiles.inc): a host batch with sequences of more than kTileMinPos k-mer positions
-  // is submitted as a batch of tiles.  Buffers are made on first use.
+  // is submitted as a batch of tiles, and so is a batch in HBM submitted with KR_TILE_DEVICE.  Buffers are made on first use.
   struct Tiles {
     bool active = false;   // the batch in flight is tiled: `nreads` real reads, `nv` reads on the device
+    bool on_device = false; // ... and the d_ arrays were filled by the kr_tile_lay_* kernels (no h_ array holds anything of it)
     uint32_t nv = 0, nlong = 0;
     PinBuf<uint8_t> h_bases; // the tiled batch's bases (tiles overlap by k - 1); one capacity with d_bases
     DevBuf<uint8_t> d_bases;
@@ -141,6 +142,11 @@ struct kr_stream {
     DevBuf<uint32_t> d_rfirst, d_longs;
     DevBuf<uint32_t> d_tile_filt, d_real_off, d_real_cnt, d_real_onmers, d_real_filt;
     DevBuf<uint8_t> d_real_na;
+    // the layout on the device: per-read scratch ([max_reads]), the block sums and the summary {nv, nlong, bases}
+    DevBuf<uint8_t> d_choice;
+    DevBuf<uint32_t> d_lread;
+    DevBuf<uint64_t> d_vsrc, d_bsum, d_sum;
+    PinBuf<uint64_t> h_sum;
   } tiles;
   bool no_tiles = false;   // (a tiled batch that overflowed a device buffer is run again untiled)
   std::vector<uint8_t> tile_choice; // per read of the batch in hand: submitted as tiles
@@ -274,12 +280,12 @@ int build_tiles(kr_stream* s, const uint8_t* bases, const uint64_t* offsets, uin
   std::vector<uint8_t>& tile_it = s->tile_choice;
   tile_it.assign(nreads, 0);
   for (uint32_t r = 0; r < nreads; ++r) {
-    const uint64_t len = offsets[r + 1] - offsets[r], nkm = len >= k ? len - k + 1 : 0;
-    const uint64_t nt = (nkm + kSegPos - 1) / kSegPos;
-    if (nkm > s->tile_min_pos && nt - 1 <= spare) {
-      spare -= nt - 1;
+    const uint64_t len = offsets[r + 1] - offsets[r];
+    const TileShape sh = tile_shape(len, k);
+    if (sh.nkm > s->tile_min_pos && sh.nt - 1 <= spare) {
+      spare -= sh.nt - 1;
       tile_it[r] = 1;
-      nv += nt, nb += len + (nt - 1) * (k - 1), ++nlong;
+      nv += sh.nt, nb += sh.bytes, ++nlong;
     } else {
       nv += 1, nb += len;
     }
@@ -304,10 +310,10 @@ int build_tiles(kr_stream* s, const uint8_t* bases, const uint64_t* offsets, uin
   uint32_t li = 0;
   for (uint32_t r = 0; r < nreads; ++r) {
     const uint8_t* src = bases + offsets[r];
-    const uint64_t len = offsets[r + 1] - offsets[r], nkm = len >= k ? len - k + 1 : 0;
+    const uint64_t len = offsets[r + 1] - offsets[r];
     h_rfirst[r] = (uint32_t)v;
     if (tile_it[r]) {
-      const uint64_t nt = (nkm + kSegPos - 1) / kSegPos;
+      const uint64_t nt = tile_shape(len, k).nt;
       h_longs[2 * li] = (uint32_t)v, h_longs[2 * li + 1] = (uint32_t)nt, ++li;
       for (uint64_t ti = 0; ti < nt; ++ti) { // tile ti: k-mer positions [ti * kSegPos, ...), bases from the first one's start
         const uint64_t b0 = ti * kSegPos, b1 = std::min<uint64_t>(len, b0 + kSegPos + k - 1);
@@ -322,7 +328,59 @@ int build_tiles(kr_stream* s, const uint8_t* bases, const uint64_t* offsets, uin
     }
   }
   h_voff[v] = pos;
-  t.nv = (uint32_t)v, t.nlong = nlong;
+  t.nv = (uint32_t)v, t.nlong = nlong, t.on_device = false;
+  *tiled = true;
+  return KR_OK;
+}
+
+// The same for a batch whose bases and offsets are in HBM (KR_TILE_DEVICE): the kr_tile_lay_* kernels fill the device arrays on
+// lane 0's stream, and the call waits for their summary {nv, nlong, bases} -- the tiled bases need room before they are copied, and
+// a batch without a long sequence is submitted as it is.  Sequences are chosen by a prefix rule (kr_dev_tiles.inc).
+int build_tiles_device(kr_stream* s, const uint8_t* bases, const uint64_t* offsets, uint32_t nreads, bool* tiled)
+{
+  *tiled = false;
+  kr_stream::Tiles& t = s->tiles;
+  HIP_TRY(hipSetDevice(s->device));
+  const uint64_t c = s->max_reads;
+  const uint32_t nblk = (uint32_t)(((uint64_t)nreads + kTileBlock - 1) / kTileBlock);
+  const uint64_t blk_cap = c / kTileBlock + 2;
+  if (!reserve_all(c + 1, t.d_voff) ||
+      !reserve_all(c, t.d_vtile, t.d_rfirst, t.d_real_off, t.d_real_cnt, t.d_real_onmers, t.d_real_na, t.d_choice, t.d_lread, t.d_vsrc) ||
+      !reserve_all(2 * c, t.d_longs, t.d_tile_filt, t.d_real_filt) || !reserve_all(4 * blk_cap, t.d_bsum) || !reserve_all(4, t.d_sum, t.h_sum))
+    return alloc_failed("build_tiles_device");
+  hipStream_t st = s->lanes[0].stream;
+  TileLayIO io;
+  io.bases = bases, io.offsets = offsets;
+  io.nreads = nreads, io.k = s->ix->dix.k, io.tile_min_pos = s->tile_min_pos;
+  io.spare = s->max_reads - nreads;
+  io.nblk = nblk;
+  io.bsum_e = t.d_bsum.get(), io.bsum_v = io.bsum_e + blk_cap, io.bsum_b = io.bsum_v + blk_cap, io.bsum_l = io.bsum_b + blk_cap;
+  io.choice = t.d_choice.get(), io.lread = t.d_lread.get(), io.vsrc = t.d_vsrc.get();
+  io.voff = t.d_voff.get(), io.vtile = t.d_vtile.get(), io.rfirst = t.d_rfirst.get(), io.longs = t.d_longs.get();
+  io.sum = t.d_sum.get();
+  io.dst = nullptr;
+  const dim3 bgrid(std::min<uint32_t>(nblk, 4096u));
+  hipLaunchKernelGGL(kr_tile_lay_count_kernel, bgrid, dim3(256), 0, st, io);
+  hipLaunchKernelGGL(kr_tile_lay_escan_kernel, dim3(1), dim3(1024), 0, st, io);
+  hipLaunchKernelGGL(kr_tile_lay_choose_kernel, bgrid, dim3(256), 0, st, io);
+  hipLaunchKernelGGL(kr_tile_lay_lscan_kernel, dim3(1), dim3(1024), 0, st, io);
+  hipLaunchKernelGGL(kr_tile_lay_reads_kernel, bgrid, dim3(256), 0, st, io);
+  // (a wave per long sequence, and there are at most `spare` + 1 ... nreads of them: the grid is bounded, the loop strides)
+  hipLaunchKernelGGL(kr_tile_lay_tiles_kernel, dim3(std::min<uint32_t>((nreads + 3) / 4, 8192u)), dim3(256), 0, st, io);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(t.h_sum.get(), t.d_sum.get(), 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const uint64_t nv = t.h_sum.get()[0], nlong = t.h_sum.get()[1], nb = t.h_sum.get()[2];
+  if (nlong == 0) return KR_OK; // nothing to tile (or no room for the first long sequence's tiles)
+  if (nv > s->max_reads) return kr::fail(KR_ERR_ARG, "kr_batch_submit: the device offsets do not ascend"); // (the prefix rule keeps nv <= max_reads)
+  if (nb + 256 > t.d_bases.size() && !t.d_bases.reserve(nb + nb / 4 + 256)) {
+    t.h_bases.reset(); // (one capacity with d_bases: build_tiles asks for both again)
+    return alloc_failed("build_tiles_device");
+  }
+  io.dst = t.d_bases.get();
+  hipLaunchKernelGGL(kr_tile_lay_copy_kernel, dim3((uint32_t)std::min<uint64_t>((nv + 3) / 4, 16384u)), dim3(256), 0, st, io);
+  HIP_TRY(hipGetLastError());
+  t.nv = (uint32_t)nv, t.nlong = (uint32_t)nlong, t.on_device = true;
   *tiled = true;
   return KR_OK;
 }
@@ -909,6 +967,17 @@ static int submit_batch(kr_stream* s, const uint8_t* bases, const uint64_t* offs
       return rc;
     }
     s->tiles.active = tiled;
+  } else if ((flags & KR_BASES_DEVICE) && (flags & KR_TILE_DEVICE) && !(flags & KR_TAP_HITS) && !s->no_tiles && !getenv("KR_NO_TILES")) {
+    bool tiled = false; // ... and a batch in HBM whose caller asks for it: the same arrays, laid out by kernels
+    const int rc = build_tiles_device(s, bases, offsets, nreads, &tiled);
+    if (rc) {
+      const std::string msg = kr_last_error();
+      (void)hipStreamSynchronize(s->lanes[0].stream);
+      (void)hipGetLastError();
+      s->waited = true, s->nlanes = 0, s->batch_rc = rc, s->batch_msg = msg;
+      return kr::fail(rc, msg);
+    }
+    s->tiles.active = tiled;
   }
   // lanes of this batch: ranges of at least lane_min_reads reads; the hit tap (tests) keeps one hit buffer, hence one lane
   uint32_t P = std::min<uint32_t>(s->max_lanes, std::max<uint32_t>(1u, nreads / s->lane_min_reads));
@@ -937,11 +1006,13 @@ static int submit_batch(kr_stream* s, const uint8_t* bases, const uint64_t* offs
     HIP_TRY(hipEventRecord(L.ev[kEvCopyIn], st));
     if (s->tiles.active) { // the tiled batch: its own bases and offsets, and what the tile kernels need
       kr_stream::Tiles& t = s->tiles;
-      HIP_TRY(hipMemcpyAsync(t.d_bases.get(), t.h_bases.get(), t.h_voff.get()[t.nv], hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(t.d_voff.get(), t.h_voff.get(), ((uint64_t)t.nv + 1) * 8, hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(t.d_vtile.get(), t.h_vtile.get(), t.nv, hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(t.d_rfirst.get(), t.h_rfirst.get(), (uint64_t)nreads * 4, hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(t.d_longs.get(), t.h_longs.get(), (uint64_t)t.nlong * 8, hipMemcpyHostToDevice, st));
+      if (!t.on_device) { // (else the layout kernels wrote them, on this stream)
+        HIP_TRY(hipMemcpyAsync(t.d_bases.get(), t.h_bases.get(), t.h_voff.get()[t.nv], hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(t.d_voff.get(), t.h_voff.get(), ((uint64_t)t.nv + 1) * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(t.d_vtile.get(), t.h_vtile.get(), t.nv, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(t.d_rfirst.get(), t.h_rfirst.get(), (uint64_t)nreads * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(t.d_longs.get(), t.h_longs.get(), (uint64_t)t.nlong * 8, hipMemcpyHostToDevice, st));
+      }
       L.in.bases = t.d_bases.get();
       L.in.offsets = t.d_voff.get();
       L.nreads = t.nv;
@@ -1490,6 +1561,41 @@ int kr_batch_timing(kr_stream* s, kr_timing* t)
 }
 
 } // extern "C"
+
+// (tests) the tiled form of the batch last submitted, as it lies on the device -- whoever laid it out
+int kr_debug_tile_layout(kr_stream* s, uint32_t* nv, uint32_t* nlong, uint64_t* voff, uint8_t* vtile, uint32_t* rfirst, uint32_t* longs, uint8_t* bases)
+{
+  kr::clear_error();
+  if (!s || !nv || !nlong) return kr::fail(KR_ERR_ARG, "kr_debug_tile_layout: null argument");
+  *nv = 0, *nlong = 0;
+  if (!s->submitted || !s->tiles.active) return KR_OK;
+  const kr_stream::Tiles& t = s->tiles;
+  HIP_TRY(hipSetDevice(s->device));
+  hipStream_t st = s->lanes[0].stream; // (a tiled batch has one lane: its copies or layout kernels are queued here)
+  *nv = t.nv, *nlong = t.nlong;
+  uint64_t nb = 0;
+  HIP_TRY(hipMemcpyAsync(&nb, t.d_voff.get() + t.nv, 8, hipMemcpyDeviceToHost, st));
+  if (voff) HIP_TRY(hipMemcpyAsync(voff, t.d_voff.get(), ((uint64_t)t.nv + 1) * 8, hipMemcpyDeviceToHost, st));
+  if (vtile) HIP_TRY(hipMemcpyAsync(vtile, t.d_vtile.get(), t.nv, hipMemcpyDeviceToHost, st));
+  if (rfirst) HIP_TRY(hipMemcpyAsync(rfirst, t.d_rfirst.get(), (uint64_t)s->nreads * 4, hipMemcpyDeviceToHost, st));
+  if (longs) HIP_TRY(hipMemcpyAsync(longs, t.d_longs.get(), (uint64_t)t.nlong * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (bases && nb) {
+    HIP_TRY(hipMemcpyAsync(bases, t.d_bases.get(), nb, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  return KR_OK;
+}
+
+// (tests, no device needed) tile_shape: k-mer positions, tiles and tiled bases of a sequence of `len` bases
+int kr_debug_tile_shape(uint64_t len, uint32_t k, uint64_t* nkm, uint64_t* nt, uint64_t* bytes)
+{
+  kr::clear_error();
+  if (!nkm || !nt || !bytes || k == 0) return kr::fail(KR_ERR_ARG, "kr_debug_tile_shape: bad argument");
+  const TileShape sh = tile_shape(len, k);
+  *nkm = sh.nkm, *nt = sh.nt, *bytes = sh.bytes;
+  return KR_OK;
+}
 
 // Bytes the last kr_batch_collect of a rows-only batch copied back to the host (bench.py's host-inclusive leg reports them).
 int kr_debug_last_d2h_bytes(kr_stream* s, uint64_t* bytes)

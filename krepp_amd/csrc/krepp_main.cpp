@@ -325,8 +325,8 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
   std::vector<kr_stream*> streams_to_free;
   kr_fastx* fx = nullptr; // (opened before the workers start; they hand batches back to it)
   // --gpu-parse (`dist` only, plain regular files): the reader only moves bytes into page-locked chunks cut at guessed record starts;
-  // each worker finds the records of its chunks on its GPU (kr_batch_submit_fastq).  The first chunk that stops early (a record
-  // that is not clean four-line FASTQ, a long sequence, a wrong cut, a batch that overflows) names the byte where the host reader
+  // each worker finds the records of its chunks on its GPU (kr_batch_submit_fastq with KR_TILE_DEVICE: long records are tiled on the
+  // device).  The first chunk that stops early (a record that is not clean four-line FASTQ, a wrong cut, a batch that overflows) names the byte where the host reader
   // (kr_fastx_open_at) takes over for good; chunks behind it were handed out already and are dropped unwritten (their sequence
   // numbers are skipped by the writer, in order), as the pool reader's "first surprise -> sequential to the end" (kr_host.cpp).
   bool gpu_parse = !place && !seek && a.flag.count("--gpu-parse") && a.flag.at("--gpu-parse");
@@ -579,7 +579,8 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
         while (pos < j->raw_len) {
           kr_fastq_parse fp;
           auto t_dev = now();
-          int rc = kr_batch_submit_fastq(st, j->raw + pos, j->raw_len - pos, text_on ? 0u : KR_ROWS_ONLY, j->at_eof ? 1u : 0u, &fp);
+          // (KR_TILE_DEVICE: a long record stays with the device, tiled there; its batch comes back through kr_batch_collect below)
+          int rc = kr_batch_submit_fastq(st, j->raw + pos, j->raw_len - pos, (text_on ? 0u : KR_ROWS_ONLY) | KR_TILE_DEVICE, j->at_eof ? 1u : 0u, &fp);
           if (rc) return rc;
           if (fp.nreads) {
             const char* dtext = nullptr;
@@ -629,7 +630,7 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
           pos += fp.consumed;
           if (fp.status == KR_FASTQ_OK) break;
           if (fp.status == KR_FASTQ_CAPACITY && fp.nreads) continue;
-          fell = true; // not clean, a long sequence, a record cut by the end of the chunk or the file: the host reader from here
+          fell = true; // not clean, a record cut by the end of the chunk or the file: the host reader from here
           break;
         }
         // in the output's order: only a chunk that no earlier chunk's stop has dropped counts
