@@ -196,8 +196,9 @@ KR_API void kr_stream_destroy(kr_stream*);
                            /* only -- the records report_distances prints (src/query.cpp:158-196),    */
                            /* compacted on the device, 12 bytes a row across PCIe: nrecs == nrows,    */
                            /* every rec_sel is 1, read_off / read_cnt are the reads' row ranges (a    */
-                           /* tiled batch still comes back as record slots with flags: same fields,   */
-                           /* same meaning, rec_sel 0 where a record is not a row)                    */
+                           /* tiled batch still comes back as record slots with flags -- same fields, */
+                           /* same meaning, rec_sel 0 where a record is not a row -- unless it is     */
+                           /* submitted with KR_TILE_ROWS)                                            */
 #define KR_ROWS_INDEXED 32u /* with KR_ROWS_ONLY: DIST leaves the device as an INDEX -- the likelihood    */
                            /* stage solves every distinct problem of a batch once (one in ~20 records), */
                            /* so a row is (rec_key, rec_dix), 8 bytes across PCIe instead of 12, and    */
@@ -211,6 +212,16 @@ KR_API void kr_stream_destroy(kr_stream*);
                            /* caller's device bases / offsets (see "Long sequences" below).  The submit then WAITS    */
                            /* for a 24-byte summary of the layout before it returns.  Ignored for host input (which   */
                            /* is tiled anyway), with KR_TAP_HITS and while KR_NO_TILES is set                          */
+#define KR_TILE_ROWS 128u  /* with KR_ROWS_ONLY: a batch that ends up TILED (a host batch with long sequences, or one tiled  */
+                           /* with KR_TILE_DEVICE) leaves the device as compact rows too, exactly as an untiled rows batch: */
+                           /* 12 bytes a row, a read's rows contiguous, nrecs == nrows, every rec_sel 1, read_off / read_cnt */
+                           /* / read_na those of the CALLER's reads -- and a batch submitted with kr_batch_submit_text or   */
+                           /* kr_batch_submit_fastq on a stream with text enabled has its report text written by the device */
+                           /* (kr_batch_collect_text returns the bytes instead of KR_ERR_UNSUPPORTED).  Without the flag a   */
+                           /* tiled batch comes back as record slots, holes of the tiles' own records included.  Opt-in;     */
+                           /* ignored (never an error) with KR_TAP_ACCS / KR_TAP_HITS, while KR_NO_ROW_COMPACTION is set, and */
+                           /* for a batch that does not end up tiled.  KR_ROWS_INDEXED stays not honoured for tiled batches  */
+                           /* (rec_dix == NULL says so).  kr_batch_collect_device still shows record slots.                  */
 
 /* Queue one batch: `bases` = concatenated ASCII sequences exactly as the FASTX
  * reader delivers them (QSeq::read_next_batch, src/rqseq.cpp:180-197),
@@ -278,7 +289,7 @@ KR_API int kr_batch_collect(kr_stream*, kr_result_view* out);
 /* As above but the arrays stay in HBM (device pointers); only counts are read back.  Device view: `nrecs` is
  * the extent of record slots handed out, unused slots (rec_key == 0) included; always go through read_off / read_cnt. */
 KR_API int kr_batch_collect_device(kr_stream*, kr_result_view* out);
-/* Bytes the last kr_batch_collect of a rows-only batch copied back over PCIe (measurement aid). */
+/* Bytes the last kr_batch_collect copied back over PCIe: rows or record slots, and the per-read arrays (measurement aid). */
 KR_API int kr_debug_last_d2h_bytes(kr_stream*, uint64_t* bytes);
 /* Tests: one number as `krepp place` rows print it (std::fixed, 5 decimals; `out` holds 80 bytes); returns its length. */
 KR_API int kr_debug_place_fixed5(double v, char* out);
@@ -420,8 +431,9 @@ KR_API int kr_format_seek(const kr_host_index*, const kr_index*, const kr_result
  *                           delivers them); ids and id_off may be pageable, they are staged before the call returns
  *   kr_batch_collect_text   waits, copies the text back; *text points into the stream's page-locked buffer and stays valid until the
  *                           next submit on this stream.  KR_ERR_CAPACITY: more text (or ids) than the buffers hold -- resubmit in
- *                           smaller pieces; KR_ERR_UNSUPPORTED: the batch could not be formatted on the device (it was tiled: long
- *                           sequences; or a DIST outside [0, 1000)): kr_batch_collect + kr_format_dist still serve it, no resubmit.
+ *                           smaller pieces; KR_ERR_UNSUPPORTED: the batch could not be formatted on the device (it was tiled -- long
+ *                           sequences -- and submitted without KR_TILE_ROWS; or a DIST outside [0, 1000)): kr_batch_collect +
+ *                           kr_format_dist still serve it, no resubmit.
  * Byte-identical to kr_format_dist (tests/test_gpu_text.py). */
 KR_API int kr_stream_text_enable(kr_stream*, const kr_host_index*, uint64_t max_text_bytes, uint64_t max_id_bytes);
 KR_API int kr_batch_submit_text(kr_stream*, const uint8_t* bases, const uint64_t* offsets, uint32_t nreads, uint32_t flags,
@@ -445,8 +457,9 @@ KR_API void kr_host_free(void*);
  *   KR_FASTQ_LONG         more k-mer positions than the stream tiles a sequence from (KR_TILE_MIN_POS): the host path tiles it
  *                         (never raised with KR_TILE_DEVICE in `flags`: the record is accepted like any other, bounded by max_reads,
  *                         max_bases and the id buffer, and the accepted prefix is submitted with KR_BASES_DEVICE | KR_TILE_DEVICE.
- *                         A batch that ends up tiled is not formatted on the device: kr_batch_collect_text gives
- *                         KR_ERR_UNSUPPORTED, kr_batch_collect + kr_format_dist with kr_batch_fastq_names serve it)
+ *                         A batch that ends up tiled is formatted on the device only with KR_TILE_ROWS in `flags` as well;
+ *                         without it kr_batch_collect_text gives KR_ERR_UNSUPPORTED, and kr_batch_collect + kr_format_dist
+ *                         with kr_batch_fastq_names serve it)
  *   KR_FASTQ_CAPACITY     past max_reads, max_bases or the id buffer: submit again from `consumed` (nreads 0: the record never fits)
  *   kr_stream_fastq_enable  once per stream: device buffers for chunks of up to max_raw_bytes (< 4 GB: positions are 32-bit)
  *   kr_batch_submit_fastq   `raw` is page-locked (kr_host_alloc), starts at a record start and stays valid until the batch has been

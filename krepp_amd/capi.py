@@ -21,6 +21,7 @@ KR_ERR_NOMEM, KR_ERR_CAPACITY, KR_ERR_STATE, KR_ERR_UNSUPPORTED = -5, -6, -7, -8
 KR_VIEW_HOST, KR_VIEW_DEVICE = 0, 1
 KR_BASES_HOST, KR_BASES_DEVICE, KR_TAP_ACCS, KR_TAP_HITS, KR_BASES_PINNED, KR_ROWS_ONLY, KR_ROWS_INDEXED = 0, 1, 2, 4, 8, 16, 32
 KR_TILE_DEVICE = 64  # with KR_BASES_DEVICE / submit_fastq: long sequences of a batch in HBM are tiled by kernels
+KR_TILE_ROWS = 128  # with KR_ROWS_ONLY: a batch that ends up tiled leaves the device as compact rows (and as device text) too
 
 u8p = C.POINTER(C.c_uint8)
 u32p = C.POINTER(C.c_uint32)
@@ -552,6 +553,16 @@ class Stream:
         self._keep = (bases, offsets, ids, id_off)
         self._flags = flags | KR_ROWS_ONLY
         check(self.lib.kr_batch_submit_text(self.h, bases.ctypes.data, offsets.ctypes.data, len(offsets) - 1, flags, ids.ctypes.data, id_off.ctypes.data, sep))
+
+    def submit_text_device(self, bases_ptr, offsets_ptr, nreads, names, flags=0, sep=1):
+        """kr_batch_submit_text of a batch whose bases and offsets are in HBM (KR_BASES_DEVICE is added); the ids come from the host"""
+        enc = [n.encode() for n in names]
+        ids = np.frombuffer((b"\0" * sep).join(enc) + b"\0" * sep, dtype=np.uint8)
+        id_off = np.zeros(len(enc) + 1, dtype=np.uint32)
+        np.cumsum(np.fromiter((len(e) + sep for e in enc), dtype=np.uint32, count=len(enc)), out=id_off[1:])
+        self._keep = (ids, id_off)
+        self._flags = flags | KR_BASES_DEVICE | KR_ROWS_ONLY
+        check(self.lib.kr_batch_submit_text(self.h, int(bases_ptr), int(offsets_ptr), int(nreads), flags | KR_BASES_DEVICE, ids.ctypes.data, id_off.ctypes.data, sep))
 
     def fastq_enable(self, max_raw_bytes):
         """kr_stream_fastq_enable: this stream can be given batches as raw FASTQ bytes (csrc/kr_dev_fastq.inc)"""

@@ -199,6 +199,8 @@ struct BatchOut {
   uint32_t* row_bsum;    // [ceil(nreads / kRowBlock) + 1] rows per block of reads, then (in place) the blocks' first rows
   uint32_t* row_key;     // [rec_cap] aliases rec_rep (dead once the select kernel has run)
   double* row_d;         // [rec_cap] aliases rep_dv (likewise)
+                         // (tiled batches submitted with KR_TILE_ROWS use the two as well: what runs behind the select kernels there --
+                         //  kr_tile_gather_kernel, per-read arrays only; kr_rebase_kernel never, a tiled batch is one lane -- reads neither)
   // KR_ROWS_INDEXED (one-lane batches): a row is (key, position of its DIST in the batch's list of distinct problems): 8 bytes
   // across PCIe instead of 12.  The row kernel reads rec_rep then, so its two arrays alias rec_d (which it no longer reads; the
   // select kernels, which do, are done), and dist_list -- rep_dv's d_llh column, dense -- aliases rec_v (not written in a

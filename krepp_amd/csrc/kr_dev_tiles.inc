@@ -15,7 +15,8 @@
 //     test and writes the sequence's records (histogram planes: the counts of a contig do not fit the packed word) in
 //     ascending key order at the sequence's first tile; the tiles' own records become holes;
 //   * kr_tile_gather_kernel lists the per-read results of the REAL reads (first tile of a long sequence, or the read itself)
-//     for the views, the copies back and `place`.
+//     for the views, the copies back and `place` -- and, for a tiled batch that leaves the device as compact rows (KR_TILE_ROWS),
+//     their row ranges, which the text kernels and the copy back index by the caller's reads.
 // The likelihood and selection kernels run over the tiled batch unchanged: tiles without records are reads without records.
 //
 // Who lays the tiled batch out: build_tiles (kr_host_stream.inc) for a host batch, while it copies the batch into page-locked
@@ -49,6 +50,8 @@ struct TileBatch {
   uint32_t* real_onmers;
   uint32_t* real_filt;
   uint8_t* real_na;
+  uint32_t* real_roff;      // rows-mode batches (KR_TILE_ROWS), else null: the real read's first row and its rows
+  uint32_t* real_rcnt;
 };
 
 __global__ __launch_bounds__(256) void kr_tile_filt_kernel(BatchOut out, TileBatch tb)
@@ -243,7 +246,8 @@ __global__ __launch_bounds__(kWave) void kr_tile_add_kernel(DevIndex ix, DevPara
   if (n_hole && lane == 0) atomicAdd(&out.counters[kCtTileHoles], n_hole);
 }
 
-// per-read results of the real reads (after the selection kernel)
+// per-read results of the real reads (after the selection kernel; in a rows-mode batch after the row kernels, whose rd_roff it
+// reads, and before the text kernels, which read what it writes)
 __global__ __launch_bounds__(256) void kr_tile_gather_kernel(BatchOut out, TileBatch tb)
 {
   for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < tb.nreal; r += gridDim.x * blockDim.x) {
@@ -253,6 +257,7 @@ __global__ __launch_bounds__(256) void kr_tile_gather_kernel(BatchOut out, TileB
     tb.real_onmers[r] = out.rd_onmers[v];
     tb.real_filt[2 * r] = out.rd_filt[2 * v], tb.real_filt[2 * r + 1] = out.rd_filt[2 * v + 1];
     tb.real_na[r] = out.rd_na[v];
+    if (tb.real_roff) tb.real_roff[r] = out.rd_roff[v], tb.real_rcnt[r] = out.rd_rcnt[v]; // (uniform over the grid)
   }
 }
 

@@ -1,6 +1,7 @@
 // kr_host_fastq.inc -- part of kr_device.hip (host side): kr_stream_fastq_enable, kr_batch_submit_fastq, kr_batch_fastq_names.
 // A batch given as the raw bytes of a plain FASTQ file; the records are found by the kernels of kr_dev_fastq.inc, then the batch
-// runs on the submit_batch path with its bases already in HBM (with KR_TILE_DEVICE: long records too, tiled by build_tiles_device).
+// runs on the submit_batch path with its bases already in HBM (with KR_TILE_DEVICE: long records too, tiled by build_tiles_device;
+// with KR_TILE_ROWS as well, such a batch's rows and text are the device's: submit_batch reads the flag, the ids are in HBM already).
 
 extern "C" {
 

@@ -142,6 +142,7 @@ struct kr_stream {
     DevBuf<uint32_t> d_rfirst, d_longs;
     DevBuf<uint32_t> d_tile_filt, d_real_off, d_real_cnt, d_real_onmers, d_real_filt;
     DevBuf<uint8_t> d_real_na;
+    DevBuf<uint32_t> d_real_roff, d_real_rcnt; // a tiled rows-mode batch (KR_TILE_ROWS): the real reads' row ranges
     // the layout on the device: per-read scratch ([max_reads]), the block sums and the summary {nv, nlong, bases}
     DevBuf<uint8_t> d_choice;
     DevBuf<uint32_t> d_lread;
@@ -200,7 +201,7 @@ struct kr_stream {
   const uint64_t* sub_offsets = nullptr;
   // state
   bool h_rec_full = false; // the pinned record buffers hold v / chisq / hist only once a batch asked for them
-  bool rows_mode = false;  // the batch in flight leaves the device as compact rows (KR_ROWS_ONLY, no taps, not tiled)
+  bool rows_mode = false;  // the batch in flight leaves the device as compact rows (KR_ROWS_ONLY, no taps; tiled: with KR_TILE_ROWS)
   bool rows_indexed = false; // ... of 8 bytes: (key, index into the batch's distinct DIST values) -- KR_ROWS_INDEXED
   PinBuf<uint32_t> h_rec_dix; // of h_rec_key's size, allocated with the first indexed batch
   PinBuf<double> h_dist_list;
@@ -297,7 +298,7 @@ int build_tiles(kr_stream* s, const uint8_t* bases, const uint64_t* offsets, uin
     // stream stays usable) and the next tiled batch asks again
     const uint64_t c = s->max_reads;
     if (!reserve_all(c + 1, t.h_voff, t.d_voff) ||
-        !reserve_all(c, t.h_vtile, t.h_rfirst, t.d_vtile, t.d_rfirst, t.d_real_off, t.d_real_cnt, t.d_real_onmers, t.d_real_na) ||
+        !reserve_all(c, t.h_vtile, t.h_rfirst, t.d_vtile, t.d_rfirst, t.d_real_off, t.d_real_cnt, t.d_real_onmers, t.d_real_na, t.d_real_roff, t.d_real_rcnt) ||
         !reserve_all(2 * c, t.h_longs, t.d_longs, t.d_tile_filt, t.d_real_filt))
       return alloc_failed("build_tiles");
   }
@@ -345,7 +346,7 @@ int build_tiles_device(kr_stream* s, const uint8_t* bases, const uint64_t* offse
   const uint32_t nblk = (uint32_t)(((uint64_t)nreads + kTileBlock - 1) / kTileBlock);
   const uint64_t blk_cap = c / kTileBlock + 2;
   if (!reserve_all(c + 1, t.d_voff) ||
-      !reserve_all(c, t.d_vtile, t.d_rfirst, t.d_real_off, t.d_real_cnt, t.d_real_onmers, t.d_real_na, t.d_choice, t.d_lread, t.d_vsrc) ||
+      !reserve_all(c, t.d_vtile, t.d_rfirst, t.d_real_off, t.d_real_cnt, t.d_real_onmers, t.d_real_na, t.d_real_roff, t.d_real_rcnt, t.d_choice, t.d_lread, t.d_vsrc) ||
       !reserve_all(2 * c, t.d_longs, t.d_tile_filt, t.d_real_filt) || !reserve_all(4 * blk_cap, t.d_bsum) || !reserve_all(4, t.d_sum, t.h_sum))
     return alloc_failed("build_tiles_device");
   hipStream_t st = s->lanes[0].stream;
@@ -422,7 +423,8 @@ TileBatch tile_batch(const kr_stream* s)
 {
   const kr_stream::Tiles& tl = s->tiles;
   return TileBatch{tl.d_vtile.get(), tl.d_longs.get(), tl.d_rfirst.get(), tl.d_tile_filt.get(), tl.nv, tl.nlong, s->nreads,
-                   tl.d_real_off.get(), tl.d_real_cnt.get(), tl.d_real_onmers.get(), tl.d_real_filt.get(), tl.d_real_na.get()};
+                   tl.d_real_off.get(), tl.d_real_cnt.get(), tl.d_real_onmers.get(), tl.d_real_filt.get(), tl.d_real_na.get(),
+                   s->rows_mode ? tl.d_real_roff.get() : nullptr, s->rows_mode ? tl.d_real_rcnt.get() : nullptr};
 }
 
 // The stages of a lane's batch, each queued on the lane's stream (everything a stage needs is in L.in / L.out); launch_lane calls
@@ -527,8 +529,10 @@ void launch_select(kr_stream* s, Lane& L)
   }, s->llh.th == 4, filt);
 }
 
-// The output rows of a rows-mode batch, compact: (key, DIST) of the selected records, a read's rows contiguous
-int launch_rows_text(kr_stream* s, Lane& L)
+// The output rows of a rows-mode batch, compact: (key, DIST) of the selected records, a read's rows contiguous.  Over the reads of
+// the batch as the device has it: a tiled batch's rows come out in tiled-batch order, which is the caller's read order (a long
+// sequence's rows lie at its first tile, its other tiles have none)
+void launch_rows(kr_stream* s, Lane& L)
 {
   hipStream_t st = L.stream;
   BatchOut& o = L.out;
@@ -538,25 +542,42 @@ int launch_rows_text(kr_stream* s, Lane& L)
   with_bools([&](auto INDEXED) { hipLaunchKernelGGL(kr_rows_write_kernel<INDEXED.value>, dim3(std::min<uint32_t>(nblk, 8192u)), dim3(256), 0, st, o, nreads); },
              o.rows_indexed != 0);
   if (o.rows_indexed) hipLaunchKernelGGL(kr_rows_dlist_kernel, dim3(2048), dim3(256), 0, st, o);
-  if (s->text.req) { // ... and as text (kr_dev_text.inc): lengths, block offsets, bytes
-    kr_stream::Text& tx = s->text;
-    TextIO t{tx.d_ids, tx.d_id_off, tx.id_sep, s->ix->d_names.get(), s->ix->d_name_off.get(), tx.d_tlen, tx.d_bsum, tx.d_text, tx.text_cap, tx.d_total};
-    HIP_TRY(hipMemsetAsync(tx.d_total, 0, 16, st));
-    hipLaunchKernelGGL(kr_text_len_kernel, dim3(std::min<uint32_t>(nblk, 8192u)), dim3(256), 0, st, o, t, nreads);
-    hipLaunchKernelGGL(kr_text_bscan_kernel, dim3(1), dim3(1024), 0, st, t.t_bsum, nblk, t.text_cap, t.total);
-    hipLaunchKernelGGL(kr_text_write_kernel, dim3(std::min<uint32_t>(nblk, 8192u)), dim3(256), 0, st, o, t, nreads);
-    HIP_TRY(hipMemcpyAsync(tx.h_total, tx.d_total, 16, hipMemcpyDeviceToHost, st));
-    tx.made = true;
+}
+
+// ... and as text (kr_dev_text.inc): lengths, block offsets, bytes.  Over the CALLER's reads -- ids are theirs --, so a tiled batch
+// hands the kernels the real reads' row ranges (kr_tile_gather_kernel has run) and the caller's read count: the blocks here are
+// blocks of the caller's reads, those of launch_rows blocks of the tiled batch's
+int launch_text(kr_stream* s, Lane& L)
+{
+  hipStream_t st = L.stream;
+  BatchOut o = L.out;
+  uint32_t nreads = L.nreads;
+  if (s->tiles.active) {
+    const kr_stream::Tiles& tl = s->tiles;
+    o.rd_roff = tl.d_real_roff.get(), o.rd_rcnt = tl.d_real_rcnt.get(), o.rd_na = tl.d_real_na.get();
+    nreads = s->nreads;
   }
+  const uint32_t nblk = (nreads + kRowBlock - 1) / kRowBlock;
+  kr_stream::Text& tx = s->text;
+  TextIO t{tx.d_ids, tx.d_id_off, tx.id_sep, s->ix->d_names.get(), s->ix->d_name_off.get(), tx.d_tlen, tx.d_bsum, tx.d_text, tx.text_cap, tx.d_total};
+  HIP_TRY(hipMemsetAsync(tx.d_total, 0, 16, st));
+  hipLaunchKernelGGL(kr_text_len_kernel, dim3(std::min<uint32_t>(nblk, 8192u)), dim3(256), 0, st, o, t, nreads);
+  hipLaunchKernelGGL(kr_text_bscan_kernel, dim3(1), dim3(1024), 0, st, t.t_bsum, nblk, t.text_cap, t.total);
+  hipLaunchKernelGGL(kr_text_write_kernel, dim3(std::min<uint32_t>(nblk, 8192u)), dim3(256), 0, st, o, t, nreads);
+  HIP_TRY(hipMemcpyAsync(tx.h_total, tx.d_total, 16, hipMemcpyDeviceToHost, st));
+  tx.made = true;
   return KR_OK;
 }
 
-void launch_gather_rebase(kr_stream* s, Lane& L)
+void launch_gather(kr_stream* s, Lane& L)
+{ // (tiled batches) per-read results of the real reads, for the views, the copies back, the text kernels and `place`
+  hipLaunchKernelGGL(kr_tile_gather_kernel, dim3(std::min<uint32_t>((s->nreads + 255) / 256, 4096u)), dim3(256), 0, L.stream, L.out, tile_batch(s));
+}
+
+void launch_rebase(kr_stream* s, Lane& L)
 {
   hipStream_t st = L.stream;
   BatchOut& o = L.out;
-  if (s->tiles.active) // per-read results of the real reads, for the views, the copies back and `place`
-    hipLaunchKernelGGL(kr_tile_gather_kernel, dim3(std::min<uint32_t>((s->nreads + 255) / 256, 4096u)), dim3(256), 0, st, o, tile_batch(s));
   if (L.rec_base) // the result view indexes the stream's arrays, the lane's kernels its slice
     hipLaunchKernelGGL(kr_rebase_kernel, dim3(std::min<uint32_t>((L.nreads + 255) / 256, 1024u)), dim3(256), 0, st, o.rd_off, o.rd_cnt, L.nreads, L.rec_base);
 }
@@ -590,9 +611,12 @@ int launch_lane(kr_stream* s, Lane& L, uint32_t flags)
   HIP_TRY(hipEventRecord(L.ev[kEvLlhStart], st));
   launch_likelihood(s, L);
   launch_select(s, L);
-  if (o.rows_mode)
-    if (int rc = launch_rows_text(s, L)) return rc;
-  launch_gather_rebase(s, L);
+  // (an untiled batch: rows, text, rebase as ever; a tiled one gathers the real reads' results between its rows and its text)
+  if (o.rows_mode) launch_rows(s, L);
+  if (s->tiles.active) launch_gather(s, L);
+  if (o.rows_mode && s->text.req)
+    if (int rc = launch_text(s, L)) return rc;
+  launch_rebase(s, L);
   HIP_TRY(hipEventRecord(L.ev[kEvLastKernel], st));
   if (!ixp->chain_off) {
     hipEvent_t& ce = ixp->chain_ev[ixp->chain_n % kr_index::kChainEvents];
@@ -922,7 +946,7 @@ int kr_batch_collect_text(kr_stream* s, const char** text, uint64_t* len)
   const int rc = kr_batch_wait(s);
   if (rc) return rc;
   kr_stream::Text& t = s->text;
-  if (!t.made) return kr::fail(KR_ERR_UNSUPPORTED, "kr_batch_collect_text: the batch left the device as record slots (long sequences): kr_batch_collect + kr_format_dist");
+  if (!t.made) return kr::fail(KR_ERR_UNSUPPORTED, "kr_batch_collect_text: the batch left the device as record slots (long sequences; submit with KR_TILE_ROWS for device text): kr_batch_collect + kr_format_dist");
   if (t.h_total[1] & kTextOverCap) return kr::fail(KR_ERR_CAPACITY, "the batch's report text exceeds max_text_bytes: submit fewer reads per batch");
   if (t.h_total[1] & kTextBadNum) return kr::fail(KR_ERR_UNSUPPORTED, "kr_batch_collect_text: a DIST outside [0, 1000): kr_batch_collect + kr_format_dist");
   HIP_TRY(hipSetDevice(s->ix->device));
@@ -987,10 +1011,11 @@ static int submit_batch(kr_stream* s, const uint8_t* bases, const uint64_t* offs
   if (s->text.req) P = 1; // (one text buffer, one prefix over the reads)
   s->text.made = false;
   s->nlanes = P;
-  s->rows_mode = (flags & KR_ROWS_ONLY) && !(flags & (KR_TAP_ACCS | KR_TAP_HITS)) && !s->tiles.active && !getenv("KR_NO_ROW_COMPACTION");
+  // (a tiled batch keeps its record slots unless the caller asks for rows with KR_TILE_ROWS)
+  s->rows_mode = (flags & KR_ROWS_ONLY) && !(flags & (KR_TAP_ACCS | KR_TAP_HITS)) && (!s->tiles.active || (flags & KR_TILE_ROWS)) && !getenv("KR_NO_ROW_COMPACTION");
   // KR_ROWS_INDEXED: 8-byte rows (key, position of DIST in the batch's distinct values).  One lane (a lane's positions are its own),
-  // no --filter (its select kernel writes rec_v, which the list of values aliases), no device text (its kernels read row_d)
-  s->rows_indexed = s->rows_mode && (flags & KR_ROWS_INDEXED) && P == 1 && !(!s->dp.no_filter && s->dp.multi) && !s->text.req;
+  // not tiled, no --filter (its select kernel writes rec_v, which the list of values aliases), no device text (its kernels read row_d)
+  s->rows_indexed = s->rows_mode && (flags & KR_ROWS_INDEXED) && P == 1 && !s->tiles.active && !(!s->dp.no_filter && s->dp.multi) && !s->text.req;
   if (flags & KR_TAP_HITS) {
     if (!reserve_all(s->hit_cap, s->d_hits, s->h_hits)) return alloc_failed("kr_batch_submit: hit tap buffers");
     s->out.hits = s->d_hits.get();
@@ -1038,7 +1063,7 @@ static int submit_batch(kr_stream* s, const uint8_t* bases, const uint64_t* offs
       L.in.bases = s->d_bases;
       L.in.offsets = s->d_offsets + r0 + l;
     }
-    if (s->text.req && !s->tiles.active && !s->text.ids_on_device) { // the reads' ids (staged in page-locked memory by kr_batch_submit_text)
+    if (s->text.req && (!s->tiles.active || s->rows_mode) && !s->text.ids_on_device) { // the reads' ids (staged in page-locked memory by kr_batch_submit_text)
       HIP_TRY(hipMemcpyAsync(s->text.d_ids, s->text.h_ids, s->text.id_bytes, hipMemcpyHostToDevice, st));
       HIP_TRY(hipMemcpyAsync(s->text.d_id_off, s->text.h_id_off, ((uint64_t)nreads + 1) * 4, hipMemcpyHostToDevice, st));
     }
@@ -1350,10 +1375,10 @@ int kr_batch_collect(kr_stream* s, kr_result_view* v)
     const uint64_t nr = tl ? s->nreads : L.nreads, nc = lane_count(L), r0 = L.read0;
     const BatchOut& o = L.out;
     const kr_stream::Tiles& t = s->tiles;
-    if (rows_mode) { // 12 bytes per output row and the reads' row ranges: nothing else crosses PCIe
-      HIP_TRY(hipMemcpyAsync(s->h_rd_off + r0, o.rd_roff, nr * 4, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(s->h_rd_cnt + r0, o.rd_rcnt, nr * 4, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(s->h_rd_na + r0, o.rd_na, nr, hipMemcpyDeviceToHost, st));
+    if (rows_mode) { // 12 bytes per output row and the reads' row ranges (a tiled batch: the real reads'): nothing else crosses PCIe
+      HIP_TRY(hipMemcpyAsync(s->h_rd_off + r0, tl ? t.d_real_roff.get() : o.rd_roff, nr * 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(s->h_rd_cnt + r0, tl ? t.d_real_rcnt.get() : o.rd_rcnt, nr * 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(s->h_rd_na + r0, tl ? t.d_real_na.get() : o.rd_na, nr, hipMemcpyDeviceToHost, st));
       s->d2h_bytes += nr * 9;
       if (nc && s->rows_indexed) { // (one lane, waited for: the counters are known)
         const uint64_t nd = std::min<uint64_t>(L.h_counters[kCtProblems], L.rec_cap);
@@ -1375,24 +1400,31 @@ int kr_batch_collect(kr_stream* s, kr_result_view* v)
     HIP_TRY(hipMemcpyAsync(s->h_rd_off + r0, tl ? t.d_real_off.get() : o.rd_off, nr * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(s->h_rd_cnt + r0, tl ? t.d_real_cnt.get() : o.rd_cnt, nr * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(s->h_rd_na + r0, tl ? t.d_real_na.get() : o.rd_na, nr, hipMemcpyDeviceToHost, st));
+    s->d2h_bytes += nr * 9;
     if (full) {
       HIP_TRY(hipMemcpyAsync(s->h_rd_onmers + r0, tl ? t.d_real_onmers.get() : o.rd_onmers, nr * 4, hipMemcpyDeviceToHost, st));
       HIP_TRY(hipMemcpyAsync(s->h_rd_filt + 2 * r0, tl ? t.d_real_filt.get() : o.rd_filt, nr * 8, hipMemcpyDeviceToHost, st));
+      s->d2h_bytes += nr * 12;
     }
     if (nc) {
       s->h_sel_ones = 0; // (real flags from here on)
+      s->d2h_bytes += nc * 13; // key, flag, DIST of every record slot
       HIP_TRY(hipMemcpyAsync(s->h_rec_key.get() + hoff, o.rec_key, nc * 4, hipMemcpyDeviceToHost, st));
       HIP_TRY(hipMemcpyAsync(s->h_rec_sel.get() + hoff, o.rec_sel, nc, hipMemcpyDeviceToHost, st));
       HIP_TRY(hipMemcpyAsync(s->h_rec_d.get() + hoff, o.rec_d, nc * 8, hipMemcpyDeviceToHost, st));
       if (full) {
         HIP_TRY(hipMemcpyAsync(s->h_rec_v.get() + hoff, o.rec_v, nc * 8, hipMemcpyDeviceToHost, st));
-        if (!s->dp.no_filter && s->dp.multi)
+        s->d2h_bytes += nc * 8;
+        if (!s->dp.no_filter && s->dp.multi) {
           HIP_TRY(hipMemcpyAsync(s->h_rec_chisq.get() + hoff, o.rec_chisq, nc * 8, hipMemcpyDeviceToHost, st));
-        else
+          s->d2h_bytes += nc * 8;
+        } else
           std::fill(s->h_rec_chisq.get() + hoff, s->h_rec_chisq.get() + hoff + nc, std::numeric_limits<double>::quiet_NaN());
         if (s->flags & KR_TAP_ACCS)
-          for (uint32_t x = 0; x < s->dp.np; ++x)
+          for (uint32_t x = 0; x < s->dp.np; ++x) {
             HIP_TRY(hipMemcpyAsync(s->h_rec_hist.get() + (uint64_t)x * hist_stride_host + hoff, o.rec_hist + (uint64_t)x * s->rec_cap, nc * 4, hipMemcpyDeviceToHost, st));
+            s->d2h_bytes += nc * 4;
+          }
       }
     }
     copies_started = true;
@@ -1597,7 +1629,8 @@ int kr_debug_tile_shape(uint64_t len, uint32_t k, uint64_t* nkm, uint64_t* nt, u
   return KR_OK;
 }
 
-// Bytes the last kr_batch_collect of a rows-only batch copied back to the host (bench.py's host-inclusive leg reports them).
+// Bytes the last kr_batch_collect copied back to the host: rows or record slots and the per-read arrays (bench.py's host-inclusive
+// leg reports them).
 int kr_debug_last_d2h_bytes(kr_stream* s, uint64_t* bytes)
 {
   kr::clear_error();

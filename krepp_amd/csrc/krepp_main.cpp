@@ -292,6 +292,7 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
   // KR_CLI_TIMING=1: seconds spent parsing, on the device (submit + collect), formatting and writing
   const bool timing = getenv("KR_CLI_TIMING") != nullptr;
   std::atomic<uint64_t> ns_parse{0}, ns_job{0}, ns_dev{0}, ns_fmt{0}, ns_write{0};
+  std::atomic<uint64_t> nb_dev_text{0}, nb_host_text{0}; // `dist` batches (pieces of them) written from device text / through kr_format_dist
   auto now = [] { return std::chrono::steady_clock::now(); };
   auto since = [](std::chrono::steady_clock::time_point t) {
     return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t).count();
@@ -491,11 +492,12 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
           std::vector<uint32_t> id_off(hi - lo + 1);
           for (size_t i = lo; i < hi; ++i) id_off[i - lo] = (uint32_t)(nm[i] - j->blob);
           id_off[hi - lo] = hi < j->n ? (uint32_t)(nm[hi] - j->blob) : (uint32_t)j->blob_bytes;
-          rc = kr_batch_submit_text(st, j->bases + j->offsets[lo], offs.data(), (uint32_t)(hi - lo), KR_BASES_HOST, j->blob,
+          // (KR_TILE_ROWS: a batch with long sequences, which runs as tiles, has its text written by the device like any other)
+          rc = kr_batch_submit_text(st, j->bases + j->offsets[lo], offs.data(), (uint32_t)(hi - lo), KR_BASES_HOST | KR_TILE_ROWS, j->blob,
                                     id_off.data(), 1);
           if (!rc) rc = kr_batch_collect_text(st, &dtext, &dlen);
           on_device = rc == 0;
-          if (rc == KR_ERR_UNSUPPORTED) rc = kr_batch_collect(st, &rv); // (a tiled batch: its rows as record slots, formatted below)
+          if (rc == KR_ERR_UNSUPPORTED) rc = kr_batch_collect(st, &rv); // (a DIST the device does not format: the batch's rows, formatted below)
         } else {
           rc = kr_batch_submit(st, j->bases + j->offsets[lo], offs.data(), (uint32_t)(hi - lo),
                                KR_BASES_HOST | (place ? KR_TAP_ACCS : (seek ? 0u : KR_ROWS_ONLY)));
@@ -512,11 +514,15 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
         }
         if (!rc && seek) rc = kr_format_seek(hx, dix[g], &rv, p.hdist_th, nm + lo, &txt, &len);
         if (!rc && on_device) {
+          ++nb_dev_text;
           emit(dtext, dlen, lo == 0 && hi == job_n);
           if (piece != SIZE_MAX && ++streak >= 16) piece = piece > SIZE_MAX / 2 ? SIZE_MAX : piece * 2, streak = 0; // (as below: grow back after a run of successes)
           return 0;
         }
-        if (!rc && !place && !seek && !summarize) rc = kr_format_dist(hx, &rv, nm + lo, &txt, &len);
+        if (!rc && !place && !seek && !summarize) {
+          rc = kr_format_dist(hx, &rv, nm + lo, &txt, &len);
+          if (!rc) ++nb_host_text;
+        }
         if (!rc && summarize && !place) { // each read shares one unit among the references it keeps (src/query.cpp:168-170)
           for (uint32_t r = 0; r < rv.nreads; ++r) {
             uint32_t o = rv.read_off[r], n = rv.read_cnt[r], ns = 0;
@@ -579,8 +585,8 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
         while (pos < j->raw_len) {
           kr_fastq_parse fp;
           auto t_dev = now();
-          // (KR_TILE_DEVICE: a long record stays with the device, tiled there; its batch comes back through kr_batch_collect below)
-          int rc = kr_batch_submit_fastq(st, j->raw + pos, j->raw_len - pos, (text_on ? 0u : KR_ROWS_ONLY) | KR_TILE_DEVICE, j->at_eof ? 1u : 0u, &fp);
+          // (KR_TILE_DEVICE: a long record stays with the device, tiled there; KR_TILE_ROWS: and its batch's text is the device's too)
+          int rc = kr_batch_submit_fastq(st, j->raw + pos, j->raw_len - pos, (text_on ? KR_TILE_ROWS : KR_ROWS_ONLY) | KR_TILE_DEVICE, j->at_eof ? 1u : 0u, &fp);
           if (rc) return rc;
           if (fp.nreads) {
             const char* dtext = nullptr;
@@ -602,6 +608,7 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
             if (rc) return rc;
             auto t_fmt = now();
             if (on_device) {
+              ++nb_dev_text;
               emit(dtext, dlen, false);
             } else if (summarize) { // each read shares one unit among the references it keeps (src/query.cpp:168-170)
               for (uint32_t r = 0; r < rv.nreads; ++r) {
@@ -621,6 +628,7 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
               rc = names_of(j->raw + pos, fp.nreads);
               if (!rc) rc = kr_format_dist(hx, &rv, nptr.data(), &txt, &len);
               if (rc) return rc;
+              ++nb_host_text;
               emit(txt, len, false);
               kr_free(txt);
             }
@@ -903,6 +911,9 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
   if (timing)
     fprintf(stderr, "[timing] parse %.3f s, job hand-over (incl. waiting for queue space) %.3f s, device %.3f s, format %.3f s, write %.3f s; of the elapsed time, until the last worker had its stream and page-locked buffers: %.3f s (the reader parses meanwhile)\n",
             ns_parse / 1e9, ns_job / 1e9, ns_dev / 1e9, ns_fmt / 1e9, ns_write / 1e9, std::chrono::duration<double>(t_loop - t_init).count());
+  if (timing && !place && !seek && !summarize) // (a batch split at capacity counts once per piece)
+    fprintf(stderr, "[timing] report text: %llu batches written from device text, %llu through the host formatter\n", (unsigned long long)nb_dev_text.load(),
+            (unsigned long long)nb_host_text.load());
   fprintf(stderr, "Total number of sequences queried: %llu\n", (unsigned long long)nreads_total);
   // Everything is written.  Unmapping 19 GB of index, 10 GB of host tables and the page-locked buffers one by one takes 0.8-1.2 s
   // that nobody is waiting for: the process ends here and the kernel reclaims the lot (KR_CLI_CLEAN_EXIT=1: free everything in
