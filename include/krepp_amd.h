@@ -207,6 +207,14 @@ KR_API void kr_stream_destroy(kr_stream*);
                            /* host view is NULL then (a formatter may format each distinct value once). */
                            /* A hint: honoured for batches that run as one lane and are not tiled --     */
                            /* otherwise the view holds rec_d as without it (rec_dix == NULL says which). */
+                           /* rec_dix != NULL exactly when it was honoured, and every rec_dix[i] of a row */
+                           /* is then below ndist: a batch whose list positions outgrow the list (nearly  */
+                           /* every record distinct, max_records set tightly) is run again by             */
+                           /* kr_batch_wait / kr_batch_collect without the hint and comes back with      */
+                           /* rec_d -- never an error the plain batch would not have raised.  A batch     */
+                           /* without rows has ndist == 0.  A DEVICE view of an honoured batch holds      */
+                           /* rec_dix per record slot (meaningful where rec_sel == 1), dist_list and      */
+                           /* ndist as device data, rec_d == NULL.                                        */
 #define KR_TILE_DEVICE 64u /* with KR_BASES_DEVICE (and for kr_batch_submit_fastq): long sequences of a batch that   */
                            /* is already in HBM are tiled too -- the tiled batch is laid out by kernels from the       */
                            /* caller's device bases / offsets (see "Long sequences" below).  The submit then WAITS    */
@@ -276,9 +284,11 @@ typedef struct kr_result_view {
                               /* rec_hist[x * rec_hist_stride + i], x = 0..hdist_th       */
   uint64_t rec_hist_stride;
   uint64_t nrows;             /* number of rec_sel == 1                                  */
-  const uint32_t* rec_dix;    /* KR_ROWS_INDEXED (host view): [nrecs] index into dist_list, rec_d == NULL; else NULL */
-  const double* dist_list;    /* [ndist] distinct d_llh values of the batch (unused positions hold anything)         */
-  uint64_t ndist;
+  const uint32_t* rec_dix;    /* KR_ROWS_INDEXED, honoured: [nrecs] index into dist_list (< ndist), rec_d == NULL; else NULL. */
+                              /* Host view: per row.  Device view: per record slot, valid where rec_sel == 1                 */
+  const double* dist_list;    /* [ndist] distinct d_llh values of the batch (unused positions hold anything); a device       */
+                              /* pointer in a device view                                                                    */
+  uint64_t ndist;             /* 0 for a batch without rows                                                                  */
 } kr_result_view;
 
 /* Waits for the batch and copies results to pinned host memory owned by the stream (lane by lane: a lane's
@@ -291,6 +301,9 @@ KR_API int kr_batch_collect(kr_stream*, kr_result_view* out);
 KR_API int kr_batch_collect_device(kr_stream*, kr_result_view* out);
 /* Bytes the last kr_batch_collect copied back over PCIe: rows or record slots, and the per-read arrays (measurement aid). */
 KR_API int kr_debug_last_d2h_bytes(kr_stream*, uint64_t* bytes);
+/* Tests: KR_ROWS_INDEXED -- `extent`: list positions the stream's last indexed launch handed out (holes included; of the first attempt
+ * if the batch was then run again without the hint); `fallbacks`: batches of this stream run again so, so far.  Either may be NULL. */
+KR_API int kr_debug_indexed_list(kr_stream*, uint64_t* extent, uint64_t* fallbacks);
 /* Tests: one number as `krepp place` rows print it (std::fixed, 5 decimals; `out` holds 80 bytes); returns its length. */
 KR_API int kr_debug_place_fixed5(double v, char* out);
 

@@ -103,7 +103,7 @@ EXPORTS = [
     "kr_debug_front_end", "kr_debug_stream_move", "kr_debug_stream_addrs", "kr_debug_item_placement", "kr_debug_brent", "kr_debug_prefix", "kr_debug_colour_classes", "kr_llh_batch", "kr_llh_eval_indexed", "kr_batch_timing",
     "kr_place_tree_create", "kr_place_tree_create_lineage", "kr_place_tree_nnodes", "kr_place_summary_add",
     "kr_place_summary_text", "kr_place_tree_free", "kr_place_tree_kinds", "kr_place_batch", "kr_place_stream", "kr_place_frame", "kr_place_counters",
-    "kr_debug_last_d2h_bytes", "kr_debug_place_fixed5", "kr_place_text_counters", "kr_place_path_counters", "kr_fastx_open", "kr_fastx_open_at", "kr_fastx_next", "kr_fastx_detach", "kr_fastx_release", "kr_fastx_close", "kr_fastx_parallel_chunks", "kr_fastx_pgz_stats", "kr_format_dist", "kr_debug_fixed5", "kr_free", "kr_host_alloc", "kr_host_free",
+    "kr_debug_last_d2h_bytes", "kr_debug_indexed_list", "kr_debug_place_fixed5", "kr_place_text_counters", "kr_place_path_counters", "kr_fastx_open", "kr_fastx_open_at", "kr_fastx_next", "kr_fastx_detach", "kr_fastx_release", "kr_fastx_close", "kr_fastx_parallel_chunks", "kr_fastx_pgz_stats", "kr_format_dist", "kr_debug_fixed5", "kr_free", "kr_host_alloc", "kr_host_free",
     "kr_build_index", "kr_minimizers_cpu", "kr_minimizers_device", "kr_minimizers_free", "kr_last_error", "kr_version",
 ]
 
@@ -481,6 +481,13 @@ class Stream:
         self.lib.kr_debug_last_d2h_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         check(self.lib.kr_debug_last_d2h_bytes(self.h, C.byref(b)))
         return int(b.value)
+
+    def indexed_list(self):
+        """(tests) kr_debug_indexed_list: (list positions the last KR_ROWS_INDEXED launch handed out, batches run again without the hint)"""
+        e, f = C.c_uint64(0), C.c_uint64(0)
+        self.lib.kr_debug_indexed_list.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        check(self.lib.kr_debug_indexed_list(self.h, C.byref(e), C.byref(f)))
+        return int(e.value), int(f.value)
 
     def collect_device(self):
         rv = KrResultView()

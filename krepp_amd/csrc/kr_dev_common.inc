@@ -164,8 +164,8 @@ struct BatchOut {
   uint32_t* rec_rep;     // [rec_cap] position of the record's representative in rep_list (0xFFFFFFFF: hole)
   uint32_t* rep_list;    // [rec_cap] record index of every distinct problem
   double2* rep_dv;       // [rec_cap] (d_llh, v_llh) per distinct problem
-  uint32_t rep_cap;      // positions rep_list / rep_dv hold for this launch (rec_cap + kRepSlack): a batch that hands out more -- its waves
-                         // leave the tails of their chunks unused -- raises kErrRecCap instead of writing past the lane's slice
+  uint32_t rep_cap;      // positions rep_list / rep_dv hold for this launch (rec_cap + kRepSlack; less in tests: KR_DEBUG_LIST_CAPS): a batch that
+                         // hands out more -- its waves leave the tails of their chunks unused -- raises kErrRecCap instead of writing past the lane's slice
   ulonglong2* dd_table;  // [dd_slots] open-addressing table: x = histogram word (0 = empty), y = leaf | (list position + 1) << 32
   // Direct-mapped part (round 5): a record whose histogram counts at most kDdMaxEvents events -- 80 % of all records -- needs no
   // table probe: its problem is (onmers slot, class of the histogram, leaf) and dd_direct[(slot * kDdClasses + class) * dd_nodes + se]
@@ -207,7 +207,9 @@ struct BatchOut {
   // rows-only batch)
   uint32_t rows_indexed;
   uint32_t* row_dix;     // [rec_cap]
-  double* dist_list;     // [counters[kCtProblems]]
+  double* dist_list;     // [min(counters[kCtProblems], dist_cap)]
+  uint32_t dist_cap;     // entries dist_list holds (rec_cap: it aliases rec_v; less in tests: KR_DEBUG_LIST_CAPS).  List positions are handed out
+                         // up to rep_cap, which is more: a batch whose positions reach beyond dist_cap is run again with rec_d (kr_batch_wait)
   uint32_t item_cap;
   uint32_t* rd_it_off;
   uint32_t* rd_it_cnt;

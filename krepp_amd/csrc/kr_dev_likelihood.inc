@@ -399,6 +399,9 @@ __global__ __launch_bounds__(256) void kr_dedup_kernel(BatchOut out)
       base = __shfl(base, 0);
       if ((uint64_t)base + size > out.rep_cap) { // (round-5 advice: the slack covers one unused chunk per wave, not every discarded tail)
         if (lane_id() == 0) atomicOr(&out.counters[kCtErr], kErrRecCap); // the batch is reported as over capacity; nothing is written past the slice
+        // (what the request takes of the slice is nobody's now: holes, or the likelihood kernels -- which still run -- would take whatever
+        //  an earlier batch, or the allocator, left there for record indices)
+        for (uint64_t q = (uint64_t)base + lane_id(); q < out.rep_cap; q += 64) out.rep_list[q] = 0xFFFFFFFFu;
         base = 0;
       }
       lp_next = base, lp_end = base + size;
@@ -546,7 +549,11 @@ __global__ __launch_bounds__(256) void kr_dedup_direct_kernel(BatchOut out)
     if (threadIdx.x == 0) {
       const uint32_t tot = s_w[0] + s_w[1] + s_w[2] + s_w[3];
       s_base = tot ? atomicAdd(&out.counters[kCtProblems], tot) : 0u;
-      if ((uint64_t)s_base + tot > out.rep_cap) atomicOr(&out.counters[kCtErr], kErrRecCap), s_base = 0; // (see take_positions)
+      if ((uint64_t)s_base + tot > out.rep_cap) { // (see take_positions; at most 4,095 holes, once per batch that fails)
+        atomicOr(&out.counters[kCtErr], kErrRecCap);
+        for (uint64_t q = s_base; q < out.rep_cap; ++q) out.rep_list[q] = 0xFFFFFFFFu;
+        s_base = 0;
+      }
     }
     __syncthreads();
     uint32_t at = s_base + inc - cnt;
@@ -1286,7 +1293,7 @@ __global__ __launch_bounds__(1024) void kr_rows_bscan_kernel(BatchOut out, uint3
 // (kr_rows_dlist_kernel makes that list dense: dist_list[pos] = rep_dv[pos].x)
 __global__ __launch_bounds__(256) void kr_rows_dlist_kernel(BatchOut out)
 {
-  const uint32_t n = min(out.counters[kCtProblems], out.rec_cap);
+  const uint32_t n = min(out.counters[kCtProblems], out.dist_cap);
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) out.dist_list[i] = out.rep_dv[i].x;
 }
 template <bool INDEXED>

@@ -1703,6 +1703,7 @@ int kr_format_dist(const kr_host_index* h, const kr_result_view* rv, const char*
   // reads are cut into contiguous ranges, one string per range, joined in order
   const int nt = std::max(1, std::min(std::min(kr::parallel_width(), 16), (int)(rv->nreads / 4096)));
   std::vector<std::string> part((size_t)nt);
+  std::vector<uint8_t> bad((size_t)nt, 0); // (KR_ROWS_INDEXED) a row's index lies beyond the list: no text at all
   kr::parallel_for(nt, [&](int t) {
     const uint32_t r0 = (uint32_t)((uint64_t)rv->nreads * t / nt), r1 = (uint32_t)((uint64_t)rv->nreads * (t + 1) / nt);
     std::string& s = part[(size_t)t];
@@ -1714,6 +1715,10 @@ int kr_format_dist(const kr_host_index* h, const kr_result_view* rv, const char*
       const uint32_t o = rv->read_off[r], n = rv->read_cnt[r];
       for (uint32_t i = o; i < o + n; ++i) {
         if (!rv->rec_sel[i]) continue;
+        if (rv->rec_dix && rv->rec_dix[i] >= rv->ndist) {
+          bad[(size_t)t] = 1;
+          return;
+        }
         const char* nm = kr_host_index_node_name(h, rv->rec_key[i] >> 1);
         const size_t nl = fmt_fixed5(rv->rec_dix ? rv->dist_list[rv->rec_dix[i]] : rv->rec_d[i], num); // (KR_ROWS_INDEXED: DIST through the batch's list)
         s.append(id, idl);
@@ -1729,6 +1734,8 @@ int kr_format_dist(const kr_host_index* h, const kr_result_view* rv, const char*
       }
     }
   });
+  for (uint8_t x : bad)
+    if (x) return kr::fail(KR_ERR_ARG, "kr_format_dist: a row's rec_dix is not below ndist (KR_ROWS_INDEXED): not a view of this library's making");
   size_t total = 0;
   for (auto& s : part) total += s.size();
   char* p = (char*)malloc(total + 1);

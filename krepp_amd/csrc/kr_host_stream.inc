@@ -205,7 +205,10 @@ struct kr_stream {
   bool rows_indexed = false; // ... of 8 bytes: (key, index into the batch's distinct DIST values) -- KR_ROWS_INDEXED
   PinBuf<uint32_t> h_rec_dix; // of h_rec_key's size, allocated with the first indexed batch
   PinBuf<double> h_dist_list;
-  uint64_t ndist = 0;
+  uint64_t ndist = 0;        // entries of the batch's list (set by kr_batch_wait: a device view shows it too), h_ndist: of its host copy
+  uint64_t h_ndist = 0;
+  bool no_indexed = false;   // (an indexed batch whose list positions outgrew dist_list is run again with rec_d)
+  uint64_t ix_extent = 0, ix_fallbacks = 0; // kr_debug_indexed_list: list positions of the last indexed launch, reruns so far
   uint64_t d2h_bytes = 0;    // what the last kr_batch_collect copied back
   uint64_t h_sel_ones = 0; // leading entries of h_rec_sel known to hold 1 (rows-mode views: every row is selected)
   bool submitted = false, waited = false, collected = false;
@@ -245,6 +248,28 @@ uint32_t next_pow2(uint32_t v)
   uint32_t p = 1;
   while (p < v) p <<= 1;
   return p;
+}
+
+// KR_DEBUG_LIST_CAPS="dist,rep" (tests; read at every submit, as KR_DEBUG_PLACE_CAPS is per batch): what the kernels are told the list of
+// distinct likelihood problems holds -- `dist` entries of dist_list (KR_ROWS_INDEXED; really the lane's rec_cap), `rep` list positions
+// before kErrRecCap (really rec_cap + kRepSlack) --, so that a small batch reaches both ends.  A value only ever lowers its capacity
+// (the buffers stay as large as they are); 0 or an empty field keeps it.  Never below kListCapFloor: a wave of kr_dedup_kernel that is
+// over capacity goes on writing at position 0, kRepChunkMax entries at most, and the lowered list has that room too (a workgroup of
+// kr_dedup_direct_kernel writes up to 4,096 there: inside the buffers, which hold kRepSlack positions and more whatever the knob says).
+constexpr uint32_t kListCapFloor = kRepChunkMax;
+struct ListCaps {
+  uint64_t dist = 0, rep = 0;
+  uint32_t lower(uint32_t cap, uint64_t to) const { return to ? (uint32_t)std::min<uint64_t>(cap, std::max<uint64_t>(to, kListCapFloor)) : cap; }
+};
+ListCaps debug_list_caps()
+{
+  ListCaps c;
+  if (const char* e = getenv("KR_DEBUG_LIST_CAPS")) {
+    char* end = nullptr;
+    c.dist = strtoull(e, &end, 10);
+    if (end && *end == ',') c.rep = strtoull(end + 1, nullptr, 10);
+  }
+  return c;
 }
 
 int check_errflags(uint32_t e)
@@ -1015,7 +1040,9 @@ static int submit_batch(kr_stream* s, const uint8_t* bases, const uint64_t* offs
   s->rows_mode = (flags & KR_ROWS_ONLY) && !(flags & (KR_TAP_ACCS | KR_TAP_HITS)) && (!s->tiles.active || (flags & KR_TILE_ROWS)) && !getenv("KR_NO_ROW_COMPACTION");
   // KR_ROWS_INDEXED: 8-byte rows (key, position of DIST in the batch's distinct values).  One lane (a lane's positions are its own),
   // not tiled, no --filter (its select kernel writes rec_v, which the list of values aliases), no device text (its kernels read row_d)
-  s->rows_indexed = s->rows_mode && (flags & KR_ROWS_INDEXED) && P == 1 && !s->tiles.active && !(!s->dp.no_filter && s->dp.multi) && !s->text.req;
+  // (no_indexed: this is the rerun of a batch whose list positions outgrew dist_list)
+  s->rows_indexed = s->rows_mode && (flags & KR_ROWS_INDEXED) && P == 1 && !s->tiles.active && !(!s->dp.no_filter && s->dp.multi) && !s->text.req && !s->no_indexed;
+  const ListCaps list_caps = debug_list_caps();
   if (flags & KR_TAP_HITS) {
     if (!reserve_all(s->hit_cap, s->d_hits, s->h_hits)) return alloc_failed("kr_batch_submit: hit tap buffers");
     s->out.hits = s->d_hits.get();
@@ -1083,7 +1110,8 @@ static int submit_batch(kr_stream* s, const uint8_t* bases, const uint64_t* offs
     o.rec_read += rb, o.rec_key += rb, o.rec_hist += rb, o.rec_d += rb, o.rec_v += rb, o.rec_chisq += rb, o.rec_sel += rb;
     o.rec_w0 += rb, o.rec_rep += rb, o.rep_list += rb + (uint64_t)l * kRepSlack, o.rep_dv += rb + (uint64_t)l * kRepSlack;
     o.rec_cap = lane_rec_cap;
-    o.rep_cap = (uint32_t)std::min<uint64_t>((uint64_t)lane_rec_cap + kRepSlack, 0xFFFFFFFFull);
+    o.rep_cap = list_caps.lower((uint32_t)std::min<uint64_t>((uint64_t)lane_rec_cap + kRepSlack, 0xFFFFFFFFull), list_caps.rep);
+    o.dist_cap = list_caps.lower(lane_rec_cap, list_caps.dist);
     o.keep_v = ((flags & KR_ROWS_ONLY) && !(flags & KR_TAP_ACCS)) ? 0u : 1u;
     o.hist_always = (flags & KR_TAP_ACCS) ? 1u : 0u; // else a record's planes exist only where its packed word cannot describe it
     o.v_tile = s->tiles.active ? s->tiles.d_vtile.get() : nullptr;
@@ -1256,6 +1284,18 @@ int kr_batch_wait(kr_stream* s)
     s->batch_rc = check_errflags(hc[kCtErr] | (lane_full ? kErrRecCap : 0u));
   if (s->batch_rc) s->batch_msg = kr_last_error();
   if (!s->batch_rc && s->tiles.active && !s->no_tiles && getenv("KR_DEBUG_TILE_OVERFLOW")) s->batch_rc = KR_ERR_CAPACITY; // (tests)
+  // KR_ROWS_INDEXED (one lane): list positions are handed out up to rep_cap, dist_list holds dist_cap of them
+  s->ndist = s->rows_indexed ? std::min<uint64_t>(hc[kCtProblems], s->lanes[0].out.dist_cap) : 0;
+  if (s->rows_indexed) s->ix_extent = hc[kCtProblems];
+  if (!s->batch_rc && s->rows_indexed && hc[kCtProblems] > s->lanes[0].out.dist_cap) {
+    // some row's position may lie beyond the list: the batch again with the hint ignored -- rows with rec_d, as the header promises
+    // for a hint that is not honoured (the caller's buffers are still valid, as for the tiled rerun below)
+    s->no_indexed = true, ++s->ix_fallbacks;
+    int rc = submit_batch(s, s->sub_bases, s->sub_offsets, s->nreads, s->flags);
+    if (!rc) rc = kr_batch_wait(s);
+    s->no_indexed = false;
+    return rc;
+  }
   if (s->batch_rc == KR_ERR_CAPACITY && s->tiles.active && !s->no_tiles) {
     // the tiles' records did not fit: the batch again, one wave per sequence (the caller's buffers are still valid)
     s->no_tiles = true;
@@ -1277,6 +1317,8 @@ static void fill_view(kr_stream* s, kr_result_view* v, bool device)
     const BatchOut ro = result_out(s); // (a tiled batch: the real reads' per-read results)
     v->read_off = ro.rd_off, v->read_cnt = ro.rd_cnt, v->read_onmers = ro.rd_onmers, v->read_na = ro.rd_na;
     v->rec_key = s->out.rec_key, v->rec_sel = s->out.rec_sel, v->rec_d = s->rows_indexed ? nullptr : s->out.rec_d; // (indexed rows lie in rec_d)
+    // ... and DIST of record slot i is dist_list[rec_dix[i]]: the select kernels left every selected record's list position in rec_rep
+    if (s->rows_indexed) v->rec_dix = s->out.rec_rep, v->dist_list = s->lanes[0].out.dist_list, v->ndist = s->ndist;
     v->rec_v = (rows_only && !(s->flags & KR_TAP_ACCS) && !(!s->dp.no_filter && s->dp.multi)) ? nullptr : s->out.rec_v; // not written then
     v->rec_chisq = (!s->dp.no_filter && s->dp.multi) ? s->out.rec_chisq : nullptr; // written in filter mode only
     // planes exist for every record only in batches that keep histograms (else only where the packed word cannot hold the problem)
@@ -1285,7 +1327,7 @@ static void fill_view(kr_stream* s, kr_result_view* v, bool device)
   } else {
     v->read_off = s->h_rd_off, v->read_cnt = s->h_rd_cnt, v->read_onmers = s->h_rd_onmers, v->read_na = s->h_rd_na;
     v->rec_key = s->h_rec_key.get(), v->rec_sel = s->h_rec_sel.get(), v->rec_d = s->h_rec_d.get();
-    if (s->rows_indexed) v->rec_d = nullptr, v->rec_dix = s->h_rec_dix.get(), v->dist_list = s->h_dist_list.get(), v->ndist = s->ndist;
+    if (s->rows_indexed) v->rec_d = nullptr, v->rec_dix = s->h_rec_dix.get(), v->dist_list = s->h_dist_list.get(), v->ndist = s->h_ndist;
     v->rec_v = rows_only ? nullptr : s->h_rec_v.get();
     v->rec_chisq = rows_only ? nullptr : s->h_rec_chisq.get();
     v->rec_hist = (s->flags & KR_TAP_ACCS) && !rows_only ? s->h_rec_hist.get() : nullptr;
@@ -1380,10 +1422,10 @@ int kr_batch_collect(kr_stream* s, kr_result_view* v)
       HIP_TRY(hipMemcpyAsync(s->h_rd_cnt + r0, tl ? t.d_real_rcnt.get() : o.rd_rcnt, nr * 4, hipMemcpyDeviceToHost, st));
       HIP_TRY(hipMemcpyAsync(s->h_rd_na + r0, tl ? t.d_real_na.get() : o.rd_na, nr, hipMemcpyDeviceToHost, st));
       s->d2h_bytes += nr * 9;
-      if (nc && s->rows_indexed) { // (one lane, waited for: the counters are known)
-        const uint64_t nd = std::min<uint64_t>(L.h_counters[kCtProblems], L.rec_cap);
+      if (s->rows_indexed) s->h_ndist = nc ? s->ndist : 0; // (a batch without rows brings no list back)
+      if (nc && s->rows_indexed) { // (one lane, waited for: kr_batch_wait has set ndist)
+        const uint64_t nd = s->ndist;
         if (nd > s->h_dist_list.size() && !s->h_dist_list.reserve(nd + nd / 4 + 1024)) return alloc_failed("kr_batch_collect: list of distinct DIST values");
-        s->ndist = nd;
         HIP_TRY(hipMemcpyAsync(s->h_rec_key.get() + hoff, o.row_key, nc * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(s->h_rec_dix.get() + hoff, o.row_dix, nc * 4, hipMemcpyDeviceToHost, st));
         if (nd) HIP_TRY(hipMemcpyAsync(s->h_dist_list.get(), o.dist_list, nd * 8, hipMemcpyDeviceToHost, st));
@@ -1556,6 +1598,17 @@ int kr_debug_item_placement(kr_stream* s, uint32_t* tried, uint32_t* kept, doubl
   if (tried) *tried = s->ipl.tried;
   if (kept) *kept = s->ipl.kept_new;
   if (best_ns_per_read) *best_ns_per_read = s->ipl.best_ns;
+  return KR_OK;
+}
+
+// (tests) KR_ROWS_INDEXED: list positions the last indexed launch handed out (counters[kCtProblems]; of the first attempt if the batch
+// was then run again with rec_d) and how many batches of this stream were run again so
+int kr_debug_indexed_list(kr_stream* s, uint64_t* extent, uint64_t* fallbacks)
+{
+  kr::clear_error();
+  if (!s) return kr::fail(KR_ERR_ARG, "kr_debug_indexed_list: null argument");
+  if (extent) *extent = s->ix_extent;
+  if (fallbacks) *fallbacks = s->ix_fallbacks;
   return KR_OK;
 }
 

@@ -676,3 +676,30 @@ def test_flat_colours_list_exactly_the_leaves_the_walk_reaches(capi):
                     assert a_ >= se or b_ >= se or size(a_) + size(b_) > 64, se
         if nleaves >= 60:
             assert nrun > 10 and nlist > 10 and nflat > 0.3 * nextra
+
+
+def test_format_dist_refuses_an_index_beyond_the_list(capi, toy_index_dir):
+    """KR_ROWS_INDEXED: DIST of a row is dist_list[rec_dix[i]].  A view with a rec_dix[i] == ndist is refused with an error and yields
+    no text (the formatter used to index with it); the same view with that index one lower formats."""
+    hx = capi.HostIndex(toy_index_dir)
+    lib = capi.load()
+    u32 = lambda a: np.array(a, np.uint32)
+    off, cnt, na = u32([0, 1, 3]), u32([1, 2, 0]), np.array([0, 0, 1], np.uint8)
+    key, sel, dix = u32([1 << 1, (2 << 1) | 1, 3 << 1]), np.ones(3, np.uint8), u32([0, 1, 2])
+    dl = np.array([0.125, 0.03125], np.float64)
+    rv = capi.KrResultView()
+    rv.nreads, rv.nrecs, rv.nrows, rv.ndist = 3, 3, 3, 2
+    rv.read_off, rv.read_cnt, rv.read_na = off.ctypes.data_as(capi.u32p), cnt.ctypes.data_as(capi.u32p), na.ctypes.data_as(capi.u8p)
+    rv.rec_key, rv.rec_sel = key.ctypes.data_as(capi.u32p), sel.ctypes.data_as(capi.u8p)
+    rv.rec_dix, rv.dist_list = dix.ctypes.data_as(capi.u32p), dl.ctypes.data_as(capi.f64p)
+    names = [b"a", b"b", b"c"]
+    arr = (C.c_char_p * 3)(*names)
+    txt, ln = C.c_void_p(), C.c_uint64(0)
+    rc = lib.kr_format_dist(hx.h, C.byref(rv), arr, C.byref(txt), C.byref(ln))
+    assert rc == capi.KR_ERR_ARG and not txt.value and ln.value == 0 and b"rec_dix" in lib.kr_last_error()
+    dix[2] = 1
+    capi.check(lib.kr_format_dist(hx.h, C.byref(rv), arr, C.byref(txt), C.byref(ln)))
+    got = C.string_at(txt, ln.value).decode()
+    lib.kr_free(txt)
+    assert got == f"a\t{hx.name(1)}\t0.12500\nb\t{hx.name(2)}\t0.03125\nb\t{hx.name(3)}\t0.03125\nc\tNA\tNaN\n"
+    hx.close()
