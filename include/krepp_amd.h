@@ -466,6 +466,7 @@ KR_API void kr_host_free(void*);
  * after the '@' to the first C-locale isspace byte.  The accepted records are then those the sequential reader gives for the same
  * bytes, with the same names and sequences; the prefix ends at the first record that is not accepted (`status`):
  *   KR_FASTQ_NOT_CLEAN    anything else (FASTA, CRLF, wrapped lines, odd quality ...): the host reader continues at `consumed`
+ *                         (FASTA has an entry point of its own: kr_batch_submit_fasta, below)
  *   KR_FASTQ_INCOMPLETE   bytes behind the last complete record: a record cut by the end of the chunk, or a last line without '\n'
  *   KR_FASTQ_LONG         more k-mer positions than the stream tiles a sequence from (KR_TILE_MIN_POS): the host path tiles it
  *                         (never raised with KR_TILE_DEVICE in `flags`: the record is accepted like any other, bounded by max_reads,
@@ -504,6 +505,40 @@ KR_API int kr_batch_submit_fastq(kr_stream*, const uint8_t* raw, uint64_t nbytes
 KR_API int kr_batch_fastq_names(kr_stream*, const uint64_t** name_pos, const uint32_t** name_len);
 /* tests: the last kr_batch_submit_fastq's accepted bases [nbases] and offsets [nreads + 1] as the device wrote them */
 KR_API int kr_debug_fastq_batch(kr_stream*, uint8_t* bases, uint64_t* offsets);
+/* measurements: the device time (ms) of the record finder's kernels in the stream's last kr_batch_submit_fastq / _fasta.  The first
+ * call makes the events and gives -1; every parse behind it is measured (two event records a submit) */
+KR_API int kr_debug_fastq_parse_ms(kr_stream*, float* ms);
+
+/* FASTA records found on the device (csrc/kr_dev_fasta.inc): a batch given as the raw bytes of a plain FASTA file -- contigs,
+ * assemblies, genomes: wrapped at any width, LF or CRLF, or one line of megabases per record.  The stream is the one
+ * kr_stream_fastq_enable prepared, `raw` and `flags` are bound as for kr_batch_submit_fastq (page-locked, below 4 GB, at most
+ * max_raw_bytes, no KR_BASES_* flags), the summary is the same kr_fastq_parse (`newlines`: the chunk's '\n' bytes, `at_eof`: the
+ * caller's `closed`), the accepted prefix is queued exactly as kr_batch_submit_fastq queues its own (KR_TILE_DEVICE and
+ * KR_TILE_ROWS are honoured the same way, nreads == 0 queues nothing), and kr_batch_fastq_names / kr_debug_fastq_batch serve it
+ * afterwards.  Every pass over the chunk's bodies is parallel over its bytes, never over a record's length (only a header is
+ * walked by one wave), so that a 4 MB record should cost about what 4 MB of short records cost (measured, 64 MB of each:
+ * docs/design/08, "FASTA records on the device").  The device buffers only FASTA needs are made by a stream's first kr_batch_submit_fasta (sized from
+ * max_raw_bytes and max_reads); kr_batch_submit_fastq still answers NOT_CLEAN for FASTA.
+ * The grammar ("device-clean FASTA"), a subset of what the sequential reader takes (character-wise: src/kseq.h:177-219), on which
+ * both give the same names and sequences:
+ *   record start   a '>' at byte 0 of the chunk or directly behind a '\n'.  The chunk must begin with one (else NOT_CLEAN, nreads 0)
+ *   header         from the record start through the next '\n' (not in the chunk: the record is INCOMPLETE)
+ *   name           from behind the '>' to the first C-locale isspace byte of the header; may be empty; a NUL byte in it makes the
+ *                  record NOT_CLEAN (the host's names are C strings).  Other header bytes are free: comments may hold > + @, bytes >= 128
+ *   body           from behind the header's '\n' to the next record start, or to the end of the chunk
+ *   sequence       the body's bytes 33..126, in order; bytes below 33 and byte 127 are dropped ('\n', '\r', blanks, tabs, blank lines)
+ *   not clean      a body that holds '+', '@', a '>' that is no record start, or a byte >= 128 (the reader ends a record at the first
+ *                  three anywhere, and takes 0xFF for the end of the file): that record ends the accepted prefix with NOT_CLEAN
+ *   last record    a FASTA record does not say where it ends, so the caller does: closed != 0 -- the chunk ends where the file does, or
+ *                  at a byte where the caller has seen the next record start -- makes the chunk's last record complete, with or
+ *                  without a final '\n'; with closed == 0 the last record is never accepted (INCOMPLETE)
+ *   consumed       the position of the first record start that was not accepted, or nbytes: kr_fastx_open_at(path, chunk_offset +
+ *                  consumed) yields exactly the remaining records.  status == KR_FASTQ_OK iff consumed == nbytes; rejected == nreads
+ *   KR_FASTQ_LONG / KR_FASTQ_CAPACITY   as for FASTQ (LONG is never raised with KR_TILE_DEVICE; nreads 0: the record never fits)
+ * kr_fasta_chunk_cut (no device): the position of the last record start in buf[1 .. n), 0 when there is none -- where a reader of
+ * raw bytes ends a chunk that it submits with closed = 1 (`krepp dist --gpu-parse`). */
+KR_API int kr_batch_submit_fasta(kr_stream*, const uint8_t* raw, uint64_t nbytes, uint32_t flags, uint32_t closed, kr_fastq_parse* out);
+KR_API uint64_t kr_fasta_chunk_cut(const uint8_t* buf, uint64_t n);
 /* tests: the tiled form of the batch last submitted on the stream as it lies on the device, laid out by the host (a host batch)
  * or by kernels (KR_TILE_DEVICE): reads of the tiled batch and long sequences; voff [nv + 1] where every read of the tiled batch
  * starts in its bases, vtile [nv] 1 = a tile of a long sequence, rfirst [nreads] the caller's read's first read of the tiled batch,

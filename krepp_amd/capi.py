@@ -99,7 +99,7 @@ EXPORTS = [
     "kr_index_upload", "kr_index_free", "kr_index_export", "kr_index_import", "kr_index_device_bytes", "kr_index_slot_words", "kr_index_slot_format", "kr_index_broadcast",
     "kr_params_default", "kr_stream_create", "kr_stream_destroy", "kr_batch_submit", "kr_batch_wait",
     "kr_batch_collect", "kr_batch_collect_device", "kr_stream_text_enable", "kr_batch_submit_text", "kr_batch_collect_text",
-    "kr_stream_fastq_enable", "kr_batch_submit_fastq", "kr_batch_fastq_names", "kr_debug_fastq_batch", "kr_debug_tile_layout", "kr_debug_tile_shape", "kr_batch_hits", "kr_batch_readtaps",
+    "kr_stream_fastq_enable", "kr_batch_submit_fastq", "kr_batch_submit_fasta", "kr_fasta_chunk_cut", "kr_batch_fastq_names", "kr_debug_fastq_batch", "kr_debug_fastq_parse_ms", "kr_debug_tile_layout", "kr_debug_tile_shape", "kr_batch_hits", "kr_batch_readtaps",
     "kr_debug_front_end", "kr_debug_stream_move", "kr_debug_stream_addrs", "kr_debug_item_placement", "kr_debug_brent", "kr_debug_prefix", "kr_debug_colour_classes", "kr_llh_batch", "kr_llh_eval_indexed", "kr_batch_timing",
     "kr_place_tree_create", "kr_place_tree_create_lineage", "kr_place_tree_nnodes", "kr_place_summary_add",
     "kr_place_summary_text", "kr_place_tree_free", "kr_place_tree_kinds", "kr_place_batch", "kr_place_stream", "kr_place_frame", "kr_place_counters",
@@ -198,8 +198,12 @@ def load():
     lib.kr_fastx_open_at.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(vp)]
     lib.kr_stream_fastq_enable.argtypes = [vp, C.c_uint64]
     lib.kr_batch_submit_fastq.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(KrFastqParse)]
+    lib.kr_batch_submit_fasta.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(KrFastqParse)]
+    lib.kr_fasta_chunk_cut.argtypes = [vp, C.c_uint64]
+    lib.kr_fasta_chunk_cut.restype = C.c_uint64
     lib.kr_batch_fastq_names.argtypes = [vp, C.POINTER(u64p), C.POINTER(u32p)]
     lib.kr_debug_fastq_batch.argtypes = [vp, vp, vp]
+    lib.kr_debug_fastq_parse_ms.argtypes = [vp, C.POINTER(C.c_float)]
     lib.kr_debug_tile_layout.argtypes = [vp, u32p, u32p, vp, vp, vp, vp, vp]
     lib.kr_debug_tile_shape.argtypes = [C.c_uint64, C.c_uint32, u64p, u64p, u64p]
     lib.kr_fastx_next.argtypes = [vp, C.c_uint64, C.POINTER(KrFastxBatch)]
@@ -575,7 +579,11 @@ class Stream:
         """kr_stream_fastq_enable: this stream can be given batches as raw FASTQ bytes (csrc/kr_dev_fastq.inc)"""
         check(self.lib.kr_stream_fastq_enable(self.h, int(max_raw_bytes)))
 
-    def submit_fastq(self, raw, flags=0, at_eof=1):
+    def submit_fasta(self, raw, flags=0, closed=1):
+        """kr_batch_submit_fasta on a page-locked copy of `raw` (kept until the next submit): the summary as a dict"""
+        return self.submit_fastq(raw, flags, closed, call=self.lib.kr_batch_submit_fasta)
+
+    def submit_fastq(self, raw, flags=0, at_eof=1, call=None):
         """kr_batch_submit_fastq on a page-locked copy of `raw` (kept until the next submit): the summary as a dict"""
         raw = bytes(raw)
         n = len(raw)
@@ -589,7 +597,7 @@ class Stream:
         C.memmove(self._pinned, raw, n)
         self._raw = raw
         out = KrFastqParse()
-        check(self.lib.kr_batch_submit_fastq(self.h, self._pinned, n, flags, at_eof, C.byref(out)))
+        check((call or self.lib.kr_batch_submit_fastq)(self.h, self._pinned, n, flags, at_eof, C.byref(out)))
         self._fq_nreads = out.nreads
         text = getattr(self, "_text_on", False) and not (flags & (KR_TAP_ACCS | KR_TAP_HITS))  # as kr_batch_submit_fastq decides
         self._flags = flags | KR_BASES_DEVICE | (KR_ROWS_ONLY if text else 0)
@@ -659,6 +667,12 @@ class Stream:
             self.close()
         except Exception:
             pass
+
+
+def fasta_chunk_cut(buf):
+    """kr_fasta_chunk_cut: the position of the last record start ('>' behind a newline) in buf[1:], 0 when there is none"""
+    buf = bytes(buf)
+    return int(load().kr_fasta_chunk_cut(buf, len(buf)))
 
 
 def tile_shape(length, k):

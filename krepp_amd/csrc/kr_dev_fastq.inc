@@ -14,6 +14,7 @@
 //   kr_fq_off_kernel       offsets (uint64) and id offsets (uint32, id_sep = 0) of every record; the first record that does not fit
 //                          max_bases or the id buffer ends the accepted prefix (CAPACITY)
 //   kr_fq_copy_kernel      a wave per accepted record copies its sequence and name; one lane writes the summary
+// The three offset kernels serve FASTA records too (kr_dev_fasta.inc): they take the record count from fq_nrec.
 // Device-clean: clean_record would return Ok AND the quality line is exactly as long as the sequence line, so that the accepted
 // records are a subset of the host's and give the same names and sequences.  Positions are uint32_t within the chunk (< 4 GB).
 constexpr uint32_t kFqTile = 4096;     // bytes per workgroup of the newline passes: 256 lanes x 16 bytes
@@ -28,6 +29,8 @@ struct FqIO {
   uint32_t *rec_slen, *rec_npos, *rec_nlen; // [max_reads] sequence length, name position and length of every record checked
   uint64_t *bsum_b, *bsum_n;     // [max_reads / kFqRecBlock + 2] per block, then (in place) the blocks' first bases / name bytes
   unsigned long long* ctl;       // [0] newlines in the chunk  [1] min(record << 8 | status) over rejected records  [2] records scanned
+                                 // [3] (FASTA, kr_dev_fasta.inc) record starts in the chunk
+  uint32_t rec_lines;            // lines of a record: 4 (FASTQ); 0: a record has any number of lines and ctl[3] counts the records
   uint8_t* bases;                // the stream's d_bases
   uint64_t* offsets;             // [max_reads + 1] the stream's d_offsets
   char* ids;                     // the name bytes back to back (nullptr: names are not copied)
@@ -84,8 +87,11 @@ __global__ __launch_bounds__(256) void kr_fq_nl_write_kernel(FqIO f)
   }
 }
 
-// records the newline passes give complete lines for, at most max_reads
-__device__ __forceinline__ uint32_t fq_nrec(const FqIO& f) { return (uint32_t)min((unsigned long long)f.max_reads, f.ctl[0] / 4ull); }
+// records the newline passes give complete lines for (FASTA: the record starts counted), at most max_reads
+__device__ __forceinline__ uint32_t fq_nrec(const FqIO& f)
+{
+  return (uint32_t)min((unsigned long long)f.max_reads, f.rec_lines ? f.ctl[0] / f.rec_lines : f.ctl[3]);
+}
 
 __device__ __forceinline__ bool fq_isspace(uint32_t c) { return c == ' ' || (c - 9u) <= 4u; } // C locale: ' ' '\t' '\n' '\v' '\f' '\r'
 

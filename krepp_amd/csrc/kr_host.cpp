@@ -1515,6 +1515,20 @@ int kr_fastx_open_at(const char* path, uint64_t offset, kr_fastx** out)
   return KR_OK;
 }
 
+// Where a reader of raw FASTA bytes cuts its chunk (kr_batch_submit_fasta with closed = 1): the last record start -- a '>' directly
+// behind a '\n' -- in buf[1 .. n), 0 when there is none (the chunk's own start at position 0 is no cut)
+uint64_t kr_fasta_chunk_cut(const uint8_t* buf, uint64_t n)
+{
+  if (!buf) return 0;
+  for (uint64_t end = n; end > 1;) { // the last '>' in buf[1 .. end), then the one in front of it, ...
+    const uint8_t* g = (const uint8_t*)memrchr(buf + 1, '>', end - 1);
+    if (!g) return 0;
+    if (g[-1] == '\n') return (uint64_t)(g - buf);
+    end = (uint64_t)(g - buf);
+  }
+  return 0;
+}
+
 // QSeq::read_next_batch (src/rqseq.cpp:180-197): keep reading until the batch holds
 // at least `min_bases` bases (reference: RBATCH_SIZE*DSEQ_LEN = 76,800) or input ends.
 int kr_fastx_next(kr_fastx* r, uint64_t min_bases, kr_fastx_batch* out)

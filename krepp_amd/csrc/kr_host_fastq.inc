@@ -2,6 +2,91 @@
 // A batch given as the raw bytes of a plain FASTQ file; the records are found by the kernels of kr_dev_fastq.inc, then the batch
 // runs on the submit_batch path with its bases already in HBM (with KR_TILE_DEVICE: long records too, tiled by build_tiles_device;
 // with KR_TILE_ROWS as well, such a batch's rows and text are the device's: submit_batch reads the flag, the ids are in HBM already).
+// kr_batch_submit_fasta (kr_host_fasta.inc) shares everything but the record finder's kernels: fq_begin / fq_finish.
+
+namespace {
+
+// What kr_batch_submit_fastq and kr_batch_submit_fasta (kr_host_fasta.inc) share.  fq_begin: the argument checks, the wait for the
+// batch in flight, the kernels' arguments that do not depend on the format, and the chunk's copy to d_raw; nbytes == 0 is accepted
+// here (nothing is queued: the caller returns).  fq_finish: the wait for the summary, and the accepted prefix queued as a batch.
+int fq_begin(kr_stream* s, const char* fn, const uint8_t* raw, uint64_t nbytes, uint32_t flags, uint32_t at_eof, kr_fastq_parse* out, FqIO& io,
+             bool& text)
+{
+  const std::string who = std::string(fn) + ": ";
+  if (!s || !raw || !out) return kr::fail(KR_ERR_ARG, who + "null argument");
+  if (nbytes >= (1ull << 32)) return kr::fail(KR_ERR_ARG, who + "a chunk must stay below 4 GB (positions are 32-bit)");
+  if (!s->fq.on) return kr::fail(KR_ERR_STATE, who + "kr_stream_fastq_enable first");
+  if (nbytes > s->fq.raw_cap) return kr::fail(KR_ERR_ARG, who + "more bytes than kr_stream_fastq_enable sized the stream for");
+  if (flags & (KR_BASES_DEVICE | KR_BASES_PINNED)) return kr::fail(KR_ERR_ARG, who + "the bases are the record finder's: no KR_BASES_* flags");
+  memset(out, 0, sizeof(*out));
+  out->at_eof = at_eof ? 1u : 0u;
+  kr_stream::Fastq& f = s->fq;
+  if (nbytes == 0) {
+    f.parsed = true, f.nreads = 0, f.have_names = false;
+    return KR_OK;
+  }
+  text = s->text.on && !(flags & (KR_TAP_ACCS | KR_TAP_HITS));
+  HIP_TRY(hipSetDevice(s->ix->device));
+  (void)hipGetLastError();
+  if (s->submitted && !s->waited) // d_bases, d_offsets and the ids belong to the batch in flight
+    for (uint32_t l = 0; l < s->nlanes; ++l) HIP_TRY(hipStreamSynchronize(s->lanes[l].stream));
+  f.parsed = false, f.have_names = false;
+  hipStream_t st = s->lanes[0].stream; // (the lane of a device-input batch: the parse and the batch are ordered on it)
+  io.raw = f.d_raw, io.nbytes = nbytes;
+  io.tile_nl = f.d_tile_nl, io.nl = nullptr, io.nl_cap = 0, io.rec_lines = 0;
+  io.rec_slen = f.d_slen, io.rec_npos = f.d_npos, io.rec_nlen = f.d_nlen;
+  io.bsum_b = f.d_bsum_b, io.bsum_n = f.d_bsum_n, io.ctl = f.d_ctl;
+  io.bases = s->d_bases, io.offsets = s->d_offsets;
+  io.ids = text ? s->text.d_ids : nullptr;
+  io.id_off = text ? s->text.d_id_off : f.d_id_off;
+  io.max_reads = s->max_reads, io.max_bases = s->max_bases, io.id_cap = text ? s->text.id_cap : ~0ull;
+  // KR_TILE_DEVICE: a long record is accepted like any other (no k-mer count exceeds the bound) and tiled on the device below
+  io.k = s->ix->dix.k, io.tile_min_pos = (flags & KR_TILE_DEVICE) ? 0xFFFFFFFFu : s->tile_min_pos;
+  io.sum = f.d_sum;
+  // queued before the index's kernel chain is waited for (launch_lane): the copy and the parse overlap other streams' batches
+  HIP_TRY(hipMemcpyAsync(f.d_raw, raw, nbytes, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(f.d_ctl, 0xFF, 32, st));
+  return KR_OK;
+}
+
+// in front of the record finder's first kernel: where kr_debug_fastq_parse_ms, once asked, starts the kernels' time
+int fq_mark(kr_stream* s)
+{
+  if (s->fq.ev_parse0) HIP_TRY(hipEventRecord(s->fq.ev_parse0, s->lanes[0].stream));
+  return KR_OK;
+}
+
+int fq_finish(kr_stream* s, uint32_t flags, uint32_t at_eof, bool text, kr_fastq_parse* out)
+{
+  kr_stream::Fastq& f = s->fq;
+  hipStream_t st = s->lanes[0].stream;
+  HIP_TRY(hipGetLastError());
+  if (f.ev_parse0) {
+    HIP_TRY(hipEventRecord(f.ev_parse1, st));
+    f.ev_set = true;
+  }
+  HIP_TRY(hipMemcpyAsync(f.h_sum, f.d_sum, sizeof(kr_fastq_parse), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  *out = *f.h_sum;
+  out->at_eof = at_eof ? 1u : 0u;
+  f.nreads = out->nreads;
+  f.parsed = true;
+  if (out->nreads == 0) return KR_OK;
+  kr_stream::Text& t = s->text;
+  int rc;
+  if (text) {
+    t.id_bytes = out->id_bytes, t.id_sep = 0;
+    t.req = true, t.ids_on_device = true;
+    rc = submit_batch(s, s->d_bases, s->d_offsets, out->nreads, flags | KR_ROWS_ONLY | KR_BASES_DEVICE);
+    if (rc) t.req = false;
+  } else {
+    t.req = false;
+    rc = submit_batch(s, s->d_bases, s->d_offsets, out->nreads, flags | KR_BASES_DEVICE);
+  }
+  return rc;
+}
+
+} // namespace
 
 extern "C" {
 
@@ -31,42 +116,16 @@ int kr_stream_fastq_enable(kr_stream* s, uint64_t max_raw_bytes)
 int kr_batch_submit_fastq(kr_stream* s, const uint8_t* raw, uint64_t nbytes, uint32_t flags, uint32_t at_eof, kr_fastq_parse* out)
 {
   kr::clear_error();
-  if (!s || !raw || !out) return kr::fail(KR_ERR_ARG, "kr_batch_submit_fastq: null argument");
-  if (nbytes >= (1ull << 32)) return kr::fail(KR_ERR_ARG, "kr_batch_submit_fastq: a chunk must stay below 4 GB (positions are 32-bit)");
-  if (!s->fq.on) return kr::fail(KR_ERR_STATE, "kr_batch_submit_fastq: kr_stream_fastq_enable first");
-  if (nbytes > s->fq.raw_cap) return kr::fail(KR_ERR_ARG, "kr_batch_submit_fastq: more bytes than kr_stream_fastq_enable sized the stream for");
-  if (flags & (KR_BASES_DEVICE | KR_BASES_PINNED)) return kr::fail(KR_ERR_ARG, "kr_batch_submit_fastq: the bases are the record finder's: no KR_BASES_* flags");
-  memset(out, 0, sizeof(*out));
-  out->at_eof = at_eof ? 1u : 0u;
-  kr_stream::Fastq& f = s->fq;
-  if (nbytes == 0) {
-    f.parsed = true, f.nreads = 0, f.have_names = false;
-    return KR_OK;
-  }
-  const bool text = s->text.on && !(flags & (KR_TAP_ACCS | KR_TAP_HITS));
-  HIP_TRY(hipSetDevice(s->ix->device));
-  (void)hipGetLastError();
-  if (s->submitted && !s->waited) // d_bases, d_offsets and the ids belong to the batch in flight
-    for (uint32_t l = 0; l < s->nlanes; ++l) HIP_TRY(hipStreamSynchronize(s->lanes[l].stream));
-  f.parsed = false, f.have_names = false;
-  hipStream_t st = s->lanes[0].stream; // (the lane of a device-input batch: the parse and the batch are ordered on it)
   FqIO io;
-  io.raw = f.d_raw, io.nbytes = nbytes;
-  io.tile_nl = f.d_tile_nl, io.nl = f.d_nl, io.nl_cap = 4u * s->max_reads;
-  io.rec_slen = f.d_slen, io.rec_npos = f.d_npos, io.rec_nlen = f.d_nlen;
-  io.bsum_b = f.d_bsum_b, io.bsum_n = f.d_bsum_n, io.ctl = f.d_ctl;
-  io.bases = s->d_bases, io.offsets = s->d_offsets;
-  io.ids = text ? s->text.d_ids : nullptr;
-  io.id_off = text ? s->text.d_id_off : f.d_id_off;
-  io.max_reads = s->max_reads, io.max_bases = s->max_bases, io.id_cap = text ? s->text.id_cap : ~0ull;
-  // KR_TILE_DEVICE: a long record is accepted like any other (no k-mer count exceeds the bound) and tiled on the device below
-  io.k = s->ix->dix.k, io.tile_min_pos = (flags & KR_TILE_DEVICE) ? 0xFFFFFFFFu : s->tile_min_pos;
-  io.sum = f.d_sum;
-  // queued before the index's kernel chain is waited for (launch_lane): the copy and the parse overlap other streams' batches
-  HIP_TRY(hipMemcpyAsync(f.d_raw, raw, nbytes, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemsetAsync(f.d_ctl, 0xFF, 32, st));
+  bool text = false;
+  int rc = fq_begin(s, "kr_batch_submit_fastq", raw, nbytes, flags, at_eof, out, io, text);
+  if (rc || nbytes == 0) return rc;
+  kr_stream::Fastq& f = s->fq;
+  hipStream_t st = s->lanes[0].stream;
+  io.nl = f.d_nl, io.nl_cap = 4u * s->max_reads, io.rec_lines = 4;
   const uint32_t ntiles = (uint32_t)((nbytes + kFqTile - 1) / kFqTile);
   const uint32_t rgrid = std::min<uint32_t>((s->max_reads + 3) / 4, 8192u), bgrid = std::min<uint32_t>(s->max_reads / kFqRecBlock + 1, 4096u);
+  if ((rc = fq_mark(s))) return rc;
   hipLaunchKernelGGL(kr_fq_nl_count_kernel, dim3(std::min<uint32_t>(ntiles, 16384u)), dim3(256), 0, st, io);
   hipLaunchKernelGGL(kr_fq_nl_scan_kernel, dim3(1), dim3(1024), 0, st, io);
   hipLaunchKernelGGL(kr_fq_nl_write_kernel, dim3(std::min<uint32_t>(ntiles, 16384u)), dim3(256), 0, st, io);
@@ -75,26 +134,7 @@ int kr_batch_submit_fastq(kr_stream* s, const uint8_t* raw, uint64_t nbytes, uin
   hipLaunchKernelGGL(kr_fq_bscan_kernel, dim3(1), dim3(1024), 0, st, io);
   hipLaunchKernelGGL(kr_fq_off_kernel, dim3(bgrid), dim3(256), 0, st, io);
   hipLaunchKernelGGL(kr_fq_copy_kernel, dim3(rgrid), dim3(256), 0, st, io);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(f.h_sum, f.d_sum, sizeof(kr_fastq_parse), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  *out = *f.h_sum;
-  out->at_eof = at_eof ? 1u : 0u;
-  f.nreads = out->nreads;
-  f.parsed = true;
-  if (out->nreads == 0) return KR_OK;
-  kr_stream::Text& t = s->text;
-  int rc;
-  if (text) {
-    t.id_bytes = out->id_bytes, t.id_sep = 0;
-    t.req = true, t.ids_on_device = true;
-    rc = submit_batch(s, s->d_bases, s->d_offsets, out->nreads, flags | KR_ROWS_ONLY | KR_BASES_DEVICE);
-    if (rc) t.req = false;
-  } else {
-    t.req = false;
-    rc = submit_batch(s, s->d_bases, s->d_offsets, out->nreads, flags | KR_BASES_DEVICE);
-  }
-  return rc;
+  return fq_finish(s, flags, at_eof, text, out);
 }
 
 int kr_batch_fastq_names(kr_stream* s, const uint64_t** name_pos, const uint32_t** name_len)
@@ -138,6 +178,27 @@ int kr_debug_fastq_batch(kr_stream* s, uint8_t* bases, uint64_t* offsets)
   HIP_TRY(hipStreamSynchronize(st));
   if (offsets[n]) HIP_TRY(hipMemcpyAsync(bases, s->d_bases, offsets[n], hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
+  return KR_OK;
+}
+
+// (measurements) the device time of the record finder's kernels in the stream's last kr_batch_submit_fastq / _fasta, behind the
+// chunk's copy and in front of the summary's.  The first call makes the events and gives *ms = -1: the next parse is the first measured.
+int kr_debug_fastq_parse_ms(kr_stream* s, float* ms)
+{
+  kr::clear_error();
+  if (!s || !ms) return kr::fail(KR_ERR_ARG, "kr_debug_fastq_parse_ms: null argument");
+  if (!s->fq.on) return kr::fail(KR_ERR_STATE, "kr_debug_fastq_parse_ms: kr_stream_fastq_enable first");
+  kr_stream::Fastq& f = s->fq;
+  *ms = -1.0f;
+  HIP_TRY(hipSetDevice(s->ix->device));
+  if (!f.ev_parse0) {
+    HIP_TRY(hipEventCreate(&f.ev_parse0));
+    HIP_TRY(hipEventCreate(&f.ev_parse1));
+    return KR_OK;
+  }
+  if (!f.ev_set) return KR_OK;
+  HIP_TRY(hipEventSynchronize(f.ev_parse1));
+  HIP_TRY(hipEventElapsedTime(ms, f.ev_parse0, f.ev_parse1));
   return KR_OK;
 }
 

@@ -196,6 +196,13 @@ struct kr_stream {
     uint32_t nreads = 0;
     uint32_t *h_npos = nullptr, *h_nlen = nullptr;
     std::vector<uint64_t> name_pos;
+    hipEvent_t ev_parse0 = nullptr, ev_parse1 = nullptr; // kr_debug_fastq_parse_ms: around the record finder's kernels, once asked for
+    bool ev_set = false;
+    // FASTA records (kr_dev_fasta.inc): made by the stream's first kr_batch_submit_fasta, sized from raw_cap and max_reads
+    bool fa_on = false;
+    uint32_t *d_tile_st = nullptr, *d_tile_gr = nullptr; // [tiles of raw_cap + 1]
+    uint32_t *d_hs = nullptr, *d_ga = nullptr;           // [max_reads + 2]
+    uint32_t *d_hg = nullptr, *d_he = nullptr;           // [max_reads]
   } fq;
   const uint8_t* sub_bases = nullptr; // the arguments of the submit in flight (host buffers stay valid until wait / collect returns)
   const uint64_t* sub_offsets = nullptr;
@@ -881,6 +888,8 @@ void kr_stream_destroy(kr_stream* s)
     if (L.stream) (void)hipStreamDestroy(L.stream);
   }
   for (hipStream_t st : s->moved_streams) (void)hipStreamDestroy(st);
+  if (s->fq.ev_parse0) (void)hipEventDestroy(s->fq.ev_parse0);
+  if (s->fq.ev_parse1) (void)hipEventDestroy(s->fq.ev_parse1);
   delete s; // (every DevBuf / PinBuf of the stream frees itself here: the device is set, the lanes' streams have been waited for)
 }
 

@@ -82,7 +82,7 @@ static void print_help(const std::string& sub)
   if (sub.empty() || sub == "dist")
     printf("\nkrepp dist -i DIR -q READS: distances of every read to the references it matches\n%s%s"
            "      --filter / --no-filter keep only references not significantly worse than the closest [no-filter]\n"
-           "      --gpu-parse            FASTQ records found on the GPU (identical output; plain files, others keep the host reader)\n",
+           "      --gpu-parse            FASTA/FASTQ records found on the GPU (identical output; plain files, others keep the host reader)\n",
            query_opts, index_query_opts);
   if (sub.empty() || sub == "place")
     printf("\nkrepp place -i DIR -q READS: placements on the backbone tree (jplace)\n%s%s"
@@ -162,6 +162,7 @@ struct Job {
   uint8_t* raw = nullptr;
   uint64_t raw_len = 0, raw_off = 0;
   bool at_eof = false;
+  bool fasta = false, closed = false; // a chunk of a FASTA file (kr_batch_submit_fasta); its last record ends where the chunk does
 };
 
 // `dist` and `place` share everything up to the per-batch back end (src/krepp.cpp:347-394, 434-504)
@@ -326,13 +327,15 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
   std::vector<kr_stream*> streams_to_free;
   kr_fastx* fx = nullptr; // (opened before the workers start; they hand batches back to it)
   // --gpu-parse (`dist` only, plain regular files): the reader only moves bytes into page-locked chunks cut at guessed record starts;
-  // each worker finds the records of its chunks on its GPU (kr_batch_submit_fastq with KR_TILE_DEVICE: long records are tiled on the
+  // each worker finds the records of its chunks on its GPU (kr_batch_submit_fastq / kr_batch_submit_fasta with KR_TILE_DEVICE: long records are tiled on the
   // device).  The first chunk that stops early (a record that is not clean four-line FASTQ, a wrong cut, a batch that overflows) names the byte where the host reader
   // (kr_fastx_open_at) takes over for good; chunks behind it were handed out already and are dropped unwritten (their sequence
   // numbers are skipped by the writer, in order), as the pool reader's "first surprise -> sequential to the end" (kr_host.cpp).
   bool gpu_parse = !place && !seek && a.flag.count("--gpu-parse") && a.flag.at("--gpu-parse");
+  // A file whose first byte is '>' is cut and parsed as FASTA (kr_fasta_chunk_cut, kr_batch_submit_fasta); any other as FASTQ.
   int qfd = -1;
   uint64_t qsize = 0;
+  bool fasta_parse = false;
   if (gpu_parse) {
     struct stat sb;
     unsigned char mg[2] = {0, 0};
@@ -342,9 +345,12 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
       qfd = -1, gpu_parse = false; // gzip / BGZF / not a regular file: the host reader
     } else {
       qsize = (uint64_t)sb.st_size;
+      fasta_parse = mg[0] == '>';
     }
   }
-  // about one reader batch of ordinary FASTQ per chunk (2 bytes of input per base); KR_CLI_PARSE_CHUNK (bytes): tests
+  // about one reader batch of ordinary FASTQ per chunk (2 bytes of input per base); KR_CLI_PARSE_CHUNK (bytes): tests.  The chunk is
+  // also the longest record the device path takes: a FASTA record longer than a chunk leaves no second record start to cut at, the
+  // chunk stops INCOMPLETE with no record, and the host reader takes the file from that record on (docs/design/08)
   const uint64_t chunk_bytes = getenv("KR_CLI_PARSE_CHUNK") ? std::max<uint64_t>(4096, strtoull(getenv("KR_CLI_PARSE_CHUNK"), nullptr, 10))
                                                             : std::min<uint64_t>(2 * batch_bases + (1u << 16), 3ull << 30);
   std::vector<uint8_t*> raw_free; // page-locked chunk buffers not in use
@@ -586,7 +592,9 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
           kr_fastq_parse fp;
           auto t_dev = now();
           // (KR_TILE_DEVICE: a long record stays with the device, tiled there; KR_TILE_ROWS: and its batch's text is the device's too)
-          int rc = kr_batch_submit_fastq(st, j->raw + pos, j->raw_len - pos, (text_on ? KR_TILE_ROWS : KR_ROWS_ONLY) | KR_TILE_DEVICE, j->at_eof ? 1u : 0u, &fp);
+          const uint32_t pflags = (text_on ? KR_TILE_ROWS : KR_ROWS_ONLY) | KR_TILE_DEVICE;
+          int rc = j->fasta ? kr_batch_submit_fasta(st, j->raw + pos, j->raw_len - pos, pflags, j->closed ? 1u : 0u, &fp)
+                            : kr_batch_submit_fastq(st, j->raw + pos, j->raw_len - pos, pflags, j->at_eof ? 1u : 0u, &fp);
           if (rc) return rc;
           if (fp.nreads) {
             const char* dtext = nullptr;
@@ -778,7 +786,12 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
       }
       const bool last = off + want >= qsize;
       uint64_t cut = want;
-      if (!last) { // a line starting with '@' whose second next line starts with '+' (the pool reader's rule, kr_host.cpp); none: the
+      bool closed = last;
+      if (!last && fasta_parse) { // the last record start of the chunk: what lies in front of it is whole records.  None: the chunk's one
+                                  // record is longer than the chunk, it stops INCOMPLETE with no record and the host reader takes over
+        const uint64_t c = kr_fasta_chunk_cut(buf, want);
+        if (c) cut = c, closed = true;
+      } else if (!last) { // a line starting with '@' whose second next line starts with '+' (the pool reader's rule, kr_host.cpp); none: the
                    // chunk ends inside a record, its last record stops INCOMPLETE and the host reader takes over there
         const uint64_t w0 = want > (1u << 20) ? want - (1u << 20) : 0;
         const uint8_t* nl = (const uint8_t*)memchr(buf + w0, '\n', want - w0);
@@ -793,6 +806,7 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
       }
       Job* j = new Job();
       j->raw = buf, j->raw_len = cut, j->raw_off = off, j->at_eof = last && cut == want;
+      j->fasta = fasta_parse, j->closed = closed;
       off += cut;
       {
         std::unique_lock<std::mutex> lk(mu);
@@ -911,6 +925,8 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
   if (timing)
     fprintf(stderr, "[timing] parse %.3f s, job hand-over (incl. waiting for queue space) %.3f s, device %.3f s, format %.3f s, write %.3f s; of the elapsed time, until the last worker had its stream and page-locked buffers: %.3f s (the reader parses meanwhile)\n",
             ns_parse / 1e9, ns_job / 1e9, ns_dev / 1e9, ns_fmt / 1e9, ns_write / 1e9, std::chrono::duration<double>(t_loop - t_init).count());
+  if (timing && gpu_parse)
+    fprintf(stderr, "[timing] gpu-parse: %llu %s records found on the device\n", (unsigned long long)nreads_dev.load(), fasta_parse ? "FASTA" : "FASTQ");
   if (timing && !place && !seek && !summarize) // (a batch split at capacity counts once per piece)
     fprintf(stderr, "[timing] report text: %llu batches written from device text, %llu through the host formatter\n", (unsigned long long)nb_dev_text.load(),
             (unsigned long long)nb_host_text.load());
