@@ -304,6 +304,18 @@ KR_API int kr_debug_last_d2h_bytes(kr_stream*, uint64_t* bytes);
 /* Tests: KR_ROWS_INDEXED -- `extent`: list positions the stream's last indexed launch handed out (holes included; of the first attempt
  * if the batch was then run again without the hint); `fallbacks`: batches of this stream run again so, so far.  Either may be NULL. */
 KR_API int kr_debug_indexed_list(kr_stream*, uint64_t* extent, uint64_t* fallbacks);
+/* Tests: path witnesses of the accumulate kernel for the batch last waited for, counted only by a stream created under
+ * KR_DEBUG_SKIP=512 (0 otherwise): the first min(n, 21) into `out`, in this order -- finalize_events_fast: calls, returned false before
+ * the compaction, compaction entered, returned false after it, finish_big_read, finished in one key batch, in several, key batches
+ * beyond the first, fix_dup calls, fix_dup calls that moved the count; finalize_events: calls with events of the one-segment, the
+ * two-segment and the merge instantiation, fused, sparse, planes in global scratch, key batches beyond the first, key table in global
+ * scratch, returned false; process_read: reads set aside by the one-segment launch, reads done again with the plane tables. */
+KR_API int kr_debug_acc_paths(kr_stream*, uint32_t* out, uint32_t n);
+/* Tests (no device needed; the stream may be NULL): the event region of the accumulate instantiation for np = hdist_th + 1 planes and
+ * reads of `segs` segments (1 or 2), or the merge instantiation (multi != 0): out8 = {events held in the LDS before a read's events
+ * spill, words of the region, words per key of a batch of the straight-line epilogue, number of path witnesses, then for the stream
+ * (0 if NULL) the events, passing-key table entries and keys a wave's global scratch holds, 0}. */
+KR_API int kr_debug_acc_layout(const kr_stream*, uint32_t np, uint32_t segs, uint32_t multi, uint32_t* out8);
 /* Tests: one number as `krepp place` rows print it (std::fixed, 5 decimals; `out` holds 80 bytes); returns its length. */
 KR_API int kr_debug_place_fixed5(double v, char* out);
 

@@ -103,9 +103,14 @@ EXPORTS = [
     "kr_debug_front_end", "kr_debug_stream_move", "kr_debug_stream_addrs", "kr_debug_item_placement", "kr_debug_brent", "kr_debug_prefix", "kr_debug_colour_classes", "kr_llh_batch", "kr_llh_eval_indexed", "kr_batch_timing",
     "kr_place_tree_create", "kr_place_tree_create_lineage", "kr_place_tree_nnodes", "kr_place_summary_add",
     "kr_place_summary_text", "kr_place_tree_free", "kr_place_tree_kinds", "kr_place_batch", "kr_place_stream", "kr_place_frame", "kr_place_counters",
-    "kr_debug_last_d2h_bytes", "kr_debug_indexed_list", "kr_debug_place_fixed5", "kr_place_text_counters", "kr_place_path_counters", "kr_fastx_open", "kr_fastx_open_at", "kr_fastx_next", "kr_fastx_detach", "kr_fastx_release", "kr_fastx_close", "kr_fastx_parallel_chunks", "kr_fastx_pgz_stats", "kr_format_dist", "kr_debug_fixed5", "kr_free", "kr_host_alloc", "kr_host_free",
+    "kr_debug_last_d2h_bytes", "kr_debug_indexed_list", "kr_debug_acc_paths", "kr_debug_acc_layout", "kr_debug_place_fixed5", "kr_place_text_counters", "kr_place_path_counters", "kr_fastx_open", "kr_fastx_open_at", "kr_fastx_next", "kr_fastx_detach", "kr_fastx_release", "kr_fastx_close", "kr_fastx_parallel_chunks", "kr_fastx_pgz_stats", "kr_format_dist", "kr_debug_fixed5", "kr_free", "kr_host_alloc", "kr_host_free",
     "kr_build_index", "kr_minimizers_cpu", "kr_minimizers_device", "kr_minimizers_free", "kr_last_error", "kr_version",
 ]
+
+# kr_debug_acc_paths: the accumulate kernel's path witnesses, in the order of CounterSlot (kr_dev_common.inc)
+ACC_PATHS = ("fast_entered", "fast_false_early", "fast_compact", "fast_false_compacted", "fast_big_read", "fast_one_batch", "fast_multi_batch",
+             "fast_extra_batches", "fix_dup_calls", "fix_dup_moved", "gen_entered_1", "gen_entered_2", "gen_entered_merge", "gen_fused", "gen_sparse",
+             "gen_big", "gen_extra_batches", "gen_keytab_global", "gen_no_fit", "set_aside", "plane_redo")
 
 _lib = None
 
@@ -154,6 +159,8 @@ def load():
     lib.kr_debug_stream_move.argtypes = [vp, C.c_int]
     lib.kr_debug_stream_addrs.argtypes = [vp, u64p]
     lib.kr_debug_item_placement.argtypes = [vp, u32p, u32p, C.POINTER(C.c_double)]
+    lib.kr_debug_acc_paths.argtypes = [vp, u32p, C.c_uint32]
+    lib.kr_debug_acc_layout.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, u32p]
     lib.kr_index_slot_words.restype = C.c_uint32
     lib.kr_params_default.argtypes = [C.POINTER(KrParams)]
     lib.kr_params_default.restype = None
@@ -493,6 +500,16 @@ class Stream:
         check(self.lib.kr_debug_indexed_list(self.h, C.byref(e), C.byref(f)))
         return int(e.value), int(f.value)
 
+    def acc_paths(self):
+        """(tests) kr_debug_acc_paths: {name: count} of the accumulate kernel's path witnesses for the batch last waited for (a stream
+        created under KR_DEBUG_SKIP=512)"""
+        a = (C.c_uint32 * len(ACC_PATHS))()
+        check(self.lib.kr_debug_acc_paths(self.h, a, len(ACC_PATHS)))
+        return dict(zip(ACC_PATHS, [int(x) for x in a]))
+
+    def acc_layout(self, segs=1, multi=0):
+        return acc_layout(self.params.hdist_th + 1, segs, multi, self)
+
     def collect_device(self):
         rv = KrResultView()
         check(self.lib.kr_batch_collect_device(self.h, C.byref(rv)))
@@ -667,6 +684,14 @@ class Stream:
             self.close()
         except Exception:
             pass
+
+
+def acc_layout(np_planes, segs=1, multi=0, stream=None):
+    """(tests) kr_debug_acc_layout: the event region of an accumulate instantiation; the spill capacities are the stream's (0 without one)"""
+    a = (C.c_uint32 * 8)()
+    check(load().kr_debug_acc_layout(stream.h if stream is not None else None, int(np_planes), int(segs), int(multi), a))
+    assert a[3] == len(ACC_PATHS)
+    return dict(ev_cap=int(a[0]), ev_words=int(a[1]), key_words=int(a[2]), ev_spill=int(a[4]), tab_spill=int(a[5]), kt_spill=int(a[6]))
 
 
 def fasta_chunk_cut(buf):

@@ -25,8 +25,9 @@
 // holds -- in the wave's global scratch (L2): same code, memory operations by pointer type.
 // Statistics of KR_DEBUG_SKIP=512 (tuning only; printed and cleared by kr_batch_wait): [0..31] reads by log2(events + 1), [32..63] by
 // log2(marked keys + 1), [64..95] by log2(records + 1), [96] straight-line epilogue, [97] general epilogue, [98] set aside: events
-// beyond the spill, [99] set aside: the epilogue's tables, [100] sparse, [101] planes in global scratch, [102] fused, [103] key
-// batches beyond the first, [104] key table in global scratch, [110..119] records by min(9, events counted in the record)
+// beyond the spill, [99] set aside: the epilogue's tables, [110..119] records by min(9, events counted in the record)
+// (the paths -- sparse, planes in global scratch, fused, key batches, key table in global scratch -- are counted in the production
+//  build: `witness`, CounterSlot kCtFp* / kCtGe* / kCtRd*)
 // Compiled in with -DKR_STATS=1 only (scripts/build_variant.sh stats -DKR_STATS=1): the extra live values cost the 80-register kernel a spill.
 #ifndef KR_STATS
 #define KR_STATS 0
@@ -37,6 +38,11 @@ __device__ __forceinline__ void stat_records(uint64_t w0, bool on)
 { // one record per lane: w0 = five 8-bit counts
   const uint32_t tot = (uint32_t)(w0 & 255u) + (uint32_t)((w0 >> 8) & 255u) + (uint32_t)((w0 >> 16) & 255u) + (uint32_t)((w0 >> 24) & 255u) + (uint32_t)((w0 >> 32) & 255u);
   if (KR_STATS && on) atomicAdd(&g_kr_stats[110u + min(tot, 9u)], 1u);
+}
+// path witness (KR_DEBUG_SKIP=512; CounterSlot kCtFp* / kCtGe* / kCtRd*): lane 0 counts where the path is entered
+__device__ __forceinline__ void witness(const BatchOut& out, uint32_t dbg, CounterSlot slot, uint32_t n = 1u)
+{
+  if ((dbg & 512u) && lane_id() == 0) atomicAdd(&out.counters[slot], n);
 }
 __device__ __forceinline__ void mem_or(lds_u32* p, uint32_t v) { lds_or(p, v); }
 __device__ __forceinline__ void mem_or(uint32_t* p, uint32_t v) { __hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, KR_SCRATCH_SCOPE); }
@@ -404,15 +410,19 @@ __device__ __forceinline__ bool finalize_events(const DevIndex& ix, const BatchO
       atomicAdd(&g_kr_stats[32u + stat_log2(nkeys)], 1u);
       atomicAdd(&g_kr_stats[64u + stat_log2(nrec)], 1u);
       atomicAdd(&g_kr_stats[97], 1u);
-      if (sparse) atomicAdd(&g_kr_stats[100], 1u);
-      if (big) atomicAdd(&g_kr_stats[101], 1u);
-      if (fused) atomicAdd(&g_kr_stats[102], 1u);
-      if (KB && nkeys > KB) atomicAdd(&g_kr_stats[103], (nkeys + KB - 1) / KB - 1u);
-      if (!kt_lds) atomicAdd(&g_kr_stats[104], 1u);
     }
     if (fits) {
       fits = nrec <= tab_cap + ws.gtab_cap;
       if (nrec > tab_cap) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    }
+    if ((dbg & 512u) && lane == 0) { // path witnesses (all of them here: one at the entry cost the any-threshold instantiation its register allocation)
+      atomicAdd(&out.counters[MERGE ? kCtGeEnteredMerge : (PB == 8 ? kCtGeEntered2 : kCtGeEntered1)], 1u);
+      if (!fits) atomicAdd(&out.counters[kCtGeNoFit], 1u);
+      if (sparse) atomicAdd(&out.counters[kCtGeSparse], 1u);
+      if (big) atomicAdd(&out.counters[kCtGeBig], 1u);
+      if (fused) atomicAdd(&out.counters[kCtGeFused], 1u);
+      if (KB && nkeys > KB) atomicAdd(&out.counters[kCtGeExtraBatches], (nkeys + KB - 1) / KB - 1u);
+      if (!kt_lds) atomicAdd(&out.counters[kCtGeKeytabGlobal], 1u);
     }
     if (fits && !MERGE) {
       const uint32_t rbase = nrec ? alloc_records(out, ws, nrec) : 0u;
@@ -463,7 +473,8 @@ __device__ __forceinline__ bool finalize_events(const DevIndex& ix, const BatchO
 // One position of a key hit twice (finalize_events_fast): the events (rank, strand, position) of vd's group, all in the LDS; the one
 // counted so far carries bit 4.  Count and flag move to an event of the group's smallest hd -- among ALL of the group's events, also
 // those the pass has not reached yet (they will find the bit set and come here, to no effect).  cnt = the key's two counter words.
-__device__ __noinline__ void fix_dup(lds_u32* e, uint32_t nev, uint32_t vd, lds_u32* cnt)
+// Returns whether count and flag moved (a path witness).
+__device__ __noinline__ bool fix_dup(lds_u32* e, uint32_t nev, uint32_t vd, lds_u32* cnt)
 {
   const uint32_t lane = lane_id();
   uint32_t best = 0xFFFFFFFFu, win = 0xFFFFFFFFu; // hd << 16 | event index
@@ -487,6 +498,7 @@ __device__ __noinline__ void fix_dup(lds_u32* e, uint32_t nev, uint32_t vd, lds_
     e[best & 0xFFFFu] |= 16u;
   }
   WAVE_SYNC();
+  return win != 0xFFFFFFFFu && (best >> 16) < (win >> 16); // (wave-uniform) count and flag moved
 }
 
 #ifndef KR_ACC_BIG_READS
@@ -601,7 +613,7 @@ __device__ __forceinline__ bool finalize_events_fast(const DevIndex& ix, const B
 #define KR_ACC_COMPACT_SPILLED 1
 #endif
   const bool spilled = nev > ws.ev_cap; // (wave-uniform) the read's later events lie in the wave's global scratch
-  if (nev == 0 || (spilled && !KR_ACC_COMPACT_SPILLED) || np != 5u) return false;
+  if (nev == 0 || (spilled && !KR_ACC_COMPACT_SPILLED) || np != 5u) return false; // (witnessed by the caller: kCtFpEntered, kCtFpFalseEarly)
   const uint64_t lt = (1ull << lane) - 1ull;
   const uint32_t lim0 = 2u * filt0 + 1u, lim1 = 2u * filt1 + 1u; // u32 wrap keeps "none" = max
   lds_u32* e = ws.ev;
@@ -634,8 +646,9 @@ __device__ __forceinline__ bool finalize_events_fast(const DevIndex& ix, const B
     nkeys += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
   }
   // (keys per batch behind n events: seven words a key -- below)
-  auto batch_keys = [&](uint32_t n) -> uint32_t { n = (n + 3u) & ~3u; return n < ws.ev_words ? ((ws.ev_words - n) / 7u) & ~3u : 0u; };
+  auto batch_keys = [&](uint32_t n) -> uint32_t { n = (n + 3u) & ~3u; return n < ws.ev_words ? ((ws.ev_words - n) / kFastKeyWords) & ~3u : 0u; };
   if (spilled || batch_keys(nev) < nkeys) {
+    witness(out, dbg, kCtFpCompact);
     // Round 5: a read whose events spilled out of the LDS took the general epilogue, every pass of which walks the spilled part
     // through the L2 -- with 512 events in the LDS 31 % of the kernel's time for 7 % of the reads of the 1000-genome index (45 % on
     // the 10,000-genome index: profiles/round5_general_epilogue_ablation.txt).  Two thirds of a read's events belong to keys that
@@ -672,7 +685,11 @@ __device__ __forceinline__ bool finalize_events_fast(const DevIndex& ix, const B
     // this one if they are all in the LDS with the room of a batch of 64 keys behind them
     if (nev > ws.ev_cap || batch_keys(nev) < min(nkeys, 64u)) {
       // (finalize_events zeroes the bitmap itself; it keeps the reads whose live events fill the LDS but do not overflow it)
-      if (!KR_ACC_BIG_READS || nev <= ws.ev_cap || (ws.ev_cap & 127u)) return false;
+      if (!KR_ACC_BIG_READS || nev <= ws.ev_cap || (ws.ev_cap & 127u)) {
+        witness(out, dbg, kCtFpFalseCompacted);
+        return false;
+      }
+      witness(out, dbg, kCtFpBigRead);
       const uint32_t rbase = alloc_records(out, ws, nkeys);
       if (lane == 0) {
         out.rd_off[read] = rbase == 0xFFFFFFFFu ? 0 : rbase;
@@ -694,7 +711,7 @@ __device__ __forceinline__ bool finalize_events_fast(const DevIndex& ix, const B
   // Keys in BATCHES of as many as fit behind the events (seven words a key: its rank, the position map's four, the counters' two)
   // -- one batch for nearly every read; the reads of many keys (the spilled ones above, mostly) pass over their events once per
   // batch, all of it in the LDS, where the general epilogue walked planes of twenty words a key and events in global scratch.
-  constexpr uint32_t kKeyWords = 6u, kWinner = 16u;
+  constexpr uint32_t kKeyWords = kFastKeyWords - 1u /* the rank: keytab */, kWinner = 16u;
   const uint32_t st_off = (nev + 3u) & ~3u;
   uint32_t KB = batch_keys(nev);
   if (KB < 64u && KB < nkeys) { // (the keys of a crowded read that was not compacted: more than 768 events, few keys -- not seen)
@@ -742,9 +759,11 @@ __device__ __forceinline__ bool finalize_events_fast(const DevIndex& ix, const B
       uint64_t dm = __ballot(dup);
       if (dm) { // one position twice for a key (rare)
         WAVE_SYNC();
+        witness(out, dbg, kCtFpDupCalls, (uint32_t)__popcll(dm));
         do {
           const int l = __builtin_ctzll(dm);
-          fix_dup(e, nev, (uint32_t)__builtin_amdgcn_readlane((int)v, l), bt + (uint32_t)__builtin_amdgcn_readlane((int)o, l) * kKeyWords + 4u);
+          if (fix_dup(e, nev, (uint32_t)__builtin_amdgcn_readlane((int)v, l), bt + (uint32_t)__builtin_amdgcn_readlane((int)o, l) * kKeyWords + 4u))
+            witness(out, dbg, kCtFpDupMoved);
           dm &= dm - 1ull;
         } while (dm);
       }
@@ -777,7 +796,10 @@ __device__ __forceinline__ bool finalize_events_fast(const DevIndex& ix, const B
   if (KB < nkeys) { // several batches: the ordinals needed the bitmap to the end
     WAVE_SYNC();
     for (uint32_t q = lane; q < A.bm_words; q += 64) A.bitmap[q] = 0;
-  }
+    witness(out, dbg, kCtFpMultiBatch);
+    witness(out, dbg, kCtFpExtraBatches, (nkeys - 1u) / KB);
+  } else
+    witness(out, dbg, kCtFpOneBatch);
   if (KR_STATS && (dbg & 512u) && lane == 0) { // statistics for tuning: the same counters finalize_events keeps
     atomicAdd(&out.counters[kCtStEvents], nev);
     atomicAdd(&out.counters[kCtStKeys], nkeys);
@@ -852,6 +874,7 @@ __device__ __forceinline__ bool process_read(const DevIndex& ix, const DevParams
     }
     if (lane == 0) out.long_list[ws.ll_next] = read;
     ++ws.ll_next;
+    witness(out, P.dbg, kCtRdSetAside);
   };
   // (PB = 8 takes the reads of two segments only: a one-segment read is on the list because it did not fit the first launch,
   //  and would not fit here either; 8192: tests want the plane tables)
@@ -1004,11 +1027,18 @@ __device__ __forceinline__ bool process_read(const DevIndex& ix, const DevParams
     for (uint32_t w = lane; w < A.bm_words; w += 64) A.rbitmap[w] = 0;
     __syncthreads();
     ws.evmode = false;
+    witness(out, P.dbg, kCtRdPlaneRedo);
     continue;
   }
   if (P.dbg & 16u) ws.nev = 0, ws.ev_full = false;
   if ((P.dbg & 32u) && ws.ev_full) ws.nev = 0, ws.ev_full = false;
   const uint64_t tf0 = (P.dbg & 512u) ? __builtin_readcyclecounter() : 0;
+  // path witnesses: finalize_events_fast is called below, and returns at once (counted here: inside it, or behind the call, they cost
+  // an instantiation its register allocation)
+  if (KR_ACC_FAST_EPILOGUE && !MULTI && PB == 7 && !ws.ev_full && !(P.dbg & ~(2u | 512u)) && (P.dbg & 512u) && lane == 0) {
+    atomicAdd(&out.counters[kCtFpEntered], 1u);
+    if (ws.nev == 0 || A.np != 5u) atomicAdd(&out.counters[kCtFpFalseEarly], 1u);
+  }
   const bool fin_ok = !ws.ev_full && ((KR_ACC_FAST_EPILOGUE && !MULTI && PB == 7 && !(P.dbg & ~(2u | 512u)) && finalize_events_fast(ix, out, A, ws, read, onmers, filt0, filt1, P.dbg)) ||
                                       finalize_events<false, PB>(ix, out, A, ws, hist_tbl, hist_words, read, onmers, filt0, filt1, P.dbg));
   if ((P.dbg & 512u) && lane == 0) {
@@ -1024,6 +1054,7 @@ __device__ __forceinline__ bool process_read(const DevIndex& ix, const DevParams
     return false;
   }
   ws.evmode = false; // does not fit: redo the read with the plane tables
+  witness(out, P.dbg, kCtRdPlaneRedo);
   } // redo loop
   if (!MULTI) return true; // (unreachable: keeps the plane code out of this instantiation)
   // records that pass `hdist_min <= 2*hdist_filt+1` (src/query.cpp:101-106,119), ordered by key so
@@ -1208,17 +1239,9 @@ __global__ __launch_bounds__(kWave, (MULTI || PB == 8 ? 4 : KR_ACC_LEAN_WPE)) vo
   ws.evmode = false;
   ws.nev = 0;
   ws.ev = A.planes; // planes + counts are contiguous: kLdsSlots * np * 5 words
-  ws.ev_words = MULTI ? (uint32_t)kLdsSlots * P.np * (kPlaneWords + 1) : lean_ev_words(P.np, PB == 8 ? 2u : 1u);
-  ws.ev_cap = 64;
-  while (ws.ev_cap * 2 <= ws.ev_words) ws.ev_cap <<= 1;
-  if (ws.ev_cap == ws.ev_words) ws.ev_cap >>= 1;
-  // a small region keeps room for keys and planes -- but not where finalize_events_fast finishes the reads (th = 4): it drops two
-  // thirds of a crowded read's events before it needs the room, and events that need not spill are worth more (round 5: 1,024
-  // events of the 1,216 words instead of 512: 17.1 -> 16.1 ms per 8 M reads, 38.1 -> 36.0 on the 10,000-genome index)
-  if (!MULTI && KR_ACC_LEAN_EV_WORDS && ws.ev_cap * 4u > ws.ev_words * 3u && !(KR_ACC_FAST_EPILOGUE && PB == 7 && P.np == 5u)) ws.ev_cap >>= 1;
-#ifdef KR_ACC_EV_CAP // (experiments: a multiple of 64)
-  if (!MULTI && PB == 7) ws.ev_cap = KR_ACC_EV_CAP;
-#endif
+  const AccLayout lay = acc_layout(P.np, PB == 8 ? 2u : 1u, MULTI);
+  ws.ev_words = lay.ev_words;
+  ws.ev_cap = lay.ev_cap;
   ws.dirty = false;
   ws.gev = A.g_list;
   ws.gev_cap = out.ev_spill;

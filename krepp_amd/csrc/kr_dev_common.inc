@@ -32,6 +32,31 @@ __host__ __device__ inline uint32_t lean_ev_words(uint32_t np, uint32_t segs = 1
   const uint32_t w = KR_ACC_LEAN_EV_WORDS ? (uint32_t)KR_ACC_LEAN_EV_WORDS : (uint32_t)kLdsSlots * np * 5u /* kPlaneWords + 1 */;
   return segs == 1 ? w : (w * (uint32_t)KR_ACC_LEAN2_EV_HALVES / 2u + 3u) & ~3u;
 }
+// Event region of an accumulate instantiation: its words, and how many of them hold events before a read's events spill to the wave's
+// global scratch (the rest: keys, planes, counters).  One function for the kernel and for the host (kr_debug_acc_layout).
+#ifndef KR_ACC_FAST_EPILOGUE
+#define KR_ACC_FAST_EPILOGUE 1
+#endif
+constexpr uint32_t kFastKeyWords = 7u; // finalize_events_fast: words per key of a batch (its rank, the position map's four, the counters' two)
+struct AccLayout {
+  uint32_t ev_words, ev_cap;
+};
+__host__ __device__ inline AccLayout acc_layout(uint32_t np, uint32_t segs, bool multi)
+{
+  AccLayout l;
+  l.ev_words = multi ? (uint32_t)kLdsSlots * np * 5u /* kPlaneWords + 1 */ : lean_ev_words(np, segs);
+  l.ev_cap = 64;
+  while (l.ev_cap * 2 <= l.ev_words) l.ev_cap <<= 1;
+  if (l.ev_cap == l.ev_words) l.ev_cap >>= 1;
+  // a small region keeps room for keys and planes -- but not where finalize_events_fast finishes the reads (th = 4): it drops two
+  // thirds of a crowded read's events before it needs the room, and events that need not spill are worth more (round 5: 1,024
+  // events of the 1,216 words instead of 512: 17.1 -> 16.1 ms per 8 M reads, 38.1 -> 36.0 on the 10,000-genome index)
+  if (!multi && KR_ACC_LEAN_EV_WORDS && l.ev_cap * 4u > l.ev_words * 3u && !(KR_ACC_FAST_EPILOGUE && segs == 1 && np == 5u)) l.ev_cap >>= 1;
+#ifdef KR_ACC_EV_CAP // (experiments: a multiple of 64)
+  if (!multi && segs == 1) l.ev_cap = KR_ACC_EV_CAP;
+#endif
+  return l;
+}
 constexpr int kLdsProbeMax = 8;   // bounded probe sequence of the level-1 table
 constexpr int kMaxPlanes = KR_MAX_HDIST_TH + 1;
 constexpr int kHistWords = (kMaxPlanes + 3) / 4; // packed 8-bit histogram counters
@@ -133,8 +158,34 @@ enum CounterSlot : uint32_t {
   kCtStackSpills = 26,  // work stacks that outgrew the LDS: kr_timing.stack_spills -- sum
   kCtRows = 27,         // output rows (rows_mode) -- lane
   kCtTileHoles = 28,    // records of tiles that became holes (tiled batches) -- sum
-  kCtCount = 29
+  // KR_DEBUG_SKIP=512: path witnesses of the accumulate kernel (kr_debug_acc_paths; tests/test_gpu_acc_paths.py), one count by lane 0
+  // where the path is entered -- all sum.  finalize_events_fast:
+  kCtFpEntered = 29,        // calls
+  kCtFpFalseEarly = 30,     // returned false at once: no events, or a threshold other than 4 (these two counted by process_read)
+  kCtFpCompact = 31,        // compaction entered (events spilled, or more keys than one batch behind the events)
+  kCtFpFalseCompacted = 32, // returned false after the compaction (the live events fill the LDS without overflowing it)
+  kCtFpBigRead = 33,        // finish_big_read
+  kCtFpOneBatch = 34,       // finished in one key batch
+  kCtFpMultiBatch = 35,     // finished in several key batches
+  kCtFpExtraBatches = 36,   // ... key batches beyond the first
+  kCtFpDupCalls = 37,       // fix_dup calls
+  kCtFpDupMoved = 38,       // ... that moved the count to another event
+  // finalize_events:
+  kCtGeEntered1 = 39,       // calls with events, one-segment instantiation
+  kCtGeEntered2 = 40,       // ... two-segment instantiation (PB = 8)
+  kCtGeEnteredMerge = 41,   // ... merge instantiation (once per segment)
+  kCtGeFused = 42,          // planes filled while the ordinals are computed
+  kCtGeSparse = 43,         // planes for the keys with several events only
+  kCtGeBig = 44,            // planes in global scratch
+  kCtGeExtraBatches = 45,   // key batches beyond the first
+  kCtGeKeytabGlobal = 46,   // key table in global scratch
+  kCtGeNoFit = 47,          // returned false: the read does not fit
+  // process_read:
+  kCtRdSetAside = 48,       // reads put on long_list by the one-segment launch
+  kCtRdPlaneRedo = 49,      // reads done again with the plane tables (merge instantiation)
+  kCtCount = 50
 };
+constexpr uint32_t kCtPathFirst = kCtFpEntered, kCtPathCount = kCtCount - kCtFpEntered;
 constexpr uint32_t kCounterWords = (kCtCount + 31u) & ~31u; // words allocated, cleared and copied per lane: whole 128-byte lines
 // Sets of BatchOut::cursors (kCursors * kCursorStride words each, kr_dev_scan.inc): every launch that hands out reads has its own
 enum CursorSet : uint32_t { kCurScan = 0, kCurAcc1 = 1 /* one segment */, kCurAccMerge = 2 /* several */, kCurAcc2 = 3 /* two segments */, kCurSets = 4 };

@@ -1165,7 +1165,12 @@ constexpr CounterRule kCounterRules[] = {
   {kCtStEvents, kSum}, {kCtStKeys, kSum}, {kCtStBatches, kSum}, {kCtStBig, kSum}, {kCtStLevelTiles, kSum}, {kCtStMaxKeys, kMax}, {kCtStMaxEvents, kMax},
   {kCtCycLevel, kSum}, {kCtCycFinalize, kSum}, {kCtCycRead, kSum},
   {kCtProblems, kSum}, {kCtStackSpills, kSum}, {kCtTileHoles, kSum},
+  {kCtFpEntered, kSum}, {kCtFpFalseEarly, kSum}, {kCtFpCompact, kSum}, {kCtFpFalseCompacted, kSum}, {kCtFpBigRead, kSum}, {kCtFpOneBatch, kSum},
+  {kCtFpMultiBatch, kSum}, {kCtFpExtraBatches, kSum}, {kCtFpDupCalls, kSum}, {kCtFpDupMoved, kSum},
+  {kCtGeEntered1, kSum}, {kCtGeEntered2, kSum}, {kCtGeEnteredMerge, kSum}, {kCtGeFused, kSum}, {kCtGeSparse, kSum}, {kCtGeBig, kSum},
+  {kCtGeExtraBatches, kSum}, {kCtGeKeytabGlobal, kSum}, {kCtGeNoFit, kSum}, {kCtRdSetAside, kSum}, {kCtRdPlaneRedo, kSum},
 };
+static_assert(kCtPathCount == 21, "kr_debug_acc_paths: the slot names in krepp_amd/capi.py (ACC_PATHS) follow CounterSlot");
 
 // After a large one-lane batch: how fast did the scan run on the item list in use?  Keep the faster of {the list set aside, the
 // one in use}, and while trials are left put a freshly allocated one in use for the next batch.  KR_ITEM_PLACEMENT_TRIALS
@@ -1277,7 +1282,7 @@ int kr_batch_wait(kr_stream* s)
       row("reads by log2(events+1)", 0, 32);
       row("reads by log2(marked keys+1)", 32, 64);
       row("reads by log2(records+1)", 64, 96);
-      row("paths (0 fast, 1 general, 2 aside:events, 3 aside:tables, 4 sparse, 5 global planes, 6 fused, 7 extra key batches, 8 global key table)", 96, 110);
+      row("paths (0 fast, 1 general, 2 aside:events, 3 aside:tables; the rest: kr_debug_acc_paths)", 96, 100);
       row("records by min(9, events counted)", 110, 120);
     }
   }
@@ -1618,6 +1623,31 @@ int kr_debug_indexed_list(kr_stream* s, uint64_t* extent, uint64_t* fallbacks)
   if (!s) return kr::fail(KR_ERR_ARG, "kr_debug_indexed_list: null argument");
   if (extent) *extent = s->ix_extent;
   if (fallbacks) *fallbacks = s->ix_fallbacks;
+  return KR_OK;
+}
+
+// (tests) The accumulate kernel's path witnesses of the batch last waited for (KR_DEBUG_SKIP=512; CounterSlot kCtFp* .. kCtRd*, summed
+// over the lanes): the first min(n, 21) of them into out.  Returns KR_OK.
+int kr_debug_acc_paths(kr_stream* s, uint32_t* out, uint32_t n)
+{
+  kr::clear_error();
+  if (!s || !out) return kr::fail(KR_ERR_ARG, "kr_debug_acc_paths: null argument");
+  if (!s->waited) return kr::fail(KR_ERR_STATE, "kr_debug_acc_paths: wait for a batch first");
+  for (uint32_t i = 0; i < std::min(n, kCtPathCount); ++i) out[i] = s->h_counters[kCtPathFirst + i];
+  return KR_OK;
+}
+
+// (tests, no device needed unless `s` is given) The event region of the accumulate instantiation for np = hdist_th + 1 planes, reads of
+// `segs` (1, 2) segments or the merge instantiation (multi): out8 = {events in the LDS before a read's events spill (ev_cap), words of
+// the region (ev_words), words per key of a batch of finalize_events_fast, number of path witnesses, events / passing-key table
+// entries / keys a wave's global scratch holds for `s` (0 without a stream), 0}
+int kr_debug_acc_layout(const kr_stream* s, uint32_t np, uint32_t segs, uint32_t multi, uint32_t* out8)
+{
+  kr::clear_error();
+  if (!out8 || np == 0 || np > (uint32_t)kMaxPlanes || segs < 1 || segs > 2) return kr::fail(KR_ERR_ARG, "kr_debug_acc_layout: bad argument");
+  const AccLayout l = acc_layout(np, segs, multi != 0);
+  out8[0] = l.ev_cap, out8[1] = l.ev_words, out8[2] = kFastKeyWords, out8[3] = kCtPathCount;
+  out8[4] = s ? s->out.ev_spill : 0u, out8[5] = s ? s->out.tab_spill : 0u, out8[6] = s ? s->out.kt_spill : 0u, out8[7] = 0;
   return KR_OK;
 }
 

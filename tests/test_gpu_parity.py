@@ -240,12 +240,13 @@ def test_long_reads_and_ragged_batches(capi, po, toy, toy_genomes):
 def test_overflow_path_many_leaves(capi, po, synth, tmp_path, monkeypatch, slot_log2w, dbg):
     """150-bp reads with k = 21 have 130 k-mer positions = two segments.  With debug bit 8192 they take the
     plane tables, and reads that reach more (strand, leaf) pairs than the LDS table holds go on to the
-    global-memory accumulators; without it every segment runs in event mode and the segments are merged through
-    the global count table.  Results must not change.  The table is dense (18 entries per bucket): scanned through
+    global-memory accumulators; without it the two-segment instantiation of the single-segment layout finishes them in event
+    mode (no merge through the global count table: that is for reads of three segments and more).  Results must not change,
+    and the path witnesses (KR_DEBUG_SKIP bit 512) say which of the two ran.  The table is dense (18 entries per bucket): scanned through
     the packed arrays ("0"), 128-byte slots (30 entries: some buckets continue in the packed array) and 256-byte
     slots."""
     monkeypatch.setenv("KR_SLOT_LOG2W", slot_log2w)
-    monkeypatch.setenv("KR_DEBUG_SKIP", dbg)
+    monkeypatch.setenv("KR_DEBUG_SKIP", str(int(dbg) + 512))  # (512: the kernel counts the paths it enters, Stream.acc_paths)
     n = 96
     names = [f"s{i}" for i in range(n)]
     # star-ish tree of close relatives: every read matches nearly every genome
@@ -265,6 +266,12 @@ def test_overflow_path_many_leaves(capi, po, synth, tmp_path, monkeypatch, slot_
     st.submit(bases, offs, capi.KR_TAP_ACCS)
     res = st.collect()
     assert (st.timing().overflow_reads > 50) == (dbg == "8192")
+    paths = st.acc_paths()
+    assert paths["set_aside"] == 400 and paths["fast_entered"] == paths["gen_entered_1"] == 0  # every read has two segments
+    if dbg == "8192":  # the plane tables did all of them
+        assert paths["gen_entered_2"] == paths["gen_entered_merge"] == 0
+    else:  # the two-segment instantiation did every read that has events
+        assert 0 < paths["gen_entered_2"] <= len(set(ref["hits"]["read"].tolist())) and paths["gen_entered_merge"] == paths["plane_redo"] == 0
     acc = ref["accs"][ref["accs"]["passed"] == 1]
     want = sorted(zip(acc["read"].tolist(), ((acc["se"] << 1) | acc["strand"]).tolist(), [tuple(x[:5]) for x in acc["hist"].tolist()]))
     got = sorted(zip(res.rec_read.tolist(), res.rec_key.tolist(), [tuple(x) for x in res.rec_hist.tolist()]))
@@ -295,9 +302,11 @@ def test_overflow_path_many_leaves(capi, po, synth, tmp_path, monkeypatch, slot_
                                           ("0", 1200, 200)])
 def test_single_segment_many_leaves_spill_paths(capi, po, synth, tmp_path, monkeypatch, dbg, n, length):
     """150-bp reads (one 128-position segment: event mode) against 160 close relatives: thousands of events and
-    hundreds of (leaf, strand) keys per read -> events spill to global scratch, the epilogue runs several plane
-    batches (or, forced by the debug bit, the single batch in global scratch; or, with event mode off, the
-    level-1/level-2 plane tables), the passing-key table spills.  Histograms must be bit-exact in every mode.
+    hundreds of (leaf, strand) keys per read -> events spill to global scratch; the straight-line epilogue compacts them and
+    finishes most reads from planes in global scratch (finish_big_read), some in several key batches, and hands a few to the
+    general epilogue, which runs several plane batches (or, forced by the debug bit, the general epilogue's single batch in
+    global scratch for every read; or, with event mode off, the level-1/level-2 plane tables).  Histograms must be bit-exact
+    in every mode, and the path witnesses (KR_DEBUG_SKIP bit 512) say that these paths ran.
     250-bp reads (222 positions = two segments) take the two-segment instantiation of the single-segment layout
     (8 position bits per event, 256-bit planes, 16-bit counters) through the same spill paths; against 1,200 relatives a
     200-bp read has 1,200 keys and ~50,000 events: events, key table and passing-key table all live in the wave's global scratch."""
@@ -314,12 +323,25 @@ def test_single_segment_many_leaves_spill_paths(capi, po, synth, tmp_path, monke
     nreads = 300 if n == 160 else 120
     bases, offs, rn = synth.sample_reads(g, nreads, seed=9, length=length)
     ref = ox.dist(bases, offs, rn, po.params(collect=7))
-    monkeypatch.setenv("KR_DEBUG_SKIP", dbg)
+    monkeypatch.setenv("KR_DEBUG_SKIP", str(int(dbg) + 512))  # (512: the kernel counts the paths it enters, Stream.acc_paths)
     st = dx.stream(max_reads=nreads, max_bases=len(bases), max_records=nreads * 2 * n)
     st.submit(bases, offs, capi.KR_TAP_ACCS)
     res = st.collect()
     acc = ref["accs"][ref["accs"]["passed"] == 1]
     assert len(acc) > nreads * (100 if n == 160 else 1000)  # the point of the test: many keys per read
+    paths = st.acc_paths()
+    if length == 150 and dbg == "0":
+        assert paths["fast_entered"] == nreads and paths["fast_compact"] > 0 and paths["fast_big_read"] > 0  # events spilled
+        assert paths["fast_multi_batch"] + paths["gen_extra_batches"] > 0 and paths["set_aside"] == 0
+    elif length == 150 and dbg == "2048":
+        assert paths["fast_entered"] == 0 and paths["gen_entered_1"] > 0 and paths["gen_big"] > 0 and paths["set_aside"] == 0
+    elif dbg == "8":
+        assert paths["set_aside"] == nreads and paths["gen_entered_1"] == paths["gen_entered_2"] == paths["gen_entered_merge"] == 0
+    else:  # two segments
+        assert paths["set_aside"] == nreads and paths["gen_entered_2"] > 0 and paths["gen_entered_merge"] == paths["plane_redo"] == 0
+        assert paths["gen_big"] > 0 if (dbg == "2048" or n == 1200) else paths["gen_extra_batches"] > 0
+        if n == 1200:
+            assert paths["gen_keytab_global"] > 0
     want = sorted(zip(acc["read"].tolist(), ((acc["se"] << 1) | acc["strand"]).tolist(), [tuple(x[:5]) for x in acc["hist"].tolist()]))
     got = sorted(zip(res.rec_read.tolist(), res.rec_key.tolist(), [tuple(x) for x in res.rec_hist.tolist()]))
     assert got == want
@@ -367,7 +389,7 @@ def test_report_modes_on_reads_of_many_records(capi, po, synth, tmp_path, n):
 
 def test_many_leaves_bitmap_spans_several_tiles(capi, po, synth, tmp_path):
     """2,300 references: 4,600 (leaf, strand) keys = 72 bitmap blocks, more than one 64-lane tile of the ordinal
-    prefix, and level-2 / merge lists longer than a wave (the 10k-genome configuration in the small)."""
+    prefix (the 10k-genome configuration in the small).  The path witnesses (KR_DEBUG_SKIP bit 512) say which instantiation ran."""
     n = 2300
     nwk = synth.yule_newick(n, 5)
     g = synth.evolve_genomes(nwk, 1500, seed=31)
@@ -378,12 +400,21 @@ def test_many_leaves_bitmap_spans_several_tiles(capi, po, synth, tmp_path):
     hx = capi.HostIndex(idx)
     dx = hx.upload(0)
     ox = po.Index(idx)
-    for length, seed in ((150, 3), (260, 4)):  # one segment (event mode), two segments (merged through the count table)
+    for length, seed in ((150, 3), (260, 4)):  # one segment (the straight-line epilogue), two segments (the two-segment instantiation)
         bases, offs, rn = synth.sample_reads(g, 400, seed=seed, length=length)
         ref = ox.dist(bases, offs, rn, po.params(collect=7))
-        st = dx.stream(max_reads=400, max_bases=len(bases), max_records=400 * 2 * n)
+        os.environ["KR_DEBUG_SKIP"] = "512"  # (the kernel counts the paths it enters, Stream.acc_paths)
+        try:
+            st = dx.stream(max_reads=400, max_bases=len(bases), max_records=400 * 2 * n)
+        finally:
+            del os.environ["KR_DEBUG_SKIP"]
         st.submit(bases, offs, capi.KR_TAP_ACCS)
         res = st.collect()
+        paths = st.acc_paths()
+        if length == 150:
+            assert paths["fast_entered"] == 400 and paths["fast_one_batch"] > 0 and paths["set_aside"] == 0
+        else:
+            assert paths["set_aside"] == 400 and paths["gen_entered_2"] > 0 and paths["gen_entered_merge"] == 0
         acc = ref["accs"][ref["accs"]["passed"] == 1]
         want = sorted(zip(acc["read"].tolist(), ((acc["se"] << 1) | acc["strand"]).tolist(), [tuple(x[:5]) for x in acc["hist"].tolist()]))
         got = sorted(zip(res.rec_read.tolist(), res.rec_key.tolist(), [tuple(x) for x in res.rec_hist.tolist()]))
@@ -459,13 +490,20 @@ def test_large_clade_colours_spill_the_work_stack(capi, po, synth, tmp_path):
         acc = ref["accs"][ref["accs"]["passed"] == 1]
         want = sorted(zip(acc["read"].tolist(), ((acc["se"] << 1) | acc["strand"]).tolist(), [tuple(x[:5]) for x in acc["hist"].tolist()]))
         assert len(want) > nreads * 800  # most reads reach most of the tree
-        os.environ["KR_DEBUG_SKIP"] = dbg
+        os.environ["KR_DEBUG_SKIP"] = str(int(dbg) + 512)  # (512: the kernel counts the paths it enters, Stream.acc_paths)
         try:
             st = dx.stream(max_reads=nreads, max_bases=len(bases), max_records=nreads * 2 * n + 4096)
             st.submit(bases, offs, capi.KR_TAP_ACCS)
             res = st.collect()
         finally:
             del os.environ["KR_DEBUG_SKIP"]
+        paths = st.acc_paths()
+        if dbg == "0" and length == 150:  # whole clades reached by one k-mer: live events beyond the LDS
+            assert paths["fast_entered"] > 0 and paths["fast_big_read"] > 0
+        elif dbg == "0":  # three segments: the merge instantiation
+            assert paths["set_aside"] == nreads and paths["gen_entered_merge"] > 0 and paths["gen_entered_2"] == 0
+        else:  # the plane tables
+            assert paths["set_aside"] == nreads and paths["gen_entered_1"] == paths["gen_entered_2"] == paths["gen_entered_merge"] == 0
         got = sorted(zip(res.rec_read.tolist(), res.rec_key.tolist(), [tuple(x) for x in res.rec_hist.tolist()]))
         assert got == want, (length, dbg)
         assert_rows_close(res.rows(), rows_of_oracle(ref))
