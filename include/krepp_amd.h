@@ -604,6 +604,27 @@ KR_API int kr_place_batch(const kr_host_index*, const kr_index*, const kr_place_
 KR_API int kr_place_stream(const kr_host_index*, const kr_index*, const kr_place_tree*, kr_stream* s, uint32_t nreads,
                            const uint64_t* offsets, const char* const* names, const kr_params* p, int tabular,
                            int* has_previous, char** text, uint64_t* len, kr_placement** placements, uint64_t* nplacements);
+/* The same for the batch that kr_batch_submit_fastq or kr_batch_submit_fasta queued last on `s`: reads given as raw file bytes are
+ * placed without a host array of offsets, names or lengths.  The submit must have carried KR_TAP_ACCS (KR_TILE_DEVICE may be added:
+ * long records are tiled on the device, the caller's reads are placed) and accepted at least one record.  nreads, the offsets and
+ * the names are the stream's own: the reads' lengths are taken from the record finder's offsets and their ids are gathered from the
+ * chunk, both by kernels on the stream, behind the batch; the output is byte for byte, and placement record for placement record,
+ * what kr_place_stream gives for the same reads under the same names.
+ *   raw    the pointer given to that submit; it stays valid through this call and is read only where the HOST formats: the whole
+ *          batch on the host back end, a range whose device text is not used (KR_PLACE_HOST_TEXT, a text flag, `placements`
+ *          wanted with rows).  Only those paths copy the offsets or the names' (position, length) pairs back; with device text
+ *          (tabular 0 or 1, no placements) the call reads back one number more than kr_place_stream: the ids' total, which sizes
+ *          the id and text buffers exactly.
+ * The chunk, the names' positions and lengths and the offsets stay in HBM, untouched, from the submit to the stream's next submit
+ * (the tiling kernels of KR_TILE_DEVICE and a batch run again by kr_batch_wait write none of them).
+ * KR_ERR_STATE: the last submit on `s` was not a raw-bytes submit, accepted no record (nothing was queued), or lacked KR_TAP_ACCS;
+ * KR_ERR_ARG: a null argument (`placements` / `nplacements` may be null); KR_ERR_CAPACITY: as kr_place_stream, or 4 GB of ids. */
+KR_API int kr_place_stream_parsed(const kr_host_index*, const kr_index*, const kr_place_tree*, kr_stream* s, const uint8_t* raw,
+                                  const kr_params* p, int tabular, int* has_previous, char** text, uint64_t* len,
+                                  kr_placement** placements, uint64_t* nplacements);
+/* tests: the reads' ids as the device laid them out for the stream's last kr_place_stream_parsed call that wrote text on the device:
+ * id_off [nreads + 1] (id_off[0] = 0), ids [id_off[nreads]] back to back.  KR_ERR_STATE after any other place call. */
+KR_API int kr_debug_place_ids(kr_stream*, char* ids, uint32_t* id_off);
 /* How many kr_place_stream batches of this process ran their back end on the device, and how many were sent whole to the
  * host back end (kr_place_batch: a placement tree that is not numbered in post-order, KR_PLACE_HOST set, or a batch that ran
  * out of candidate slots); heavy_reads: reads with more leaves / distinct ancestors than kr_place_kernel's LDS arrays hold

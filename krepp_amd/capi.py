@@ -102,7 +102,7 @@ EXPORTS = [
     "kr_stream_fastq_enable", "kr_batch_submit_fastq", "kr_batch_submit_fasta", "kr_fasta_chunk_cut", "kr_batch_fastq_names", "kr_debug_fastq_batch", "kr_debug_fastq_parse_ms", "kr_debug_tile_layout", "kr_debug_tile_shape", "kr_batch_hits", "kr_batch_readtaps",
     "kr_debug_front_end", "kr_debug_stream_move", "kr_debug_stream_addrs", "kr_debug_item_placement", "kr_debug_brent", "kr_debug_prefix", "kr_debug_colour_classes", "kr_llh_batch", "kr_llh_eval_indexed", "kr_batch_timing",
     "kr_place_tree_create", "kr_place_tree_create_lineage", "kr_place_tree_nnodes", "kr_place_summary_add",
-    "kr_place_summary_text", "kr_place_tree_free", "kr_place_tree_kinds", "kr_place_batch", "kr_place_stream", "kr_place_frame", "kr_place_counters",
+    "kr_place_summary_text", "kr_place_tree_free", "kr_place_tree_kinds", "kr_place_batch", "kr_place_stream", "kr_place_stream_parsed", "kr_debug_place_ids", "kr_place_frame", "kr_place_counters",
     "kr_debug_last_d2h_bytes", "kr_debug_indexed_list", "kr_debug_acc_paths", "kr_debug_acc_layout", "kr_debug_place_fixed5", "kr_place_text_counters", "kr_place_path_counters", "kr_fastx_open", "kr_fastx_open_at", "kr_fastx_next", "kr_fastx_detach", "kr_fastx_release", "kr_fastx_close", "kr_fastx_parallel_chunks", "kr_fastx_pgz_stats", "kr_format_dist", "kr_debug_fixed5", "kr_free", "kr_host_alloc", "kr_host_free",
     "kr_build_index", "kr_minimizers_cpu", "kr_minimizers_device", "kr_minimizers_free", "kr_last_error", "kr_version",
 ]
@@ -198,6 +198,9 @@ def load():
                                    C.POINTER(C.c_int), C.POINTER(vp), u64p, C.POINTER(vp), u64p]
     lib.kr_place_stream.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, C.POINTER(C.c_char_p), C.POINTER(KrParams), C.c_int,
                                     C.POINTER(C.c_int), C.POINTER(vp), u64p, C.POINTER(vp), u64p]
+    lib.kr_place_stream_parsed.argtypes = [vp, vp, vp, vp, vp, C.POINTER(KrParams), C.c_int, C.POINTER(C.c_int), C.POINTER(vp), u64p,
+                                           C.POINTER(vp), u64p]
+    lib.kr_debug_place_ids.argtypes = [vp, vp, vp]
     lib.kr_place_frame.argtypes = [vp, C.c_int, C.c_int, C.c_char_p, C.c_uint64, C.POINTER(vp), u64p]
     lib.kr_place_counters.argtypes = [u64p, u64p, u64p]
     lib.kr_place_counters.restype = None
@@ -631,6 +634,16 @@ class Stream:
         q = np.ctypeslib.as_array(ln, shape=(n,))
         return [self._raw[int(a):int(a) + int(b)].decode("latin-1") for a, b in zip(p, q)]
 
+    def place_ids(self):
+        """(tests) kr_debug_place_ids: the reads' ids as the device laid them out for the last kr_place_stream_parsed call on this
+        stream (Placer.place_parsed with device text), as a list of bytes"""
+        n = self._fq_nreads
+        id_off = np.zeros(n + 1, np.uint32)
+        ids = np.zeros(max(1, len(self._raw)), np.uint8)  # (the names are pieces of the chunk)
+        check(self.lib.kr_debug_place_ids(self.h, ids.ctypes.data, id_off.ctypes.data))
+        assert id_off[0] == 0
+        return [ids[int(id_off[i]):int(id_off[i + 1])].tobytes() for i in range(n)]
+
     def fastq_batch(self, summary):
         """(tests) the accepted records' sequences as the record finder wrote them (kr_debug_fastq_batch)"""
         offs = np.zeros(summary["nreads"] + 1, np.uint64)
@@ -950,6 +963,29 @@ class Placer:
         self.lib.kr_free(txt)
         self.lib.kr_free(pls)
         return text, pl
+
+    def place_parsed(self, raw, fasta=False, flags=0, want_placements=True, at_eof=1):
+        """One batch given as raw FASTQ (fasta=True: FASTA) bytes: kr_batch_submit_fastq / _fasta with KR_TAP_ACCS | flags on a
+        page-locked copy of `raw`, then kr_place_stream_parsed.  The first call runs kr_stream_fastq_enable for chunks of up to
+        max(len(raw), 1 MB) bytes.  Returns (text, placements, summary): the accepted prefix of the chunk is placed, and
+        summary["consumed"] says where the next submit starts."""
+        if not getattr(self, "_fq_on", False):
+            self.st.fastq_enable(max(len(raw), 1 << 20))
+            self._fq_on = True
+        submit = self.st.submit_fasta if fasta else self.st.submit_fastq
+        summ = submit(raw, KR_TAP_ACCS | flags, at_eof)
+        txt, ln, pls, npl = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
+        check(self.lib.kr_place_stream_parsed(self.hx.h, self.dx.h, self.pt, self.st.h, self.st._pinned, C.byref(self.popts), int(self.tabular),
+                                              C.byref(self.prev), C.byref(txt), C.byref(ln), C.byref(pls) if want_placements else None,
+                                              C.byref(npl) if want_placements else None))
+        text = C.string_at(txt, ln.value).decode()
+        pl = (np.frombuffer(C.string_at(pls, npl.value * PLACEMENT_DT.itemsize), dtype=PLACEMENT_DT).copy()
+              if npl.value else np.zeros(0, PLACEMENT_DT))
+        if int(self.tabular) == 2:
+            check(self.lib.kr_place_summary_add(self.pt, pls, npl.value, self.wcount.ctypes.data, C.byref(self.twcount)))
+        self.lib.kr_free(txt)
+        self.lib.kr_free(pls)
+        return text, pl, summ
 
     def summary(self):
         txt, ln = C.c_void_p(), C.c_uint64()

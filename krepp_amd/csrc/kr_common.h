@@ -221,6 +221,19 @@ void place_device_abort(kr_stream* s);
 // the first place_device_launch.  names: the batch's read ids; tabular 0 = jplace rows, 1 = tabular rows.  Off again at the next
 // place_device_begin.
 int place_device_text_begin(kr_stream* s, const PlaceTreeArrays& T, const char* const* names, uint32_t nreads, int tabular, bool multi);
+// The same two for the batch that kr_batch_submit_fastq / kr_batch_submit_fasta queued last on `s` (kr_place_stream_parsed): the
+// reads' lengths and ids are laid out by kernels from what the record finder left in HBM (kr_dev_place_parsed.inc), no host array
+// is read.  want_ids: place_device_text_begin_parsed follows.  KR_ERR_STATE unless such a batch, with KR_TAP_ACCS, is the stream's last.
+int place_device_begin_parsed(kr_stream* s, const void* tree_tag, const PlaceTreeArrays& T, bool want_ids);
+int place_device_text_begin_parsed(kr_stream* s, const PlaceTreeArrays& T, int tabular, bool multi);
+// ... and what the host formatters need of it, copied back on demand: the state check alone, the reads accepted (0: no such
+// batch), offsets[nreads + 1]
+// Every kr_place_stream / kr_place_stream_parsed call opens with this, whichever back end it ends at: the ids an earlier call laid
+// out on the device are no longer what kr_debug_place_ids may show.
+void place_call_begin(kr_stream* s);
+int place_parsed_check(const kr_stream* s);
+uint32_t place_parsed_nreads(const kr_stream* s);
+int place_parsed_offsets(kr_stream* s, uint64_t* offsets);
 // Which of the back end's recovery paths ran (kr_place_path_counters, krepp_amd.h: the order of its values): counted where they are
 // taken, in place_device_finish and kr_place_stream.
 enum PlacePath : uint32_t {

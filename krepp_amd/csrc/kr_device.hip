@@ -48,13 +48,14 @@
 //   kr_dev_fastq.inc       FASTQ records found in a chunk of raw file bytes (kr_batch_submit_fastq)
 //   kr_dev_fasta.inc       FASTA records found in a chunk of raw file bytes, every pass parallel over bytes (kr_batch_submit_fasta)
 //   kr_dev_place.inc       back end of `place`: ancestor accumulation, candidates, their likelihoods (kr_place_kernel)
+//   kr_dev_place_parsed.inc  read lengths and ids of a batch the record finders queued, for the place kernels (kr_place_stream_parsed)
 //   kr_dev_debug.inc       debug / tap kernels and the re-layout kernels of kr_index_upload
 // and the host side of the device ABI:
 //   kr_host_index.inc      kr_index: kr_index_upload / export / import / free, kr_index_broadcast (RCCL)
 //   kr_host_stream.inc     kr_stream: lanes, kr_stream_create, kr_batch_submit / wait / collect / timing
 //   kr_host_fastq.inc      kr_stream_fastq_enable, kr_batch_submit_fastq, kr_batch_fastq_names
 //   kr_host_fasta.inc      kr_batch_submit_fasta
-//   kr_host_place.inc      kr::place_on_device (launch of the place kernels for kr_place_stream)
+//   kr_host_place.inc      kr::place_on_device (launch of the place kernels for kr_place_stream and kr_place_stream_parsed)
 //   (below, in this file)  kr_host_alloc, debug entry points, kr_llh_batch, kr_llh_eval_indexed
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -93,6 +94,7 @@ namespace {
 #include "kr_dev_fastq.inc"
 #include "kr_dev_fasta.inc"
 #include "kr_dev_place.inc"
+#include "kr_dev_place_parsed.inc"
 #include "kr_dev_debug.inc"
 
 // ---------------------------------------------------------------------------

@@ -1,4 +1,5 @@
-// kr_host_place.inc -- part of kr_device.hip (host side): kr::place_on_device, the launch of the place kernels for kr_place_stream.
+// kr_host_place.inc -- part of kr_device.hip (host side): kr::place_on_device, the launch of the place kernels for kr_place_stream
+// and, for a batch the record finders queued, kr_place_stream_parsed (the _parsed entry points; kernels: kr_dev_place_parsed.inc).
 
 namespace {
 // Growth of the place workspace.  place_renew: a new block whatever the buffer holds; place_grow: when n exceeds its size;
@@ -63,9 +64,12 @@ int kr::place_on_device(kr_stream* s, const void* tree_tag, const kr::PlaceTreeA
   return kr::place_device_finish(s, T, 0, s->nreads, tau, no_filter, chisq, 0, out);
 }
 
-int kr::place_device_begin(kr_stream* s, const void* tree_tag, const kr::PlaceTreeArrays& T, const uint32_t* read_len)
+namespace {
+// What place_device_begin and place_device_begin_parsed share: the wait for the front end, the tree, the workspaces -- everything but
+// the reads' lengths in d_len, which the caller queues behind it on lane 0's stream.
+int place_begin_common(kr_stream* s, const void* tree_tag, const kr::PlaceTreeArrays& T)
 {
-  if (!s || !read_len || !T.parent || !T.eff || !T.elig || !T.lo || !T.idx_to_pt || !T.depth) return kr::fail(KR_ERR_ARG, "place_on_device: null argument");
+  if (!s || !T.parent || !T.eff || !T.elig || !T.lo || !T.idx_to_pt || !T.depth) return kr::fail(KR_ERR_ARG, "place_on_device: null argument");
   if (!s->submitted || !(s->flags & KR_TAP_ACCS))
     return kr::fail(KR_ERR_STATE, "place: the batch must be submitted with KR_TAP_ACCS (the back end reads every record's histogram)");
   static const bool timing0 = getenv("KR_PLACE_TIMING") != nullptr;
@@ -158,8 +162,70 @@ int kr::place_device_begin(kr_stream* s, const void* tree_tag, const kr::PlaceTr
     }
   }
   lap("workspaces");
+  return KR_OK;
+}
+
+// The batch a record finder queued last on the stream, as kr_place_stream_parsed needs it (krepp_amd.h: the state errors)
+int place_parsed_state(const kr_stream* s)
+{
+  if (!s->fq.on || !s->fq.parsed) return kr::fail(KR_ERR_STATE, "kr_place_stream_parsed: the last submit on the stream was not kr_batch_submit_fastq / kr_batch_submit_fasta");
+  if (!s->fq.nreads || !s->submitted || s->nreads != s->fq.nreads) return kr::fail(KR_ERR_STATE, "kr_place_stream_parsed: the last submit accepted no record (nothing was queued)");
+  if (!(s->flags & KR_TAP_ACCS)) return kr::fail(KR_ERR_STATE, "kr_place_stream_parsed: the batch must be submitted with KR_TAP_ACCS (the back end reads every record's histogram)");
+  return KR_OK;
+}
+
+PlaceParsedIO place_parsed_io(kr_stream* s)
+{
+  kr_stream::PlaceWs& w = s->pw;
+  return PlaceParsedIO{s->d_offsets, s->fq.d_raw, s->fq.d_npos, s->fq.d_nlen, s->nreads, w.d_len.get(), w.d_idbsum.get(), w.d_id_off.get(), w.d_ids.get()};
+}
+} // namespace
+
+int kr::place_device_begin(kr_stream* s, const void* tree_tag, const kr::PlaceTreeArrays& T, const uint32_t* read_len)
+{
+  if (!read_len) return kr::fail(KR_ERR_ARG, "place_on_device: null argument");
+  if (s) s->pw.ids_queued = false, s->pw.ids_reads = 0; // (the ids of this batch, if any, are the host's staging)
+  const int rc = place_begin_common(s, tree_tag, T);
+  if (rc) return rc;
+  kr_stream::PlaceWs& w = s->pw;
+  const uint32_t n = s->nreads;
   memcpy(w.h_len.get(), read_len, (uint64_t)n * 4);
-  HIP_TRY(hipMemcpyAsync(w.d_len.get(), w.h_len.get(), (uint64_t)n * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(w.d_len.get(), w.h_len.get(), (uint64_t)n * 4, hipMemcpyHostToDevice, s->lanes[0].stream));
+  return KR_OK;
+}
+
+// The same for the batch that kr_batch_submit_fastq / kr_batch_submit_fasta queued last on the stream: the reads' lengths come from
+// the record finder's offsets, on the device (kr_pp_len_kernel).  want_ids: the offsets of the reads' ids too (the three prefix-sum
+// steps over the names' lengths), queued BEFORE the front end is waited for, so that their total is on the host when that wait
+// returns -- place_device_text_begin_parsed sizes d_ids and d_text from it.
+// Whose buffers: d_raw, d_npos and d_nlen (kr_stream::Fastq) are written by fq_begin's copy and the record finder's kernels only, and
+// d_offsets by the record finder and by a host batch's copy in submit_batch only; build_tiles_device reads bases and offsets and
+// writes the Tiles' own arrays, a batch that kr_batch_wait runs again is submitted from d_bases / d_offsets as they lie, and the
+// place kernels touch none of the four: they hold the parsed batch until the stream's next submit.
+int kr::place_device_begin_parsed(kr_stream* s, const void* tree_tag, const kr::PlaceTreeArrays& T, bool want_ids)
+{
+  if (!s) return kr::fail(KR_ERR_ARG, "place_on_device: null argument");
+  int rc = place_parsed_state(s);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  kr_stream::PlaceWs& w = s->pw;
+  hipStream_t st = s->lanes[0].stream;
+  const uint32_t n = s->nreads, nblk = n / kPpBlock + 1u;
+  w.ids_queued = false, w.ids_reads = 0;
+  if (want_ids) {
+    if ((uint64_t)n + 1 > w.d_id_off.size() && (rc = place_grow_all((uint64_t)n + n / 4 + 16, w.d_id_off, w.h_id_off))) return rc;
+    if ((rc = place_grow(w.d_idbsum, (uint64_t)nblk + nblk / 4 + 2)) || (rc = place_grow(w.h_idtot, 2))) return rc;
+    const PlaceParsedIO io = place_parsed_io(s);
+    hipLaunchKernelGGL(kr_pp_idsum_kernel, dim3(std::min<uint32_t>(nblk, 4096u)), dim3(256), 0, st, io);
+    hipLaunchKernelGGL(kr_pp_idscan_kernel, dim3(1), dim3(1024), 0, st, io);
+    hipLaunchKernelGGL(kr_pp_idoff_kernel, dim3(std::min<uint32_t>(nblk, 4096u)), dim3(256), 0, st, io);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(w.h_idtot.get(), w.d_idbsum.get() + nblk, 8, hipMemcpyDeviceToHost, st));
+    w.ids_queued = true;
+  }
+  if ((rc = place_begin_common(s, tree_tag, T))) return rc;
+  hipLaunchKernelGGL(kr_pp_len_kernel, dim3(std::min<uint32_t>((n + 255u) / 256u, 4096u)), dim3(256), 0, st, place_parsed_io(s));
+  HIP_TRY(hipGetLastError());
   return KR_OK;
 }
 
@@ -329,12 +395,12 @@ int kr::place_device_finish(kr_stream* s, const kr::PlaceTreeArrays& T, uint32_t
 
 uint32_t kr::place_stream_nreads(const kr_stream* s) { return s ? s->nreads : 0; }
 
-int kr::place_device_text_begin(kr_stream* s, const kr::PlaceTreeArrays& T, const char* const* names, uint32_t nreads, int tabular, bool multi)
+namespace {
+// What place_device_text_begin and place_device_text_begin_parsed share.  place_text_tree: the tree's part of the text on the device;
+// place_text_rooms: what is sized by the batch once its ids (`total` bytes of them) are placed, and the switch itself.
+int place_text_tree(kr_stream* s, const kr::PlaceTreeArrays& T)
 {
-  if (!s || !names || !T.blen || !T.card || !T.labels || !T.label_off) return kr::fail(KR_ERR_ARG, "place_device_text_begin: null argument");
   kr_stream::PlaceWs& w = s->pw;
-  HIP_TRY(hipSetDevice(s->device));
-  hipStream_t st = s->lanes[0].stream;
   int rc = 0;
   if (w.text_tree_tag != w.tree_tag || !w.d_blen.get()) { // the tree's branch lengths, subtree sizes and labels (once per tree)
     const uint64_t n1 = (uint64_t)T.pn + 1;
@@ -347,6 +413,33 @@ int kr::place_device_text_begin(kr_stream* s, const kr::PlaceTreeArrays& T, cons
     if (lb) HIP_TRY(hipMemcpy(w.d_labels.get(), T.labels, lb, hipMemcpyHostToDevice));
     w.text_tree_tag = w.tree_tag;
   }
+  return KR_OK;
+}
+int place_text_rooms(kr_stream* s, uint32_t nreads, uint64_t total, int tabular, bool multi)
+{
+  kr_stream::PlaceWs& w = s->pw;
+  int rc = 0;
+  // per-read lengths, block sums, the text itself: room for the ids and 512 bytes of rows a read (a range with more comes back
+  // with flag 2 and is formatted by the host)
+  if (nreads > w.d_tlen.size() && (rc = place_grow(w.d_tlen, (uint64_t)nreads + nreads / 4 + 16))) return rc;
+  if ((rc = place_grow(w.d_tbsum, w.d_tlen.size() / kPlTextBlock + 4)) || (rc = place_grow_all(2, w.d_ttotal, w.h_ttotal))) return rc; // (the block sums: sized by the lengths' array)
+  const uint64_t want = std::max<uint64_t>(w.dbg_text ? w.dbg_text : total + (uint64_t)nreads * 512ull + (1u << 20), w.text_want_min); // (text_want_min: what a range that outgrew the buffer asked for)
+  if ((rc = place_grow(w.d_text, want))) return rc;
+  if (nreads > w.d_rtotal.size() && (rc = place_grow_all((uint64_t)nreads + nreads / 4 + 16, w.d_rtotal, w.d_rbest))) return rc;
+  w.text_tabular = tabular ? 1u : 0u, w.text_multi = multi ? 1u : 0u;
+  w.text_on = true;
+  return place_size_candidates(s, w.d_cse.size()); // (the sorted copy of the kept candidates: sized with them, now and when a range is run again)
+}
+} // namespace
+
+int kr::place_device_text_begin(kr_stream* s, const kr::PlaceTreeArrays& T, const char* const* names, uint32_t nreads, int tabular, bool multi)
+{
+  if (!s || !names || !T.blen || !T.card || !T.labels || !T.label_off) return kr::fail(KR_ERR_ARG, "place_device_text_begin: null argument");
+  kr_stream::PlaceWs& w = s->pw;
+  HIP_TRY(hipSetDevice(s->device));
+  hipStream_t st = s->lanes[0].stream;
+  int rc = place_text_tree(s, T);
+  if (rc) return rc;
   // the reads' ids back to back (lengths and copies by the host pool: 400,000 names are 400,000 pointers to chase)
   if ((uint64_t)nreads + 1 > w.d_id_off.size() && (rc = place_grow_all((uint64_t)nreads + nreads / 4 + 16, w.d_id_off, w.h_id_off))) return rc;
   const int nt = std::max(1, std::min(std::min(kr::parallel_width(), 16), (int)(nreads / 8192)));
@@ -363,7 +456,8 @@ int kr::place_device_text_begin(kr_stream* s, const kr::PlaceTreeArrays& T, cons
   for (int t = 0; t < nt; ++t) part[(size_t)t + 1] += part[(size_t)t];
   const uint64_t total = part[(size_t)nt];
   if (total >= 0xFFFFFFF0ull) return kr::fail(KR_ERR_CAPACITY, "place: more than 4 GB of read ids in one batch");
-  if (total + 16 > w.d_ids.size() && (rc = place_grow_all(total + total / 4 + 4096, w.d_ids, w.h_ids))) return rc;
+  // (the smaller of the two: a parsed batch grows d_ids alone)
+  if (total + 16 > std::min(w.d_ids.size(), w.h_ids.size()) && (rc = place_grow_all(total + total / 4 + 4096, w.d_ids, w.h_ids))) return rc;
   w.h_id_off.get()[0] = 0;
   kr::parallel_for(nt, [&](int t) {
     uint64_t at = part[(size_t)t];
@@ -376,16 +470,65 @@ int kr::place_device_text_begin(kr_stream* s, const kr::PlaceTreeArrays& T, cons
   });
   HIP_TRY(hipMemcpyAsync(w.d_id_off.get(), w.h_id_off.get(), ((uint64_t)nreads + 1) * 4, hipMemcpyHostToDevice, st));
   if (total) HIP_TRY(hipMemcpyAsync(w.d_ids.get(), w.h_ids.get(), total, hipMemcpyHostToDevice, st));
-  // per-read lengths, block sums, the text itself: room for the ids and 512 bytes of rows a read (a range with more comes back
-  // with flag 2 and is formatted by the host)
-  if (nreads > w.d_tlen.size() && (rc = place_grow(w.d_tlen, (uint64_t)nreads + nreads / 4 + 16))) return rc;
-  if ((rc = place_grow(w.d_tbsum, w.d_tlen.size() / kPlTextBlock + 4)) || (rc = place_grow_all(2, w.d_ttotal, w.h_ttotal))) return rc; // (the block sums: sized by the lengths' array)
-  const uint64_t want = std::max<uint64_t>(w.dbg_text ? w.dbg_text : total + (uint64_t)nreads * 512ull + (1u << 20), w.text_want_min); // (text_want_min: what a range that outgrew the buffer asked for)
-  if ((rc = place_grow(w.d_text, want))) return rc;
-  if (nreads > w.d_rtotal.size() && (rc = place_grow_all((uint64_t)nreads + nreads / 4 + 16, w.d_rtotal, w.d_rbest))) return rc;
-  w.text_tabular = tabular ? 1u : 0u, w.text_multi = multi ? 1u : 0u;
-  w.text_on = true;
-  return place_size_candidates(s, w.d_cse.size()); // (the sorted copy of the kept candidates: sized with them, now and when a range is run again)
+  return place_text_rooms(s, nreads, total, tabular, multi);
+}
+
+// The same for a batch begun with place_device_begin_parsed(want_ids): the ids' offsets are in d_id_off already and their total is on
+// the host (the front end has been waited for behind them); d_ids and d_text are sized from it, and the copy kernel is queued.
+int kr::place_device_text_begin_parsed(kr_stream* s, const kr::PlaceTreeArrays& T, int tabular, bool multi)
+{
+  if (!s || !T.blen || !T.card || !T.labels || !T.label_off) return kr::fail(KR_ERR_ARG, "place_device_text_begin: null argument");
+  int rc = place_parsed_state(s);
+  if (rc) return rc;
+  kr_stream::PlaceWs& w = s->pw;
+  HIP_TRY(hipSetDevice(s->device));
+  hipStream_t st = s->lanes[0].stream;
+  if (!w.ids_queued) return kr::fail(KR_ERR_STATE, "place_device_text_begin: place_device_begin_parsed did not lay out the ids");
+  if ((rc = place_text_tree(s, T))) return rc;
+  HIP_TRY(hipStreamSynchronize(st)); // (at once as a rule: kr_batch_wait has waited for this stream behind the total's copy)
+  const uint32_t nreads = s->nreads;
+  const uint64_t total = w.h_idtot.get()[0];
+  if (total >= 0xFFFFFFF0ull) return kr::fail(KR_ERR_CAPACITY, "place: more than 4 GB of read ids in one batch");
+  if (total + 16 > w.d_ids.size() && (rc = place_grow(w.d_ids, total + total / 4 + 4096))) return rc; // (d_ids alone: no id is staged on the host, nothing is page-locked for them)
+  hipLaunchKernelGGL(kr_pp_idcopy_kernel, dim3(std::max<uint32_t>(1u, std::min<uint32_t>((nreads + 15u) / 16u, 8192u))), dim3(256), 0, st, place_parsed_io(s));
+  HIP_TRY(hipGetLastError());
+  w.ids_reads = nreads;
+  return place_text_rooms(s, nreads, total, tabular, multi);
+}
+
+// The host's side of a parsed batch, asked for only by the paths that format on the host: the caller's offsets, and the accepted
+// records' names as (position in the chunk, length) -- kr_batch_fastq_names.
+int kr::place_parsed_offsets(kr_stream* s, uint64_t* offsets)
+{
+  if (!s || !offsets) return kr::fail(KR_ERR_ARG, "place_parsed_offsets: null argument");
+  const int rc = place_parsed_state(s);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  hipStream_t st = s->lanes[0].stream;
+  HIP_TRY(hipMemcpyAsync(offsets, s->d_offsets, ((uint64_t)s->nreads + 1) * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return KR_OK;
+}
+void kr::place_call_begin(kr_stream* s)
+{
+  if (s) s->pw.ids_queued = false, s->pw.ids_reads = 0;
+}
+uint32_t kr::place_parsed_nreads(const kr_stream* s) { return s && s->fq.on && s->fq.parsed && s->submitted && s->nreads == s->fq.nreads ? s->fq.nreads : 0; }
+int kr::place_parsed_check(const kr_stream* s) { return s ? place_parsed_state(s) : kr::fail(KR_ERR_ARG, "kr_place_stream_parsed: null argument"); }
+
+extern "C" int kr_debug_place_ids(kr_stream* s, char* ids, uint32_t* id_off)
+{
+  kr::clear_error();
+  if (!s || !ids || !id_off) return kr::fail(KR_ERR_ARG, "kr_debug_place_ids: null argument");
+  kr_stream::PlaceWs& w = s->pw;
+  if (!w.ids_reads) return kr::fail(KR_ERR_STATE, "kr_debug_place_ids: the stream's last place call was not a kr_place_stream_parsed that laid out ids on the device");
+  HIP_TRY(hipSetDevice(s->device));
+  hipStream_t st = s->lanes[0].stream;
+  HIP_TRY(hipMemcpyAsync(id_off, w.d_id_off.get(), ((uint64_t)w.ids_reads + 1) * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (id_off[w.ids_reads]) HIP_TRY(hipMemcpyAsync(ids, w.d_ids.get(), id_off[w.ids_reads], hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return KR_OK;
 }
 void kr::place_device_abort(kr_stream* s)
 {

@@ -119,6 +119,12 @@ struct kr_stream {
     DevBuf<char> d_text;
     PinBuf<char> h_text;
     uint64_t text_want_min = 0;
+    // a batch the record finders queued (kr_place_stream_parsed; kr_dev_place_parsed.inc): the block sums of the names' lengths
+    // and, page-locked, their total; ids_reads: reads whose ids the device laid out in d_ids / d_id_off for the last such call
+    DevBuf<uint64_t> d_idbsum;
+    PinBuf<uint64_t> h_idtot;
+    uint32_t ids_reads = 0;
+    bool ids_queued = false; // this batch's place_device_begin_parsed queued the id offsets and their total (want_ids)
     DevBuf<uint32_t> d_sse, d_rbest; // the kept candidates sorted by node (same slots as d_kse ...), per-read --no-multi choice
     DevBuf<double> d_sd, d_sv, d_sc, d_rtotal;
     // KR_DEBUG_PLACE_CAPS (tests; place_device_begin reads it per batch): what the kernels are told the candidate slots, the kept

@@ -930,27 +930,68 @@ int kr_place_batch(const kr_host_index* hx, const kr_index* dix, const kr_place_
   return emit_placements(pt, rv->nreads, src, names, p, tabular, has_previous, text, len, placements, nplacements, lap);
 }
 
-// As kr_place_batch, for the batch last submitted on `s` with KR_TAP_ACCS, which need not be collected: the tree
-// aggregation, the Brent minimisations of the internal candidates and the chi-squares run on the device
-// (kr_place_kernel) on the records where they lie; what comes back is the candidates (node, d, v, chi-square), and the
-// host does the last phase only (filter, exp / LWR, Jukes-Cantor, text).  Bit-identical to kr_place_batch.  Reads
-// beyond the kernel's LDS arrays (256 leaves / 1024 ancestors) are done by its second launch with the arrays in global
-// scratch; only a placement tree whose numbering is not post-order (or a batch that runs out of candidate slots) sends
-// the whole batch through kr_place_batch.
-int kr_place_stream(const kr_host_index* hx, const kr_index* dix, const kr_place_tree* pt, kr_stream* s, uint32_t nreads,
-                    const uint64_t* offsets, const char* const* names, const kr_params* p, int tabular, int* has_previous, char** text,
-                    uint64_t* len, kr_placement** placements, uint64_t* nplacements)
+namespace {
+// The host's view of the batch kr_place_stream's body works on.  kr_place_stream: the caller's arrays.  kr_place_stream_parsed (a
+// batch the record finders queued from `raw`): nothing until a path that formats on the host asks for it -- then the offsets come
+// back from the stream and the names are cut out of the chunk, NUL-terminated, by kr_batch_fastq_names' (position, length) pairs.
+struct StreamBatch {
+  kr_stream* s = nullptr;
+  uint32_t nreads = 0;
+  const uint64_t* offsets = nullptr;
+  const char* const* names = nullptr;
+  const uint8_t* raw = nullptr; // the chunk of a parsed batch, else null
+  const char* who = "kr_place_stream";
+  std::vector<uint64_t> own_offsets;
+  std::string blob;
+  std::vector<const char*> own_names;
+  bool parsed() const { return raw != nullptr; }
+  int need_offsets()
+  {
+    if (offsets || !parsed()) return KR_OK;
+    own_offsets.resize((size_t)nreads + 1);
+    const int rc = kr::place_parsed_offsets(s, own_offsets.data());
+    if (!rc) offsets = own_offsets.data();
+    return rc;
+  }
+  int need_names()
+  {
+    if (names || !parsed()) return KR_OK;
+    const uint64_t* np = nullptr;
+    const uint32_t* nl = nullptr;
+    const int rc = kr_batch_fastq_names(s, &np, &nl);
+    if (rc) return rc;
+    uint64_t total = 0;
+    for (uint32_t r = 0; r < nreads; ++r) total += (uint64_t)nl[r] + 1;
+    blob.resize(total);
+    own_names.resize(nreads);
+    uint64_t at = 0;
+    for (uint32_t r = 0; r < nreads; ++r) {
+      own_names[r] = blob.data() + at;
+      memcpy(&blob[at], raw + np[r], nl[r]);
+      at += nl[r];
+      blob[at++] = 0;
+    }
+    names = own_names.data();
+    return KR_OK;
+  }
+};
+
+// The body of kr_place_stream and kr_place_stream_parsed: the entry points check their arguments and say where the batch's read
+// lengths, ids and host-side names come from (StreamBatch); everything else is one code.
+int place_stream_run(const kr_host_index* hx, const kr_index* dix, const kr_place_tree* pt, kr_stream* s, StreamBatch& B, const kr_params* p,
+                     int tabular, int* has_previous, char** text, uint64_t* len, kr_placement** placements, uint64_t* nplacements)
 {
-  kr::clear_error();
-  if (!hx || !dix || !pt || !s || !offsets || !p || !has_previous || !text || !len || !nreads)
-    return kr::fail(KR_ERR_ARG, "kr_place_stream: null argument");
+  const uint32_t nreads = B.nreads;
+  const std::string who = B.who;
+  kr::place_call_begin(s);
   auto host_path = [&]() -> int {
     g_place_host_batches.fetch_add(1, std::memory_order_relaxed);
     kr_result_view rv;
     int rc = kr_batch_collect(s, &rv);
     if (rc) return rc;
-    if (rv.nreads != nreads) return kr::fail(KR_ERR_ARG, "kr_place_stream: nreads does not match the submitted batch");
-    return kr_place_batch(hx, dix, pt, &rv, offsets, names, p, tabular, has_previous, text, len, placements, nplacements);
+    if (rv.nreads != nreads) return kr::fail(KR_ERR_ARG, who + ": nreads does not match the submitted batch");
+    if ((rc = B.need_offsets()) || (rc = B.need_names())) return rc;
+    return kr_place_batch(hx, dix, pt, &rv, B.offsets, B.names, p, tabular, has_previous, text, len, placements, nplacements);
   };
   if (!pt->postorder || getenv("KR_PLACE_HOST")) return host_path();
   const bool timing = getenv("KR_PLACE_TIMING") != nullptr;
@@ -963,10 +1004,11 @@ int kr_place_stream(const kr_host_index* hx, const kr_index* dix, const kr_place
     t_mark = now;
   };
   const int nt = std::max(1, std::min(std::min(kr::parallel_width(), 32), (int)(nreads / 4096)));
-  std::vector<uint32_t> read_len(nreads);
-  kr::parallel_for(nt, [&](int t) {
-    for (size_t r = (size_t)nreads * t / nt; r < (size_t)nreads * (t + 1) / nt; ++r) read_len[r] = (uint32_t)(offsets[r + 1] - offsets[r]);
-  });
+  std::vector<uint32_t> read_len(B.parsed() ? 0 : nreads); // (a parsed batch: kr_pp_len_kernel, from the offsets in HBM)
+  if (!B.parsed())
+    kr::parallel_for(nt, [&](int t) {
+      for (size_t r = (size_t)nreads * t / nt; r < (size_t)nreads * (t + 1) / nt; ++r) read_len[r] = (uint32_t)(B.offsets[r + 1] - B.offsets[r]);
+    });
   kr::PlaceTreeArrays T;
   T.pn = pt->t.nnodes(), T.nidx = (uint32_t)pt->idx_to_pt.size() - 1;
   T.parent = pt->parent_arr.data(), T.eff = pt->eff.data(), T.elig = pt->elig.data(), T.lo = pt->lo.data(), T.idx_to_pt = pt->idx_to_pt.data(), T.depth = pt->depth.data();
@@ -978,16 +1020,16 @@ int kr_place_stream(const kr_host_index* hx, const kr_index* dix, const kr_place
   // Round 6: jplace and tabular rows are written on the DEVICE, where the placements are (kr_dev_place.inc), when the caller wants
   // text and no placement records (the CLI's text modes): the candidates stay in HBM, the range's text comes back as bytes, and
   // with no last phase on the host there is nothing for a second range to hide.  KR_PLACE_HOST_TEXT=1: the host's last phase.
-  const bool dev_text = (tabular == 0 || tabular == 1) && !(placements && nplacements) && names && pt->card.size() == (size_t)T.pn + 1 && !getenv("KR_PLACE_HOST_TEXT");
+  const bool dev_text = (tabular == 0 || tabular == 1) && !(placements && nplacements) && (B.names || B.parsed()) && pt->card.size() == (size_t)T.pn + 1 && !getenv("KR_PLACE_HOST_TEXT");
   if (dev_text) T.blen = pt->blen_arr.data(), T.card = pt->card.data(), T.labels = pt->label_blob.data(), T.label_off = pt->label_off.data();
   uint32_t nranges = (nreads >= 131072u && !dev_text) ? 2u : 1u;
   if (const char* e = getenv("KR_PLACE_RANGES")) nranges = (uint32_t)std::max(1, std::min(16, atoi(e)));
   nranges = std::min<uint32_t>(nranges, std::max<uint32_t>(1u, nreads));
-  int rc = kr::place_device_begin(s, pt, T, read_len.data());
+  int rc = B.parsed() ? kr::place_device_begin_parsed(s, pt, T, dev_text) : kr::place_device_begin(s, pt, T, read_len.data());
   if (rc) return rc;
-  if (kr::place_stream_nreads(s) != nreads) return kr::fail(KR_ERR_ARG, "kr_place_stream: nreads does not match the submitted batch");
+  if (kr::place_stream_nreads(s) != nreads) return kr::fail(KR_ERR_ARG, who + ": nreads does not match the submitted batch");
   auto r_of = [&](uint32_t k) { return (uint32_t)((uint64_t)nreads * k / nranges); };
-  if (dev_text && (rc = kr::place_device_text_begin(s, T, names, nreads, tabular, p->multi != 0))) return rc;
+  if (dev_text && (rc = B.parsed() ? kr::place_device_text_begin_parsed(s, T, tabular, p->multi != 0) : kr::place_device_text_begin(s, T, B.names, nreads, tabular, p->multi != 0))) return rc;
   lap("front end waited for, workspaces");
   if ((rc = kr::place_device_launch(s, T, 0, r_of(1), p->tau, p->no_filter != 0, p->chisq))) return rc;
   struct Piece { char* text = nullptr; uint64_t len = 0; kr_placement* pl = nullptr; uint64_t npl = 0; };
@@ -1028,7 +1070,7 @@ int kr_place_stream(const kr_host_index* hx, const kr_index* dix, const kr_place
       Piece& pcd = pieces[k];
       pcd.text = (char*)kr::big_alloc(tl + 1);
       if (!pcd.text) {
-        rc = kr::fail(KR_ERR_NOMEM, "kr_place_stream: out of memory");
+        rc = kr::fail(KR_ERR_NOMEM, who + ": out of memory");
         break;
       }
       const int sl = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)std::min(kr::parallel_width(), 16), tl >> 20));
@@ -1058,7 +1100,8 @@ int kr_place_stream(const kr_host_index* hx, const kr_index* dix, const kr_place
       }
     } src{res};
     Piece& pc = pieces[k];
-    rc = emit_placements(pt, r1 - r0, src, names, p, tabular, &prev, &pc.text, &pc.len, placements ? &pc.pl : nullptr, nplacements ? &pc.npl : nullptr, lap, r0);
+    if (tabular != 2 && (rc = B.need_names())) break; // (a parsed batch: the names the host formats with, made here and only here)
+    rc = emit_placements(pt, r1 - r0, src, B.names, p, tabular, &prev, &pc.text, &pc.len, placements ? &pc.pl : nullptr, nplacements ? &pc.npl : nullptr, lap, r0);
   }
   if (rc) {
     drop();
@@ -1084,7 +1127,7 @@ int kr_place_stream(const kr_host_index* hx, const kr_index* dix, const kr_place
     if (!buf || ((placements && nplacements) && !pb)) {
       kr::big_free(buf), kr::big_free(pb);
       drop();
-      return kr::fail(KR_ERR_NOMEM, "kr_place_stream: out of memory");
+      return kr::fail(KR_ERR_NOMEM, who + ": out of memory");
     }
     std::vector<uint64_t> at(nranges + 1, 0), pat(nranges + 1, 0);
     for (uint32_t k = 0; k < nranges; ++k) at[k + 1] = at[k] + pieces[k].len, pat[k + 1] = pat[k] + pieces[k].npl;
@@ -1104,6 +1147,43 @@ int kr_place_stream(const kr_host_index* hx, const kr_index* dix, const kr_place
   }
   *has_previous = prev;
   return KR_OK;
+}
+
+} // namespace
+
+// As kr_place_batch, for the batch last submitted on `s` with KR_TAP_ACCS, which need not be collected: the tree
+// aggregation, the Brent minimisations of the internal candidates and the chi-squares run on the device
+// (kr_place_kernel) on the records where they lie; what comes back is the candidates (node, d, v, chi-square), and the
+// host does the last phase only (filter, exp / LWR, Jukes-Cantor, text).  Bit-identical to kr_place_batch.  Reads
+// beyond the kernel's LDS arrays (256 leaves / 1024 ancestors) are done by its second launch with the arrays in global
+// scratch; only a placement tree whose numbering is not post-order (or a batch that runs out of candidate slots) sends
+// the whole batch through kr_place_batch.
+int kr_place_stream(const kr_host_index* hx, const kr_index* dix, const kr_place_tree* pt, kr_stream* s, uint32_t nreads,
+                    const uint64_t* offsets, const char* const* names, const kr_params* p, int tabular, int* has_previous, char** text,
+                    uint64_t* len, kr_placement** placements, uint64_t* nplacements)
+{
+  kr::clear_error();
+  if (!hx || !dix || !pt || !s || !offsets || !p || !has_previous || !text || !len || !nreads)
+    return kr::fail(KR_ERR_ARG, "kr_place_stream: null argument");
+  StreamBatch B;
+  B.s = s, B.nreads = nreads, B.offsets = offsets, B.names = names;
+  return place_stream_run(hx, dix, pt, s, B, p, tabular, has_previous, text, len, placements, nplacements);
+}
+
+// As kr_place_stream, for the batch that kr_batch_submit_fastq / kr_batch_submit_fasta queued last on `s` from `raw` (KR_TAP_ACCS,
+// with or without KR_TILE_DEVICE): nreads, the offsets and the names are the stream's own, and on the device-text path nothing of
+// them is touched by the host.  The same bytes and placement records as kr_place_stream for the same reads under the same names.
+int kr_place_stream_parsed(const kr_host_index* hx, const kr_index* dix, const kr_place_tree* pt, kr_stream* s, const uint8_t* raw,
+                           const kr_params* p, int tabular, int* has_previous, char** text, uint64_t* len, kr_placement** placements,
+                           uint64_t* nplacements)
+{
+  kr::clear_error();
+  if (!hx || !dix || !pt || !s || !raw || !p || !has_previous || !text || !len) return kr::fail(KR_ERR_ARG, "kr_place_stream_parsed: null argument");
+  const int rc = kr::place_parsed_check(s);
+  if (rc) return rc;
+  StreamBatch B;
+  B.s = s, B.nreads = kr::place_parsed_nreads(s), B.raw = raw, B.who = "kr_place_stream_parsed";
+  return place_stream_run(hx, dix, pt, s, B, p, tabular, has_previous, text, len, placements, nplacements);
 }
 
 void kr_place_text_counters(uint64_t* device_ranges, uint64_t* fallback_ranges)

@@ -90,11 +90,14 @@ static void print_help(const std::string& sub)
            "  -l, --lineage-file PATH    place on the taxonomy of a Greengenes/GTDB style lineage file\n"
            "      --tau N                highest Hamming distance counted by the placement threshold [2]\n"
            "      --filter / --no-filter [filter]\n"
-           "      --tabular              tab-separated rows instead of jplace\n",
+           "      --tabular              tab-separated rows instead of jplace\n"
+           "      --gpu-parse            FASTA/FASTQ records found on the GPU (identical output; plain files, others keep the host reader)\n",
            query_opts, index_query_opts);
   if (sub.empty() || sub == "seek")
     printf("\nkrepp seek -i SKETCH -q READS: distance of every read to the one sketched reference\n"
-           "  -i, --sketch-path PATH     sketch file (as written by `krepp sketch`)\n%s", query_opts);
+           "  -i, --sketch-path PATH     sketch file (as written by `krepp sketch`)\n%s"
+           "      --gpu-parse            FASTA/FASTQ records found on the GPU (identical output; plain files, others keep the host reader)\n",
+           query_opts);
   if (sub.empty() || sub == "index")
     printf("\nkrepp index -i MAP.tsv -o DIR: build an index (reference ID <tab> FASTA path per line)\n"
            "  -t, --nwk-file PATH        rooted guide tree (default: a balanced tree over the IDs)\n%s"
@@ -326,12 +329,15 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
   int workers_ready = 0;
   std::vector<kr_stream*> streams_to_free;
   kr_fastx* fx = nullptr; // (opened before the workers start; they hand batches back to it)
-  // --gpu-parse (`dist` only, plain regular files): the reader only moves bytes into page-locked chunks cut at guessed record starts;
+  // --gpu-parse (plain regular files): the reader only moves bytes into page-locked chunks cut at guessed record starts;
   // each worker finds the records of its chunks on its GPU (kr_batch_submit_fastq / kr_batch_submit_fasta with KR_TILE_DEVICE: long records are tiled on the
   // device).  The first chunk that stops early (a record that is not clean four-line FASTQ, a wrong cut, a batch that overflows) names the byte where the host reader
   // (kr_fastx_open_at) takes over for good; chunks behind it were handed out already and are dropped unwritten (their sequence
   // numbers are skipped by the writer, in order), as the pool reader's "first surprise -> sequential to the end" (kr_host.cpp).
-  bool gpu_parse = !place && !seek && a.flag.count("--gpu-parse") && a.flag.at("--gpu-parse");
+  // `place`: the batch is queued with KR_TAP_ACCS and placed where it lies (kr_place_stream_parsed: lengths and ids from the chunk, on
+  // the device); `seek`: queued with no flag, collected, and formatted with the names cut out of the chunk.  Their rows go through
+  // the job's text and the writer, as the host reader's do.
+  bool gpu_parse = a.flag.count("--gpu-parse") && a.flag.at("--gpu-parse");
   // A file whose first byte is '>' is cut and parsed as FASTA (kr_fasta_chunk_cut, kr_batch_submit_fasta); any other as FASTQ.
   int qfd = -1;
   uint64_t qsize = 0;
@@ -592,11 +598,41 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
           kr_fastq_parse fp;
           auto t_dev = now();
           // (KR_TILE_DEVICE: a long record stays with the device, tiled there; KR_TILE_ROWS: and its batch's text is the device's too)
-          const uint32_t pflags = (text_on ? KR_TILE_ROWS : KR_ROWS_ONLY) | KR_TILE_DEVICE;
+          const uint32_t pflags = place ? (KR_TAP_ACCS | KR_TILE_DEVICE) : seek ? 0u : ((text_on ? KR_TILE_ROWS : KR_ROWS_ONLY) | KR_TILE_DEVICE);
           int rc = j->fasta ? kr_batch_submit_fasta(st, j->raw + pos, j->raw_len - pos, pflags, j->closed ? 1u : 0u, &fp)
                             : kr_batch_submit_fastq(st, j->raw + pos, j->raw_len - pos, pflags, j->at_eof ? 1u : 0u, &fp);
           if (rc) return rc;
-          if (fp.nreads) {
+          if (fp.nreads && (place || seek)) {
+            char* txt = nullptr;
+            uint64_t len = 0;
+            kr_result_view rv;
+            if (seek) rc = kr_batch_collect(st, &rv);
+            ns_dev += since(t_dev);
+            auto t_fmt = now();
+            if (!rc && seek) rc = names_of(j->raw + pos, fp.nreads);
+            if (!rc && seek) rc = kr_format_seek(hx, dix[g], &rv, p.hdist_th, nptr.data(), &txt, &len);
+            if (!rc && place) {
+              int prev = (!tabular && !text.empty()) ? 1 : 0; // (submits of a chunk are joined here, chunks by the writer)
+              kr_placement* pp = nullptr;
+              uint64_t npp = 0;
+              rc = kr_place_stream_parsed(hx, dix[g], ptree, st, j->raw + pos, &p, tabular, &prev, &txt, &len, tabular == 2 ? &pp : nullptr,
+                                          tabular == 2 ? &npp : nullptr);
+              for (uint64_t i = 0; !rc && i < npp; ++i) { // (`read`: the number within the chunk; the chunk's first read is known when its turn comes)
+                pp[i].read = (uint32_t)(nr_job + pp[i].read);
+                pls.push_back(pp[i]);
+              }
+              kr_free(pp);
+            }
+            if (!rc && txt) text.append(txt, len);
+            kr_free(txt);
+            ns_fmt += since(t_fmt);
+            if (rc == KR_ERR_CAPACITY) { // more records than a batch holds: the host reader takes over at this batch's first record
+              fell = true;
+              break;
+            }
+            if (rc) return rc;
+            nr_job += fp.nreads;
+          } else if (fp.nreads) {
             const char* dtext = nullptr;
             uint64_t dlen = 0;
             kr_result_view rv;
@@ -653,9 +689,15 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
         std::unique_lock<std::mutex> lk(mu);
         if (!my_turn) cv_done.wait(lk, [&] { return next_seq == j->seq || !worker_err.empty(); });
         my_turn = true;
-        if (fb_seq < j->seq) return 0;
+        if (fb_seq < j->seq) {
+          text.clear(), pls.clear(); // (`place` / `seek`: rows made before the earlier chunk's stop was known)
+          return 0;
+        }
         for (size_t q = 0; q < wc_job.size(); ++q) wc_local[q] += wc_job[q];
         tw_local += tw_job;
+        // place --summarize sums per 512 reads by global read number: every chunk in front of this one has had its turn
+        j->first_read = nreads_dev, j->n = (size_t)nr_job;
+        for (kr_placement& x : pls) x.read = (uint32_t)(j->first_read + x.read);
         nreads_dev += nr_job;
         if (fell) fb_seq = j->seq, fb_off = j->raw_off + pos;
         return 0;
@@ -726,7 +768,7 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
       if (tabular == 2) {
         const uint32_t end_group = (uint32_t)(j->first_read + j->n) >> 9;
         carry.insert(carry.end(), j->pls.begin(), j->pls.end());
-        size_t cut = carry.size();
+        size_t cut = j->n ? carry.size() : 0; // (--gpu-parse: a chunk that was dropped, or stopped at its first record, has no reads and no last group)
         if ((j->first_read + j->n) & 511u)
           while (cut > 0 && (carry[cut - 1].read >> 9) == end_group) --cut;
         if (kr_place_summary_add(ptree, carry.data(), cut, pwcount.data(), &ptwcount)) {
@@ -823,6 +865,7 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
       cv_done.wait(lk, [&] { return gpu_done == gpu_issued || !worker_err.empty(); });
     }
     close(qfd);
+    nreads_total = nreads_dev; // (the host reader, if it takes over, numbers its reads behind the device's: place --summarize)
     if (fb_seq != UINT64_MAX && worker_err.empty()) {
       if (kr_fastx_open_at(a.get("--query").c_str(), fb_off, &fx)) error_exit(kr_last_error());
     }
@@ -893,7 +936,6 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
   ready_watch.join();
   writer.join();
   if (!worker_err.empty()) error_exit(worker_err);
-  nreads_total += nreads_dev; // (--gpu-parse: the records found on the device)
   if (summarize && !place) // src/krepp.cpp:388-393 (ascending colour id instead of hash-map order)
     for (uint32_t se = 0; se < wcount.size(); ++se)
       if (wcount[se] != 0) fprintf(out, "%s\t%.5f\t%.5f\n", kr_host_index_node_name(hx, se), wcount[se], wcount[se] / twcount);
