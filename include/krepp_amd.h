@@ -667,6 +667,8 @@ typedef struct kr_build_params {
   const uint8_t* ppos;          /* optional explicit LSH positions [h] (descending)    */
   uint32_t gpu_minimizers;      /* 1: leaf stage (window minimizers) on the GPU `device`; */
   int32_t device;               /*    identical output, checked by tests/test_minimizers.py */
+  uint32_t sdust_t, sdust_w;    /* --sdust-t / --sdust-w (src/krepp.cpp:530-531,576-577): both > 0 keeps the sdust intervals  */
+                                /* of every contig out of the minimizer windows (src/rqseq.cpp:71-107); either 0: off    */
 } kr_build_params;
 KR_API int kr_build_index(const char* input_tsv, const char* nwk_path /*may be NULL*/, const char* out_dir,
                           const kr_build_params*);
@@ -691,6 +693,18 @@ KR_API int kr_minimizers_cpu(const kr_build_params*, const uint8_t* bases, const
 KR_API int kr_minimizers_device(int device, const kr_build_params*, const uint8_t* bases, const uint64_t* offsets,
                                 uint32_t ncontigs, kr_minimizer_result* out);
 KR_API void kr_minimizers_free(kr_minimizer_result*);
+
+/* The masker on its own: per contig the list that the reference's sdust(0, seq, -1, T, W, &n) (src/sdust.h) returns, element for
+ * element: intervals[offsets[c] .. offsets[c+1]) = (start << 32 | finish), finish exclusive.  Its alphabet is sdust's own (bytes
+ * 0..3 and ACGTacgt are bases); an interval may cover non-bases and, behind one, reach up to W bases past the contig's end, as
+ * the reference's do.  T > 0, W >= 4, contigs below 2^31 bases. */
+typedef struct kr_sdust_result {
+  uint64_t* intervals;
+  uint64_t* offsets; /* [ncontigs + 1] */
+  uint32_t ncontigs;
+} kr_sdust_result;
+KR_API int kr_sdust_cpu(const uint8_t* bases, const uint64_t* offsets, uint32_t ncontigs, uint32_t T, uint32_t W, kr_sdust_result* out);
+KR_API void kr_sdust_free(kr_sdust_result*);
 
 KR_API const char* kr_last_error(void);
 KR_API const char* kr_version(void);

@@ -89,7 +89,11 @@ class KrMinimizerResult(C.Structure):
 class KrBuildParams(C.Structure):
     _fields_ = [("k", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32), ("m", C.c_uint32), ("r", C.c_uint32),
                 ("frac", C.c_uint32), ("num_threads", C.c_uint32), ("seed", C.c_uint32), ("ppos", u8p),
-                ("gpu_minimizers", C.c_uint32), ("device", C.c_int32)]
+                ("gpu_minimizers", C.c_uint32), ("device", C.c_int32), ("sdust_t", C.c_uint32), ("sdust_w", C.c_uint32)]
+
+
+class KrSdustResult(C.Structure):
+    _fields_ = [("intervals", u64p), ("offsets", u64p), ("ncontigs", C.c_uint32)]
 
 
 # every symbol include/krepp_amd.h declares (tests check that the library exports them all)
@@ -105,6 +109,7 @@ EXPORTS = [
     "kr_place_summary_text", "kr_place_tree_free", "kr_place_tree_kinds", "kr_place_batch", "kr_place_stream", "kr_place_stream_parsed", "kr_debug_place_ids", "kr_place_frame", "kr_place_counters",
     "kr_debug_last_d2h_bytes", "kr_debug_indexed_list", "kr_debug_acc_paths", "kr_debug_acc_layout", "kr_debug_place_fixed5", "kr_place_text_counters", "kr_place_path_counters", "kr_fastx_open", "kr_fastx_open_at", "kr_fastx_next", "kr_fastx_detach", "kr_fastx_release", "kr_fastx_close", "kr_fastx_parallel_chunks", "kr_fastx_pgz_stats", "kr_format_dist", "kr_debug_fixed5", "kr_free", "kr_host_alloc", "kr_host_free",
     "kr_build_index", "kr_minimizers_cpu", "kr_minimizers_device", "kr_minimizers_free", "kr_last_error", "kr_version",
+    "kr_sdust_cpu", "kr_sdust_free",
 ]
 
 # kr_debug_acc_paths: the accumulate kernel's path witnesses, in the order of CounterSlot (kr_dev_common.inc)
@@ -845,11 +850,11 @@ def place_heavy_reads():
 
 
 def build_index(input_tsv, out_dir, nwk=None, k=29, w=35, h=13, m=4, r=1, frac=True, num_threads=1, seed=0, ppos=None,
-                gpu_minimizers=False, device=0):
-    """`krepp index` on the CPU (reference: src/krepp.cpp:131-303)."""
+                gpu_minimizers=False, device=0, sdust_t=0, sdust_w=0):
+    """`krepp index` on the CPU (reference: src/krepp.cpp:131-303).  sdust_t, sdust_w both > 0: --sdust-t/-w masking."""
     lib = load()
     p = KrBuildParams(k=k, w=w, h=h, m=m, r=r, frac=int(frac), num_threads=num_threads, seed=seed, ppos=None,
-                      gpu_minimizers=int(gpu_minimizers), device=device)
+                      gpu_minimizers=int(gpu_minimizers), device=device, sdust_t=sdust_t, sdust_w=sdust_w)
     keep = None
     if ppos is not None:
         keep = (C.c_uint8 * len(ppos))(*ppos)
@@ -858,12 +863,13 @@ def build_index(input_tsv, out_dir, nwk=None, k=29, w=35, h=13, m=4, r=1, frac=T
                              os.fsencode(str(out_dir)), C.byref(p)))
 
 
-def build_sketch(input_path, out_path, k=26, w=None, h=None, m=4, r=1, frac=True, seed=0, ppos=None):
+def build_sketch(input_path, out_path, k=26, w=None, h=None, m=4, r=1, frac=True, seed=0, ppos=None, sdust_t=0, sdust_w=0):
     """`krepp sketch` (reference: src/krepp.cpp:110-129; defaults k 26, w k+6, h k-16)."""
     lib = load()
     w = k + 6 if w is None else w
     h = k - 16 if h is None else h
-    p = KrBuildParams(k=k, w=w, h=h, m=m, r=r, frac=int(frac), num_threads=1, seed=seed, ppos=None, gpu_minimizers=0, device=0)
+    p = KrBuildParams(k=k, w=w, h=h, m=m, r=r, frac=int(frac), num_threads=1, seed=seed, ppos=None, gpu_minimizers=0, device=0,
+                      sdust_t=sdust_t, sdust_w=sdust_w)
     keep = None
     if ppos is not None:
         keep = (C.c_uint8 * len(ppos))(*ppos)
@@ -872,14 +878,14 @@ def build_sketch(input_path, out_path, k=26, w=None, h=None, m=4, r=1, frac=True
     check(lib.kr_build_sketch(os.fsencode(str(input_path)), os.fsencode(str(out_path)), C.byref(p)))
 
 
-def minimizers(bases, offsets, k, w, h, ppos, m=4, r=1, frac=True, device=None):
+def minimizers(bases, offsets, k, w, h, ppos, m=4, r=1, frac=True, device=None, sdust_t=0, sdust_w=0):
     """(keys, n1, n2) of one genome: kr_minimizers_cpu (device=None) or kr_minimizers_device."""
     lib = load()
     bases = np.ascontiguousarray(bases, dtype=np.uint8)
     offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
     keep = (C.c_uint8 * len(ppos))(*ppos)
     p = KrBuildParams(k=k, w=w, h=h, m=m, r=r, frac=int(frac), num_threads=1, seed=0, ppos=C.cast(keep, u8p),
-                      gpu_minimizers=0, device=0)
+                      gpu_minimizers=0, device=0, sdust_t=sdust_t, sdust_w=sdust_w)
     res = KrMinimizerResult()
     if device is None:
         check(lib.kr_minimizers_cpu(C.byref(p), bases.ctypes.data, offsets.ctypes.data, len(offsets) - 1, C.byref(res)))
@@ -889,6 +895,26 @@ def minimizers(bases, offsets, k, w, h, ppos, m=4, r=1, frac=True, device=None):
     keys = _np(res.keys, res.nkeys, np.uint64)
     out = (keys, res.n1, res.n2)
     lib.kr_minimizers_free(C.byref(res))
+    return out
+
+
+def sdust(bases, offsets, T, W):
+    """Per contig the sdust interval list [(start, finish), ...] (finish exclusive): kr_sdust_cpu."""
+    lib = load()
+    bases = np.ascontiguousarray(bases, dtype=np.uint8)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    n = len(offsets) - 1
+    res = KrSdustResult()
+    vp = C.c_void_p
+    bp = bases.ctypes.data if len(bases) else (C.c_uint8 * 1)()
+    lib.kr_sdust_cpu.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(KrSdustResult)]
+    check(lib.kr_sdust_cpu(bp, offsets.ctypes.data, n, T, W, C.byref(res)))
+    off = _np(res.offsets, n + 1, np.uint64)
+    iv = _np(res.intervals, int(off[-1]), np.uint64)
+    out = [[(int(v) >> 32, int(v) & 0xFFFFFFFF) for v in iv[int(off[c]):int(off[c + 1])]] for c in range(n)]
+    lib.kr_sdust_free.argtypes = [C.POINTER(KrSdustResult)]
+    lib.kr_sdust_free.restype = None
+    lib.kr_sdust_free(C.byref(res))
     return out
 
 

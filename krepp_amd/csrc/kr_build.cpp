@@ -19,6 +19,7 @@
 // colours that are not tree nodes depend on hash-map iteration order in the
 // reference and on creation order here (set-level results unchanged).
 #include "kr_common.h"
+#include "kr_sdust.h"
 
 #include <algorithm>
 #include <cmath>
@@ -118,9 +119,10 @@ bool make_positions(uint32_t k, uint32_t h, const uint8_t* ppos, LshPositions& l
   return lsh.pasc.size() == h && lsh.pasc.back() < k && lsh.npos.size() == k - h;
 }
 
-// RSeq::extract_mers (src/rqseq.cpp:51-144) for one contig, sdust off.
+// RSeq::extract_mers (src/rqseq.cpp:51-144) for one contig.  rgs[0 .. mn): the contig's sdust intervals (start << 32 | finish),
+// walked one at a time as :91-107 does; mn = 0: sdust off.
 void extract_contig_cpu(const uint8_t* seq, uint64_t len, const BuildCfg& c, const LshPositions& lsh,
-                        std::vector<uint64_t>& keys, double& n1, double& n2)
+                        std::vector<uint64_t>& keys, double& n1, double& n2, const uint64_t* rgs, size_t mn)
 {
   uint32_t k = c.k, w = c.w;
   uint32_t ldiff = w > k ? w - k + 1 : 1;
@@ -134,6 +136,9 @@ void extract_contig_cpu(const uint8_t* seq, uint64_t len, const BuildCfg& c, con
   const uint64_t mask_bp = ~0ull >> ((32 - k) * 2);
   uint64_t bp = 0;
   uint32_t l = 0;
+  uint64_t mrs = 0, mre = len;
+  size_t mi = 0;
+  if (mn > 0) mre = (uint32_t)rgs[0], mrs = (uint32_t)(rgs[0] >> 32);
   for (uint64_t i = 0; i < len;) {
     unsigned cd = code_of(seq[i]);
     if (cd >= 4) {
@@ -144,6 +149,14 @@ void extract_contig_cpu(const uint8_t* seq, uint64_t len, const BuildCfg& c, con
     bp = (bp << 2) + cd; // compute/update_encoding give the same enc_bp once masked
     if (l < k) continue;
     uint64_t x = bp & mask_bp;
+    if (mi < mn && i + k > mrs) { // src/rqseq.cpp:91-107: counted, kept out of the window; the interval ends with l = 0
+      c1.add((uint32_t)fmix64(x));
+      if (i < mre) continue;
+      mi++;
+      l = 0;
+      if (mi < mn) mre = (uint32_t)rgs[mi], mrs = (uint32_t)(rgs[mi] >> 32);
+      continue;
+    }
     Slot s{x, fmix64(x)};
     win[kix % ldiff] = s;
     c1.add((uint32_t)s.z);
@@ -153,35 +166,92 @@ void extract_contig_cpu(const uint8_t* seq, uint64_t len, const BuildCfg& c, con
     size_t best = 0;
     for (size_t q = 1; q < win.size(); ++q)
       if (win[q].z < win[best].z) best = q;
-    const Slot& mn = win[best];
-    c2.add((uint32_t)mn.z);
-    int64_t row = build_row(lsh.rix(mn.x), c);
-    if (row >= 0) keys.push_back(((uint64_t)row << 32) | lsh.enc32(mn.x));
+    const Slot& mn_slot = win[best];
+    c2.add((uint32_t)mn_slot.z);
+    int64_t row = build_row(lsh.rix(mn_slot.x), c);
+    if (row >= 0) keys.push_back(((uint64_t)row << 32) | lsh.enc32(mn_slot.x));
   }
   n1 += hll12_estimate(c1.reg.data());
   n2 += hll12_estimate(c2.reg.data());
 }
 
-bool contig_end_special(const uint8_t* seq, uint64_t len, const BuildCfg& c, uint64_t& x, uint64_t& z)
+// The interval walk of src/rqseq.cpp:91-107 as two bit strings over the contig (what the device's leaf stage reads):
+//   skip[g]: the k-mer whose LAST base is g is counted for c1 but kept out of the window;
+//   brk[b]:  l is set to 0 between bases b-1 and b (no k-mer spans that point).
+// For interval j, skipping starts at the first valid k-mer end i (exclusive) with i + k > mrs_j and lasts up to and including the
+// first valid one with i >= mre_j, i*_j, where the break falls.  "Valid" is l >= k, and l restarts at i*_(j-1): the chain runs over
+// intervals.  Bits of invalid k-mers are set too; nobody reads them.
+void resolve_mask(const uint8_t* seq, uint64_t len, uint32_t k, const uint64_t* rgs, size_t mn, std::vector<uint64_t>& skip,
+                  std::vector<uint64_t>& brk)
+{
+  const size_t nw = (size_t)(len / 64) + 2;
+  skip.assign(nw, 0);
+  brk.assign(nw, 0);
+  auto set_range = [&](uint64_t a, uint64_t b) { // bits [a, b)
+    for (uint64_t q = a; q < b;) {
+      if ((q & 63u) == 0 && b - q >= 64) {
+        skip[q >> 6] = ~0ull, q += 64;
+      } else {
+        skip[q >> 6] |= 1ull << (q & 63u), ++q;
+      }
+    }
+  };
+  uint64_t last_break = 0;
+  for (size_t j = 0; j < mn; ++j) {
+    const uint64_t mrs = (uint32_t)(rgs[j] >> 32), mre = (uint32_t)rgs[j];
+    const uint64_t from = mrs + 1 > k ? mrs + 1 - k : 0; // first end i with i + k > mrs
+    // i*: the first i >= max(mre, last_break + k, from) with no non-base in [i - k, i)
+    uint64_t i = std::max(std::max(mre, last_break + k), std::max<uint64_t>(from, k));
+    bool found = false;
+    while (i <= len) {
+      uint64_t q = i;
+      while (q > i - k && code_of(seq[q - 1]) < 4) --q;
+      if (q == i - k) {
+        found = true;
+        break;
+      }
+      i = q + k; // q - 1 is no base: the next k-mer without it ends at q + k
+    }
+    if (!found) { // the contig ends while this interval is current
+      if (from < len) set_range(from ? from - 1 : 0, len);
+      return;
+    }
+    set_range(from ? from - 1 : 0, i); // ends from .. i  =  last bases from-1 .. i-1
+    if (i < len) brk[i >> 6] |= 1ull << (i & 63u);
+    last_break = i;
+  }
+}
+
+bool contig_end_special(const uint8_t* seq, uint64_t len, const BuildCfg& c, uint64_t& x, uint64_t& z, const uint64_t* skip,
+                        const uint64_t* brk)
 {
   const uint32_t k = c.k, w = std::max(c.w, c.k), ldiff = w - k + 1;
-  // length of the final run of valid bases
+  auto bit = [](const uint64_t* a, uint64_t q) { return a && ((a[q >> 6] >> (q & 63u)) & 1u); };
+  // length of the final run of valid bases (behind the last non-base or the last break of the interval walk)
   uint64_t l = 0;
-  while (l < len && code_of(seq[len - 1 - l]) < 4) ++l;
+  while (l < len && code_of(seq[len - 1 - l]) < 4) {
+    ++l;
+    if (bit(brk, len - l)) break;
+  }
   if (l < k || l >= w) return false; // no k-mer at the end, or the regular window rule applies
-  // the ring buffer holds the last `ldiff` k-mers computed anywhere in the contig (it is never
-  // reset), and zeros where fewer than ldiff have been computed
+  if (bit(skip, len - 1)) return false; // the contig ends while skipping: src/rqseq.cpp:91-95 continues before :112
+  // the ring buffer holds the last `ldiff` k-mers PUSHED anywhere in the contig (it is never reset; skipped k-mers are not
+  // pushed), and zeros where fewer than ldiff have been pushed
   const uint64_t mask_bp = ~0ull >> ((32 - k) * 2);
   std::vector<uint64_t> xs; // most recent first
   uint64_t i = len;
   while (i > 0 && xs.size() < ldiff) {
-    // k-mer ending at base i-1 is valid iff the k bases [i-k, i) are valid
-    if (i >= k) {
+    // k-mer ending at base i-1 is valid iff the k bases [i-k, i) are valid and no break lies strictly inside
+    if (skip && i >= 64 && (i & 63u) == 0 && skip[(i >> 6) - 1] == ~0ull) {
+      i -= 64; // 64 skipped ends at once
+      continue;
+    }
+    if (i >= k && !bit(skip, i - 1)) {
       bool ok = true;
       uint64_t bp = 0;
       for (uint64_t q = i - k; q < i; ++q) {
         unsigned cd = code_of(seq[q]);
-        if (cd >= 4) {
+        if (cd >= 4 || (q > i - k && bit(brk, q))) {
           ok = false;
           break;
         }
@@ -200,6 +270,92 @@ bool contig_end_special(const uint8_t* seq, uint64_t len, const BuildCfg& c, uin
   }
   if (have_zero && (first || 0 < z)) x = 0, z = 0; // a never-written slot {0,0,0} wins unless some hash is 0
   return true;
+}
+
+// ---- sdust on the host (kr_sdust.h) ----
+int sdust_check(uint32_t T, uint32_t W, const uint64_t* offsets, uint32_t ncontigs, const char* who)
+{
+  if (T == 0 || W < 4 || T > 0x7FFFFFFFu || W > 0x7FFFFFFFu) return fail(KR_ERR_ARG, std::string(who) + ": sdust needs T > 0 and W >= 4");
+  for (uint32_t q = 0; q < ncontigs; ++q) {
+    if (offsets[q + 1] < offsets[q]) return fail(KR_ERR_ARG, std::string(who) + ": offsets must not decrease");
+    if (offsets[q + 1] - offsets[q] >= (1ull << 31))
+      return fail(KR_ERR_ARG, std::string(who) + ": contig of 2^31 bases or more (the reference's sdust positions are int)");
+  }
+  return KR_OK;
+}
+
+namespace {
+struct HostSdust { // a state with room for any W; P grows on demand (the contig is run again)
+  std::vector<uint8_t> ring;
+  std::vector<SdustPerf> P;
+  SdustState<int32_t> S;
+  HostSdust(uint32_t T, uint32_t W)
+    : ring(W - 2)
+    , P(256)
+  {
+    sdust_init(S, ring.data(), (int32_t)ring.size(), P.data(), (int32_t)P.size(), (int32_t)T, (int32_t)W);
+  }
+  void grow()
+  {
+    P.resize(P.size() * 2);
+    sdust_init(S, ring.data(), (int32_t)ring.size(), P.data(), (int32_t)P.size(), S.T, S.W);
+  }
+};
+} // namespace
+
+// sdust(0, seq, -1, T, W, &n) for one contig: whole replay, the list merged as save_masked_regions does (src/sdust.h:117-122)
+void sdust_contig_host(const uint8_t* seq, uint64_t len, uint32_t T, uint32_t W, std::vector<uint64_t>& out, uint32_t* pmax)
+{
+  HostSdust h(T, W);
+  const size_t n0 = out.size();
+  for (;;) {
+    auto emit = [&](int32_t s, int32_t f) {
+      if (out.size() > n0) {
+        const int32_t ps = (int32_t)(out.back() >> 32), pf = (int32_t)(uint32_t)out.back();
+        if (s <= pf) {
+          out.back() = (uint64_t)(uint32_t)ps << 32 | (uint32_t)(pf > f ? pf : f);
+          return;
+        }
+      }
+      out.push_back((uint64_t)(uint32_t)s << 32 | (uint32_t)f);
+    };
+    sdust_scan(seq, len, W, [&](SdustEvent e) {
+      if (!h.S.overflow) sdust_event(h.S, e, emit);
+    });
+    if (!h.S.overflow) break;
+    out.resize(n0);
+    h.grow();
+  }
+  if (pmax && (uint32_t)h.S.pmax > *pmax) *pmax = (uint32_t)h.S.pmax;
+}
+
+int sdust_lists_host(const uint8_t* bases, const uint64_t* offsets, uint32_t ncontigs, uint32_t T, uint32_t W, std::vector<uint64_t>& iv,
+                     std::vector<uint64_t>& ioff)
+{
+  int rc = sdust_check(T, W, offsets, ncontigs, "sdust");
+  if (rc) return rc;
+  ioff.assign(1, 0);
+  iv.clear();
+  for (uint32_t q = 0; q < ncontigs; ++q) {
+    sdust_contig_host(bases + offsets[q], offsets[q + 1] - offsets[q], T, W, iv, nullptr);
+    ioff.push_back(iv.size());
+  }
+  return KR_OK;
+}
+
+int finish_sdust(const std::vector<uint64_t>& iv, const std::vector<uint64_t>& ioff, kr_sdust_result* out)
+{
+  out->ncontigs = (uint32_t)ioff.size() - 1;
+  out->intervals = (uint64_t*)malloc(std::max<size_t>(1, iv.size()) * 8);
+  out->offsets = (uint64_t*)malloc(ioff.size() * 8);
+  if (!out->intervals || !out->offsets) {
+    free(out->intervals), free(out->offsets);
+    out->intervals = out->offsets = nullptr;
+    return fail(KR_ERR_NOMEM, "kr_sdust: out of memory");
+  }
+  if (!iv.empty()) memcpy(out->intervals, iv.data(), iv.size() * 8);
+  memcpy(out->offsets, ioff.data(), ioff.size() * 8);
+  return KR_OK;
 }
 
 } // namespace kr
@@ -340,6 +496,21 @@ bool write_file(const std::string& path, const void* hdr, size_t hdr_bytes, cons
   return fclose(f) == 0 && ok;
 }
 
+// One contig through the leaf stage, masked when sdust is on.  Returns "" or what is wrong with the contig.
+std::string masked_contig_cpu(const uint8_t* seq, uint64_t len, const BuildCfg& c, const LshPositions& lsh, uint32_t sdust_t,
+                              uint32_t sdust_w, std::vector<uint64_t>& keys, double& n1, double& n2)
+{
+  if (!sdust_t) {
+    kr::extract_contig_cpu(seq, len, c, lsh, keys, n1, n2);
+    return "";
+  }
+  if (len >= (1ull << 31)) return "sdust: contig of 2^31 bases or more (the reference's sdust positions are int)";
+  std::vector<uint64_t> iv;
+  kr::sdust_contig_host(seq, len, sdust_t, sdust_w, iv, nullptr);
+  kr::extract_contig_cpu(seq, len, c, lsh, keys, n1, n2, iv.data(), iv.size());
+  return "";
+}
+
 } // namespace
 
 extern "C" int kr_build_index(const char* input_tsv, const char* nwk_path, const char* out_dir,
@@ -433,6 +604,9 @@ extern "C" int kr_build_index(const char* input_tsv, const char* nwk_path, const
   int nthreads = bp->num_threads ? (int)bp->num_threads : 1;
   (void)nthreads;
   std::string first_err;
+  int first_rc = KR_ERR_IO;
+  const uint32_t sdust_t = bp->sdust_t && bp->sdust_w ? bp->sdust_t : 0, sdust_w = sdust_t ? bp->sdust_w : 0; // either at 0: off
+  if (sdust_t && sdust_w < 4) return kr::fail(KR_ERR_ARG, "--sdust-w must be at least 4");
 #if defined(_OPENMP)
 #pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads)
 #endif
@@ -458,7 +632,13 @@ extern "C" int kr_build_index(const char* input_tsv, const char* nwk_path, const
           all_bases.insert(all_bases.end(), b.bases + b.offsets[q], b.bases + b.offsets[q + 1]);
           all_offs.push_back(all_bases.size());
         } else if (len >= c.w) {
-          kr::extract_contig_cpu(b.bases + b.offsets[q], len, c, lsh, g.keys, g.n1, g.n2); // RSeq::set_curr_seq: len >= w
+          std::string why = masked_contig_cpu(b.bases + b.offsets[q], len, c, lsh, sdust_t, sdust_w, g.keys, g.n1, g.n2); // RSeq::set_curr_seq: len >= w
+          if (!why.empty()) {
+#if defined(_OPENMP)
+#pragma omp critical
+#endif
+            if (first_err.empty()) first_err = why, first_rc = KR_ERR_ARG;
+          }
         }
       }
     } while (b.more);
@@ -468,11 +648,19 @@ extern "C" int kr_build_index(const char* input_tsv, const char* nwk_path, const
       bq.ppos = lsh.ppos.data();
       kr_minimizer_result mr;
       memset(&mr, 0, sizeof(mr));
-      int mrc;
+      int mrc = KR_OK;
+      // sdust: the host masker runs here, beside the other genomes' threads and outside the lock around the device; the device's
+      // leaf stage reads the mask as uploaded bit strings
+      std::vector<uint64_t> iv, ioff;
+      const bool host_mask = sdust_t && sdust_w;
+      if (host_mask) mrc = kr::sdust_lists_host(all_bases.data(), all_offs.data(), (uint32_t)all_offs.size() - 1, sdust_t, sdust_w, iv, ioff);
+      if (mrc == KR_OK) {
 #if defined(_OPENMP)
 #pragma omp critical(kr_gpu_minimizers)
 #endif
-      mrc = kr_minimizers_device(bp->device, &bq, all_bases.data(), all_offs.data(), (uint32_t)all_offs.size() - 1, &mr);
+        mrc = kr::minimizers_device(bp->device, &bq, all_bases.data(), all_offs.data(), (uint32_t)all_offs.size() - 1,
+                                    host_mask ? &iv : nullptr, host_mask ? &ioff : nullptr, &mr);
+      }
       if (mrc != KR_OK) {
 #if defined(_OPENMP)
 #pragma omp critical
@@ -488,7 +676,7 @@ extern "C" int kr_build_index(const char* input_tsv, const char* nwk_path, const
     g.keys.erase(std::unique(g.keys.begin(), g.keys.end()), g.keys.end());
     g.present = true;
   }
-  if (!first_err.empty()) return kr::fail(KR_ERR_IO, first_err);
+  if (!first_err.empty()) return kr::fail(first_rc, first_err);
 
   // group equal keys across genomes
   struct KL {
@@ -593,6 +781,7 @@ extern "C" int kr_build_index(const char* input_tsv, const char* nwk_path, const
     info << "krepp version: v0.8.3-compatible (krepp-amd)\nseed: " << bp->seed << "\nk: " << c.k << "\nw: " << c.w
          << "\nh: " << c.h << "\nm: " << c.m << "\nfrac: " << (c.frac ? "true" : "false") << "\nnrows: " << nrows
          << "\ntotal_num_kmers: " << nk << "\n";
+    if (sdust_t) info << "sdust-t: " << sdust_t << "\nsdust-w: " << sdust_w << "\n";
     std::string s = info.str();
     ok = ok && write_file(dir + "/metadata" + sfx + ".txt", s.data(), s.size(), nullptr, 0);
   }
@@ -638,11 +827,31 @@ extern "C" int kr_minimizers_cpu(const kr_build_params* bp, const uint8_t* bases
   if (rc) return rc;
   std::vector<uint64_t> keys;
   double n1 = 0, n2 = 0;
+  const uint32_t sdust_t = bp->sdust_t && bp->sdust_w ? bp->sdust_t : 0, sdust_w = sdust_t ? bp->sdust_w : 0;
+  if (sdust_t && (rc = kr::sdust_check(sdust_t, sdust_w, offsets, ncontigs, "kr_minimizers_cpu"))) return rc;
   for (uint32_t q = 0; q < ncontigs; ++q) {
     uint64_t len = offsets[q + 1] - offsets[q];
-    if (len >= c.w) kr::extract_contig_cpu(bases + offsets[q], len, c, lsh, keys, n1, n2);
+    if (len >= c.w) masked_contig_cpu(bases + offsets[q], len, c, lsh, sdust_t, sdust_w, keys, n1, n2);
   }
   return kr::finish_minimizers(keys, n1, n2, out);
+}
+
+extern "C" int kr_sdust_cpu(const uint8_t* bases, const uint64_t* offsets, uint32_t ncontigs, uint32_t T, uint32_t W, kr_sdust_result* out)
+{
+  kr::clear_error();
+  if (!bases || !offsets || !out) return kr::fail(KR_ERR_ARG, "kr_sdust_cpu: null argument");
+  std::vector<uint64_t> iv, ioff;
+  int rc = kr::sdust_lists_host(bases, offsets, ncontigs, T, W, iv, ioff);
+  return rc ? rc : kr::finish_sdust(iv, ioff, out);
+}
+
+extern "C" void kr_sdust_free(kr_sdust_result* r)
+{
+  if (!r) return;
+  free(r->intervals);
+  free(r->offsets);
+  r->intervals = r->offsets = nullptr;
+  r->ncontigs = 0;
 }
 
 extern "C" void kr_minimizers_free(kr_minimizer_result* r)
@@ -667,6 +876,8 @@ extern "C" int kr_build_sketch(const char* input_path, const char* out_path, con
   LshPositions lsh;
   if (!choose_positions(bp, c, lsh)) return kr::fail(KR_ERR_ARG, "bad LSH positions");
   const uint32_t nrows = nrows_of(c);
+  const uint32_t sdust_t = bp->sdust_t && bp->sdust_w ? bp->sdust_t : 0, sdust_w = sdust_t ? bp->sdust_w : 0; // either at 0: off
+  if (sdust_t && sdust_w < 4) return kr::fail(KR_ERR_ARG, "--sdust-w must be at least 4");
   kr_fastx* fx = nullptr;
   if (kr_fastx_open(input_path, &fx) != KR_OK) return kr::fail(KR_ERR_IO, std::string("Failed to open the file at ") + input_path);
   std::vector<uint64_t> keys;
@@ -679,7 +890,12 @@ extern "C" int kr_build_sketch(const char* input_path, const char* out_path, con
     }
     for (uint32_t q = 0; q < b.nreads; ++q) {
       const uint64_t len = b.offsets[q + 1] - b.offsets[q];
-      if (len >= c.w) kr::extract_contig_cpu(b.bases + b.offsets[q], len, c, lsh, keys, n1, n2); // RSeq::set_curr_seq
+      if (len < c.w) continue; // RSeq::set_curr_seq
+      std::string why = masked_contig_cpu(b.bases + b.offsets[q], len, c, lsh, sdust_t, sdust_w, keys, n1, n2);
+      if (!why.empty()) {
+        kr_fastx_close(fx);
+        return kr::fail(KR_ERR_ARG, why);
+      }
     }
   } while (b.more);
   kr_fastx_close(fx);

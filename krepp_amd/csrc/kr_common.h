@@ -151,12 +151,27 @@ inline uint64_t fmix64(uint64_t v)
   return v;
 }
 // One contig on the CPU (RSeq::extract_mers): appends keys, adds the contig's HLL estimates.
+// rgs[0 .. mn): the contig's sdust intervals (start << 32 | finish), walked as src/rqseq.cpp:91-107 does; none: sdust off.
 void extract_contig_cpu(const uint8_t* seq, uint64_t len, const BuildCfg& c, const LshPositions& lsh,
-                        std::vector<uint64_t>& keys, double& n1, double& n2);
+                        std::vector<uint64_t>& keys, double& n1, double& n2, const uint64_t* rgs = nullptr, size_t mn = 0);
 // What the ring buffer of RSeq::extract_mers yields at the END of a contig whose last run of valid
 // bases is shorter than w (src/rqseq.cpp:108-116: stale or zero slots take part): true if a
 // minimizer is emitted there; `x` is its k-mer code, `z` its hash.
-bool contig_end_special(const uint8_t* seq, uint64_t len, const BuildCfg& c, uint64_t& x, uint64_t& z);
+// skip / brk: the contig's interval walk as bit strings (resolve_mask), or null with sdust off: a skipped k-mer is not in the ring,
+// a break ends a run of valid bases as a non-base does, and a contig that ends while skipping emits nothing.
+bool contig_end_special(const uint8_t* seq, uint64_t len, const BuildCfg& c, uint64_t& x, uint64_t& z, const uint64_t* skip = nullptr,
+                        const uint64_t* brk = nullptr);
+// ---- sdust (kr_sdust.h): host masker, the interval walk as bit strings, the device's leaf stage with a mask ----
+int sdust_check(uint32_t T, uint32_t W, const uint64_t* offsets, uint32_t ncontigs, const char* who);
+void sdust_contig_host(const uint8_t* seq, uint64_t len, uint32_t T, uint32_t W, std::vector<uint64_t>& out, uint32_t* pmax);
+int sdust_lists_host(const uint8_t* bases, const uint64_t* offsets, uint32_t ncontigs, uint32_t T, uint32_t W, std::vector<uint64_t>& iv,
+                     std::vector<uint64_t>& ioff);
+int finish_sdust(const std::vector<uint64_t>& iv, const std::vector<uint64_t>& ioff, kr_sdust_result* out);
+void resolve_mask(const uint8_t* seq, uint64_t len, uint32_t k, const uint64_t* rgs, size_t mn, std::vector<uint64_t>& skip,
+                  std::vector<uint64_t>& brk);
+// kr_minimizers_device with the contigs' sdust lists given (iv / ioff as kr_sdust_result lays them out), or null: made inside
+int minimizers_device(int device, const kr_build_params* bp, const uint8_t* bases, const uint64_t* offsets, uint32_t ncontigs,
+                      const std::vector<uint64_t>* iv, const std::vector<uint64_t>* ioff, kr_minimizer_result* out);
 
 // ---- `place` back end on the device (kr_device.hip), driven by kr_place.cpp ----
 // The placement tree as flat arrays over its nodes q = 1..pn (q = post-order number, so the subtree of q is the

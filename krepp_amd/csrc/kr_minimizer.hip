@@ -19,8 +19,15 @@
 // The one case that depends on the ring buffer's history — a contig whose LAST run of valid bases
 // is shorter than w (stale or never-written slots take part, src/rqseq.cpp:108-116) — is a single
 // extra emission per contig and is computed on the host (kr::contig_end_special).
+//
+// With sdust on (kr_build_params::sdust_t/sdust_w) the kernel's MASKED instantiation reads two more bit strings per tile, made on
+// the host from the contig's interval list (kr::resolve_mask, the walk of src/rqseq.cpp:91-107): skip, indexed by the k-mer's last
+// base, and break-before-base.  A k-mer counts for the first sketch iff it holds no non-base and no break; it enters a window iff
+// it is not skipped either; a position emits iff all w-k+1 k-mers ending in its window entered.  The interval lists come from the
+// host masker (kr_sdust.h), made here or handed in by the caller.
 #include "kr_common.h"
 #include "kr_devutil.h"
+#include "kr_sdust.h"
 
 #include <algorithm>
 #include <cstring>
@@ -78,11 +85,15 @@ __device__ __forceinline__ void hll_add(uint32_t* reg, uint32_t hsh)
   if (reg[ix] < rank) atomicMax(&reg[ix], rank); // registers saturate quickly: most adds stop at the read
 }
 
+// MASKED: skip / brk are the contigs' bit strings back to back, contig ci's from word mwoff[ci] on (mwoff[ci + 1] - mwoff[ci] words)
+template <bool MASKED>
 __global__ __launch_bounds__(256) void kr_minimizer_kernel(MinParams P, const uint8_t* bases, const uint64_t* offsets,
                                                            const uint2* tiles, uint32_t* hll, uint64_t* keys,
-                                                           unsigned long long* nkeys, unsigned long long key_cap)
+                                                           unsigned long long* nkeys, unsigned long long key_cap,
+                                                           const uint64_t* skip, const uint64_t* brk, const uint64_t* mwoff)
 {
   __shared__ uint64_t sL[kWords + 1], sH[kWords + 1], sN[kWords + 1];
+  __shared__ uint64_t sS[MASKED ? kWords + 1 : 1], sB[MASKED ? kWords + 1 : 1];
   __shared__ uint64_t sZ[kTile + kMaxWin], sX[kTile + kMaxWin];
   __shared__ uint8_t sOk[kTile + kMaxWin];
   const uint2 tl = tiles[blockIdx.x];
@@ -103,6 +114,14 @@ __global__ __launch_bounds__(256) void kr_minimizer_kernel(MinParams P, const ui
     if (lane == 0) sL[c] = L, sH[c] = H, sN[c] = N;
   }
   if (tid == 0) sL[kWords] = 0, sH[kWords] = 0, sN[kWords] = ~0ull;
+  if constexpr (MASKED) { // b0 is a multiple of 64: LDS word c is the contig's mask word b0 / 64 + c
+    if (tid <= (uint32_t)kWords) {
+      const int64_t wi = b0 / 64 + (int64_t)tid, nw = (int64_t)(mwoff[ci + 1] - mwoff[ci]);
+      const bool in = tid < (uint32_t)kWords && wi >= 0 && wi < nw;
+      sS[tid] = in ? skip[mwoff[ci] + (uint64_t)wi] : 0ull;
+      sB[tid] = in ? brk[mwoff[ci] + (uint64_t)wi] : 0ull;
+    }
+  }
   __syncthreads();
   // ---- 2. hash of the k-mer ENDING at base g, for g in [p0 - ldiff + 1, p0 + kTile)
   const int64_t g0 = p0 - (int64_t)P.ldiff + 1;
@@ -115,13 +134,19 @@ __global__ __launch_bounds__(256) void kr_minimizer_kernel(MinParams P, const ui
     if (g >= (int64_t)P.k - 1 && g < len) {
       uint32_t s = (uint32_t)(g - (int64_t)P.k + 1 - b0);
       uint32_t wn = window_bits(sN, s) & mk;
-      if (wn == 0) {
+      bool whole = wn == 0;
+      if constexpr (MASKED) whole = whole && (window_bits(sB, s + 1) & (mk >> 1)) == 0; // no break behind its 2nd .. k-th base
+      if (whole) {
         uint32_t wl = window_bits(sL, s) & mk, wh = window_bits(sH, s) & mk;
         uint32_t lo = __brev(wl) >> (32 - P.k), hi = __brev(wh) >> (32 - P.k); // position 0 = LAST base
         x = spread32(lo) | (spread32(hi) << 1);
         z = dev_fmix64(x);
         ok = true;
         if (g >= p0) hll_add(reg1, (uint32_t)z); // c1: every valid k-mer, once
+        if constexpr (MASKED) { // counted, but kept out of the windows
+          const uint32_t sg = (uint32_t)(g - b0);
+          if ((sS[sg >> 6] >> (sg & 63u)) & 1u) ok = false, z = ~0ull;
+        }
       }
     }
     sZ[t] = z;
@@ -184,21 +209,27 @@ __global__ __launch_bounds__(256) void kr_minimizer_kernel(MinParams P, const ui
                       std::string(#expr) + ": " + hipGetErrorString(e__));                              \
   } while (0)
 
+int pick_device(int device, const char* who)
+{
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return kr::fail(KR_ERR_NO_DEVICE, "no HIP device available");
+  if (device < 0 || device >= ndev) return kr::fail(KR_ERR_ARG, std::string(who) + ": bad device ordinal");
+  HIP_TRY(hipSetDevice(device));
+  return KR_OK;
+}
+
 } // namespace
 
-extern "C" int kr_minimizers_device(int device, const kr_build_params* bp, const uint8_t* bases, const uint64_t* offsets,
-                                    uint32_t ncontigs, kr_minimizer_result* out)
+int kr::minimizers_device(int device, const kr_build_params* bp, const uint8_t* bases, const uint64_t* offsets, uint32_t ncontigs,
+                          const std::vector<uint64_t>* iv_in, const std::vector<uint64_t>* ioff_in, kr_minimizer_result* out)
 {
-  kr::clear_error();
-  if (!bases || !offsets || !out) return kr::fail(KR_ERR_ARG, "kr_minimizers_device: null argument");
   kr::BuildCfg c;
   kr::LshPositions lsh;
   int rc = kr::check_minimizer_params(bp, c, lsh);
   if (rc) return rc;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return kr::fail(KR_ERR_NO_DEVICE, "no HIP device available");
-  if (device < 0 || device >= ndev) return kr::fail(KR_ERR_ARG, "kr_minimizers_device: bad device ordinal");
-  HIP_TRY(hipSetDevice(device));
+  const uint32_t sdust_t = bp->sdust_t && bp->sdust_w ? bp->sdust_t : 0, sdust_w = sdust_t ? bp->sdust_w : 0;
+  if (sdust_t && (rc = kr::sdust_check(sdust_t, sdust_w, offsets, ncontigs, "kr_minimizers_device"))) return rc;
+  if ((rc = pick_device(device, "kr_minimizers_device"))) return rc;
   const uint32_t w = std::max(c.w, c.k);
   MinParams P;
   P.k = c.k, P.w = w, P.ldiff = w - c.k + 1, P.m = c.m, P.r = c.r, P.frac = c.frac ? 1 : 0;
@@ -217,11 +248,12 @@ extern "C" int kr_minimizers_device(int device, const kr_build_params* bp, const
   }
   std::vector<uint64_t> keys;
   double n1 = 0, n2 = 0;
+  std::vector<uint64_t> skip, brk, mwoff; // sdust: the interval walks of all contigs as bit strings
   if (!tiles.empty()) {
     std::vector<uint32_t> regs((size_t)ncontigs * 8192);
     { // the device's part; its arrays are freed where this block is left, at an error too
     DevBuf<uint8_t> b_bases;
-    DevBuf<uint64_t> b_off, b_keys;
+    DevBuf<uint64_t> b_off, b_keys, b_skip, b_brk, b_mwoff;
     DevBuf<uint2> b_tiles;
     DevBuf<uint32_t> b_hll;
     DevBuf<unsigned long long> b_n;
@@ -239,8 +271,35 @@ extern "C" int kr_minimizers_device(int device, const kr_build_params* bp, const
     HIP_TRY(hipMemcpy(d_tiles, tiles.data(), tiles.size() * sizeof(uint2), hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(d_hll, 0, (uint64_t)ncontigs * 8192 * 4));
     HIP_TRY(hipMemset(d_n, 0, 8));
-    hipLaunchKernelGGL(kr_minimizer_kernel, dim3((uint32_t)tiles.size()), dim3(256), 0, 0, P, d_bases, d_off, d_tiles, d_hll,
-                       d_keys, d_n, cap);
+    if (sdust_t) {
+      std::vector<uint64_t> iv_own, ioff_own;
+      if (!iv_in || !ioff_in) {
+        if ((rc = kr::sdust_lists_host(bases, offsets, ncontigs, sdust_t, sdust_w, iv_own, ioff_own))) return rc;
+        iv_in = &iv_own, ioff_in = &ioff_own;
+      }
+      if (ioff_in->size() != (size_t)ncontigs + 1 || ioff_in->back() != iv_in->size())
+        return kr::fail(KR_ERR_ARG, "kr_minimizers_device: interval lists do not fit the contigs");
+      mwoff.assign((size_t)ncontigs + 1, 0);
+      std::vector<uint64_t> s1, b1;
+      for (uint32_t q = 0; q < ncontigs; ++q) {
+        const uint64_t len = offsets[q + 1] - offsets[q];
+        if (len >= c.w) {
+          kr::resolve_mask(bases + offsets[q], len, c.k, iv_in->data() + (*ioff_in)[q], (size_t)((*ioff_in)[q + 1] - (*ioff_in)[q]), s1, b1);
+          skip.insert(skip.end(), s1.begin(), s1.end());
+          brk.insert(brk.end(), b1.begin(), b1.end());
+        }
+        mwoff[q + 1] = skip.size();
+      }
+      if (!b_skip.reserve(skip.size() + 1) || !b_brk.reserve(brk.size() + 1) || !b_mwoff.reserve(mwoff.size())) return alloc_failed("kr_minimizers_device");
+      HIP_TRY(hipMemcpy(b_skip.get(), skip.data(), skip.size() * 8, hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(b_brk.get(), brk.data(), brk.size() * 8, hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(b_mwoff.get(), mwoff.data(), mwoff.size() * 8, hipMemcpyHostToDevice));
+      hipLaunchKernelGGL(kr_minimizer_kernel<true>, dim3((uint32_t)tiles.size()), dim3(256), 0, 0, P, d_bases, d_off, d_tiles, d_hll, d_keys,
+                         d_n, cap, (const uint64_t*)b_skip.get(), (const uint64_t*)b_brk.get(), (const uint64_t*)b_mwoff.get());
+    } else {
+      hipLaunchKernelGGL(kr_minimizer_kernel<false>, dim3((uint32_t)tiles.size()), dim3(256), 0, 0, P, d_bases, d_off, d_tiles, d_hll,
+                         d_keys, d_n, cap, (const uint64_t*)nullptr, (const uint64_t*)nullptr, (const uint64_t*)nullptr);
+    }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     unsigned long long nk = 0;
@@ -258,7 +317,8 @@ extern "C" int kr_minimizers_device(int device, const kr_build_params* bp, const
       uint32_t* r1 = regs.data() + (size_t)q * 8192;
       uint32_t* r2 = r1 + 4096;
       uint64_t x = 0, z = 0;
-      if (kr::contig_end_special(seq, len, c, x, z)) {
+      const uint64_t *sk = sdust_t ? skip.data() + mwoff[q] : nullptr, *bk = sdust_t ? brk.data() + mwoff[q] : nullptr;
+      if (kr::contig_end_special(seq, len, c, x, z, sk, bk)) {
         uint32_t hsh = (uint32_t)z, ix = hsh >> 20, rest = hsh << 12;
         uint32_t rank = (uint32_t)std::min(20, rest ? __builtin_clz(rest) : 32) + 1u;
         r2[ix] = std::max(r2[ix], rank);
@@ -272,4 +332,12 @@ extern "C" int kr_minimizers_device(int device, const kr_build_params* bp, const
     }
   }
   return kr::finish_minimizers(keys, n1, n2, out);
+}
+
+extern "C" int kr_minimizers_device(int device, const kr_build_params* bp, const uint8_t* bases, const uint64_t* offsets,
+                                    uint32_t ncontigs, kr_minimizer_result* out)
+{
+  kr::clear_error();
+  if (!bases || !offsets || !out) return kr::fail(KR_ERR_ARG, "kr_minimizers_device: null argument");
+  return kr::minimizers_device(device, bp, bases, offsets, ncontigs, nullptr, nullptr, out);
 }

@@ -77,7 +77,9 @@ static void print_help(const std::string& sub)
     "  -m, --modulo-lsh N         modulo partitioning the LSH space [4]\n"
     "  -r, --residue-lsh N        keep k-mers with LSH(x) mod m == r [1]\n"
     "      --frac / --no-frac     keep k-mers with LSH(x) mod m <= r [frac]\n"
-    "      --seed N               seed of the random LSH positions\n";
+    "      --seed N               seed of the random LSH positions\n"
+    "      --sdust-t N            sdust score threshold; with --sdust-w > 0 low-complexity intervals stay out of the windows [0: off]\n"
+    "      --sdust-w N            sdust window length, >= 4 [0: off]\n";
   printf("krepp (MI355X build, mirrors krepp v0.8.3): dist | place | seek | index | sketch\n");
   if (sub.empty() || sub == "dist")
     printf("\nkrepp dist -i DIR -q READS: distances of every read to the references it matches\n%s%s"
@@ -990,6 +992,26 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
   return 0;
 }
 
+// --sdust-t / --sdust-w (src/krepp.cpp:530-531,576-577): non-negative integers, masking on when both are positive, and then the
+// two lines of validate_configuration (src/krepp.hpp:80-83)
+static void sdust_options(const Args& a, kr_build_params& bp)
+{
+  auto value = [&](const char* name) -> uint32_t {
+    if (!a.has(name)) return 0;
+    const std::string v = a.get(name);
+    char* end = nullptr;
+    const long long n = strtoll(v.c_str(), &end, 10);
+    if (v.empty() || *end || n < 0 || n > 0x7FFFFFFFll) error_exit(std::string(name) + ": a non-negative integer is required");
+    return (uint32_t)n;
+  };
+  bp.sdust_t = value("--sdust-t");
+  bp.sdust_w = value("--sdust-w");
+  if (bp.sdust_t != 0 && bp.sdust_w != 0) {
+    fprintf(stderr, "Setting --sdust-w and --sdust-t to >0 will enable dustmasker.\n");
+    fprintf(stderr, "With dustmasker, krepp might fail to model subsampling and be slightly inaccurate.\n");
+  }
+}
+
 static int run_index(const Args& a)
 {
   // the reference's `index` takes -i,--input-file (name<TAB>path map) and -o,--index-dir
@@ -1021,6 +1043,7 @@ static int run_index(const Args& a)
   bp.seed = a.has("--seed") ? (uint32_t)atoi(a.get("--seed").c_str()) : 0;
   bp.gpu_minimizers = a.flag.count("--gpu-minimizers") && a.flag.at("--gpu-minimizers");
   bp.device = a.has("--device") ? atoi(a.get("--device").c_str()) : 0;
+  sdust_options(a, bp);
   fprintf(stderr, "Building the index...\n");
   std::string nwk = a.get("--nwk-file");
   if (kr_build_index(input.c_str(), nwk.empty() ? nullptr : nwk.c_str(), outdir.c_str(), &bp)) error_exit(kr_last_error());
@@ -1046,6 +1069,7 @@ static int run_sketch(const Args& a)
   if (a.has("--residue-lsh")) bp.r = (uint32_t)atoi(a.get("--residue-lsh").c_str());
   if (a.flag.count("--frac")) bp.frac = a.flag.at("--frac");
   bp.seed = a.has("--seed") ? (uint32_t)atoi(a.get("--seed").c_str()) : 0;
+  sdust_options(a, bp);
   fprintf(stderr, "Initializing the sketch...\n");
   if (kr_build_sketch(input.c_str(), outp.c_str(), &bp)) error_exit(kr_last_error());
   fprintf(stderr, "Done sketching & saving\n");
