@@ -137,6 +137,10 @@ KR_API uint32_t kr_index_slot_words(const kr_index*);
  * 9 FILTER slots -- two 128-byte lines of 24-bit codes per row, one line per probe for most buckets, candidates verified by
  * the accumulate kernel (kr_scan_filt_kernel_t; replaces the linear bucket scan of src/query.cpp:361-368). */
 KR_API uint32_t kr_index_slot_format(const kr_index*);
+/* The packed scan's shape and front: log2 of the lanes that share a probe (0, 2 or 3: from the mean bucket length, or KR_LOG_G at
+ * upload), and whether the packed tables carry the row-occupancy bitmap (sparse tables, or KR_OCC_BITMAP at upload). */
+KR_API uint32_t kr_index_log_g(const kr_index*);
+KR_API uint32_t kr_index_occ_bitmap(const kr_index*);
 
 /* Replicate an uploaded index into the HBM of `ndev` more devices of this node by RCCL broadcast
  * (ncclBroadcast per flat buffer, one communicator over the root's device and the targets, xGMI):
@@ -316,6 +320,17 @@ KR_API int kr_debug_acc_paths(kr_stream*, uint32_t* out, uint32_t n);
  * spill, words of the region, words per key of a batch of the straight-line epilogue, number of path witnesses, then for the stream
  * (0 if NULL) the events, passing-key table entries and keys a wave's global scratch holds, 0}. */
 KR_API int kr_debug_acc_layout(const kr_stream*, uint32_t np, uint32_t segs, uint32_t multi, uint32_t* out8);
+/* Tests (no device needed): the numbers of the scan shape chosen for a table of `slot_format` (0 packed: the shape follows log_g = 0,
+ * 2, 3; 5..8 slotted; 9 filter slots), the constants the kernels are built with: out16 = {G lanes per probe, CPL 16-byte chunks per lane
+ * and pass, PPS probes per pass, words per slot (0: packed), CAP entries a slot holds, step bits of a group before its hit chunks are
+ * dealt out, probes a group lists at most, items staged per read before a flush, item slots a wave takes at a time, reads per visit to
+ * a cursor, cursors, k-mer positions per segment, codes per line and per slot of format 9 (else 0), 1 if slotted, largest hdist_th
+ * the scan of format 9 serves}. */
+KR_API int kr_debug_scan_layout(uint32_t slot_format, uint32_t log_g, uint32_t* out16);
+/* Tests: the scan of this stream: out4 = {1 if the pipelined slotted kernel is launched (formats 5..8; KR_SCAN_PIPE=0 when the stream is
+ * made selects the one-group-at-a-time kernel), 1 if the filter-slot kernel is, item slots a lane's scan may use (KR_DEBUG_ITEM_CAP=n
+ * when the stream is made lowers it), item slots the scan of the batch last waited for asked for}. */
+KR_API int kr_debug_scan_stream(const kr_stream*, uint32_t* out4);
 /* Tests: one number as `krepp place` rows print it (std::fixed, 5 decimals; `out` holds 80 bytes); returns its length. */
 KR_API int kr_debug_place_fixed5(double v, char* out);
 

@@ -100,14 +100,14 @@ class KrSdustResult(C.Structure):
 EXPORTS = [
     "kr_host_index_load", "kr_host_sketch_load", "kr_format_seek", "kr_build_sketch", "kr_host_index_free", "kr_host_index_view", "kr_host_index_node_name",
     "kr_host_index_node_label", "kr_host_index_node_parent", "kr_host_index_node_blen",
-    "kr_index_upload", "kr_index_free", "kr_index_export", "kr_index_import", "kr_index_device_bytes", "kr_index_slot_words", "kr_index_slot_format", "kr_index_broadcast",
+    "kr_index_upload", "kr_index_free", "kr_index_export", "kr_index_import", "kr_index_device_bytes", "kr_index_slot_words", "kr_index_slot_format", "kr_index_log_g", "kr_index_occ_bitmap", "kr_index_broadcast",
     "kr_params_default", "kr_stream_create", "kr_stream_destroy", "kr_batch_submit", "kr_batch_wait",
     "kr_batch_collect", "kr_batch_collect_device", "kr_stream_text_enable", "kr_batch_submit_text", "kr_batch_collect_text",
     "kr_stream_fastq_enable", "kr_batch_submit_fastq", "kr_batch_submit_fasta", "kr_fasta_chunk_cut", "kr_batch_fastq_names", "kr_debug_fastq_batch", "kr_debug_fastq_parse_ms", "kr_debug_tile_layout", "kr_debug_tile_shape", "kr_batch_hits", "kr_batch_readtaps",
     "kr_debug_front_end", "kr_debug_stream_move", "kr_debug_stream_addrs", "kr_debug_item_placement", "kr_debug_brent", "kr_debug_prefix", "kr_debug_colour_classes", "kr_llh_batch", "kr_llh_eval_indexed", "kr_batch_timing",
     "kr_place_tree_create", "kr_place_tree_create_lineage", "kr_place_tree_nnodes", "kr_place_summary_add",
     "kr_place_summary_text", "kr_place_tree_free", "kr_place_tree_kinds", "kr_place_batch", "kr_place_stream", "kr_place_stream_parsed", "kr_debug_place_ids", "kr_place_frame", "kr_place_counters",
-    "kr_debug_last_d2h_bytes", "kr_debug_indexed_list", "kr_debug_acc_paths", "kr_debug_acc_layout", "kr_debug_place_fixed5", "kr_place_text_counters", "kr_place_path_counters", "kr_fastx_open", "kr_fastx_open_at", "kr_fastx_next", "kr_fastx_detach", "kr_fastx_release", "kr_fastx_close", "kr_fastx_parallel_chunks", "kr_fastx_pgz_stats", "kr_format_dist", "kr_debug_fixed5", "kr_free", "kr_host_alloc", "kr_host_free",
+    "kr_debug_last_d2h_bytes", "kr_debug_indexed_list", "kr_debug_acc_paths", "kr_debug_acc_layout", "kr_debug_scan_layout", "kr_debug_scan_stream", "kr_debug_place_fixed5", "kr_place_text_counters", "kr_place_path_counters", "kr_fastx_open", "kr_fastx_open_at", "kr_fastx_next", "kr_fastx_detach", "kr_fastx_release", "kr_fastx_close", "kr_fastx_parallel_chunks", "kr_fastx_pgz_stats", "kr_format_dist", "kr_debug_fixed5", "kr_free", "kr_host_alloc", "kr_host_free",
     "kr_build_index", "kr_minimizers_cpu", "kr_minimizers_device", "kr_minimizers_free", "kr_last_error", "kr_version",
     "kr_sdust_cpu", "kr_sdust_free",
 ]
@@ -161,6 +161,12 @@ def load():
     lib.kr_index_slot_words.argtypes = [vp]
     lib.kr_index_slot_format.argtypes = [vp]
     lib.kr_index_slot_format.restype = C.c_uint32
+    lib.kr_index_log_g.argtypes = [vp]
+    lib.kr_index_log_g.restype = C.c_uint32
+    lib.kr_index_occ_bitmap.argtypes = [vp]
+    lib.kr_index_occ_bitmap.restype = C.c_uint32
+    lib.kr_debug_scan_layout.argtypes = [C.c_uint32, C.c_uint32, u32p]
+    lib.kr_debug_scan_stream.argtypes = [vp, u32p]
     lib.kr_debug_stream_move.argtypes = [vp, C.c_int]
     lib.kr_debug_stream_addrs.argtypes = [vp, u64p]
     lib.kr_debug_item_placement.argtypes = [vp, u32p, u32p, C.POINTER(C.c_double)]
@@ -373,6 +379,14 @@ class DeviceIndex:
     def slot_format(self):
         return int(self.lib.kr_index_slot_format(self.h))
 
+    @property
+    def log_g(self):
+        return int(self.lib.kr_index_log_g(self.h))
+
+    @property
+    def occ_bitmap(self):
+        return bool(self.lib.kr_index_occ_bitmap(self.h))
+
     def stream(self, params=None, max_reads=1 << 16, max_bases=None, max_records=0):
         return Stream(self, params or default_params(), max_reads, max_bases or max_reads * 160, max_records)
 
@@ -517,6 +531,13 @@ class Stream:
 
     def acc_layout(self, segs=1, multi=0):
         return acc_layout(self.params.hdist_th + 1, segs, multi, self)
+
+    def scan_info(self):
+        """(tests) kr_debug_scan_stream: which scan kernel this stream launches, the item slots a lane's scan may use, and the item
+        slots the batch last waited for asked for"""
+        a = (C.c_uint32 * 4)()
+        check(self.lib.kr_debug_scan_stream(self.h, a))
+        return dict(pipe=bool(a[0]), filt=bool(a[1]), item_cap=int(a[2]), item_slots=int(a[3]))
 
     def collect_device(self):
         rv = KrResultView()
@@ -710,6 +731,17 @@ def acc_layout(np_planes, segs=1, multi=0, stream=None):
     check(load().kr_debug_acc_layout(stream.h if stream is not None else None, int(np_planes), int(segs), int(multi), a))
     assert a[3] == len(ACC_PATHS)
     return dict(ev_cap=int(a[0]), ev_words=int(a[1]), key_words=int(a[2]), ev_spill=int(a[4]), tab_spill=int(a[5]), kt_spill=int(a[6]))
+
+
+SCAN_LAYOUT = ("G", "CPL", "PPS", "W", "CAP", "step_bits", "list_cap", "item_stage", "item_chunk", "read_chunk", "cursors", "seg_pos",
+               "line_codes", "slot_codes", "slotted", "filt_max_th")
+
+
+def scan_layout(slot_format, log_g=0):
+    """(tests) kr_debug_scan_layout: the numbers of the scan shape chosen for a table of this slot format (0: packed, shape by log_g)"""
+    a = (C.c_uint32 * 16)()
+    check(load().kr_debug_scan_layout(int(slot_format), int(log_g), a))
+    return dict(zip(SCAN_LAYOUT, [int(x) for x in a]))
 
 
 def fasta_chunk_cut(buf):

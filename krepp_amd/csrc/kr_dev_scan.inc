@@ -4,6 +4,11 @@
 // Probe list of one group (64 positions x 2 strands) and the bucket scan.
 // ---------------------------------------------------------------------------
 constexpr int kListCap = 128;
+// The numbers of a scan shape (2^LOG_G lanes x CPL 16-byte chunks per probe), in one place for the kernels and for the host
+// (kr_debug_scan_layout): words of a slot (2 header words + CAP entries), steps of scan_group before it flushes its hit bits.
+constexpr uint32_t scan_slot_words(int log_g, int cpl) { return (1u << log_g) * (uint32_t)cpl * 4u; }
+constexpr uint32_t scan_slot_cap(int log_g, int cpl) { return scan_slot_words(log_g, cpl) - 2u; }
+constexpr uint32_t scan_step_bits(int cpl) { return 64u / (uint32_t)cpl * (uint32_t)cpl; }
 struct ProbeList {
   lds_u64* bkt; // [128] (start << 24) | len
   lds_u32* q;   // [128] residual code of the query k-mer
@@ -277,7 +282,7 @@ __device__ __forceinline__ void scan_group(const DevIndex& ix, const DevParams& 
                                            uint32_t base0)
 {
   constexpr uint32_t G = 1u << LOG_G, PPS = 64u >> LOG_G;
-  constexpr uint32_t kBits = 64u / CPL * CPL; // steps per flush
+  constexpr uint32_t kBits = scan_step_bits(CPL); // steps per flush
   const uint32_t lane = lane_id(), sub = lane & (G - 1u);
   uint32_t p0 = 0, cb = 0; // scan position: pass start, chunk block (units of G chunks)
   while (p0 < nact) {
@@ -369,7 +374,7 @@ template <int LOG_G, int CPL, bool SL, bool TAP>
 __device__ __forceinline__ void scan_group_slots(const DevIndex& ix, const DevParams& P, const BatchOut& out, ScanWave& sw,
                                                  const ProbeList& pl, lds_u32* queue, uint32_t nact, uint32_t read, uint32_t base0)
 {
-  constexpr uint32_t G = 1u << LOG_G, PPS = 64u >> LOG_G, W = G * CPL * 4u, CAP = W - 2u;
+  constexpr uint32_t G = 1u << LOG_G, PPS = 64u >> LOG_G, W = scan_slot_words(LOG_G, CPL), CAP = scan_slot_cap(LOG_G, CPL);
   static_assert((kListCap / PPS) * CPL <= 64, "one hit bit per (pass, chunk)");
   const uint32_t lane = lane_id(), sub = lane & (G - 1u);
   uint64_t hitbits = 0;

@@ -204,6 +204,9 @@ __device__ __forceinline__ void filt_resolve(const DevIndex& ix, const DevParams
   }
 }
 
+// the shape of this scan, as kr_debug_scan_layout reports it: 4 lanes x 2 chunks per probe = one 128-byte line, 16 probes per pass
+constexpr uint32_t kFiltG = 4u, kFiltCpl = 2u, kFiltPps = 64u / kFiltG;
+static_assert(kFiltG * kFiltCpl * 5u == kFiltLineCodes && 2u * kFiltLineCodes == kFiltSlotCodes, "five 24-bit codes per chunk, two lines per slot");
 #ifndef KR_SCAN_FILT_DEPTH
 #define KR_SCAN_FILT_DEPTH 2 // passes (16 probes = 16 lines each) a wave keeps in flight: 32 lines, as many as the 256-byte scan
 #endif
@@ -214,7 +217,7 @@ __device__ __forceinline__ void filt_resolve(const DevIndex& ix, const DevParams
 template <int DEPTH, int WPE, bool SL, bool TAP>
 __global__ __launch_bounds__(kScanWaves* kWave, WPE) void kr_scan_filt_kernel_t(DevIndex ix, DevParams P, BatchIn in, BatchOut out)
 {
-  static_assert((kListCap / 16) * 2 <= 64, "one hit bit per (pass, chunk)");
+  static_assert((kListCap / kFiltPps) * kFiltCpl <= 64, "one hit bit per (pass, chunk)");
   // three probe lists per wave: two take turns holding the current and the next group, the third the current group's probes
   // that go on in the second line
   __shared__ uint32_t s_row[kScanWaves][3][kListCap], s_q[kScanWaves][3][kListCap], s_tag[kScanWaves][3][kListCap], s_queue[kScanWaves][64];

@@ -177,7 +177,7 @@ struct GroupGen {
 template <int LOG_G, int CPL, int DEPTH, bool SL>
 __device__ __forceinline__ void pipe_issue(const DevIndex& ix, const SlotList& L, uint32_t nact, uint32_t c, uint4 (&v)[DEPTH * CPL])
 {
-  constexpr uint32_t G = 1u << LOG_G, PPS = 64u >> LOG_G, W = G * CPL * 4u;
+  constexpr uint32_t G = 1u << LOG_G, PPS = 64u >> LOG_G, W = scan_slot_words(LOG_G, CPL);
   const uint32_t lane = lane_id(), sub = lane & (G - 1u);
 #pragma unroll
   for (int d = 0; d < DEPTH; ++d) {
@@ -198,7 +198,7 @@ template <int LOG_G, int CPL, int DEPTH, bool SL, bool TAP>
 __device__ __forceinline__ uint64_t pipe_test(const DevIndex& ix, const DevParams& P, const BatchOut& out, ScanWave& sw, const SlotList& L,
                                               const GroupDesc& g, uint32_t c, const uint4 (&v)[DEPTH * CPL])
 {
-  constexpr uint32_t G = 1u << LOG_G, PPS = 64u >> LOG_G, W = G * CPL * 4u, CAP = W - 2u;
+  constexpr uint32_t G = 1u << LOG_G, PPS = 64u >> LOG_G, W = scan_slot_words(LOG_G, CPL), CAP = scan_slot_cap(LOG_G, CPL);
   const uint32_t lane = lane_id(), sub = lane & (G - 1u);
   uint64_t bits = 0;
 #pragma unroll
@@ -245,7 +245,7 @@ template <int LOG_G, int CPL, bool SL, bool TAP>
 __device__ __forceinline__ void pipe_resolve(const DevIndex& ix, const DevParams& P, const BatchOut& out, ScanWave& sw, const SlotList& L,
                                              lds_u32* queue, const GroupDesc& g, uint64_t hitbits)
 {
-  constexpr uint32_t G = 1u << LOG_G, PPS = 64u >> LOG_G, W = G * CPL * 4u, CAP = W - 2u;
+  constexpr uint32_t G = 1u << LOG_G, PPS = 64u >> LOG_G, W = scan_slot_words(LOG_G, CPL), CAP = scan_slot_cap(LOG_G, CPL);
   const uint32_t lane = lane_id(), sub = lane & (G - 1u);
   const uint32_t cnt = (uint32_t)__popcll(hitbits);
   const uint32_t inc = wave_scan_incl(cnt);

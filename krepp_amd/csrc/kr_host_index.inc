@@ -3,6 +3,7 @@
 struct kr_index {
   int device = 0;
   uint32_t log_g = 0;           // lanes per probe in the bucket scan = 2^log_g (from the mean bucket length)
+  uint32_t occ = 0;             // 1: the packed tables carry a row-occupancy bitmap (sparse tables)
   uint32_t slot_log2w = 0;      // slotted table copy: format code (slot_words(): 5 / 6 / 7 = 32 / 64 / 128 words, 8 = 48 words; 0: none)
   DevIndex dix;
   std::vector<DevLib> hlibs;    // host copy of the device DevLib array
@@ -120,6 +121,7 @@ int alloc_from_desc(kr_index* ix, const DescHeader& H, const std::vector<DescLib
   ix->bufs.push_back({p, b});
   ix->dix.nleaves = H.nleaves;
   ix->log_g = H.log_g;
+  ix->occ = H.occ;
   ix->slot_log2w = H.slot_log2w;
   b = (uint64_t)H.m * 4;
   if ((rc = dev_alloc(ix, &p, b))) return rc;
@@ -451,6 +453,8 @@ void kr_index_free(kr_index* ix)
 uint64_t kr_index_device_bytes(const kr_index* ix) { return ix ? ix->bytes : 0; }
 uint32_t kr_index_slot_words(const kr_index* ix) { return ix && ix->slot_log2w ? slot_words(ix->slot_log2w) : 0; }
 uint32_t kr_index_slot_format(const kr_index* ix) { return ix ? ix->slot_log2w : 0; }
+uint32_t kr_index_log_g(const kr_index* ix) { return ix ? ix->log_g : 0; }
+uint32_t kr_index_occ_bitmap(const kr_index* ix) { return ix ? ix->occ : 0; }
 
 int kr_index_export(const kr_index* ix, void* desc, uint64_t* desc_bytes, kr_index_buffer* bufs, uint32_t* nbufs)
 {

@@ -229,6 +229,8 @@ struct kr_stream {
   std::string batch_msg;
   uint32_t nreads = 0, flags = 0, nrecs = 0;
   uint32_t scan_blocks = 0, scan_pipe_blocks = 0, scan_filt_blocks = 0;
+  bool scan_pipe = true; // slotted tables: the pipelined scan kernel (KR_SCAN_PIPE=0 when the stream was made: the one-group-at-a-time kernel)
+  uint32_t item_cap_dbg = 0; // (tests) KR_DEBUG_ITEM_CAP when the stream was made: item slots a lane's scan is told its list holds (0: all of them)
   bool fk = false; // the index has filter slots (format 9) and this stream's threshold fits their candidates: kr_scan_filt_kernel_t + FK accumulate
   uint64_t nhits = 0;
 };
@@ -474,9 +476,9 @@ void launch_scan(kr_stream* s, Lane& L, bool single, bool tap)
   BatchOut& o = L.out;
   const dim3 block(kScanWaves * kWave);
   auto grid = [&](uint32_t blocks) { return dim3(std::min<uint32_t>((L.nreads + kScanWaves - 1) / kScanWaves, blocks)); };
-  // slotted tables: the scan as a software pipeline across probe groups (kr_dev_scan_pipe.inc); KR_SCAN_PIPE=0: the
-  // one-group-at-a-time kernel
-  static const bool pipe = !getenv("KR_SCAN_PIPE") || atoi(getenv("KR_SCAN_PIPE")) != 0;
+  // slotted tables: the scan as a software pipeline across probe groups (kr_dev_scan_pipe.inc); KR_SCAN_PIPE=0 (read when the
+  // stream is made): the one-group-at-a-time kernel
+  const bool pipe = s->scan_pipe;
   with_bools([&](auto SL, auto TAP) {
     if (s->fk) { // filter slots: one line per probe, candidates verified by the accumulate kernel
       hipLaunchKernelGGL((kr_scan_filt_kernel_t<KR_SCAN_FILT_DEPTH, KR_SCAN_FILT_WPE, SL.value, TAP.value>), grid(s->scan_filt_blocks), block, 0, st, dix, s->dp, L.in, o);
@@ -800,6 +802,9 @@ int kr_stream_create(const kr_index* ix, const kr_params* p, uint32_t max_reads,
   if (const char* e = getenv("KR_DEBUG_SCAN_BLOCKS_PER_CU"))
     s->scan_blocks = s->scan_pipe_blocks = s->scan_filt_blocks = (uint32_t)prop.multiProcessorCount * (uint32_t)std::max(1, atoi(e));
   s->fk = ix->slot_log2w == kSlotFilter && p->hdist_th <= kFiltMaxTh && !getenv("KR_NO_FILTER_SCAN");
+  s->scan_pipe = !getenv("KR_SCAN_PIPE") || atoi(getenv("KR_SCAN_PIPE")) != 0;
+  // KR_DEBUG_ITEM_CAP=n (tests): the scan of every lane is told that its item list holds n slots -- only ever fewer than it does
+  if (const char* e = getenv("KR_DEBUG_ITEM_CAP")) s->item_cap_dbg = (uint32_t)std::min<uint64_t>(strtoull(e, nullptr, 10), 0xFFFFFFFFull);
   s->item_cap = (uint32_t)std::min<uint64_t>((uint64_t)max_reads * 256u + (uint64_t)ML * std::max(std::max(s->scan_blocks, s->scan_pipe_blocks), s->scan_filt_blocks) * kScanWaves * 2u * kItemChunk, 1ull << 31);
   if ((rc = new_item_list(s.get(), s->items))) { kr_stream_destroy(s.release()); return rc; }
   o.items = s->items.get();
@@ -1063,7 +1068,8 @@ static int submit_batch(kr_stream* s, const uint8_t* bases, const uint64_t* offs
     s->out.hits = s->d_hits.get();
   }
   const uint32_t lane_rec_cap = P == 1 ? s->rec_cap : (s->rec_cap / P) & ~63u;
-  const uint32_t lane_item_cap = s->item_cap / P;
+  const uint32_t lane_item_cap = s->item_cap / P; // (the lane's slice; what its scan may use of it: lane_item_room)
+  const uint32_t lane_item_room = s->item_cap_dbg ? std::min(lane_item_cap, s->item_cap_dbg) : lane_item_cap;
   auto submit_lane = [&](uint32_t l) -> int {
     Lane& L = s->lanes[l];
     const uint32_t r0 = (uint32_t)((uint64_t)nreads * l / P), r1 = (uint32_t)((uint64_t)nreads * (l + 1) / P);
@@ -1120,7 +1126,7 @@ static int submit_batch(kr_stream* s, const uint8_t* bases, const uint64_t* offs
     o.rd_off += r0, o.rd_cnt += r0, o.rd_onmers += r0, o.rd_filt += 2ull * r0, o.rd_na += r0;
     o.rd_it_off += r0, o.rd_it_cnt += r0;
     o.long_list += r0 + 16ull * s->nwaves * l;
-    o.items += (uint64_t)l * lane_item_cap, o.item_cap = lane_item_cap;
+    o.items += (uint64_t)l * lane_item_cap, o.item_cap = lane_item_room;
     const uint64_t rb = L.rec_base;
     o.rec_read += rb, o.rec_key += rb, o.rec_hist += rb, o.rec_d += rb, o.rec_v += rb, o.rec_chisq += rb, o.rec_sel += rb;
     o.rec_w0 += rb, o.rec_rep += rb, o.rep_list += rb + (uint64_t)l * kRepSlack, o.rep_dv += rb + (uint64_t)l * kRepSlack;
@@ -1167,7 +1173,7 @@ struct CounterRule {
   CounterCombine how;
 };
 constexpr CounterRule kCounterRules[] = {
-  {kCtErr, kOr}, {kCtL2Reads, kSum}, {kCtTapHits, kSum}, {kCtRecords, kSum},
+  {kCtErr, kOr}, {kCtL2Reads, kSum}, {kCtTapHits, kSum}, {kCtRecords, kSum}, {kCtItemSlots, kSum},
   {kCtStEvents, kSum}, {kCtStKeys, kSum}, {kCtStBatches, kSum}, {kCtStBig, kSum}, {kCtStLevelTiles, kSum}, {kCtStMaxKeys, kMax}, {kCtStMaxEvents, kMax},
   {kCtCycLevel, kSum}, {kCtCycFinalize, kSum}, {kCtCycRead, kSum},
   {kCtProblems, kSum}, {kCtStackSpills, kSum}, {kCtTileHoles, kSum},
@@ -1654,6 +1660,53 @@ int kr_debug_acc_layout(const kr_stream* s, uint32_t np, uint32_t segs, uint32_t
   const AccLayout l = acc_layout(np, segs, multi != 0);
   out8[0] = l.ev_cap, out8[1] = l.ev_words, out8[2] = kFastKeyWords, out8[3] = kCtPathCount;
   out8[4] = s ? s->out.ev_spill : 0u, out8[5] = s ? s->out.tab_spill : 0u, out8[6] = s ? s->out.kt_spill : 0u, out8[7] = 0;
+  return KR_OK;
+}
+
+// (tests, no device needed) The numbers of the scan shape with_scan_shape picks for a table of `slot_format` (0: packed, shape by
+// log_g; 5..8: slotted; 9: filter slots), the very constants the kernels are instantiated with: out16 = {G lanes per probe, CPL
+// chunks per lane and pass, PPS probes per pass, words per slot (0: packed), CAP entries of a slot, step bits of a group before the
+// hit chunks are dealt out (packed: scan_group's kBits; slotted: the bits a full list uses), kListCap, kItemStage, kItemChunk,
+// kReadChunk, kCursors, kSegPos, codes per line and per slot of format 9 (else 0), 1 if slotted, largest hdist_th of format 9's scan}
+int kr_debug_scan_layout(uint32_t slot_format, uint32_t log_g, uint32_t* out16)
+{
+  kr::clear_error();
+  if (!out16 || log_g > 3 || log_g == 1 || (slot_format != 0 && (slot_format < 5 || slot_format > kSlotFilter)))
+    return kr::fail(KR_ERR_ARG, "kr_debug_scan_layout: bad argument");
+  memset(out16, 0, 16 * sizeof(uint32_t));
+  if (slot_format == kSlotFilter) {
+    out16[0] = kFiltG, out16[1] = kFiltCpl, out16[2] = kFiltPps, out16[3] = slot_words(kSlotFilter), out16[4] = kFiltSlotCodes;
+    out16[5] = (kListCap / kFiltPps) * kFiltCpl, out16[12] = kFiltLineCodes, out16[13] = kFiltSlotCodes, out16[14] = 1;
+  } else {
+    with_scan_shape(slot_format, log_g, [&](auto LG, auto CP, auto SLOTTED) {
+      constexpr uint32_t G = 1u << LG.value, PPS = 64u >> LG.value;
+      out16[0] = G, out16[1] = (uint32_t)CP.value, out16[2] = PPS;
+      if (SLOTTED.value) {
+        out16[3] = scan_slot_words(LG.value, CP.value), out16[4] = scan_slot_cap(LG.value, CP.value);
+        out16[5] = (kListCap / PPS) * (uint32_t)CP.value, out16[14] = 1;
+      } else {
+        out16[5] = scan_step_bits(CP.value);
+      }
+    });
+    if (out16[3] != slot_words(slot_format)) return kr::fail(KR_ERR_STATE, "kr_debug_scan_layout: slot_words() and the scan shape disagree");
+  }
+  out16[6] = kListCap, out16[7] = kItemStage, out16[8] = kItemChunk, out16[9] = kReadChunk, out16[10] = kCursors, out16[11] = kSegPos;
+  out16[15] = kFiltMaxTh;
+  return KR_OK;
+}
+
+// (tests) What the scan of this stream's batches is: out4 = {1 if kr_scan_pipe_kernel_t is launched (a slotted table, formats 5..8, and
+// KR_SCAN_PIPE not 0 when the stream was made), 1 if kr_scan_filt_kernel_t is (format 9 and a threshold its candidates carry), item slots
+// a lane's scan may use (KR_DEBUG_ITEM_CAP), item slots the scan of the batch last waited for asked for (kCtItemSlots, over the lanes)}
+int kr_debug_scan_stream(const kr_stream* s, uint32_t* out4)
+{
+  kr::clear_error();
+  if (!s || !out4) return kr::fail(KR_ERR_ARG, "kr_debug_scan_stream: null argument");
+  const uint32_t f = s->ix->slot_log2w;
+  out4[0] = (!s->fk && f >= 5 && f <= 8 && s->scan_pipe) ? 1u : 0u;
+  out4[1] = s->fk ? 1u : 0u;
+  out4[2] = s->item_cap_dbg ? std::min(s->item_cap, s->item_cap_dbg) : s->item_cap;
+  out4[3] = s->waited ? s->h_counters[kCtItemSlots] : 0u;
   return KR_OK;
 }
 
