@@ -308,6 +308,60 @@ KR_API int kr_debug_last_d2h_bytes(kr_stream*, uint64_t* bytes);
 /* Tests: KR_ROWS_INDEXED -- `extent`: list positions the stream's last indexed launch handed out (holes included; of the first attempt
  * if the batch was then run again without the hint); `fallbacks`: batches of this stream run again so, so far.  Either may be NULL. */
 KR_API int kr_debug_indexed_list(kr_stream*, uint64_t* extent, uint64_t* fallbacks);
+/* Tests: crafted records through the production select and row kernels (tests/select_craft.py, tests/test_gpu_select_forms.py).
+ * `kr_select_tables` is what the stages before the selection leave behind for one lane: the reads' record ranges, the records in key
+ * order, and the values of the distinct likelihood problems, reached through the list (rec_rep = position) or through a direct place
+ * (rec_rep = 0x80000000 | place, dd_direct[place] = position, dd_dv[place] = the value). */
+typedef struct kr_select_tables {
+  uint32_t nreads, nrecs;       /* reads; record slots in use (slots between two reads' ranges belong to nobody) */
+  const uint32_t* rd_off;       /* [nreads] ascending, the ranges [rd_off, rd_off + rd_cnt) disjoint and within nrecs */
+  const uint32_t* rd_cnt;       /* [nreads] */
+  const uint32_t* rd_onmers;    /* [nreads] k-mers of the read */
+  const uint32_t* rec_key;      /* [nrecs] se << 1 | strand, strictly ascending within a read, se below the index's node count */
+  const uint32_t* rec_rep;      /* [nrecs] see above; 0xFFFFFFFF (a hole) only outside the reads' ranges */
+  const uint64_t* rec_w0;       /* [nrecs] the packed problem (hdist_th 4 only), or 0: then rec_hist and rec_read describe the record */
+  const uint32_t* rec_hist;     /* [nrecs][hdist_th + 1] row-major, or NULL if every record has a word */
+  const uint32_t* rec_read;     /* [nrecs] the record's read, or NULL likewise */
+  uint32_t nrep, ndirect;       /* list positions; direct places (0 unless the stream has a direct part: hdist_th 4) */
+  const double* rep_dv;         /* [nrep][2] (d, v) */
+  const uint32_t* dd_direct;    /* [ndirect] list position of the place, 0xFFFFFFFF for a place no record names */
+  const double* dd_dv;          /* [ndirect][2] */
+  uint32_t problems;            /* counters[kCtProblems]: the extent of the list the indexed rows' dist_list covers, at most nrep */
+} kr_select_tables;
+/* What the kernels wrote; every array is the caller's, any may be NULL.  The record arrays are read back behind the select kernel (the
+ * indexed row kernel then reuses rec_d and rec_v), the rows behind the row kernels. */
+typedef struct kr_select_result {
+  uint8_t* rd_na;      /* [nreads] */
+  uint32_t* rd_rcnt;   /* [nreads] rows modes; else as poisoned */
+  uint32_t* rd_roff;   /* [nreads] likewise */
+  uint8_t* rec_sel;    /* [nrecs] */
+  double* rec_d;       /* [nrecs] */
+  double* rec_v;       /* [nrecs] */
+  double* rec_chisq;   /* [nrecs] */
+  uint32_t* rec_rep;   /* [nrecs] behind the select kernel: indexed rows leave the resolved list position there */
+  uint32_t* row_key;   /* [nrecs] rows modes: the first nrows entries are rows, the rest as the device left it */
+  double* row_d;       /* [nrecs] plain rows */
+  uint32_t* row_dix;   /* [nrecs] indexed rows */
+  double* dist_list;   /* [problems] indexed rows */
+  uint64_t nrows;      /* counters[kCtRows] in a rows mode, else 0 */
+  uint32_t rows_mode, rows_indexed, keep_v; /* the lane's BatchOut fields as the submit path derives them from `flags` (the --filter kernel
+                                             * writes rec_v whatever keep_v says) */
+} kr_select_result;
+/* Sets lane 0 of an idle one-lane stream up as kr_batch_submit(flags) would (flags: 0, KR_TAP_ACCS, KR_ROWS_ONLY, KR_ROWS_ONLY |
+ * KR_ROWS_INDEXED), fills every output with 0xA5 bytes, uploads `in`, and runs the select kernel the stream's parameters call for
+ * (form 0: as a batch would, KR_SELECT_LANE included; form 1: the wave-per-read kernel) and, in a rows mode, the row kernels.
+ * KR_ERR_ARG for tables the kernels could not be given safely, KR_ERR_STATE for a stream with a batch in flight or several lanes. */
+KR_API int kr_debug_select(kr_stream*, const kr_select_tables* in, uint32_t flags, uint32_t form, kr_select_result* out);
+/* Tests (no device needed): the checks kr_debug_select makes of `in`, against limits given as numbers: reads and records the stream
+ * holds, nodes of the index (rho entries), hdist_th, and the nodes the stream's direct part is laid out for (BatchOut::dd_nodes: tree nodes
+ * + 1 at hdist_th 4, else 0; the library multiplies by its places per node).  KR_OK or KR_ERR_ARG. */
+KR_API int kr_debug_select_check(const kr_select_tables* in, uint32_t max_reads, uint64_t max_records, uint32_t nnodes, uint32_t hdist_th,
+                                 uint32_t direct_nodes);
+/* Tests (no device needed): the constants the select and row kernels are compiled with: out8 = {most records of a read a lane walks
+ * itself (kSelectLaneMax), lanes of the small and of the middle group (16, 32), lanes per read of the wave-per-read kernel
+ * (KR_SELECT_GL), most records the big form keeps in registers (256), records per step of its second pass in memory (128), reads per
+ * block of the row kernels (kRowBlock), reads the row kernel's workgroup takes per round (16)}. */
+KR_API int kr_debug_select_layout(uint32_t* out8);
 /* Tests: path witnesses of the accumulate kernel for the batch last waited for, counted only by a stream created under
  * KR_DEBUG_SKIP=512 (0 otherwise): the first min(n, 21) into `out`, in this order -- finalize_events_fast: calls, returned false before
  * the compaction, compaction entered, returned false after it, finish_big_read, finished in one key batch, in several, key batches

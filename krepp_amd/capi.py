@@ -96,6 +96,19 @@ class KrSdustResult(C.Structure):
     _fields_ = [("intervals", u64p), ("offsets", u64p), ("ncontigs", C.c_uint32)]
 
 
+class KrSelectTables(C.Structure):
+    _fields_ = [("nreads", C.c_uint32), ("nrecs", C.c_uint32), ("rd_off", u32p), ("rd_cnt", u32p), ("rd_onmers", u32p),
+                ("rec_key", u32p), ("rec_rep", u32p), ("rec_w0", u64p), ("rec_hist", u32p), ("rec_read", u32p),
+                ("nrep", C.c_uint32), ("ndirect", C.c_uint32), ("rep_dv", f64p), ("dd_direct", u32p), ("dd_dv", f64p),
+                ("problems", C.c_uint32)]
+
+
+class KrSelectResult(C.Structure):
+    _fields_ = [("rd_na", u8p), ("rd_rcnt", u32p), ("rd_roff", u32p), ("rec_sel", u8p), ("rec_d", f64p), ("rec_v", f64p),
+                ("rec_chisq", f64p), ("rec_rep", u32p), ("row_key", u32p), ("row_d", f64p), ("row_dix", u32p), ("dist_list", f64p),
+                ("nrows", C.c_uint64), ("rows_mode", C.c_uint32), ("rows_indexed", C.c_uint32), ("keep_v", C.c_uint32)]
+
+
 # every symbol include/krepp_amd.h declares (tests check that the library exports them all)
 EXPORTS = [
     "kr_host_index_load", "kr_host_sketch_load", "kr_format_seek", "kr_build_sketch", "kr_host_index_free", "kr_host_index_view", "kr_host_index_node_name",
@@ -107,7 +120,7 @@ EXPORTS = [
     "kr_debug_front_end", "kr_debug_stream_move", "kr_debug_stream_addrs", "kr_debug_item_placement", "kr_debug_brent", "kr_debug_prefix", "kr_debug_colour_classes", "kr_llh_batch", "kr_llh_eval_indexed", "kr_batch_timing",
     "kr_place_tree_create", "kr_place_tree_create_lineage", "kr_place_tree_nnodes", "kr_place_summary_add",
     "kr_place_summary_text", "kr_place_tree_free", "kr_place_tree_kinds", "kr_place_batch", "kr_place_stream", "kr_place_stream_parsed", "kr_debug_place_ids", "kr_place_frame", "kr_place_counters",
-    "kr_debug_last_d2h_bytes", "kr_debug_indexed_list", "kr_debug_acc_paths", "kr_debug_acc_layout", "kr_debug_scan_layout", "kr_debug_scan_stream", "kr_debug_place_fixed5", "kr_place_text_counters", "kr_place_path_counters", "kr_fastx_open", "kr_fastx_open_at", "kr_fastx_next", "kr_fastx_detach", "kr_fastx_release", "kr_fastx_close", "kr_fastx_parallel_chunks", "kr_fastx_pgz_stats", "kr_format_dist", "kr_debug_fixed5", "kr_free", "kr_host_alloc", "kr_host_free",
+    "kr_debug_last_d2h_bytes", "kr_debug_indexed_list", "kr_debug_select", "kr_debug_select_check", "kr_debug_select_layout", "kr_debug_acc_paths", "kr_debug_acc_layout", "kr_debug_scan_layout", "kr_debug_scan_stream", "kr_debug_place_fixed5", "kr_place_text_counters", "kr_place_path_counters", "kr_fastx_open", "kr_fastx_open_at", "kr_fastx_next", "kr_fastx_detach", "kr_fastx_release", "kr_fastx_close", "kr_fastx_parallel_chunks", "kr_fastx_pgz_stats", "kr_format_dist", "kr_debug_fixed5", "kr_free", "kr_host_alloc", "kr_host_free",
     "kr_build_index", "kr_minimizers_cpu", "kr_minimizers_device", "kr_minimizers_free", "kr_last_error", "kr_version",
     "kr_sdust_cpu", "kr_sdust_free",
 ]
@@ -171,6 +184,9 @@ def load():
     lib.kr_debug_stream_addrs.argtypes = [vp, u64p]
     lib.kr_debug_item_placement.argtypes = [vp, u32p, u32p, C.POINTER(C.c_double)]
     lib.kr_debug_acc_paths.argtypes = [vp, u32p, C.c_uint32]
+    lib.kr_debug_select.argtypes = [vp, C.POINTER(KrSelectTables), C.c_uint32, C.c_uint32, C.POINTER(KrSelectResult)]
+    lib.kr_debug_select_check.argtypes = [C.POINTER(KrSelectTables), C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32]
+    lib.kr_debug_select_layout.argtypes = [u32p]
     lib.kr_debug_acc_layout.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, u32p]
     lib.kr_index_slot_words.restype = C.c_uint32
     lib.kr_params_default.argtypes = [C.POINTER(KrParams)]
@@ -532,6 +548,23 @@ class Stream:
     def acc_layout(self, segs=1, multi=0):
         return acc_layout(self.params.hdist_th + 1, segs, multi, self)
 
+    def debug_select(self, tables, flags=0, form=0):
+        """(tests) kr_debug_select: crafted records (a dict as select_tables takes it) through the select and row kernels of this idle
+        one-lane stream; what they wrote, as a dict of numpy arrays (record arrays as the select kernel left them, rows as the row
+        kernels did), with nrows and the lane's rows_mode / rows_indexed / keep_v"""
+        t, keep = select_tables(tables)
+        nreads, nrecs, nprob = t.nreads, t.nrecs, t.problems
+        shapes = dict(rd_na=(np.uint8, nreads), rd_rcnt=(np.uint32, nreads), rd_roff=(np.uint32, nreads), rec_sel=(np.uint8, nrecs),
+                      rec_d=(np.float64, nrecs), rec_v=(np.float64, nrecs), rec_chisq=(np.float64, nrecs), rec_rep=(np.uint32, nrecs),
+                      row_key=(np.uint32, nrecs), row_d=(np.float64, nrecs), row_dix=(np.uint32, nrecs), dist_list=(np.float64, nprob))
+        out = {k: np.full(n * np.dtype(dt).itemsize, 0x5A, np.uint8).view(dt) for k, (dt, n) in shapes.items()}  # (0x5A: not copied back)
+        r = KrSelectResult()
+        for k, a in out.items():
+            setattr(r, k, a.ctypes.data_as(dict(KrSelectResult._fields_)[k]) if a.size else None)
+        check(self.lib.kr_debug_select(self.h, C.byref(t), int(flags), int(form), C.byref(r)))
+        out.update(nrows=int(r.nrows), rows_mode=int(r.rows_mode), rows_indexed=int(r.rows_indexed), keep_v=int(r.keep_v))
+        return out
+
     def scan_info(self):
         """(tests) kr_debug_scan_stream: which scan kernel this stream launches, the item slots a lane's scan may use, and the item
         slots the batch last waited for asked for"""
@@ -735,6 +768,39 @@ def acc_layout(np_planes, segs=1, multi=0, stream=None):
 
 SCAN_LAYOUT = ("G", "CPL", "PPS", "W", "CAP", "step_bits", "list_cap", "item_stage", "item_chunk", "read_chunk", "cursors", "seg_pos",
                "line_codes", "slot_codes", "slotted", "filt_max_th")
+
+
+SELECT_LAYOUT = ("lane_max", "group_small", "group_mid", "wave_gl", "big_regs", "big_step2", "row_block", "row_round")
+
+
+def select_layout():
+    """(tests) kr_debug_select_layout: the constants of the select and row kernels, by name"""
+    a = (C.c_uint32 * 8)()
+    check(load().kr_debug_select_layout(a))
+    return dict(zip(SELECT_LAYOUT, [int(x) for x in a]))
+
+
+def select_tables(t):
+    """KrSelectTables over the arrays of dict `t` (keys as the structure's fields; rec_hist [nrecs, th + 1] and rec_read optional,
+    counts taken from the arrays unless given); returns it with the arrays that must outlive it"""
+    spec = dict(rd_off=np.uint32, rd_cnt=np.uint32, rd_onmers=np.uint32, rec_key=np.uint32, rec_rep=np.uint32, rec_w0=np.uint64,
+                rec_hist=np.uint32, rec_read=np.uint32, rep_dv=np.float64, dd_direct=np.uint32, dd_dv=np.float64)
+    keep = {k: np.ascontiguousarray(t[k], dtype=dt) for k, dt in spec.items() if t.get(k) is not None}
+    s = KrSelectTables()
+    for k, a in keep.items():
+        setattr(s, k, a.ctypes.data_as(dict(KrSelectTables._fields_)[k]) if a.size else None)
+    s.nreads = int(t.get("nreads", len(keep["rd_off"])))
+    s.nrecs = int(t.get("nrecs", len(keep["rec_key"]) if "rec_key" in keep else 0))
+    s.nrep = int(t.get("nrep", keep["rep_dv"].size // 2 if "rep_dv" in keep else 0))
+    s.ndirect = int(t.get("ndirect", len(keep["dd_direct"]) if "dd_direct" in keep else 0))
+    s.problems = int(t.get("problems", s.nrep))
+    return s, keep
+
+
+def select_check(t, max_reads, max_records, nnodes, hdist_th=4, direct_nodes=0):
+    """(tests, no device) kr_debug_select_check: the return code.  direct_nodes: the nodes the stream's direct part is laid out for"""
+    s, keep = select_tables(t)
+    return load().kr_debug_select_check(C.byref(s), int(max_reads), int(max_records), int(nnodes), int(hdist_th), int(direct_nodes))
 
 
 def scan_layout(slot_format, log_g=0):

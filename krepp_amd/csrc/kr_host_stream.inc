@@ -549,7 +549,14 @@ void launch_likelihood(kr_stream* s, Lane& L)
   if (direct) hipLaunchKernelGGL(kr_dedup_dv_kernel, dim3(std::min<uint32_t>((places + 1023u) / 1024u, 4096u)), dim3(256), 0, st, o);
 }
 
-void launch_select(kr_stream* s, Lane& L)
+// without --filter: a lane per read (kr_select_lane_kernel) by default; KR_SELECT_LANE=0 (read once per process): the wave-per-read kernel
+// for every read
+bool select_lane_default()
+{
+  static const bool lane_sel = !getenv("KR_SELECT_LANE") || atoi(getenv("KR_SELECT_LANE")) != 0;
+  return lane_sel;
+}
+void launch_select(kr_stream* s, Lane& L, bool lane_sel = select_lane_default())
 {
   hipStream_t st = L.stream;
   const DevIndex& dix = s->ix->dix;
@@ -557,8 +564,6 @@ void launch_select(kr_stream* s, Lane& L)
   const uint32_t nreads = L.nreads;
   const uint32_t sgrid = std::min<uint32_t>((nreads + 7) / 8, 16384u);
   const bool filt = !s->dp.no_filter && s->dp.multi;
-  // without --filter: a lane per read (kr_select_lane_kernel); KR_SELECT_LANE=0: the wave-per-read kernel for every read
-  static const bool lane_sel = !getenv("KR_SELECT_LANE") || atoi(getenv("KR_SELECT_LANE")) != 0;
   const uint32_t lgrid = std::min<uint32_t>((nreads + 255) / 256, 8192u);
   with_bools([&](auto NP5, auto FILT) {
     constexpr int NPV = NP5.value ? 5 : 0;
@@ -620,6 +625,49 @@ void launch_rebase(kr_stream* s, Lane& L)
   BatchOut& o = L.out;
   if (L.rec_base) // the result view indexes the stream's arrays, the lane's kernels its slice
     hipLaunchKernelGGL(kr_rebase_kernel, dim3(std::min<uint32_t>((L.nreads + 255) / 256, 1024u)), dim3(256), 0, st, o.rd_off, o.rd_cnt, L.nreads, L.rec_base);
+}
+
+// How a batch submitted with `flags` in P lanes leaves the device (kr_stream::rows_mode / rows_indexed)
+void set_row_modes(kr_stream* s, uint32_t flags, uint32_t P)
+{
+  // (a tiled batch keeps its record slots unless the caller asks for rows with KR_TILE_ROWS)
+  s->rows_mode = (flags & KR_ROWS_ONLY) && !(flags & (KR_TAP_ACCS | KR_TAP_HITS)) && (!s->tiles.active || (flags & KR_TILE_ROWS)) && !getenv("KR_NO_ROW_COMPACTION");
+  // KR_ROWS_INDEXED: 8-byte rows (key, position of DIST in the batch's distinct values).  One lane (a lane's positions are its own),
+  // not tiled, no --filter (its select kernel writes rec_v, which the list of values aliases), no device text (its kernels read row_d)
+  // (no_indexed: this is the rerun of a batch whose list positions outgrew dist_list)
+  s->rows_indexed = s->rows_mode && (flags & KR_ROWS_INDEXED) && P == 1 && !s->tiles.active && !(!s->dp.no_filter && s->dp.multi) && !s->text.req && !s->no_indexed;
+}
+// Lane l's view of the output for a batch submitted with `flags` (set_row_modes has run): private scratch + slices of the stream's
+// arrays, the lane's reads starting at r0.  One function for kr_batch_submit and kr_debug_select: the aliases of the row arrays
+// (rec_rep / rep_dv, indexed: rec_d / rec_v) exist once.
+void set_lane_view(kr_stream* s, Lane& L, uint32_t l, uint32_t r0, uint32_t flags, uint32_t lane_rec_cap, uint32_t lane_item_cap, uint32_t lane_item_room,
+                   const ListCaps& list_caps)
+{
+  BatchOut& o = L.out;
+  o = s->out;
+  o.counters = L.d_counters, o.cursors = L.d_cursors;
+  o.dd_table = L.d_dd, o.dd_slots = L.dd_slots;
+  o.dd_direct = L.d_dd_direct, o.dd_dv = L.d_dd_dv, o.dd_ohist = L.d_dd_ohist, o.dd_oslot = L.d_dd_oslot;
+  o.g_planes = L.d_g_planes, o.g_counts = L.d_g_counts, o.g_list = L.d_g_list, o.stk_spill = L.d_stk;
+  o.rd_off += r0, o.rd_cnt += r0, o.rd_onmers += r0, o.rd_filt += 2ull * r0, o.rd_na += r0;
+  o.rd_it_off += r0, o.rd_it_cnt += r0;
+  o.long_list += r0 + 16ull * s->nwaves * l;
+  o.items += (uint64_t)l * lane_item_cap, o.item_cap = lane_item_room;
+  const uint64_t rb = L.rec_base;
+  o.rec_read += rb, o.rec_key += rb, o.rec_hist += rb, o.rec_d += rb, o.rec_v += rb, o.rec_chisq += rb, o.rec_sel += rb;
+  o.rec_w0 += rb, o.rec_rep += rb, o.rep_list += rb + (uint64_t)l * kRepSlack, o.rep_dv += rb + (uint64_t)l * kRepSlack;
+  o.rec_cap = lane_rec_cap;
+  o.rep_cap = list_caps.lower((uint32_t)std::min<uint64_t>((uint64_t)lane_rec_cap + kRepSlack, 0xFFFFFFFFull), list_caps.rep);
+  o.dist_cap = list_caps.lower(lane_rec_cap, list_caps.dist);
+  o.keep_v = ((flags & KR_ROWS_ONLY) && !(flags & KR_TAP_ACCS)) ? 0u : 1u;
+  o.hist_always = (flags & KR_TAP_ACCS) ? 1u : 0u; // else a record's planes exist only where its packed word cannot describe it
+  o.v_tile = s->tiles.active ? s->tiles.d_vtile.get() : nullptr;
+  o.rows_mode = s->rows_mode ? 1u : 0u;
+  o.rd_rcnt += r0, o.rd_roff += r0, o.row_bsum += r0 / kRowBlock + 2ull * l;
+  o.row_key = o.rec_rep, o.row_d = reinterpret_cast<double*>(o.rep_dv); // (the lane's slices: dead once the select kernel has run)
+  o.rows_indexed = s->rows_indexed ? 1u : 0u;
+  if (s->rows_indexed) // (see BatchOut: the row kernel reads rec_rep here, so its output lies in rec_d; the values in rec_v)
+    o.row_key = reinterpret_cast<uint32_t*>(o.rec_d), o.row_dix = o.row_key + lane_rec_cap, o.dist_list = o.rec_v;
 }
 
 // Queue the kernels of one lane on its stream.
@@ -1056,12 +1104,7 @@ static int submit_batch(kr_stream* s, const uint8_t* bases, const uint64_t* offs
   if (s->text.req) P = 1; // (one text buffer, one prefix over the reads)
   s->text.made = false;
   s->nlanes = P;
-  // (a tiled batch keeps its record slots unless the caller asks for rows with KR_TILE_ROWS)
-  s->rows_mode = (flags & KR_ROWS_ONLY) && !(flags & (KR_TAP_ACCS | KR_TAP_HITS)) && (!s->tiles.active || (flags & KR_TILE_ROWS)) && !getenv("KR_NO_ROW_COMPACTION");
-  // KR_ROWS_INDEXED: 8-byte rows (key, position of DIST in the batch's distinct values).  One lane (a lane's positions are its own),
-  // not tiled, no --filter (its select kernel writes rec_v, which the list of values aliases), no device text (its kernels read row_d)
-  // (no_indexed: this is the rerun of a batch whose list positions outgrew dist_list)
-  s->rows_indexed = s->rows_mode && (flags & KR_ROWS_INDEXED) && P == 1 && !s->tiles.active && !(!s->dp.no_filter && s->dp.multi) && !s->text.req && !s->no_indexed;
+  set_row_modes(s, flags, P);
   const ListCaps list_caps = debug_list_caps();
   if (flags & KR_TAP_HITS) {
     if (!reserve_all(s->hit_cap, s->d_hits, s->h_hits)) return alloc_failed("kr_batch_submit: hit tap buffers");
@@ -1116,32 +1159,7 @@ static int submit_batch(kr_stream* s, const uint8_t* bases, const uint64_t* offs
       HIP_TRY(hipMemcpyAsync(s->text.d_id_off, s->text.h_id_off, ((uint64_t)nreads + 1) * 4, hipMemcpyHostToDevice, st));
     }
     L.in.nreads = L.nreads;
-    // the lane's view of the output: private scratch + slices of the stream's arrays
-    BatchOut& o = L.out;
-    o = s->out;
-    o.counters = L.d_counters, o.cursors = L.d_cursors;
-    o.dd_table = L.d_dd, o.dd_slots = L.dd_slots;
-    o.dd_direct = L.d_dd_direct, o.dd_dv = L.d_dd_dv, o.dd_ohist = L.d_dd_ohist, o.dd_oslot = L.d_dd_oslot;
-    o.g_planes = L.d_g_planes, o.g_counts = L.d_g_counts, o.g_list = L.d_g_list, o.stk_spill = L.d_stk;
-    o.rd_off += r0, o.rd_cnt += r0, o.rd_onmers += r0, o.rd_filt += 2ull * r0, o.rd_na += r0;
-    o.rd_it_off += r0, o.rd_it_cnt += r0;
-    o.long_list += r0 + 16ull * s->nwaves * l;
-    o.items += (uint64_t)l * lane_item_cap, o.item_cap = lane_item_room;
-    const uint64_t rb = L.rec_base;
-    o.rec_read += rb, o.rec_key += rb, o.rec_hist += rb, o.rec_d += rb, o.rec_v += rb, o.rec_chisq += rb, o.rec_sel += rb;
-    o.rec_w0 += rb, o.rec_rep += rb, o.rep_list += rb + (uint64_t)l * kRepSlack, o.rep_dv += rb + (uint64_t)l * kRepSlack;
-    o.rec_cap = lane_rec_cap;
-    o.rep_cap = list_caps.lower((uint32_t)std::min<uint64_t>((uint64_t)lane_rec_cap + kRepSlack, 0xFFFFFFFFull), list_caps.rep);
-    o.dist_cap = list_caps.lower(lane_rec_cap, list_caps.dist);
-    o.keep_v = ((flags & KR_ROWS_ONLY) && !(flags & KR_TAP_ACCS)) ? 0u : 1u;
-    o.hist_always = (flags & KR_TAP_ACCS) ? 1u : 0u; // else a record's planes exist only where its packed word cannot describe it
-    o.v_tile = s->tiles.active ? s->tiles.d_vtile.get() : nullptr;
-    o.rows_mode = s->rows_mode ? 1u : 0u;
-    o.rd_rcnt += r0, o.rd_roff += r0, o.row_bsum += r0 / kRowBlock + 2ull * l;
-    o.row_key = o.rec_rep, o.row_d = reinterpret_cast<double*>(o.rep_dv); // (the lane's slices: dead once the select kernel has run)
-    o.rows_indexed = s->rows_indexed ? 1u : 0u;
-    if (s->rows_indexed) // (see BatchOut: the row kernel reads rec_rep here, so its output lies in rec_d; the values in rec_v)
-      o.row_key = reinterpret_cast<uint32_t*>(o.rec_d), o.row_dix = o.row_key + lane_rec_cap, o.dist_list = o.rec_v;
+    set_lane_view(s, L, l, r0, flags, lane_rec_cap, lane_item_cap, lane_item_room, list_caps);
     return launch_lane(s, L, flags);
   };
   for (uint32_t l = 0; l < P; ++l) {
@@ -1635,6 +1653,154 @@ int kr_debug_indexed_list(kr_stream* s, uint64_t* extent, uint64_t* fallbacks)
   if (!s) return kr::fail(KR_ERR_ARG, "kr_debug_indexed_list: null argument");
   if (extent) *extent = s->ix_extent;
   if (fallbacks) *fallbacks = s->ix_fallbacks;
+  return KR_OK;
+}
+
+// (tests, no device needed) The constants of the select and row kernels (kr_dev_likelihood.inc) that decide which form a read of n
+// records takes.  kSelectLaneMax, KR_SELECT_GL and kRowBlock are the kernels' own; the others are literals there -- the ballots of
+// kr_select_lane_kernel (n <= 16, n <= 32), select_big_read (n <= 256: registers; t0 += 128: its second pass), kr_rows_write_kernel
+// (U = 4 reads for each of the workgroup's four waves) -- and are restated here.
+int kr_debug_select_layout(uint32_t* out8)
+{
+  kr::clear_error();
+  if (!out8) return kr::fail(KR_ERR_ARG, "kr_debug_select_layout: null argument");
+  out8[0] = kSelectLaneMax, out8[1] = 16, out8[2] = 32, out8[3] = KR_SELECT_GL, out8[4] = 256, out8[5] = 128, out8[6] = kRowBlock, out8[7] = 16;
+  return KR_OK;
+}
+
+// what kr_debug_select requires of its tables, given the limits of a stream (kr_debug_select_check: the same without one)
+static int select_check(const kr_select_tables* in, uint32_t max_reads, uint64_t max_records, uint32_t nnodes, uint32_t hdist_th, uint32_t places)
+{
+  auto bad = [](const char* what) { return kr::fail(KR_ERR_ARG, std::string("kr_debug_select: ") + what); };
+  const uint32_t nreads = in->nreads, nrecs = in->nrecs;
+  if (nreads == 0 || nreads > max_reads) return bad("nreads out of range for this stream");
+  if (nrecs > max_records) return bad("more records than the stream's max_records");
+  if (!in->rd_off || !in->rd_cnt || !in->rd_onmers) return bad("null read table");
+  if (nrecs && (!in->rec_key || !in->rec_rep || !in->rec_w0)) return bad("null record table");
+  if ((in->rec_hist == nullptr) != (in->rec_read == nullptr)) return bad("rec_hist and rec_read come together");
+  if (in->nrep > max_records || in->problems > in->nrep || (in->nrep && !in->rep_dv)) return bad("list of distinct problems out of range");
+  if (in->ndirect > places || (in->ndirect && (!in->dd_direct || !in->dd_dv))) return bad("direct places out of range");
+  uint64_t end = 0;
+  for (uint32_t r = 0; r < nreads; ++r) {
+    const uint64_t o = in->rd_off[r], n = in->rd_cnt[r];
+    if (o < end || o + n > nrecs) return bad("read ranges overlap, descend or leave the records");
+    end = o + n;
+    for (uint64_t i = o; i < o + n; ++i) {
+      const uint32_t key = in->rec_key[i], rep = in->rec_rep[i];
+      if (i > o && key <= in->rec_key[i - 1]) return bad("keys of a read do not ascend strictly");
+      if ((key >> 1) >= nnodes) return bad("key beyond the index's nodes");
+      if (rep == 0xFFFFFFFFu) return bad("hole inside a read");
+      if (rep & kDdDirectFlag) {
+        const uint32_t pl = rep & ~kDdDirectFlag;
+        if (pl >= in->ndirect || in->dd_direct[pl] >= in->nrep) return bad("direct place out of range");
+      } else if (rep >= in->nrep) {
+        return bad("list position out of range");
+      }
+      if (in->rec_w0[i] != 0 ? hdist_th != 4 : (!in->rec_hist || in->rec_read[i] != r)) return bad("record without a problem");
+    }
+  }
+  return KR_OK;
+}
+int kr_debug_select_check(const kr_select_tables* in, uint32_t max_reads, uint64_t max_records, uint32_t nnodes, uint32_t hdist_th, uint32_t direct_nodes)
+{
+  kr::clear_error();
+  if (!in) return kr::fail(KR_ERR_ARG, "kr_debug_select_check: null argument");
+  if (direct_nodes > (1u << 20)) return kr::fail(KR_ERR_ARG, "kr_debug_select_check: direct_nodes out of range");
+  return select_check(in, max_reads, max_records, nnodes, hdist_th, kDdOslots * kDdClasses * direct_nodes);
+}
+// (tests) Crafted records through the select and row kernels as a one-lane batch submitted with `flags` would run them: the lane's view
+// is set_lane_view's, the launches are launch_select's and launch_rows'.  Everything the kernels may read is checked first: a table that
+// passes cannot send them outside the stream's buffers.
+int kr_debug_select(kr_stream* s, const kr_select_tables* in, uint32_t flags, uint32_t form, kr_select_result* out)
+{
+  kr::clear_error();
+  if (!s || !in || !out) return kr::fail(KR_ERR_ARG, "kr_debug_select: null argument");
+  if (s->max_lanes != 1 || (s->submitted && !s->waited)) return kr::fail(KR_ERR_STATE, "kr_debug_select: needs an idle one-lane stream");
+  auto bad = [](const char* what) { return kr::fail(KR_ERR_ARG, std::string("kr_debug_select: ") + what); };
+  if (form > 1) return bad("form is 0 or 1");
+  if (flags != 0 && flags != KR_TAP_ACCS && flags != KR_ROWS_ONLY && flags != (KR_ROWS_ONLY | KR_ROWS_INDEXED)) return bad("unsupported flags");
+  if (int rc = select_check(in, s->max_reads, std::min<uint64_t>(s->rec_user_cap, s->rec_cap), s->ix->dix.libs[0].nnodes, s->llh.th, kDdOslots * kDdClasses * s->out.dd_nodes))
+    return rc;
+  const uint32_t nreads = in->nreads, nrecs = in->nrecs, np = s->dp.np;
+  HIP_TRY(hipSetDevice(s->device));
+  Lane& L = s->lanes[0];
+  hipStream_t st = L.stream;
+  s->tiles.active = false, s->text.req = false; // (a crafted batch is neither tiled nor text)
+  s->nlanes = 1, s->submitted = false, s->waited = false;
+  set_row_modes(s, flags, 1);
+  L.read0 = 0, L.nreads = nreads, L.rec_base = 0, L.rec_cap = s->rec_cap, L.nrecs = nrecs;
+  set_lane_view(s, L, 0, 0, flags, s->rec_cap, s->item_cap, s->item_cap, debug_list_caps());
+  BatchOut& o = L.out;
+  // ---- poison, then the tables (the plain rows alias rec_rep / rep_dv: what is uploaded there stands)
+  const uint64_t nr = nrecs;
+  HIP_TRY(hipMemsetAsync(o.rd_na, 0xA5, nreads, st));
+  HIP_TRY(hipMemsetAsync(o.rd_rcnt, 0xA5, (uint64_t)nreads * 4, st));
+  HIP_TRY(hipMemsetAsync(o.rd_roff, 0xA5, (uint64_t)nreads * 4, st));
+  if (nr) {
+    HIP_TRY(hipMemsetAsync(o.rec_sel, 0xA5, nr, st));
+    HIP_TRY(hipMemsetAsync(o.rec_d, 0xA5, nr * 8, st));
+    HIP_TRY(hipMemsetAsync(o.rec_v, 0xA5, nr * 8, st));
+    HIP_TRY(hipMemsetAsync(o.rec_chisq, 0xA5, nr * 8, st));
+    HIP_TRY(hipMemsetAsync(o.row_key, 0xA5, nr * 4, st));
+    if (o.rows_indexed) HIP_TRY(hipMemsetAsync(o.row_dix, 0xA5, nr * 4, st));
+    else HIP_TRY(hipMemsetAsync(o.row_d, 0xA5, nr * 8, st));
+  }
+  if (o.rows_indexed && in->problems) HIP_TRY(hipMemsetAsync(o.dist_list, 0xA5, (uint64_t)in->problems * 8, st));
+  HIP_TRY(hipMemsetAsync(o.counters, 0, kCounterWords * 4, st));
+  HIP_TRY(hipMemcpyAsync(o.counters + kCtProblems, &in->problems, 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(o.rd_off, in->rd_off, (uint64_t)nreads * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(o.rd_cnt, in->rd_cnt, (uint64_t)nreads * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(o.rd_onmers, in->rd_onmers, (uint64_t)nreads * 4, hipMemcpyHostToDevice, st));
+  std::vector<uint32_t> planes;
+  if (nr) {
+    HIP_TRY(hipMemcpyAsync(o.rec_key, in->rec_key, nr * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(o.rec_rep, in->rec_rep, nr * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(o.rec_w0, in->rec_w0, nr * 8, hipMemcpyHostToDevice, st));
+    if (in->rec_hist) {
+      planes.resize(nr * np);
+      for (uint64_t i = 0; i < nr; ++i)
+        for (uint32_t x = 0; x < np; ++x) planes[x * nr + i] = in->rec_hist[i * np + x];
+      for (uint32_t x = 0; x < np; ++x) HIP_TRY(hipMemcpyAsync(o.rec_hist + x * o.rec_stride, planes.data() + x * nr, nr * 4, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(o.rec_read, in->rec_read, nr * 4, hipMemcpyHostToDevice, st));
+    }
+  }
+  if (in->nrep) HIP_TRY(hipMemcpyAsync(o.rep_dv, in->rep_dv, (uint64_t)in->nrep * 16, hipMemcpyHostToDevice, st));
+  if (in->ndirect) {
+    HIP_TRY(hipMemcpyAsync(o.dd_direct, in->dd_direct, (uint64_t)in->ndirect * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(o.dd_dv, in->dd_dv, (uint64_t)in->ndirect * 16, hipMemcpyHostToDevice, st));
+  }
+  // ---- the select kernel; the record arrays as it leaves them
+  launch_select(s, L, form == 0 ? select_lane_default() : false);
+  HIP_TRY(hipGetLastError());
+  auto back = [&](void* dst, const void* src, uint64_t bytes) -> hipError_t { return (dst && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) : hipSuccess; };
+  HIP_TRY(back(out->rd_na, o.rd_na, nreads));
+  HIP_TRY(back(out->rd_rcnt, o.rd_rcnt, (uint64_t)nreads * 4));
+  HIP_TRY(back(out->rec_sel, o.rec_sel, nr));
+  HIP_TRY(back(out->rec_d, o.rec_d, nr * 8));
+  HIP_TRY(back(out->rec_v, o.rec_v, nr * 8));
+  HIP_TRY(back(out->rec_chisq, o.rec_chisq, nr * 8));
+  HIP_TRY(back(out->rec_rep, o.rec_rep, nr * 4));
+  HIP_TRY(hipStreamSynchronize(st));
+  // ---- the rows
+  out->nrows = 0;
+  out->rows_mode = o.rows_mode, out->rows_indexed = o.rows_indexed, out->keep_v = o.keep_v;
+  if (o.rows_mode) {
+    launch_rows(s, L);
+    HIP_TRY(hipGetLastError());
+    uint32_t nrows = 0;
+    HIP_TRY(hipMemcpyAsync(&nrows, o.counters + kCtRows, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(back(out->row_key, o.row_key, nr * 4));
+    if (o.rows_indexed) {
+      HIP_TRY(back(out->row_dix, o.row_dix, nr * 4));
+      HIP_TRY(back(out->dist_list, o.dist_list, (uint64_t)in->problems * 8));
+    } else {
+      HIP_TRY(back(out->row_d, o.row_d, nr * 8));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    out->nrows = nrows;
+  }
+  HIP_TRY(back(out->rd_roff, o.rd_roff, (uint64_t)nreads * 4));
+  HIP_TRY(hipStreamSynchronize(st));
   return KR_OK;
 }
 
