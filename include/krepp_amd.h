@@ -617,9 +617,13 @@ KR_API int kr_debug_fastq_parse_ms(kr_stream*, float* ms);
  *                  consumed) yields exactly the remaining records.  status == KR_FASTQ_OK iff consumed == nbytes; rejected == nreads
  *   KR_FASTQ_LONG / KR_FASTQ_CAPACITY   as for FASTQ (LONG is never raised with KR_TILE_DEVICE; nreads 0: the record never fits)
  * kr_fasta_chunk_cut (no device): the position of the last record start in buf[1 .. n), 0 when there is none -- where a reader of
- * raw bytes ends a chunk that it submits with closed = 1 (`krepp dist --gpu-parse`). */
+ * raw bytes ends a chunk that it submits with closed = 1 (`krepp dist --gpu-parse`).
+ * kr_fastq_chunk_cut (no device): where the same reader ends a chunk of FASTQ -- the last line start c in the chunk's last MiB,
+ * behind the first newline there, with buf[c] == '@', the line after next starting with '+', both lines between them complete and
+ * that '+' inside buf[0 .. n); 0 when there is none (the chunk is submitted whole and its last record stops INCOMPLETE). */
 KR_API int kr_batch_submit_fasta(kr_stream*, const uint8_t* raw, uint64_t nbytes, uint32_t flags, uint32_t closed, kr_fastq_parse* out);
 KR_API uint64_t kr_fasta_chunk_cut(const uint8_t* buf, uint64_t n);
+KR_API uint64_t kr_fastq_chunk_cut(const uint8_t* buf, uint64_t n);
 /* tests: the tiled form of the batch last submitted on the stream as it lies on the device, laid out by the host (a host batch)
  * or by kernels (KR_TILE_DEVICE): reads of the tiled batch and long sequences; voff [nv + 1] where every read of the tiled batch
  * starts in its bases, vtile [nv] 1 = a tile of a long sequence, rfirst [nreads] the caller's read's first read of the tiled batch,

@@ -116,7 +116,7 @@ EXPORTS = [
     "kr_index_upload", "kr_index_free", "kr_index_export", "kr_index_import", "kr_index_device_bytes", "kr_index_slot_words", "kr_index_slot_format", "kr_index_log_g", "kr_index_occ_bitmap", "kr_index_broadcast",
     "kr_params_default", "kr_stream_create", "kr_stream_destroy", "kr_batch_submit", "kr_batch_wait",
     "kr_batch_collect", "kr_batch_collect_device", "kr_stream_text_enable", "kr_batch_submit_text", "kr_batch_collect_text",
-    "kr_stream_fastq_enable", "kr_batch_submit_fastq", "kr_batch_submit_fasta", "kr_fasta_chunk_cut", "kr_batch_fastq_names", "kr_debug_fastq_batch", "kr_debug_fastq_parse_ms", "kr_debug_tile_layout", "kr_debug_tile_shape", "kr_batch_hits", "kr_batch_readtaps",
+    "kr_stream_fastq_enable", "kr_batch_submit_fastq", "kr_batch_submit_fasta", "kr_fasta_chunk_cut", "kr_fastq_chunk_cut", "kr_batch_fastq_names", "kr_debug_fastq_batch", "kr_debug_fastq_parse_ms", "kr_debug_tile_layout", "kr_debug_tile_shape", "kr_batch_hits", "kr_batch_readtaps",
     "kr_debug_front_end", "kr_debug_stream_move", "kr_debug_stream_addrs", "kr_debug_item_placement", "kr_debug_brent", "kr_debug_prefix", "kr_debug_colour_classes", "kr_llh_batch", "kr_llh_eval_indexed", "kr_batch_timing",
     "kr_place_tree_create", "kr_place_tree_create_lineage", "kr_place_tree_nnodes", "kr_place_summary_add",
     "kr_place_summary_text", "kr_place_tree_free", "kr_place_tree_kinds", "kr_place_batch", "kr_place_stream", "kr_place_stream_parsed", "kr_debug_place_ids", "kr_place_frame", "kr_place_counters",
@@ -238,6 +238,8 @@ def load():
     lib.kr_batch_submit_fasta.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(KrFastqParse)]
     lib.kr_fasta_chunk_cut.argtypes = [vp, C.c_uint64]
     lib.kr_fasta_chunk_cut.restype = C.c_uint64
+    lib.kr_fastq_chunk_cut.argtypes = [vp, C.c_uint64]
+    lib.kr_fastq_chunk_cut.restype = C.c_uint64
     lib.kr_batch_fastq_names.argtypes = [vp, C.POINTER(u64p), C.POINTER(u32p)]
     lib.kr_debug_fastq_batch.argtypes = [vp, vp, vp]
     lib.kr_debug_fastq_parse_ms.argtypes = [vp, C.POINTER(C.c_float)]
@@ -814,6 +816,13 @@ def fasta_chunk_cut(buf):
     """kr_fasta_chunk_cut: the position of the last record start ('>' behind a newline) in buf[1:], 0 when there is none"""
     buf = bytes(buf)
     return int(load().kr_fasta_chunk_cut(buf, len(buf)))
+
+
+def fastq_chunk_cut(buf):
+    """kr_fastq_chunk_cut: the last line start in buf's last MiB that begins with '@' and whose second next line begins with '+'
+    (that '+' still inside buf), 0 when there is none"""
+    buf = bytes(buf)
+    return int(load().kr_fastq_chunk_cut(buf, len(buf)))
 
 
 def tile_shape(length, k):

@@ -1529,6 +1529,27 @@ uint64_t kr_fasta_chunk_cut(const uint8_t* buf, uint64_t n)
   return 0;
 }
 
+// Its FASTQ sibling (kr_batch_submit_fastq): the last line start in the chunk's last MiB, behind the first newline there, that looks
+// like a record start -- a line starting with '@' whose second next line starts with '+' (the pool reader's rule), both lines
+// between them complete and at least that '+' inside the chunk; 0 when there is none (the chunk then ends inside a record, which
+// stops INCOMPLETE, and the host reader takes over there)
+uint64_t kr_fastq_chunk_cut(const uint8_t* buf, uint64_t n)
+{
+  if (!buf) return 0;
+  uint64_t cut = 0;
+  const uint64_t w0 = n > (1u << 20) ? n - (1u << 20) : 0;
+  const uint8_t* nl = (const uint8_t*)memchr(buf + w0, '\n', n - w0);
+  while (nl) {
+    const uint64_t c = (uint64_t)(nl - buf) + 1;
+    const uint8_t* l1 = c < n ? (const uint8_t*)memchr(buf + c, '\n', n - c) : nullptr;
+    const uint8_t* l2 = l1 && (uint64_t)(l1 - buf) + 1 < n ? (const uint8_t*)memchr(l1 + 1, '\n', n - (uint64_t)(l1 - buf) - 1) : nullptr;
+    if (!l2 || (uint64_t)(l2 - buf) + 1 >= n) break;
+    if (buf[c] == '@' && l2[1] == '+') cut = c;
+    nl = l1;
+  }
+  return cut;
+}
+
 // QSeq::read_next_batch (src/rqseq.cpp:180-197): keep reading until the batch holds
 // at least `min_bases` bases (reference: RBATCH_SIZE*DSEQ_LEN = 76,800) or input ends.
 int kr_fastx_next(kr_fastx* r, uint64_t min_bases, kr_fastx_batch* out)

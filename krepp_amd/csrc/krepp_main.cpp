@@ -4,9 +4,11 @@
 // src/krepp.hpp:206-221); everything else of the reference CLI (place, seek, sketch,
 // inspect) is out of scope here and reported as such.
 //
-// `dist` pipeline: reader thread (gz/FASTX, src/rqseq.cpp:180-197) -> one worker per GPU,
-// each with its own replica of the index and its own kr_stream -> writer emitting batches
-// in INPUT order (the reference emits in task-completion order, src/krepp.cpp:368-383).
+// Query pipeline (run_query): reader thread (gz/FASTX, src/rqseq.cpp:180-197) -> workers, each
+// GPU with its own replica of the index and each worker with its own kr_stream -> writer emitting
+// batches in INPUT order (the reference emits in task-completion order, src/krepp.cpp:368-383).
+// Settings: what a run was asked; OutputOrder: who may write when; Run: what the threads share;
+// Worker: one stream and the job on it.
 #include "krepp_amd.h"
 
 #include <cerrno>
@@ -21,8 +23,8 @@
 #include <deque>
 #include <malloc.h>
 #include <atomic>
-#include <functional>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <sys/stat.h>
@@ -144,6 +146,100 @@ static Args parse(int argc, char** argv)
   return a;
 }
 
+
+using Clock = std::chrono::steady_clock;
+static uint64_t since(Clock::time_point t) { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(Clock::now() - t).count(); }
+
+// `dist` and `place` share everything up to the per-batch back end (src/krepp.cpp:347-394, 434-504); `seek` is a sketch file
+// served as a one-leaf index (src/krepp.cpp:321-345, src/seek.cpp).  What a run of them takes from the command line and the
+// environment, resolved once (resolve_settings: mode 0 `dist`, 1 `place`, 2 `seek`) before any thread starts:
+struct Settings {
+  bool place = false, seek = false, summarize = false;
+  int tabular = 0; // place: 0 jplace, 1 tabular, 2 summary (--summarize wins over --tabular: src/krepp.cpp:401-405,441,467,493)
+  kr_params p, pfront; // (the device front end of `place` keeps every chosen leaf: the place options act in the back end)
+  std::string query, index_arg, invocation;
+  bool gpu_parse = false; // --gpu-parse asked for (Run::open_input decides whether the file qualifies)
+  int ngpus = 1, dev0 = 0, wpg = 2, nworkers = 2, write_threads = 4;
+  uint32_t max_reads = 0;
+  uint64_t batch_bases = 0, max_bases = 0, chunk_bytes = 0, max_records = 0, text_bytes = 0;
+  bool timing = false, host_text = false, dev_text = false, serial_write = false, copy_batches = false, clean_exit = false;
+  bool plain_dist() const { return !place && !seek && !summarize; }
+  // What a submit asks of the front end, per mode.  dist rows / the summary need (leaf, selected, DIST) only: nothing else is copied
+  // back (KR_TILE_ROWS: a batch with long sequences, which runs as tiles, has its text written by the device like any other);
+  // place keeps its records on the device; seek also reads the k-mer counts.  What is collected: Worker::collect.
+  uint32_t rows_flags(bool text_on) const { return place ? KR_TAP_ACCS : seek ? 0u : text_on ? KR_TILE_ROWS : KR_ROWS_ONLY; }
+};
+
+static Settings resolve_settings(const Args& a, const std::string& invocation, int mode)
+{
+  Settings s;
+  s.place = mode == 1, s.seek = mode == 2, s.invocation = invocation;
+  const bool place = s.place, seek = s.seek;
+  s.index_arg = a.has("--index-dir") ? a.get("--index-dir") : a.get("--sketch-path");
+  if (!a.has("--query") || s.index_arg.empty()) error_exit("dist/place/seek require -q/--query and -i (index directory or sketch file)");
+  if (a.has("--lineage-file") && !place) error_exit("-l/--lineage-file is an option of `place`");
+  s.query = a.get("--query");
+  s.summarize = !seek && a.flag.count("--summarize") && a.flag.at("--summarize");
+  kr_params& p = s.p;
+  kr_params_default(&p);
+  if (a.has("--hdist-th")) p.hdist_th = (uint32_t)atoi(a.get("--hdist-th").c_str());
+  if (a.has("--chisq")) p.chisq = atof(a.get("--chisq").c_str());
+  if (a.has("--dist-max")) {
+    p.dist_max = atof(a.get("--dist-max").c_str());
+    if (!(p.dist_max >= 1e-8 && p.dist_max <= 0.33)) error_exit("--dist-max: value not in range [1e-08, 0.33]");
+  }
+  if (a.flag.count("--multi")) p.multi = a.flag.at("--multi");
+  if (place) p.no_filter = 0; // filter defaults to on for place (src/krepp.cpp:612-615)
+  if (s.summarize && !place) p.no_filter = 0, p.multi = 1; // "Overrides --no-multi and --no-filter" (src/krepp.cpp:669-672, src/query.cpp:160-171)
+  if (a.flag.count("--filter")) p.no_filter = !a.flag.at("--filter");
+  if (a.has("--tau")) p.tau = (uint32_t)atoi(a.get("--tau").c_str());
+  if (place && p.hdist_th < p.tau) error_exit("The threshold tau must be less than HD threshold --hdist-th!");
+  kr_params_default(&s.pfront);
+  s.pfront.hdist_th = p.hdist_th;
+  const bool tabular_flag = a.flag.count("--tabular") && a.flag.at("--tabular");
+  s.tabular = (place && s.summarize) ? 2 : (tabular_flag ? 1 : 0);
+  s.ngpus = std::max(1, a.has("--gpus") ? atoi(a.get("--gpus").c_str()) : 1);
+  s.dev0 = a.has("--device") ? atoi(a.get("--device").c_str()) : 0;
+  s.gpu_parse = a.flag.count("--gpu-parse") && a.flag.at("--gpu-parse");
+
+  // reads per batch: the kernels' efficiency grows with the batch (launch tails amortise, likelihood problems repeat): 262,144 reads
+  // for `dist` on a large input, 65,536 for `place` / `seek` (more state per read) and for inputs of a few batches anyway
+  uint32_t max_reads_default = 1u << 16;
+  if (!place && !seek) {
+    struct stat sb;
+    if (stat(s.query.c_str(), &sb) == 0 && S_ISREG(sb.st_mode) && (uint64_t)sb.st_size >= (64ull << 20)) max_reads_default = 1u << 18;
+  }
+  s.max_reads = getenv("KR_CLI_BATCH_READS") ? (uint32_t)std::max(1, atoi(getenv("KR_CLI_BATCH_READS"))) : max_reads_default;
+  s.batch_bases = (uint64_t)s.max_reads * 150, s.max_bases = s.batch_bases * 4;
+  // --gpu-parse: about one reader batch of ordinary FASTQ per chunk (2 bytes of input per base); KR_CLI_PARSE_CHUNK (bytes): tests.
+  // The chunk is also the longest record the device path takes: a FASTA record longer than a chunk leaves no second record start to
+  // cut at, the chunk stops INCOMPLETE with no record, and the host reader takes the file from that record on (docs/design/08)
+  s.chunk_bytes = getenv("KR_CLI_PARSE_CHUNK") ? std::max<uint64_t>(4096, strtoull(getenv("KR_CLI_PARSE_CHUNK"), nullptr, 10))
+                                               : std::min<uint64_t>(2 * s.batch_bases + (1u << 16), 3ull << 30);
+  // two workers (each with its own stream) per GPU: one formats its rows while the other's batch is on the device.  (`place` on a
+  // 1000-genome tree, 8 M reads, 65,536-read batches: 8.2 M reads/s with two workers, 7.6 M with three -- `scripts/time_cli_place_big.py`;
+  // with 400,000-read batches through the C ABI a third host thread does pay: DESIGN.md 3.4)
+  s.wpg = getenv("KR_CLI_WORKERS_PER_GPU") ? std::max(1, atoi(getenv("KR_CLI_WORKERS_PER_GPU"))) : 2;
+  s.nworkers = s.ngpus * s.wpg;
+  s.max_records = (uint64_t)s.max_reads * (place ? 128 : 64);
+  if (const char* e = getenv("KR_DEBUG_CLI_RECORDS")) s.max_records = strtoull(e, nullptr, 10); // tests: force the split-and-retry path
+  // device text: room for 1.5 KB of rows per read (33 rows of ~28 bytes on a 1000-genome index); a batch with more is split like one
+  // with too many records.  KR_CLI_TEXT_PER_READ (tests): a buffer that is too small
+  const char* tpr = getenv("KR_CLI_TEXT_PER_READ");
+  s.text_bytes = tpr ? std::max<uint64_t>(4096, (uint64_t)s.max_reads * strtoull(tpr, nullptr, 10)) : std::max<uint64_t>(32ull << 20, (uint64_t)s.max_reads * 1536ull);
+  s.write_threads = getenv("KR_CLI_WRITE_THREADS") ? std::max(1, atoi(getenv("KR_CLI_WRITE_THREADS"))) : 4; // (per worker: Worker::emit)
+  s.timing = getenv("KR_CLI_TIMING") != nullptr; // seconds spent parsing, on the device (submit + collect), formatting and writing
+  // Plain `dist` rows are formatted on the device (kr_batch_submit_text / kr_batch_collect_text: the text of a batch arrives as
+  // bytes in the stream's page-locked buffer) and written by the WORKER itself, straight from that buffer, when the batch's turn
+  // has come.  KR_CLI_HOST_TEXT=1: the host formatter (kr_format_dist) as before round 5.
+  s.host_text = getenv("KR_CLI_HOST_TEXT") != nullptr;
+  s.dev_text = s.plain_dist() && !s.host_text;
+  s.serial_write = getenv("KR_CLI_SERIAL_WRITE") != nullptr;  // (OutputOrder::open)
+  s.copy_batches = getenv("KR_CLI_COPY_BATCHES") != nullptr;  // (Run::read_host)
+  s.clean_exit = getenv("KR_CLI_CLEAN_EXIT") != nullptr;      // (Run::finish)
+  return s;
+}
+
 struct Job {
   uint64_t seq = 0;
   // the batch as views: into a batch the reader handed over whole (kr_fastx_detach: nothing copied, given back by the worker
@@ -162,7 +258,6 @@ struct Job {
   std::string text;
   std::vector<kr_placement> pls; // place --summarize: the placements, `read` = global read number
   uint64_t first_read = 0;
-  bool done = false;
   // --gpu-parse: a chunk of the file's raw bytes (page-locked), cut at a guessed record start; its records are found on the device
   uint8_t* raw = nullptr;
   uint64_t raw_len = 0, raw_off = 0;
@@ -170,49 +265,216 @@ struct Job {
   bool fasta = false, closed = false; // a chunk of a FASTA file (kr_batch_submit_fasta); its last record ends where the chunk does
 };
 
-// `dist` and `place` share everything up to the per-batch back end (src/krepp.cpp:347-394, 434-504)
-// mode 0 `dist`, 1 `place`, 2 `seek` (a sketch file served as a one-leaf index: src/krepp.cpp:321-345, src/seek.cpp)
-static int run_query(const Args& a, const std::string& invocation, int mode)
-{
-  const bool place = mode == 1, seek = mode == 2;
-  const std::string index_arg = a.has("--index-dir") ? a.get("--index-dir") : a.get("--sketch-path");
-  if (!a.has("--query") || index_arg.empty()) error_exit("dist/place/seek require -q/--query and -i (index directory or sketch file)");
-  if (a.has("--lineage-file") && !place) error_exit("-l/--lineage-file is an option of `place`");
-  const bool summarize = !seek && a.flag.count("--summarize") && a.flag.at("--summarize");
-  kr_params p;
-  kr_params_default(&p);
-  if (a.has("--hdist-th")) p.hdist_th = (uint32_t)atoi(a.get("--hdist-th").c_str());
-  if (a.has("--chisq")) p.chisq = atof(a.get("--chisq").c_str());
-  if (a.has("--dist-max")) {
-    p.dist_max = atof(a.get("--dist-max").c_str());
-    if (!(p.dist_max >= 1e-8 && p.dist_max <= 0.33)) error_exit("--dist-max: value not in range [1e-08, 0.33]");
-  }
-  if (a.flag.count("--multi")) p.multi = a.flag.at("--multi");
-  if (place) p.no_filter = 0; // filter defaults to on for place (src/krepp.cpp:612-615)
-  if (summarize && !place) p.no_filter = 0, p.multi = 1; // "Overrides --no-multi and --no-filter" (src/krepp.cpp:669-672, src/query.cpp:160-171)
-  if (a.flag.count("--filter")) p.no_filter = !a.flag.at("--filter");
-  if (a.has("--tau")) p.tau = (uint32_t)atoi(a.get("--tau").c_str());
-  if (place && p.hdist_th < p.tau) error_exit("The threshold tau must be less than HD threshold --hdist-th!");
-  const bool tabular_flag = a.flag.count("--tabular") && a.flag.at("--tabular");
-  // place: 0 jplace, 1 tabular, 2 summary (--summarize wins over --tabular: src/krepp.cpp:401-405,441,467,493)
-  const int tabular = (place && summarize) ? 2 : (tabular_flag ? 1 : 0);
-  int ngpus = a.has("--gpus") ? atoi(a.get("--gpus").c_str()) : 1;
-  int dev0 = a.has("--device") ? atoi(a.get("--device").c_str()) : 0;
-  if (ngpus < 1) ngpus = 1;
+// The run's one lock and everything it protects about the ORDER of the output.  Jobs are numbered by the reader; their rows appear
+// in that order whoever writes them: a worker in its job's turn (device text; side by side with pwrite when the output is a regular
+// file, since a job's place in it is known as soon as the jobs before it know their lengths) or the writer thread from the job's
+// text.  `next_seq` is the job the output is waiting for; only the writer advances it, when it has been given that job.
+// --gpu-parse: the first chunk (in file order) that stops early names the byte where the host reader takes over for good; chunks
+// behind it were handed out already and produce nothing -- the rule lives in dropped_locked() and nowhere else.
+// A job that has been given to the writer is gone from the worker: finish() and a whole-job claim() take the unique_ptr.
+// (The run's queues borrow `mu` and `cv_work`: their waits also end on an error or an early stop, and one lock keeps that free of
+// missed wake-ups.)
+class OutputOrder {
+public:
+  std::mutex mu;
+  std::condition_variable cv_work, cv_done;
 
+  // A regular output file is written side by side (one thread copies ~10 GB/s into the page cache: 13 M reads/s of 33 rows each);
+  // anything else (a pipe, a terminal) is written in turn.  KR_CLI_SERIAL_WRITE=1: in turn always.
+  void open(FILE* out, bool side_by_side)
+  {
+    struct stat sb;
+    if (!side_by_side || out == stdout) return;
+    fflush(out);
+    if (fstat(fileno(out), &sb) == 0 && S_ISREG(sb.st_mode) && (file_off_ = ftello(out)) >= 0) seekable_ = true;
+  }
+  void rewind_to_end(FILE* out) const // (when every thread has been joined: the stream continues behind what the workers wrote)
+  {
+    if (!seekable_) return;
+    fflush(out);
+    (void)fseeko(out, file_off_, SEEK_SET);
+  }
+
+  // Waits for the job's turn.  False: nothing of this job reaches the output (an error, or a chunk behind the first early stop).
+  bool wait_turn(const Job& j)
+  {
+    std::unique_lock<std::mutex> lk(mu);
+    return turn(lk, j);
+  }
+  // The job's turn, and room for `n` bytes of it: *at is their place in the file (pwrite), or -1 (write them now, in turn).
+  // whole_job: these are all its rows -- the job goes to the writer here, so that the next job may take its place in the file
+  // while this one is being copied, and `j` is empty afterwards.  False: write nothing.
+  bool claim(std::unique_ptr<Job>& j, size_t n, bool whole_job, off_t* at)
+  {
+    std::unique_lock<std::mutex> lk(mu);
+    if (!turn(lk, *j)) return false;
+    *at = seekable_ ? file_off_ : (off_t)-1;
+    if (!seekable_) return true;
+    file_off_ += (off_t)n;
+    if (whole_job) {
+      const uint64_t seq = j->seq;
+      finished_[seq] = std::move(j);
+      lk.unlock();
+      cv_done.notify_all();
+    }
+    return true;
+  }
+  void finish(std::unique_ptr<Job> j, std::string& text, std::vector<kr_placement>& pls)
+  {
+    const uint64_t seq = j->seq;
+    j->text.swap(text), j->pls.swap(pls);
+    { std::lock_guard<std::mutex> lk(mu); finished_[seq] = std::move(j); }
+    cv_done.notify_all();
+  }
+  bool dropped(const Job& j) { std::lock_guard<std::mutex> lk(mu); return dropped_locked(j); }
+  // (in the chunk's turn: every chunk in front of it has had its own, so this is the first stop in file order)
+  void stop_at(const Job& j, uint64_t byte) { std::lock_guard<std::mutex> lk(mu); fb_seq_ = j.seq, fb_off_ = byte; }
+  bool stopped(uint64_t* byte) { std::lock_guard<std::mutex> lk(mu); *byte = fb_off_; return stopped_locked(); }
+  void fail(const std::string& msg)
+  {
+    { std::lock_guard<std::mutex> lk(mu); err_ = msg; }
+    cv_done.notify_all(), cv_work.notify_all();
+  }
+  bool failed() { std::lock_guard<std::mutex> lk(mu); return !err_.empty(); }
+  const std::string& error() const { return err_; } // (when every thread has been joined)
+  bool failed_locked() const { return !err_.empty(); }
+  bool stopped_locked() const { return fb_seq_ != UINT64_MAX; }
+
+  void close(uint64_t total) // the reader: no job numbered `total` or above will come
+  {
+    { std::lock_guard<std::mutex> lk(mu); total_ = total; }
+    cv_done.notify_all();
+  }
+  // the writer: the job the output is waiting for (null: the end of the input, or an error), and on to the next when it is written
+  std::unique_ptr<Job> take_next()
+  {
+    std::unique_lock<std::mutex> lk(mu);
+    cv_done.wait(lk, [&] { return finished_.count(next_seq_) || next_seq_ >= total_ || !err_.empty(); });
+    auto it = finished_.find(next_seq_);
+    if (!err_.empty() || it == finished_.end()) return nullptr;
+    std::unique_ptr<Job> j = std::move(it->second);
+    finished_.erase(it);
+    return j;
+  }
+  void advance()
+  {
+    { std::lock_guard<std::mutex> lk(mu); ++next_seq_; }
+    cv_done.notify_all();
+  }
+
+private:
+  bool dropped_locked(const Job& j) const { return j.raw && fb_seq_ < j.seq; } // (the host reader covers the chunk's bytes)
+  bool turn(std::unique_lock<std::mutex>& lk, const Job& j)
+  {
+    cv_done.wait(lk, [&] { return next_seq_ == j.seq || !err_.empty(); });
+    return err_.empty() && !dropped_locked(j);
+  }
+  uint64_t next_seq_ = 0, total_ = UINT64_MAX;
+  std::map<uint64_t, std::unique_ptr<Job>> finished_;
+  bool seekable_ = false;
+  off_t file_off_ = 0;
+  uint64_t fb_seq_ = UINT64_MAX, fb_off_ = 0; // the first chunk that stopped early, and the byte the host reader starts at
+  std::string err_;
+};
+
+// each read shares one unit among the references it keeps (src/query.cpp:168-170)
+static void add_weights(const kr_result_view& rv, std::vector<double>& wc, double& tw)
+{
+  for (uint32_t r = 0; r < rv.nreads; ++r) {
+    uint32_t o = rv.read_off[r], n = rv.read_cnt[r], ns = 0;
+    for (uint32_t i = o; i < o + n; ++i) ns += rv.rec_sel[i];
+    const double w = 1.0 / ns;
+    for (uint32_t i = o; i < o + n; ++i)
+      if (rv.rec_sel[i]) {
+        const uint32_t se = rv.rec_key[i] >> 1;
+        if (se < wc.size()) wc[se] += w;
+        tw += w;
+      }
+  }
+}
+
+// What the threads of a run share: reader (the main thread) -> todo -> workers -> OutputOrder -> writer.
+struct Run {
+  const Settings& s;
+  explicit Run(const Settings& s_) : s(s_) {}
   FILE* out = stdout;
+  kr_host_index* hx = nullptr;
+  kr_index_view view;
+  kr_place_tree* ptree = nullptr;
+  std::vector<kr_index*> dix;
+  kr_fastx* fx = nullptr; // (opened before the workers start; they hand batches back to it)
+  // --gpu-parse (plain regular files): the reader only moves bytes into page-locked chunks cut at guessed record starts; each worker
+  // finds the records of its chunks on its GPU (kr_batch_submit_fastq / kr_batch_submit_fasta with KR_TILE_DEVICE: long records are
+  // tiled on the device).  The first chunk that stops early (a record that is not clean four-line FASTQ, a wrong cut, a batch that
+  // overflows) names the byte where the host reader (kr_fastx_open_at) takes over for good, as the pool reader's "first surprise ->
+  // sequential to the end" (kr_host.cpp).  `place`: the batch is queued with KR_TAP_ACCS and placed where it lies
+  // (kr_place_stream_parsed: lengths and ids from the chunk, on the device); `seek`: queued with no flag, collected, and formatted
+  // with the names cut out of the chunk.  Their rows go through the job's text and the writer, as the host reader's do.
+  bool gpu_parse = false;
+  int qfd = -1;
+  uint64_t qsize = 0;
+  bool fasta_parse = false; // a file whose first byte is '>' is cut and parsed as FASTA; any other as FASTQ
+
+  OutputOrder order;
+  // under order.mu, waited for on order.cv_work (gpu_done: cv_done)
+  std::deque<std::unique_ptr<Job>> todo;
+  bool eof = false;
+  std::vector<uint8_t*> raw_free; // page-locked chunk buffers not in use
+  uint64_t gpu_issued = 0, gpu_done = 0;
+  int workers_ready = 0;
+  std::vector<kr_stream*> streams_to_free;
+  // --summarize: reference -> weighted read count (src/krepp.cpp:374-378), by colour id; every worker sums its batches in an array
+  // of its own (264 M rows per 8 M reads on a 1000-genome index: a shared map under a mutex was the whole run) and adds it here
+  // when it ends -- the reference adds per batch under `omp critical`, in whatever order the tasks finish
+  std::vector<double> wcount;
+  double twcount = 0;
+
+  std::atomic<uint64_t> nreads_dev{0}; // records found on the device so far, in the output's order (advanced in a chunk's turn)
+  uint64_t nbatches = 0, nreads_total = 0; // the reader's
+  // the writer's.  place --summarize: counts per placement-tree node, summed in input order; placements of a 512-read group that
+  // straddles two jobs wait in `carry` (the groups are the reference's batches)
+  bool jplace_prev = false;
+  std::vector<double> pwcount;
+  double ptwcount = 0;
+  std::vector<kr_placement> carry;
+
+  // "Loading the index and initializing..." (src/krepp.cpp:756-757) ends when the index is in device memory: t_init.  The elapsed
+  // time reported at the end is everything after it -- the workers' streams and page-locked buffers, then the batch loop
+  // (estimate_distances(), src/krepp.cpp:347-394,759-762: the reference's clock covers all it does after the index load, so this
+  // one does too since round 6; until then it began when the streams were ready) -- taken when the last row has been written and
+  // before anything is torn down, as the reference takes it before its destructors run.  The reader opens the query file and
+  // parses the first batches while the streams come up.
+  Clock::time_point t_init, t_loop; // t_loop: when the last worker was ready ([timing] only)
+  std::atomic<uint64_t> ns_parse{0}, ns_job{0}, ns_dev{0}, ns_fmt{0}, ns_write{0};
+  std::atomic<uint64_t> nb_dev_text{0}, nb_host_text{0}; // `dist` batches (pieces of them) written from device text / through kr_format_dist
+  std::atomic<int> worker_ids{0};
+  double at() const { return std::chrono::duration<double>(Clock::now() - t_init).count(); } // seconds since the query phase began
+
+  void start_up(const Args& a);
+  void open_input();
+  void worker_ready(const char* err);
+  std::unique_ptr<Job> next_job();
+  void chunk_done(uint8_t* raw);
+  void enqueue(std::unique_ptr<Job> j);
+  void read_chunks();
+  void read_host();
+  void end_of_input();
+  void write_loop();
+  int finish();
+};
+
+// the output file, the index on the host and on every GPU, the placement tree, the report's first lines
+void Run::start_up(const Args& a)
+{
   if (a.has("--output-path")) {
     out = fopen(a.get("--output-path").c_str(), "w");
     if (!out) error_exit("Failed to open " + a.get("--output-path"));
   }
   fprintf(stderr, "Loading the index and initializing...\n");
-  kr_host_index* hx = nullptr;
-  if (seek ? kr_host_sketch_load(index_arg.c_str(), &hx) : kr_host_index_load(index_arg.c_str(), &hx)) error_exit(kr_last_error());
-  kr_index_view view;
+  if (s.seek ? kr_host_sketch_load(s.index_arg.c_str(), &hx) : kr_host_index_load(s.index_arg.c_str(), &hx)) error_exit(kr_last_error());
   kr_host_index_view(hx, &view);
-  kr_place_tree* ptree = nullptr;
-  if (place) {
-    auto slurp = [&](const std::string& path) {
+  if (s.place) {
+    auto slurp = [](const std::string& path) {
       std::string text;
       FILE* tf = fopen(path.c_str(), "rb");
       if (!tf) error_exit("Error opening " + path);
@@ -232,20 +494,22 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
       fprintf(stderr, "Placing given sequences on the backbone tree...\n");
     }
     view.node_kind = kr_place_tree_kinds(ptree); // leaves absent from the placement tree become null nodes
+    pwcount.assign(kr_place_tree_nnodes(ptree) + 1, 0.0);
   }
+  if (s.summarize && !s.place) wcount.assign((size_t)view.tree_nnodes + 2, 0.0);
   // the index crosses PCIe once; the other GPUs receive it by RCCL broadcast over xGMI (load time only)
-  std::vector<kr_index*> dix(ngpus, nullptr);
-  if (kr_index_upload(&view, dev0, KR_VIEW_HOST, &dix[0])) error_exit(kr_last_error());
-  if (ngpus > 1) {
+  dix.assign(s.ngpus, nullptr);
+  if (kr_index_upload(&view, s.dev0, KR_VIEW_HOST, &dix[0])) error_exit(kr_last_error());
+  if (s.ngpus > 1) {
     std::vector<int> devs;
-    for (int g = 1; g < ngpus; ++g) devs.push_back(dev0 + g);
+    for (int g = 1; g < s.ngpus; ++g) devs.push_back(s.dev0 + g);
     // RCCL may print a version banner on stdout when its first communicator is made; stdout is where the report rows go
-    // (src/krepp.cpp:372-382).  This process is still single-threaded here (the workers start below), so pointing file
+    // (src/krepp.cpp:372-382).  This process is still single-threaded here (the workers start later), so pointing file
     // descriptor 1 at stderr for the duration of the call is safe -- the application's decision, not the library's.
     fflush(stdout);
     const int saved_out = dup(1);
     if (saved_out >= 0) (void)dup2(2, 1);
-    const int brc = kr_index_broadcast(dix[0], ngpus - 1, devs.data(), dix.data() + 1);
+    const int brc = kr_index_broadcast(dix[0], s.ngpus - 1, devs.data(), dix.data() + 1);
     if (saved_out >= 0) {
       fflush(stdout);
       (void)dup2(saved_out, 1);
@@ -253,645 +517,475 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
     }
     if (brc) error_exit(kr_last_error());
   }
-  // "Loading the index and initializing..." (src/krepp.cpp:756-757) ends HERE, when the index is in device memory.  The elapsed
-  // time reported at the end is everything after it -- the workers' streams and page-locked buffers, then the batch loop
-  // (estimate_distances(), src/krepp.cpp:347-394,759-762: the reference's clock covers all it does after the index load, so this
-  // one does too since round 6; until then it began when the streams were ready) -- taken when the last row has been written and
-  // before anything is torn down, as the reference takes it before its destructors run.  The reader opens the query file and
-  // parses the first batches while the streams come up.
-  auto t_init = std::chrono::steady_clock::now();
-  const auto t0 = t_init;
-  auto t_loop = t_init; // when the workers were ready ([timing] only)
-  if (seek) { // QuerySketch::header_dreport (src/krepp.cpp:305-309)
-    fprintf(out, "# software: krepp\tversion: " KREPP_VERSION "\tinvocation :%s\nSEQ_ID\tDIST\n", invocation.c_str());
-  } else if (!place) { // header (src/krepp.cpp:311-319)
-    fprintf(out, "# software: krepp\tversion: " KREPP_VERSION "\tinvocation :%s\n%s\n", invocation.c_str(),
-            summarize ? "REFERENCE_NAME\tWEIGHTED_COUNT\tSEQUENCE_ABUNDANCE" : "SEQ_ID\tREFERENCE_NAME\tDIST");
+  t_init = t_loop = Clock::now();
+  if (s.seek) { // QuerySketch::header_dreport (src/krepp.cpp:305-309)
+    fprintf(out, "# software: krepp\tversion: " KREPP_VERSION "\tinvocation :%s\nSEQ_ID\tDIST\n", s.invocation.c_str());
+  } else if (!s.place) { // header (src/krepp.cpp:311-319)
+    fprintf(out, "# software: krepp\tversion: " KREPP_VERSION "\tinvocation :%s\n%s\n", s.invocation.c_str(),
+            s.summarize ? "REFERENCE_NAME\tWEIGHTED_COUNT\tSEQUENCE_ABUNDANCE" : "SEQ_ID\tREFERENCE_NAME\tDIST");
   } else { // jplace opening or tabular header (src/krepp.cpp:440-447)
     char* t = nullptr;
     uint64_t l = 0;
-    if (kr_place_frame(ptree, 0, tabular, invocation.c_str(), 0, &t, &l)) error_exit(kr_last_error());
+    if (kr_place_frame(ptree, 0, s.tabular, s.invocation.c_str(), 0, &t, &l)) error_exit(kr_last_error());
     fwrite(t, 1, l, out);
     kr_free(t);
   }
-  // the device front end of `place` keeps every chosen leaf: the place options act in the back end
-  kr_params pfront;
-  kr_params_default(&pfront);
-  pfront.hdist_th = p.hdist_th;
+  order.open(out, s.dev_text && !s.serial_write);
+}
 
-  // reads per batch: the kernels' efficiency grows with the batch (launch tails amortise, likelihood problems repeat): 262,144 reads
-  // for `dist` on a large input, 65,536 for `place` / `seek` (more state per read) and for inputs of a few batches anyway
-  uint32_t max_reads_default = 1u << 16;
-  if (!place && !seek) {
-    struct stat sb;
-    if (stat(a.get("--query").c_str(), &sb) == 0 && S_ISREG(sb.st_mode) && (uint64_t)sb.st_size >= (64ull << 20)) max_reads_default = 1u << 18;
-  }
-  const uint32_t max_reads = getenv("KR_CLI_BATCH_READS") ? (uint32_t)std::max(1, atoi(getenv("KR_CLI_BATCH_READS"))) : max_reads_default;
-  const uint64_t batch_bases = (uint64_t)max_reads * 150, max_bases = batch_bases * 4;
-  std::mutex mu;
-  std::condition_variable cv_work, cv_done;
-  std::deque<Job*> todo;
-  std::map<uint64_t, Job*> finished;
-  bool eof = false;
-  uint64_t total_batches = 0;
-  std::string worker_err;
-  // KR_CLI_TIMING=1: seconds spent parsing, on the device (submit + collect), formatting and writing
-  const bool timing = getenv("KR_CLI_TIMING") != nullptr;
-  std::atomic<uint64_t> ns_parse{0}, ns_job{0}, ns_dev{0}, ns_fmt{0}, ns_write{0};
-  std::atomic<uint64_t> nb_dev_text{0}, nb_host_text{0}; // `dist` batches (pieces of them) written from device text / through kr_format_dist
-  auto now = [] { return std::chrono::steady_clock::now(); };
-  auto since = [](std::chrono::steady_clock::time_point t) {
-    return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t).count();
-  };
-  // --summarize: reference -> weighted read count (src/krepp.cpp:374-378), by colour id; every worker sums its batches in an array
-  // of its own (264 M rows per 8 M reads on a 1000-genome index: a shared map under a mutex was the whole run) and adds it here
-  // when it ends -- the reference adds per batch under `omp critical`, in whatever order the tasks finish
-  std::vector<double> wcount(summarize && !place ? (size_t)view.tree_nnodes + 2 : 0, 0.0);
-  double twcount = 0;
-  // Plain `dist` rows are formatted on the device (kr_batch_submit_text / kr_batch_collect_text: the text of a batch arrives as
-  // bytes in the stream's page-locked buffer) and written by the WORKER itself, straight from that buffer, when the batch's turn
-  // has come: `next_seq` is the batch the output is waiting for (advanced by the writer thread, which still orders the batches).
-  // KR_CLI_HOST_TEXT=1: the host formatter (kr_format_dist) as before round 5.
-  const bool dev_text = !place && !seek && !summarize && !getenv("KR_CLI_HOST_TEXT");
-  uint64_t next_seq = 0;
-  // A regular output file: a batch's place in it is known as soon as the batches before it know their lengths, so the workers
-  // pwrite() their texts side by side (one thread copies ~10 GB/s into the page cache: 13 M reads/s of 33 rows each); anything
-  // else (a pipe, a terminal) is written in turn.  KR_CLI_SERIAL_WRITE=1: in turn always.
-  bool out_seekable = false;
-  off_t file_off = 0;
-  if (dev_text && out != stdout && !getenv("KR_CLI_SERIAL_WRITE")) {
-    struct stat sb;
-    fflush(out);
-    if (fstat(fileno(out), &sb) == 0 && S_ISREG(sb.st_mode) && (file_off = ftello(out)) >= 0) out_seekable = true;
-  }
-
-  // KR_CLI_TIMING: when things happened, in seconds since the query phase began
-  auto at = [&] { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
-  std::atomic<int> worker_ids{0};
-  int workers_ready = 0;
-  std::vector<kr_stream*> streams_to_free;
-  kr_fastx* fx = nullptr; // (opened before the workers start; they hand batches back to it)
-  // --gpu-parse (plain regular files): the reader only moves bytes into page-locked chunks cut at guessed record starts;
-  // each worker finds the records of its chunks on its GPU (kr_batch_submit_fastq / kr_batch_submit_fasta with KR_TILE_DEVICE: long records are tiled on the
-  // device).  The first chunk that stops early (a record that is not clean four-line FASTQ, a wrong cut, a batch that overflows) names the byte where the host reader
-  // (kr_fastx_open_at) takes over for good; chunks behind it were handed out already and are dropped unwritten (their sequence
-  // numbers are skipped by the writer, in order), as the pool reader's "first surprise -> sequential to the end" (kr_host.cpp).
-  // `place`: the batch is queued with KR_TAP_ACCS and placed where it lies (kr_place_stream_parsed: lengths and ids from the chunk, on
-  // the device); `seek`: queued with no flag, collected, and formatted with the names cut out of the chunk.  Their rows go through
-  // the job's text and the writer, as the host reader's do.
-  bool gpu_parse = a.flag.count("--gpu-parse") && a.flag.at("--gpu-parse");
-  // A file whose first byte is '>' is cut and parsed as FASTA (kr_fasta_chunk_cut, kr_batch_submit_fasta); any other as FASTQ.
-  int qfd = -1;
-  uint64_t qsize = 0;
-  bool fasta_parse = false;
-  if (gpu_parse) {
+// --gpu-parse on a plain regular file: the file for pread and the page-locked chunk buffers; anything else: the host reader
+void Run::open_input()
+{
+  if (s.gpu_parse) {
     struct stat sb;
     unsigned char mg[2] = {0, 0};
-    qfd = open(a.get("--query").c_str(), O_RDONLY);
+    qfd = open(s.query.c_str(), O_RDONLY);
     if (qfd < 0 || fstat(qfd, &sb) != 0 || !S_ISREG(sb.st_mode) || (pread(qfd, mg, 2, 0) == 2 && mg[0] == 0x1f && mg[1] == 0x8b)) {
       if (qfd >= 0) close(qfd);
-      qfd = -1, gpu_parse = false; // gzip / BGZF / not a regular file: the host reader
+      qfd = -1; // gzip / BGZF / not a regular file: the host reader
     } else {
+      gpu_parse = true;
       qsize = (uint64_t)sb.st_size;
       fasta_parse = mg[0] == '>';
     }
   }
-  // about one reader batch of ordinary FASTQ per chunk (2 bytes of input per base); KR_CLI_PARSE_CHUNK (bytes): tests.  The chunk is
-  // also the longest record the device path takes: a FASTA record longer than a chunk leaves no second record start to cut at, the
-  // chunk stops INCOMPLETE with no record, and the host reader takes the file from that record on (docs/design/08)
-  const uint64_t chunk_bytes = getenv("KR_CLI_PARSE_CHUNK") ? std::max<uint64_t>(4096, strtoull(getenv("KR_CLI_PARSE_CHUNK"), nullptr, 10))
-                                                            : std::min<uint64_t>(2 * batch_bases + (1u << 16), 3ull << 30);
-  std::vector<uint8_t*> raw_free; // page-locked chunk buffers not in use
-  uint64_t fb_seq = UINT64_MAX, fb_off = 0; // the first (in file order) chunk that stopped early, and the byte the host reader starts at
-  uint64_t gpu_issued = 0, gpu_done = 0;
-  std::atomic<uint64_t> nreads_dev{0};
-  auto worker = [&](int g) {
-    const int wid = worker_ids++;
-    double t_ready = 0, t_first = -1, t_last = 0;
-    uint64_t njobs = 0;
-    kr_stream* st = nullptr;
-    uint64_t max_records = (uint64_t)max_reads * (place ? 128 : 64);
-    if (const char* e = getenv("KR_DEBUG_CLI_RECORDS")) max_records = strtoull(e, nullptr, 10); // tests: force the split-and-retry path
-    // (four times the reads of a batch: a batch of contigs is submitted as tiles of 128 k-mer positions, include/krepp_amd.h)
-    if (kr_stream_create(dix[g], (place || seek) ? &pfront : &p, 4 * max_reads, max_bases, max_records, &st)) {
-      std::lock_guard<std::mutex> lk(mu);
-      worker_err = kr_last_error();
-      ++workers_ready;
-      cv_done.notify_all();
-      return;
-    }
-    std::vector<double> wc_local(wcount.size(), 0.0); // --summarize: this worker's sums
-    double tw_local = 0;
-    bool text_on = false;
-    if (dev_text) { // room for 1.5 KB of rows per read (33 rows of ~28 bytes on a 1000-genome index) and 64 bytes of id; a batch with
-                    // more is split like one with too many records (KR_ERR_CAPACITY below)
-      const char* tpr = getenv("KR_CLI_TEXT_PER_READ"); // (tests: a buffer that is too small)
-      const uint64_t tb = tpr ? std::max<uint64_t>(4096, (uint64_t)max_reads * strtoull(tpr, nullptr, 10)) : std::max<uint64_t>(32ull << 20, (uint64_t)max_reads * 1536ull);
-      if (kr_stream_text_enable(st, hx, tb, std::max<uint64_t>(1ull << 20, (uint64_t)max_reads * 64)) == 0)
-        text_on = true;
-      else
-        fprintf(stderr, "[krepp_amd] report text on the host: %s\n", kr_last_error());
-    }
-    if (gpu_parse && kr_stream_fastq_enable(st, chunk_bytes)) {
-      std::lock_guard<std::mutex> lk(mu);
-      worker_err = kr_last_error();
-      ++workers_ready;
-      cv_done.notify_all();
-      return;
-    }
-    t_ready = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_init).count();
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      ++workers_ready;
-    }
-    cv_done.notify_all();
-    // reads per submit this worker currently trusts: halved when a submit overflows a device buffer, doubled again
-    // after a run of successes -- data with hundreds of rows per read settle at a piece size instead of failing a
-    // full-size submit (and every intermediate size) for every batch
-    size_t piece = SIZE_MAX;
-    int streak = 0;
-    for (;;) {
-      Job* j = nullptr;
-      {
-        std::unique_lock<std::mutex> lk(mu);
-        cv_work.wait(lk, [&] { return !todo.empty() || eof; });
-        if (todo.empty()) break;
-        j = todo.front();
-        todo.pop_front();
-      }
-      cv_work.notify_all(); // the reader may be waiting for queue space
-      const char* const* nm = j->names;
-      const size_t job_n = j->n;             // (`j` may be gone once its rows have taken their place in the output)
-      kr_fastx_held* const job_held = j->held;
-      std::string text;
-      std::vector<kr_placement> pls;
-      bool my_turn = false; // this worker holds the output (plain `dist` with device text: rows are written as they arrive)
-      bool handed_over = false; // ... and has passed it on already (the job's only piece took its place in the file; `j` is gone)
-      const bool gpu_job = j->raw != nullptr;
-      auto emit = [&](const char* p, size_t n, bool whole_job) {
-        off_t at_off = -1;
-        {
-          std::unique_lock<std::mutex> lk(mu);
-          if (!my_turn) cv_done.wait(lk, [&] { return next_seq == j->seq || !worker_err.empty(); });
-          my_turn = true;
-          if (!worker_err.empty()) return;
-          if (gpu_job && fb_seq < j->seq) return; // (a chunk behind the first early stop: the host reader covers its bytes)
-          if (out_seekable) {
-            at_off = file_off;
-            file_off += (off_t)n;
-            if (whole_job) { // the next batch may take its place while this one is being copied
-              j->done = true;
-              finished[j->seq] = j;
-              handed_over = true;
-            }
-          }
-        }
-        if (handed_over) cv_done.notify_all();
-        auto t_w = now();
-        if (at_off >= 0) {
-          // A batch's text is hundreds of megabytes (262,144 reads x 33 rows x 28 bytes), and one thread copies 2.5-5 GB/s into the
-          // page cache: with two workers the 38 GB of a 50 M-read run were written at 5 GB/s and the run was that (round 6,
-          // profiles/round6_cli_syn1000_50m.txt).  The text goes out in slices of at least 16 MB, side by side (KR_CLI_WRITE_THREADS,
-          // default 4 per worker).
-          const int fd = fileno(out);
-          auto write_slice = [&](size_t a, size_t b) {
-            size_t done = a;
-            while (done < b) {
-              const ssize_t w = pwrite(fd, p + done, b - done, at_off + (off_t)done);
-              if (w < 0) {
-                if (errno == EINTR) continue;
-                std::lock_guard<std::mutex> lk(mu);
-                worker_err = std::string("cannot write the output: ") + strerror(errno);
-                break;
-              }
-              done += (size_t)w;
-            }
-          };
-          static const int wt_env = getenv("KR_CLI_WRITE_THREADS") ? std::max(1, atoi(getenv("KR_CLI_WRITE_THREADS"))) : 4;
-          const size_t nsl = std::max<size_t>(1, std::min<size_t>((size_t)wt_env, n >> 24));
-          if (nsl == 1) {
-            write_slice(0, n);
-          } else {
-            std::vector<std::thread> ws_;
-            for (size_t q = 1; q < nsl; ++q) ws_.emplace_back(write_slice, n * q / nsl, n * (q + 1) / nsl);
-            write_slice(0, n / nsl);
-            for (auto& t_ : ws_) t_.join();
-          }
-        } else if (n) {
-          fwrite(p, 1, n, out);
-        }
-        ns_write += since(t_w);
-      };
-      // reads [lo, hi) of the job; a batch that overflows a device-side buffer (KR_ERR_CAPACITY: unusually many
-      // table hits or records per read) is resubmitted in halves, as include/krepp_amd.h prescribes
-      std::function<int(size_t, size_t)> run = [&](size_t lo, size_t hi) -> int {
-        if (hi - lo > piece && hi - lo > 1) { // known to be too much for one submit
-          const size_t mid = lo + (hi - lo) / 2;
-          const int rc0 = run(lo, mid);
-          return rc0 ? rc0 : run(mid, hi);
-        }
-        std::vector<uint64_t> offs(hi - lo + 1);
-        for (size_t i = lo; i <= hi; ++i) offs[i - lo] = j->offsets[i] - j->offsets[lo];
-        kr_result_view rv;
-        char* txt = nullptr;
-        uint64_t len = 0;
-        auto t_dev = now();
-        // dist rows / the summary need (leaf, selected, DIST) only: nothing else is copied back; place keeps its records
-        // on the device; seek also reads the k-mer counts
-        int rc;
-        const char* dtext = nullptr;
-        uint64_t dlen = 0;
-        bool on_device = false;
-        if (text_on) {
-          std::vector<uint32_t> id_off(hi - lo + 1);
-          for (size_t i = lo; i < hi; ++i) id_off[i - lo] = (uint32_t)(nm[i] - j->blob);
-          id_off[hi - lo] = hi < j->n ? (uint32_t)(nm[hi] - j->blob) : (uint32_t)j->blob_bytes;
-          // (KR_TILE_ROWS: a batch with long sequences, which runs as tiles, has its text written by the device like any other)
-          rc = kr_batch_submit_text(st, j->bases + j->offsets[lo], offs.data(), (uint32_t)(hi - lo), KR_BASES_HOST | KR_TILE_ROWS, j->blob,
-                                    id_off.data(), 1);
-          if (!rc) rc = kr_batch_collect_text(st, &dtext, &dlen);
-          on_device = rc == 0;
-          if (rc == KR_ERR_UNSUPPORTED) rc = kr_batch_collect(st, &rv); // (a DIST the device does not format: the batch's rows, formatted below)
-        } else {
-          rc = kr_batch_submit(st, j->bases + j->offsets[lo], offs.data(), (uint32_t)(hi - lo),
-                               KR_BASES_HOST | (place ? KR_TAP_ACCS : (seek ? 0u : KR_ROWS_ONLY)));
-          if (!rc) rc = place ? kr_batch_wait(st) : kr_batch_collect(st, &rv); // place: the records stay on the device
-        }
-        ns_dev += since(t_dev);
-        auto t_fmt = now();
-        if (rc == KR_ERR_CAPACITY && hi - lo > 1) {
-          piece = std::min(piece, (hi - lo + 1) / 2);
-          streak = 0;
-          const size_t mid = lo + (hi - lo) / 2;
-          rc = run(lo, mid);
-          return rc ? rc : run(mid, hi);
-        }
-        if (!rc && seek) rc = kr_format_seek(hx, dix[g], &rv, p.hdist_th, nm + lo, &txt, &len);
-        if (!rc && on_device) {
-          ++nb_dev_text;
-          emit(dtext, dlen, lo == 0 && hi == job_n);
-          if (piece != SIZE_MAX && ++streak >= 16) piece = piece > SIZE_MAX / 2 ? SIZE_MAX : piece * 2, streak = 0; // (as below: grow back after a run of successes)
-          return 0;
-        }
-        if (!rc && !place && !seek && !summarize) {
-          rc = kr_format_dist(hx, &rv, nm + lo, &txt, &len);
-          if (!rc) ++nb_host_text;
-        }
-        if (!rc && summarize && !place) { // each read shares one unit among the references it keeps (src/query.cpp:168-170)
-          for (uint32_t r = 0; r < rv.nreads; ++r) {
-            uint32_t o = rv.read_off[r], n = rv.read_cnt[r], ns = 0;
-            for (uint32_t i = o; i < o + n; ++i) ns += rv.rec_sel[i];
-            const double w = 1.0 / ns;
-            for (uint32_t i = o; i < o + n; ++i)
-              if (rv.rec_sel[i]) {
-                const uint32_t se = rv.rec_key[i] >> 1;
-                if (se < wc_local.size()) wc_local[se] += w;
-                tw_local += w;
-              }
-          }
-        }
-        if (!rc && place) {
-          int prev = (!tabular && !text.empty()) ? 1 : 0; // pieces of a batch are joined here, batches by the writer (src/krepp.cpp:474-484)
-          kr_placement* pp = nullptr;
-          uint64_t npp = 0;
-          rc = kr_place_stream(hx, dix[g], ptree, st, (uint32_t)(hi - lo), offs.data(), nm + lo, &p, tabular, &prev, &txt, &len,
-                               tabular == 2 ? &pp : nullptr, tabular == 2 ? &npp : nullptr);
-          for (uint64_t i = 0; i < npp; ++i) {
-            pp[i].read = (uint32_t)(j->first_read + lo + pp[i].read);
-            pls.push_back(pp[i]);
-          }
-          kr_free(pp);
-        }
-        if (!rc && txt && dev_text)
-          emit(txt, len, false); // (in order with the pieces the device wrote)
-        else if (!rc && txt)
-          text.append(txt, len);
-        kr_free(txt);
-        ns_fmt += since(t_fmt);
-        if (!rc && piece != SIZE_MAX && ++streak >= 16) piece = piece > SIZE_MAX / 2 ? SIZE_MAX : piece * 2, streak = 0;
-        return rc;
-      };
-      // --gpu-parse: the chunk's records found on the device, submitted again from `consumed` while a batch stops at capacity
-      auto run_chunk = [&]() -> int {
-        {
-          std::lock_guard<std::mutex> lk(mu);
-          if (fb_seq < j->seq) return 0; // (dropped: the host reader covers these bytes)
-        }
-        uint64_t pos = 0;
-        std::vector<double> wc_job(wc_local.size(), 0.0);
-        double tw_job = 0;
-        uint64_t nr_job = 0;
-        bool fell = false;
-        std::string blob;
-        std::vector<const char*> nptr;
-        auto names_of = [&](const uint8_t* raw, uint32_t n) -> int { // the accepted records' names, NUL-terminated, for the host formatter
-          const uint64_t* np = nullptr;
-          const uint32_t* nl = nullptr;
-          const int r = kr_batch_fastq_names(st, &np, &nl);
-          if (r) return r;
-          std::vector<size_t> at_(n);
-          blob.clear();
-          for (uint32_t i = 0; i < n; ++i) at_[i] = blob.size(), blob.append((const char*)raw + np[i], nl[i]), blob.push_back('\0');
-          nptr.resize(n);
-          for (uint32_t i = 0; i < n; ++i) nptr[i] = blob.data() + at_[i];
-          return 0;
-        };
-        while (pos < j->raw_len) {
-          kr_fastq_parse fp;
-          auto t_dev = now();
-          // (KR_TILE_DEVICE: a long record stays with the device, tiled there; KR_TILE_ROWS: and its batch's text is the device's too)
-          const uint32_t pflags = place ? (KR_TAP_ACCS | KR_TILE_DEVICE) : seek ? 0u : ((text_on ? KR_TILE_ROWS : KR_ROWS_ONLY) | KR_TILE_DEVICE);
-          int rc = j->fasta ? kr_batch_submit_fasta(st, j->raw + pos, j->raw_len - pos, pflags, j->closed ? 1u : 0u, &fp)
-                            : kr_batch_submit_fastq(st, j->raw + pos, j->raw_len - pos, pflags, j->at_eof ? 1u : 0u, &fp);
-          if (rc) return rc;
-          if (fp.nreads && (place || seek)) {
-            char* txt = nullptr;
-            uint64_t len = 0;
-            kr_result_view rv;
-            if (seek) rc = kr_batch_collect(st, &rv);
-            ns_dev += since(t_dev);
-            auto t_fmt = now();
-            if (!rc && seek) rc = names_of(j->raw + pos, fp.nreads);
-            if (!rc && seek) rc = kr_format_seek(hx, dix[g], &rv, p.hdist_th, nptr.data(), &txt, &len);
-            if (!rc && place) {
-              int prev = (!tabular && !text.empty()) ? 1 : 0; // (submits of a chunk are joined here, chunks by the writer)
-              kr_placement* pp = nullptr;
-              uint64_t npp = 0;
-              rc = kr_place_stream_parsed(hx, dix[g], ptree, st, j->raw + pos, &p, tabular, &prev, &txt, &len, tabular == 2 ? &pp : nullptr,
-                                          tabular == 2 ? &npp : nullptr);
-              for (uint64_t i = 0; !rc && i < npp; ++i) { // (`read`: the number within the chunk; the chunk's first read is known when its turn comes)
-                pp[i].read = (uint32_t)(nr_job + pp[i].read);
-                pls.push_back(pp[i]);
-              }
-              kr_free(pp);
-            }
-            if (!rc && txt) text.append(txt, len);
-            kr_free(txt);
-            ns_fmt += since(t_fmt);
-            if (rc == KR_ERR_CAPACITY) { // more records than a batch holds: the host reader takes over at this batch's first record
-              fell = true;
-              break;
-            }
-            if (rc) return rc;
-            nr_job += fp.nreads;
-          } else if (fp.nreads) {
-            const char* dtext = nullptr;
-            uint64_t dlen = 0;
-            kr_result_view rv;
-            bool on_device = false;
-            if (text_on) {
-              rc = kr_batch_collect_text(st, &dtext, &dlen);
-              on_device = rc == 0;
-              if (rc == KR_ERR_UNSUPPORTED) rc = kr_batch_collect(st, &rv);
-            } else {
-              rc = kr_batch_collect(st, &rv);
-            }
-            ns_dev += since(t_dev);
-            if (rc == KR_ERR_CAPACITY) { // more records or text than a batch holds: the host reader takes over at this batch's first record
-              fell = true;
-              break;
-            }
-            if (rc) return rc;
-            auto t_fmt = now();
-            if (on_device) {
-              ++nb_dev_text;
-              emit(dtext, dlen, false);
-            } else if (summarize) { // each read shares one unit among the references it keeps (src/query.cpp:168-170)
-              for (uint32_t r = 0; r < rv.nreads; ++r) {
-                uint32_t o = rv.read_off[r], n = rv.read_cnt[r], ns = 0;
-                for (uint32_t i = o; i < o + n; ++i) ns += rv.rec_sel[i];
-                const double w = 1.0 / ns;
-                for (uint32_t i = o; i < o + n; ++i)
-                  if (rv.rec_sel[i]) {
-                    const uint32_t se = rv.rec_key[i] >> 1;
-                    if (se < wc_job.size()) wc_job[se] += w;
-                    tw_job += w;
-                  }
-              }
-            } else {
-              char* txt = nullptr;
-              uint64_t len = 0;
-              rc = names_of(j->raw + pos, fp.nreads);
-              if (!rc) rc = kr_format_dist(hx, &rv, nptr.data(), &txt, &len);
-              if (rc) return rc;
-              ++nb_host_text;
-              emit(txt, len, false);
-              kr_free(txt);
-            }
-            ns_fmt += since(t_fmt);
-            nr_job += fp.nreads;
-          }
-          pos += fp.consumed;
-          if (fp.status == KR_FASTQ_OK) break;
-          if (fp.status == KR_FASTQ_CAPACITY && fp.nreads) continue;
-          fell = true; // not clean, a record cut by the end of the chunk or the file: the host reader from here
-          break;
-        }
-        // in the output's order: only a chunk that no earlier chunk's stop has dropped counts
-        std::unique_lock<std::mutex> lk(mu);
-        if (!my_turn) cv_done.wait(lk, [&] { return next_seq == j->seq || !worker_err.empty(); });
-        my_turn = true;
-        if (fb_seq < j->seq) {
-          text.clear(), pls.clear(); // (`place` / `seek`: rows made before the earlier chunk's stop was known)
-          return 0;
-        }
-        for (size_t q = 0; q < wc_job.size(); ++q) wc_local[q] += wc_job[q];
-        tw_local += tw_job;
-        // place --summarize sums per 512 reads by global read number: every chunk in front of this one has had its turn
-        j->first_read = nreads_dev, j->n = (size_t)nr_job;
-        for (kr_placement& x : pls) x.read = (uint32_t)(j->first_read + x.read);
-        nreads_dev += nr_job;
-        if (fell) fb_seq = j->seq, fb_off = j->raw_off + pos;
-        return 0;
-      };
-      const int rc = gpu_job ? run_chunk() : run(0, job_n);
-      if (gpu_job) {
-        std::lock_guard<std::mutex> lk(mu);
-        raw_free.push_back(j->raw);
-        ++gpu_done;
-        cv_work.notify_all();
-        cv_done.notify_all();
-      }
-      if (job_held) kr_fastx_release(fx, job_held); // (the batch's buffers go back to the reader)
-      t_last = at(), ++njobs;
-      if (t_first < 0) t_first = t_last;
-      if (handed_over) continue; // (its rows are in the file; the writer thread has the job)
-      std::lock_guard<std::mutex> lk(mu);
-      if (rc) {
-        worker_err = kr_last_error();
-      } else {
-        j->text.swap(text);
-        j->pls.swap(pls);
-      }
-      j->done = true;
-      finished[j->seq] = j;
-      cv_done.notify_all();
-    }
-    if (timing) fprintf(stderr, "[timing] worker %d: stream ready %.3f s into the initialisation, first batch done at %.3f s, last of %llu at %.3f s\n", wid, t_ready, t_first, (unsigned long long)njobs, t_last);
-    std::lock_guard<std::mutex> lk(mu);
-    for (size_t q = 0; q < wc_local.size(); ++q) wcount[q] += wc_local[q];
-    twcount += tw_local;
-    streams_to_free.push_back(st); // (torn down with the index, after the elapsed time has been taken)
-  };
-  // two workers (each with its own stream) per GPU: one formats its rows while the other's batch is on the device.  (`place` on a
-  // 1000-genome tree, 8 M reads, 65,536-read batches: 8.2 M reads/s with two workers, 7.6 M with three -- `scripts/time_cli_place_big.py`;
-  // with 400,000-read batches through the C ABI a third host thread does pay: DESIGN.md 3.4)
-  const int wpg = getenv("KR_CLI_WORKERS_PER_GPU") ? std::max(1, atoi(getenv("KR_CLI_WORKERS_PER_GPU"))) : 2;
-  const int nworkers = ngpus * wpg;
-  if (!gpu_parse && kr_fastx_open(a.get("--query").c_str(), &fx)) error_exit(kr_last_error()); // (before the workers: they hand batches back to it)
-  if (gpu_parse) // page-locked chunk buffers: one per worker at work, one being filled, one waiting per worker
-    for (int q = 0; q < 2 * nworkers + 1; ++q) {
-      uint8_t* b_ = (uint8_t*)kr_host_alloc(chunk_bytes + 16);
+  if (!gpu_parse && kr_fastx_open(s.query.c_str(), &fx)) error_exit(kr_last_error());
+  if (gpu_parse) // one buffer per worker at work, one being filled, one waiting per worker
+    for (int q = 0; q < 2 * s.nworkers + 1; ++q) {
+      uint8_t* b_ = (uint8_t*)kr_host_alloc(s.chunk_bytes + 16);
       if (!b_) error_exit("cannot allocate page-locked chunk buffers for --gpu-parse");
       raw_free.push_back(b_);
     }
-  std::vector<std::thread> workers;
-  for (int w = 0; w < nworkers; ++w) workers.emplace_back(worker, w % ngpus);
+}
 
-  bool jplace_prev = false;
-  // place --summarize: counts per placement-tree node, summed by the writer in input order; placements of a
-  // 512-read group that straddles two jobs wait in `carry` (the groups are the reference's batches)
-  std::vector<double> pwcount(place ? kr_place_tree_nnodes(ptree) + 1 : 0, 0.0);
-  double ptwcount = 0;
-  std::vector<kr_placement> carry;
-  std::thread writer([&] {
-    uint64_t next = 0;
-    for (;;) {
-      Job* j = nullptr;
-      {
-        std::unique_lock<std::mutex> lk(mu);
-        cv_done.wait(lk, [&] { return finished.count(next) || (eof && next >= total_batches) || !worker_err.empty(); });
-        if (!worker_err.empty()) return;
-        auto it = finished.find(next);
-        if (it == finished.end()) return;
-        j = it->second;
-        finished.erase(it);
-      }
-      if (tabular == 2) {
-        const uint32_t end_group = (uint32_t)(j->first_read + j->n) >> 9;
-        carry.insert(carry.end(), j->pls.begin(), j->pls.end());
-        size_t cut = j->n ? carry.size() : 0; // (--gpu-parse: a chunk that was dropped, or stopped at its first record, has no reads and no last group)
-        if ((j->first_read + j->n) & 511u)
-          while (cut > 0 && (carry[cut - 1].read >> 9) == end_group) --cut;
-        if (kr_place_summary_add(ptree, carry.data(), cut, pwcount.data(), &ptwcount)) {
-          std::lock_guard<std::mutex> lk(mu);
-          worker_err = kr_last_error();
-          return;
-        }
-        carry.erase(carry.begin(), carry.begin() + cut);
-      } else if (place && !tabular) {
-        if (!j->text.empty()) {
-          if (jplace_prev) fputs(",\n", out);
-          fwrite(j->text.data(), 1, j->text.size(), out);
-          jplace_prev = true;
-        }
-      } else {
-        auto t_w = now();
-        fwrite(j->text.data(), 1, j->text.size(), out);
-        ns_write += since(t_w);
-      }
-      delete j;
-      ++next;
-      {
-        std::lock_guard<std::mutex> lk(mu);
-        next_seq = next;
-      }
-      cv_done.notify_all();
-      cv_work.notify_all();
-    }
-  });
+// a worker has its stream, or failed to get it (err); the last one stamps t_loop
+void Run::worker_ready(const char* err)
+{
+  if (err) order.fail(err);
+  std::lock_guard<std::mutex> lk(order.mu);
+  if (++workers_ready == s.nworkers) t_loop = Clock::now();
+}
 
-  if (seek) fprintf(stderr, "Seeking query sequences in the sketch...\n");
-  if (!place && !seek) fprintf(stderr, "Estimating distances between given sequences and references...\n");
-  std::thread ready_watch([&] { // ([timing]: when the last worker had its stream)
-    std::unique_lock<std::mutex> lk(mu);
-    cv_done.wait(lk, [&] { return workers_ready == nworkers; });
-    t_loop = std::chrono::steady_clock::now();
-  });
-  uint64_t nbatches = 0, nreads_total = 0;
-  if (gpu_parse) { // the reader moves bytes only
-    auto t_parse = now();
-    uint64_t off = 0;
-    while (off < qsize) {
-      uint8_t* buf = nullptr;
-      {
-        std::unique_lock<std::mutex> lk(mu);
-        cv_work.wait(lk, [&] { return !raw_free.empty() || fb_seq != UINT64_MAX || !worker_err.empty(); });
-        if (fb_seq != UINT64_MAX || !worker_err.empty()) break; // (an early stop: nothing behind it will be used)
-        buf = raw_free.back();
-        raw_free.pop_back();
-      }
-      const uint64_t want = std::min<uint64_t>(chunk_bytes, qsize - off);
-      uint64_t got = 0;
-      while (got < want) {
-        const ssize_t k = pread(qfd, buf + got, want - got, (off_t)(off + got));
-        if (k <= 0) error_exit("cannot read " + a.get("--query"));
-        got += (uint64_t)k;
-      }
-      const bool last = off + want >= qsize;
-      uint64_t cut = want;
-      bool closed = last;
-      if (!last && fasta_parse) { // the last record start of the chunk: what lies in front of it is whole records.  None: the chunk's one
-                                  // record is longer than the chunk, it stops INCOMPLETE with no record and the host reader takes over
-        const uint64_t c = kr_fasta_chunk_cut(buf, want);
-        if (c) cut = c, closed = true;
-      } else if (!last) { // a line starting with '@' whose second next line starts with '+' (the pool reader's rule, kr_host.cpp); none: the
-                   // chunk ends inside a record, its last record stops INCOMPLETE and the host reader takes over there
-        const uint64_t w0 = want > (1u << 20) ? want - (1u << 20) : 0;
-        const uint8_t* nl = (const uint8_t*)memchr(buf + w0, '\n', want - w0);
-        while (nl) {
-          const uint64_t c = (uint64_t)(nl - buf) + 1;
-          const uint8_t* l1 = c < want ? (const uint8_t*)memchr(buf + c, '\n', want - c) : nullptr;
-          const uint8_t* l2 = l1 && (uint64_t)(l1 - buf) + 1 < want ? (const uint8_t*)memchr(l1 + 1, '\n', want - (uint64_t)(l1 - buf) - 1) : nullptr;
-          if (!l2 || (uint64_t)(l2 - buf) + 1 >= want) break;
-          if (buf[c] == '@' && l2[1] == '+') cut = c;
-          nl = l1;
-        }
-      }
-      Job* j = new Job();
-      j->raw = buf, j->raw_len = cut, j->raw_off = off, j->at_eof = last && cut == want;
-      j->fasta = fasta_parse, j->closed = closed;
-      off += cut;
-      {
-        std::unique_lock<std::mutex> lk(mu);
-        j->seq = nbatches++;
-        ++gpu_issued;
-        cv_work.wait(lk, [&] { return todo.size() < (size_t)(2 * nworkers) || !worker_err.empty(); });
-        todo.push_back(j);
-      }
-      cv_work.notify_all();
-    }
-    ns_parse += since(t_parse);
-    { // every chunk handed out is done (an earlier one may still stop early): then the first stop, if any, is final
-      std::unique_lock<std::mutex> lk(mu);
-      cv_done.wait(lk, [&] { return gpu_done == gpu_issued || !worker_err.empty(); });
-    }
-    close(qfd);
-    nreads_total = nreads_dev; // (the host reader, if it takes over, numbers its reads behind the device's: place --summarize)
-    if (fb_seq != UINT64_MAX && worker_err.empty()) {
-      if (kr_fastx_open_at(a.get("--query").c_str(), fb_off, &fx)) error_exit(kr_last_error());
-    }
+std::unique_ptr<Job> Run::next_job()
+{
+  std::unique_ptr<Job> j;
+  {
+    std::unique_lock<std::mutex> lk(order.mu);
+    order.cv_work.wait(lk, [&] { return !todo.empty() || eof; });
+    if (todo.empty()) return nullptr;
+    j = std::move(todo.front());
+    todo.pop_front();
   }
-  for (;;) {
-    if (gpu_parse && !fx) break; // (every record went through the device)
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      if (!worker_err.empty()) break; // (a worker without a stream, or one whose batch failed: reported below)
+  order.cv_work.notify_all(); // the reader may be waiting for queue space
+  return j;
+}
+
+void Run::chunk_done(uint8_t* raw)
+{
+  {
+    std::lock_guard<std::mutex> lk(order.mu);
+    raw_free.push_back(raw);
+    ++gpu_done;
+  }
+  order.cv_work.notify_all();
+  order.cv_done.notify_all();
+}
+
+// the reader numbers the job and queues it; the number of batches in flight is bounded
+void Run::enqueue(std::unique_ptr<Job> j)
+{
+  {
+    std::unique_lock<std::mutex> lk(order.mu);
+    j->seq = nbatches++;
+    if (j->raw) ++gpu_issued;
+    order.cv_work.wait(lk, [&] { return todo.size() < (size_t)(2 * s.nworkers) || order.failed_locked(); });
+    todo.push_back(std::move(j));
+  }
+  order.cv_work.notify_all();
+}
+
+// One worker: a kr_stream of its own on GPU `g`, and the job it is running.
+struct Worker {
+  Run& r;
+  const Settings& s;
+  const int g;
+  Worker(Run& r_, int g_) : r(r_), s(r_.s), g(g_) {}
+  kr_stream* st = nullptr;
+  bool text_on = false; // the stream formats `dist` rows on the device
+  // reads per submit this worker currently trusts: halved when a submit overflows a device buffer, doubled again
+  // after a run of successes -- data with hundreds of rows per read settle at a piece size instead of failing a
+  // full-size submit (and every intermediate size) for every batch
+  size_t piece = SIZE_MAX;
+  int streak = 0;
+  std::vector<double> wc; // --summarize: this worker's sums
+  double tw = 0;
+  std::unique_ptr<Job> j; // the job at hand; empty once its rows have taken their place in the output (OutputOrder::claim)
+  std::string text;       // its rows for the writer, its placements
+  std::vector<kr_placement> pls;
+  std::string blob; // chunk_names
+  std::vector<const char*> nptr;
+
+  void loop();
+  int run_batch(size_t lo, size_t hi);
+  int run_halves(size_t lo, size_t hi);
+  int run_chunk();
+  int collect(kr_result_view* rv, const char** dtext, uint64_t* dlen, bool* on_device);
+  int chunk_names(const uint8_t* raw, uint32_t n);
+  void keep_placements(int rc, kr_placement* pp, uint64_t npp, uint64_t base);
+  void emit(const char* p, size_t n, bool whole_job);
+  int joins() const { return (!s.tabular && !text.empty()) ? 1 : 0; } // jplace: pieces of a job are joined by the worker, jobs by the writer (src/krepp.cpp:474-484)
+  void succeeded() // (grow back after a run of successes)
+  {
+    if (piece != SIZE_MAX && ++streak >= 16) piece = piece > SIZE_MAX / 2 ? SIZE_MAX : piece * 2, streak = 0;
+  }
+};
+
+void Worker::loop()
+{
+  const int wid = r.worker_ids++;
+  double t_first = -1, t_last = 0;
+  uint64_t njobs = 0;
+  // (four times the reads of a batch: a batch of contigs is submitted as tiles of 128 k-mer positions, include/krepp_amd.h)
+  if (kr_stream_create(r.dix[g], (s.place || s.seek) ? &s.pfront : &s.p, 4 * s.max_reads, s.max_bases, s.max_records, &st)) return r.worker_ready(kr_last_error());
+  wc.assign(r.wcount.size(), 0.0);
+  if (s.dev_text) { // (and 64 bytes of id per read)
+    if (kr_stream_text_enable(st, r.hx, s.text_bytes, std::max<uint64_t>(1ull << 20, (uint64_t)s.max_reads * 64)) == 0)
+      text_on = true;
+    else
+      fprintf(stderr, "[krepp_amd] report text on the host: %s\n", kr_last_error());
+  }
+  if (r.gpu_parse && kr_stream_fastq_enable(st, s.chunk_bytes)) return r.worker_ready(kr_last_error());
+  const double t_ready = r.at();
+  r.worker_ready(nullptr);
+  while ((j = r.next_job())) {
+    kr_fastx_held* const held = j->held; // (what outlives a job that is handed over: the reader's buffers, the chunk's)
+    uint8_t* const raw = j->raw;
+    const int rc = raw ? run_chunk() : run_batch(0, j->n);
+    if (raw) r.chunk_done(raw);
+    if (held) kr_fastx_release(r.fx, held); // (the batch's buffers go back to the reader)
+    t_last = r.at(), ++njobs;
+    if (t_first < 0) t_first = t_last;
+    if (j) {
+      if (rc) r.order.fail(kr_last_error()), text.clear(), pls.clear();
+      r.order.finish(std::move(j), text, pls);
     }
+    text.clear(), pls.clear();
+  }
+  if (s.timing) fprintf(stderr, "[timing] worker %d: stream ready %.3f s into the initialisation, first batch done at %.3f s, last of %llu at %.3f s\n", wid, t_ready, t_first, (unsigned long long)njobs, t_last);
+  std::lock_guard<std::mutex> lk(r.order.mu);
+  for (size_t q = 0; q < wc.size(); ++q) r.wcount[q] += wc[q];
+  r.twcount += tw;
+  r.streams_to_free.push_back(st); // (torn down with the index, after the elapsed time has been taken)
+}
+
+// Rows in the job's turn: into their place in the file, or written now.
+void Worker::emit(const char* p, size_t n, bool whole_job)
+{
+  off_t at_off = -1;
+  if (!r.order.claim(j, n, whole_job, &at_off)) return;
+  auto t_w = Clock::now();
+  if (at_off >= 0) {
+    // A batch's text is hundreds of megabytes (262,144 reads x 33 rows x 28 bytes), and one thread copies 2.5-5 GB/s into the
+    // page cache: with two workers the 38 GB of a 50 M-read run were written at 5 GB/s and the run was that (round 6,
+    // profiles/round6_cli_syn1000_50m.txt).  The text goes out in slices of at least 16 MB, side by side (KR_CLI_WRITE_THREADS,
+    // default 4 per worker).
+    const int fd = fileno(r.out);
+    auto write_slice = [&](size_t a, size_t b) {
+      size_t done = a;
+      while (done < b) {
+        const ssize_t w = pwrite(fd, p + done, b - done, at_off + (off_t)done);
+        if (w < 0) {
+          if (errno == EINTR) continue;
+          r.order.fail(std::string("cannot write the output: ") + strerror(errno));
+          break;
+        }
+        done += (size_t)w;
+      }
+    };
+    const size_t nsl = std::max<size_t>(1, std::min<size_t>((size_t)s.write_threads, n >> 24));
+    std::vector<std::thread> ws_;
+    for (size_t q = 1; q < nsl; ++q) ws_.emplace_back(write_slice, n * q / nsl, n * (q + 1) / nsl);
+    write_slice(0, n / nsl);
+    for (auto& t_ : ws_) t_.join();
+  } else if (n) {
+    fwrite(p, 1, n, r.out);
+  }
+  r.ns_write += since(t_w);
+}
+
+// What a submit's rows are collected as: device text where the stream formats it (*on_device), else the row view
+// (KR_ERR_UNSUPPORTED: a DIST the device does not format -- the batch's rows, for the host formatter)
+int Worker::collect(kr_result_view* rv, const char** dtext, uint64_t* dlen, bool* on_device)
+{
+  if (!text_on) return kr_batch_collect(st, rv);
+  int rc = kr_batch_collect_text(st, dtext, dlen);
+  *on_device = rc == 0;
+  if (rc == KR_ERR_UNSUPPORTED) rc = kr_batch_collect(st, rv);
+  return rc;
+}
+
+// place --summarize: the piece's placements, `read` counted from `base`
+void Worker::keep_placements(int rc, kr_placement* pp, uint64_t npp, uint64_t base)
+{
+  for (uint64_t i = 0; !rc && i < npp; ++i) {
+    pp[i].read = (uint32_t)(base + pp[i].read);
+    pls.push_back(pp[i]);
+  }
+  kr_free(pp);
+}
+
+int Worker::run_halves(size_t lo, size_t hi)
+{
+  const size_t mid = lo + (hi - lo) / 2;
+  const int rc = run_batch(lo, mid);
+  return rc ? rc : run_batch(mid, hi);
+}
+
+// reads [lo, hi) of a host job; a batch that overflows a device-side buffer (KR_ERR_CAPACITY: unusually many
+// table hits or records per read) is resubmitted in halves, as include/krepp_amd.h prescribes
+int Worker::run_batch(size_t lo, size_t hi)
+{
+  const size_t n = hi - lo;
+  if (n > piece && n > 1) return run_halves(lo, hi); // known to be too much for one submit
+  const bool whole_job = lo == 0 && hi == j->n;
+  const char* const* nm = j->names + lo;
+  std::vector<uint64_t> offs(n + 1);
+  for (size_t i = lo; i <= hi; ++i) offs[i - lo] = j->offsets[i] - j->offsets[lo];
+  kr_result_view rv;
+  char* txt = nullptr;
+  uint64_t len = 0, dlen = 0;
+  const char* dtext = nullptr;
+  bool on_device = false;
+  auto t_dev = Clock::now();
+  int rc;
+  if (text_on) {
+    std::vector<uint32_t> id_off(n + 1);
+    for (size_t i = 0; i < n; ++i) id_off[i] = (uint32_t)(nm[i] - j->blob);
+    id_off[n] = hi < j->n ? (uint32_t)(nm[n] - j->blob) : (uint32_t)j->blob_bytes;
+    rc = kr_batch_submit_text(st, j->bases + j->offsets[lo], offs.data(), (uint32_t)n, KR_BASES_HOST | s.rows_flags(true), j->blob, id_off.data(), 1);
+  } else {
+    rc = kr_batch_submit(st, j->bases + j->offsets[lo], offs.data(), (uint32_t)n, KR_BASES_HOST | s.rows_flags(false));
+  }
+  if (!rc) rc = s.place ? kr_batch_wait(st) : collect(&rv, &dtext, &dlen, &on_device); // place: the records stay on the device
+  r.ns_dev += since(t_dev);
+  auto t_fmt = Clock::now();
+  if (rc == KR_ERR_CAPACITY && n > 1) {
+    piece = std::min(piece, (n + 1) / 2);
+    streak = 0;
+    return run_halves(lo, hi);
+  }
+  if (!rc && s.seek) rc = kr_format_seek(r.hx, r.dix[g], &rv, s.p.hdist_th, nm, &txt, &len);
+  if (!rc && on_device) {
+    ++r.nb_dev_text;
+    emit(dtext, dlen, whole_job); // (`j` is gone if these were all its rows)
+    succeeded();
+    return 0;
+  }
+  if (!rc && s.plain_dist()) {
+    rc = kr_format_dist(r.hx, &rv, nm, &txt, &len);
+    if (!rc) ++r.nb_host_text;
+  }
+  if (!rc && s.summarize && !s.place) add_weights(rv, wc, tw);
+  if (!rc && s.place) {
+    int prev = joins();
+    kr_placement* pp = nullptr;
+    uint64_t npp = 0;
+    rc = kr_place_stream(r.hx, r.dix[g], r.ptree, st, (uint32_t)n, offs.data(), nm, &s.p, s.tabular, &prev, &txt, &len, s.tabular == 2 ? &pp : nullptr,
+                         s.tabular == 2 ? &npp : nullptr);
+    keep_placements(rc, pp, npp, j->first_read + lo);
+  }
+  if (!rc && txt && s.dev_text)
+    emit(txt, len, false); // (in order with the pieces the device wrote)
+  else if (!rc && txt)
+    text.append(txt, len);
+  kr_free(txt);
+  r.ns_fmt += since(t_fmt);
+  if (!rc) succeeded();
+  return rc;
+}
+
+// the accepted records' names, NUL-terminated, cut out of the chunk for the host formatters
+int Worker::chunk_names(const uint8_t* raw, uint32_t n)
+{
+  const uint64_t* np = nullptr;
+  const uint32_t* nl = nullptr;
+  const int rc = kr_batch_fastq_names(st, &np, &nl);
+  if (rc) return rc;
+  std::vector<size_t> at_(n);
+  blob.clear();
+  for (uint32_t i = 0; i < n; ++i) at_[i] = blob.size(), blob.append((const char*)raw + np[i], nl[i]), blob.push_back('\0');
+  nptr.resize(n);
+  for (uint32_t i = 0; i < n; ++i) nptr[i] = blob.data() + at_[i];
+  return 0;
+}
+
+// --gpu-parse: the chunk's records found on the device, submitted again from `consumed` while a batch stops at capacity; anything
+// else that keeps it from being taken whole (`fell`) hands the file to the host reader from the first record not taken
+int Worker::run_chunk()
+{
+  if (r.order.dropped(*j)) return 0;
+  uint64_t pos = 0, nr_job = 0;
+  std::vector<double> wc_job(wc.size(), 0.0); // (sums that count only once the chunk's turn confirms it was not dropped)
+  double tw_job = 0;
+  bool fell = false;
+  // (KR_TILE_DEVICE: a long record stays with the device, tiled there)
+  const uint32_t flags = s.rows_flags(text_on) | (s.seek ? 0u : KR_TILE_DEVICE);
+  while (pos < j->raw_len) {
+    const uint8_t* raw = j->raw + pos;
+    kr_fastq_parse fp;
+    auto t_dev = Clock::now();
+    int rc = j->fasta ? kr_batch_submit_fasta(st, raw, j->raw_len - pos, flags, j->closed ? 1u : 0u, &fp)
+                      : kr_batch_submit_fastq(st, raw, j->raw_len - pos, flags, j->at_eof ? 1u : 0u, &fp);
+    if (rc) return rc;
+    if (fp.nreads) {
+      kr_result_view rv;
+      char* txt = nullptr;
+      uint64_t len = 0, dlen = 0;
+      const char* dtext = nullptr;
+      bool on_device = false;
+      if (!s.place) rc = collect(&rv, &dtext, &dlen, &on_device); // (place: kr_place_stream_parsed waits for the batch)
+      r.ns_dev += since(t_dev);
+      auto t_fmt = Clock::now();
+      if (!rc && on_device) {
+        ++r.nb_dev_text;
+        emit(dtext, dlen, false);
+      } else if (!rc && s.summarize && !s.place) {
+        add_weights(rv, wc_job, tw_job);
+      } else if (!rc && !s.place) {
+        rc = chunk_names(raw, fp.nreads);
+        if (!rc) rc = s.seek ? kr_format_seek(r.hx, r.dix[g], &rv, s.p.hdist_th, nptr.data(), &txt, &len) : kr_format_dist(r.hx, &rv, nptr.data(), &txt, &len);
+        if (!rc && !s.seek) ++r.nb_host_text;
+      } else if (!rc) {
+        int prev = joins();
+        kr_placement* pp = nullptr;
+        uint64_t npp = 0;
+        rc = kr_place_stream_parsed(r.hx, r.dix[g], r.ptree, st, raw, &s.p, s.tabular, &prev, &txt, &len, s.tabular == 2 ? &pp : nullptr,
+                                    s.tabular == 2 ? &npp : nullptr);
+        keep_placements(rc, pp, npp, nr_job); // (`read`: the number within the chunk; the chunk's first read is known when its turn comes)
+      }
+      if (!rc && txt && s.plain_dist())
+        emit(txt, len, false);
+      else if (!rc && txt)
+        text.append(txt, len);
+      kr_free(txt);
+      r.ns_fmt += since(t_fmt);
+      if (rc == KR_ERR_CAPACITY) { // more records or text than a batch holds: the host reader takes over at this batch's first record
+        fell = true;
+        break;
+      }
+      if (rc) return rc;
+      nr_job += fp.nreads;
+    }
+    pos += fp.consumed;
+    if (fp.status == KR_FASTQ_OK) break;
+    if (fp.status == KR_FASTQ_CAPACITY && fp.nreads) continue;
+    fell = true; // not clean, a record cut by the end of the chunk or the file: the host reader from here
+    break;
+  }
+  // in the output's order: only a chunk that no earlier chunk's stop has dropped counts
+  if (!r.order.wait_turn(*j)) {
+    text.clear(), pls.clear(); // (`place` / `seek`: rows made before the earlier chunk's stop was known)
+    return 0;
+  }
+  for (size_t q = 0; q < wc_job.size(); ++q) wc[q] += wc_job[q];
+  tw += tw_job;
+  // place --summarize sums per 512 reads by global read number: every chunk in front of this one has had its turn
+  j->first_read = r.nreads_dev, j->n = (size_t)nr_job;
+  for (kr_placement& x : pls) x.read = (uint32_t)(j->first_read + x.read);
+  r.nreads_dev += nr_job;
+  if (fell) r.order.stop_at(*j, j->raw_off + pos);
+  return 0;
+}
+
+// the writer thread: the jobs' texts in input order (jobs whose rows a worker wrote pass through empty)
+void Run::write_loop()
+{
+  while (std::unique_ptr<Job> j = order.take_next()) {
+    if (s.tabular == 2) {
+      const uint32_t end_group = (uint32_t)(j->first_read + j->n) >> 9;
+      carry.insert(carry.end(), j->pls.begin(), j->pls.end());
+      size_t cut = j->n ? carry.size() : 0; // (--gpu-parse: a chunk that was dropped, or stopped at its first record, has no reads and no last group)
+      if ((j->first_read + j->n) & 511u)
+        while (cut > 0 && (carry[cut - 1].read >> 9) == end_group) --cut;
+      if (kr_place_summary_add(ptree, carry.data(), cut, pwcount.data(), &ptwcount)) return order.fail(kr_last_error());
+      carry.erase(carry.begin(), carry.begin() + cut);
+    } else if (s.place && !s.tabular) {
+      if (!j->text.empty()) {
+        if (jplace_prev) fputs(",\n", out);
+        fwrite(j->text.data(), 1, j->text.size(), out);
+        jplace_prev = true;
+      }
+    } else {
+      auto t_w = Clock::now();
+      fwrite(j->text.data(), 1, j->text.size(), out);
+      ns_write += since(t_w);
+    }
+    j.reset();
+    order.advance();
+  }
+}
+
+// --gpu-parse: the reader moves bytes only, until the file ends or a chunk stops early
+void Run::read_chunks()
+{
+  auto t_parse = Clock::now();
+  uint64_t off = 0;
+  while (off < qsize) {
+    uint8_t* buf = nullptr;
+    {
+      std::unique_lock<std::mutex> lk(order.mu);
+      order.cv_work.wait(lk, [&] { return !raw_free.empty() || order.stopped_locked() || order.failed_locked(); });
+      if (order.stopped_locked() || order.failed_locked()) break; // (an early stop: nothing behind it will be used)
+      buf = raw_free.back();
+      raw_free.pop_back();
+    }
+    const uint64_t want = std::min<uint64_t>(s.chunk_bytes, qsize - off);
+    uint64_t got = 0;
+    while (got < want) {
+      const ssize_t k = pread(qfd, buf + got, want - got, (off_t)(off + got));
+      if (k <= 0) error_exit("cannot read " + s.query);
+      got += (uint64_t)k;
+    }
+    // The chunk ends at its last record start: what lies in front of it is whole records.  None (FASTA: the chunk's one record is
+    // longer than the chunk; FASTQ: no line that looks like a record start): it goes out whole, its last record stops INCOMPLETE
+    // and the host reader takes over there
+    const bool last = off + want >= qsize;
+    const uint64_t c = last ? 0 : fasta_parse ? kr_fasta_chunk_cut(buf, want) : kr_fastq_chunk_cut(buf, want);
+    const uint64_t cut = c ? c : want;
+    std::unique_ptr<Job> j(new Job());
+    j->raw = buf, j->raw_len = cut, j->raw_off = off, j->at_eof = last && cut == want;
+    j->fasta = fasta_parse, j->closed = last || (fasta_parse && c);
+    off += cut;
+    enqueue(std::move(j));
+  }
+  ns_parse += since(t_parse);
+  { // every chunk handed out is done (an earlier one may still stop early): then the first stop, if any, is final
+    std::unique_lock<std::mutex> lk(order.mu);
+    order.cv_done.wait(lk, [&] { return gpu_done == gpu_issued || order.failed_locked(); });
+  }
+  close(qfd);
+  nreads_total = nreads_dev; // (the host reader, if it takes over, numbers its reads behind the device's: place --summarize)
+  uint64_t fb_off = 0;
+  if (order.stopped(&fb_off) && !order.failed() && kr_fastx_open_at(s.query.c_str(), fb_off, &fx)) error_exit(kr_last_error());
+}
+
+// the host reader: batches of parsed records, split so that they fit the stream limits
+void Run::read_host()
+{
+  while (!order.failed()) { // (a worker without a stream, or one whose batch failed: reported at the end)
     kr_fastx_batch b;
-    auto t_parse = now();
-    if (kr_fastx_next(fx, batch_bases, &b)) error_exit(kr_last_error());
+    auto t_parse = Clock::now();
+    if (kr_fastx_next(fx, s.batch_bases, &b)) error_exit(kr_last_error());
     ns_parse += since(t_parse);
-    auto t_job = now();
-    // split over-long batches so that they fit the stream limits
+    auto t_job = Clock::now();
     uint32_t r0 = 0;
     while (r0 < b.nreads) {
       uint32_t r1 = r0;
-      while (r1 < b.nreads && r1 - r0 < max_reads && b.offsets[r1 + 1] - b.offsets[r0] <= max_bases) ++r1;
+      while (r1 < b.nreads && r1 - r0 < s.max_reads && b.offsets[r1 + 1] - b.offsets[r0] <= s.max_bases) ++r1;
       if (r1 == r0) error_exit("A query sequence is longer than the supported maximum per batch");
-      Job* j = new Job();
+      std::unique_ptr<Job> j(new Job());
       j->n = r1 - r0;
-      if (r0 == 0 && r1 == b.nreads && !getenv("KR_CLI_COPY_BATCHES")) {
+      if (r0 == 0 && r1 == b.nreads && !s.copy_batches) {
         // the whole batch is one job: it changes hands as it is (QSeq gives IBatch its vectors by swap, src/query.cpp:32-33); the
         // reader thread copies nothing and the worker gives the buffers back when the batch is done
         if (kr_fastx_detach(fx, &j->held)) error_exit(kr_last_error());
@@ -912,36 +1006,34 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
       j->blob_bytes = (size_t)(j->names[j->n - 1] - j->names[0]) + strlen(j->names[j->n - 1]) + 1;
       j->first_read = nreads_total;
       nreads_total += r1 - r0;
-      {
-        std::unique_lock<std::mutex> lk(mu);
-        j->seq = nbatches++;
-        // bound the number of batches in flight
-        cv_work.wait(lk, [&] { return todo.size() < (size_t)(2 * nworkers) || !worker_err.empty(); });
-        todo.push_back(j);
-      }
-      cv_work.notify_all();
+      enqueue(std::move(j));
       r0 = r1;
     }
     ns_job += since(t_job);
     if (!b.more) break;
   }
-  if (timing) fprintf(stderr, "[timing] reader: end of input at %.3f s (%llu batches)\n", at(), (unsigned long long)nbatches);
+}
+
+void Run::end_of_input()
+{
+  if (s.timing) fprintf(stderr, "[timing] reader: end of input at %.3f s (%llu batches)\n", at(), (unsigned long long)nbatches);
   {
-    std::lock_guard<std::mutex> lk(mu);
+    std::lock_guard<std::mutex> lk(order.mu);
     eof = true;
-    total_batches = nbatches;
   }
-  cv_work.notify_all();
-  cv_done.notify_all();
-  for (auto& w : workers) w.join();
-  cv_done.notify_all();
-  ready_watch.join();
-  writer.join();
-  if (!worker_err.empty()) error_exit(worker_err);
-  if (summarize && !place) // src/krepp.cpp:388-393 (ascending colour id instead of hash-map order)
+  order.cv_work.notify_all();
+  order.close(nbatches);
+}
+
+// every thread has been joined: the summary rows, the jplace frame, the closing lines; then the process ends, or tears down
+int Run::finish()
+{
+  const bool place = s.place, seek = s.seek;
+  if (order.failed()) error_exit(order.error());
+  if (s.summarize && !place) // src/krepp.cpp:388-393 (ascending colour id instead of hash-map order)
     for (uint32_t se = 0; se < wcount.size(); ++se)
       if (wcount[se] != 0) fprintf(out, "%s\t%.5f\t%.5f\n", kr_host_index_node_name(hx, se), wcount[se], wcount[se] / twcount);
-  if (tabular == 2) { // src/krepp.cpp:493-497
+  if (s.tabular == 2) { // src/krepp.cpp:493-497
     char* t = nullptr;
     uint64_t l = 0;
     if (kr_place_summary_add(ptree, carry.data(), carry.size(), pwcount.data(), &ptwcount) ||
@@ -953,43 +1045,60 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
   if (place) {
     char* t = nullptr;
     uint64_t l = 0;
-    if (kr_place_frame(ptree, 1, tabular, invocation.c_str(), nreads_total, &t, &l)) error_exit(kr_last_error());
+    if (kr_place_frame(ptree, 1, s.tabular, s.invocation.c_str(), nreads_total, &t, &l)) error_exit(kr_last_error());
     fwrite(t, 1, l, out);
     kr_free(t);
     kr_place_tree_free(ptree);
   }
-  if (out_seekable) {
-    fflush(out);
-    (void)fseeko(out, file_off, SEEK_SET);
-  }
+  order.rewind_to_end(out);
   if (out != stdout) fclose(out);
-  double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  const double sec = at();
   fprintf(stderr, place ? "Done placing queries, elapsed: %g sec (%.0f reads/s on %d GPU(s))\n" : seek ? "Done seeking query sequences, elapsed: %g sec (%.0f reads/s on %d GPU(s))\n" : "Done estimating distances, elapsed: %g sec (%.0f reads/s on %d GPU(s))\n", sec,
-          sec > 0 ? nreads_total / sec : 0.0, ngpus);
-  if (timing)
+          sec > 0 ? nreads_total / sec : 0.0, s.ngpus);
+  if (s.timing)
     fprintf(stderr, "[timing] parse %.3f s, job hand-over (incl. waiting for queue space) %.3f s, device %.3f s, format %.3f s, write %.3f s; of the elapsed time, until the last worker had its stream and page-locked buffers: %.3f s (the reader parses meanwhile)\n",
             ns_parse / 1e9, ns_job / 1e9, ns_dev / 1e9, ns_fmt / 1e9, ns_write / 1e9, std::chrono::duration<double>(t_loop - t_init).count());
-  if (timing && gpu_parse)
+  if (s.timing && gpu_parse)
     fprintf(stderr, "[timing] gpu-parse: %llu %s records found on the device\n", (unsigned long long)nreads_dev.load(), fasta_parse ? "FASTA" : "FASTQ");
-  if (timing && !place && !seek && !summarize) // (a batch split at capacity counts once per piece)
+  if (s.timing && s.plain_dist()) // (a batch split at capacity counts once per piece)
     fprintf(stderr, "[timing] report text: %llu batches written from device text, %llu through the host formatter\n", (unsigned long long)nb_dev_text.load(),
             (unsigned long long)nb_host_text.load());
   fprintf(stderr, "Total number of sequences queried: %llu\n", (unsigned long long)nreads_total);
   // Everything is written.  Unmapping 19 GB of index, 10 GB of host tables and the page-locked buffers one by one takes 0.8-1.2 s
   // that nobody is waiting for: the process ends here and the kernel reclaims the lot (KR_CLI_CLEAN_EXIT=1: free everything in
   // order -- leak checkers, tests of the tear-down path).
-  if (!getenv("KR_CLI_CLEAN_EXIT")) {
+  if (!s.clean_exit) {
     fflush(stdout);
     fflush(stderr);
     _exit(0);
   }
-  auto t_down = now();
+  auto t_down = Clock::now();
   kr_fastx_close(fx); // (the reader's thread pool and chunk buffers)
   for (kr_stream* st : streams_to_free) kr_stream_destroy(st);
   for (auto* d : dix) kr_index_free(d);
   kr_host_index_free(hx);
-  if (timing) fprintf(stderr, "[timing] tear-down %.3f s\n", since(t_down) / 1e9);
+  if (s.timing) fprintf(stderr, "[timing] tear-down %.3f s\n", since(t_down) / 1e9);
   return 0;
+}
+
+// reader (this thread) -> one worker per stream, each GPU with its own replica of the index -> writer, in input order
+static int run_query(const Args& a, const std::string& invocation, int mode)
+{
+  const Settings s = resolve_settings(a, invocation, mode);
+  Run r(s);
+  r.start_up(a);
+  r.open_input();
+  std::vector<std::thread> workers;
+  for (int w = 0; w < s.nworkers; ++w) workers.emplace_back([&r, w] { Worker(r, w % r.s.ngpus).loop(); });
+  std::thread writer([&r] { r.write_loop(); });
+  if (s.seek) fprintf(stderr, "Seeking query sequences in the sketch...\n");
+  if (!s.place && !s.seek) fprintf(stderr, "Estimating distances between given sequences and references...\n");
+  if (r.gpu_parse) r.read_chunks();
+  if (r.fx) r.read_host();
+  r.end_of_input();
+  for (auto& w : workers) w.join();
+  writer.join();
+  return r.finish();
 }
 
 // --sdust-t / --sdust-w (src/krepp.cpp:530-531,576-577): non-negative integers, masking on when both are positive, and then the

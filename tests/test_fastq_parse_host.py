@@ -83,3 +83,45 @@ def test_cli_help_lists_gpu_parse():
     exe = os.path.join(ROOT, "krepp_amd", "lib", "krepp")
     out = subprocess.run([exe, "dist", "--help"], capture_output=True).stdout.decode()
     assert "--gpu-parse" in out and "FASTQ records found on the GPU (identical output" in out, out
+
+
+def test_fastq_chunk_cut_is_the_last_record_start_whose_plus_line_is_inside(capi):
+    """kr_fastq_chunk_cut on prefixes of clean four-line records: the last record start s > 0 whose '+' line begins inside the
+    prefix (its name and sequence lines are then complete, and a byte follows them), by the generator's own bookkeeping; quality
+    lines that begin with '@' or '+' are no record starts.  0 when there is none, for no bytes, and when the last MiB has no newline."""
+    import numpy as np
+    rng = np.random.default_rng(20260119)
+    qual = np.frombuffer(b"@+!#5?FIJ~", np.uint8)
+    parts, starts, plus, pos = [], [], [], 0
+    for i in range(3000):
+        ln = int(rng.integers(1, 151))
+        name = b"@r%d" % i + (b" lane %d/1" % int(rng.integers(0, 9)) if i % 3 == 0 else b"")
+        seq = np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, ln)].tobytes()
+        q = bytearray(qual[rng.integers(2, len(qual), ln)].tobytes())
+        if i % 5 == 1:
+            q[0] = ord("@")
+        if i % 5 == 3:
+            q[0] = ord("+")
+        rec = name + b"\n" + seq + b"\n+" + (name[1:] if i % 7 == 0 else b"") + b"\n" + bytes(q) + b"\n"
+        starts.append(pos)
+        plus.append(pos + len(name) + 1 + ln + 1)
+        parts.append(rec)
+        pos += len(rec)
+    raw = b"".join(parts)
+    assert len(raw) < (1 << 20) and all(raw[s] == 64 for s in starts) and all(raw[p] == 43 and raw[p - 1] == 10 for p in plus)
+    starts, plus = np.array(starts), np.array(plus)
+
+    def want(n):  # (plus is ascending: the records in front of the first '+' at or behind n)
+        k = int(np.searchsorted(plus, n, side="left")) - 1
+        return int(starts[k]) if k >= 1 else 0
+
+    lib = capi.load()
+    assert lib.kr_fastq_chunk_cut(None, 0) == 0 and lib.kr_fastq_chunk_cut(None, 4096) == 0
+    ns = {0, 1, len(raw), len(raw) - 1} | set(range(int(starts[0]), int(starts[3]) + 2)) | set(range(int(starts[1500]) - 2, int(starts[1502]) + 2))
+    ns |= {int(x) for x in rng.integers(0, len(raw) + 1, 400)}
+    ns |= {int(p) + d for p in plus[rng.integers(0, len(plus), 60)] for d in (0, 1)}
+    for n in sorted(ns):
+        assert capi.fastq_chunk_cut(raw[:n]) == want(n), n
+    assert want(0) == want(1) == 0 and want(int(plus[1])) == 0 and want(int(plus[1]) + 1) == int(starts[1])
+    # longer than 1 MiB, no newline in the last MiB: no cut, whatever lies in front
+    assert capi.fastq_chunk_cut(raw[:int(starts[2000])] + b"@long\n" + b"A" * ((1 << 20) + 7)) == 0
