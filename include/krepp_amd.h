@@ -624,6 +624,41 @@ KR_API int kr_debug_fastq_parse_ms(kr_stream*, float* ms);
 KR_API int kr_batch_submit_fasta(kr_stream*, const uint8_t* raw, uint64_t nbytes, uint32_t flags, uint32_t closed, kr_fastq_parse* out);
 KR_API uint64_t kr_fasta_chunk_cut(const uint8_t* buf, uint64_t n);
 KR_API uint64_t kr_fastq_chunk_cut(const uint8_t* buf, uint64_t n);
+
+/* ---- `seek` on kernels of its own (csrc/kr_dev_seek.inc; docs/design/13_seek.md; INTEGRATION.md "A seek batch") ----
+ * SBatch::seek_sequences (src/seek.cpp:22-126) on a SKETCH index (kr_host_sketch_load): per k-mer and strand the minimum Hamming
+ * distance over one bucket, a histogram of hdist_th + 1 bins per strand, one minimisation per strand, the smaller d -- or NaN when
+ * neither strand matched.  A batch flagged KR_SEEK runs these kernels instead of the dist chain: no item list, no record slots, no
+ * accumulate scratch; a sequence of any length is split into units of kr_debug_seek_layout's [0] k-mer positions, one wave each,
+ * whose counts are added with integer atomics (exact, deterministic).  It runs as one lane, ordered by the index's kernel chain.
+ *   kr_stream_seek_enable   once per stream, on a sketch index (else KR_ERR_ARG): the per-read counters and values; with
+ *                           max_text_bytes / max_id_bytes (both, or both 0: values only) the id and text buffers, unless
+ *                           kr_stream_text_enable made them already (then they must be at least as large: KR_ERR_STATE)
+ *   kr_batch_submit(flags | KR_SEEK)        with KR_BASES_HOST, KR_BASES_PINNED or KR_BASES_DEVICE; then kr_batch_collect_seek
+ *   kr_batch_submit_text(flags | KR_SEEK)   the same with ids; kr_batch_collect_text returns the report: SEQ_ID '\t' DIST '\n' with
+ *                           DIST as "%.5f", or SEQ_ID "\tNaN\n" (byte for byte kr_format_seek's); more text than max_text_bytes:
+ *                           KR_ERR_CAPACITY.  kr_batch_collect_seek serves such a batch too
+ *   kr_batch_submit_fastq / _fasta(KR_SEEK)   the accepted prefix as a seek batch (text when the stream has text buffers); alone,
+ *                           the record finder stops at the first long record as ever (KR_FASTQ_LONG); with KR_SEEK | KR_TILE_DEVICE
+ *                           long records are accepted, NO tile layout is built and the seek units do the splitting
+ * KR_SEEK is refused (KR_ERR_ARG) with KR_TAP_ACCS, KR_TAP_HITS, KR_ROWS_ONLY, KR_ROWS_INDEXED, KR_TILE_ROWS, and with KR_TILE_DEVICE
+ * on kr_batch_submit / kr_batch_submit_text; KR_ERR_STATE when seek was not enabled.  kr_batch_wait serves a seek batch;
+ * kr_batch_collect, kr_batch_collect_device and kr_batch_timing give KR_ERR_STATE after one, kr_batch_collect_seek after a batch
+ * that was not one, kr_batch_collect_text after a seek batch without ids. */
+#define KR_SEEK 256u  /* the batch is a `seek` batch: seek kernels instead of the dist chain (sketch indexes only) */
+
+typedef struct kr_seek_view {
+  uint32_t nreads, np;        /* np = hdist_th + 1 */
+  const double*   d;          /* [nreads]  reported DIST, NaN: no k-mer of either strand matched */
+  const double*   d_strand;   /* [2*nreads] d of the forward / reverse-complement summary (where d is not NaN) */
+  const uint32_t* hist;       /* [nreads*2*np] matched k-mers by minimum Hamming distance: read, strand, bin */
+  const uint32_t* onmers;     /* [nreads]  valid k-mers */
+} kr_seek_view;               /* page-locked, valid until the stream's next submit */
+
+KR_API int kr_stream_seek_enable(kr_stream*, uint64_t max_text_bytes, uint64_t max_id_bytes); /* 0, 0: values only, no text */
+KR_API int kr_batch_collect_seek(kr_stream*, kr_seek_view* out);
+KR_API int kr_debug_seek_layout(uint32_t* out4);   /* [0] = T (positions per unit), [1] positions per segment, [2] waves per workgroup of the hist kernel, [3] reads per prefix block; no device needed */
+KR_API int kr_debug_seek_ms(kr_stream*, float* ms3); /* hist (with the unit count), solve, text of the last seek batch (HIP events) */
 /* tests: the tiled form of the batch last submitted on the stream as it lies on the device, laid out by the host (a host batch)
  * or by kernels (KR_TILE_DEVICE): reads of the tiled batch and long sequences; voff [nv + 1] where every read of the tiled batch
  * starts in its bases, vtile [nv] 1 = a tile of a long sequence, rfirst [nreads] the caller's read's first read of the tiled batch,

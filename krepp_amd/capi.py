@@ -22,6 +22,7 @@ KR_VIEW_HOST, KR_VIEW_DEVICE = 0, 1
 KR_BASES_HOST, KR_BASES_DEVICE, KR_TAP_ACCS, KR_TAP_HITS, KR_BASES_PINNED, KR_ROWS_ONLY, KR_ROWS_INDEXED = 0, 1, 2, 4, 8, 16, 32
 KR_TILE_DEVICE = 64  # with KR_BASES_DEVICE / submit_fastq: long sequences of a batch in HBM are tiled by kernels
 KR_TILE_ROWS = 128  # with KR_ROWS_ONLY: a batch that ends up tiled leaves the device as compact rows (and as device text) too
+KR_SEEK = 256  # the batch is a `seek` batch: seek kernels instead of the dist chain (sketch indexes only)
 
 u8p = C.POINTER(C.c_uint8)
 u32p = C.POINTER(C.c_uint32)
@@ -56,6 +57,11 @@ class KrResultView(C.Structure):
                 ("rec_key", u32p), ("rec_sel", u8p), ("rec_d", f64p), ("rec_v", f64p),
                 ("rec_chisq", f64p), ("rec_hist", u32p), ("rec_hist_stride", C.c_uint64), ("nrows", C.c_uint64),
                 ("rec_dix", u32p), ("dist_list", f64p), ("ndist", C.c_uint64)]
+
+
+class KrSeekView(C.Structure):
+    _fields_ = [("nreads", C.c_uint32), ("np", C.c_uint32), ("d", C.POINTER(C.c_double)), ("d_strand", C.POINTER(C.c_double)),
+                ("hist", u32p), ("onmers", u32p)]
 
 
 class KrHit(C.Structure):
@@ -123,6 +129,7 @@ EXPORTS = [
     "kr_debug_last_d2h_bytes", "kr_debug_indexed_list", "kr_debug_select", "kr_debug_select_check", "kr_debug_select_layout", "kr_debug_acc_paths", "kr_debug_acc_layout", "kr_debug_scan_layout", "kr_debug_scan_stream", "kr_debug_place_fixed5", "kr_place_text_counters", "kr_place_path_counters", "kr_fastx_open", "kr_fastx_open_at", "kr_fastx_next", "kr_fastx_detach", "kr_fastx_release", "kr_fastx_close", "kr_fastx_parallel_chunks", "kr_fastx_pgz_stats", "kr_format_dist", "kr_debug_fixed5", "kr_free", "kr_host_alloc", "kr_host_free",
     "kr_build_index", "kr_minimizers_cpu", "kr_minimizers_device", "kr_minimizers_free", "kr_last_error", "kr_version",
     "kr_sdust_cpu", "kr_sdust_free",
+    "kr_stream_seek_enable", "kr_batch_collect_seek", "kr_debug_seek_layout", "kr_debug_seek_ms",
 ]
 
 # kr_debug_acc_paths: the accumulate kernel's path witnesses, in the order of CounterSlot (kr_dev_common.inc)
@@ -244,6 +251,10 @@ def load():
     lib.kr_debug_fastq_batch.argtypes = [vp, vp, vp]
     lib.kr_debug_fastq_parse_ms.argtypes = [vp, C.POINTER(C.c_float)]
     lib.kr_debug_tile_layout.argtypes = [vp, u32p, u32p, vp, vp, vp, vp, vp]
+    lib.kr_stream_seek_enable.argtypes = [vp, C.c_uint64, C.c_uint64]
+    lib.kr_batch_collect_seek.argtypes = [vp, C.POINTER(KrSeekView)]
+    lib.kr_debug_seek_layout.argtypes = [u32p]
+    lib.kr_debug_seek_ms.argtypes = [vp, C.POINTER(C.c_float)]
     lib.kr_debug_tile_shape.argtypes = [C.c_uint64, C.c_uint32, u64p, u64p, u64p]
     lib.kr_fastx_next.argtypes = [vp, C.c_uint64, C.POINTER(KrFastxBatch)]
     lib.kr_fastx_detach.argtypes = [vp, C.POINTER(vp)]
@@ -736,6 +747,25 @@ class Stream:
         check(self.lib.kr_batch_collect_text(self.h, C.byref(txt), C.byref(ln)))
         return C.string_at(txt, ln.value) if ln.value else b""
 
+    def seek_enable(self, max_text_bytes=0, max_id_bytes=0):
+        """kr_stream_seek_enable: this stream takes batches flagged KR_SEEK (csrc/kr_dev_seek.inc); 0, 0: values only, no text"""
+        check(self.lib.kr_stream_seek_enable(self.h, int(max_text_bytes), int(max_id_bytes)))
+
+    def collect_seek(self):
+        """kr_batch_collect_seek: numpy copies of the seek batch's values -- d [nreads], d_strand [nreads, 2], hist [nreads, 2, np],
+        onmers [nreads]"""
+        v = KrSeekView()
+        check(self.lib.kr_batch_collect_seek(self.h, C.byref(v)))
+        n, npl = int(v.nreads), int(v.np)
+        return {"nreads": n, "np": npl, "d": _np(v.d, n, np.float64), "d_strand": _np(v.d_strand, 2 * n, np.float64).reshape(n, 2),
+                "hist": _np(v.hist, n * 2 * npl, np.uint32).reshape(n, 2, npl), "onmers": _np(v.onmers, n, np.uint32)}
+
+    def seek_ms(self):
+        """kr_debug_seek_ms: device milliseconds of the last seek batch's hist, solve and text stages"""
+        ms = (C.c_float * 3)()
+        check(self.lib.kr_debug_seek_ms(self.h, ms))
+        return tuple(float(x) for x in ms)
+
     def format_dist(self, host_index, names):
         arr = (C.c_char_p * len(names))(*[n.encode() for n in names])
         txt = C.c_void_p()
@@ -803,6 +833,14 @@ def select_check(t, max_reads, max_records, nnodes, hdist_th=4, direct_nodes=0):
     """(tests, no device) kr_debug_select_check: the return code.  direct_nodes: the nodes the stream's direct part is laid out for"""
     s, keep = select_tables(t)
     return load().kr_debug_select_check(C.byref(s), int(max_reads), int(max_records), int(nnodes), int(hdist_th), int(direct_nodes))
+
+
+def seek_layout():
+    """kr_debug_seek_layout (no device): positions per unit, positions per segment, waves per workgroup of the hist kernel, reads per
+    prefix block"""
+    out = (C.c_uint32 * 4)()
+    check(load().kr_debug_seek_layout(out))
+    return {"unit": int(out[0]), "segment": int(out[1]), "hist_waves": int(out[2]), "row_block": int(out[3])}
 
 
 def scan_layout(slot_format, log_g=0):

@@ -45,6 +45,7 @@
 //   kr_dev_tiles.inc       long sequences across waves: tiles of a host batch, their merge per key, the real reads' results
 //   kr_dev_likelihood.inc  likelihood, Brent, de-duplication, selection kernels
 //   kr_dev_text.inc        the report rows as text, written on the device (kr_batch_submit_text / kr_batch_collect_text)
+//   kr_dev_seek.inc        `seek` on kernels of its own (a batch flagged KR_SEEK): unit split, histograms per strand, solver, report text
 //   kr_dev_fastq.inc       FASTQ records found in a chunk of raw file bytes (kr_batch_submit_fastq)
 //   kr_dev_fasta.inc       FASTA records found in a chunk of raw file bytes, every pass parallel over bytes (kr_batch_submit_fasta)
 //   kr_dev_place.inc       back end of `place`: ancestor accumulation, candidates, their likelihoods (kr_place_kernel)
@@ -56,6 +57,7 @@
 //   kr_host_fastq.inc      kr_stream_fastq_enable, kr_batch_submit_fastq, kr_batch_fastq_names
 //   kr_host_fasta.inc      kr_batch_submit_fasta
 //   kr_host_place.inc      kr::place_on_device (launch of the place kernels for kr_place_stream and kr_place_stream_parsed)
+//   kr_host_seek.inc       kr_stream_seek_enable, a KR_SEEK batch's submit / wait, kr_batch_collect_seek, kr_debug_seek_layout / _ms
 //   (below, in this file)  kr_host_alloc, debug entry points, kr_llh_batch, kr_llh_eval_indexed
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -91,6 +93,7 @@ namespace {
 #include "kr_dev_tiles.inc"
 #include "kr_dev_likelihood.inc"
 #include "kr_dev_text.inc"
+#include "kr_dev_seek.inc"
 #include "kr_dev_fastq.inc"
 #include "kr_dev_fasta.inc"
 #include "kr_dev_place.inc"
@@ -158,6 +161,7 @@ LlhConst make_llh_const(uint32_t k, uint32_t h, uint32_t th)
 #include "kr_host_fastq.inc"
 #include "kr_host_fasta.inc"
 #include "kr_host_place.inc"
+#include "kr_host_seek.inc"
 
 // Room for `need` doubles in the index's likelihood workspace, device and page-locked (under ix->llh_mu); grown with 25 % to spare
 static int llh_workspace(const kr_index* ix, uint64_t need)

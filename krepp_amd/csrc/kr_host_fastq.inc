@@ -18,6 +18,8 @@ int fq_begin(kr_stream* s, const char* fn, const uint8_t* raw, uint64_t nbytes, 
   if (!s->fq.on) return kr::fail(KR_ERR_STATE, who + "kr_stream_fastq_enable first");
   if (nbytes > s->fq.raw_cap) return kr::fail(KR_ERR_ARG, who + "more bytes than kr_stream_fastq_enable sized the stream for");
   if (flags & (KR_BASES_DEVICE | KR_BASES_PINNED)) return kr::fail(KR_ERR_ARG, who + "the bases are the record finder's: no KR_BASES_* flags");
+  if (flags & KR_SEEK) // (a seek batch: with KR_TILE_DEVICE long records are accepted and the seek units do the splitting)
+    if (int rc = seek_check(s, flags, true, fn)) return rc;
   memset(out, 0, sizeof(*out));
   out->at_eof = at_eof ? 1u : 0u;
   kr_stream::Fastq& f = s->fq;
@@ -25,7 +27,7 @@ int fq_begin(kr_stream* s, const char* fn, const uint8_t* raw, uint64_t nbytes, 
     f.parsed = true, f.nreads = 0, f.have_names = false;
     return KR_OK;
   }
-  text = s->text.on && !(flags & (KR_TAP_ACCS | KR_TAP_HITS));
+  text = s->text.on && !(flags & (KR_TAP_ACCS | KR_TAP_HITS)) && ((flags & KR_SEEK) || !s->text.seek_only);
   HIP_TRY(hipSetDevice(s->ix->device));
   (void)hipGetLastError();
   if (s->submitted && !s->waited) // d_bases, d_offsets and the ids belong to the batch in flight
@@ -74,7 +76,12 @@ int fq_finish(kr_stream* s, uint32_t flags, uint32_t at_eof, bool text, kr_fastq
   if (out->nreads == 0) return KR_OK;
   kr_stream::Text& t = s->text;
   int rc;
-  if (text) {
+  if (flags & KR_SEEK) { // no dist tile layout: the batch as the record finder left it
+    t.id_bytes = out->id_bytes, t.id_sep = 0;
+    t.req = text, t.ids_on_device = text;
+    rc = seek_submit(s, s->d_bases, s->d_offsets, out->nreads, KR_SEEK | KR_BASES_DEVICE);
+    if (rc) t.req = false;
+  } else if (text) {
     t.id_bytes = out->id_bytes, t.id_sep = 0;
     t.req = true, t.ids_on_device = true;
     rc = submit_batch(s, s->d_bases, s->d_offsets, out->nreads, flags | KR_ROWS_ONLY | KR_BASES_DEVICE);

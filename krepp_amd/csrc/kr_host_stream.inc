@@ -186,7 +186,23 @@ struct kr_stream {
     PinBuf<char> h_text; // (made by the first batch that needs it, as large as that batch's text asks)
     uint64_t text_cap = 0, id_bytes = 0;
     bool ids_on_device = false; // the batch's ids were written into d_ids / d_id_off by the record finder (kr_batch_submit_fastq)
+    bool seek_only = false;     // the buffers were made by kr_stream_seek_enable: no node names are uploaded, `dist` text is not served
   } text;
+  // `seek` on kernels of its own (kr_dev_seek.inc, kr_host_seek.inc; kr_stream_seek_enable).  A seek batch runs as one lane and uses
+  // none of the item list, the record slots or the accumulate scratch
+  struct Seek {
+    bool on = false;
+    bool active = false;    // the batch in flight (or the last one) is a seek batch
+    bool have_view = false; // ... and its values are in the page-locked mirrors
+    uint32_t np = 0;
+    uint32_t *d_first = nullptr, *d_bsum = nullptr; // [max_reads + 1], [max_reads / kRowBlock + 2]
+    uint32_t* d_cnt = nullptr;                      // a batch's hist [nreads * 2 * np], then its onmers [nreads]
+    double* d_d = nullptr;                          // a batch's d [nreads], then its d_strand [2 * nreads]
+    uint32_t* h_cnt = nullptr;
+    double* h_d = nullptr;
+    hipEvent_t ev[4] = {}; // in front of the unit count, behind the hist kernel, behind the solve kernel, behind the text kernels
+    bool timed = false;
+  } seek;
   // FASTQ records found on the device (kr_dev_fastq.inc; kr_stream_fastq_enable)
   struct Fastq {
     bool on = false;
@@ -720,6 +736,11 @@ int launch_lane(kr_stream* s, Lane& L, uint32_t flags)
 
 } // namespace
 
+// kr_host_seek.inc: a batch submitted with KR_SEEK leaves the dist chain here
+static int seek_check(const kr_stream* s, uint32_t flags, bool tile_ok, const char* who);
+static int seek_submit(kr_stream* s, const uint8_t* bases, const uint64_t* offsets, uint32_t nreads, uint32_t flags);
+static int seek_wait(kr_stream* s);
+
 extern "C" {
 
 int kr_stream_create(const kr_index* ix, const kr_params* p, uint32_t max_reads, uint64_t max_bases, uint64_t max_records,
@@ -949,6 +970,8 @@ void kr_stream_destroy(kr_stream* s)
   for (hipStream_t st : s->moved_streams) (void)hipStreamDestroy(st);
   if (s->fq.ev_parse0) (void)hipEventDestroy(s->fq.ev_parse0);
   if (s->fq.ev_parse1) (void)hipEventDestroy(s->fq.ev_parse1);
+  for (auto& e : s->seek.ev)
+    if (e) (void)hipEventDestroy(e);
   delete s; // (every DevBuf / PinBuf of the stream frees itself here: the device is set, the lanes' streams have been waited for)
 }
 
@@ -960,11 +983,14 @@ int kr_batch_submit(kr_stream* s, const uint8_t* bases, const uint64_t* offsets,
 }
 
 // ---- report text on the device (include/krepp_amd.h; kernels: kr_dev_text.inc) ----
+static int text_buffers(kr_stream* s, uint64_t max_text_bytes, uint64_t max_id_bytes);
 int kr_stream_text_enable(kr_stream* s, const kr_host_index* h, uint64_t max_text_bytes, uint64_t max_id_bytes)
 {
   kr::clear_error();
   if (!s || !h || max_text_bytes == 0 || max_id_bytes == 0) return kr::fail(KR_ERR_ARG, "kr_stream_text_enable: bad argument");
-  if (s->text.on) return kr::fail(KR_ERR_STATE, "kr_stream_text_enable: already enabled");
+  if (s->text.on && !s->text.seek_only) return kr::fail(KR_ERR_STATE, "kr_stream_text_enable: already enabled");
+  if (s->text.on && (max_text_bytes > s->text.text_cap || max_id_bytes > s->text.id_cap))
+    return kr::fail(KR_ERR_STATE, "kr_stream_text_enable: kr_stream_seek_enable made smaller text buffers on this stream: enable the dist text first");
   if (max_id_bytes >= (1ull << 32)) return kr::fail(KR_ERR_ARG, "kr_stream_text_enable: the ids of one batch must stay below 4 GB");
   HIP_TRY(hipSetDevice(s->ix->device));
   const kr_index* ix = s->ix;
@@ -990,6 +1016,17 @@ int kr_stream_text_enable(kr_stream* s, const kr_host_index* h, uint64_t max_tex
     }
   }
   kr_stream::Text& t = s->text;
+  if (t.on) { // (the seek text's buffers serve: the node names were all that was missing)
+    t.seek_only = false;
+    return KR_OK;
+  }
+  return text_buffers(s, max_text_bytes, max_id_bytes);
+}
+
+// the buffers of the device text, for kr_stream_text_enable and kr_stream_seek_enable
+static int text_buffers(kr_stream* s, uint64_t max_text_bytes, uint64_t max_id_bytes)
+{
+  kr_stream::Text& t = s->text;
   int rc = 0;
   const uint64_t nblk = (uint64_t)s->max_reads / kRowBlock + 2;
   if ((rc = salloc(s, &t.d_ids, max_id_bytes)) || (rc = salloc(s, &t.d_id_off, (uint64_t)s->max_reads + 1)) || (rc = salloc(s, &t.d_tlen, (uint64_t)s->max_reads)) ||
@@ -1011,6 +1048,11 @@ int kr_batch_submit_text(kr_stream* s, const uint8_t* bases, const uint64_t* off
   if (!s || !ids || !id_off) return kr::fail(KR_ERR_ARG, "kr_batch_submit_text: null argument");
   if (!s->text.on) return kr::fail(KR_ERR_STATE, "kr_batch_submit_text: kr_stream_text_enable first");
   if (nreads == 0 || nreads > s->max_reads) return kr::fail(KR_ERR_ARG, "kr_batch_submit_text: nreads out of range for this stream");
+  if (flags & KR_SEEK) {
+    if (int rc = seek_check(s, flags, false, "kr_batch_submit_text")) return rc;
+  } else if (s->text.seek_only) {
+    return kr::fail(KR_ERR_STATE, "kr_batch_submit_text: this stream's text buffers are kr_stream_seek_enable's: kr_stream_text_enable for the dist text");
+  }
   if (flags & (KR_TAP_ACCS | KR_TAP_HITS)) return kr::fail(KR_ERR_ARG, "kr_batch_submit_text: taps keep record slots, not rows");
   const uint64_t nb = (uint64_t)id_off[nreads] - id_off[0];
   if (nb > s->text.id_cap) return kr::fail(KR_ERR_CAPACITY, "kr_batch_submit_text: the batch's ids exceed max_id_bytes: submit fewer reads per batch");
@@ -1026,7 +1068,7 @@ int kr_batch_submit_text(kr_stream* s, const uint8_t* bases, const uint64_t* off
   t.id_bytes = nb, t.id_sep = id_sep;
   t.req = true, t.ids_on_device = false;
   s->fq.parsed = false;
-  const int rc = submit_batch(s, bases, offsets, nreads, flags | KR_ROWS_ONLY);
+  const int rc = submit_batch(s, bases, offsets, nreads, (flags & KR_SEEK) ? flags : flags | KR_ROWS_ONLY);
   if (rc) t.req = false;
   return rc;
 }
@@ -1062,6 +1104,11 @@ static int submit_batch(kr_stream* s, const uint8_t* bases, const uint64_t* offs
   // every argument is checked before the stream's state is touched: a rejected submit leaves the previous batch as it was
   if (!(flags & KR_BASES_DEVICE) && offsets[nreads] - offsets[0] > s->max_bases)
     return kr::fail(KR_ERR_ARG, "kr_batch_submit: more bases than the stream was created for");
+  if (flags & KR_SEEK) {
+    if (int rc = seek_check(s, flags, false, "kr_batch_submit")) return rc;
+    return seek_submit(s, bases, offsets, nreads, flags);
+  }
+  s->seek.active = false;
   HIP_TRY(hipSetDevice(s->ix->device));
   (void)hipGetLastError(); // a stale error of an earlier, unrelated call on this thread is not this batch's
   if (s->submitted && !s->waited)
@@ -1276,6 +1323,7 @@ int kr_batch_wait(kr_stream* s)
 {
   if (!s || !s->submitted) return kr::fail(KR_ERR_STATE, "kr_batch_wait: nothing submitted");
   if (s->waited) return s->batch_rc ? kr::fail(s->batch_rc, s->batch_msg) : KR_OK;
+  if (s->seek.active) return seek_wait(s);
   HIP_TRY(hipSetDevice(s->ix->device));
   memset(s->h_counters, 0, sizeof(s->h_counters));
   uint32_t extent = 0;
@@ -1384,6 +1432,7 @@ int kr_batch_collect(kr_stream* s, kr_result_view* v)
   kr::clear_error();
   if (!s || !v) return kr::fail(KR_ERR_ARG, "kr_batch_collect: null argument");
   if (!s->submitted) return kr::fail(KR_ERR_STATE, "kr_batch_collect: nothing submitted");
+  if (s->seek.active) return kr::fail(KR_ERR_STATE, "kr_batch_collect: the batch is a seek batch: kr_batch_collect_seek / kr_batch_collect_text");
   HIP_TRY(hipSetDevice(s->ix->device));
   const bool rows_only = (s->flags & KR_ROWS_ONLY) != 0, full = !rows_only;
   const bool pipelined = !s->waited && !s->collected;
@@ -1567,6 +1616,7 @@ int kr_batch_collect_device(kr_stream* s, kr_result_view* v)
 {
   kr::clear_error();
   if (!s || !v) return kr::fail(KR_ERR_ARG, "kr_batch_collect_device: null argument");
+  if (s->submitted && s->seek.active) return kr::fail(KR_ERR_STATE, "kr_batch_collect_device: the batch is a seek batch: kr_batch_collect_seek");
   int rc = kr_batch_wait(s);
   if (rc) return rc;
   fill_view(s, v, true);
@@ -1879,6 +1929,7 @@ int kr_debug_scan_stream(const kr_stream* s, uint32_t* out4)
 int kr_batch_timing(kr_stream* s, kr_timing* t)
 {
   if (!s || !t || !s->waited) return kr::fail(KR_ERR_STATE, "kr_batch_timing: wait for a batch first");
+  if (s->seek.active) return kr::fail(KR_ERR_STATE, "kr_batch_timing: the batch is a seek batch: kr_debug_seek_ms");
   memset(t, 0, sizeof(*t));
   // per phase: the sum over the lanes of the time between the lane's events (with one lane: the kernels' own time;
   // with several, lanes share the chip and the sums exceed ms_total, the span from the first lane's first kernel to the

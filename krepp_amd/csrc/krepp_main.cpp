@@ -56,7 +56,7 @@ static const std::map<std::string, std::string> kAlias = {
   {"-i", "--index-dir"}, {"-q", "--query"}, {"-o", "--output-path"}, {"-t", "--nwk-file"}, {"-k", "--kmer-len"},
   {"-w", "--win-len"}, {"-h", "--num-positions"}, {"-m", "--modulo-lsh"}, {"-r", "--residue-lsh"}, {"-l", "--lineage-file"},
 };
-static const char* kFlags[] = {"--multi", "--filter", "--summarize", "--frac", "--verbose", "--gpu-minimizers", "--tabular", "--gpu-parse"};
+static const char* kFlags[] = {"--multi", "--filter", "--summarize", "--frac", "--verbose", "--gpu-minimizers", "--tabular", "--gpu-parse", "--gpu-seek"};
 
 // options as in the reference's CLI (src/krepp.cpp:516-675); the texts are this build's own
 static void print_help(const std::string& sub)
@@ -100,7 +100,8 @@ static void print_help(const std::string& sub)
   if (sub.empty() || sub == "seek")
     printf("\nkrepp seek -i SKETCH -q READS: distance of every read to the one sketched reference\n"
            "  -i, --sketch-path PATH     sketch file (as written by `krepp sketch`)\n%s"
-           "      --gpu-parse            FASTA/FASTQ records found on the GPU (identical output; plain files, others keep the host reader)\n",
+           "      --gpu-parse            FASTA/FASTQ records found on the GPU (identical output; plain files, others keep the host reader)\n"
+           "      --gpu-seek             seek kernels and report text on the GPU (identical output)\n",
            query_opts);
   if (sub.empty() || sub == "index")
     printf("\nkrepp index -i MAP.tsv -o DIR: build an index (reference ID <tab> FASTA path per line)\n"
@@ -159,6 +160,7 @@ struct Settings {
   kr_params p, pfront; // (the device front end of `place` keeps every chosen leaf: the place options act in the back end)
   std::string query, index_arg, invocation;
   bool gpu_parse = false; // --gpu-parse asked for (Run::open_input decides whether the file qualifies)
+  bool gpu_seek = false;  // seek --gpu-seek: batches flagged KR_SEEK, the report as the device's text
   int ngpus = 1, dev0 = 0, wpg = 2, nworkers = 2, write_threads = 4;
   uint32_t max_reads = 0;
   uint64_t batch_bases = 0, max_bases = 0, chunk_bytes = 0, max_records = 0, text_bytes = 0;
@@ -201,6 +203,8 @@ static Settings resolve_settings(const Args& a, const std::string& invocation, i
   s.ngpus = std::max(1, a.has("--gpus") ? atoi(a.get("--gpus").c_str()) : 1);
   s.dev0 = a.has("--device") ? atoi(a.get("--device").c_str()) : 0;
   s.gpu_parse = a.flag.count("--gpu-parse") && a.flag.at("--gpu-parse");
+  s.gpu_seek = a.flag.count("--gpu-seek") && a.flag.at("--gpu-seek");
+  if (s.gpu_seek && !seek) error_exit("--gpu-seek is an option of `seek`");
 
   // reads per batch: the kernels' efficiency grows with the batch (launch tails amortise, likelihood problems repeat): 262,144 reads
   // for `dist` on a large input, 65,536 for `place` / `seek` (more state per read) and for inputs of a few batches anyway
@@ -430,6 +434,7 @@ struct Run {
   double twcount = 0;
 
   std::atomic<uint64_t> nreads_dev{0}; // records found on the device so far, in the output's order (advanced in a chunk's turn)
+  std::atomic<uint64_t> nreads_seek{0}; // seek --gpu-seek: reads whose rows the seek kernels wrote ([timing] only)
   uint64_t nbatches = 0, nreads_total = 0; // the reader's
   // the writer's.  place --summarize: counts per placement-tree node, summed in input order; placements of a 512-read group that
   // straddles two jobs wait in `carry` (the groups are the reference's batches)
@@ -654,6 +659,7 @@ void Worker::loop()
     else
       fprintf(stderr, "[krepp_amd] report text on the host: %s\n", kr_last_error());
   }
+  if (s.gpu_seek && kr_stream_seek_enable(st, s.text_bytes, std::max<uint64_t>(1ull << 20, (uint64_t)s.max_reads * 64))) return r.worker_ready(kr_last_error());
   if (r.gpu_parse && kr_stream_fastq_enable(st, s.chunk_bytes)) return r.worker_ready(kr_last_error());
   const double t_ready = r.at();
   r.worker_ready(nullptr);
@@ -758,6 +764,24 @@ int Worker::run_batch(size_t lo, size_t hi)
   bool on_device = false;
   auto t_dev = Clock::now();
   int rc;
+  if (s.gpu_seek) { // the seek kernels: the report comes back as bytes, in the job's text for the writer
+    std::vector<uint32_t> id_off(n + 1);
+    for (size_t i = 0; i < n; ++i) id_off[i] = (uint32_t)(nm[i] - j->blob);
+    id_off[n] = hi < j->n ? (uint32_t)(nm[n] - j->blob) : (uint32_t)j->blob_bytes;
+    rc = kr_batch_submit_text(st, j->bases + j->offsets[lo], offs.data(), (uint32_t)n, KR_BASES_HOST | KR_SEEK, j->blob, id_off.data(), 1);
+    if (!rc) rc = kr_batch_collect_text(st, &dtext, &dlen);
+    r.ns_dev += since(t_dev);
+    if (rc == KR_ERR_CAPACITY && n > 1) {
+      piece = std::min(piece, (n + 1) / 2);
+      streak = 0;
+      return run_halves(lo, hi);
+    }
+    if (rc) return rc;
+    text.append(dtext, dlen);
+    r.nreads_seek += n;
+    succeeded();
+    return 0;
+  }
   if (text_on) {
     std::vector<uint32_t> id_off(n + 1);
     for (size_t i = 0; i < n; ++i) id_off[i] = (uint32_t)(nm[i] - j->blob);
@@ -829,7 +853,8 @@ int Worker::run_chunk()
   double tw_job = 0;
   bool fell = false;
   // (KR_TILE_DEVICE: a long record stays with the device, tiled there)
-  const uint32_t flags = s.rows_flags(text_on) | (s.seek ? 0u : KR_TILE_DEVICE);
+  // (--gpu-seek: long records too, split by the seek units)
+  const uint32_t flags = s.gpu_seek ? (KR_SEEK | KR_TILE_DEVICE) : s.rows_flags(text_on) | (s.seek ? 0u : KR_TILE_DEVICE);
   while (pos < j->raw_len) {
     const uint8_t* raw = j->raw + pos;
     kr_fastq_parse fp;
@@ -843,10 +868,15 @@ int Worker::run_chunk()
       uint64_t len = 0, dlen = 0;
       const char* dtext = nullptr;
       bool on_device = false;
-      if (!s.place) rc = collect(&rv, &dtext, &dlen, &on_device); // (place: kr_place_stream_parsed waits for the batch)
+      if (s.gpu_seek)
+        rc = kr_batch_collect_text(st, &dtext, &dlen);
+      else if (!s.place)
+        rc = collect(&rv, &dtext, &dlen, &on_device); // (place: kr_place_stream_parsed waits for the batch)
       r.ns_dev += since(t_dev);
       auto t_fmt = Clock::now();
-      if (!rc && on_device) {
+      if (s.gpu_seek) {
+        if (!rc) text.append(dtext, dlen);
+      } else if (!rc && on_device) {
         ++r.nb_dev_text;
         emit(dtext, dlen, false);
       } else if (!rc && s.summarize && !s.place) {
@@ -893,6 +923,7 @@ int Worker::run_chunk()
   j->first_read = r.nreads_dev, j->n = (size_t)nr_job;
   for (kr_placement& x : pls) x.read = (uint32_t)(j->first_read + x.read);
   r.nreads_dev += nr_job;
+  if (s.gpu_seek) r.nreads_seek += nr_job;
   if (fell) r.order.stop_at(*j, j->raw_off + pos);
   return 0;
 }
@@ -1058,6 +1089,7 @@ int Run::finish()
   if (s.timing)
     fprintf(stderr, "[timing] parse %.3f s, job hand-over (incl. waiting for queue space) %.3f s, device %.3f s, format %.3f s, write %.3f s; of the elapsed time, until the last worker had its stream and page-locked buffers: %.3f s (the reader parses meanwhile)\n",
             ns_parse / 1e9, ns_job / 1e9, ns_dev / 1e9, ns_fmt / 1e9, ns_write / 1e9, std::chrono::duration<double>(t_loop - t_init).count());
+  if (s.timing && s.gpu_seek) fprintf(stderr, "[timing] gpu-seek: %llu reads through the seek kernels\n", (unsigned long long)nreads_seek.load());
   if (s.timing && gpu_parse)
     fprintf(stderr, "[timing] gpu-parse: %llu %s records found on the device\n", (unsigned long long)nreads_dev.load(), fasta_parse ? "FASTA" : "FASTQ");
   if (s.timing && s.plain_dist()) // (a batch split at capacity counts once per piece)
