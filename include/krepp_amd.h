@@ -477,7 +477,8 @@ KR_API int kr_batch_timing(kr_stream*, kr_timing* out);
 /* default min(8, cores/2); 0 = off): a batch is then one chunk of about 2 * min_bases bytes of input. */
 /* Block-gzipped files (BGZF: independent members with a "BC" extra field) are inflated member by       */
 /* member on the same threads (CRC-checked; a damaged member is KR_ERR_IO); ordinary gzip is one stream  */
-/* and is inflated by zlib in the calling thread.                                                        */
+/* and is inflated by zlib in the calling thread.  (The members can be inflated on the device instead:  */
+/* kr_batch_submit_bgzf, below.)                                                                         */
 /* Records, names and order are those of the sequential reader in every case.                          */
 typedef struct kr_fastx kr_fastx;
 typedef struct kr_fastx_batch {
@@ -624,6 +625,47 @@ KR_API int kr_debug_fastq_parse_ms(kr_stream*, float* ms);
 KR_API int kr_batch_submit_fasta(kr_stream*, const uint8_t* raw, uint64_t nbytes, uint32_t flags, uint32_t closed, kr_fastq_parse* out);
 KR_API uint64_t kr_fasta_chunk_cut(const uint8_t* buf, uint64_t n);
 KR_API uint64_t kr_fastq_chunk_cut(const uint8_t* buf, uint64_t n);
+
+/* ---- block-gzipped bytes inflated on the device (csrc/kr_inflate.h, csrc/kr_dev_bgzf.inc; docs/design/08 "BGZF on the device") ----
+ * A BGZF file is a run of independent gzip members of at most 64 KB of inflated bytes; each announces its compressed size ("BC"
+ * extra field) and its inflated size (ISIZE).  kr_batch_submit_bgzf takes WHOLE members, inflates them on the device -- one wave
+ * per member, CRC-32 checked there -- into the buffer the record finders read, and is from there on kr_batch_submit_fastq
+ * (fasta == 0) or kr_batch_submit_fasta (fasta != 0) for those bytes.
+ *   kr_stream_bgzf_enable   once per stream, after kr_stream_fastq_enable (else KR_ERR_STATE; twice: KR_ERR_STATE): device buffers for
+ *                           up to max_comp_bytes (< 4 GB) of compressed bytes, a table of max_comp_bytes / 28 + 1 members, their
+ *                           statuses and two 64 KB scratch windows
+ *   kr_batch_submit_bgzf    `comp` is page-locked and holds whole members only, U inflated bytes in all.  The chunk is bytes
+ *                           [skip, skip + nbytes) of them: skip lies inside the first member, skip + nbytes <= U, nbytes <=
+ *                           max_raw_bytes, and only the first and the last member may reach outside the chunk (KR_ERR_ARG).
+ *                           raw_out (page-locked, [nbytes], may be NULL) receives the chunk's bytes; `out`, kr_batch_fastq_names
+ *                           (positions in raw_out), kr_debug_fastq_batch, kr_place_stream_parsed(raw = raw_out) and the flags are
+ *                           those of a raw-bytes submit of raw_out[0 .. nbytes).  After KR_FASTQ_CAPACITY the caller goes on
+ *                           with kr_batch_submit_fastq(raw_out + consumed, ...).  KR_ERR_FORMAT: bytes that are no whole BGZF
+ *                           member, ISIZE above 65,536, a member the decoder rejects, a wrong CRC or length -- the message names the
+ *                           member's offset in `comp` and the rule; nothing is queued and the stream serves the next submit.
+ *   kr_debug_bgzf_inflate   (tests) the inflate kernel alone: all U bytes of comp's members into out[0 .. cap), U <= max_raw_bytes
+ *   kr_debug_bgzf_inflate_host  the same members through the decoder's host instantiation: no device, the same codes and messages
+ *   kr_debug_bgzf_ms        (measurements) device time of the inflate kernel of the stream's last chunk; as kr_debug_fastq_parse_ms
+ * No device:
+ *   kr_bgzf_member_size     the size of the BGZF member that starts at h[0 .. avail), 0 when these bytes are not one
+ *   kr_bgzf_walk            the whole, well-formed members at the front of buf whose inflated sizes stay within max_inflated (always
+ *                           one when one is complete): their number, compressed and inflated bytes
+ *   kr_bgzf_chunk_cut       the last record start of the chunk that is bytes [skip, U) of buf's members, as the member's offset in buf
+ *                           and the byte inside it (the trailing members are inflated with zlib, the last two first, then up to
+ *                           1 MiB, and cut by kr_fastq_chunk_cut / kr_fasta_chunk_cut); returns the cut's position in the chunk, 0
+ *                           when there is none
+ *   kr_fastx_open_at_bgzf   the host reader from byte uoff of the member at file offset member_off, a record start (kr_fastx_open_at
+ *                           for a block-gzipped file); bytes at member_off that are no BGZF member are read as ordinary gzip */
+KR_API int kr_stream_bgzf_enable(kr_stream*, uint64_t max_comp_bytes);
+KR_API int kr_batch_submit_bgzf(kr_stream*, const uint8_t* comp, uint64_t ncomp, uint32_t skip, uint64_t nbytes, uint8_t* raw_out,
+                                uint32_t flags, uint32_t fasta, uint32_t at_eof_or_closed, kr_fastq_parse* out);
+KR_API int kr_debug_bgzf_inflate(kr_stream*, const uint8_t* comp, uint64_t ncomp, uint8_t* out, uint64_t cap, uint64_t* len);
+KR_API int kr_debug_bgzf_inflate_host(const uint8_t* comp, uint64_t ncomp, uint8_t* out, uint64_t cap, uint64_t* len);
+KR_API int kr_debug_bgzf_ms(kr_stream*, float* ms);
+KR_API uint32_t kr_bgzf_member_size(const uint8_t* h, uint64_t avail);
+KR_API int kr_bgzf_walk(const uint8_t* buf, uint64_t n, uint64_t max_inflated, uint32_t* nmembers, uint64_t* comp_bytes, uint64_t* inflated);
+KR_API uint64_t kr_bgzf_chunk_cut(const uint8_t* buf, uint64_t comp_bytes, uint32_t skip, uint32_t fasta, uint64_t* member_off, uint32_t* uoff);
+KR_API int kr_fastx_open_at_bgzf(const char* path, uint64_t member_off, uint32_t uoff, kr_fastx** out);
 
 /* ---- `seek` on kernels of its own (csrc/kr_dev_seek.inc; docs/design/13_seek.md; INTEGRATION.md "A seek batch") ----
  * SBatch::seek_sequences (src/seek.cpp:22-126) on a SKETCH index (kr_host_sketch_load): per k-mer and strand the minimum Hamming

@@ -130,6 +130,8 @@ EXPORTS = [
     "kr_build_index", "kr_minimizers_cpu", "kr_minimizers_device", "kr_minimizers_free", "kr_last_error", "kr_version",
     "kr_sdust_cpu", "kr_sdust_free",
     "kr_stream_seek_enable", "kr_batch_collect_seek", "kr_debug_seek_layout", "kr_debug_seek_ms",
+    "kr_stream_bgzf_enable", "kr_batch_submit_bgzf", "kr_debug_bgzf_inflate", "kr_debug_bgzf_inflate_host", "kr_debug_bgzf_ms",
+    "kr_bgzf_member_size", "kr_bgzf_walk", "kr_bgzf_chunk_cut", "kr_fastx_open_at_bgzf",
 ]
 
 # kr_debug_acc_paths: the accumulate kernel's path witnesses, in the order of CounterSlot (kr_dev_common.inc)
@@ -250,6 +252,17 @@ def load():
     lib.kr_batch_fastq_names.argtypes = [vp, C.POINTER(u64p), C.POINTER(u32p)]
     lib.kr_debug_fastq_batch.argtypes = [vp, vp, vp]
     lib.kr_debug_fastq_parse_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    lib.kr_stream_bgzf_enable.argtypes = [vp, C.c_uint64]
+    lib.kr_batch_submit_bgzf.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint64, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(KrFastqParse)]
+    lib.kr_debug_bgzf_inflate.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+    lib.kr_debug_bgzf_inflate_host.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+    lib.kr_debug_bgzf_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    lib.kr_bgzf_member_size.argtypes = [vp, C.c_uint64]
+    lib.kr_bgzf_member_size.restype = C.c_uint32
+    lib.kr_bgzf_walk.argtypes = [vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.kr_bgzf_chunk_cut.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
+    lib.kr_bgzf_chunk_cut.restype = C.c_uint64
+    lib.kr_fastx_open_at_bgzf.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, C.POINTER(vp)]
     lib.kr_debug_tile_layout.argtypes = [vp, u32p, u32p, vp, vp, vp, vp, vp]
     lib.kr_stream_seek_enable.argtypes = [vp, C.c_uint64, C.c_uint64]
     lib.kr_batch_collect_seek.argtypes = [vp, C.POINTER(KrSeekView)]
@@ -695,6 +708,49 @@ class Stream:
         self._flags = flags | KR_BASES_DEVICE | (KR_ROWS_ONLY if text else 0)
         return {f: getattr(out, f) for f in ("consumed", "nbases", "id_bytes", "newlines", "nreads", "status", "rejected", "at_eof")}
 
+    def bgzf_enable(self, max_comp_bytes):
+        """kr_stream_bgzf_enable (after fastq_enable): this stream can be given batches as whole BGZF members (csrc/kr_dev_bgzf.inc)"""
+        check(self.lib.kr_stream_bgzf_enable(self.h, int(max_comp_bytes)))
+
+    def submit_bgzf(self, comp, skip, nbytes, flags=0, fasta=False, at_eof=1, want_raw=True):
+        """kr_batch_submit_bgzf on a page-locked copy of the members `comp`: (summary as a dict, the chunk's inflated bytes or None).
+        The chunk is bytes [skip, skip + nbytes) of the members' inflated bytes; names are cut out of the bytes that came back."""
+        comp = bytes(comp)
+        n = len(comp)
+        need = max(n, 1) + max(int(nbytes), 1)
+        if getattr(self, "_pinned_cap", 0) < need:
+            if getattr(self, "_pinned", None):
+                self.lib.kr_host_free(self._pinned)
+            self._pinned = self.lib.kr_host_alloc(need)
+            if not self._pinned:
+                raise MemoryError("kr_host_alloc failed")
+            self._pinned_cap = need
+        C.memmove(self._pinned, comp, n)
+        raw_out = self._pinned + max(n, 1) if want_raw else None
+        self._raw_out = raw_out
+        out = KrFastqParse()
+        check(self.lib.kr_batch_submit_bgzf(self.h, self._pinned, n, int(skip), int(nbytes), raw_out, flags, 1 if fasta else 0, at_eof, C.byref(out)))
+        self._raw = C.string_at(raw_out, int(nbytes)) if want_raw else b""
+        self._fq_nreads = out.nreads
+        text = getattr(self, "_text_on", False) and not (flags & (KR_TAP_ACCS | KR_TAP_HITS))
+        self._flags = flags | KR_BASES_DEVICE | (KR_ROWS_ONLY if text else 0)
+        return {f: getattr(out, f) for f in ("consumed", "nbases", "id_bytes", "newlines", "nreads", "status", "rejected", "at_eof")}, (self._raw if want_raw else None)
+
+    def bgzf_inflate(self, comp, cap=None):
+        """(tests) kr_debug_bgzf_inflate: the inflate kernel alone on whole members, all their bytes"""
+        comp = bytes(comp)
+        cap = (len(comp) // 28 + 1) * 65536 if cap is None else int(cap)
+        out = np.zeros(max(1, cap), np.uint8)
+        n = C.c_uint64(0)
+        check(self.lib.kr_debug_bgzf_inflate(self.h, comp, len(comp), out.ctypes.data, cap, C.byref(n)))
+        return out[: n.value].tobytes()
+
+    def bgzf_ms(self):
+        """(measurements) kr_debug_bgzf_ms: device time of the last chunk's inflate kernel, -1 before the first measured one"""
+        ms = C.c_float(0)
+        check(self.lib.kr_debug_bgzf_ms(self.h, C.byref(ms)))
+        return float(ms.value)
+
     def fastq_names(self):
         """kr_batch_fastq_names: the accepted records' names, cut out of the bytes given to submit_fastq"""
         pos, ln = u64p(), u32p()
@@ -863,6 +919,38 @@ def fastq_chunk_cut(buf):
     return int(load().kr_fastq_chunk_cut(buf, len(buf)))
 
 
+def bgzf_inflate_host(comp, cap=None):
+    """kr_debug_bgzf_inflate_host: whole BGZF members through the decoder's host instantiation (no device), all their bytes"""
+    comp = bytes(comp)
+    cap = (len(comp) // 28 + 1) * 65536 if cap is None else int(cap)
+    out = np.zeros(max(1, cap), np.uint8)
+    n = C.c_uint64(0)
+    check(load().kr_debug_bgzf_inflate_host(comp, len(comp), out.ctypes.data, cap, C.byref(n)))
+    return out[: n.value].tobytes()
+
+
+def bgzf_member_size(buf):
+    """kr_bgzf_member_size: the size of the BGZF member that `buf` starts with, 0 when it does not start with one"""
+    buf = bytes(buf)
+    return int(load().kr_bgzf_member_size(buf, len(buf)))
+
+
+def bgzf_walk(buf, max_inflated):
+    """kr_bgzf_walk: (members, compressed bytes, inflated bytes) of the whole members at the front of buf within max_inflated"""
+    buf = bytes(buf)
+    k, c, u = C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
+    check(load().kr_bgzf_walk(buf, len(buf), int(max_inflated), C.byref(k), C.byref(c), C.byref(u)))
+    return int(k.value), int(c.value), int(u.value)
+
+
+def bgzf_chunk_cut(buf, skip=0, fasta=False):
+    """kr_bgzf_chunk_cut on the whole members `buf`: (cut's position in the chunk or 0, member offset in buf, byte inside the member)"""
+    buf = bytes(buf)
+    m, u = C.c_uint64(0), C.c_uint32(0)
+    cut = load().kr_bgzf_chunk_cut(buf, len(buf), int(skip), 1 if fasta else 0, C.byref(m), C.byref(u))
+    return int(cut), int(m.value), int(u.value)
+
+
 def tile_shape(length, k):
     """(tests) kr_debug_tile_shape: (k-mer positions, tiles of 128 positions, bases in a tiled batch) of a sequence of `length` bases"""
     a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
@@ -898,16 +986,19 @@ def colour_classes(pse, node_kind):
     return cls, out, lists[: nl.value]
 
 
-def read_fastx(path, min_bases=76800, stats=None, detach=0, offset=None):
+def read_fastx(path, min_bases=76800, stats=None, detach=0, offset=None, bgzf_at=None):
     """All records of a FASTA/FASTQ(.gz) file via the library's reader: (names, bases, offsets).
     detach = K > 0: every batch is taken over (kr_fastx_detach), read only when K further batches have been parsed, then handed
     back (kr_fastx_release) -- the way the CLI's workers hold batches in flight.
-    offset: the sequential reader from that record start of a plain file on (kr_fastx_open_at)."""
+    offset: the sequential reader from that record start of a plain file on (kr_fastx_open_at).
+    bgzf_at = (member_off, uoff): the same for a block-gzipped file (kr_fastx_open_at_bgzf)."""
     lib = load()
     lib.kr_fastx_parallel_chunks.restype = C.c_uint64
     lib.kr_fastx_parallel_chunks.argtypes = [C.c_void_p]
     h = C.c_void_p()
-    if offset is None:
+    if bgzf_at is not None:
+        check(lib.kr_fastx_open_at_bgzf(os.fsencode(str(path)), int(bgzf_at[0]), int(bgzf_at[1]), C.byref(h)))
+    elif offset is None:
         check(lib.kr_fastx_open(os.fsencode(str(path)), C.byref(h)))
     else:
         check(lib.kr_fastx_open_at(os.fsencode(str(path)), int(offset), C.byref(h)))
@@ -1135,18 +1226,26 @@ class Placer:
         self.lib.kr_free(pls)
         return text, pl
 
-    def place_parsed(self, raw, fasta=False, flags=0, want_placements=True, at_eof=1):
+    def place_parsed(self, raw, fasta=False, flags=0, want_placements=True, at_eof=1, bgzf=None):
         """One batch given as raw FASTQ (fasta=True: FASTA) bytes: kr_batch_submit_fastq / _fasta with KR_TAP_ACCS | flags on a
         page-locked copy of `raw`, then kr_place_stream_parsed.  The first call runs kr_stream_fastq_enable for chunks of up to
         max(len(raw), 1 MB) bytes.  Returns (text, placements, summary): the accepted prefix of the chunk is placed, and
-        summary["consumed"] says where the next submit starts."""
+        summary["consumed"] says where the next submit starts.
+        bgzf = (skip, nbytes): `raw` holds whole BGZF members instead and the batch is kr_batch_submit_bgzf's chunk of them."""
         if not getattr(self, "_fq_on", False):
-            self.st.fastq_enable(max(len(raw), 1 << 20))
+            self.st.fastq_enable(max(len(raw), bgzf[1] if bgzf else 0, 1 << 20))
+            if bgzf:
+                self.st.bgzf_enable(max(len(raw), 1 << 20))
             self._fq_on = True
-        submit = self.st.submit_fasta if fasta else self.st.submit_fastq
-        summ = submit(raw, KR_TAP_ACCS | flags, at_eof)
+        if bgzf:
+            summ, _ = self.st.submit_bgzf(raw, bgzf[0], bgzf[1], KR_TAP_ACCS | flags, fasta, at_eof)
+            raw_ptr = self.st._raw_out
+        else:
+            submit = self.st.submit_fasta if fasta else self.st.submit_fastq
+            summ = submit(raw, KR_TAP_ACCS | flags, at_eof)
+            raw_ptr = self.st._pinned
         txt, ln, pls, npl = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
-        check(self.lib.kr_place_stream_parsed(self.hx.h, self.dx.h, self.pt, self.st.h, self.st._pinned, C.byref(self.popts), int(self.tabular),
+        check(self.lib.kr_place_stream_parsed(self.hx.h, self.dx.h, self.pt, self.st.h, raw_ptr, C.byref(self.popts), int(self.tabular),
                                               C.byref(self.prev), C.byref(txt), C.byref(ln), C.byref(pls) if want_placements else None,
                                               C.byref(npl) if want_placements else None))
         text = C.string_at(txt, ln.value).decode()

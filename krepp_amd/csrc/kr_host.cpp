@@ -11,6 +11,7 @@
 //   FASTX records / batching         src/kseq.h:177-219, src/rqseq.cpp:180-197
 //   report text                      src/query.cpp:152-196, src/query.hpp:210
 #include "kr_common.h"
+#include "kr_inflate.h"
 
 #include <sched.h>
 
@@ -1042,19 +1043,8 @@ struct BgzfSource {
   std::unique_ptr<Run> cur;
   size_t cur_pos = 0;
 
-  // size of the member at `off` (0: not a BGZF member / end of file)
-  static uint32_t member_size(const unsigned char* h, size_t avail)
-  {
-    if (avail < 18 || h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || !(h[3] & 4)) return 0;
-    const uint32_t xlen = h[10] | (h[11] << 8);
-    if (avail < 12 + (size_t)xlen) return 0;
-    for (uint32_t p = 12; p + 4 <= 12 + xlen;) {
-      const uint32_t slen = h[p + 2] | (h[p + 3] << 8);
-      if (h[p] == 'B' && h[p + 1] == 'C' && slen == 2 && p + 6 <= 12 + xlen) return (uint32_t)(h[p + 4] | (h[p + 5] << 8)) + 1u;
-      p += 4 + slen;
-    }
-    return 0;
-  }
+  // size of the member at `off` (0: not a BGZF member / end of file): kr_bgzf_member_size is the same function
+  static uint32_t member_size(const unsigned char* h, size_t avail) { return kr::bgzf_member_size(h, avail); }
   static bool is_bgzf(int fd)
   {
     unsigned char h[64];
@@ -1548,6 +1538,148 @@ uint64_t kr_fastq_chunk_cut(const uint8_t* buf, uint64_t n)
     nl = l1;
   }
   return cut;
+}
+
+// ---- block-gzipped bytes for the device's inflate (kr_batch_submit_bgzf): the walk over members, the chunk cut, the hand-over -------
+uint32_t kr_bgzf_member_size(const uint8_t* h, uint64_t avail) { return h ? kr::bgzf_member_size(h, avail) : 0u; }
+
+// The whole members at the front of buf whose inflated sizes, summed, stay within max_inflated -- at least one when one is complete.
+// The walk ends without an error at bytes that are no whole well-formed member (the caller sees it: comp_bytes < n).
+int kr_bgzf_walk(const uint8_t* buf, uint64_t n, uint64_t max_inflated, uint32_t* nmembers, uint64_t* comp_bytes, uint64_t* inflated)
+{
+  kr::clear_error();
+  if (!buf || !nmembers || !comp_bytes || !inflated) return kr::fail(KR_ERR_ARG, "kr_bgzf_walk: null argument");
+  uint32_t k = 0;
+  uint64_t off = 0, total = 0;
+  while (off < n) {
+    kr::BgzfMember m;
+    uint32_t ms = 0;
+    if (kr::bgzf_member_at(buf, n, off, &m, &ms)) break;
+    if (k && total + m.isize > max_inflated) break;
+    total += m.isize, off += ms, ++k;
+  }
+  *nmembers = k, *comp_bytes = off, *inflated = total;
+  return KR_OK;
+}
+
+// Whole members through the decoder's host instantiation (kr_inflate.h), CRC-checked: what kr_debug_bgzf_inflate does on the device
+int kr_debug_bgzf_inflate_host(const uint8_t* comp, uint64_t ncomp, uint8_t* out, uint64_t cap, uint64_t* len)
+{
+  kr::clear_error();
+  if (!comp || !out || !len) return kr::fail(KR_ERR_ARG, "bgzf: null argument");
+  *len = 0;
+  uint64_t off = 0, total = 0;
+  std::unique_ptr<kr::InfTables> T(new kr::InfTables());
+  while (off < ncomp) {
+    kr::BgzfMember m;
+    uint32_t ms = 0, pos = 0;
+    if (const char* why = kr::bgzf_member_at(comp, ncomp, off, &m, &ms))
+      return kr::fail(KR_ERR_FORMAT, "bgzf: BGZF member at offset " + std::to_string(off) + ": " + why);
+    if (m.isize > cap - total) return kr::fail(KR_ERR_ARG, "bgzf: the members inflate to more bytes than the buffer holds");
+    kr::InfSerial L;
+    uint32_t rule = kr::inflate_member(comp + m.in_off, m.in_size, out + total, m.isize, *T, L, &pos);
+    if (!rule && ~kr::crc_raw(kr::crc_host_table(), 0xFFFFFFFFu, out + total, m.isize) != m.crc) rule = kr::INF_CRC;
+    if (rule) return kr::fail(KR_ERR_FORMAT, kr::bgzf_member_message("bgzf", off, rule, pos));
+    total += m.isize, off += ms;
+  }
+  *len = total;
+  return KR_OK;
+}
+
+// The last record start of the chunk that is bytes [skip, U) of the members' inflated bytes, as (member, byte inside it): the
+// trailing members are inflated with zlib -- the last two, then as many as hold 1 MiB -- and cut by kr_fastq_chunk_cut /
+// kr_fasta_chunk_cut.  Returns the cut's position in the chunk, 0 when there is none (the chunk then goes out whole).
+uint64_t kr_bgzf_chunk_cut(const uint8_t* buf, uint64_t comp_bytes, uint32_t skip, uint32_t fasta, uint64_t* member_off, uint32_t* uoff)
+{
+  if (!buf || !member_off || !uoff) return 0;
+  *member_off = comp_bytes, *uoff = 0;
+  std::vector<std::array<uint64_t, 2>> mem; // offset in buf, inflated bytes in front
+  std::vector<kr::BgzfMember> ent;
+  uint64_t off = 0, total = 0;
+  while (off < comp_bytes) {
+    kr::BgzfMember m;
+    uint32_t ms = 0;
+    if (kr::bgzf_member_at(buf, comp_bytes, off, &m, &ms)) return 0;
+    mem.push_back({off, total}), ent.push_back(m);
+    total += m.isize, off += ms;
+  }
+  if (mem.empty() || skip >= total) return 0;
+  z_stream zs;
+  memset(&zs, 0, sizeof(zs));
+  if (inflateInit2(&zs, -15) != Z_OK) return 0;
+  const size_t k = mem.size();
+  std::vector<uint8_t> T;
+  uint64_t cut = 0;
+  size_t j = k >= 2 ? k - 2 : 0;
+  for (int round = 0; round < 2 && !cut; ++round) {
+    if (round == 1) {
+      if (j == 0) break;
+      while (j > 0 && total - mem[j - 1][1] <= (1u << 20)) --j;
+    }
+    const uint64_t t0 = std::max<uint64_t>(mem[j][1], skip); // the span [t0, total) of the inflated bytes
+    T.resize((size_t)(total - mem[j][1]) + 1);
+    bool ok = true;
+    for (size_t i = j; i < k && ok; ++i) {
+      ok = inflateReset(&zs) == Z_OK;
+      zs.next_in = const_cast<unsigned char*>(buf + ent[i].in_off), zs.avail_in = ent[i].in_size;
+      zs.next_out = T.data() + (mem[i][1] - mem[j][1]), zs.avail_out = ent[i].isize;
+      ok = ok && inflate(&zs, Z_FINISH) == Z_STREAM_END && zs.avail_out == 0;
+    }
+    if (!ok) break; // (a damaged member: the submit reports it)
+    const uint8_t* t = T.data() + (t0 - mem[j][1]);
+    const uint64_t c = fasta ? kr_fasta_chunk_cut(t, total - t0) : kr_fastq_chunk_cut(t, total - t0);
+    if (c) cut = t0 + c;
+  }
+  inflateEnd(&zs);
+  if (!cut) return 0;
+  size_t m = k - 1;
+  while (mem[m][1] > cut) --m; // (the last member that starts at or in front of the cut; empty members in between are passed over)
+  *member_off = mem[m][0], *uoff = (uint32_t)(cut - mem[m][1]);
+  return cut - skip;
+}
+
+// The host reader from byte uoff of the member at file offset member_off, a record start: a BgzfSource started at that member with
+// the first uoff inflated bytes discarded, in kseq's "look for the next marker" state (as kr_fastx_open_at).  Bytes at member_off that
+// are no BGZF member are zlib's from there on (BgzfSource::issue); uoff must be 0 then.
+int kr_fastx_open_at_bgzf(const char* path, uint64_t member_off, uint32_t uoff, kr_fastx** out)
+{
+  kr::clear_error();
+  if (!path || !out) return kr::fail(KR_ERR_ARG, "kr_fastx_open_at_bgzf: null argument");
+  struct stat sb;
+  if (stat(path, &sb) != 0) return kr::fail(KR_ERR_IO, std::string("Failed to open the file at ") + path);
+  if (!S_ISREG(sb.st_mode)) return kr::fail(KR_ERR_UNSUPPORTED, std::string("kr_fastx_open_at_bgzf: not a regular file: ") + path);
+  if (member_off > (uint64_t)sb.st_size) return kr::fail(KR_ERR_ARG, "kr_fastx_open_at_bgzf: offset past the end of the file");
+  if (uoff >= kr::kBgzfMaxIsize) return kr::fail(KR_ERR_ARG, "kr_fastx_open_at_bgzf: a member holds at most 65,536 bytes");
+  int fd = open(path, O_RDONLY);
+  gzFile f = fd >= 0 ? gzopen(path, "rb") : nullptr; // (closed with the reader; leave_bgzf replaces it)
+  if (!f) {
+    if (fd >= 0) close(fd);
+    return kr::fail(KR_ERR_IO, std::string("Failed to open the file at ") + path);
+  }
+  const char* et = getenv("KR_FASTX_THREADS");
+  const unsigned nt = std::max(1u, et ? (unsigned)atoi(et) : std::min(12u, std::max(1u, kr::usable_cpus() * 3 / 4)));
+  kr_fastx* r = new kr_fastx();
+  r->f = f;
+  r->path = path;
+  r->buf.resize(4 << 20);
+  r->bgzf.reset(new BgzfSource());
+  r->bgzf->fd = fd;
+  r->bgzf->size = (uint64_t)sb.st_size;
+  r->bgzf->next_off = member_off;
+  r->bgzf->depth = 2 * nt;
+  r->bgzf->st.parsed_mode.store(false); // bytes, not records: the first record may start anywhere in a run
+  for (unsigned t = 0; t < nt; ++t) r->bgzf->threads.emplace_back([p = r->bgzf.get()] { p->work(); });
+  for (uint32_t left = uoff; left;) {
+    const int n = r->bgzf->read(r->buf.data(), left);
+    if (n <= 0) {
+      kr_fastx_close(r);
+      return kr::fail(KR_ERR_FORMAT, std::string("kr_fastx_open_at_bgzf: no ") + std::to_string(uoff) + " inflated bytes at offset " +
+                                         std::to_string(member_off) + " of " + path);
+    }
+    left -= (uint32_t)n;
+  }
+  *out = r;
+  return KR_OK;
 }
 
 // QSeq::read_next_batch (src/rqseq.cpp:180-197): keep reading until the batch holds

@@ -3,14 +3,15 @@
 // prefix is queued exactly as kr_batch_submit_fastq queues its own (fq_begin / fq_finish, kr_host_fastq.inc), and
 // kr_batch_fastq_names / kr_debug_fastq_batch serve it unchanged.  (kr_fasta_chunk_cut needs no device: kr_host.cpp.)
 
-extern "C" {
+namespace {
 
-int kr_batch_submit_fasta(kr_stream* s, const uint8_t* raw, uint64_t nbytes, uint32_t flags, uint32_t closed, kr_fastq_parse* out)
+// kr_batch_submit_fasta; with hooks: the same for bytes that a kernel writes into d_raw (kr_batch_submit_bgzf)
+int submit_fasta(kr_stream* s, const char* fn, const uint8_t* raw, uint64_t nbytes, uint32_t flags, uint32_t closed, kr_fastq_parse* out,
+                 const FqHooks* hooks)
 {
-  kr::clear_error();
   FaIO io;
   bool text = false;
-  int rc = fq_begin(s, "kr_batch_submit_fasta", raw, nbytes, flags, closed, out, io.q, text);
+  int rc = fq_begin(s, fn, raw, nbytes, flags, closed, out, io.q, text, hooks);
   if (rc || nbytes == 0) return rc;
   kr_stream::Fastq& f = s->fq;
   if (!f.fa_on) { // what only FASTA needs, on the stream's first FASTA chunk (after a failed attempt: the buffers still missing)
@@ -36,7 +37,17 @@ int kr_batch_submit_fasta(kr_stream* s, const uint8_t* raw, uint64_t nbytes, uin
   hipLaunchKernelGGL(kr_fq_bscan_kernel, dim3(1), dim3(1024), 0, st, io.q);
   hipLaunchKernelGGL(kr_fq_off_kernel, dim3(bgrid), dim3(256), 0, st, io.q);
   hipLaunchKernelGGL(kr_fa_copy_kernel, dim3(std::max(tgrid, std::min(rgrid, 1024u))), dim3(256), 0, st, io);
-  return fq_finish(s, flags, closed, text, out);
+  return fq_finish(s, flags, closed, text, out, hooks);
+}
+
+} // namespace
+
+extern "C" {
+
+int kr_batch_submit_fasta(kr_stream* s, const uint8_t* raw, uint64_t nbytes, uint32_t flags, uint32_t closed, kr_fastq_parse* out)
+{
+  kr::clear_error();
+  return submit_fasta(s, "kr_batch_submit_fasta", raw, nbytes, flags, closed, out, nullptr);
 }
 
 } // extern "C"

@@ -9,8 +9,16 @@ namespace {
 // What kr_batch_submit_fastq and kr_batch_submit_fasta (kr_host_fasta.inc) share.  fq_begin: the argument checks, the wait for the
 // batch in flight, the kernels' arguments that do not depend on the format, and the chunk's copy to d_raw; nbytes == 0 is accepted
 // here (nothing is queued: the caller returns).  fq_finish: the wait for the summary, and the accepted prefix queued as a batch.
+// FqHooks (kr_batch_submit_bgzf, kr_host_bgzf.inc): `fill` queues what writes the chunk into d_raw in place of the copy, `check`
+// runs behind the wait for the summary and in front of the queueing -- when it fails nothing is queued.
+struct FqHooks {
+  int (*fill)(kr_stream*, hipStream_t, void*);
+  int (*check)(kr_stream*, void*);
+  void* arg;
+};
+
 int fq_begin(kr_stream* s, const char* fn, const uint8_t* raw, uint64_t nbytes, uint32_t flags, uint32_t at_eof, kr_fastq_parse* out, FqIO& io,
-             bool& text)
+             bool& text, const FqHooks* hooks = nullptr)
 {
   const std::string who = std::string(fn) + ": ";
   if (!s || !raw || !out) return kr::fail(KR_ERR_ARG, who + "null argument");
@@ -46,7 +54,10 @@ int fq_begin(kr_stream* s, const char* fn, const uint8_t* raw, uint64_t nbytes, 
   io.k = s->ix->dix.k, io.tile_min_pos = (flags & KR_TILE_DEVICE) ? 0xFFFFFFFFu : s->tile_min_pos;
   io.sum = f.d_sum;
   // queued before the index's kernel chain is waited for (launch_lane): the copy and the parse overlap other streams' batches
-  HIP_TRY(hipMemcpyAsync(f.d_raw, raw, nbytes, hipMemcpyHostToDevice, st));
+  if (hooks) {
+    if (int rc = hooks->fill(s, st, hooks->arg)) return rc;
+  } else
+    HIP_TRY(hipMemcpyAsync(f.d_raw, raw, nbytes, hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemsetAsync(f.d_ctl, 0xFF, 32, st));
   return KR_OK;
 }
@@ -58,7 +69,7 @@ int fq_mark(kr_stream* s)
   return KR_OK;
 }
 
-int fq_finish(kr_stream* s, uint32_t flags, uint32_t at_eof, bool text, kr_fastq_parse* out)
+int fq_finish(kr_stream* s, uint32_t flags, uint32_t at_eof, bool text, kr_fastq_parse* out, const FqHooks* hooks = nullptr)
 {
   kr_stream::Fastq& f = s->fq;
   hipStream_t st = s->lanes[0].stream;
@@ -69,6 +80,8 @@ int fq_finish(kr_stream* s, uint32_t flags, uint32_t at_eof, bool text, kr_fastq
   }
   HIP_TRY(hipMemcpyAsync(f.h_sum, f.d_sum, sizeof(kr_fastq_parse), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
+  if (hooks)
+    if (int rc = hooks->check(s, hooks->arg)) return rc; // (f.parsed stays false: the stream serves the next submit)
   *out = *f.h_sum;
   out->at_eof = at_eof ? 1u : 0u;
   f.nreads = out->nreads;
@@ -91,6 +104,31 @@ int fq_finish(kr_stream* s, uint32_t flags, uint32_t at_eof, bool text, kr_fastq
     rc = submit_batch(s, s->d_bases, s->d_offsets, out->nreads, flags | KR_BASES_DEVICE);
   }
   return rc;
+}
+
+// kr_batch_submit_fastq; with hooks: the same for bytes that a kernel writes into d_raw (`raw` is then only checked for NULL)
+int submit_fastq(kr_stream* s, const char* fn, const uint8_t* raw, uint64_t nbytes, uint32_t flags, uint32_t at_eof, kr_fastq_parse* out,
+                 const FqHooks* hooks)
+{
+  FqIO io;
+  bool text = false;
+  int rc = fq_begin(s, fn, raw, nbytes, flags, at_eof, out, io, text, hooks);
+  if (rc || nbytes == 0) return rc;
+  kr_stream::Fastq& f = s->fq;
+  hipStream_t st = s->lanes[0].stream;
+  io.nl = f.d_nl, io.nl_cap = 4u * s->max_reads, io.rec_lines = 4;
+  const uint32_t ntiles = (uint32_t)((nbytes + kFqTile - 1) / kFqTile);
+  const uint32_t rgrid = std::min<uint32_t>((s->max_reads + 3) / 4, 8192u), bgrid = std::min<uint32_t>(s->max_reads / kFqRecBlock + 1, 4096u);
+  if ((rc = fq_mark(s))) return rc;
+  hipLaunchKernelGGL(kr_fq_nl_count_kernel, dim3(std::min<uint32_t>(ntiles, 16384u)), dim3(256), 0, st, io);
+  hipLaunchKernelGGL(kr_fq_nl_scan_kernel, dim3(1), dim3(1024), 0, st, io);
+  hipLaunchKernelGGL(kr_fq_nl_write_kernel, dim3(std::min<uint32_t>(ntiles, 16384u)), dim3(256), 0, st, io);
+  hipLaunchKernelGGL(kr_fq_rec_kernel, dim3(rgrid), dim3(256), 0, st, io);
+  hipLaunchKernelGGL(kr_fq_bsum_kernel, dim3(bgrid), dim3(256), 0, st, io);
+  hipLaunchKernelGGL(kr_fq_bscan_kernel, dim3(1), dim3(1024), 0, st, io);
+  hipLaunchKernelGGL(kr_fq_off_kernel, dim3(bgrid), dim3(256), 0, st, io);
+  hipLaunchKernelGGL(kr_fq_copy_kernel, dim3(rgrid), dim3(256), 0, st, io);
+  return fq_finish(s, flags, at_eof, text, out, hooks);
 }
 
 } // namespace
@@ -123,25 +161,7 @@ int kr_stream_fastq_enable(kr_stream* s, uint64_t max_raw_bytes)
 int kr_batch_submit_fastq(kr_stream* s, const uint8_t* raw, uint64_t nbytes, uint32_t flags, uint32_t at_eof, kr_fastq_parse* out)
 {
   kr::clear_error();
-  FqIO io;
-  bool text = false;
-  int rc = fq_begin(s, "kr_batch_submit_fastq", raw, nbytes, flags, at_eof, out, io, text);
-  if (rc || nbytes == 0) return rc;
-  kr_stream::Fastq& f = s->fq;
-  hipStream_t st = s->lanes[0].stream;
-  io.nl = f.d_nl, io.nl_cap = 4u * s->max_reads, io.rec_lines = 4;
-  const uint32_t ntiles = (uint32_t)((nbytes + kFqTile - 1) / kFqTile);
-  const uint32_t rgrid = std::min<uint32_t>((s->max_reads + 3) / 4, 8192u), bgrid = std::min<uint32_t>(s->max_reads / kFqRecBlock + 1, 4096u);
-  if ((rc = fq_mark(s))) return rc;
-  hipLaunchKernelGGL(kr_fq_nl_count_kernel, dim3(std::min<uint32_t>(ntiles, 16384u)), dim3(256), 0, st, io);
-  hipLaunchKernelGGL(kr_fq_nl_scan_kernel, dim3(1), dim3(1024), 0, st, io);
-  hipLaunchKernelGGL(kr_fq_nl_write_kernel, dim3(std::min<uint32_t>(ntiles, 16384u)), dim3(256), 0, st, io);
-  hipLaunchKernelGGL(kr_fq_rec_kernel, dim3(rgrid), dim3(256), 0, st, io);
-  hipLaunchKernelGGL(kr_fq_bsum_kernel, dim3(bgrid), dim3(256), 0, st, io);
-  hipLaunchKernelGGL(kr_fq_bscan_kernel, dim3(1), dim3(1024), 0, st, io);
-  hipLaunchKernelGGL(kr_fq_off_kernel, dim3(bgrid), dim3(256), 0, st, io);
-  hipLaunchKernelGGL(kr_fq_copy_kernel, dim3(rgrid), dim3(256), 0, st, io);
-  return fq_finish(s, flags, at_eof, text, out);
+  return submit_fastq(s, "kr_batch_submit_fastq", raw, nbytes, flags, at_eof, out, nullptr);
 }
 
 int kr_batch_fastq_names(kr_stream* s, const uint64_t** name_pos, const uint32_t** name_len)

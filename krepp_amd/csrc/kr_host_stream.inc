@@ -226,6 +226,19 @@ struct kr_stream {
     uint32_t *d_hs = nullptr, *d_ga = nullptr;           // [max_reads + 2]
     uint32_t *d_hg = nullptr, *d_he = nullptr;           // [max_reads]
   } fq;
+  // block-gzipped chunks inflated into fq.d_raw (kr_dev_bgzf.inc; kr_stream_bgzf_enable)
+  struct Bgzf {
+    bool on = false;
+    uint64_t comp_cap = 0;
+    uint32_t max_members = 0;
+    uint8_t *d_comp = nullptr, *d_scratch = nullptr; // [comp_cap], [2][65536]
+    kr::BgzfMember *d_tab = nullptr, *h_tab = nullptr; // [max_members]
+    uint32_t* d_status = nullptr;
+    BgzfSum *d_sum = nullptr, *h_sum = nullptr;
+    std::vector<uint64_t> member_off; // of the last chunk's members in `comp`, for the message of a rejected one
+    hipEvent_t ev0 = nullptr, ev1 = nullptr; // kr_debug_bgzf_ms: around the inflate kernel, once asked for
+    bool ev_set = false;
+  } bgzf;
   const uint8_t* sub_bases = nullptr; // the arguments of the submit in flight (host buffers stay valid until wait / collect returns)
   const uint64_t* sub_offsets = nullptr;
   // state
@@ -970,6 +983,8 @@ void kr_stream_destroy(kr_stream* s)
   for (hipStream_t st : s->moved_streams) (void)hipStreamDestroy(st);
   if (s->fq.ev_parse0) (void)hipEventDestroy(s->fq.ev_parse0);
   if (s->fq.ev_parse1) (void)hipEventDestroy(s->fq.ev_parse1);
+  if (s->bgzf.ev0) (void)hipEventDestroy(s->bgzf.ev0);
+  if (s->bgzf.ev1) (void)hipEventDestroy(s->bgzf.ev1);
   for (auto& e : s->seek.ev)
     if (e) (void)hipEventDestroy(e);
   delete s; // (every DevBuf / PinBuf of the stream frees itself here: the device is set, the lanes' streams have been waited for)

@@ -86,7 +86,7 @@ static void print_help(const std::string& sub)
   if (sub.empty() || sub == "dist")
     printf("\nkrepp dist -i DIR -q READS: distances of every read to the references it matches\n%s%s"
            "      --filter / --no-filter keep only references not significantly worse than the closest [no-filter]\n"
-           "      --gpu-parse            FASTA/FASTQ records found on the GPU (identical output; plain files, others keep the host reader)\n",
+           "      --gpu-parse            FASTA/FASTQ records found on the GPU (identical output; plain files, and BGZF files, inflated on the GPU; others keep the host reader)\n",
            query_opts, index_query_opts);
   if (sub.empty() || sub == "place")
     printf("\nkrepp place -i DIR -q READS: placements on the backbone tree (jplace)\n%s%s"
@@ -95,12 +95,12 @@ static void print_help(const std::string& sub)
            "      --tau N                highest Hamming distance counted by the placement threshold [2]\n"
            "      --filter / --no-filter [filter]\n"
            "      --tabular              tab-separated rows instead of jplace\n"
-           "      --gpu-parse            FASTA/FASTQ records found on the GPU (identical output; plain files, others keep the host reader)\n",
+           "      --gpu-parse            FASTA/FASTQ records found on the GPU (identical output; plain files, and BGZF files, inflated on the GPU; others keep the host reader)\n",
            query_opts, index_query_opts);
   if (sub.empty() || sub == "seek")
     printf("\nkrepp seek -i SKETCH -q READS: distance of every read to the one sketched reference\n"
            "  -i, --sketch-path PATH     sketch file (as written by `krepp sketch`)\n%s"
-           "      --gpu-parse            FASTA/FASTQ records found on the GPU (identical output; plain files, others keep the host reader)\n"
+           "      --gpu-parse            FASTA/FASTQ records found on the GPU (identical output; plain files, and BGZF files, inflated on the GPU; others keep the host reader)\n"
            "      --gpu-seek             seek kernels and report text on the GPU (identical output)\n",
            query_opts);
   if (sub.empty() || sub == "index")
@@ -267,6 +267,21 @@ struct Job {
   uint64_t raw_len = 0, raw_off = 0;
   bool at_eof = false;
   bool fasta = false, closed = false; // a chunk of a FASTA file (kr_batch_submit_fasta); its last record ends where the chunk does
+  // ... of a block-gzipped file: whole members (page-locked) that the device inflates (kr_batch_submit_bgzf); the chunk is bytes
+  // [skip, skip + raw_len) of what they hold, and `raw` receives them.  m_off / m_u: every member's offset in the file and its first
+  // inflated byte among the job's, with the end of the last member behind them
+  uint8_t* comp = nullptr;
+  uint64_t comp_len = 0;
+  uint32_t skip = 0;
+  std::vector<uint64_t> m_off, m_u;
+  // chunk position -> BGZF virtual offset (member's file offset << 16 | byte inside the member)
+  uint64_t voffset(uint64_t pos) const
+  {
+    const uint64_t u = skip + pos;
+    size_t m = m_u.size() - 1;
+    while (m > 0 && m_u[m] > u) --m;
+    return m_off[m] << 16 | (u - m_u[m]);
+  }
 };
 
 // The run's one lock and everything it protects about the ORDER of the output.  Jobs are numbered by the reader; their rows appear
@@ -336,7 +351,7 @@ public:
   bool stopped(uint64_t* byte) { std::lock_guard<std::mutex> lk(mu); *byte = fb_off_; return stopped_locked(); }
   void fail(const std::string& msg)
   {
-    { std::lock_guard<std::mutex> lk(mu); err_ = msg; }
+    { std::lock_guard<std::mutex> lk(mu); if (err_.empty()) err_ = msg; } // (the first error is the one reported)
     cv_done.notify_all(), cv_work.notify_all();
   }
   bool failed() { std::lock_guard<std::mutex> lk(mu); return !err_.empty(); }
@@ -407,7 +422,7 @@ struct Run {
   kr_place_tree* ptree = nullptr;
   std::vector<kr_index*> dix;
   kr_fastx* fx = nullptr; // (opened before the workers start; they hand batches back to it)
-  // --gpu-parse (plain regular files): the reader only moves bytes into page-locked chunks cut at guessed record starts; each worker
+  // --gpu-parse (plain regular files; block-gzipped ones: `bgzf` below): the reader only moves bytes into page-locked chunks cut at guessed record starts; each worker
   // finds the records of its chunks on its GPU (kr_batch_submit_fastq / kr_batch_submit_fasta with KR_TILE_DEVICE: long records are
   // tiled on the device).  The first chunk that stops early (a record that is not clean four-line FASTQ, a wrong cut, a batch that
   // overflows) names the byte where the host reader (kr_fastx_open_at) takes over for good, as the pool reader's "first surprise ->
@@ -418,6 +433,11 @@ struct Run {
   int qfd = -1;
   uint64_t qsize = 0;
   bool fasta_parse = false; // a file whose first byte is '>' is cut and parsed as FASTA; any other as FASTQ
+  // a block-gzipped file: the chunks are whole members, inflated on the device (kr_batch_submit_bgzf) into the job's `raw`; an early
+  // stop is a BGZF virtual offset and kr_fastx_open_at_bgzf takes over there.  Every `raw` buffer has a buffer for the members.
+  bool bgzf = false;
+  std::map<uint8_t*, uint8_t*> comp_of;
+  uint64_t chunk_cap() const { return s.chunk_bytes + (bgzf ? 2 * 65536 : 0); } // (a chunk may begin and end inside a member)
 
   OutputOrder order;
   // under order.mu, waited for on order.cv_work (gpu_done: cv_done)
@@ -462,6 +482,8 @@ struct Run {
   void chunk_done(uint8_t* raw);
   void enqueue(std::unique_ptr<Job> j);
   void read_chunks();
+  void read_chunks_bgzf();
+  void chunks_done(uint64_t foreign_at);
   void read_host();
   void end_of_input();
   void write_loop();
@@ -538,16 +560,44 @@ void Run::start_up(const Args& a)
   order.open(out, s.dev_text && !s.serial_write);
 }
 
-// --gpu-parse on a plain regular file: the file for pread and the page-locked chunk buffers; anything else: the host reader
+// The first inflated byte of a block-gzipped file ('>': FASTA), from its first member that holds one, inflated on the host.
+// False: the file does not begin with BGZF members that inflate -- the host reader's case.
+static bool bgzf_first_byte(int fd, uint64_t size, uint8_t* first)
+{
+  std::vector<uint8_t> m(65536 + 18 + 256), u(65536);
+  uint64_t off = 0;
+  for (int k = 0; k < 64 && off < size; ++k) {
+    const ssize_t n = pread(fd, m.data(), (size_t)std::min<uint64_t>(m.size(), size - off), (off_t)off);
+    const uint32_t ms = n > 0 ? kr_bgzf_member_size(m.data(), (uint64_t)n) : 0;
+    uint64_t len = 0;
+    if (ms == 0 || ms > (uint64_t)n || kr_debug_bgzf_inflate_host(m.data(), ms, u.data(), u.size(), &len)) return false;
+    if (len) {
+      *first = u[0];
+      return true;
+    }
+    off += ms;
+  }
+  return false;
+}
+
+// --gpu-parse on a plain or block-gzipped regular file: the file for pread and the page-locked chunk buffers; anything else (ordinary
+// gzip, a pipe): the host reader
 void Run::open_input()
 {
   if (s.gpu_parse) {
     struct stat sb;
     unsigned char mg[2] = {0, 0};
+    uint8_t first = 0;
     qfd = open(s.query.c_str(), O_RDONLY);
-    if (qfd < 0 || fstat(qfd, &sb) != 0 || !S_ISREG(sb.st_mode) || (pread(qfd, mg, 2, 0) == 2 && mg[0] == 0x1f && mg[1] == 0x8b)) {
+    const bool regular = qfd >= 0 && fstat(qfd, &sb) == 0 && S_ISREG(sb.st_mode);
+    const bool gz = regular && pread(qfd, mg, 2, 0) == 2 && mg[0] == 0x1f && mg[1] == 0x8b;
+    if (regular && gz && bgzf_first_byte(qfd, (uint64_t)sb.st_size, &first)) {
+      gpu_parse = bgzf = true;
+      qsize = (uint64_t)sb.st_size;
+      fasta_parse = first == '>';
+    } else if (!regular || gz) {
       if (qfd >= 0) close(qfd);
-      qfd = -1; // gzip / BGZF / not a regular file: the host reader
+      qfd = -1; // ordinary gzip / not a regular file: the host reader
     } else {
       gpu_parse = true;
       qsize = (uint64_t)sb.st_size;
@@ -557,9 +607,11 @@ void Run::open_input()
   if (!gpu_parse && kr_fastx_open(s.query.c_str(), &fx)) error_exit(kr_last_error());
   if (gpu_parse) // one buffer per worker at work, one being filled, one waiting per worker
     for (int q = 0; q < 2 * s.nworkers + 1; ++q) {
-      uint8_t* b_ = (uint8_t*)kr_host_alloc(s.chunk_bytes + 16);
-      if (!b_) error_exit("cannot allocate page-locked chunk buffers for --gpu-parse");
+      uint8_t* b_ = (uint8_t*)kr_host_alloc(chunk_cap() + 16);
+      uint8_t* c_ = bgzf ? (uint8_t*)kr_host_alloc(chunk_cap() + 16) : nullptr;
+      if (!b_ || (bgzf && !c_)) error_exit("cannot allocate page-locked chunk buffers for --gpu-parse");
       raw_free.push_back(b_);
+      if (bgzf) comp_of[b_] = c_;
     }
 }
 
@@ -660,7 +712,8 @@ void Worker::loop()
       fprintf(stderr, "[krepp_amd] report text on the host: %s\n", kr_last_error());
   }
   if (s.gpu_seek && kr_stream_seek_enable(st, s.text_bytes, std::max<uint64_t>(1ull << 20, (uint64_t)s.max_reads * 64))) return r.worker_ready(kr_last_error());
-  if (r.gpu_parse && kr_stream_fastq_enable(st, s.chunk_bytes)) return r.worker_ready(kr_last_error());
+  if (r.gpu_parse && kr_stream_fastq_enable(st, r.chunk_cap())) return r.worker_ready(kr_last_error());
+  if (r.bgzf && kr_stream_bgzf_enable(st, r.chunk_cap())) return r.worker_ready(kr_last_error());
   const double t_ready = r.at();
   r.worker_ready(nullptr);
   while ((j = r.next_job())) {
@@ -859,8 +912,14 @@ int Worker::run_chunk()
     const uint8_t* raw = j->raw + pos;
     kr_fastq_parse fp;
     auto t_dev = Clock::now();
-    int rc = j->fasta ? kr_batch_submit_fasta(st, raw, j->raw_len - pos, flags, j->closed ? 1u : 0u, &fp)
-                      : kr_batch_submit_fastq(st, raw, j->raw_len - pos, flags, j->at_eof ? 1u : 0u, &fp);
+    int rc;
+    if (j->comp && pos == 0) { // (after KR_FASTQ_CAPACITY the chunk's bytes are in `raw`: the submits below)
+      rc = kr_batch_submit_bgzf(st, j->comp, j->comp_len, j->skip, j->raw_len, j->raw, flags, j->fasta ? 1u : 0u, (j->fasta ? j->closed : j->at_eof) ? 1u : 0u, &fp);
+      if (rc == KR_ERR_FORMAT) // as the host reader reports a member that does not inflate: the file, and where
+        r.order.fail("damaged block-gzipped file: " + s.query + ": in the members from offset " + std::to_string(j->m_off[0]) + ": " + kr_last_error());
+    } else
+      rc = j->fasta ? kr_batch_submit_fasta(st, raw, j->raw_len - pos, flags, j->closed ? 1u : 0u, &fp)
+                    : kr_batch_submit_fastq(st, raw, j->raw_len - pos, flags, j->at_eof ? 1u : 0u, &fp);
     if (rc) return rc;
     if (fp.nreads) {
       kr_result_view rv;
@@ -924,7 +983,7 @@ int Worker::run_chunk()
   for (kr_placement& x : pls) x.read = (uint32_t)(j->first_read + x.read);
   r.nreads_dev += nr_job;
   if (s.gpu_seek) r.nreads_seek += nr_job;
-  if (fell) r.order.stop_at(*j, j->raw_off + pos);
+  if (fell) r.order.stop_at(*j, j->comp ? j->voffset(pos) : j->raw_off + pos);
   return 0;
 }
 
@@ -990,14 +1049,104 @@ void Run::read_chunks()
     enqueue(std::move(j));
   }
   ns_parse += since(t_parse);
-  { // every chunk handed out is done (an earlier one may still stop early): then the first stop, if any, is final
+  chunks_done(UINT64_MAX);
+}
+
+// Every chunk handed out is done (an earlier one may still stop early): then the first stop, if any, is final, and the host reader
+// takes over there.  foreign_at: where a block-gzipped file goes on with bytes that are no BGZF member (UINT64_MAX: nowhere) -- the
+// host reader's from that offset when no chunk stopped in front of it.
+void Run::chunks_done(uint64_t foreign_at)
+{
+  {
     std::unique_lock<std::mutex> lk(order.mu);
     order.cv_done.wait(lk, [&] { return gpu_done == gpu_issued || order.failed_locked(); });
   }
   close(qfd);
   nreads_total = nreads_dev; // (the host reader, if it takes over, numbers its reads behind the device's: place --summarize)
   uint64_t fb_off = 0;
-  if (order.stopped(&fb_off) && !order.failed() && kr_fastx_open_at(s.query.c_str(), fb_off, &fx)) error_exit(kr_last_error());
+  const bool stopped = order.stopped(&fb_off);
+  if (order.failed()) return;
+  if (stopped && (bgzf ? kr_fastx_open_at_bgzf(s.query.c_str(), fb_off >> 16, (uint32_t)(fb_off & 0xFFFFu), &fx) : kr_fastx_open_at(s.query.c_str(), fb_off, &fx)))
+    error_exit(kr_last_error());
+  if (!stopped && foreign_at != UINT64_MAX && kr_fastx_open_at_bgzf(s.query.c_str(), foreign_at, 0, &fx)) error_exit(kr_last_error());
+}
+
+// --gpu-parse on a block-gzipped file: the reader moves whole members, as many as inflate to a chunk, and cuts the chunk at its last
+// record start (kr_bgzf_chunk_cut inflates the last members to find it); the next chunk begins at the member that holds the cut,
+// `skip` bytes into it.  The device inflates the members and finds the records (kr_batch_submit_bgzf).
+void Run::read_chunks_bgzf()
+{
+  auto t_parse = Clock::now();
+  uint64_t off = 0, foreign_at = UINT64_MAX;
+  uint32_t skip = 0;
+  while (off < qsize) {
+    uint8_t* buf = nullptr;
+    {
+      std::unique_lock<std::mutex> lk(order.mu);
+      order.cv_work.wait(lk, [&] { return !raw_free.empty() || order.stopped_locked() || order.failed_locked(); });
+      if (order.stopped_locked() || order.failed_locked()) break; // (an early stop: nothing behind it will be used)
+      buf = raw_free.back();
+      raw_free.pop_back();
+    }
+    auto give_back = [&] {
+      std::lock_guard<std::mutex> lk(order.mu);
+      raw_free.push_back(buf);
+    };
+    uint8_t* comp = comp_of[buf];
+    const uint64_t want = std::min<uint64_t>(chunk_cap(), qsize - off);
+    uint64_t got = 0;
+    while (got < want) {
+      const ssize_t k = pread(qfd, comp + got, want - got, (off_t)(off + got));
+      if (k <= 0) error_exit("cannot read " + s.query);
+      got += (uint64_t)k;
+    }
+    uint32_t nm = 0;
+    uint64_t cb = 0, U = 0;
+    if (kr_bgzf_walk(comp, want, s.chunk_bytes + skip, &nm, &cb, &U)) error_exit(kr_last_error());
+    if (nm == 0) { // no whole member here: the file ends inside one, the member is malformed, or these bytes are no BGZF member
+      give_back();
+      if (kr_bgzf_member_size(comp, want) != 0)
+        order.fail("damaged block-gzipped file (a member is cut short or malformed at offset " + std::to_string(off) + "): " + s.query);
+      else
+        foreign_at = off; // an ordinary gzip member appended, say: zlib's from here on
+      break;
+    }
+    // The chunk ends at its last record start, as a plain file's does; none, or the file's last members: it goes out whole
+    bool last = off + cb >= qsize;
+    uint64_t moff = cb;
+    uint32_t uoff = 0;
+    uint64_t c = last ? 0 : kr_bgzf_chunk_cut(comp, cb, skip, fasta_parse ? 1u : 0u, &moff, &uoff);
+    if (!c && !last) { // a chunk that begins near the end of a member may hold the head of one record only: one more member's worth
+      if (kr_bgzf_walk(comp, want, s.chunk_bytes + skip + 65536, &nm, &cb, &U)) error_exit(kr_last_error());
+      last = off + cb >= qsize;
+      moff = cb;
+      c = last ? 0 : kr_bgzf_chunk_cut(comp, cb, skip, fasta_parse ? 1u : 0u, &moff, &uoff);
+    }
+    const uint64_t comp_len = !c ? cb : uoff ? moff + kr_bgzf_member_size(comp + moff, cb - moff) : moff;
+    const uint64_t nbytes = c ? c : U - skip;
+    const uint64_t next_off = c ? off + moff : off + cb;
+    const uint32_t next_skip = c ? uoff : 0;
+    if (nbytes == 0) { // (empty members only: the end-of-file marker)
+      give_back();
+      off = next_off, skip = next_skip;
+      continue;
+    }
+    std::unique_ptr<Job> j(new Job());
+    j->raw = buf, j->raw_len = nbytes, j->raw_off = off, j->at_eof = last;
+    j->fasta = fasta_parse, j->closed = last || (fasta_parse && c);
+    j->comp = comp, j->comp_len = comp_len, j->skip = skip;
+    for (uint64_t p = 0, u = 0; p < comp_len;) {
+      const uint32_t ms = kr_bgzf_member_size(comp + p, comp_len - p);
+      j->m_off.push_back(off + p), j->m_u.push_back(u);
+      u += (uint32_t)comp[p + ms - 4] | (uint32_t)comp[p + ms - 3] << 8 | (uint32_t)comp[p + ms - 2] << 16 | (uint32_t)comp[p + ms - 1] << 24;
+      p += ms;
+      if (p >= comp_len) j->m_off.push_back(off + p), j->m_u.push_back(u);
+    }
+    off = next_off, skip = next_skip;
+    enqueue(std::move(j));
+  }
+  ns_parse += since(t_parse);
+  chunks_done(foreign_at);
 }
 
 // the host reader: batches of parsed records, split so that they fit the stream limits
@@ -1125,7 +1274,7 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
   std::thread writer([&r] { r.write_loop(); });
   if (s.seek) fprintf(stderr, "Seeking query sequences in the sketch...\n");
   if (!s.place && !s.seek) fprintf(stderr, "Estimating distances between given sequences and references...\n");
-  if (r.gpu_parse) r.read_chunks();
+  if (r.gpu_parse) r.bgzf ? r.read_chunks_bgzf() : r.read_chunks();
   if (r.fx) r.read_host();
   r.end_of_input();
   for (auto& w : workers) w.join();
