@@ -142,9 +142,8 @@ int kr_debug_bgzf_inflate(kr_stream* s, const uint8_t* comp, uint64_t ncomp, uin
   if (nbytes > cap) return kr::fail(KR_ERR_ARG, "bgzf: the members inflate to more bytes than the buffer holds");
   HIP_TRY(hipSetDevice(s->ix->device));
   (void)hipGetLastError();
-  if (s->submitted && !s->waited) // d_raw may still be read by the batch in flight
-    for (uint32_t l = 0; l < s->nlanes; ++l) HIP_TRY(hipStreamSynchronize(s->lanes[l].stream));
-  s->fq.parsed = false, s->fq.have_names = false;
+  if (int rc = drain_batch(s)) return rc; // d_raw may still be read by the batch in flight
+  s->parse = LastParse{}; // (... and is overwritten: the last parse's names are gone)
   hipStream_t st = s->lanes[0].stream;
   if (int rc = bgzf_queue(s, st, comp, ncomp, nm, nbytes)) return rc;
   HIP_TRY(hipStreamSynchronize(st));

@@ -31,16 +31,15 @@ int fq_begin(kr_stream* s, const char* fn, const uint8_t* raw, uint64_t nbytes, 
   memset(out, 0, sizeof(*out));
   out->at_eof = at_eof ? 1u : 0u;
   kr_stream::Fastq& f = s->fq;
-  if (nbytes == 0) {
-    f.parsed = true, f.nreads = 0, f.have_names = false;
+  if (nbytes == 0) { // (a parse of no record: the batch in flight stays as it is)
+    s->parse = LastParse{true, false, 0};
     return KR_OK;
   }
   text = s->text.on && !(flags & (KR_TAP_ACCS | KR_TAP_HITS)) && ((flags & KR_SEEK) || !s->text.seek_only);
   HIP_TRY(hipSetDevice(s->ix->device));
   (void)hipGetLastError();
-  if (s->submitted && !s->waited) // d_bases, d_offsets and the ids belong to the batch in flight
-    for (uint32_t l = 0; l < s->nlanes; ++l) HIP_TRY(hipStreamSynchronize(s->lanes[l].stream));
-  f.parsed = false, f.have_names = false;
+  if (int rc = drain_batch(s)) return rc; // d_bases, d_offsets and the ids belong to the batch in flight
+  s->parse = LastParse{}; // (d_raw is overwritten: the last parse's names are gone)
   hipStream_t st = s->lanes[0].stream; // (the lane of a device-input batch: the parse and the batch are ordered on it)
   io.raw = f.d_raw, io.nbytes = nbytes;
   io.tile_nl = f.d_tile_nl, io.nl = nullptr, io.nl_cap = 0, io.rec_lines = 0;
@@ -81,29 +80,17 @@ int fq_finish(kr_stream* s, uint32_t flags, uint32_t at_eof, bool text, kr_fastq
   HIP_TRY(hipMemcpyAsync(f.h_sum, f.d_sum, sizeof(kr_fastq_parse), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   if (hooks)
-    if (int rc = hooks->check(s, hooks->arg)) return rc; // (f.parsed stays false: the stream serves the next submit)
+    if (int rc = hooks->check(s, hooks->arg)) return rc; // (parse.parsed stays false: the stream serves the next submit)
   *out = *f.h_sum;
   out->at_eof = at_eof ? 1u : 0u;
-  f.nreads = out->nreads;
-  f.parsed = true;
-  if (out->nreads == 0) return KR_OK;
-  kr_stream::Text& t = s->text;
-  int rc;
-  if (flags & KR_SEEK) { // no dist tile layout: the batch as the record finder left it
-    t.id_bytes = out->id_bytes, t.id_sep = 0;
-    t.req = text, t.ids_on_device = text;
-    rc = seek_submit(s, s->d_bases, s->d_offsets, out->nreads, KR_SEEK | KR_BASES_DEVICE);
-    if (rc) t.req = false;
-  } else if (text) {
-    t.id_bytes = out->id_bytes, t.id_sep = 0;
-    t.req = true, t.ids_on_device = true;
-    rc = submit_batch(s, s->d_bases, s->d_offsets, out->nreads, flags | KR_ROWS_ONLY | KR_BASES_DEVICE);
-    if (rc) t.req = false;
-  } else {
-    t.req = false;
-    rc = submit_batch(s, s->d_bases, s->d_offsets, out->nreads, flags | KR_BASES_DEVICE);
-  }
-  return rc;
+  s->parse = LastParse{true, false, out->nreads};
+  if (out->nreads == 0) return KR_OK; // (nothing to queue: the batch in flight stays as it is)
+  BatchOrigin from;
+  from.parsed = true;
+  if (text) from.ids = kIdsDevice, from.id_bytes = out->id_bytes; // (the record finder wrote them into text.d_ids / d_id_off)
+  if (flags & KR_SEEK) // no dist tile layout: the batch as the record finder left it
+    return seek_submit(s, s->d_bases, s->d_offsets, out->nreads, KR_SEEK | KR_BASES_DEVICE, from);
+  return submit_batch(s, s->d_bases, s->d_offsets, out->nreads, flags | KR_BASES_DEVICE | (text ? KR_ROWS_ONLY : 0u), from);
 }
 
 // kr_batch_submit_fastq; with hooks: the same for bytes that a kernel writes into d_raw (`raw` is then only checked for NULL)
@@ -168,10 +155,10 @@ int kr_batch_fastq_names(kr_stream* s, const uint64_t** name_pos, const uint32_t
 {
   kr::clear_error();
   if (!s || !name_pos || !name_len) return kr::fail(KR_ERR_ARG, "kr_batch_fastq_names: null argument");
-  if (!s->fq.on || !s->fq.parsed) return kr::fail(KR_ERR_STATE, "kr_batch_fastq_names: the last submit was not kr_batch_submit_fastq");
+  if (!s->fq.on || !s->parse.parsed) return kr::fail(KR_ERR_STATE, "kr_batch_fastq_names: the last submit was not kr_batch_submit_fastq");
   kr_stream::Fastq& f = s->fq;
-  const uint32_t n = f.nreads;
-  if (!f.have_names && n) {
+  const uint32_t n = s->parse.nreads;
+  if (!s->parse.have_names && n) {
     HIP_TRY(hipSetDevice(s->ix->device));
     if (!f.h_npos) { // page-locked mirrors, made on first use
       int rc = 0;
@@ -184,7 +171,7 @@ int kr_batch_fastq_names(kr_stream* s, const uint64_t** name_pos, const uint32_t
     f.name_pos.assign(f.h_npos, f.h_npos + n);
   }
   if (!n) f.name_pos.clear();
-  f.have_names = true;
+  s->parse.have_names = true;
   *name_pos = f.name_pos.data();
   *name_len = f.h_nlen;
   return KR_OK;
@@ -195,8 +182,8 @@ int kr_debug_fastq_batch(kr_stream* s, uint8_t* bases, uint64_t* offsets)
 {
   kr::clear_error();
   if (!s || !bases || !offsets) return kr::fail(KR_ERR_ARG, "kr_debug_fastq_batch: null argument");
-  if (!s->fq.on || !s->fq.parsed) return kr::fail(KR_ERR_STATE, "kr_debug_fastq_batch: the last submit was not kr_batch_submit_fastq");
-  const uint32_t n = s->fq.nreads;
+  if (!s->fq.on || !s->parse.parsed) return kr::fail(KR_ERR_STATE, "kr_debug_fastq_batch: the last submit was not kr_batch_submit_fastq");
+  const uint32_t n = s->parse.nreads;
   offsets[0] = 0;
   if (!n) return KR_OK;
   HIP_TRY(hipSetDevice(s->ix->device));

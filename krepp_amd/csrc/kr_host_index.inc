@@ -33,6 +33,31 @@ struct kr_index {
 
 namespace {
 
+// One link of an index's kernel chain, as a scope around a batch's kernels on `st`: construction takes chain_mu and queues the wait for
+// the previous batch's kernels (its result: `opened`), close() records the event the next batch waits for.  A scope that is left
+// without close() -- a HIP call failed in between -- releases the lock and records no link.
+struct ChainLink {
+  const kr_index* ix;
+  std::unique_lock<std::mutex> lock;
+  hipError_t opened = hipSuccess;
+  ChainLink(const kr_index* index, hipStream_t st) : ix(index), lock(index->chain_mu)
+  {
+    if (!ix->chain_off && ix->chain_n) opened = hipStreamWaitEvent(st, ix->chain_ev[(ix->chain_n - 1) % kr_index::kChainEvents], 0);
+  }
+  hipError_t close(hipStream_t st)
+  {
+    if (!ix->chain_off) {
+      hipEvent_t& ce = ix->chain_ev[ix->chain_n % kr_index::kChainEvents];
+      if (!ce)
+        if (hipError_t e = hipEventCreateWithFlags(&ce, hipEventDisableTiming)) return e;
+      if (hipError_t e = hipEventRecord(ce, st)) return e;
+      ++ix->chain_n;
+    }
+    lock.unlock();
+    return hipSuccess;
+  }
+};
+
 struct DescHeader {
   uint32_t magic, k, h, m, nlibs, tree_nnodes, nleaves, log_g;
   uint32_t slot_log2w, occ; // format code of the slotted table copy (slot_words(); 0: none); 1: row-occupancy bitmaps

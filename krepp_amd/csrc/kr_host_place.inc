@@ -60,8 +60,8 @@ int kr::place_on_device(kr_stream* s, const void* tree_tag, const kr::PlaceTreeA
 {
   int rc = kr::place_device_begin(s, tree_tag, T, read_len);
   if (rc) return rc;
-  if ((rc = kr::place_device_launch(s, T, 0, s->nreads, tau, no_filter, chisq))) return rc;
-  return kr::place_device_finish(s, T, 0, s->nreads, tau, no_filter, chisq, 0, out);
+  if ((rc = kr::place_device_launch(s, T, 0, s->batch.nreads, tau, no_filter, chisq))) return rc;
+  return kr::place_device_finish(s, T, 0, s->batch.nreads, tau, no_filter, chisq, 0, out);
 }
 
 namespace {
@@ -70,7 +70,7 @@ namespace {
 int place_begin_common(kr_stream* s, const void* tree_tag, const kr::PlaceTreeArrays& T)
 {
   if (!s || !T.parent || !T.eff || !T.elig || !T.lo || !T.idx_to_pt || !T.depth) return kr::fail(KR_ERR_ARG, "place_on_device: null argument");
-  if (!s->submitted || !(s->flags & KR_TAP_ACCS))
+  if (!s->batch.submitted || !(s->batch.flags & KR_TAP_ACCS))
     return kr::fail(KR_ERR_STATE, "place: the batch must be submitted with KR_TAP_ACCS (the back end reads every record's histogram)");
   static const bool timing0 = getenv("KR_PLACE_TIMING") != nullptr;
   const auto t_w0 = std::chrono::steady_clock::now();
@@ -101,7 +101,7 @@ int place_begin_common(kr_stream* s, const void* tree_tag, const kr::PlaceTreeAr
     }
     w.tree_tag = tree_tag, w.pn = T.pn, w.nidx = T.nidx;
   }
-  const uint32_t n = s->nreads;
+  const uint32_t n = s->batch.nreads;
   if (n > w.d_len.size() && (rc = place_grow_all((uint64_t)n + n / 4, w.d_len, w.d_c0, w.d_info, w.h_len, w.h_c0, w.h_info))) return rc;
   if ((rc = place_grow_all(kPlCntCount * kPlCnt, w.d_cnt, w.h_cnt))) return rc;
   // candidate slots: a read may need one per leaf and per distinct ancestor while it is worked on, and keeps what it
@@ -168,16 +168,16 @@ int place_begin_common(kr_stream* s, const void* tree_tag, const kr::PlaceTreeAr
 // The batch a record finder queued last on the stream, as kr_place_stream_parsed needs it (krepp_amd.h: the state errors)
 int place_parsed_state(const kr_stream* s)
 {
-  if (!s->fq.on || !s->fq.parsed) return kr::fail(KR_ERR_STATE, "kr_place_stream_parsed: the last submit on the stream was not kr_batch_submit_fastq / kr_batch_submit_fasta");
-  if (!s->fq.nreads || !s->submitted || s->nreads != s->fq.nreads) return kr::fail(KR_ERR_STATE, "kr_place_stream_parsed: the last submit accepted no record (nothing was queued)");
-  if (!(s->flags & KR_TAP_ACCS)) return kr::fail(KR_ERR_STATE, "kr_place_stream_parsed: the batch must be submitted with KR_TAP_ACCS (the back end reads every record's histogram)");
+  if (!s->fq.on || !s->parse.parsed) return kr::fail(KR_ERR_STATE, "kr_place_stream_parsed: the last submit on the stream was not kr_batch_submit_fastq / kr_batch_submit_fasta");
+  if (!s->parse.nreads || !s->batch.submitted || !s->batch.from.parsed) return kr::fail(KR_ERR_STATE, "kr_place_stream_parsed: the last submit accepted no record (nothing was queued)");
+  if (!(s->batch.flags & KR_TAP_ACCS)) return kr::fail(KR_ERR_STATE, "kr_place_stream_parsed: the batch must be submitted with KR_TAP_ACCS (the back end reads every record's histogram)");
   return KR_OK;
 }
 
 PlaceParsedIO place_parsed_io(kr_stream* s)
 {
   kr_stream::PlaceWs& w = s->pw;
-  return PlaceParsedIO{s->d_offsets, s->fq.d_raw, s->fq.d_npos, s->fq.d_nlen, s->nreads, w.d_len.get(), w.d_idbsum.get(), w.d_id_off.get(), w.d_ids.get()};
+  return PlaceParsedIO{s->d_offsets, s->fq.d_raw, s->fq.d_npos, s->fq.d_nlen, s->batch.nreads, w.d_len.get(), w.d_idbsum.get(), w.d_id_off.get(), w.d_ids.get()};
 }
 } // namespace
 
@@ -188,7 +188,7 @@ int kr::place_device_begin(kr_stream* s, const void* tree_tag, const kr::PlaceTr
   const int rc = place_begin_common(s, tree_tag, T);
   if (rc) return rc;
   kr_stream::PlaceWs& w = s->pw;
-  const uint32_t n = s->nreads;
+  const uint32_t n = s->batch.nreads;
   memcpy(w.h_len.get(), read_len, (uint64_t)n * 4);
   HIP_TRY(hipMemcpyAsync(w.d_len.get(), w.h_len.get(), (uint64_t)n * 4, hipMemcpyHostToDevice, s->lanes[0].stream));
   return KR_OK;
@@ -210,7 +210,7 @@ int kr::place_device_begin_parsed(kr_stream* s, const void* tree_tag, const kr::
   HIP_TRY(hipSetDevice(s->device));
   kr_stream::PlaceWs& w = s->pw;
   hipStream_t st = s->lanes[0].stream;
-  const uint32_t n = s->nreads, nblk = n / kPpBlock + 1u;
+  const uint32_t n = s->batch.nreads, nblk = n / kPpBlock + 1u;
   w.ids_queued = false, w.ids_reads = 0;
   if (want_ids) {
     if ((uint64_t)n + 1 > w.d_id_off.size() && (rc = place_grow_all((uint64_t)n + n / 4 + 16, w.d_id_off, w.h_id_off))) return rc;
@@ -237,7 +237,7 @@ int kr::place_device_launch(kr_stream* s, const kr::PlaceTreeArrays& T, uint32_t
   hipStream_t st = s->lanes[0].stream;
   const uint32_t cus = w.cu_count;
   const uint32_t grid = std::min<uint32_t>(n, cus * 16u);
-  BatchOut ro = result_out(s); // the range's reads as reads 0 .. n: the per-read arrays moved by r0 (records are named by rd_off)
+  BatchOut ro = result_out(s, s->out); // the range's reads as reads 0 .. n: the per-read arrays moved by r0 (records are named by rd_off)
   ro.rd_off += r0, ro.rd_cnt += r0, ro.rd_onmers += r0;
   const uint32_t* d_len = w.d_len.get() + r0;
   // the second launch's arrays in LDS where the tree allows it (KR_PLACE_HEAVY_GLOBAL=1: always global scratch, as for large trees)
@@ -393,7 +393,7 @@ int kr::place_device_finish(kr_stream* s, const kr::PlaceTreeArrays& T, uint32_t
   return KR_OK;
 }
 
-uint32_t kr::place_stream_nreads(const kr_stream* s) { return s ? s->nreads : 0; }
+uint32_t kr::place_stream_nreads(const kr_stream* s) { return s ? s->batch.nreads : 0; }
 
 namespace {
 // What place_device_text_begin and place_device_text_begin_parsed share.  place_text_tree: the tree's part of the text on the device;
@@ -486,7 +486,7 @@ int kr::place_device_text_begin_parsed(kr_stream* s, const kr::PlaceTreeArrays& 
   if (!w.ids_queued) return kr::fail(KR_ERR_STATE, "place_device_text_begin: place_device_begin_parsed did not lay out the ids");
   if ((rc = place_text_tree(s, T))) return rc;
   HIP_TRY(hipStreamSynchronize(st)); // (at once as a rule: kr_batch_wait has waited for this stream behind the total's copy)
-  const uint32_t nreads = s->nreads;
+  const uint32_t nreads = s->batch.nreads;
   const uint64_t total = w.h_idtot.get()[0];
   if (total >= 0xFFFFFFF0ull) return kr::fail(KR_ERR_CAPACITY, "place: more than 4 GB of read ids in one batch");
   if (total + 16 > w.d_ids.size() && (rc = place_grow(w.d_ids, total + total / 4 + 4096))) return rc; // (d_ids alone: no id is staged on the host, nothing is page-locked for them)
@@ -505,7 +505,7 @@ int kr::place_parsed_offsets(kr_stream* s, uint64_t* offsets)
   if (rc) return rc;
   HIP_TRY(hipSetDevice(s->device));
   hipStream_t st = s->lanes[0].stream;
-  HIP_TRY(hipMemcpyAsync(offsets, s->d_offsets, ((uint64_t)s->nreads + 1) * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(offsets, s->d_offsets, ((uint64_t)s->batch.nreads + 1) * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return KR_OK;
 }
@@ -513,7 +513,7 @@ void kr::place_call_begin(kr_stream* s)
 {
   if (s) s->pw.ids_queued = false, s->pw.ids_reads = 0;
 }
-uint32_t kr::place_parsed_nreads(const kr_stream* s) { return s && s->fq.on && s->fq.parsed && s->submitted && s->nreads == s->fq.nreads ? s->fq.nreads : 0; }
+uint32_t kr::place_parsed_nreads(const kr_stream* s) { return s && s->fq.on && s->parse.parsed && s->batch.submitted && s->batch.from.parsed ? s->parse.nreads : 0; }
 int kr::place_parsed_check(const kr_stream* s) { return s ? place_parsed_state(s) : kr::fail(KR_ERR_ARG, "kr_place_stream_parsed: null argument"); }
 
 extern "C" int kr_debug_place_ids(kr_stream* s, char* ids, uint32_t* id_off)

@@ -39,34 +39,20 @@ static int seek_queue(kr_stream* s, const uint8_t* bases, const uint64_t* offset
   L.read0 = 0, L.nreads = nreads, L.nrecs = 0, L.nrows = 0;
   const uint8_t* d_bases = bases;
   const uint64_t* d_offsets = offsets;
-  if (!(flags & KR_BASES_DEVICE)) { // as a dist batch's first lane: the bases at their offsets relative to offsets[0]
-    const uint64_t nb = offsets[nreads] - offsets[0];
-    const uint64_t* ho = s->h_offsets;
-    const uint8_t* src = bases + offsets[0];
-    if (!(flags & KR_BASES_PINNED)) {
-      memcpy(s->h_bases, src, nb);
-      src = s->h_bases;
-    }
-    if ((flags & KR_BASES_PINNED) && offsets[0] == 0)
-      ho = offsets;
-    else
-      for (uint32_t r = 0; r <= nreads; ++r) s->h_offsets[r] = offsets[r] - offsets[0];
-    HIP_TRY(hipMemcpyAsync(s->d_bases, src, nb, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(s->d_offsets, ho, ((uint64_t)nreads + 1) * 8, hipMemcpyHostToDevice, st));
+  if (!(flags & KR_BASES_DEVICE)) { // as a dist batch's first lane
+    if (int rc = stage_reads(s, st, bases, offsets, 0, nreads, 0, flags)) return rc;
     d_bases = s->d_bases, d_offsets = s->d_offsets;
   }
   kr_stream::Text& tx = s->text;
-  if (tx.req && !tx.ids_on_device) {
-    HIP_TRY(hipMemcpyAsync(tx.d_ids, tx.h_ids, tx.id_bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(tx.d_id_off, tx.h_id_off, ((uint64_t)nreads + 1) * 4, hipMemcpyHostToDevice, st));
-  }
+  const Batch& b = s->batch;
+  if (b.from.ids == kIdsHost)
+    if (int rc = upload_ids(s, st)) return rc;
   const SeekIO io = seek_io(s, d_bases, d_offsets, nreads);
   HIP_TRY(hipMemsetAsync(k.d_cnt, 0, (uint64_t)nreads * (2u * k.np + 1u) * 4, st)); // the batch's counters
   // the kernel chain of the index (see kr_index): wait for the previous batch's kernels, record behind ours
-  const kr_index* ixp = s->ix;
-  const DevIndex& dix = ixp->dix;
-  std::unique_lock<std::mutex> chain(ixp->chain_mu);
-  if (!ixp->chain_off && ixp->chain_n) HIP_TRY(hipStreamWaitEvent(st, ixp->chain_ev[(ixp->chain_n - 1) % kr_index::kChainEvents], 0));
+  const DevIndex& dix = s->ix->dix;
+  ChainLink chain(s->ix, st);
+  HIP_TRY(chain.opened);
   HIP_TRY(hipEventRecord(k.ev[0], st));
   const uint32_t nblk = (nreads + kRowBlock - 1) / kRowBlock, bgrid = std::min<uint32_t>(nblk, 4096u);
   hipLaunchKernelGGL(kr_seek_count_kernel, dim3(bgrid), dim3(256), 0, st, io, dix.k);
@@ -85,51 +71,31 @@ static int seek_queue(kr_stream* s, const uint8_t* bases, const uint64_t* offset
     hipLaunchKernelGGL(kr_seek_solve_kernel<NPV>, dim3(sgrid), dim3(256), 0, st, s->llh, dix, io);
   }, s->llh.th == 4);
   HIP_TRY(hipEventRecord(k.ev[2], st));
-  if (tx.req) {
-    TextIO t{tx.d_ids, tx.d_id_off, tx.id_sep, nullptr, nullptr, tx.d_tlen, tx.d_bsum, tx.d_text, tx.text_cap, tx.d_total};
+  if (b.has_ids()) {
+    TextIO t{tx.d_ids, tx.d_id_off, b.from.id_sep, nullptr, nullptr, tx.d_tlen, tx.d_bsum, tx.d_text, tx.text_cap, tx.d_total};
     HIP_TRY(hipMemsetAsync(tx.d_total, 0, 16, st));
     hipLaunchKernelGGL(kr_seek_text_len_kernel, dim3(std::min<uint32_t>(nblk, 8192u)), dim3(256), 0, st, io, t);
     hipLaunchKernelGGL(kr_text_bscan_kernel, dim3(1), dim3(1024), 0, st, t.t_bsum, nblk, t.text_cap, t.total);
     hipLaunchKernelGGL(kr_seek_text_write_kernel, dim3(std::min<uint32_t>(nblk, 8192u)), dim3(256), 0, st, io, t);
     HIP_TRY(hipMemcpyAsync(tx.h_total, tx.d_total, 16, hipMemcpyDeviceToHost, st));
-    tx.made = true;
+    s->batch.text_made = true;
   }
   HIP_TRY(hipEventRecord(k.ev[3], st));
   k.timed = true;
-  if (!ixp->chain_off) {
-    hipEvent_t& ce = ixp->chain_ev[ixp->chain_n % kr_index::kChainEvents];
-    if (!ce) HIP_TRY(hipEventCreateWithFlags(&ce, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(ce, st));
-    ++ixp->chain_n;
-  }
-  chain.unlock();
+  HIP_TRY(chain.close(st));
   HIP_TRY(hipGetLastError());
   return KR_OK;
 }
 
 // (the arguments were checked by the caller: submit_batch, or the raw-bytes submits behind their record finder)
-static int seek_submit(kr_stream* s, const uint8_t* bases, const uint64_t* offsets, uint32_t nreads, uint32_t flags)
+static int seek_submit(kr_stream* s, const uint8_t* bases, const uint64_t* offsets, uint32_t nreads, uint32_t flags, const BatchOrigin& from)
 {
   HIP_TRY(hipSetDevice(s->ix->device));
   (void)hipGetLastError(); // a stale error of an earlier, unrelated call on this thread is not this batch's
-  if (s->submitted && !s->waited)
-    for (uint32_t l = 0; l < s->nlanes; ++l) HIP_TRY(hipStreamSynchronize(s->lanes[l].stream));
-  s->nreads = nreads, s->flags = flags;
-  s->submitted = true, s->waited = false, s->collected = false;
-  s->batch_rc = KR_OK;
-  s->sub_bases = bases, s->sub_offsets = offsets;
-  s->tiles.active = false, s->rows_mode = false, s->rows_indexed = false;
-  s->text.made = false;
-  s->nlanes = 1, s->nrecs = 0, s->nhits = 0, s->ndist = 0;
-  s->seek.active = true, s->seek.have_view = false;
-  const int rc = seek_queue(s, bases, offsets, nreads, flags);
-  if (rc) { // what was queued runs to its end; every later wait / collect reports this error until the next submit
-    const std::string msg = kr_last_error();
-    if (s->lanes[0].stream) (void)hipStreamSynchronize(s->lanes[0].stream);
-    (void)hipGetLastError();
-    s->nlanes = 0, s->waited = true, s->batch_rc = rc, s->batch_msg = msg;
-    return kr::fail(rc, msg);
-  }
+  if (int rc = drain_batch(s)) return rc;
+  Batch& b = begin_batch(s, bases, offsets, nreads, flags, from);
+  b.seek = true, b.nlanes = 1;
+  if (int rc = seek_queue(s, bases, offsets, nreads, flags)) return fail_submit(s, rc, 1);
   return KR_OK;
 }
 
@@ -137,7 +103,7 @@ static int seek_wait(kr_stream* s)
 {
   HIP_TRY(hipSetDevice(s->ix->device));
   HIP_TRY(hipStreamSynchronize(s->lanes[0].stream));
-  s->waited = true;
+  s->batch.waited = true;
   return KR_OK;
 }
 
@@ -174,23 +140,23 @@ int kr_batch_collect_seek(kr_stream* s, kr_seek_view* out)
   kr::clear_error();
   if (!s || !out) return kr::fail(KR_ERR_ARG, "kr_batch_collect_seek: null argument");
   if (!s->seek.on) return kr::fail(KR_ERR_STATE, "kr_batch_collect_seek: kr_stream_seek_enable first");
-  if (!s->submitted || !s->seek.active) return kr::fail(KR_ERR_STATE, "kr_batch_collect_seek: the last batch was not submitted with KR_SEEK");
+  if (!s->batch.submitted || !s->batch.seek) return kr::fail(KR_ERR_STATE, "kr_batch_collect_seek: the last batch was not submitted with KR_SEEK");
   const int rc = kr_batch_wait(s);
   if (rc) return rc;
   kr_stream::Seek& k = s->seek;
-  const uint64_t n = s->nreads;
-  if (!k.have_view) {
+  const uint64_t n = s->batch.nreads;
+  if (!s->batch.seek_view) {
     HIP_TRY(hipSetDevice(s->ix->device));
     hipStream_t st = s->lanes[0].stream;
     HIP_TRY(hipMemcpyAsync(k.h_cnt, k.d_cnt, n * (2u * k.np + 1u) * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(k.h_d, k.d_d, 3 * n * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    k.have_view = true;
+    s->batch.seek_view = true;
   }
-  out->nreads = s->nreads, out->np = k.np;
+  out->nreads = s->batch.nreads, out->np = k.np;
   out->d = k.h_d, out->d_strand = k.h_d + n;
   out->hist = k.h_cnt, out->onmers = k.h_cnt + n * 2u * k.np;
-  s->collected = true;
+  s->batch.collected = true;
   return KR_OK;
 }
 

@@ -41,6 +41,48 @@ struct Lane {
   uint64_t host_off = 0;       // where the lane's records (rows) start in the compacted host arrays
 };
 
+// The batch in flight (docs/design/08, "The batch in flight").  BatchOrigin: what the caller of the internal submit knows about the
+// batch and hands in; the reruns of kr_batch_wait submit again from the record of the batch they rerun, one mode bit changed.
+enum IdSource : uint8_t { kIdsNone, kIdsHost, kIdsDevice }; // no ids; staged in text.h_ids by kr_batch_submit_text; written into text.d_ids by a record finder
+struct BatchOrigin {
+  IdSource ids = kIdsNone;
+  uint64_t id_bytes = 0;
+  uint32_t id_sep = 0;
+  bool parsed = false;    // a record finder produced the batch (kr_batch_submit_fastq / _fasta / _bgzf): bases, offsets and names are the device's
+  bool untiled = false;   // (rerun) a tiled batch that overflowed a device buffer: one wave per sequence this time
+  bool unindexed = false; // (rerun) an indexed batch whose list positions outgrew dist_list: KR_ROWS_INDEXED is ignored this time
+};
+// Everything that is true of the batch in flight and of nothing else.  begin_batch assigns a fresh one: what nobody sets is at its default
+struct Batch {
+  bool submitted = false, waited = false, collected = false;
+  int rc = 0; // result of the batch, returned by every wait / collect until the next submit (errors are sticky)
+  std::string msg;
+  const uint8_t* bases = nullptr; // the arguments of the submit (host buffers stay valid until wait / collect returns)
+  const uint64_t* offsets = nullptr;
+  uint32_t nreads = 0, flags = 0;
+  BatchOrigin from;
+  uint32_t nlanes = 0;
+  bool tiled = false;           // submitted as tiles: `nreads` real reads, `nv` reads on the device, `nlong` long sequences among them
+  bool tiles_on_device = false; // ... and the Tiles' d_ arrays were filled by the kr_tile_lay_* kernels (no h_ array holds anything of it)
+  uint32_t nv = 0, nlong = 0;
+  bool rows_mode = false;    // leaves the device as compact rows (KR_ROWS_ONLY, no taps; tiled: with KR_TILE_ROWS)
+  bool rows_indexed = false; // ... of 8 bytes: (key, index into the batch's distinct DIST values) -- KR_ROWS_INDEXED
+  bool text_made = false;    // submitted with ids, and its text kernels were queued
+  bool seek = false;         // a seek batch (kr_host_seek.inc)
+  bool seek_view = false;    // ... whose values are in the page-locked mirrors
+  uint32_t nrecs = 0;
+  uint64_t nhits = 0;
+  uint64_t ndist = 0, h_ndist = 0; // entries of the batch's list of distinct values (set by kr_batch_wait: a device view shows it too), of its host copy
+  bool has_ids() const { return from.ids != kIdsNone; }
+};
+// The last call of a record finder on the stream: not every one queues a batch (zero bytes, zero accepted records, a rejected BGZF
+// member), and its names can be asked for either way.  A batch that no record finder produced ends it.
+struct LastParse {
+  bool parsed = false;     // the last submit on the stream was kr_batch_submit_fastq / _fasta / _bgzf: its names can be asked for
+  bool have_names = false; // ... and they are in Fastq::name_pos / h_nlen
+  uint32_t nreads = 0;
+};
+
 struct kr_stream {
   const kr_index* ix = nullptr;
   int device = 0; // copy of ix->device: destroying a stream must not read an index that may already be gone
@@ -52,7 +94,7 @@ struct kr_stream {
   uint32_t rec_cap = 0, hit_cap = 0, item_cap = 0;
   uint64_t rec_user_cap = 0; // the caller's max_records (rec_cap adds per-wave chunk slack per lane)
   uint32_t nwaves = 0, nwaves_full = 0, nwaves_lean = 0, nwaves_lean2 = 0; // per-wave scratch slots; grids of the accumulate launches
-  uint32_t max_lanes = 1, nlanes = 1;  // lanes created / lanes of the current batch
+  uint32_t max_lanes = 1; // lanes created (of the batch in flight: Batch::nlanes)
   uint32_t lane_min_reads = 1u << 16;
   bool lanes_for_device_input = false;
   Lane lanes[kMaxLanes];
@@ -135,9 +177,6 @@ struct kr_stream {
   // Long sequences across waves (kr_dev_tiles.inc): a host batch with sequences of more than kTileMinPos k-mer positions
   // is submitted as a batch of tiles, and so is a batch in HBM submitted with KR_TILE_DEVICE.  Buffers are made on first use.
   struct Tiles {
-    bool active = false;   // the batch in flight is tiled: `nreads` real reads, `nv` reads on the device
-    bool on_device = false; // ... and the d_ arrays were filled by the kr_tile_lay_* kernels (no h_ array holds anything of it)
-    uint32_t nv = 0, nlong = 0;
     PinBuf<uint8_t> h_bases; // the tiled batch's bases (tiles overlap by k - 1); one capacity with d_bases
     DevBuf<uint8_t> d_bases;
     PinBuf<uint64_t> h_voff; // [max_reads + 1]
@@ -155,7 +194,6 @@ struct kr_stream {
     DevBuf<uint64_t> d_vsrc, d_bsum, d_sum;
     PinBuf<uint64_t> h_sum;
   } tiles;
-  bool no_tiles = false;   // (a tiled batch that overflowed a device buffer is run again untiled)
   std::vector<uint8_t> tile_choice; // per read of the batch in hand: submitted as tiles
   uint32_t tile_min_pos = kTileMinPos; // (KR_TILE_MIN_POS: experiments)
   std::vector<hipStream_t> moved_streams; // (kr_debug_stream_move: lane 0's earlier streams, destroyed with the stream)
@@ -174,26 +212,20 @@ struct kr_stream {
   // report text written on the device (kr_dev_text.inc; kr_stream_text_enable)
   struct Text {
     bool on = false;   // buffers exist
-    bool req = false;  // the batch in flight was submitted with ids (kr_batch_submit_text)
-    bool made = false; // ... and its text kernels were queued (a rows-mode batch)
     char *d_ids = nullptr, *h_ids = nullptr;
     uint32_t *d_id_off = nullptr, *h_id_off = nullptr;
     uint64_t id_cap = 0;
-    uint32_t id_sep = 0;
     uint32_t* d_tlen = nullptr;
     uint64_t *d_bsum = nullptr, *d_total = nullptr, *h_total = nullptr;
     char* d_text = nullptr;
     PinBuf<char> h_text; // (made by the first batch that needs it, as large as that batch's text asks)
-    uint64_t text_cap = 0, id_bytes = 0;
-    bool ids_on_device = false; // the batch's ids were written into d_ids / d_id_off by the record finder (kr_batch_submit_fastq)
+    uint64_t text_cap = 0;
     bool seek_only = false;     // the buffers were made by kr_stream_seek_enable: no node names are uploaded, `dist` text is not served
   } text;
   // `seek` on kernels of its own (kr_dev_seek.inc, kr_host_seek.inc; kr_stream_seek_enable).  A seek batch runs as one lane and uses
   // none of the item list, the record slots or the accumulate scratch
   struct Seek {
     bool on = false;
-    bool active = false;    // the batch in flight (or the last one) is a seek batch
-    bool have_view = false; // ... and its values are in the page-locked mirrors
     uint32_t np = 0;
     uint32_t *d_first = nullptr, *d_bsum = nullptr; // [max_reads + 1], [max_reads / kRowBlock + 2]
     uint32_t* d_cnt = nullptr;                      // a batch's hist [nreads * 2 * np], then its onmers [nreads]
@@ -213,9 +245,6 @@ struct kr_stream {
     uint64_t *d_bsum_b = nullptr, *d_bsum_n = nullptr;
     unsigned long long* d_ctl = nullptr;
     kr_fastq_parse *d_sum = nullptr, *h_sum = nullptr;
-    bool parsed = false;              // the last submit on the stream was kr_batch_submit_fastq: its names can be asked for
-    bool have_names = false;          // ... and they are in name_pos / h_nlen
-    uint32_t nreads = 0;
     uint32_t *h_npos = nullptr, *h_nlen = nullptr;
     std::vector<uint64_t> name_pos;
     hipEvent_t ev_parse0 = nullptr, ev_parse1 = nullptr; // kr_debug_fastq_parse_ms: around the record finder's kernels, once asked for
@@ -239,29 +268,19 @@ struct kr_stream {
     hipEvent_t ev0 = nullptr, ev1 = nullptr; // kr_debug_bgzf_ms: around the inflate kernel, once asked for
     bool ev_set = false;
   } bgzf;
-  const uint8_t* sub_bases = nullptr; // the arguments of the submit in flight (host buffers stay valid until wait / collect returns)
-  const uint64_t* sub_offsets = nullptr;
+  Batch batch;     // the batch in flight
+  LastParse parse; // the last record finder's call
   // state
   bool h_rec_full = false; // the pinned record buffers hold v / chisq / hist only once a batch asked for them
-  bool rows_mode = false;  // the batch in flight leaves the device as compact rows (KR_ROWS_ONLY, no taps; tiled: with KR_TILE_ROWS)
-  bool rows_indexed = false; // ... of 8 bytes: (key, index into the batch's distinct DIST values) -- KR_ROWS_INDEXED
   PinBuf<uint32_t> h_rec_dix; // of h_rec_key's size, allocated with the first indexed batch
   PinBuf<double> h_dist_list;
-  uint64_t ndist = 0;        // entries of the batch's list (set by kr_batch_wait: a device view shows it too), h_ndist: of its host copy
-  uint64_t h_ndist = 0;
-  bool no_indexed = false;   // (an indexed batch whose list positions outgrew dist_list is run again with rec_d)
   uint64_t ix_extent = 0, ix_fallbacks = 0; // kr_debug_indexed_list: list positions of the last indexed launch, reruns so far
   uint64_t d2h_bytes = 0;    // what the last kr_batch_collect copied back
   uint64_t h_sel_ones = 0; // leading entries of h_rec_sel known to hold 1 (rows-mode views: every row is selected)
-  bool submitted = false, waited = false, collected = false;
-  int batch_rc = 0; // result of the batch, returned by every wait / collect until the next submit (errors are sticky)
-  std::string batch_msg;
-  uint32_t nreads = 0, flags = 0, nrecs = 0;
   uint32_t scan_blocks = 0, scan_pipe_blocks = 0, scan_filt_blocks = 0;
   bool scan_pipe = true; // slotted tables: the pipelined scan kernel (KR_SCAN_PIPE=0 when the stream was made: the one-group-at-a-time kernel)
   uint32_t item_cap_dbg = 0; // (tests) KR_DEBUG_ITEM_CAP when the stream was made: item slots a lane's scan is told its list holds (0: all of them)
   bool fk = false; // the index has filter slots (format 9) and this stream's threshold fits their candidates: kr_scan_filt_kernel_t + FK accumulate
-  uint64_t nhits = 0;
 };
 
 namespace {
@@ -326,22 +345,23 @@ int check_errflags(uint32_t e)
   return KR_OK;
 }
 
-// The device's view of the batch's per-read results: the stream's arrays, or for a tiled batch the real reads' (kr_tile_gather_kernel)
-BatchOut result_out(const kr_stream* s)
+// The device's view of the batch's per-read results: the arrays of `o` (the stream's, or a lane's), or for a tiled batch the real
+// reads' (kr_tile_gather_kernel), their row ranges included
+BatchOut result_out(const kr_stream* s, BatchOut o)
 {
-  BatchOut o = s->out;
-  if (s->tiles.active) {
+  if (s->batch.tiled) {
     const kr_stream::Tiles& t = s->tiles;
     o.rd_off = t.d_real_off.get(), o.rd_cnt = t.d_real_cnt.get(), o.rd_onmers = t.d_real_onmers.get(), o.rd_filt = t.d_real_filt.get(), o.rd_na = t.d_real_na.get();
+    o.rd_roff = t.d_real_roff.get(), o.rd_rcnt = t.d_real_rcnt.get();
   }
   return o;
 }
 
-// Does this host batch hold long sequences, and does its tiled form fit the stream?  Fills the tiled batch (bases with the
+// Does this host batch hold long sequences, and does its tiled form fit the stream?  Then the batch in flight is tiled
+// (Batch::tiled, nv, nlong).  Fills the tiled batch (bases with the
 // k - 1 overlaps, offsets, tile flags, first tile of every real read, list of long sequences) into the pinned buffers.
-int build_tiles(kr_stream* s, const uint8_t* bases, const uint64_t* offsets, uint32_t nreads, bool* tiled)
+int build_tiles(kr_stream* s, const uint8_t* bases, const uint64_t* offsets, uint32_t nreads)
 {
-  *tiled = false;
   const uint32_t k = s->ix->dix.k;
   // a long sequence of nt tiles takes nt - 1 reads more than the batch has: as many sequences as the stream has reads for
   // are tiled (in order), the others stay one wave's work each
@@ -398,17 +418,15 @@ int build_tiles(kr_stream* s, const uint8_t* bases, const uint64_t* offsets, uin
     }
   }
   h_voff[v] = pos;
-  t.nv = (uint32_t)v, t.nlong = nlong, t.on_device = false;
-  *tiled = true;
+  s->batch.nv = (uint32_t)v, s->batch.nlong = nlong, s->batch.tiled = true;
   return KR_OK;
 }
 
 // The same for a batch whose bases and offsets are in HBM (KR_TILE_DEVICE): the kr_tile_lay_* kernels fill the device arrays on
 // lane 0's stream, and the call waits for their summary {nv, nlong, bases} -- the tiled bases need room before they are copied, and
 // a batch without a long sequence is submitted as it is.  Sequences are chosen by a prefix rule (kr_dev_tiles.inc).
-int build_tiles_device(kr_stream* s, const uint8_t* bases, const uint64_t* offsets, uint32_t nreads, bool* tiled)
+int build_tiles_device(kr_stream* s, const uint8_t* bases, const uint64_t* offsets, uint32_t nreads)
 {
-  *tiled = false;
   kr_stream::Tiles& t = s->tiles;
   HIP_TRY(hipSetDevice(s->device));
   const uint64_t c = s->max_reads;
@@ -450,8 +468,7 @@ int build_tiles_device(kr_stream* s, const uint8_t* bases, const uint64_t* offse
   io.dst = t.d_bases.get();
   hipLaunchKernelGGL(kr_tile_lay_copy_kernel, dim3((uint32_t)std::min<uint64_t>((nv + 3) / 4, 16384u)), dim3(256), 0, st, io);
   HIP_TRY(hipGetLastError());
-  t.nv = (uint32_t)nv, t.nlong = (uint32_t)nlong, t.on_device = true;
-  *tiled = true;
+  s->batch.nv = (uint32_t)nv, s->batch.nlong = (uint32_t)nlong, s->batch.tiled = s->batch.tiles_on_device = true;
   return KR_OK;
 }
 
@@ -491,9 +508,10 @@ void with_scan_shape(uint32_t slot_log2w, uint32_t log_g, F&& f)
 TileBatch tile_batch(const kr_stream* s)
 {
   const kr_stream::Tiles& tl = s->tiles;
-  return TileBatch{tl.d_vtile.get(), tl.d_longs.get(), tl.d_rfirst.get(), tl.d_tile_filt.get(), tl.nv, tl.nlong, s->nreads,
+  const Batch& b = s->batch;
+  return TileBatch{tl.d_vtile.get(), tl.d_longs.get(), tl.d_rfirst.get(), tl.d_tile_filt.get(), b.nv, b.nlong, b.nreads,
                    tl.d_real_off.get(), tl.d_real_cnt.get(), tl.d_real_onmers.get(), tl.d_real_filt.get(), tl.d_real_na.get(),
-                   s->rows_mode ? tl.d_real_roff.get() : nullptr, s->rows_mode ? tl.d_real_rcnt.get() : nullptr};
+                   b.rows_mode ? tl.d_real_roff.get() : nullptr, b.rows_mode ? tl.d_real_rcnt.get() : nullptr};
 }
 
 // The stages of a lane's batch, each queued on the lane's stream (everything a stage needs is in L.in / L.out); launch_lane calls
@@ -530,10 +548,10 @@ void launch_accumulate(kr_stream* s, Lane& L, bool single)
   const DevIndex& dix = s->ix->dix;
   BatchOut& o = L.out;
   const uint32_t nreads = L.nreads;
-  const kr_stream::Tiles& tl = s->tiles;
+  const Batch& b = s->batch;
   const TileBatch tb = tile_batch(s);
-  if (tl.active) // the tiles' hdist_filt moved aside: their keys are judged by the sequence's, in kr_tile_merge_kernel
-    hipLaunchKernelGGL(kr_tile_filt_kernel, dim3(std::min<uint32_t>((tl.nv + 255) / 256, 4096u)), dim3(256), 0, st, o, tb);
+  if (b.tiled) // the tiles' hdist_filt moved aside: their keys are judged by the sequence's, in kr_tile_merge_kernel
+    hipLaunchKernelGGL(kr_tile_filt_kernel, dim3(std::min<uint32_t>((b.nv + 255) / 256, 4096u)), dim3(256), 0, st, o, tb);
   const uint32_t lds = probe_lds_bytes(s->dp.np, o.bm_words), lds_lean = probe_lds_bytes(s->dp.np, o.bm_words, true);
   const uint32_t lds_lean2 = probe_lds_bytes(s->dp.np, o.bm_words, true, 2);
   static const bool no_lean2 = getenv("KR_DEBUG_NO_LEAN2") != nullptr; // (experiments: two-segment reads through the merge instantiation, as before round 3)
@@ -547,13 +565,13 @@ void launch_accumulate(kr_stream* s, Lane& L, bool single)
       hipLaunchKernelGGL((kr_acc_kernel_t<SL.value, NPV, false, 8, FK.value>), dim3(grid_lean2), dim3(kWave), lds_lean2, st, dix, s->dp, L.in, o);
     hipLaunchKernelGGL((kr_acc_kernel_t<SL.value, NPV, true, 7, FK.value>), dim3(grid_full), dim3(kWave), lds, st, dix, s->dp, L.in, o);
   }, single, np5, s->fk);
-  if (tl.active) { // the tiles' histograms added per key, the sequence's records at its first tile
-    const uint32_t W = std::min<uint32_t>(32u, s->nwaves / std::max<uint32_t>(1u, tl.nlong)); // adding waves per sequence
-    if (W >= 2 && tl.nlong <= s->nwaves) { // few long sequences: the adding spread over W waves each, then a wave per sequence emits
-      hipLaunchKernelGGL(kr_tile_add_kernel, dim3(tl.nlong * W), dim3(kWave), 0, st, dix, s->dp, o, tb, W);
-      hipLaunchKernelGGL(kr_tile_merge_kernel<true>, dim3(tl.nlong), dim3(kWave), (o.bm_words * 4u + 15u) & ~15u, st, dix, s->dp, o, tb);
+  if (b.tiled) { // the tiles' histograms added per key, the sequence's records at its first tile
+    const uint32_t W = std::min<uint32_t>(32u, s->nwaves / std::max<uint32_t>(1u, b.nlong)); // adding waves per sequence
+    if (W >= 2 && b.nlong <= s->nwaves) { // few long sequences: the adding spread over W waves each, then a wave per sequence emits
+      hipLaunchKernelGGL(kr_tile_add_kernel, dim3(b.nlong * W), dim3(kWave), 0, st, dix, s->dp, o, tb, W);
+      hipLaunchKernelGGL(kr_tile_merge_kernel<true>, dim3(b.nlong), dim3(kWave), (o.bm_words * 4u + 15u) & ~15u, st, dix, s->dp, o, tb);
     } else { // many: a wave per sequence does both
-      hipLaunchKernelGGL(kr_tile_merge_kernel<false>, dim3(std::min<uint32_t>(tl.nlong, s->nwaves)), dim3(kWave), (o.bm_words * 4u + 15u) & ~15u, st,
+      hipLaunchKernelGGL(kr_tile_merge_kernel<false>, dim3(std::min<uint32_t>(b.nlong, s->nwaves)), dim3(kWave), (o.bm_words * 4u + 15u) & ~15u, st,
                          dix, s->dp, o, tb);
     }
   }
@@ -626,26 +644,26 @@ int launch_text(kr_stream* s, Lane& L)
   hipStream_t st = L.stream;
   BatchOut o = L.out;
   uint32_t nreads = L.nreads;
-  if (s->tiles.active) {
+  if (s->batch.tiled) {
     const kr_stream::Tiles& tl = s->tiles;
     o.rd_roff = tl.d_real_roff.get(), o.rd_rcnt = tl.d_real_rcnt.get(), o.rd_na = tl.d_real_na.get();
-    nreads = s->nreads;
+    nreads = s->batch.nreads;
   }
   const uint32_t nblk = (nreads + kRowBlock - 1) / kRowBlock;
   kr_stream::Text& tx = s->text;
-  TextIO t{tx.d_ids, tx.d_id_off, tx.id_sep, s->ix->d_names.get(), s->ix->d_name_off.get(), tx.d_tlen, tx.d_bsum, tx.d_text, tx.text_cap, tx.d_total};
+  TextIO t{tx.d_ids, tx.d_id_off, s->batch.from.id_sep, s->ix->d_names.get(), s->ix->d_name_off.get(), tx.d_tlen, tx.d_bsum, tx.d_text, tx.text_cap, tx.d_total};
   HIP_TRY(hipMemsetAsync(tx.d_total, 0, 16, st));
   hipLaunchKernelGGL(kr_text_len_kernel, dim3(std::min<uint32_t>(nblk, 8192u)), dim3(256), 0, st, o, t, nreads);
   hipLaunchKernelGGL(kr_text_bscan_kernel, dim3(1), dim3(1024), 0, st, t.t_bsum, nblk, t.text_cap, t.total);
   hipLaunchKernelGGL(kr_text_write_kernel, dim3(std::min<uint32_t>(nblk, 8192u)), dim3(256), 0, st, o, t, nreads);
   HIP_TRY(hipMemcpyAsync(tx.h_total, tx.d_total, 16, hipMemcpyDeviceToHost, st));
-  tx.made = true;
+  s->batch.text_made = true;
   return KR_OK;
 }
 
 void launch_gather(kr_stream* s, Lane& L)
 { // (tiled batches) per-read results of the real reads, for the views, the copies back, the text kernels and `place`
-  hipLaunchKernelGGL(kr_tile_gather_kernel, dim3(std::min<uint32_t>((s->nreads + 255) / 256, 4096u)), dim3(256), 0, L.stream, L.out, tile_batch(s));
+  hipLaunchKernelGGL(kr_tile_gather_kernel, dim3(std::min<uint32_t>((s->batch.nreads + 255) / 256, 4096u)), dim3(256), 0, L.stream, L.out, tile_batch(s));
 }
 
 void launch_rebase(kr_stream* s, Lane& L)
@@ -656,17 +674,20 @@ void launch_rebase(kr_stream* s, Lane& L)
     hipLaunchKernelGGL(kr_rebase_kernel, dim3(std::min<uint32_t>((L.nreads + 255) / 256, 1024u)), dim3(256), 0, st, o.rd_off, o.rd_cnt, L.nreads, L.rec_base);
 }
 
-// How a batch submitted with `flags` in P lanes leaves the device (kr_stream::rows_mode / rows_indexed)
-void set_row_modes(kr_stream* s, uint32_t flags, uint32_t P)
+// The batch in flight runs in P lanes: how it leaves the device (Batch::rows_mode / rows_indexed)
+void set_lanes_and_row_modes(kr_stream* s, uint32_t P)
 {
+  Batch& b = s->batch;
+  const uint32_t flags = b.flags;
+  b.nlanes = P;
   // (a tiled batch keeps its record slots unless the caller asks for rows with KR_TILE_ROWS)
-  s->rows_mode = (flags & KR_ROWS_ONLY) && !(flags & (KR_TAP_ACCS | KR_TAP_HITS)) && (!s->tiles.active || (flags & KR_TILE_ROWS)) && !getenv("KR_NO_ROW_COMPACTION");
+  b.rows_mode = (flags & KR_ROWS_ONLY) && !(flags & (KR_TAP_ACCS | KR_TAP_HITS)) && (!b.tiled || (flags & KR_TILE_ROWS)) && !getenv("KR_NO_ROW_COMPACTION");
   // KR_ROWS_INDEXED: 8-byte rows (key, position of DIST in the batch's distinct values).  One lane (a lane's positions are its own),
   // not tiled, no --filter (its select kernel writes rec_v, which the list of values aliases), no device text (its kernels read row_d)
-  // (no_indexed: this is the rerun of a batch whose list positions outgrew dist_list)
-  s->rows_indexed = s->rows_mode && (flags & KR_ROWS_INDEXED) && P == 1 && !s->tiles.active && !(!s->dp.no_filter && s->dp.multi) && !s->text.req && !s->no_indexed;
+  // (unindexed: this is the rerun of a batch whose list positions outgrew dist_list)
+  b.rows_indexed = b.rows_mode && (flags & KR_ROWS_INDEXED) && P == 1 && !b.tiled && !(!s->dp.no_filter && s->dp.multi) && !b.has_ids() && !b.from.unindexed;
 }
-// Lane l's view of the output for a batch submitted with `flags` (set_row_modes has run): private scratch + slices of the stream's
+// Lane l's view of the output for a batch submitted with `flags` (set_lanes_and_row_modes has run): private scratch + slices of the stream's
 // arrays, the lane's reads starting at r0.  One function for kr_batch_submit and kr_debug_select: the aliases of the row arrays
 // (rec_rep / rep_dv, indexed: rec_d / rec_v) exist once.
 void set_lane_view(kr_stream* s, Lane& L, uint32_t l, uint32_t r0, uint32_t flags, uint32_t lane_rec_cap, uint32_t lane_item_cap, uint32_t lane_item_room,
@@ -690,12 +711,12 @@ void set_lane_view(kr_stream* s, Lane& L, uint32_t l, uint32_t r0, uint32_t flag
   o.dist_cap = list_caps.lower(lane_rec_cap, list_caps.dist);
   o.keep_v = ((flags & KR_ROWS_ONLY) && !(flags & KR_TAP_ACCS)) ? 0u : 1u;
   o.hist_always = (flags & KR_TAP_ACCS) ? 1u : 0u; // else a record's planes exist only where its packed word cannot describe it
-  o.v_tile = s->tiles.active ? s->tiles.d_vtile.get() : nullptr;
-  o.rows_mode = s->rows_mode ? 1u : 0u;
+  o.v_tile = s->batch.tiled ? s->tiles.d_vtile.get() : nullptr;
+  o.rows_mode = s->batch.rows_mode ? 1u : 0u;
   o.rd_rcnt += r0, o.rd_roff += r0, o.row_bsum += r0 / kRowBlock + 2ull * l;
   o.row_key = o.rec_rep, o.row_d = reinterpret_cast<double*>(o.rep_dv); // (the lane's slices: dead once the select kernel has run)
-  o.rows_indexed = s->rows_indexed ? 1u : 0u;
-  if (s->rows_indexed) // (see BatchOut: the row kernel reads rec_rep here, so its output lies in rec_d; the values in rec_v)
+  o.rows_indexed = s->batch.rows_indexed ? 1u : 0u;
+  if (s->batch.rows_indexed) // (see BatchOut: the row kernel reads rec_rep here, so its output lies in rec_d; the values in rec_v)
     o.row_key = reinterpret_cast<uint32_t*>(o.rec_d), o.row_dix = o.row_key + lane_rec_cap, o.dist_list = o.rec_v;
 }
 
@@ -716,8 +737,8 @@ int launch_lane(kr_stream* s, Lane& L, uint32_t flags)
   HIP_TRY(hipMemsetAsync(o.rec_sel, 0, (uint64_t)o.rec_cap, st));
   // the kernel chain of the index (see kr_index): wait for the previous batch's kernels, record behind ours
   const kr_index* ixp = s->ix;
-  std::unique_lock<std::mutex> chain(ixp->chain_mu);
-  if (!ixp->chain_off && ixp->chain_n) HIP_TRY(hipStreamWaitEvent(st, ixp->chain_ev[(ixp->chain_n - 1) % kr_index::kChainEvents], 0));
+  ChainLink chain(ixp, st);
+  HIP_TRY(chain.opened);
   HIP_TRY(hipEventRecord(L.ev[kEvFirstKernel], st));
   const bool single = ixp->dix.nlibs == 1 && ixp->dix.m <= 64;
   launch_scan(s, L, single, (flags & KR_TAP_HITS) != 0);
@@ -730,20 +751,82 @@ int launch_lane(kr_stream* s, Lane& L, uint32_t flags)
   launch_select(s, L);
   // (an untiled batch: rows, text, rebase as ever; a tiled one gathers the real reads' results between its rows and its text)
   if (o.rows_mode) launch_rows(s, L);
-  if (s->tiles.active) launch_gather(s, L);
-  if (o.rows_mode && s->text.req)
+  if (s->batch.tiled) launch_gather(s, L);
+  if (o.rows_mode && s->batch.has_ids())
     if (int rc = launch_text(s, L)) return rc;
   launch_rebase(s, L);
   HIP_TRY(hipEventRecord(L.ev[kEvLastKernel], st));
-  if (!ixp->chain_off) {
-    hipEvent_t& ce = ixp->chain_ev[ixp->chain_n % kr_index::kChainEvents];
-    if (!ce) HIP_TRY(hipEventCreateWithFlags(&ce, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(ce, st));
-    ++ixp->chain_n;
-  }
-  chain.unlock();
+  HIP_TRY(chain.close(st));
   HIP_TRY(hipMemcpyAsync(L.h_counters, o.counters, kCounterWords * 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipGetLastError());
+  return KR_OK;
+}
+
+// ---- the steps every way into the stream shares ----
+
+// Wait for the batch in flight: the staging buffers (bases, offsets, ids, the record finders' chunk) are about to be overwritten.
+// The batch stays waitable and collectable as it was
+int drain_batch(kr_stream* s)
+{
+  if (s->batch.submitted && !s->batch.waited)
+    for (uint32_t l = 0; l < s->batch.nlanes; ++l) HIP_TRY(hipStreamSynchronize(s->lanes[l].stream));
+  return KR_OK;
+}
+
+// A new batch begins here and nowhere else: a fresh record, then what its submit knows.  (`queued` is false for the crafted batch of
+// kr_debug_select, which there is nothing to wait for.)  A batch that no record finder produced ends the last parse
+Batch& begin_batch(kr_stream* s, const uint8_t* bases, const uint64_t* offsets, uint32_t nreads, uint32_t flags, const BatchOrigin& from, bool queued = true)
+{
+  s->batch = Batch{};
+  Batch& b = s->batch;
+  b.submitted = queued;
+  b.bases = bases, b.offsets = offsets, b.nreads = nreads, b.flags = flags, b.from = from;
+  if (!from.parsed) s->parse = LastParse{};
+  return b;
+}
+
+// A submit failed with `rc` (kr_last_error() says why) after work was queued on lanes 0 .. queued_lanes - 1: what was queued runs to
+// its end (or fails with the same device error), nothing of this batch is handed out, and every later wait / collect on the stream
+// reports this error until the next submit.  queued_lanes == 0: nothing is on the device yet, nothing is waited for
+int fail_submit(kr_stream* s, int rc, uint32_t queued_lanes)
+{
+  const std::string msg = kr_last_error();
+  for (uint32_t j = 0; j < queued_lanes; ++j)
+    if (s->lanes[j].stream) (void)hipStreamSynchronize(s->lanes[j].stream);
+  if (queued_lanes) (void)hipGetLastError();
+  Batch& b = s->batch;
+  b.nlanes = 0, b.nrecs = 0, b.nhits = 0;
+  b.waited = true;
+  b.rc = rc, b.msg = msg;
+  return kr::fail(rc, msg);
+}
+
+// Reads [r0, r1) of a host batch on their way to the device, queued on `st`: the bases land at the same offsets in d_bases as in the
+// caller's buffer (relative to offsets[0]), the offsets are rebased to the staging buffer and go to d_offsets + r0 + slot (every lane
+// has its own r1 - r0 + 1 entries).  KR_BASES_PINNED: the caller's buffers are page-locked, the bases are copied from where they are
+int stage_reads(kr_stream* s, hipStream_t st, const uint8_t* bases, const uint64_t* offsets, uint32_t r0, uint32_t r1, uint32_t slot, uint32_t flags)
+{
+  const uint64_t b0 = offsets[r0] - offsets[0], b1 = offsets[r1] - offsets[0];
+  const uint64_t* ho = s->h_offsets; // [nreads + 1], shared boundary entries are written with the same value
+  const uint8_t* src = bases + offsets[r0];
+  if (!(flags & KR_BASES_PINNED)) {
+    memcpy(s->h_bases + b0, src, b1 - b0);
+    src = s->h_bases + b0;
+  }
+  if ((flags & KR_BASES_PINNED) && offsets[0] == 0)
+    ho = offsets; // page-locked and already relative to the staging buffer: no host pass at all
+  else
+    for (uint32_t r = r0; r <= r1; ++r) s->h_offsets[r] = offsets[r] - offsets[0];
+  HIP_TRY(hipMemcpyAsync(s->d_bases + b0, src, b1 - b0, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(s->d_offsets + r0 + slot, ho + r0, ((uint64_t)(r1 - r0) + 1) * 8, hipMemcpyHostToDevice, st));
+  return KR_OK;
+}
+
+// The ids kr_batch_submit_text staged in page-locked memory, on their way to the device
+int upload_ids(kr_stream* s, hipStream_t st)
+{
+  HIP_TRY(hipMemcpyAsync(s->text.d_ids, s->text.h_ids, s->batch.from.id_bytes, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(s->text.d_id_off, s->text.h_id_off, ((uint64_t)s->batch.nreads + 1) * 4, hipMemcpyHostToDevice, st));
   return KR_OK;
 }
 
@@ -751,7 +834,7 @@ int launch_lane(kr_stream* s, Lane& L, uint32_t flags)
 
 // kr_host_seek.inc: a batch submitted with KR_SEEK leaves the dist chain here
 static int seek_check(const kr_stream* s, uint32_t flags, bool tile_ok, const char* who);
-static int seek_submit(kr_stream* s, const uint8_t* bases, const uint64_t* offsets, uint32_t nreads, uint32_t flags);
+static int seek_submit(kr_stream* s, const uint8_t* bases, const uint64_t* offsets, uint32_t nreads, uint32_t flags, const BatchOrigin& from);
 static int seek_wait(kr_stream* s);
 
 extern "C" {
@@ -990,11 +1073,10 @@ void kr_stream_destroy(kr_stream* s)
   delete s; // (every DevBuf / PinBuf of the stream frees itself here: the device is set, the lanes' streams have been waited for)
 }
 
-static int submit_batch(kr_stream* s, const uint8_t* bases, const uint64_t* offsets, uint32_t nreads, uint32_t flags);
+static int submit_batch(kr_stream* s, const uint8_t* bases, const uint64_t* offsets, uint32_t nreads, uint32_t flags, const BatchOrigin& from);
 int kr_batch_submit(kr_stream* s, const uint8_t* bases, const uint64_t* offsets, uint32_t nreads, uint32_t flags)
 {
-  if (s) s->text.req = false, s->fq.parsed = false;
-  return submit_batch(s, bases, offsets, nreads, flags);
+  return submit_batch(s, bases, offsets, nreads, flags, BatchOrigin{});
 }
 
 // ---- report text on the device (include/krepp_amd.h; kernels: kr_dev_text.inc) ----
@@ -1072,31 +1154,27 @@ int kr_batch_submit_text(kr_stream* s, const uint8_t* bases, const uint64_t* off
   const uint64_t nb = (uint64_t)id_off[nreads] - id_off[0];
   if (nb > s->text.id_cap) return kr::fail(KR_ERR_CAPACITY, "kr_batch_submit_text: the batch's ids exceed max_id_bytes: submit fewer reads per batch");
   HIP_TRY(hipSetDevice(s->ix->device));
-  if (s->submitted && !s->waited) // the staging buffers belong to the batch in flight
-    for (uint32_t l = 0; l < s->nlanes; ++l) HIP_TRY(hipStreamSynchronize(s->lanes[l].stream));
+  if (int rc = drain_batch(s)) return rc; // the staging buffers belong to the batch in flight
   kr_stream::Text& t = s->text;
   memcpy(t.h_ids, ids + id_off[0], nb);
   for (uint32_t r = 0; r <= nreads; ++r) {
     if (r && id_off[r] < id_off[r - 1] + id_sep) return kr::fail(KR_ERR_ARG, "kr_batch_submit_text: id offsets must ascend by at least id_sep");
     t.h_id_off[r] = id_off[r] - id_off[0];
   }
-  t.id_bytes = nb, t.id_sep = id_sep;
-  t.req = true, t.ids_on_device = false;
-  s->fq.parsed = false;
-  const int rc = submit_batch(s, bases, offsets, nreads, (flags & KR_SEEK) ? flags : flags | KR_ROWS_ONLY);
-  if (rc) t.req = false;
-  return rc;
+  BatchOrigin from;
+  from.ids = kIdsHost, from.id_bytes = nb, from.id_sep = id_sep;
+  return submit_batch(s, bases, offsets, nreads, (flags & KR_SEEK) ? flags : flags | KR_ROWS_ONLY, from);
 }
 
 int kr_batch_collect_text(kr_stream* s, const char** text, uint64_t* len)
 {
   kr::clear_error();
   if (!s || !text || !len) return kr::fail(KR_ERR_ARG, "kr_batch_collect_text: null argument");
-  if (!s->submitted || !s->text.req) return kr::fail(KR_ERR_STATE, "kr_batch_collect_text: no batch submitted with kr_batch_submit_text");
+  if (!s->batch.submitted || !s->batch.has_ids()) return kr::fail(KR_ERR_STATE, "kr_batch_collect_text: no batch submitted with kr_batch_submit_text");
   const int rc = kr_batch_wait(s);
   if (rc) return rc;
   kr_stream::Text& t = s->text;
-  if (!t.made) return kr::fail(KR_ERR_UNSUPPORTED, "kr_batch_collect_text: the batch left the device as record slots (long sequences; submit with KR_TILE_ROWS for device text): kr_batch_collect + kr_format_dist");
+  if (!s->batch.text_made) return kr::fail(KR_ERR_UNSUPPORTED, "kr_batch_collect_text: the batch left the device as record slots (long sequences; submit with KR_TILE_ROWS for device text): kr_batch_collect + kr_format_dist");
   if (t.h_total[1] & kTextOverCap) return kr::fail(KR_ERR_CAPACITY, "the batch's report text exceeds max_text_bytes: submit fewer reads per batch");
   if (t.h_total[1] & kTextBadNum) return kr::fail(KR_ERR_UNSUPPORTED, "kr_batch_collect_text: a DIST outside [0, 1000): kr_batch_collect + kr_format_dist");
   HIP_TRY(hipSetDevice(s->ix->device));
@@ -1111,7 +1189,7 @@ int kr_batch_collect_text(kr_stream* s, const char** text, uint64_t* len)
   return KR_OK;
 }
 
-static int submit_batch(kr_stream* s, const uint8_t* bases, const uint64_t* offsets, uint32_t nreads, uint32_t flags)
+static int submit_batch(kr_stream* s, const uint8_t* bases, const uint64_t* offsets, uint32_t nreads, uint32_t flags, const BatchOrigin& from)
 {
   kr::clear_error();
   if (!s || !bases || !offsets) return kr::fail(KR_ERR_ARG, "kr_batch_submit: null argument");
@@ -1121,52 +1199,27 @@ static int submit_batch(kr_stream* s, const uint8_t* bases, const uint64_t* offs
     return kr::fail(KR_ERR_ARG, "kr_batch_submit: more bases than the stream was created for");
   if (flags & KR_SEEK) {
     if (int rc = seek_check(s, flags, false, "kr_batch_submit")) return rc;
-    return seek_submit(s, bases, offsets, nreads, flags);
+    return seek_submit(s, bases, offsets, nreads, flags, from);
   }
-  s->seek.active = false;
   HIP_TRY(hipSetDevice(s->ix->device));
   (void)hipGetLastError(); // a stale error of an earlier, unrelated call on this thread is not this batch's
-  if (s->submitted && !s->waited)
-    for (uint32_t l = 0; l < s->nlanes; ++l) HIP_TRY(hipStreamSynchronize(s->lanes[l].stream));
-  s->nreads = nreads;
-  s->flags = flags;
-  s->submitted = true;
-  s->waited = false;
-  s->collected = false;
-  s->batch_rc = KR_OK;
-  s->sub_bases = bases, s->sub_offsets = offsets;
+  if (int rc = drain_batch(s)) return rc;
+  Batch& b = begin_batch(s, bases, offsets, nreads, flags, from);
   // long sequences across waves: a host batch that holds any is submitted as a batch of tiles (kr_dev_tiles.inc); the hit tap
   // (tests) reports positions within reads and keeps the batch as it is
-  s->tiles.active = false;
-  if (!(flags & (KR_BASES_DEVICE | KR_TAP_HITS)) && !s->no_tiles && !getenv("KR_NO_TILES")) {
-    bool tiled = false;
-    const int rc = build_tiles(s, bases, offsets, nreads, &tiled);
-    if (rc) {
-      s->waited = true, s->nlanes = 0, s->batch_rc = rc, s->batch_msg = kr_last_error();
-      return rc;
-    }
-    s->tiles.active = tiled;
-  } else if ((flags & KR_BASES_DEVICE) && (flags & KR_TILE_DEVICE) && !(flags & KR_TAP_HITS) && !s->no_tiles && !getenv("KR_NO_TILES")) {
-    bool tiled = false; // ... and a batch in HBM whose caller asks for it: the same arrays, laid out by kernels
-    const int rc = build_tiles_device(s, bases, offsets, nreads, &tiled);
-    if (rc) {
-      const std::string msg = kr_last_error();
-      (void)hipStreamSynchronize(s->lanes[0].stream);
-      (void)hipGetLastError();
-      s->waited = true, s->nlanes = 0, s->batch_rc = rc, s->batch_msg = msg;
-      return kr::fail(rc, msg);
-    }
-    s->tiles.active = tiled;
+  const bool may_tile = !(flags & KR_TAP_HITS) && !from.untiled && !getenv("KR_NO_TILES");
+  if (may_tile && !(flags & KR_BASES_DEVICE)) {
+    if (int rc = build_tiles(s, bases, offsets, nreads)) return fail_submit(s, rc, 0);
+  } else if (may_tile && (flags & KR_TILE_DEVICE)) { // ... and a batch in HBM whose caller asks for it: the same arrays, laid out by kernels on lane 0
+    if (int rc = build_tiles_device(s, bases, offsets, nreads)) return fail_submit(s, rc, 1);
   }
   // lanes of this batch: ranges of at least lane_min_reads reads; the hit tap (tests) keeps one hit buffer, hence one lane
   uint32_t P = std::min<uint32_t>(s->max_lanes, std::max<uint32_t>(1u, nreads / s->lane_min_reads));
   if (flags & KR_TAP_HITS) P = 1;
-  if (s->tiles.active) P = 1; // (a sequence's tiles belong to one launch)
+  if (b.tiled) P = 1; // (a sequence's tiles belong to one launch)
   if ((flags & KR_BASES_DEVICE) && !s->lanes_for_device_input) P = 1; // nothing to copy, nothing to overlap
-  if (s->text.req) P = 1; // (one text buffer, one prefix over the reads)
-  s->text.made = false;
-  s->nlanes = P;
-  set_row_modes(s, flags, P);
+  if (b.has_ids()) P = 1; // (one text buffer, one prefix over the reads)
+  set_lanes_and_row_modes(s, P);
   const ListCaps list_caps = debug_list_caps();
   if (flags & KR_TAP_HITS) {
     if (!reserve_all(s->hit_cap, s->d_hits, s->h_hits)) return alloc_failed("kr_batch_submit: hit tap buffers");
@@ -1182,66 +1235,34 @@ static int submit_batch(kr_stream* s, const uint8_t* bases, const uint64_t* offs
     if (!L.stream) HIP_TRY(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
     hipStream_t st = L.stream;
     HIP_TRY(hipEventRecord(L.ev[kEvCopyIn], st));
-    if (s->tiles.active) { // the tiled batch: its own bases and offsets, and what the tile kernels need
+    if (b.tiled) { // the tiled batch: its own bases and offsets, and what the tile kernels need
       kr_stream::Tiles& t = s->tiles;
-      if (!t.on_device) { // (else the layout kernels wrote them, on this stream)
-        HIP_TRY(hipMemcpyAsync(t.d_bases.get(), t.h_bases.get(), t.h_voff.get()[t.nv], hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(t.d_voff.get(), t.h_voff.get(), ((uint64_t)t.nv + 1) * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(t.d_vtile.get(), t.h_vtile.get(), t.nv, hipMemcpyHostToDevice, st));
+      if (!b.tiles_on_device) { // (else the layout kernels wrote them, on this stream)
+        HIP_TRY(hipMemcpyAsync(t.d_bases.get(), t.h_bases.get(), t.h_voff.get()[b.nv], hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(t.d_voff.get(), t.h_voff.get(), ((uint64_t)b.nv + 1) * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(t.d_vtile.get(), t.h_vtile.get(), b.nv, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(t.d_rfirst.get(), t.h_rfirst.get(), (uint64_t)nreads * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(t.d_longs.get(), t.h_longs.get(), (uint64_t)t.nlong * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(t.d_longs.get(), t.h_longs.get(), (uint64_t)b.nlong * 8, hipMemcpyHostToDevice, st));
       }
       L.in.bases = t.d_bases.get();
       L.in.offsets = t.d_voff.get();
-      L.nreads = t.nv;
+      L.nreads = b.nv;
     } else if (flags & KR_BASES_DEVICE) {
       L.in.bases = bases;
       L.in.offsets = offsets + r0;
     } else {
-      // the lane's bases land at the same offsets in d_bases as in the caller's buffer (relative to offsets[0]); its
-      // offsets are rebased to the staging buffer
-      const uint64_t b0 = offsets[r0] - offsets[0], b1 = offsets[r1] - offsets[0];
-      const uint64_t* ho = s->h_offsets; // [nreads + 1], shared boundary entries are written with the same value
-      const uint8_t* src = bases + offsets[r0];
-      if (!(flags & KR_BASES_PINNED)) {
-        memcpy(s->h_bases + b0, src, b1 - b0);
-        src = s->h_bases + b0;
-      }
-      if ((flags & KR_BASES_PINNED) && offsets[0] == 0)
-        ho = offsets; // page-locked and already relative to the staging buffer: no host pass at all
-      else
-        for (uint32_t r = r0; r <= r1; ++r) s->h_offsets[r] = offsets[r] - offsets[0];
-      HIP_TRY(hipMemcpyAsync(s->d_bases + b0, src, b1 - b0, hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(s->d_offsets + r0 + l, ho + r0, ((uint64_t)(r1 - r0) + 1) * 8, hipMemcpyHostToDevice, st));
+      if (int rc = stage_reads(s, st, bases, offsets, r0, r1, l, flags)) return rc;
       L.in.bases = s->d_bases;
       L.in.offsets = s->d_offsets + r0 + l;
     }
-    if (s->text.req && (!s->tiles.active || s->rows_mode) && !s->text.ids_on_device) { // the reads' ids (staged in page-locked memory by kr_batch_submit_text)
-      HIP_TRY(hipMemcpyAsync(s->text.d_ids, s->text.h_ids, s->text.id_bytes, hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(s->text.d_id_off, s->text.h_id_off, ((uint64_t)nreads + 1) * 4, hipMemcpyHostToDevice, st));
-    }
+    if (from.ids == kIdsHost && (!b.tiled || b.rows_mode)) // (a tiled batch that keeps its record slots has no text kernels to read them)
+      if (int rc = upload_ids(s, st)) return rc;
     L.in.nreads = L.nreads;
     set_lane_view(s, L, l, r0, flags, lane_rec_cap, lane_item_cap, lane_item_room, list_caps);
     return launch_lane(s, L, flags);
   };
-  for (uint32_t l = 0; l < P; ++l) {
-    const int rc = submit_lane(l);
-    if (rc) {
-      // lane l failed somewhere between its copies and its last launch: what was queued on lanes 0..l runs to its end (or
-      // fails with the same device error), nothing of this batch is handed out, and every later wait / collect on the
-      // stream reports this error until the next submit
-      const std::string msg = kr_last_error();
-      for (uint32_t j = 0; j <= l; ++j)
-        if (s->lanes[j].stream) (void)hipStreamSynchronize(s->lanes[j].stream);
-      (void)hipGetLastError();
-      s->nlanes = 0;
-      s->nrecs = 0, s->nhits = 0;
-      s->waited = true;
-      s->batch_rc = rc;
-      s->batch_msg = msg;
-      return kr::fail(rc, msg);
-    }
-  }
+  for (uint32_t l = 0; l < P; ++l)
+    if (int rc = submit_lane(l)) return fail_submit(s, rc, l + 1); // (lane l failed somewhere between its copies and its last launch)
   return KR_OK;
 }
 
@@ -1281,9 +1302,9 @@ int item_placement_step(kr_stream* s)
     ip.trials_left = (e && *e) ? std::max(0, atoi(e)) : kItemPlacementTrials;
   }
   if (ip.trials_left == 0 && !ip.aside.get()) return KR_OK;
-  if (s->tiles.active || s->nreads < 1000000u || (s->flags & KR_TAP_HITS)) return KR_OK; // (small batches: the launch is not what their time is)
+  if (s->batch.tiled || s->batch.nreads < 1000000u || (s->batch.flags & KR_TAP_HITS)) return KR_OK; // (small batches: the launch is not what their time is)
   float ms = 0;
-  for (uint32_t l = 0; l < s->nlanes; ++l) { // (the lanes of a batch work in slices of the one list: their scan times are added)
+  for (uint32_t l = 0; l < s->batch.nlanes; ++l) { // (the lanes of a batch work in slices of the one list: their scan times are added)
     float ml = 0;
     if (hipEventElapsedTime(&ml, s->lanes[l].ev[kEvFirstKernel], s->lanes[l].ev[kEvScanDone]) != hipSuccess) {
       (void)hipGetLastError(); // (not this batch's business: leave no sticky error behind)
@@ -1291,7 +1312,7 @@ int item_placement_step(kr_stream* s)
     }
     ms += ml;
   }
-  const double ns = (double)ms * 1e6 / s->nreads;
+  const double ns = (double)ms * 1e6 / s->batch.nreads;
   static const bool verbose = getenv("KR_ITEM_PLACEMENT_VERBOSE") != nullptr;
   if (ip.settling > 0) { // an early launch on this list (the stream's own, or a trial): a later one counts
     --ip.settling;
@@ -1334,16 +1355,27 @@ int item_placement_step(kr_stream* s)
   return KR_OK;
 }
 
+// kr_batch_wait runs the batch it has just waited for again, from the batch's own record with one mode bit set: the same arguments,
+// the same ids (a text batch stays one: staged ids are still staged, a record finder's still lie in HBM), the same origin
+static int rerun_batch(kr_stream* s, bool BatchOrigin::*mode)
+{
+  const Batch was = s->batch; // (a copy: submit_batch begins a fresh record)
+  BatchOrigin from = was.from;
+  from.*mode = true;
+  const int rc = submit_batch(s, was.bases, was.offsets, was.nreads, was.flags, from);
+  return rc ? rc : kr_batch_wait(s);
+}
+
 int kr_batch_wait(kr_stream* s)
 {
-  if (!s || !s->submitted) return kr::fail(KR_ERR_STATE, "kr_batch_wait: nothing submitted");
-  if (s->waited) return s->batch_rc ? kr::fail(s->batch_rc, s->batch_msg) : KR_OK;
-  if (s->seek.active) return seek_wait(s);
+  if (!s || !s->batch.submitted) return kr::fail(KR_ERR_STATE, "kr_batch_wait: nothing submitted");
+  if (s->batch.waited) return s->batch.rc ? kr::fail(s->batch.rc, s->batch.msg) : KR_OK;
+  if (s->batch.seek) return seek_wait(s);
   HIP_TRY(hipSetDevice(s->ix->device));
   memset(s->h_counters, 0, sizeof(s->h_counters));
   uint32_t extent = 0;
   bool lane_full = false;
-  for (uint32_t l = 0; l < s->nlanes; ++l) {
+  for (uint32_t l = 0; l < s->batch.nlanes; ++l) {
     Lane& L = s->lanes[l];
     HIP_TRY(hipStreamSynchronize(L.stream)); // kernels done, counters in L.h_counters
     const uint32_t* c = L.h_counters;
@@ -1356,10 +1388,10 @@ int kr_batch_wait(kr_stream* s)
       a = r.how == kSum ? a + c[r.slot] : (r.how == kMax ? std::max(a, c[r.slot]) : (a | c[r.slot]));
     }
   }
-  s->waited = true;
+  s->batch.waited = true;
   const uint32_t* hc = s->h_counters;
   if (s->dp.dbg & 512u)
-    fprintf(stderr, "[kr stats] reads %u events %u keys %u batches %u big %u level-tiles %u max keys %u max events %u records %u distinct likelihood problems (list positions) %u\n", s->nreads,
+    fprintf(stderr, "[kr stats] reads %u events %u keys %u batches %u big %u level-tiles %u max keys %u max events %u records %u distinct likelihood problems (list positions) %u\n", s->batch.nreads,
             hc[kCtStEvents], hc[kCtStKeys], hc[kCtStBatches], hc[kCtStBig], hc[kCtStLevelTiles], hc[kCtStMaxKeys], hc[kCtStMaxEvents], hc[kCtRecords], hc[kCtProblems]);
   if (s->dp.dbg & 512u)
     fprintf(stderr, "[kr stats] wave cycles/64 per launch: level passes %u, finalize %u, whole read %u\n", hc[kCtCycLevel], hc[kCtCycFinalize], hc[kCtCycRead]);
@@ -1380,65 +1412,196 @@ int kr_batch_wait(kr_stream* s)
     }
   }
   if (int prc = item_placement_step(s)) return prc;
-  s->nrecs = extent; // record slots of the device view, unused ones (rec_key == 0) included
-  s->nhits = std::min<uint64_t>(hc[kCtTapHits], s->hit_cap);
+  s->batch.nrecs = extent; // record slots of the device view, unused ones (rec_key == 0) included
+  s->batch.nhits = std::min<uint64_t>(hc[kCtTapHits], s->hit_cap);
   // (a tiled batch: the tiles' own records became holes when their sequences' records were written: kCtTileHoles; what survives
   //  is what the caller's max_records bounds)
-  const uint32_t recs = hc[kCtRecords], holes = s->tiles.active ? hc[kCtTileHoles] : 0u;
+  const uint32_t recs = hc[kCtRecords], holes = s->batch.tiled ? hc[kCtTileHoles] : 0u;
   if (recs - std::min(recs, holes) > s->rec_user_cap)
-    s->batch_rc = kr::fail(KR_ERR_CAPACITY, "the batch produced more records than max_records: submit fewer reads per batch");
+    s->batch.rc = kr::fail(KR_ERR_CAPACITY, "the batch produced more records than max_records: submit fewer reads per batch");
   else
-    s->batch_rc = check_errflags(hc[kCtErr] | (lane_full ? kErrRecCap : 0u));
-  if (s->batch_rc) s->batch_msg = kr_last_error();
-  if (!s->batch_rc && s->tiles.active && !s->no_tiles && getenv("KR_DEBUG_TILE_OVERFLOW")) s->batch_rc = KR_ERR_CAPACITY; // (tests)
+    s->batch.rc = check_errflags(hc[kCtErr] | (lane_full ? kErrRecCap : 0u));
+  if (s->batch.rc) s->batch.msg = kr_last_error();
+  if (!s->batch.rc && s->batch.tiled && getenv("KR_DEBUG_TILE_OVERFLOW")) s->batch.rc = KR_ERR_CAPACITY; // (tests)
   // KR_ROWS_INDEXED (one lane): list positions are handed out up to rep_cap, dist_list holds dist_cap of them
-  s->ndist = s->rows_indexed ? std::min<uint64_t>(hc[kCtProblems], s->lanes[0].out.dist_cap) : 0;
-  if (s->rows_indexed) s->ix_extent = hc[kCtProblems];
-  if (!s->batch_rc && s->rows_indexed && hc[kCtProblems] > s->lanes[0].out.dist_cap) {
+  s->batch.ndist = s->batch.rows_indexed ? std::min<uint64_t>(hc[kCtProblems], s->lanes[0].out.dist_cap) : 0;
+  if (s->batch.rows_indexed) s->ix_extent = hc[kCtProblems];
+  if (!s->batch.rc && s->batch.rows_indexed && hc[kCtProblems] > s->lanes[0].out.dist_cap) {
     // some row's position may lie beyond the list: the batch again with the hint ignored -- rows with rec_d, as the header promises
     // for a hint that is not honoured (the caller's buffers are still valid, as for the tiled rerun below)
-    s->no_indexed = true, ++s->ix_fallbacks;
-    int rc = submit_batch(s, s->sub_bases, s->sub_offsets, s->nreads, s->flags);
-    if (!rc) rc = kr_batch_wait(s);
-    s->no_indexed = false;
-    return rc;
+    ++s->ix_fallbacks;
+    return rerun_batch(s, &BatchOrigin::unindexed);
   }
-  if (s->batch_rc == KR_ERR_CAPACITY && s->tiles.active && !s->no_tiles) {
-    // the tiles' records did not fit: the batch again, one wave per sequence (the caller's buffers are still valid)
-    s->no_tiles = true;
-    int rc = submit_batch(s, s->sub_bases, s->sub_offsets, s->nreads, s->flags); // (not kr_batch_submit: a text batch stays one -- its ids are staged)
-    if (!rc) rc = kr_batch_wait(s);
-    s->no_tiles = false;
-    return rc;
-  }
-  return s->batch_rc;
+  // the tiles' records did not fit: the batch again, one wave per sequence (the caller's buffers are still valid)
+  if (s->batch.rc == KR_ERR_CAPACITY && s->batch.tiled) return rerun_batch(s, &BatchOrigin::untiled);
+  return s->batch.rc;
 }
 
 static void fill_view(kr_stream* s, kr_result_view* v, bool device)
 {
   memset(v, 0, sizeof(*v));
-  v->nreads = s->nreads;
-  v->nrecs = s->nrecs;
-  const bool rows_only = (s->flags & KR_ROWS_ONLY) != 0;
+  v->nreads = s->batch.nreads;
+  v->nrecs = s->batch.nrecs;
+  const bool rows_only = (s->batch.flags & KR_ROWS_ONLY) != 0;
   if (device) {
-    const BatchOut ro = result_out(s); // (a tiled batch: the real reads' per-read results)
+    const BatchOut ro = result_out(s, s->out); // (a tiled batch: the real reads' per-read results)
     v->read_off = ro.rd_off, v->read_cnt = ro.rd_cnt, v->read_onmers = ro.rd_onmers, v->read_na = ro.rd_na;
-    v->rec_key = s->out.rec_key, v->rec_sel = s->out.rec_sel, v->rec_d = s->rows_indexed ? nullptr : s->out.rec_d; // (indexed rows lie in rec_d)
+    v->rec_key = s->out.rec_key, v->rec_sel = s->out.rec_sel, v->rec_d = s->batch.rows_indexed ? nullptr : s->out.rec_d; // (indexed rows lie in rec_d)
     // ... and DIST of record slot i is dist_list[rec_dix[i]]: the select kernels left every selected record's list position in rec_rep
-    if (s->rows_indexed) v->rec_dix = s->out.rec_rep, v->dist_list = s->lanes[0].out.dist_list, v->ndist = s->ndist;
-    v->rec_v = (rows_only && !(s->flags & KR_TAP_ACCS) && !(!s->dp.no_filter && s->dp.multi)) ? nullptr : s->out.rec_v; // not written then
+    if (s->batch.rows_indexed) v->rec_dix = s->out.rec_rep, v->dist_list = s->lanes[0].out.dist_list, v->ndist = s->batch.ndist;
+    v->rec_v = (rows_only && !(s->batch.flags & KR_TAP_ACCS) && !(!s->dp.no_filter && s->dp.multi)) ? nullptr : s->out.rec_v; // not written then
     v->rec_chisq = (!s->dp.no_filter && s->dp.multi) ? s->out.rec_chisq : nullptr; // written in filter mode only
     // planes exist for every record only in batches that keep histograms (else only where the packed word cannot hold the problem)
-    v->rec_hist = (s->flags & KR_TAP_ACCS) ? s->out.rec_hist : nullptr;
-    v->rec_hist_stride = (s->flags & KR_TAP_ACCS) ? s->rec_cap : 0;
+    v->rec_hist = (s->batch.flags & KR_TAP_ACCS) ? s->out.rec_hist : nullptr;
+    v->rec_hist_stride = (s->batch.flags & KR_TAP_ACCS) ? s->rec_cap : 0;
   } else {
     v->read_off = s->h_rd_off, v->read_cnt = s->h_rd_cnt, v->read_onmers = s->h_rd_onmers, v->read_na = s->h_rd_na;
     v->rec_key = s->h_rec_key.get(), v->rec_sel = s->h_rec_sel.get(), v->rec_d = s->h_rec_d.get();
-    if (s->rows_indexed) v->rec_d = nullptr, v->rec_dix = s->h_rec_dix.get(), v->dist_list = s->h_dist_list.get(), v->ndist = s->h_ndist;
+    if (s->batch.rows_indexed) v->rec_d = nullptr, v->rec_dix = s->h_rec_dix.get(), v->dist_list = s->h_dist_list.get(), v->ndist = s->batch.h_ndist;
     v->rec_v = rows_only ? nullptr : s->h_rec_v.get();
     v->rec_chisq = rows_only ? nullptr : s->h_rec_chisq.get();
-    v->rec_hist = (s->flags & KR_TAP_ACCS) && !rows_only ? s->h_rec_hist.get() : nullptr;
-    v->rec_hist_stride = s->nrecs;
+    v->rec_hist = (s->batch.flags & KR_TAP_ACCS) && !rows_only ? s->h_rec_hist.get() : nullptr;
+    v->rec_hist_stride = s->batch.nrecs;
+  }
+}
+
+// ---- kr_batch_collect in three pieces: room on the host, one lane's copies, the offsets and the row count ----
+
+static bool collect_full(const kr_stream* s) { return !(s->batch.flags & KR_ROWS_ONLY); }
+// what a lane brings back: compact rows -- (key, DIST) per output row, every one selected -- or its record slots
+static uint64_t lane_count(const kr_stream* s, const Lane& L) { return s->batch.rows_mode ? L.nrows : L.nrecs; }
+static uint64_t batch_count(const kr_stream* s)
+{
+  uint64_t total = 0;
+  for (uint32_t l = 0; l < s->batch.nlanes; ++l) total += lane_count(s, s->lanes[l]);
+  return total;
+}
+
+// Room for `need` records (rows) in the page-locked record arrays
+static int collect_room(kr_stream* s, uint64_t need)
+{
+  const bool full = collect_full(s);
+  const uint64_t have = s->h_rec_key.size();
+  if (need <= have && (s->h_rec_full || !full) && (s->h_rec_dix.get() || !s->batch.rows_indexed)) return KR_OK;
+  const uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(need + need / 4, have), 1u << 16);
+  // all of them anew, every old one freed first (v / chisq / hist stay empty until a batch asks for them, dix until an indexed one
+  // does); a failure leaves none behind, and the next collect starts over
+  auto drop = [&] { s->h_rec_key.reset(), s->h_rec_sel.reset(), s->h_rec_d.reset(), s->h_rec_hist.reset(), s->h_rec_v.reset(), s->h_rec_chisq.reset(); };
+  drop();
+  s->h_sel_ones = 0;
+  bool ok = s->h_rec_key.renew(cap) && s->h_rec_sel.renew(cap) && s->h_rec_d.renew(cap);
+  s->h_rec_dix.reset();
+  if (ok && s->batch.rows_indexed) ok = s->h_rec_dix.renew(cap);
+  if (ok) s->h_rec_full = s->h_rec_full || full;
+  if (ok && s->h_rec_full) ok = s->h_rec_hist.renew(cap * s->dp.np) && s->h_rec_v.renew(cap) && s->h_rec_chisq.renew(cap);
+  if (ok) return KR_OK;
+  drop(), s->h_rec_dix.reset();
+  return alloc_failed("kr_batch_collect: page-locked record arrays");
+}
+
+// The copies of lane L, queued on its stream: its records (rows) land at `hoff` in the compact host arrays, the per-read results at
+// the lane's reads, read through result_out: a tiled batch is one lane, and its per-read results are the real reads'
+static int collect_lane(kr_stream* s, Lane& L, uint64_t hoff)
+{
+  Batch& b = s->batch;
+  hipStream_t st = L.stream;
+  const BatchOut o = result_out(s, L.out);
+  const bool full = collect_full(s);
+  const uint64_t nr = b.tiled ? b.nreads : L.nreads, nc = lane_count(s, L), r0 = L.read0;
+  L.host_off = hoff;
+  if (b.rows_mode) { // 12 bytes per output row and the reads' row ranges: nothing else crosses PCIe
+    HIP_TRY(hipMemcpyAsync(s->h_rd_off + r0, o.rd_roff, nr * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(s->h_rd_cnt + r0, o.rd_rcnt, nr * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(s->h_rd_na + r0, o.rd_na, nr, hipMemcpyDeviceToHost, st));
+    s->d2h_bytes += nr * 9;
+    if (b.rows_indexed) b.h_ndist = nc ? b.ndist : 0; // (a batch without rows brings no list back)
+    if (nc && b.rows_indexed) { // (one lane, waited for: kr_batch_wait has set ndist)
+      const uint64_t nd = b.ndist;
+      if (nd > s->h_dist_list.size() && !s->h_dist_list.reserve(nd + nd / 4 + 1024)) return alloc_failed("kr_batch_collect: list of distinct DIST values");
+      HIP_TRY(hipMemcpyAsync(s->h_rec_key.get() + hoff, o.row_key, nc * 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(s->h_rec_dix.get() + hoff, o.row_dix, nc * 4, hipMemcpyDeviceToHost, st));
+      if (nd) HIP_TRY(hipMemcpyAsync(s->h_dist_list.get(), o.dist_list, nd * 8, hipMemcpyDeviceToHost, st));
+      s->d2h_bytes += nc * 8 + nd * 8;
+    } else if (nc) {
+      HIP_TRY(hipMemcpyAsync(s->h_rec_key.get() + hoff, o.row_key, nc * 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(s->h_rec_d.get() + hoff, o.row_d, nc * 8, hipMemcpyDeviceToHost, st));
+      s->d2h_bytes += nc * 12;
+    }
+    return KR_OK;
+  }
+  HIP_TRY(hipMemcpyAsync(s->h_rd_off + r0, o.rd_off, nr * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(s->h_rd_cnt + r0, o.rd_cnt, nr * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(s->h_rd_na + r0, o.rd_na, nr, hipMemcpyDeviceToHost, st));
+  s->d2h_bytes += nr * 9;
+  if (full) {
+    HIP_TRY(hipMemcpyAsync(s->h_rd_onmers + r0, o.rd_onmers, nr * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(s->h_rd_filt + 2 * r0, o.rd_filt, nr * 8, hipMemcpyDeviceToHost, st));
+    s->d2h_bytes += nr * 12;
+  }
+  if (!nc) return KR_OK;
+  s->h_sel_ones = 0; // (real flags from here on)
+  s->d2h_bytes += nc * 13; // key, flag, DIST of every record slot
+  HIP_TRY(hipMemcpyAsync(s->h_rec_key.get() + hoff, o.rec_key, nc * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(s->h_rec_sel.get() + hoff, o.rec_sel, nc, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(s->h_rec_d.get() + hoff, o.rec_d, nc * 8, hipMemcpyDeviceToHost, st));
+  if (!full) return KR_OK;
+  HIP_TRY(hipMemcpyAsync(s->h_rec_v.get() + hoff, o.rec_v, nc * 8, hipMemcpyDeviceToHost, st));
+  s->d2h_bytes += nc * 8;
+  if (!s->dp.no_filter && s->dp.multi) {
+    HIP_TRY(hipMemcpyAsync(s->h_rec_chisq.get() + hoff, o.rec_chisq, nc * 8, hipMemcpyDeviceToHost, st));
+    s->d2h_bytes += nc * 8;
+  } else
+    std::fill(s->h_rec_chisq.get() + hoff, s->h_rec_chisq.get() + hoff + nc, std::numeric_limits<double>::quiet_NaN());
+  if (b.flags & KR_TAP_ACCS) { // (waited for: the planes are laid out by the total record count)
+    uint64_t hist_stride_host = 0;
+    for (uint32_t l = 0; l < b.nlanes; ++l) hist_stride_host += s->lanes[l].nrecs;
+    for (uint32_t x = 0; x < s->dp.np; ++x) {
+      HIP_TRY(hipMemcpyAsync(s->h_rec_hist.get() + (uint64_t)x * hist_stride_host + hoff, o.rec_hist + (uint64_t)x * s->rec_cap, nc * 4, hipMemcpyDeviceToHost, st));
+      s->d2h_bytes += nc * 4;
+    }
+  }
+  return KR_OK;
+}
+
+// The copies have landed, `total` records (rows) in all: the reads' offsets from the stream's arrays (lane slices) to the compact
+// host arrays, the host view and its number of output rows
+static void collect_finish(kr_stream* s, uint64_t total, kr_result_view* v)
+{
+  const bool rows_mode = s->batch.rows_mode;
+  for (uint32_t l = 0; l < s->batch.nlanes; ++l) {
+    const Lane& L = s->lanes[l];
+    const uint32_t delta = rows_mode ? (uint32_t)L.host_off : (uint32_t)L.host_off - L.rec_base; // (mod 2^32; a lane's rows are numbered from 0)
+    if (!delta) continue;
+    uint32_t* off = s->h_rd_off + L.read0;
+    const uint32_t* cnt = s->h_rd_cnt + L.read0;
+    for (uint32_t r = 0; r < L.nreads; ++r) off[r] = cnt[r] ? off[r] + delta : 0u;
+  }
+  fill_view(s, v, false);
+  v->nrecs = (uint32_t)total;
+  v->rec_hist_stride = total;
+  if (rows_mode) { // every row is an output row: the flags are a block of ones that is written once and kept
+    if (s->h_sel_ones < total) {
+      const uint64_t a0 = s->h_sel_ones, len = total - a0;
+      const int nt = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)std::min(kr::parallel_width(), 16), len >> 22));
+      kr::parallel_for(nt, [&](int t) {
+        const uint64_t a = a0 + len * (uint64_t)t / nt, b = a0 + len * (uint64_t)(t + 1) / nt;
+        memset(s->h_rec_sel.get() + a, 1, b - a);
+      });
+      s->h_sel_ones = total;
+    }
+    v->nrows = total;
+  } else { // number of output rows: tens of millions of flags for a large batch, summed by the host pool
+    const int nt = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)std::min(kr::parallel_width(), 16), total >> 20));
+    std::vector<uint64_t> part((size_t)nt, 0);
+    const uint8_t* sel = s->h_rec_sel.get();
+    kr::parallel_for(nt, [&](int t) {
+      uint64_t a = total * (uint64_t)t / nt, b = total * (uint64_t)(t + 1) / nt, c = 0;
+      for (uint64_t i = a; i < b; ++i) c += sel[i];
+      part[(size_t)t] = c;
+    });
+    uint64_t nrows = 0;
+    for (uint64_t c : part) nrows += c;
+    v->nrows = nrows;
   }
 }
 
@@ -1446,11 +1609,11 @@ int kr_batch_collect(kr_stream* s, kr_result_view* v)
 {
   kr::clear_error();
   if (!s || !v) return kr::fail(KR_ERR_ARG, "kr_batch_collect: null argument");
-  if (!s->submitted) return kr::fail(KR_ERR_STATE, "kr_batch_collect: nothing submitted");
-  if (s->seek.active) return kr::fail(KR_ERR_STATE, "kr_batch_collect: the batch is a seek batch: kr_batch_collect_seek / kr_batch_collect_text");
+  Batch& b = s->batch;
+  if (!b.submitted) return kr::fail(KR_ERR_STATE, "kr_batch_collect: nothing submitted");
+  if (b.seek) return kr::fail(KR_ERR_STATE, "kr_batch_collect: the batch is a seek batch: kr_batch_collect_seek / kr_batch_collect_text");
   HIP_TRY(hipSetDevice(s->ix->device));
-  const bool rows_only = (s->flags & KR_ROWS_ONLY) != 0, full = !rows_only;
-  const bool pipelined = !s->waited && !s->collected;
+  const bool pipelined = !b.waited && !b.collected;
   s->d2h_bytes = 0;
   static const bool timing = getenv("KR_COLLECT_TIMING") != nullptr;
   auto wall = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -1461,168 +1624,48 @@ int kr_batch_collect(kr_stream* s, kr_result_view* v)
     fprintf(stderr, "[collect] %s %.2f ms\n", what, (now - t_mark) * 1e3);
     t_mark = now;
   };
-  // Lane by lane: as soon as a lane's kernels are done its results start their way to the host on the lane's own
-  // stream, while later lanes still compute.  The host arrays are compact (no unused slots between lanes), so a lane's
-  // records land behind those of the lanes before it.
-  auto ensure_host = [&](uint64_t need) -> int {
-    const uint64_t have = s->h_rec_key.size();
-    if (need <= have && (s->h_rec_full || !full) && (s->h_rec_dix.get() || !s->rows_indexed)) return KR_OK;
-    const uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(need + need / 4, have), 1u << 16);
-    // all of them anew, every old one freed first (v / chisq / hist stay empty until a batch asks for them, dix until an indexed one
-    // does); a failure leaves none behind, and the next collect starts over
-    auto drop = [&] { s->h_rec_key.reset(), s->h_rec_sel.reset(), s->h_rec_d.reset(), s->h_rec_hist.reset(), s->h_rec_v.reset(), s->h_rec_chisq.reset(); };
-    drop();
-    s->h_sel_ones = 0;
-    bool ok = s->h_rec_key.renew(cap) && s->h_rec_sel.renew(cap) && s->h_rec_d.renew(cap);
-    s->h_rec_dix.reset();
-    if (ok && s->rows_indexed) ok = s->h_rec_dix.renew(cap);
-    if (ok) s->h_rec_full = s->h_rec_full || full;
-    if (ok && s->h_rec_full) ok = s->h_rec_hist.renew(cap * s->dp.np) && s->h_rec_v.renew(cap) && s->h_rec_chisq.renew(cap);
-    if (ok) return KR_OK;
-    drop(), s->h_rec_dix.reset();
-    return alloc_failed("kr_batch_collect: page-locked record arrays");
-  };
-  if (!pipelined || s->nlanes == 1 || (s->flags & KR_TAP_ACCS)) {
+  if (!pipelined || b.nlanes == 1 || (b.flags & KR_TAP_ACCS)) {
     int rc = kr_batch_wait(s); // (the histogram planes are laid out by the total record count: it must be known first)
     if (rc) return rc;
   }
   lap("wait for the kernels");
+  if (b.waited)
+    if (int rc = collect_room(s, batch_count(s))) return rc;
+  // Lane by lane: as soon as a lane's kernels are done its results start their way to the host on the lane's own
+  // stream, while later lanes still compute.  The host arrays are compact (no unused slots between lanes), so a lane's
+  // records land behind those of the lanes before it.
   uint64_t hoff = 0;
-  bool copies_started = false;
-  const bool rows_mode = s->rows_mode; // compact rows leave the device: (key, DIST) per output row, every one selected
-  auto lane_count = [&](const Lane& L) -> uint64_t { return rows_mode ? L.nrows : L.nrecs; };
-  if (s->waited) {
-    uint64_t total = 0;
-    for (uint32_t l = 0; l < s->nlanes; ++l) total += lane_count(s->lanes[l]);
-    int rc = ensure_host(total);
-    if (rc) return rc;
-  }
-  const uint64_t hist_stride_host = [&] { uint64_t t = 0; for (uint32_t l = 0; l < s->nlanes; ++l) t += s->lanes[l].nrecs; return t; }();
-  for (uint32_t l = 0; l < s->nlanes; ++l) {
+  for (uint32_t l = 0; l < b.nlanes; ++l) {
     Lane& L = s->lanes[l];
-    hipStream_t st = L.stream;
-    if (!s->waited) {
-      HIP_TRY(hipStreamSynchronize(st));
+    if (!b.waited) {
+      HIP_TRY(hipStreamSynchronize(L.stream));
       L.nrecs = std::min(L.h_counters[kCtRecSlots], L.rec_cap);
       L.nrows = L.h_counters[kCtRows];
-      // room for this lane and, by its measure, for the lanes still running; if not, start over once everything is known
-      const uint64_t guess = hoff + lane_count(L) * (s->nlanes - l) + lane_count(L) / 8 * (s->nlanes - l - 1);
-      if (guess > s->h_rec_key.size() || (full && !s->h_rec_full)) {
-        for (uint32_t j = 0; j < s->nlanes; ++j) HIP_TRY(hipStreamSynchronize(s->lanes[j].stream));
+      // room for this lane and, by its measure, for the lanes still running; if not, everything is waited for and the room made
+      const uint64_t nc = lane_count(s, L), guess = hoff + nc * (b.nlanes - l) + nc / 8 * (b.nlanes - l - 1);
+      if (guess > s->h_rec_key.size() || (collect_full(s) && !s->h_rec_full)) {
+        for (uint32_t j = 0; j < b.nlanes; ++j) HIP_TRY(hipStreamSynchronize(s->lanes[j].stream));
         int rc = kr_batch_wait(s);
         if (rc) return rc;
-        uint64_t total = 0;
-        for (uint32_t j = 0; j < s->nlanes; ++j) total += lane_count(s->lanes[j]);
-        if ((rc = ensure_host(total))) return rc;
-        if (copies_started) { // restart: the buffers moved
-          l = (uint32_t)-1, hoff = 0, copies_started = false;
-          continue;
+        if ((rc = collect_room(s, batch_count(s)))) return rc;
+        hoff = 0; // the buffers moved: the copies of the lanes before this one start over (once: the batch is waited for now)
+        for (uint32_t j = 0; j < l; ++j) {
+          if ((rc = collect_lane(s, s->lanes[j], hoff))) return rc;
+          hoff += lane_count(s, s->lanes[j]);
         }
       }
     }
-    L.host_off = hoff;
-    const bool tl = s->tiles.active; // one lane, and the per-read results are those of the real reads
-    const uint64_t nr = tl ? s->nreads : L.nreads, nc = lane_count(L), r0 = L.read0;
-    const BatchOut& o = L.out;
-    const kr_stream::Tiles& t = s->tiles;
-    if (rows_mode) { // 12 bytes per output row and the reads' row ranges (a tiled batch: the real reads'): nothing else crosses PCIe
-      HIP_TRY(hipMemcpyAsync(s->h_rd_off + r0, tl ? t.d_real_roff.get() : o.rd_roff, nr * 4, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(s->h_rd_cnt + r0, tl ? t.d_real_rcnt.get() : o.rd_rcnt, nr * 4, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(s->h_rd_na + r0, tl ? t.d_real_na.get() : o.rd_na, nr, hipMemcpyDeviceToHost, st));
-      s->d2h_bytes += nr * 9;
-      if (s->rows_indexed) s->h_ndist = nc ? s->ndist : 0; // (a batch without rows brings no list back)
-      if (nc && s->rows_indexed) { // (one lane, waited for: kr_batch_wait has set ndist)
-        const uint64_t nd = s->ndist;
-        if (nd > s->h_dist_list.size() && !s->h_dist_list.reserve(nd + nd / 4 + 1024)) return alloc_failed("kr_batch_collect: list of distinct DIST values");
-        HIP_TRY(hipMemcpyAsync(s->h_rec_key.get() + hoff, o.row_key, nc * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(s->h_rec_dix.get() + hoff, o.row_dix, nc * 4, hipMemcpyDeviceToHost, st));
-        if (nd) HIP_TRY(hipMemcpyAsync(s->h_dist_list.get(), o.dist_list, nd * 8, hipMemcpyDeviceToHost, st));
-        s->d2h_bytes += nc * 8 + nd * 8;
-      } else if (nc) {
-        HIP_TRY(hipMemcpyAsync(s->h_rec_key.get() + hoff, o.row_key, nc * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(s->h_rec_d.get() + hoff, o.row_d, nc * 8, hipMemcpyDeviceToHost, st));
-        s->d2h_bytes += nc * 12;
-      }
-      copies_started = true;
-      hoff += nc;
-      continue;
-    }
-    HIP_TRY(hipMemcpyAsync(s->h_rd_off + r0, tl ? t.d_real_off.get() : o.rd_off, nr * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(s->h_rd_cnt + r0, tl ? t.d_real_cnt.get() : o.rd_cnt, nr * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(s->h_rd_na + r0, tl ? t.d_real_na.get() : o.rd_na, nr, hipMemcpyDeviceToHost, st));
-    s->d2h_bytes += nr * 9;
-    if (full) {
-      HIP_TRY(hipMemcpyAsync(s->h_rd_onmers + r0, tl ? t.d_real_onmers.get() : o.rd_onmers, nr * 4, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(s->h_rd_filt + 2 * r0, tl ? t.d_real_filt.get() : o.rd_filt, nr * 8, hipMemcpyDeviceToHost, st));
-      s->d2h_bytes += nr * 12;
-    }
-    if (nc) {
-      s->h_sel_ones = 0; // (real flags from here on)
-      s->d2h_bytes += nc * 13; // key, flag, DIST of every record slot
-      HIP_TRY(hipMemcpyAsync(s->h_rec_key.get() + hoff, o.rec_key, nc * 4, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(s->h_rec_sel.get() + hoff, o.rec_sel, nc, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(s->h_rec_d.get() + hoff, o.rec_d, nc * 8, hipMemcpyDeviceToHost, st));
-      if (full) {
-        HIP_TRY(hipMemcpyAsync(s->h_rec_v.get() + hoff, o.rec_v, nc * 8, hipMemcpyDeviceToHost, st));
-        s->d2h_bytes += nc * 8;
-        if (!s->dp.no_filter && s->dp.multi) {
-          HIP_TRY(hipMemcpyAsync(s->h_rec_chisq.get() + hoff, o.rec_chisq, nc * 8, hipMemcpyDeviceToHost, st));
-          s->d2h_bytes += nc * 8;
-        } else
-          std::fill(s->h_rec_chisq.get() + hoff, s->h_rec_chisq.get() + hoff + nc, std::numeric_limits<double>::quiet_NaN());
-        if (s->flags & KR_TAP_ACCS)
-          for (uint32_t x = 0; x < s->dp.np; ++x) {
-            HIP_TRY(hipMemcpyAsync(s->h_rec_hist.get() + (uint64_t)x * hist_stride_host + hoff, o.rec_hist + (uint64_t)x * s->rec_cap, nc * 4, hipMemcpyDeviceToHost, st));
-            s->d2h_bytes += nc * 4;
-          }
-      }
-    }
-    copies_started = true;
-    hoff += nc;
+    if (int rc = collect_lane(s, L, hoff)) return rc;
+    hoff += lane_count(s, L);
   }
-  if ((s->flags & KR_TAP_HITS) && s->waited && s->nhits)
-    HIP_TRY(hipMemcpyAsync(s->h_hits.get(), s->out.hits, s->nhits * sizeof(kr_hit), hipMemcpyDeviceToHost, s->lanes[0].stream));
+  if ((b.flags & KR_TAP_HITS) && b.waited && b.nhits)
+    HIP_TRY(hipMemcpyAsync(s->h_hits.get(), s->out.hits, b.nhits * sizeof(kr_hit), hipMemcpyDeviceToHost, s->lanes[0].stream));
   int rc = kr_batch_wait(s); // (a no-op when it already ran; otherwise every lane is idle by now: aggregates the counters)
-  for (uint32_t l = 0; l < s->nlanes; ++l) HIP_TRY(hipStreamSynchronize(s->lanes[l].stream));
+  for (uint32_t l = 0; l < b.nlanes; ++l) HIP_TRY(hipStreamSynchronize(s->lanes[l].stream));
   if (rc) return rc;
   lap("copies to the host");
-  // device offsets index the stream's arrays (lane slices); the host arrays are compact
-  for (uint32_t l = 0; l < s->nlanes; ++l) {
-    const Lane& L = s->lanes[l];
-    const uint32_t delta = rows_mode ? (uint32_t)L.host_off : (uint32_t)L.host_off - L.rec_base; // (mod 2^32; a lane's rows are numbered from 0)
-    if (!delta) continue;
-    uint32_t* off = s->h_rd_off + L.read0;
-    const uint32_t* cnt = s->h_rd_cnt + L.read0;
-    for (uint32_t r = 0; r < L.nreads; ++r) off[r] = cnt[r] ? off[r] + delta : 0u;
-  }
-  s->collected = true;
-  fill_view(s, v, false);
-  v->nrecs = (uint32_t)hoff;
-  v->rec_hist_stride = hoff;
-  if (rows_mode) { // every row is an output row: the flags are a block of ones that is written once and kept
-    if (s->h_sel_ones < hoff) {
-      const uint64_t a0 = s->h_sel_ones, len = hoff - a0;
-      const int nt = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)std::min(kr::parallel_width(), 16), len >> 22));
-      kr::parallel_for(nt, [&](int t) {
-        const uint64_t a = a0 + len * (uint64_t)t / nt, b = a0 + len * (uint64_t)(t + 1) / nt;
-        memset(s->h_rec_sel.get() + a, 1, b - a);
-      });
-      s->h_sel_ones = hoff;
-    }
-    v->nrows = hoff;
-  } else { // number of output rows: tens of millions of flags for a large batch, summed by the host pool
-    const int nt = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)std::min(kr::parallel_width(), 16), hoff >> 20));
-    std::vector<uint64_t> part((size_t)nt, 0);
-    const uint8_t* sel = s->h_rec_sel.get();
-    kr::parallel_for(nt, [&](int t) {
-      uint64_t a = hoff * (uint64_t)t / nt, b = hoff * (uint64_t)(t + 1) / nt, c = 0;
-      for (uint64_t i = a; i < b; ++i) c += sel[i];
-      part[(size_t)t] = c;
-    });
-    uint64_t nrows = 0;
-    for (uint64_t c : part) nrows += c;
-    v->nrows = nrows;
-  }
+  b.collected = true;
+  collect_finish(s, hoff, v);
   lap("offsets + row count");
   return KR_OK;
 }
@@ -1631,7 +1674,7 @@ int kr_batch_collect_device(kr_stream* s, kr_result_view* v)
 {
   kr::clear_error();
   if (!s || !v) return kr::fail(KR_ERR_ARG, "kr_batch_collect_device: null argument");
-  if (s->submitted && s->seek.active) return kr::fail(KR_ERR_STATE, "kr_batch_collect_device: the batch is a seek batch: kr_batch_collect_seek");
+  if (s->batch.submitted && s->batch.seek) return kr::fail(KR_ERR_STATE, "kr_batch_collect_device: the batch is a seek batch: kr_batch_collect_seek");
   int rc = kr_batch_wait(s);
   if (rc) return rc;
   fill_view(s, v, true);
@@ -1640,15 +1683,15 @@ int kr_batch_collect_device(kr_stream* s, kr_result_view* v)
 
 int kr_batch_hits(kr_stream* s, const kr_hit** hits, uint64_t* nhits)
 {
-  if (!s || !hits || !nhits || !s->waited) return kr::fail(KR_ERR_STATE, "kr_batch_hits: collect a KR_TAP_HITS batch first");
+  if (!s || !hits || !nhits || !s->batch.waited) return kr::fail(KR_ERR_STATE, "kr_batch_hits: collect a KR_TAP_HITS batch first");
   *hits = s->h_hits.get();
-  *nhits = s->nhits;
+  *nhits = s->batch.nhits;
   return KR_OK;
 }
 
 int kr_batch_readtaps(kr_stream* s, const kr_readtap** taps)
 {
-  if (!s || !taps || !s->waited) return kr::fail(KR_ERR_STATE, "kr_batch_readtaps: collect a batch first");
+  if (!s || !taps || !s->batch.waited) return kr::fail(KR_ERR_STATE, "kr_batch_readtaps: collect a batch first");
   *taps = reinterpret_cast<const kr_readtap*>(s->h_rd_filt);
   return KR_OK;
 }
@@ -1658,7 +1701,7 @@ int kr_batch_readtaps(kr_stream* s, const kr_readtap** taps)
 // stream.  0: item list; 1: per-read arrays; 2: counters + cursors; 3: records, de-duplication table; 4: HIP stream.
 int kr_debug_stream_move(kr_stream* s, int which)
 {
-  if (!s || (s->submitted && !s->waited)) return kr::fail(KR_ERR_STATE, "kr_debug_stream_move: wait for the batch first");
+  if (!s || (s->batch.submitted && !s->batch.waited)) return kr::fail(KR_ERR_STATE, "kr_debug_stream_move: wait for the batch first");
   HIP_TRY(hipSetDevice(s->device));
   BatchOut& o = s->out;
   Lane& L = s->lanes[0];
@@ -1780,7 +1823,7 @@ int kr_debug_select(kr_stream* s, const kr_select_tables* in, uint32_t flags, ui
 {
   kr::clear_error();
   if (!s || !in || !out) return kr::fail(KR_ERR_ARG, "kr_debug_select: null argument");
-  if (s->max_lanes != 1 || (s->submitted && !s->waited)) return kr::fail(KR_ERR_STATE, "kr_debug_select: needs an idle one-lane stream");
+  if (s->max_lanes != 1 || (s->batch.submitted && !s->batch.waited)) return kr::fail(KR_ERR_STATE, "kr_debug_select: needs an idle one-lane stream");
   auto bad = [](const char* what) { return kr::fail(KR_ERR_ARG, std::string("kr_debug_select: ") + what); };
   if (form > 1) return bad("form is 0 or 1");
   if (flags != 0 && flags != KR_TAP_ACCS && flags != KR_ROWS_ONLY && flags != (KR_ROWS_ONLY | KR_ROWS_INDEXED)) return bad("unsupported flags");
@@ -1790,9 +1833,8 @@ int kr_debug_select(kr_stream* s, const kr_select_tables* in, uint32_t flags, ui
   HIP_TRY(hipSetDevice(s->device));
   Lane& L = s->lanes[0];
   hipStream_t st = L.stream;
-  s->tiles.active = false, s->text.req = false; // (a crafted batch is neither tiled nor text)
-  s->nlanes = 1, s->submitted = false, s->waited = false;
-  set_row_modes(s, flags, 1);
+  begin_batch(s, nullptr, nullptr, nreads, flags, BatchOrigin{}, false); // (a crafted batch: neither tiled nor text, nothing to wait for)
+  set_lanes_and_row_modes(s, 1);
   L.read0 = 0, L.nreads = nreads, L.rec_base = 0, L.rec_cap = s->rec_cap, L.nrecs = nrecs;
   set_lane_view(s, L, 0, 0, flags, s->rec_cap, s->item_cap, s->item_cap, debug_list_caps());
   BatchOut& o = L.out;
@@ -1875,7 +1917,7 @@ int kr_debug_acc_paths(kr_stream* s, uint32_t* out, uint32_t n)
 {
   kr::clear_error();
   if (!s || !out) return kr::fail(KR_ERR_ARG, "kr_debug_acc_paths: null argument");
-  if (!s->waited) return kr::fail(KR_ERR_STATE, "kr_debug_acc_paths: wait for a batch first");
+  if (!s->batch.waited) return kr::fail(KR_ERR_STATE, "kr_debug_acc_paths: wait for a batch first");
   for (uint32_t i = 0; i < std::min(n, kCtPathCount); ++i) out[i] = s->h_counters[kCtPathFirst + i];
   return KR_OK;
 }
@@ -1937,20 +1979,20 @@ int kr_debug_scan_stream(const kr_stream* s, uint32_t* out4)
   out4[0] = (!s->fk && f >= 5 && f <= 8 && s->scan_pipe) ? 1u : 0u;
   out4[1] = s->fk ? 1u : 0u;
   out4[2] = s->item_cap_dbg ? std::min(s->item_cap, s->item_cap_dbg) : s->item_cap;
-  out4[3] = s->waited ? s->h_counters[kCtItemSlots] : 0u;
+  out4[3] = s->batch.waited ? s->h_counters[kCtItemSlots] : 0u;
   return KR_OK;
 }
 
 int kr_batch_timing(kr_stream* s, kr_timing* t)
 {
-  if (!s || !t || !s->waited) return kr::fail(KR_ERR_STATE, "kr_batch_timing: wait for a batch first");
-  if (s->seek.active) return kr::fail(KR_ERR_STATE, "kr_batch_timing: the batch is a seek batch: kr_debug_seek_ms");
+  if (!s || !t || !s->batch.waited) return kr::fail(KR_ERR_STATE, "kr_batch_timing: wait for a batch first");
+  if (s->batch.seek) return kr::fail(KR_ERR_STATE, "kr_batch_timing: the batch is a seek batch: kr_debug_seek_ms");
   memset(t, 0, sizeof(*t));
   // per phase: the sum over the lanes of the time between the lane's events (with one lane: the kernels' own time;
   // with several, lanes share the chip and the sums exceed ms_total, the span from the first lane's first kernel to the
   // last lane's last)
   float first = 0, last = 0;
-  for (uint32_t l = 0; l < s->nlanes; ++l) {
+  for (uint32_t l = 0; l < s->batch.nlanes; ++l) {
     Lane& L = s->lanes[l];
     float a = 0;
     HIP_TRY(hipEventElapsedTime(&a, L.ev[kEvCopyIn], L.ev[kEvFirstKernel]));
@@ -1969,7 +2011,7 @@ int kr_batch_timing(kr_stream* s, kr_timing* t)
     last = std::max(last, a);
   }
   t->ms_total = last - first;
-  t->lanes = s->nlanes;
+  t->lanes = s->batch.nlanes;
   t->overflow_reads = s->h_counters[kCtL2Reads];
   t->stack_spills = s->h_counters[kCtStackSpills];
   return KR_OK;
@@ -1983,17 +2025,18 @@ int kr_debug_tile_layout(kr_stream* s, uint32_t* nv, uint32_t* nlong, uint64_t* 
   kr::clear_error();
   if (!s || !nv || !nlong) return kr::fail(KR_ERR_ARG, "kr_debug_tile_layout: null argument");
   *nv = 0, *nlong = 0;
-  if (!s->submitted || !s->tiles.active) return KR_OK;
+  if (!s->batch.submitted || !s->batch.tiled) return KR_OK;
   const kr_stream::Tiles& t = s->tiles;
   HIP_TRY(hipSetDevice(s->device));
   hipStream_t st = s->lanes[0].stream; // (a tiled batch has one lane: its copies or layout kernels are queued here)
-  *nv = t.nv, *nlong = t.nlong;
+  const uint32_t tnv = s->batch.nv, tnlong = s->batch.nlong;
+  *nv = tnv, *nlong = tnlong;
   uint64_t nb = 0;
-  HIP_TRY(hipMemcpyAsync(&nb, t.d_voff.get() + t.nv, 8, hipMemcpyDeviceToHost, st));
-  if (voff) HIP_TRY(hipMemcpyAsync(voff, t.d_voff.get(), ((uint64_t)t.nv + 1) * 8, hipMemcpyDeviceToHost, st));
-  if (vtile) HIP_TRY(hipMemcpyAsync(vtile, t.d_vtile.get(), t.nv, hipMemcpyDeviceToHost, st));
-  if (rfirst) HIP_TRY(hipMemcpyAsync(rfirst, t.d_rfirst.get(), (uint64_t)s->nreads * 4, hipMemcpyDeviceToHost, st));
-  if (longs) HIP_TRY(hipMemcpyAsync(longs, t.d_longs.get(), (uint64_t)t.nlong * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&nb, t.d_voff.get() + tnv, 8, hipMemcpyDeviceToHost, st));
+  if (voff) HIP_TRY(hipMemcpyAsync(voff, t.d_voff.get(), ((uint64_t)tnv + 1) * 8, hipMemcpyDeviceToHost, st));
+  if (vtile) HIP_TRY(hipMemcpyAsync(vtile, t.d_vtile.get(), tnv, hipMemcpyDeviceToHost, st));
+  if (rfirst) HIP_TRY(hipMemcpyAsync(rfirst, t.d_rfirst.get(), (uint64_t)s->batch.nreads * 4, hipMemcpyDeviceToHost, st));
+  if (longs) HIP_TRY(hipMemcpyAsync(longs, t.d_longs.get(), (uint64_t)tnlong * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   if (bases && nb) {
     HIP_TRY(hipMemcpyAsync(bases, t.d_bases.get(), nb, hipMemcpyDeviceToHost, st));
