@@ -798,6 +798,20 @@ KR_API void kr_place_text_counters(uint64_t* device_ranges, uint64_t* fallback_r
  * [0..9] only grow.  For tests (KR_DEBUG_PLACE_CAPS lowers the capacities). */
 #define KR_PLACE_PATHS 20
 KR_API void kr_place_path_counters(uint64_t* out, uint32_t n);
+/* Tests (no device needed): the constants the per-read kernel of `place` is compiled with: out8 = {leaves of a read the LDS arrays hold
+ * (kPlLeaves), distinct ancestors (kPlNodes), leaves an ancestor's lane handles at a time (kPlBlock), (leaf, ancestor) weights a wave's
+ * global scratch holds (kPlChain), candidate slots a wave takes at a time (kPlChunk), the factor of the chained threshold (weights go
+ * through the scratch where their number exceeds factor * leaves), most leaves of a read whose ancestor lanes walk their own run of
+ * the leaf list, the multiple of kPlChain a wave of the first launch has for a read it does in global scratch}. */
+KR_API int kr_debug_place_layout(uint32_t* out8);
+/* Tests: path witnesses of the per-read kernel of `place`, counted only in calls made under KR_DEBUG_PLACE_PATHS=1 (read per call) and
+ * summed over the ranges finished in this process (the last attempt of each): the first min(n, 12) into `out`, in this order -- reads
+ * whose (leaf, ancestor) weights went through global scratch, whose weights were walked on a shallow tree, walked because they exceed
+ * the scratch, whose histograms were re-read from the records, whose ancestor lanes walked the whole leaf list, with a record dropped
+ * for a later one on its node, single placements, reads stopped by the tau gate of their closest leaf, reads finished with their arrays
+ * in the first launch's LDS, in global scratch by the first launch, by the second launch, ancestor lanes that took more than one block
+ * of leaves.  All but the single placements and the tau gate count reads of two leaves or more that got their candidate slots. */
+KR_API void kr_debug_place_paths(uint64_t* out, uint32_t n);
 /* `tabular`: 0 jplace, 1 --tabular, 2 --summarize (no per-read text; feed the placements to
  * kr_place_summary_add).  place --summarize (src/krepp.cpp:466-471,493-497): `wcount` has
  * kr_place_tree_nnodes + 1 doubles, zeroed by the caller before the first batch and indexed by edge + 1. */

@@ -126,7 +126,7 @@ EXPORTS = [
     "kr_debug_front_end", "kr_debug_stream_move", "kr_debug_stream_addrs", "kr_debug_item_placement", "kr_debug_brent", "kr_debug_prefix", "kr_debug_colour_classes", "kr_llh_batch", "kr_llh_eval_indexed", "kr_batch_timing",
     "kr_place_tree_create", "kr_place_tree_create_lineage", "kr_place_tree_nnodes", "kr_place_summary_add",
     "kr_place_summary_text", "kr_place_tree_free", "kr_place_tree_kinds", "kr_place_batch", "kr_place_stream", "kr_place_stream_parsed", "kr_debug_place_ids", "kr_place_frame", "kr_place_counters",
-    "kr_debug_last_d2h_bytes", "kr_debug_indexed_list", "kr_debug_select", "kr_debug_select_check", "kr_debug_select_layout", "kr_debug_acc_paths", "kr_debug_acc_layout", "kr_debug_scan_layout", "kr_debug_scan_stream", "kr_debug_place_fixed5", "kr_place_text_counters", "kr_place_path_counters", "kr_fastx_open", "kr_fastx_open_at", "kr_fastx_next", "kr_fastx_detach", "kr_fastx_release", "kr_fastx_close", "kr_fastx_parallel_chunks", "kr_fastx_pgz_stats", "kr_format_dist", "kr_debug_fixed5", "kr_free", "kr_host_alloc", "kr_host_free",
+    "kr_debug_last_d2h_bytes", "kr_debug_indexed_list", "kr_debug_select", "kr_debug_select_check", "kr_debug_select_layout", "kr_debug_acc_paths", "kr_debug_acc_layout", "kr_debug_scan_layout", "kr_debug_scan_stream", "kr_debug_place_fixed5", "kr_place_text_counters", "kr_place_path_counters", "kr_debug_place_layout", "kr_debug_place_paths", "kr_fastx_open", "kr_fastx_open_at", "kr_fastx_next", "kr_fastx_detach", "kr_fastx_release", "kr_fastx_close", "kr_fastx_parallel_chunks", "kr_fastx_pgz_stats", "kr_format_dist", "kr_debug_fixed5", "kr_free", "kr_host_alloc", "kr_host_free",
     "kr_build_index", "kr_minimizers_cpu", "kr_minimizers_device", "kr_minimizers_free", "kr_last_error", "kr_version",
     "kr_sdust_cpu", "kr_sdust_free",
     "kr_stream_seek_enable", "kr_batch_collect_seek", "kr_debug_seek_layout", "kr_debug_seek_ms",
@@ -1078,6 +1078,32 @@ def place_path_counters():
     return dict(zip(PLACE_PATHS, (int(v) for v in out)))
 
 
+# kr_debug_place_paths: the path witnesses of place_read, in the order of PlaceCnt's kPlWitChained .. (kr_dev_place.inc)
+PLACE_WITNESSES = ("chained", "walked_shallow", "walked_deep", "wide", "runs_off", "dup_dropped", "single", "tau_stopped", "home_lds",
+                   "home_inline", "home_second", "multi_block_lanes")
+PLACE_LAYOUT = ("leaves", "nodes", "block", "chain", "chunk", "chain_factor", "runs_leaves", "inline_chain")
+
+
+def place_paths():
+    """(tests) kr_debug_place_paths: {name: count} of place_read's path witnesses, summed over this process's `place` calls made under
+    KR_DEBUG_PLACE_PATHS=1 (they only grow: take differences)."""
+    out = (C.c_uint64 * len(PLACE_WITNESSES))()
+    lib = load()
+    lib.kr_debug_place_paths.restype = None
+    lib.kr_debug_place_paths.argtypes = [C.POINTER(C.c_uint64), C.c_uint32]
+    lib.kr_debug_place_paths(out, len(PLACE_WITNESSES))
+    return dict(zip(PLACE_WITNESSES, (int(v) for v in out)))
+
+
+def place_layout():
+    """(tests) kr_debug_place_layout: the constants of the per-read kernel of `place` (no device needed)"""
+    a = (C.c_uint32 * 8)()
+    lib = load()
+    lib.kr_debug_place_layout.argtypes = [u32p]
+    check(lib.kr_debug_place_layout(a))
+    return dict(zip(PLACE_LAYOUT, (int(v) for v in a)))
+
+
 def place_heavy_reads():
     """Reads (upper bound, in chunks of 8) that kr_place_kernel's second launch did with its arrays in global scratch."""
     c = C.c_uint64(0)
@@ -1162,8 +1188,9 @@ class Placer:
     """`krepp place` on one GPU: placement tree + device index (uploaded with the tree's node kinds) + stream."""
 
     def __init__(self, host_index, nwk_text=None, device=0, tabular=False, max_reads=1 << 16, max_bases=None, lineage_text=None,
-                 **place_opts):
-        """tabular: False/0 jplace, True/1 --tabular, 2 --summarize; lineage_text: -l instead of a Newick tree"""
+                 max_records=None, **place_opts):
+        """tabular: False/0 jplace, True/1 --tabular, 2 --summarize; lineage_text: -l instead of a Newick tree; max_records: the
+        stream's record slots (default: 128 a read)"""
         self.lib = load()
         self.hx = host_index
         self.tabular = tabular
@@ -1181,7 +1208,7 @@ class Placer:
         # options of `place` (filter defaults to on: src/krepp.cpp:593-630)
         self.popts = default_params(no_filter=0, **place_opts)
         front = default_params(hdist_th=self.popts.hdist_th)  # multi, no_filter, no dist-max: every chosen leaf
-        self.st = self.dx.stream(params=front, max_reads=max_reads, max_bases=max_bases, max_records=max_reads * 128)
+        self.st = self.dx.stream(params=front, max_reads=max_reads, max_bases=max_bases, max_records=max_reads * 128 if max_records is None else int(max_records))
         self.prev = C.c_int(0)
 
     def frame(self, which, invocation="", total=0):

@@ -257,6 +257,9 @@ enum PlacePath : uint32_t {
   kPathLastTextFlags, kPathLastAttempts, kPathCount
 };
 extern std::atomic<uint64_t> g_place_paths[kPathCount];
+// place_read's path witnesses (kr_dev_place.inc: kPlWitChained ..), summed over the ranges finished in this process: kr_debug_place_paths
+constexpr uint32_t kPlaceWitCount = 12;
+extern std::atomic<uint64_t> g_place_wit[kPlaceWitCount];
 
 } // namespace kr
 

@@ -40,8 +40,26 @@ enum PlaceCnt : uint32_t { // the counters of PlaceOut::cnt (pl_cnt below), clea
   kPlListSlots = 12,   // entries of the internal candidates' list handed out (k_se until the compaction)
   kPlBigOut = 13,      // ... of the listed big reads handed out
   kPlInlineReads = 14, // reads beyond the LDS arrays done at once in global scratch by the first launch
-  kPlCntCount = 16     // lines allocated
+  // 15 .. 26: path witnesses of place_read, counted by lane 0 in the WIT instantiations only (launched under KR_DEBUG_PLACE_PATHS=1;
+  // kr_debug_place_paths, names: PLACE_WITNESSES in krepp_amd/capi.py).  A read is counted where it is FINISHED -- a read that exceeds the arrays of one home
+  // counts in the home that does it -- and only if it has two leaves or more and got its candidate slots, but for the two early exits.
+  kPlWitChained = 15,       // reads whose (leaf, ancestor) weights went through the wave's global scratch
+  kPlWitWalkedShallow = 16, // reads whose weights were walked: tot_chain <= kPlChainFactor * nl
+  kPlWitWalkedDeep = 17,    // ... tot_chain beyond the chain scratch of the read's home
+  kPlWitWide = 18,          // reads whose histograms were re-read from the records (a count above 255, or th >= 8)
+  kPlWitRunsOff = 19,       // reads whose ancestor lanes walked the whole leaf list (more than kPlRunsLeaves leaves)
+  kPlWitDup = 20,           // reads with a record dropped for a later one on the same node
+  kPlWitSingle = 21,        // single placements (one leaf)
+  kPlWitTau = 22,           // reads stopped by the tau gate of their closest leaf
+  kPlWitLds = 23,           // reads finished with their arrays in the first launch's LDS
+  kPlWitInline = 24,        // ... in global scratch by a wave of the first launch
+  kPlWitSecond = 25,        // ... by the second launch (dynamic LDS or global scratch)
+  kPlWitMultiBlock = 26,    // ancestor lanes whose walk took more than one block of kPlBlock leaves
+  kPlWitEnd = 27,
+  kPlCntCount = 32     // lines allocated
 };
+constexpr uint32_t kPlChainFactor = 12;  // the weights go through global scratch only where tot_chain > kPlChainFactor * leaves (place_read: chained)
+constexpr uint32_t kPlRunsLeaves = 4096; // most leaves of a read whose ancestor words still carry their first leaf (place_read: runs)
 enum PlaceFlag : uint32_t {
   kPlFlagLimits = 1u,  // a read exceeded even the global arrays (cannot happen: they hold the whole tree)
   kPlFlagCandCap = 2u, // out of candidate slots
@@ -54,6 +72,7 @@ __host__ __device__ __forceinline__ uint32_t& pl_cnt(uint32_t* cnt, uint32_t slo
 #endif
 constexpr uint32_t kPlReadChunk = KR_PL_READ_CHUNK; // reads a wave of the first launch takes at a time (kPlReadsOut)
 constexpr uint32_t kPlChain = 8192; // (leaf, ancestor) weights of one read held in the wave's global scratch (more: they are recomputed by walking up)
+constexpr uint32_t kPlInlineChain = 4; // a wave of the first launch that does an over-limit read in global scratch has kPlInlineChain * kPlChain weights for it
 constexpr uint32_t kPlChunk = 128;   // candidate slots a wave takes at a time (every wave leaves part of one unused: the host copies slots)
 
 struct PlaceTree {
@@ -148,11 +167,15 @@ struct PlaceArrays {
 // NPT = th + 1 where the launch knows it (5 by default): the histograms' loops unroll and the two LlhProblem of a lane stay in
 // registers -- with a run-time bound they are indexed dynamically and live in scratch MEMORY, which made every `mc[x] += ...`
 // of the ancestors' loop a round trip (80 % of the kernel on the 1000-genome tree).  NPT = 0: any th.
-template <typename M, int NPT>
+// WIT: the path witnesses are counted.  A template parameter and not a flag in PlaceOut: every form of run-time flag tried -- even one
+// that guarded two atomics in the early exits -- moved the register allocation of some instantiation (docs/design/06_place.md), so the
+// kernels that are launched without KR_DEBUG_PLACE_PATHS are compiled from the text they had before, and the switch is the host's.
+template <typename M, int NPT, bool WIT>
 __device__ __forceinline__ bool place_read(const LlhConst& C, const DevIndex& ix, const BatchOut& o, uint32_t r, const uint32_t* read_len,
                                            const PlaceTree& T, const PlaceOut& po, uint32_t tau, uint32_t no_filter, const PlaceArrays<M>& A,
-                                           lds_u32* s_n, uint32_t& c_pos, uint32_t& c_end, uint32_t& i_pos, uint32_t& i_end, double* chain, uint32_t chain_cap)
-{
+                                           lds_u32* s_n, uint32_t& c_pos, uint32_t& c_end, uint32_t& i_pos, uint32_t& i_end, double* chain, uint32_t chain_cap,
+                                           uint32_t home)
+{ // home: the witness slot of the arrays' home (kPlWitLds, kPlWitInline, kPlWitSecond)
   const uint32_t lane = lane_id(), np = NPT ? (uint32_t)NPT : C.th + 1;
   const double kMax = 1.7976931348623157e308;
   const uint32_t ro = o.rd_off[r], n = o.rd_cnt[r];
@@ -199,6 +222,7 @@ __device__ __forceinline__ bool place_read(const LlhConst& C, const DevIndex& ix
     d_c = o.rec_d[cl], v_c = o.rec_v[cl];
     closest_pt = (kcl >> 1) <= T.nidx ? T.idx_to_pt[kcl >> 1] : 0u;
     go = no_filter || leq > 1.0; // src/query.cpp:220
+    if (WIT && !go && lane == 0) atomicAdd(&pl_cnt(po.cnt, kPlWitTau), 1u);
   }
   // ---- the read's leaves on the placement tree: the chosen record of every leaf (rec_sel)
   uint32_t nl = 0;
@@ -234,6 +258,7 @@ __device__ __forceinline__ bool place_read(const LlhConst& C, const DevIndex& ix
         po.c_se[c0] = closest_pt ? closest_pt : 0x7FFFFFFFu, po.c_read[c0] = r | (2u << 30), po.c_d[c0] = d_c, po.c_v[c0] = v_c, po.c_chisq[c0] = 0.0;
       c_pos += 1;
       info = (1u << 31) | (1u << 30) | 1u;
+      if (WIT && lane == 0) atomicAdd(&pl_cnt(po.cnt, kPlWitSingle), 1u);
     }
     go = false;
   }
@@ -245,6 +270,7 @@ __device__ __forceinline__ bool place_read(const LlhConst& C, const DevIndex& ix
   }
   KR_PL_MARK(0); // closest, leaves gathered, single placement
   uint32_t na = 0;
+  uint32_t wit_dup = 0, wit_multi = 0; // (WIT only, per lane: records dropped for a later one on their node; ancestors whose walk took more than one block)
   bool wide = false; // wave-uniform: some count of some leaf does not fit the packed histogram
   bool runs = false; // wave-uniform: the ancestors' words carry their first leaf
   typename M::u32p hpk = (typename M::u32p)A.lmatch; // [2 * leaves]
@@ -285,12 +311,15 @@ __device__ __forceinline__ bool place_read(const LlhConst& C, const DevIndex& ix
     for (uint32_t e = lane; e < nl; e += kWave) A.li0[e] = (e + 1 < nl && A.lq1[e + 1] == A.lq1[e]) ? 1u : 0u;
     M::sync();
     for (uint32_t e = lane; e < nl; e += kWave)
-      if (A.li0[e]) A.lq1[e] = 0;
+      if (A.li0[e]) {
+        A.lq1[e] = 0;
+        if (WIT) ++wit_dup;
+      }
     M::sync();
     KR_PL_MARK(1); // sort, per-leaf fields
     // (node numbers fit 20 bits -- trees of up to 65,536 leaves; with at most 4,096 leaves in the read the ancestor's word also
     //  says where its leaves start in the sorted list: they are a contiguous run, which its lane then walks instead of the list)
-    runs = nl <= 4096u && T.pn < (1u << 20);
+    runs = nl <= kPlRunsLeaves && T.pn < (1u << 20);
     // ---- distinct ancestors: leaf e lists the ancestors its predecessor is not below
     for (uint32_t e0 = 0; e0 < nl; e0 += kWave) {
       const uint32_t e = e0 + lane;
@@ -321,6 +350,7 @@ __device__ __forceinline__ bool place_read(const LlhConst& C, const DevIndex& ix
   //      leaves again (on a 1000-leaf tree: 33 leaves x 25 levels of fp64 divisions per ancestor lane, 34 ms per 400,000 reads)
   KR_PL_MARK(2); // ancestors listed
   bool chained = false;
+  bool chain_over = false; // (witnesses: the weights are walked because they exceed the scratch, not because the tree is shallow)
   if (go) {
     uint32_t tot_chain = 0;
     for (uint32_t e0 = 0; e0 < nl; e0 += kWave) {
@@ -333,7 +363,8 @@ __device__ __forceinline__ bool place_read(const LlhConst& C, const DevIndex& ix
     }
     // (on a shallow tree the walk is a handful of divisions: cheaper than a round trip through the wave's global scratch --
     //  the 25-leaf toy tree lost a factor of two to it)
-    chained = tot_chain <= chain_cap && tot_chain > 12u * nl;
+    chained = tot_chain <= chain_cap && tot_chain > kPlChainFactor * nl;
+    chain_over = tot_chain > chain_cap;
     M::sync();
     if (chained) {
       for (uint32_t e = lane; e < nl; e += kWave) {
@@ -414,7 +445,9 @@ __device__ __forceinline__ bool place_read(const LlhConst& C, const DevIndex& ix
         // ... in blocks of kPlBlock leaves: the weights of a block's members -- one load each from the wave's global scratch, half a
         // microsecond away -- are requested together and then used in leaf order (a lane near the root has hundreds of leaves)
         bool past = false; // a leaf beyond the run has been seen
+        uint32_t wit_blocks = 0;
         for (uint32_t e0 = runs ? aw >> 20 : 0u; e0 < nl && !past; e0 += kPlBlock) {
+          if (WIT) ++wit_blocks;
           double dn[kPlBlock];
           uint32_t w0[kPlBlock], w1[kPlBlock];
           bool mem[kPlBlock];
@@ -465,6 +498,7 @@ __device__ __forceinline__ bool place_read(const LlhConst& C, const DevIndex& ix
             a_rho = a_rho > A.lrho[e] ? a_rho : A.lrho[e];
           }
         }
+        if (WIT && wit_blocks > 1u) ++wit_multi;
         if (T.elig[a]) {
           double leq = 0;
 #pragma unroll
@@ -505,6 +539,17 @@ __device__ __forceinline__ bool place_read(const LlhConst& C, const DevIndex& ix
     KR_PL_MARK(5); // ancestors accumulated and emitted
     c_pos += emitted; // (room for nl + na was made sure of; what was not used serves the wave's next read)
     info = (1u << 31) | emitted;
+    if (WIT) { // path witnesses: the read is finished here, in this home; the two per-lane counts were made where the loops ran
+      const uint32_t ndup = wave_sum_u32(wit_dup), nmulti = wave_sum_u32(wit_multi);
+      if (lane == 0) {
+        atomicAdd(&pl_cnt(po.cnt, home), 1u);
+        atomicAdd(&pl_cnt(po.cnt, chained ? kPlWitChained : (chain_over ? kPlWitWalkedDeep : kPlWitWalkedShallow)), 1u);
+        if (wide) atomicAdd(&pl_cnt(po.cnt, kPlWitWide), 1u);
+        if (!runs) atomicAdd(&pl_cnt(po.cnt, kPlWitRunsOff), 1u);
+        if (ndup) atomicAdd(&pl_cnt(po.cnt, kPlWitDup), 1u);
+        if (nmulti) atomicAdd(&pl_cnt(po.cnt, kPlWitMultiBlock), nmulti);
+      }
+    }
   }
   if (!over && lane == 0) po.rd_c0[r] = c0, po.rd_info[r] = info;
   M::sync();
@@ -530,7 +575,7 @@ __global__ __launch_bounds__(256) void kr_place_big_first_kernel(BatchOut o, uin
 // HEAVY = false: every read of the batch, arrays in LDS; a read with more leaves or ancestors than they hold is put on the
 // heavy list (po.heavy, counted in pl_cnt(po.cnt, kPlHeavySlots)).  HEAVY = true (second launch): the listed reads, arrays in the wave's
 // global scratch, sized for the whole tree.
-template <bool HEAVY, int NPT>
+template <bool HEAVY, int NPT, bool WIT>
 __global__ __launch_bounds__(kWave) void kr_place_kernel(LlhConst C, DevIndex ix, BatchOut o, uint32_t nreads, const uint32_t* read_len,
                                                          PlaceTree T, PlaceOut po, uint32_t tau, uint32_t no_filter)
 {
@@ -556,11 +601,11 @@ __global__ __launch_bounds__(kWave) void kr_place_kernel(LlhConst C, DevIndex ix
                                    sd, sd + po.heavy_leaves, su + 4ull * po.heavy_leaves, po.heavy_leaves, po.heavy_nodes};
     uint32_t n_inline = 0;
     auto one_read = [&](uint32_t r) {
-      if (place_read<PlaceLdsMem, NPT>(C, ix, o, r, read_len, T, po, tau, no_filter, A, (lds_u32*)&s_n, c_pos, c_end, i_pos, i_end, po.chain + (uint64_t)blockIdx.x * po.chain_cap, po.chain_cap))
+      if (place_read<PlaceLdsMem, NPT, WIT>(C, ix, o, r, read_len, T, po, tau, no_filter, A, (lds_u32*)&s_n, c_pos, c_end, i_pos, i_end, po.chain + (uint64_t)blockIdx.x * po.chain_cap, po.chain_cap, kPlWitLds))
         return;
       if (has_scratch) {
         ++n_inline;
-        if (!place_read<PlaceGlobalMem, NPT>(C, ix, o, r, read_len, T, po, tau, no_filter, AG, (lds_u32*)&s_n, c_pos, c_end, i_pos, i_end, po.chain_inline + (uint64_t)blockIdx.x * po.chain_inline_cap, po.chain_inline_cap))
+        if (!place_read<PlaceGlobalMem, NPT, WIT>(C, ix, o, r, read_len, T, po, tau, no_filter, AG, (lds_u32*)&s_n, c_pos, c_end, i_pos, i_end, po.chain_inline + (uint64_t)blockIdx.x * po.chain_inline_cap, po.chain_inline_cap, kPlWitInline))
           if (lane_id() == 0) atomicOr(&pl_cnt(po.cnt, kPlFlags), kPlFlagLimits); // (cannot happen: the arrays hold the whole tree)
         return;
       }
@@ -611,7 +656,7 @@ __global__ __launch_bounds__(kWave) void kr_place_kernel(LlhConst C, DevIndex ix
     for (uint32_t j = blockIdx.x; j < nh; j += gridDim.x) {
       const uint32_t r = (uint32_t)__builtin_amdgcn_readfirstlane((int)po.heavy[j]);
       if (r == 0xFFFFFFFFu) continue;
-      if (!place_read<PlaceLdsMem, NPT>(C, ix, o, r, read_len, T, po, tau, no_filter, A, (lds_u32*)&s_n, c_pos, c_end, i_pos, i_end, po.chain + (uint64_t)blockIdx.x * po.chain_cap_heavy, po.chain_cap_heavy))
+      if (!place_read<PlaceLdsMem, NPT, WIT>(C, ix, o, r, read_len, T, po, tau, no_filter, A, (lds_u32*)&s_n, c_pos, c_end, i_pos, i_end, po.chain + (uint64_t)blockIdx.x * po.chain_cap_heavy, po.chain_cap_heavy, kPlWitSecond))
         if (lane_id() == 0) atomicOr(&pl_cnt(po.cnt, kPlFlags), kPlFlagLimits); // (cannot happen: the arrays hold the whole tree)
     }
   } else {
@@ -624,7 +669,7 @@ __global__ __launch_bounds__(kWave) void kr_place_kernel(LlhConst C, DevIndex ix
     for (uint32_t j = blockIdx.x; j < nh; j += gridDim.x) {
       const uint32_t r = (uint32_t)__builtin_amdgcn_readfirstlane((int)po.heavy[j]);
       if (r == 0xFFFFFFFFu) continue;
-      if (!place_read<PlaceGlobalMem, NPT>(C, ix, o, r, read_len, T, po, tau, no_filter, A, (lds_u32*)&s_n, c_pos, c_end, i_pos, i_end, po.chain + (uint64_t)blockIdx.x * po.chain_cap_heavy, po.chain_cap_heavy))
+      if (!place_read<PlaceGlobalMem, NPT, WIT>(C, ix, o, r, read_len, T, po, tau, no_filter, A, (lds_u32*)&s_n, c_pos, c_end, i_pos, i_end, po.chain + (uint64_t)blockIdx.x * po.chain_cap_heavy, po.chain_cap_heavy, kPlWitSecond))
         if (lane_id() == 0) atomicOr(&pl_cnt(po.cnt, kPlFlags), kPlFlagLimits); // (cannot happen: the arrays hold the whole tree)
     }
   }

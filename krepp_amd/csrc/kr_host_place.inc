@@ -150,7 +150,7 @@ int place_begin_common(kr_stream* s, const void* tree_tag, const kr::PlaceTreeAr
     const uint32_t cwaves = std::max(grid, 1024u);
     if (!w.d_chain.get() || cwaves > w.chain_waves) { // the weights of every (leaf, ancestor) pair of a read: kPlChain doubles per wave of either launch
       // (+ a larger piece for each wave that may do an over-limit read itself: PlaceOut::chain_inline)
-      if ((rc = place_renew(w.d_chain, (uint64_t)cwaves * kPlChain + 1024ull * 4ull * kPlChain))) return rc;
+      if ((rc = place_renew(w.d_chain, (uint64_t)cwaves * kPlChain + 1024ull * kPlInlineChain * kPlChain))) return rc;
       w.chain_cap = kPlChain, w.chain_waves = cwaves;
     }
     const uint32_t hl = std::max<uint32_t>(kPlLeaves, s->ix->dix.nleaves), hn = std::max<uint32_t>(kPlNodes, T.pn);
@@ -253,7 +253,9 @@ int kr::place_device_launch(kr_stream* s, const kr::PlaceTreeArrays& T, uint32_t
               w.d_kse.get(), w.d_kd.get(), w.d_kv.get(), w.d_kchi.get(), (uint32_t)std::min<uint64_t>(place_keep_slots(w), 0xFFFFFFFFull), w.d_chain.get(), w.chain_cap,
               w.chain_cap * std::max<uint32_t>(1u, w.chain_waves / std::max<uint32_t>(1u, w.heavy_waves)), heavy_lds ? 1u : 0u,
               (uint32_t)((uint64_t)n + 8ull * grid), 0u, big_first ? std::min<uint32_t>(std::min<uint32_t>(w.heavy_waves, grid), 1024u) : 0u,
-              w.d_chain.get() + (uint64_t)w.chain_waves * w.chain_cap, 4u * w.chain_cap, 0u};
+              w.d_chain.get() + (uint64_t)w.chain_waves * w.chain_cap, kPlInlineChain * w.chain_cap, 0u};
+  const char* wit_env = getenv("KR_DEBUG_PLACE_PATHS"); // tests: the instantiations of kr_place_kernel that count their paths (read per call)
+  const bool witness = wit_env && atoi(wit_env) != 0;
   PO.lcap = w.dbg_list ? (uint32_t)std::min<uint64_t>(w.dbg_list, PO.kcap) : PO.kcap;
   if (const char* e = getenv("KR_DEBUG_PLACE_LDS")) { // tests: "leaves,nodes" the LDS launch accepts, so that small trees have heavy reads
     unsigned a = kPlLeaves, b = kPlNodes;
@@ -263,17 +265,21 @@ int kr::place_device_launch(kr_stream* s, const kr::PlaceTreeArrays& T, uint32_t
   if (PO.inline_waves) hipLaunchKernelGGL(kr_place_big_first_kernel, dim3(std::min<uint32_t>((n + 255u) / 256u, 2048u)), dim3(256), 0, st, ro, n, PO);
   // (th = 4, the default: the instantiations whose histogram loops are unrolled, kr_dev_place.inc.  Second launch: the heavy reads the
   //  first one listed -- their number is final at the kernel boundary; usually none: the waves leave at once)
-#define KR_PLACE_LAUNCH(NPV)  \
+#define KR_PLACE_LAUNCH(NPV, W)  \
   do {  \
-      hipLaunchKernelGGL((kr_place_kernel<false, NPV>), dim3(grid), dim3(kWave), 0, st, s->llh, s->ix->dix, ro, n, d_len, PT, PO, tau, no_filter ? 1u : 0u);  \
-      hipLaunchKernelGGL((kr_place_kernel<true, NPV>), dim3(w.heavy_waves), dim3(kWave), heavy_lds ? heavy_lds_bytes : 0u, st, s->llh, s->ix->dix, ro, n, d_len, PT, PO, tau, no_filter ? 1u : 0u);  \
+      hipLaunchKernelGGL((kr_place_kernel<false, NPV, W>), dim3(grid), dim3(kWave), 0, st, s->llh, s->ix->dix, ro, n, d_len, PT, PO, tau, no_filter ? 1u : 0u);  \
+      hipLaunchKernelGGL((kr_place_kernel<true, NPV, W>), dim3(w.heavy_waves), dim3(kWave), heavy_lds ? heavy_lds_bytes : 0u, st, s->llh, s->ix->dix, ro, n, d_len, PT, PO, tau, no_filter ? 1u : 0u);  \
       hipLaunchKernelGGL((kr_place_brent_kernel<NPV>), dim3(cus * 8u), dim3(256), 0, st, s->llh, PO);  \
       hipLaunchKernelGGL((kr_place_llh_kernel<NPV>), dim3(cus * 8u), dim3(256), 0, st, s->llh, PO);  \
   } while (0)
-  if (s->llh.th == 4)
-    KR_PLACE_LAUNCH(5);
+  if (s->llh.th == 4 && !witness)
+    KR_PLACE_LAUNCH(5, false);
+  else if (!witness)
+    KR_PLACE_LAUNCH(0, false);
+  else if (s->llh.th == 4)
+    KR_PLACE_LAUNCH(5, true);
   else
-    KR_PLACE_LAUNCH(0);
+    KR_PLACE_LAUNCH(0, true);
 #undef KR_PLACE_LAUNCH
   // (a wave of the compaction takes kept-candidate slots in chunks of kPlKeepChunk and leaves part of its last one unused, and what
   //  is copied back is every slot handed out: at least 64 reads to a wave, so that a 65,536-read batch does not copy 2 M slots back
@@ -343,6 +349,10 @@ int kr::place_device_finish(kr_stream* s, const kr::PlaceTreeArrays& T, uint32_t
     set(kr::kPathLastText, w.text_on ? w.h_ttotal.get()[0] : 0), set(kr::kPathLastCandCap, place_cand_slots(w)), set(kr::kPathLastKeepCap, place_keep_slots(w));
     set(kr::kPathLastTextCap, w.text_on ? place_text_bytes(w) : 0), set(kr::kPathLastFlags, pl_cnt(w.h_cnt.get(), kPlFlags));
     set(kr::kPathLastTextFlags, w.text_on ? w.h_ttotal.get()[1] : 0), set(kr::kPathLastAttempts, (uint64_t)attempt + 1);
+    // place_read's path witnesses of the range's last attempt (all 0 without KR_DEBUG_PLACE_PATHS=1): kr_debug_place_paths
+    static_assert(kPlWitEnd - kPlWitChained == kr::kPlaceWitCount && kPlWitEnd <= kPlCntCount, "kr_debug_place_paths: the names in krepp_amd/capi.py (PLACE_WITNESSES) follow PlaceCnt");
+    for (uint32_t k = 0; k < kr::kPlaceWitCount; ++k)
+      if (const uint32_t c = pl_cnt(w.h_cnt.get(), kPlWitChained + k)) kr::g_place_wit[k].fetch_add(c, std::memory_order_relaxed);
   }
   lap("place kernels (both launches, likelihoods, compaction) to their counters on the host");
   HIP_TRY(hipMemcpyAsync(w.h_c0.get() + r0, w.d_c0.get() + r0, (uint64_t)n * 4, hipMemcpyDeviceToHost, st));
@@ -515,6 +525,15 @@ void kr::place_call_begin(kr_stream* s)
 }
 uint32_t kr::place_parsed_nreads(const kr_stream* s) { return s && s->fq.on && s->parse.parsed && s->batch.submitted && s->batch.from.parsed ? s->parse.nreads : 0; }
 int kr::place_parsed_check(const kr_stream* s) { return s ? place_parsed_state(s) : kr::fail(KR_ERR_ARG, "kr_place_stream_parsed: null argument"); }
+
+extern "C" int kr_debug_place_layout(uint32_t* out8)
+{ // (krepp_amd.h: the order of the values; no device is touched)
+  kr::clear_error();
+  if (!out8) return kr::fail(KR_ERR_ARG, "kr_debug_place_layout: null argument");
+  const uint32_t v[8] = {kPlLeaves, kPlNodes, kPlBlock, kPlChain, kPlChunk, kPlChainFactor, kPlRunsLeaves, kPlInlineChain};
+  memcpy(out8, v, sizeof(v));
+  return KR_OK;
+}
 
 extern "C" int kr_debug_place_ids(kr_stream* s, char* ids, uint32_t* id_off)
 {

@@ -126,6 +126,7 @@ char* dup_text(const std::string& s, uint64_t* len)
 static std::atomic<uint64_t> g_place_device_batches{0}, g_place_host_batches{0}, g_place_heavy_reads{0};
 std::atomic<uint64_t> g_place_text_device{0}, g_place_text_fallback{0};
 std::atomic<uint64_t> kr::g_place_paths[kr::kPathCount] = {};
+std::atomic<uint64_t> kr::g_place_wit[kr::kPlaceWitCount] = {};
 
 extern "C" {
 
@@ -1195,6 +1196,11 @@ void kr_place_text_counters(uint64_t* device_ranges, uint64_t* fallback_ranges)
 void kr_place_path_counters(uint64_t* out, uint32_t n)
 { // (krepp_amd.h: the order of the values)
   for (uint32_t i = 0; out && i < n && i < kr::kPathCount; ++i) out[i] = kr::g_place_paths[i].load(std::memory_order_relaxed);
+}
+
+void kr_debug_place_paths(uint64_t* out, uint32_t n)
+{ // (krepp_amd.h: the order of the values)
+  for (uint32_t i = 0; out && i < n && i < kr::kPlaceWitCount; ++i) out[i] = kr::g_place_wit[i].load(std::memory_order_relaxed);
 }
 
 void kr_place_counters(uint64_t* device_batches, uint64_t* host_batches, uint64_t* heavy_reads)
