@@ -822,15 +822,20 @@ KR_API int kr_place_summary_text(const kr_place_tree*, const double* wcount, dou
 KR_API int kr_place_frame(const kr_place_tree*, int which, int tabular, const char* invocation, uint64_t total_qseq,
                           char** text, uint64_t* len);
 
-/* CPU-side index construction (`krepp index`, src/krepp.cpp:131-303): stays on the
- * CPU as in the reference; needed to make any index at all. */
+/* Index construction (`krepp index`, src/krepp.cpp:131-303); needed to make any index at all.  On the CPU by default, as in
+ * the reference.  `gpu_minimizers` is a bit set that moves stages to the GPU `device`, with identical files:
+ *   KR_BUILD_GPU_MINIMIZERS  the leaf stage (window minimizers of every genome; kr_minimizers_device)
+ *   KR_BUILD_GPU_KEYS        also the key stage: all genomes' keys stay in a device pool and are sorted and grouped there
+ *                            (kr_key_groups_device); implies the leaf stage.  The colours of the groups stay on the host. */
+#define KR_BUILD_GPU_MINIMIZERS 1u
+#define KR_BUILD_GPU_KEYS 2u
 typedef struct kr_build_params {
   uint32_t k, w, h, m, r, frac; /* defaults 29, 35, 13, 4, 1, 1 (src/krepp.hpp:47-58) */
   uint32_t num_threads;
   uint32_t seed;
   const uint8_t* ppos;          /* optional explicit LSH positions [h] (descending)    */
-  uint32_t gpu_minimizers;      /* 1: leaf stage (window minimizers) on the GPU `device`; */
-  int32_t device;               /*    identical output, checked by tests/test_minimizers.py */
+  uint32_t gpu_minimizers;      /* bit set KR_BUILD_GPU_*: 1 leaf stage, 2 key stage too, on the GPU `device`;     */
+  int32_t device;               /*    identical output, checked by tests/test_minimizers.py, test_gpu_build_keys.py */
   uint32_t sdust_t, sdust_w;    /* --sdust-t / --sdust-w (src/krepp.cpp:530-531,576-577): both > 0 keeps the sdust intervals  */
                                 /* of every contig out of the minimizer windows (src/rqseq.cpp:71-107); either 0: off    */
 } kr_build_params;
@@ -857,6 +862,28 @@ KR_API int kr_minimizers_cpu(const kr_build_params*, const uint8_t* bases, const
 KR_API int kr_minimizers_device(int device, const kr_build_params*, const uint8_t* bases, const uint64_t* offsets,
                                 uint32_t ncontigs, kr_minimizer_result* out);
 KR_API void kr_minimizers_free(kr_minimizer_result*);
+
+/* The key stage of the build on its own: n (key, leaf rank) pairs in any order, whole pairs possibly repeated, come back sorted by
+ * (key, rank) without duplicates and cut into groups of equal key, with the cumulative row counts of the inc-* file.
+ * KR_ERR_FORMAT ("row out of range") if a key's row is >= nrows; KR_ERR_ARG if a rank is >= nleaves or nleaves > 65536.
+ * _cpu is the builder's own host path (one comparison sort, one walk over the runs); _device is a least-significant-digit
+ * radix sort (8-bit digits, the rank's first, only digits that can differ) and a flag / scan / scatter grouping on the GPU and
+ * must return identical arrays. */
+typedef struct kr_key_groups {
+  uint64_t* keys;    /* [nkeys]  distinct keys, ascending: (row << 32) | enc32                              */
+  uint64_t* goff;    /* [nkeys + 1] group i owns ranks[goff[i] .. goff[i+1])                                  */
+  uint32_t* ranks;   /* [npairs] leaf ranks of a group ascending, each once                                   */
+  uint64_t* inc;     /* [nrows]  number of distinct keys with row <= r (what inc-* holds)                     */
+  uint64_t nkeys, npairs;
+  uint32_t nrows;
+} kr_key_groups;
+KR_API int kr_key_groups_cpu(const uint64_t* keys, const uint32_t* ranks, uint64_t n, uint32_t nrows, uint32_t nleaves, kr_key_groups* out);
+KR_API int kr_key_groups_device(int device, const uint64_t* keys, const uint32_t* ranks, uint64_t n, uint32_t nrows, uint32_t nleaves, kr_key_groups* out);
+KR_API void kr_key_groups_free(kr_key_groups*);
+/* Tests: the calling process's last kr_key_groups_device or GPU key build (KR_BUILD_GPU_KEYS): {pairs in, pairs out, keys out,
+ * radix passes run, pool growths, path taken (1 device, 2 fell back to the host for memory, 3 fell back for more than 65,536
+ * leaves), pairs per tile of the sort, 0}. */
+KR_API void kr_debug_build_keys(uint64_t out[8]);
 
 /* The masker on its own: per contig the list that the reference's sdust(0, seq, -1, T, W, &n) (src/sdust.h) returns, element for
  * element: intervals[offsets[c] .. offsets[c+1]) = (start << 32 | finish), finish exclusive.  Its alphabet is sdust's own (bytes

@@ -98,6 +98,11 @@ class KrBuildParams(C.Structure):
                 ("gpu_minimizers", C.c_uint32), ("device", C.c_int32), ("sdust_t", C.c_uint32), ("sdust_w", C.c_uint32)]
 
 
+class KrKeyGroups(C.Structure):
+    _fields_ = [("keys", u64p), ("goff", u64p), ("ranks", u32p), ("inc", u64p), ("nkeys", C.c_uint64), ("npairs", C.c_uint64),
+                ("nrows", C.c_uint32)]
+
+
 class KrSdustResult(C.Structure):
     _fields_ = [("intervals", u64p), ("offsets", u64p), ("ncontigs", C.c_uint32)]
 
@@ -129,6 +134,7 @@ EXPORTS = [
     "kr_debug_last_d2h_bytes", "kr_debug_indexed_list", "kr_debug_select", "kr_debug_select_check", "kr_debug_select_layout", "kr_debug_acc_paths", "kr_debug_acc_layout", "kr_debug_scan_layout", "kr_debug_scan_stream", "kr_debug_place_fixed5", "kr_place_text_counters", "kr_place_path_counters", "kr_debug_place_layout", "kr_debug_place_paths", "kr_fastx_open", "kr_fastx_open_at", "kr_fastx_next", "kr_fastx_detach", "kr_fastx_release", "kr_fastx_close", "kr_fastx_parallel_chunks", "kr_fastx_pgz_stats", "kr_format_dist", "kr_debug_fixed5", "kr_free", "kr_host_alloc", "kr_host_free",
     "kr_build_index", "kr_minimizers_cpu", "kr_minimizers_device", "kr_minimizers_free", "kr_last_error", "kr_version",
     "kr_sdust_cpu", "kr_sdust_free",
+    "kr_key_groups_cpu", "kr_key_groups_device", "kr_key_groups_free", "kr_debug_build_keys",
     "kr_stream_seek_enable", "kr_batch_collect_seek", "kr_debug_seek_layout", "kr_debug_seek_ms",
     "kr_stream_bgzf_enable", "kr_batch_submit_bgzf", "kr_debug_bgzf_inflate", "kr_debug_bgzf_inflate_host", "kr_debug_bgzf_ms",
     "kr_bgzf_member_size", "kr_bgzf_walk", "kr_bgzf_chunk_cut", "kr_fastx_open_at_bgzf",
@@ -1111,12 +1117,61 @@ def place_heavy_reads():
     return int(c.value)
 
 
+KR_BUILD_GPU_MINIMIZERS, KR_BUILD_GPU_KEYS = 1, 2  # bits of kr_build_params.gpu_minimizers
+
+
+def _gpu_build_bits(gpu_minimizers, gpu_keys):
+    return (KR_BUILD_GPU_MINIMIZERS if gpu_minimizers else 0) | (KR_BUILD_GPU_MINIMIZERS | KR_BUILD_GPU_KEYS if gpu_keys else 0)
+
+
+def key_groups(keys, ranks, nrows, nleaves, device=None, copy=True):
+    """The key stage on its own: dict(keys, goff, ranks, inc) of the (key, rank) pairs: kr_key_groups_cpu (device=None) or _device.
+    copy=False: the arrays are views of the library's memory (an inc of 2^30 rows is 8 GB), valid until the dict's "free"() is called."""
+    lib = load()
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    ranks = np.ascontiguousarray(ranks, dtype=np.uint32)
+    assert len(keys) == len(ranks)
+    res = KrKeyGroups()
+    vp = C.c_void_p
+    kp = keys.ctypes.data if len(keys) else None
+    rp = ranks.ctypes.data if len(ranks) else None
+    lib.kr_key_groups_cpu.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(KrKeyGroups)]
+    lib.kr_key_groups_device.argtypes = [C.c_int, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(KrKeyGroups)]
+    lib.kr_key_groups_free.argtypes = [C.POINTER(KrKeyGroups)]
+    lib.kr_key_groups_free.restype = None
+    if device is None:
+        check(lib.kr_key_groups_cpu(kp, rp, len(keys), nrows, nleaves, C.byref(res)))
+    else:
+        check(lib.kr_key_groups_device(int(device), kp, rp, len(keys), nrows, nleaves, C.byref(res)))
+    if not copy:
+        view = lambda ptr, n, dt: np.ctypeslib.as_array(ptr, shape=(int(n),)).view(dt) if n and ptr else np.zeros(0, dtype=dt)
+        return {"keys": view(res.keys, res.nkeys, np.uint64), "goff": view(res.goff, res.nkeys + 1, np.uint64),
+                "ranks": view(res.ranks, res.npairs, np.uint32), "inc": view(res.inc, res.nrows, np.uint64),
+                "free": lambda: lib.kr_key_groups_free(C.byref(res))}
+    out = {"keys": _np(res.keys, res.nkeys, np.uint64), "goff": _np(res.goff, res.nkeys + 1, np.uint64),
+           "ranks": _np(res.ranks, res.npairs, np.uint32), "inc": _np(res.inc, res.nrows, np.uint64)}
+    lib.kr_key_groups_free(C.byref(res))
+    return out
+
+
+def build_keys_stats():
+    """kr_debug_build_keys: the process's last kr_key_groups_device or GPU key build."""
+    v = (C.c_uint64 * 8)()
+    lib = load()
+    lib.kr_debug_build_keys.argtypes = [C.POINTER(C.c_uint64 * 8)]
+    lib.kr_debug_build_keys.restype = None
+    lib.kr_debug_build_keys(C.byref(v))
+    return {"pairs_in": int(v[0]), "pairs_out": int(v[1]), "keys_out": int(v[2]), "passes": int(v[3]), "pool_growths": int(v[4]),
+            "path": int(v[5]), "tile": int(v[6])}
+
+
 def build_index(input_tsv, out_dir, nwk=None, k=29, w=35, h=13, m=4, r=1, frac=True, num_threads=1, seed=0, ppos=None,
-                gpu_minimizers=False, device=0, sdust_t=0, sdust_w=0):
-    """`krepp index` on the CPU (reference: src/krepp.cpp:131-303).  sdust_t, sdust_w both > 0: --sdust-t/-w masking."""
+                gpu_minimizers=False, device=0, sdust_t=0, sdust_w=0, gpu_keys=False):
+    """`krepp index` (reference: src/krepp.cpp:131-303), on the CPU unless gpu_minimizers (the leaf stage on `device`) or gpu_keys
+    (the key sort and grouping there too; implies the leaf stage).  sdust_t, sdust_w both > 0: --sdust-t/-w masking."""
     lib = load()
     p = KrBuildParams(k=k, w=w, h=h, m=m, r=r, frac=int(frac), num_threads=num_threads, seed=seed, ppos=None,
-                      gpu_minimizers=int(gpu_minimizers), device=device, sdust_t=sdust_t, sdust_w=sdust_w)
+                      gpu_minimizers=_gpu_build_bits(gpu_minimizers, gpu_keys), device=device, sdust_t=sdust_t, sdust_w=sdust_w)
     keep = None
     if ppos is not None:
         keep = (C.c_uint8 * len(ppos))(*ppos)
@@ -1125,13 +1180,14 @@ def build_index(input_tsv, out_dir, nwk=None, k=29, w=35, h=13, m=4, r=1, frac=T
                              os.fsencode(str(out_dir)), C.byref(p)))
 
 
-def build_sketch(input_path, out_path, k=26, w=None, h=None, m=4, r=1, frac=True, seed=0, ppos=None, sdust_t=0, sdust_w=0):
-    """`krepp sketch` (reference: src/krepp.cpp:110-129; defaults k 26, w k+6, h k-16)."""
+def build_sketch(input_path, out_path, k=26, w=None, h=None, m=4, r=1, frac=True, seed=0, ppos=None, sdust_t=0, sdust_w=0,
+                 gpu_minimizers=False, gpu_keys=False, device=0):
+    """`krepp sketch` (reference: src/krepp.cpp:110-129; defaults k 26, w k+6, h k-16); gpu_minimizers / gpu_keys as in build_index."""
     lib = load()
     w = k + 6 if w is None else w
     h = k - 16 if h is None else h
-    p = KrBuildParams(k=k, w=w, h=h, m=m, r=r, frac=int(frac), num_threads=1, seed=seed, ppos=None, gpu_minimizers=0, device=0,
-                      sdust_t=sdust_t, sdust_w=sdust_w)
+    p = KrBuildParams(k=k, w=w, h=h, m=m, r=r, frac=int(frac), num_threads=1, seed=seed, ppos=None,
+                      gpu_minimizers=_gpu_build_bits(gpu_minimizers, gpu_keys), device=device, sdust_t=sdust_t, sdust_w=sdust_w)
     keep = None
     if ppos is not None:
         keep = (C.c_uint8 * len(ppos))(*ppos)

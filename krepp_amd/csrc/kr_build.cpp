@@ -1,6 +1,6 @@
-// kr_build.cpp — CPU index construction (`krepp index`).  Stays on the CPU, as the
-// north star asks; it exists because no index can be obtained any other way (the
-// reference ships none).  Output files follow the reference's on-disk format
+// kr_build.cpp — index construction (`krepp index`, `krepp sketch`).  On the CPU by default; the leaf stage and the key stage
+// can run on the GPU (kr_build_params::gpu_minimizers, kr_minimizer.hip, kr_build_keys.hip) with identical files.  It exists
+// because no index can be obtained any other way (the reference ships none).  Output files follow the reference's on-disk format
 // byte for byte (src/krepp.cpp:18-29,206-246; src/table.cpp:77-83;
 // src/record.cpp:213-219).
 //
@@ -22,6 +22,7 @@
 #include "kr_sdust.h"
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -358,7 +359,74 @@ int finish_sdust(const std::vector<uint64_t>& iv, const std::vector<uint64_t>& i
   return KR_OK;
 }
 
+// ---- the key stage on the host ----
+int key_groups_alloc(kr_key_groups* out, uint64_t nkeys, uint64_t npairs, uint32_t nrows)
+{
+  memset(out, 0, sizeof(*out));
+  out->keys = (uint64_t*)malloc(std::max<uint64_t>(1, nkeys) * 8);
+  out->goff = (uint64_t*)malloc((nkeys + 1) * 8);
+  out->ranks = (uint32_t*)malloc(std::max<uint64_t>(1, npairs) * 4);
+  out->inc = (uint64_t*)calloc(std::max<uint64_t>(1, nrows), 8);
+  if (!out->keys || !out->goff || !out->ranks || !out->inc) {
+    kr_key_groups_free(out);
+    return fail(KR_ERR_NOMEM, "key stage: out of memory");
+  }
+  out->goff[0] = 0;
+  out->nkeys = nkeys, out->npairs = npairs, out->nrows = nrows;
+  return KR_OK;
+}
+
+int key_groups_host(std::vector<KeyRank>& all, uint32_t nrows, uint32_t nleaves, kr_key_groups* out)
+{
+  std::sort(all.begin(), all.end(), [](const KeyRank& a, const KeyRank& b) { return a.key != b.key ? a.key < b.key : a.rank < b.rank; });
+  // runs of equal keys; within a run a rank counts once
+  uint64_t nkeys = 0, npairs = 0;
+  for (size_t a = 0; a < all.size(); ++a) {
+    const bool head = a == 0 || all[a].key != all[a - 1].key;
+    nkeys += head;
+    npairs += head || all[a].rank != all[a - 1].rank;
+    if ((uint32_t)(all[a].key >> 32) >= nrows) return fail(KR_ERR_FORMAT, "row out of range");
+    if (all[a].rank >= nleaves) return fail(KR_ERR_ARG, "key stage: leaf rank out of range");
+  }
+  int rc = key_groups_alloc(out, nkeys, npairs, nrows);
+  if (rc) return rc;
+  uint64_t ik = 0, ip = 0;
+  for (size_t a = 0; a < all.size();) {
+    size_t b = a;
+    out->keys[ik] = all[a].key, out->goff[ik] = ip;
+    while (b < all.size() && all[b].key == all[a].key) {
+      if (b == a || all[b].rank != all[b - 1].rank) out->ranks[ip++] = all[b].rank;
+      ++b;
+    }
+    out->inc[(uint32_t)(all[a].key >> 32)]++;
+    ++ik;
+    a = b;
+  }
+  out->goff[nkeys] = npairs;
+  for (uint32_t rr = 1; rr < nrows; ++rr) out->inc[rr] += out->inc[rr - 1];
+  std::vector<KeyRank>().swap(all);
+  return KR_OK;
+}
+
 } // namespace kr
+
+extern "C" int kr_key_groups_cpu(const uint64_t* keys, const uint32_t* ranks, uint64_t n, uint32_t nrows, uint32_t nleaves, kr_key_groups* out)
+{
+  kr::clear_error();
+  if (!out || (n && (!keys || !ranks))) return kr::fail(KR_ERR_ARG, "kr_key_groups_cpu: null argument");
+  memset(out, 0, sizeof(*out));
+  if (nleaves > 65536u) return kr::fail(KR_ERR_ARG, "kr_key_groups_cpu: more than 65536 leaves");
+  std::vector<kr::KeyRank> all(n);
+  for (uint64_t i = 0; i < n; ++i) all[i] = kr::KeyRank{keys[i], ranks[i]};
+  return kr::key_groups_host(all, nrows, nleaves, out);
+}
+
+extern "C" void kr_key_groups_free(kr_key_groups* g)
+{
+  if (!g) return;
+  free(g->keys), free(g->goff), free(g->ranks), free(g->inc);
+  memset(g, 0, sizeof(*g));
+}
 
 namespace {
 using kr::BuildCfg;
@@ -496,6 +564,36 @@ bool write_file(const std::string& path, const void* hdr, size_t hdr_bytes, cons
   return fclose(f) == 0 && ok;
 }
 
+// KR_BUILD_TIMING=1: the build's phases on stderr, one line each
+struct PhaseClock {
+  const bool on = getenv("KR_BUILD_TIMING") && atoi(getenv("KR_BUILD_TIMING")) != 0;
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now(), last = t0;
+  void done(const char* phase)
+  {
+    if (!on) return;
+    const auto now = std::chrono::steady_clock::now();
+    fprintf(stderr, "build timing: %-24s %10.3f s\n", phase, std::chrono::duration<double>(now - last).count());
+    last = now;
+  }
+  // the key stage's counts; pairs_in / passes: what the device path saw (0: the host path, whose input is unique per genome already)
+  void keys(const kr_key_groups& g, bool device_pool)
+  {
+    if (!on) return;
+    uint64_t st[8] = {0};
+    if (device_pool) kr_debug_build_keys(st);
+    fprintf(stderr, "build keys: pairs_in %llu pairs_out %llu keys %llu passes %llu pool_growths %llu path %llu\n", (unsigned long long)st[0],
+            (unsigned long long)g.npairs, (unsigned long long)g.nkeys, (unsigned long long)st[3], (unsigned long long)st[4], (unsigned long long)st[5]);
+  }
+  void total(const char* what)
+  {
+    if (on) fprintf(stderr, "build timing: %-24s %10.3f s\n", what, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+  }
+};
+struct PoolOwner { // the device pool of a build, given back at every return
+  kr::KeyPool* p = nullptr;
+  ~PoolOwner() { kr::key_pool_free(p); }
+};
+
 // One contig through the leaf stage, masked when sdust is on.  Returns "" or what is wrong with the contig.
 std::string masked_contig_cpu(const uint8_t* seq, uint64_t len, const BuildCfg& c, const LshPositions& lsh, uint32_t sdust_t,
                               uint32_t sdust_w, std::vector<uint64_t>& keys, double& n1, double& n2)
@@ -520,6 +618,7 @@ extern "C" int kr_build_index(const char* input_tsv, const char* nwk_path, const
   if (!input_tsv || !out_dir || !bp) return kr::fail(KR_ERR_ARG, "kr_build_index: null argument");
   BuildCfg c{bp->k, bp->w, bp->h, bp->m, bp->r, bp->frac != 0};
   if (const char* why = bad_configuration(c)) return kr::fail(KR_ERR_ARG, why);
+  PhaseClock clk;
 
   // input map: name \t path (src/krepp.cpp:147-162)
   std::vector<Genome> genomes;
@@ -607,6 +706,14 @@ extern "C" int kr_build_index(const char* input_tsv, const char* nwk_path, const
   int first_rc = KR_ERR_IO;
   const uint32_t sdust_t = bp->sdust_t && bp->sdust_w ? bp->sdust_t : 0, sdust_w = sdust_t ? bp->sdust_w : 0; // either at 0: off
   if (sdust_t && sdust_w < 4) return kr::fail(KR_ERR_ARG, "--sdust-w must be at least 4");
+  // KR_BUILD_GPU_KEYS: the genomes' raw keys stay on the device, in a pool that the key stage sorts and groups after the last genome
+  PoolOwner pool;
+  if (bp->gpu_minimizers & KR_BUILD_GPU_KEYS) {
+    if (nleaves > 65536u)
+      kr::key_stage_note_path(3); // two rank digits at most: this build keeps its keys on the host
+    else if (int prc = kr::key_pool_create(bp->device, &pool.p))
+      return prc;
+  }
 #if defined(_OPENMP)
 #pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads)
 #endif
@@ -654,12 +761,13 @@ extern "C" int kr_build_index(const char* input_tsv, const char* nwk_path, const
       std::vector<uint64_t> iv, ioff;
       const bool host_mask = sdust_t && sdust_w;
       if (host_mask) mrc = kr::sdust_lists_host(all_bases.data(), all_offs.data(), (uint32_t)all_offs.size() - 1, sdust_t, sdust_w, iv, ioff);
+      const kr::MinSink sink{pool.p, pool.p ? bt.leaf_rank[leaf_by_name.at(g.name)] : 0u, 0.0, 0.0};
       if (mrc == KR_OK) {
 #if defined(_OPENMP)
 #pragma omp critical(kr_gpu_minimizers)
 #endif
         mrc = kr::minimizers_device(bp->device, &bq, all_bases.data(), all_offs.data(), (uint32_t)all_offs.size() - 1,
-                                    host_mask ? &iv : nullptr, host_mask ? &ioff : nullptr, &mr);
+                                    host_mask ? &iv : nullptr, host_mask ? &ioff : nullptr, &mr, &sink);
       }
       if (mrc != KR_OK) {
 #if defined(_OPENMP)
@@ -677,50 +785,47 @@ extern "C" int kr_build_index(const char* input_tsv, const char* nwk_path, const
     g.present = true;
   }
   if (!first_err.empty()) return kr::fail(first_rc, first_err);
+  clk.done("read + leaf stage");
 
-  // group equal keys across genomes
-  struct KL {
-    uint64_t key;
-    uint32_t rank;
-  };
-  std::vector<KL> all;
-  {
+  // group equal keys across genomes: the key stage, on the device's pool or on the host
+  struct Groups : kr_key_groups {
+    Groups() { memset(static_cast<kr_key_groups*>(this), 0, sizeof(kr_key_groups)); }
+    ~Groups() { kr_key_groups_free(this); }
+  } grp;
+  const bool pooled = pool.p != nullptr;
+  if (pooled) {
+    int krc = kr::key_pool_finish(pool.p, nrows, nleaves, &grp);
+    kr::key_pool_free(pool.p), pool.p = nullptr;
+    if (krc) return krc;
+  } else {
+    std::vector<kr::KeyRank> all;
     size_t tot = 0;
     for (auto& g : genomes) tot += g.keys.size();
     all.reserve(tot);
     for (auto& g : genomes) {
       if (!g.present) continue;
       uint32_t rank = bt.leaf_rank[leaf_by_name[g.name]];
-      for (uint64_t key : g.keys) all.push_back(KL{key, rank});
+      for (uint64_t key : g.keys) all.push_back(kr::KeyRank{key, rank});
       std::vector<uint64_t>().swap(g.keys);
     }
+    if (all.empty()) return kr::fail(KR_ERR_FORMAT, "No k-mers to index!");
+    if (int krc = kr::key_groups_host(all, nrows, nleaves, &grp)) return krc;
   }
-  std::sort(all.begin(), all.end(), [](const KL& a, const KL& b) { return a.key != b.key ? a.key < b.key : a.rank < b.rank; });
-  if (all.empty()) return kr::fail(KR_ERR_FORMAT, "No k-mers to index!");
+  if (grp.nkeys == 0) return kr::fail(KR_ERR_FORMAT, "No k-mers to index!");
+  clk.done("key sort + group");
+  clk.keys(grp, pooled);
 
-  std::vector<uint64_t> inc(nrows, 0);
-  std::vector<uint64_t> out_sh;
-  std::vector<uint32_t> out_enc;
-  std::vector<uint32_t> out_row;
-  std::vector<uint32_t> ranks;
+  // colours of the groups IN KEY ORDER: Colours::created's order fixes the ids of the colours that are no tree nodes
+  std::vector<uint32_t> leaf_se(nleaves, 0);
+  for (uint32_t se = 1; se <= nn; ++se)
+    if (bt.t.nodes[se].kind == 1) leaf_se[bt.leaf_rank[se]] = se;
+  std::vector<uint64_t> out_sh(grp.nkeys);
   uint32_t root_se = nn;
-  for (size_t a = 0; a < all.size();) {
-    size_t b = a;
-    ranks.clear();
-    while (b < all.size() && all[b].key == all[a].key) {
-      if (ranks.empty() || ranks.back() != all[b].rank) ranks.push_back(all[b].rank);
-      ++b;
-    }
-    uint64_t s = colour_of(bt, col, root_se, ranks.data(), 0, ranks.size());
-    uint32_t row = (uint32_t)(all[a].key >> 32);
-    if (row >= nrows) return kr::fail(KR_ERR_FORMAT, "row out of range");
-    out_sh.push_back(s);
-    out_enc.push_back((uint32_t)all[a].key);
-    out_row.push_back(row);
-    inc[row]++;
-    a = b;
+  for (uint64_t i = 0; i < grp.nkeys; ++i) {
+    const uint64_t a = grp.goff[i], b = grp.goff[i + 1];
+    // one leaf: colour_of would walk down to it and create nothing on the way
+    out_sh[i] = b - a == 1 ? bt.sh[leaf_se[grp.ranks[a]]] : colour_of(bt, col, root_se, grp.ranks, (size_t)a, (size_t)b);
   }
-  for (uint32_t rr = 1; rr < nrows; ++rr) inc[rr] += inc[rr - 1];
 
   // Record::make_compact + CRecord(record) (src/record.cpp:131-176)
   uint32_t next_se = nn + 1;
@@ -738,20 +843,21 @@ extern "C" int kr_build_index(const char* input_tsv, const char* nwk_path, const
   std::vector<double> rho(nn + 1, 0.0);
   for (auto& g : genomes)
     if (g.present) rho[leaf_by_name[g.name]] = g.n1 > 0 ? g.n2 / g.n1 : 0.0; // RSeq::compute_rho, src/rqseq.hpp:79
-  std::vector<uint32_t> cmer(out_enc.size() * 2);
-  for (size_t i = 0; i < out_enc.size(); ++i) {
-    cmer[2 * i] = out_enc[i];
+  std::vector<uint32_t> cmer(out_sh.size() * 2);
+  for (size_t i = 0; i < out_sh.size(); ++i) {
+    cmer[2 * i] = (uint32_t)grp.keys[i];
     cmer[2 * i + 1] = col.by_sh[out_sh[i]].se;
   }
+  clk.done("colours");
 
   // save_index (src/krepp.cpp:206-246)
   mkdir(out_dir, 0777);
   std::string sfx = "-m" + std::to_string(c.m) + "r" + std::to_string(c.r) + (c.frac ? "-frac" : "-no_frac");
   std::string dir = out_dir;
-  uint64_t nk = out_enc.size();
+  uint64_t nk = out_sh.size();
   uint32_t nn1 = nn + 1;
   bool ok = write_file(dir + "/cmer" + sfx, &nk, 8, cmer.data(), cmer.size() * 4);
-  ok = ok && write_file(dir + "/inc" + sfx, &nrows, 4, inc.data(), inc.size() * 8);
+  ok = ok && write_file(dir + "/inc" + sfx, &nrows, 4, grp.inc, (size_t)nrows * 8);
   {
     std::string blob;
     blob.append((const char*)&nn1, 4);
@@ -786,6 +892,8 @@ extern "C" int kr_build_index(const char* input_tsv, const char* nwk_path, const
     ok = ok && write_file(dir + "/metadata" + sfx + ".txt", s.data(), s.size(), nullptr, 0);
   }
   if (!ok) return kr::fail(KR_ERR_IO, std::string("failed to write index files under ") + out_dir);
+  clk.done("write");
+  clk.total("total");
   return KR_OK;
 }
 
@@ -878,6 +986,15 @@ extern "C" int kr_build_sketch(const char* input_path, const char* out_path, con
   const uint32_t nrows = nrows_of(c);
   const uint32_t sdust_t = bp->sdust_t && bp->sdust_w ? bp->sdust_t : 0, sdust_w = sdust_t ? bp->sdust_w : 0; // either at 0: off
   if (sdust_t && sdust_w < 4) return kr::fail(KR_ERR_ARG, "--sdust-w must be at least 4");
+  PhaseClock clk;
+  // gpu_minimizers, as in kr_build_index: the leaf stage of every batch of records on the device; KR_BUILD_GPU_KEYS: the keys stay
+  // there, and the sort, the unique and the row counts are the key stage with one leaf
+  const bool gpu_leaf = bp->gpu_minimizers != 0;
+  PoolOwner pool;
+  if (bp->gpu_minimizers & KR_BUILD_GPU_KEYS)
+    if (int prc = kr::key_pool_create(bp->device, &pool.p)) return prc;
+  kr_build_params bq = *bp;
+  bq.ppos = lsh.ppos.data();
   kr_fastx* fx = nullptr;
   if (kr_fastx_open(input_path, &fx) != KR_OK) return kr::fail(KR_ERR_IO, std::string("Failed to open the file at ") + input_path);
   std::vector<uint64_t> keys;
@@ -887,6 +1004,20 @@ extern "C" int kr_build_sketch(const char* input_path, const char* out_path, con
     if (kr_fastx_next(fx, 1u << 20, &b)) {
       kr_fastx_close(fx);
       return KR_ERR_IO;
+    }
+    if (gpu_leaf) {
+      if (b.nreads == 0) continue;
+      kr_minimizer_result mr;
+      memset(&mr, 0, sizeof(mr));
+      const kr::MinSink sink{pool.p, 0u, n1, n2}; // the contigs' estimates are added in file order, as on the host
+      if (int mrc = kr::minimizers_device(bp->device, &bq, b.bases, b.offsets, b.nreads, nullptr, nullptr, &mr, &sink)) {
+        kr_fastx_close(fx);
+        return mrc;
+      }
+      keys.insert(keys.end(), mr.keys, mr.keys + mr.nkeys);
+      n1 = mr.n1, n2 = mr.n2;
+      kr_minimizers_free(&mr);
+      continue;
     }
     for (uint32_t q = 0; q < b.nreads; ++q) {
       const uint64_t len = b.offsets[q + 1] - b.offsets[q];
@@ -899,17 +1030,32 @@ extern "C" int kr_build_sketch(const char* input_path, const char* out_path, con
     }
   } while (b.more);
   kr_fastx_close(fx);
-  std::sort(keys.begin(), keys.end());
-  keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
-  std::vector<uint32_t> enc(keys.size());
+  clk.done("read + leaf stage");
+  std::vector<uint32_t> enc;
   std::vector<uint64_t> inc(nrows, 0);
-  for (size_t i = 0; i < keys.size(); ++i) {
-    const uint32_t row = (uint32_t)(keys[i] >> 32);
-    if (row >= nrows) return kr::fail(KR_ERR_STATE, "kr_build_sketch: row out of range");
-    enc[i] = (uint32_t)keys[i];
-    inc[row]++;
+  if (pool.p) {
+    kr_key_groups grp;
+    memset(&grp, 0, sizeof(grp));
+    int krc = kr::key_pool_finish(pool.p, nrows, 1, &grp);
+    kr::key_pool_free(pool.p), pool.p = nullptr;
+    if (krc) return krc;
+    enc.resize(grp.nkeys);
+    for (uint64_t i = 0; i < grp.nkeys; ++i) enc[i] = (uint32_t)grp.keys[i];
+    std::copy(grp.inc, grp.inc + nrows, inc.begin());
+    kr_key_groups_free(&grp);
+  } else {
+    std::sort(keys.begin(), keys.end());
+    keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+    enc.resize(keys.size());
+    for (size_t i = 0; i < keys.size(); ++i) {
+      const uint32_t row = (uint32_t)(keys[i] >> 32);
+      if (row >= nrows) return kr::fail(KR_ERR_STATE, "kr_build_sketch: row out of range");
+      enc[i] = (uint32_t)keys[i];
+      inc[row]++;
+    }
+    for (uint32_t r = 1; r < nrows; ++r) inc[r] += inc[r - 1];
   }
-  for (uint32_t r = 1; r < nrows; ++r) inc[r] += inc[r - 1];
+  clk.done("key sort + group");
   const double rho = n1 > 0 ? n2 / n1 : 0.0; // RSeq::compute_rho, src/rqseq.hpp:79
   std::string blob;
   const uint64_t nk = enc.size();
@@ -925,6 +1071,8 @@ extern "C" int kr_build_sketch(const char* input_path, const char* out_path, con
   blob.append((const char*)lsh.npos.data(), lsh.npos.size());
   blob.append((const char*)&rho, 8);
   if (!write_file(out_path, blob.data(), blob.size(), nullptr, 0)) return kr::fail(KR_ERR_IO, "Failed to write the sketch!");
+  clk.done("write");
+  clk.total("total");
   fprintf(stderr, "Total number of k-mers included in the sketch: %llu\nSubsampling rate (rho) is: %g\n", (unsigned long long)nk, rho);
   return KR_OK;
 }

@@ -1,0 +1,556 @@
+// kr_build_keys.hip — the key stage of the index and sketch builds on gfx950: all genomes' (key, leaf rank) pairs sorted by
+// (key, rank), duplicates dropped, cut into groups of equal key, rows counted (kr_key_groups_device; the builder's pool of keys).
+//
+// Sort: least-significant-digit radix sort, 8-bit digits, out of place between two buffers; the rank's digits first, then the
+// key's, so that the final order is (key, rank).  Only digits that can differ are sorted: ceil(log2(nleaves)) bits of rank,
+// 32 bits of enc plus ceil(log2(nrows)) bits of row (digit_passes).  One pass is
+//   kr_keys_hist_kernel      a workgroup per tile of kTile pairs: the tile's digit histogram in LDS -> counts[digit][tile]
+//   three scan kernels       exclusive prefix sum over the 256 x ntiles counts in that (digit-major) order: a pair's digit
+//                            bucket starts where all smaller digits and the same digit's earlier tiles end (kr_dev_prefix.inc)
+//   kr_keys_scatter_kernel   the waves of a workgroup own consecutive quarters of the tile; a wave takes 64 pairs at a time in
+//                            tile order, finds each pair's peers of equal digit by eight ballots, and puts it at the digit's
+//                            running position plus the number of peers in lower lanes
+// Every pass is STABLE: tiles, a tile's quarters, a quarter's steps and a step's lanes all keep the input order within a digit.
+// The leaf stage appends keys by atomics, so the arrival order differs between runs; the output does not.
+//
+// Grouping, on the sorted pairs: a pair is kept unless it equals its predecessor, and is a head if its key differs from the
+// predecessor's.  Block sums of both flags, their scans, and one kernel that recomputes the flags, scans them within the block and
+// writes ranks[kept position], keys / goff[head position], and adds 1 to inc[row] at a head (an ordinary vector atomic); a 64-bit
+// inclusive scan over the rows turns inc into the cumulative counts.
+//
+// No per-lane private arrays, no dynamic LDS: the kernels hold scalars and statically sized LDS only.
+#include "kr_common.h"
+#include "kr_devutil.h"
+
+#include <algorithm>
+#include <atomic>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+namespace {
+
+#include "kr_dev_prefix.inc" // (64-bit sums only here: the 32-bit wave scan on the DPP network is kr_dev_common.inc's)
+
+constexpr uint32_t kTile = 2048;        // pairs per workgroup of a pass
+constexpr uint32_t kQuarter = kTile / 4; // ... per wave
+constexpr uint32_t kScanBlock = 1024;   // items per workgroup of the scans (4 per thread)
+
+// digit `shift / 8` of the rank (from_rank) or of the key
+__device__ __forceinline__ uint32_t digit_at(const uint64_t* keys, const uint32_t* ranks, uint64_t i, uint32_t from_rank, uint32_t shift)
+{
+  return from_rank ? (ranks[i] >> shift) & 255u : (uint32_t)(keys[i] >> shift) & 255u;
+}
+
+// bit 0: a row >= nrows, bit 1: a rank >= nleaves
+__global__ __launch_bounds__(256) void kr_keys_check_kernel(const uint64_t* keys, const uint32_t* ranks, uint64_t n, uint32_t nrows, uint32_t nleaves,
+                                                            uint32_t* bad)
+{
+  uint32_t f = 0;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u) {
+    if ((uint32_t)(keys[i] >> 32) >= nrows) f |= 1u;
+    if (ranks[i] >= nleaves) f |= 2u;
+  }
+  if (f) atomicOr(bad, f);
+}
+
+// ranks[i] = the leaf rank of the segment that holds i: seg_off[0 .. nseg] ascending, seg_off[nseg] = n
+__global__ __launch_bounds__(256) void kr_keys_expand_kernel(const uint64_t* seg_off, const uint32_t* seg_rank, uint32_t nseg, uint64_t n, uint32_t* ranks)
+{
+  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u) {
+    uint32_t lo = 0, hi = nseg; // the last segment with seg_off <= i (empty segments share an offset: the last of them is skipped over)
+    while (hi - lo > 1u) {
+      const uint32_t mid = lo + (hi - lo) / 2u;
+      if (seg_off[mid] <= i) lo = mid;
+      else hi = mid;
+    }
+    ranks[i] = seg_rank[lo];
+  }
+}
+
+__global__ __launch_bounds__(256) void kr_keys_hist_kernel(const uint64_t* keys, const uint32_t* ranks, uint64_t n, uint32_t ntiles, uint32_t from_rank,
+                                                           uint32_t shift, uint64_t* counts)
+{
+  __shared__ uint32_t s_h[256];
+  const uint32_t tid = threadIdx.x, tile = blockIdx.x;
+  s_h[tid] = 0;
+  __syncthreads();
+  const uint64_t t0 = (uint64_t)tile * kTile;
+#pragma unroll
+  for (uint32_t q = 0; q < kTile / 256u; ++q) {
+    const uint64_t i = t0 + q * 256u + tid;
+    if (i < n) atomicAdd(&s_h[digit_at(keys, ranks, i, from_rank, shift)], 1u);
+  }
+  __syncthreads();
+  counts[(uint64_t)tid * ntiles + tile] = s_h[tid];
+}
+
+// The three steps of kr_dev_prefix.inc over m 64-bit items, in place; INCL: every item gets the sum up to and including itself
+__global__ __launch_bounds__(256) void kr_keys_bsum_kernel(const uint64_t* v, uint64_t m, uint64_t* bsum)
+{
+  for (uint64_t b = blockIdx.x; b * kScanBlock < m; b += gridDim.x) {
+    uint64_t c = 0;
+#pragma unroll
+    for (uint32_t q = 0; q < 4; ++q) {
+      const uint64_t i = b * kScanBlock + 4u * threadIdx.x + q;
+      if (i < m) c += v[i];
+    }
+    const uint64_t tot = block_sum<uint64_t>(c);
+    if (threadIdx.x == 0) bsum[b] = tot;
+  }
+}
+__global__ __launch_bounds__(1024) void kr_keys_bscan_kernel(uint64_t* bsum, uint32_t nblk, uint64_t* total)
+{
+  const uint64_t tot = scan_block_sums<uint64_t>(bsum, nblk);
+  if (threadIdx.x == 0) *total = tot;
+}
+template <bool INCL>
+__global__ __launch_bounds__(256) void kr_keys_bwrite_kernel(uint64_t* v, uint64_t m, const uint64_t* bsum)
+{
+  for (uint64_t b = blockIdx.x; b * kScanBlock < m; b += gridDim.x) {
+    const uint64_t i0 = b * kScanBlock + 4u * threadIdx.x;
+    const uint64_t c0 = i0 < m ? v[i0] : 0, c1 = i0 + 1 < m ? v[i0 + 1] : 0, c2 = i0 + 2 < m ? v[i0 + 2] : 0, c3 = i0 + 3 < m ? v[i0 + 3] : 0;
+    uint64_t run = bsum[b] + block_scan_excl<uint64_t>(c0 + c1 + c2 + c3);
+    if (INCL) run += c0;
+    if (i0 < m) v[i0] = run;
+    run += INCL ? c1 : c0;
+    if (i0 + 1 < m) v[i0 + 1] = run;
+    run += INCL ? c2 : c1;
+    if (i0 + 2 < m) v[i0 + 2] = run;
+    run += INCL ? c3 : c2;
+    if (i0 + 3 < m) v[i0 + 3] = run;
+  }
+}
+
+// offs: the scanned counts.  Positions stay below n because the histogram counted these very pairs.
+__global__ __launch_bounds__(256) void kr_keys_scatter_kernel(const uint64_t* kin, const uint32_t* rin, uint64_t* kout, uint32_t* rout, uint64_t n,
+                                                              uint32_t ntiles, uint32_t from_rank, uint32_t shift, const uint64_t* offs)
+{
+  __shared__ uint32_t s_cnt[4][256];  // pairs of a digit in each wave's quarter
+  __shared__ uint64_t s_pos[4][256];  // where the wave's next pair of a digit goes
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, tile = blockIdx.x;
+  s_cnt[0][tid] = 0, s_cnt[1][tid] = 0, s_cnt[2][tid] = 0, s_cnt[3][tid] = 0;
+  __syncthreads();
+  const uint64_t w0 = (uint64_t)tile * kTile + (uint64_t)wave * kQuarter;
+#pragma unroll
+  for (uint32_t s = 0; s < kQuarter / 64u; ++s) {
+    const uint64_t i = w0 + s * 64u + lane;
+    if (i < n) atomicAdd(&s_cnt[wave][digit_at(kin, rin, i, from_rank, shift)], 1u);
+  }
+  __syncthreads();
+  { // thread = digit: the digit's first position in this tile, then quarter by quarter
+    uint64_t run = offs[(uint64_t)tid * ntiles + tile];
+    s_pos[0][tid] = run, run += s_cnt[0][tid];
+    s_pos[1][tid] = run, run += s_cnt[1][tid];
+    s_pos[2][tid] = run, run += s_cnt[2][tid];
+    s_pos[3][tid] = run;
+  }
+  __syncthreads();
+  const uint64_t below = (1ull << lane) - 1ull;
+  for (uint32_t s = 0; s < kQuarter / 64u; ++s) { // (from here on a wave touches its own row of s_pos only)
+    const uint64_t i = w0 + s * 64u + lane;
+    const bool valid = i < n;
+    uint64_t key = 0;
+    uint32_t rank = 0;
+    if (valid) key = kin[i], rank = rin[i];
+    const uint32_t d = from_rank ? (rank >> shift) & 255u : (uint32_t)(key >> shift) & 255u;
+    uint64_t peers = __ballot(valid); // the valid lanes with this lane's digit
+#pragma unroll
+    for (uint32_t b = 0; b < 8; ++b) {
+      const bool bit = (d >> b) & 1u;
+      const uint64_t m = __ballot(valid && bit);
+      peers &= bit ? m : ~m;
+    }
+    if (valid) {
+      const uint64_t at = s_pos[wave][d] + (uint64_t)__popcll(peers & below);
+      if (at < n) kout[at] = key, rout[at] = rank;
+    }
+    __builtin_amdgcn_wave_barrier(); // every peer has read the digit's position before its first lane moves it on
+    if (valid && (peers & below) == 0) s_pos[wave][d] += (uint64_t)__popcll(peers);
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
+// flags of the sorted pair i: kept (not a repeat of pair i - 1), head (first pair of its key)
+__device__ __forceinline__ void pair_flags(const uint64_t* keys, const uint32_t* ranks, uint64_t i, uint64_t n, uint32_t& keep, uint32_t& head)
+{
+  keep = head = 0;
+  if (i >= n) return;
+  if (i == 0) {
+    keep = head = 1;
+    return;
+  }
+  const bool same_key = keys[i] == keys[i - 1];
+  head = !same_key;
+  keep = !same_key || ranks[i] != ranks[i - 1];
+}
+
+__global__ __launch_bounds__(256) void kr_keys_flag_bsum_kernel(const uint64_t* keys, const uint32_t* ranks, uint64_t n, uint64_t* bsum_keep, uint64_t* bsum_head)
+{
+  for (uint64_t b = blockIdx.x; b * kScanBlock < n; b += gridDim.x) {
+    uint64_t ck = 0, ch = 0;
+#pragma unroll
+    for (uint32_t q = 0; q < 4; ++q) {
+      uint32_t keep, head;
+      pair_flags(keys, ranks, b * kScanBlock + 4u * threadIdx.x + q, n, keep, head);
+      ck += keep, ch += head;
+    }
+    const uint64_t tk = block_sum<uint64_t>(ck), th = block_sum<uint64_t>(ch);
+    if (threadIdx.x == 0) bsum_keep[b] = tk, bsum_head[b] = th;
+  }
+}
+
+// bsum_*: scanned.  keys_out / goff have room for the heads, ranks_out for the kept pairs, inc for nrows (rows were checked).
+__global__ __launch_bounds__(256) void kr_keys_group_kernel(const uint64_t* keys, const uint32_t* ranks, uint64_t n, const uint64_t* bsum_keep,
+                                                            const uint64_t* bsum_head, uint64_t* keys_out, uint64_t* goff, uint32_t* ranks_out,
+                                                            unsigned long long* inc, uint32_t nrows)
+{
+  for (uint64_t b = blockIdx.x; b * kScanBlock < n; b += gridDim.x) {
+    const uint64_t i0 = b * kScanBlock + 4u * threadIdx.x;
+    uint32_t k0, k1, k2, k3, h0, h1, h2, h3;
+    pair_flags(keys, ranks, i0, n, k0, h0);
+    pair_flags(keys, ranks, i0 + 1, n, k1, h1);
+    pair_flags(keys, ranks, i0 + 2, n, k2, h2);
+    pair_flags(keys, ranks, i0 + 3, n, k3, h3);
+    uint64_t pk = bsum_keep[b] + block_scan_excl<uint64_t>((uint64_t)(k0 + k1 + k2 + k3));
+    uint64_t ph = bsum_head[b] + block_scan_excl<uint64_t>((uint64_t)(h0 + h1 + h2 + h3));
+    auto put = [&](uint64_t i, uint32_t keep, uint32_t head) {
+      if (keep) ranks_out[pk] = ranks[i];
+      if (head) {
+        const uint64_t key = keys[i];
+        keys_out[ph] = key, goff[ph] = pk;
+        if ((uint32_t)(key >> 32) < nrows) atomicAdd(&inc[key >> 32], 1ull);
+      }
+      pk += keep, ph += head;
+    };
+    put(i0, k0, h0);
+    put(i0 + 1, k1, h1);
+    put(i0 + 2, k2, h2);
+    put(i0 + 3, k3, h3);
+  }
+}
+
+#define HIP_TRY(expr)                                                                                   \
+  do {                                                                                                  \
+    hipError_t e__ = (expr);                                                                            \
+    if (e__ != hipSuccess)                                                                              \
+      return kr::fail(e__ == hipErrorOutOfMemory ? KR_ERR_NOMEM : KR_ERR_NO_DEVICE,                      \
+                      std::string(#expr) + ": " + hipGetErrorString(e__));                              \
+  } while (0)
+
+// kr_debug_build_keys: {pairs in, pairs out, keys out, passes, pool growths, path, kTile, 0}
+std::atomic<uint64_t> g_stat[8];
+void note(uint64_t in, uint64_t pairs, uint64_t keys, uint64_t passes, uint64_t growths, uint64_t path)
+{
+  const uint64_t v[8] = {in, pairs, keys, passes, growths, path, kTile, 0};
+  for (int q = 0; q < 8; ++q) g_stat[q].store(v[q]);
+}
+
+int set_device(int device, const char* who)
+{
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return kr::fail(KR_ERR_NO_DEVICE, "no HIP device available");
+  if (device < 0 || device >= ndev) return kr::fail(KR_ERR_ARG, std::string(who) + ": bad device ordinal");
+  HIP_TRY(hipSetDevice(device));
+  return KR_OK;
+}
+
+uint32_t ceil_log2(uint64_t v)
+{ // bits needed to tell v values apart
+  uint32_t b = 0;
+  while (b < 64 && (1ull << b) < v) ++b;
+  return b;
+}
+struct Pass {
+  uint32_t from_rank, shift;
+};
+// The digits that can differ, least significant first: the rank's, then the key's
+std::vector<Pass> digit_passes(uint32_t nrows, uint32_t nleaves)
+{
+  std::vector<Pass> p;
+  for (uint32_t s = 0; s < ceil_log2(nleaves); s += 8) p.push_back(Pass{1u, s});
+  for (uint32_t s = 0; s < 32u + ceil_log2(nrows); s += 8) p.push_back(Pass{0u, s});
+  return p;
+}
+
+uint64_t scan_blocks(uint64_t m) { return (m + kScanBlock - 1) / kScanBlock; }
+uint32_t grid_for(uint64_t blocks) { return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(blocks, 1), 65536); }
+
+// Device bytes of the stage for n pairs: the two sort buffers (24 B a pair), the digit counts, the block sums, goff and inc
+uint64_t stage_bytes(uint64_t n, uint32_t nrows)
+{
+  const uint64_t ntiles = (n + kTile - 1) / kTile;
+  const uint64_t nblk = std::max(std::max(scan_blocks(256 * ntiles), scan_blocks(n)), scan_blocks(nrows));
+  return 24 * n + 8 * 256 * ntiles + 2 * 8 * nblk + 8 * (n + 1) + 8 * (uint64_t)nrows + 4096;
+}
+// Does the stage fit?  `held`: bytes of it the caller has on the device already.  KR_BUILD_KEYS_MAX_MB caps the whole stage.
+bool stage_fits(uint64_t n, uint32_t nrows, uint64_t held)
+{
+  const uint64_t need = stage_bytes(n, nrows);
+  if (const char* e = getenv("KR_BUILD_KEYS_MAX_MB"))
+    if (need > (uint64_t)strtoull(e, nullptr, 10) << 20) return false;
+  size_t fr = 0, tot = 0;
+  if (hipMemGetInfo(&fr, &tot) != hipSuccess) return false;
+  const uint64_t margin = 64ull << 20;
+  return need - std::min(need, held) + margin <= (uint64_t)fr;
+}
+
+// In-place exclusive (or inclusive) prefix sum over v[0 .. m) on the null stream; the total into *d_total
+template <bool INCL>
+void scan_u64(uint64_t* v, uint64_t m, uint64_t* bsum, uint64_t* d_total)
+{
+  const uint64_t nblk = scan_blocks(m);
+  hipLaunchKernelGGL(kr_keys_bsum_kernel, dim3(grid_for(nblk)), dim3(256), 0, 0, v, m, bsum);
+  hipLaunchKernelGGL(kr_keys_bscan_kernel, dim3(1), dim3(1024), 0, 0, bsum, (uint32_t)nblk, d_total);
+  hipLaunchKernelGGL(kr_keys_bwrite_kernel<INCL>, dim3(grid_for(nblk)), dim3(256), 0, 0, v, m, bsum);
+}
+
+// The stage on n > 0 pairs that are on the device: ka / ra are sorted between themselves and two buffers made here.  Every buffer
+// is had before the first kernel runs: KR_ERR_NOMEM means that ka / ra are as they were (the callers finish on the host then).
+int run_stage(uint64_t* ka, uint32_t* ra, uint64_t n, uint32_t nrows, uint32_t nleaves, kr_key_groups* out, uint64_t* npasses)
+{
+  const uint64_t ntiles64 = (n + kTile - 1) / kTile;
+  if (ntiles64 >= (1ull << 31)) return kr::fail(KR_ERR_ARG, "key stage: too many pairs for one sort");
+  const uint32_t ntiles = (uint32_t)ntiles64;
+  const uint64_t ncounts = 256ull * ntiles;
+  const uint64_t nblk = std::max(std::max(scan_blocks(ncounts), scan_blocks(n)), scan_blocks(nrows));
+  DevBuf<uint64_t> b_kb, b_counts, b_bsum, b_bsum2, b_small, b_goff, b_inc; // (freed at every return)
+  DevBuf<uint32_t> b_rb;
+  if (!b_kb.reserve(n) || !b_rb.reserve(n) || !b_counts.reserve(ncounts) || !b_bsum.reserve(nblk) || !b_bsum2.reserve(nblk) || !b_small.reserve(4) ||
+      !b_goff.reserve(n + 1) || !b_inc.reserve(nrows)) {
+    (void)hipGetLastError();
+    return kr::fail(KR_ERR_NOMEM, "key stage: out of device memory");
+  }
+  uint64_t* d_total = b_small.get();       // [0], [1]: totals of the scans
+  uint32_t* d_bad = (uint32_t*)(d_total + 2);
+  HIP_TRY(hipMemset(d_total, 0, 32));
+  hipLaunchKernelGGL(kr_keys_check_kernel, dim3(grid_for((n + 255) / 256)), dim3(256), 0, 0, ka, ra, n, nrows, nleaves, d_bad);
+  HIP_TRY(hipGetLastError());
+  uint32_t bad = 0;
+  HIP_TRY(hipMemcpy(&bad, d_bad, 4, hipMemcpyDeviceToHost)); // (synchronises with the kernel: null stream)
+  if (bad & 1u) return kr::fail(KR_ERR_FORMAT, "row out of range");
+  if (bad & 2u) return kr::fail(KR_ERR_ARG, "key stage: leaf rank out of range");
+
+  uint64_t *kin = ka, *kout = b_kb.get();
+  uint32_t *rin = ra, *rout = b_rb.get();
+  const std::vector<Pass> passes = digit_passes(nrows, nleaves);
+  for (const Pass& p : passes) {
+    hipLaunchKernelGGL(kr_keys_hist_kernel, dim3(ntiles), dim3(256), 0, 0, kin, rin, n, ntiles, p.from_rank, p.shift, b_counts.get());
+    scan_u64<false>(b_counts.get(), ncounts, b_bsum.get(), d_total);
+    hipLaunchKernelGGL(kr_keys_scatter_kernel, dim3(ntiles), dim3(256), 0, 0, kin, rin, kout, rout, n, ntiles, p.from_rank, p.shift, b_counts.get());
+    std::swap(kin, kout), std::swap(rin, rout);
+  }
+  *npasses = passes.size();
+  // kin / rin: sorted.  The other pair of buffers takes the distinct keys and the kept ranks.
+  const uint64_t nfb = scan_blocks(n);
+  hipLaunchKernelGGL(kr_keys_flag_bsum_kernel, dim3(grid_for(nfb)), dim3(256), 0, 0, kin, rin, n, b_bsum.get(), b_bsum2.get());
+  hipLaunchKernelGGL(kr_keys_bscan_kernel, dim3(1), dim3(1024), 0, 0, b_bsum.get(), (uint32_t)nfb, d_total);
+  hipLaunchKernelGGL(kr_keys_bscan_kernel, dim3(1), dim3(1024), 0, 0, b_bsum2.get(), (uint32_t)nfb, d_total + 1);
+  HIP_TRY(hipGetLastError());
+  uint64_t tot[2] = {0, 0};
+  HIP_TRY(hipMemcpy(tot, d_total, 16, hipMemcpyDeviceToHost));
+  const uint64_t npairs = tot[0], nkeys = tot[1];
+  if (npairs > n || nkeys > npairs || nkeys == 0) return kr::fail(KR_ERR_STATE, "key stage: inconsistent group counts");
+  HIP_TRY(hipMemset(b_inc.get(), 0, (uint64_t)nrows * 8));
+  HIP_TRY(hipMemcpy(b_goff.get() + nkeys, &npairs, 8, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(kr_keys_group_kernel, dim3(grid_for(nfb)), dim3(256), 0, 0, kin, rin, n, b_bsum.get(), b_bsum2.get(), kout, b_goff.get(), rout,
+                     (unsigned long long*)b_inc.get(), nrows);
+  scan_u64<true>(b_inc.get(), nrows, b_bsum.get(), d_total);
+  HIP_TRY(hipGetLastError());
+  int rc = kr::key_groups_alloc(out, nkeys, npairs, nrows);
+  if (rc) return rc;
+  hipError_t e = hipMemcpy(out->keys, kout, nkeys * 8, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(out->goff, b_goff.get(), (nkeys + 1) * 8, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(out->ranks, rout, npairs * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(out->inc, b_inc.get(), (uint64_t)nrows * 8, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) {
+    kr_key_groups_free(out);
+    return kr::fail(KR_ERR_NO_DEVICE, std::string("key stage: ") + hipGetErrorString(e));
+  }
+  return KR_OK;
+}
+
+} // namespace
+
+// ---------------------------------------------------------------------------
+// The builder's pool
+// ---------------------------------------------------------------------------
+struct kr::KeyPool {
+  int device = 0;
+  DevBuf<uint64_t> keys; // capacity keys.size(), `used` of it filled
+  uint64_t used = 0, growths = 0;
+  struct Seg {
+    uint64_t off, count;
+    uint32_t rank;
+  };
+  std::vector<Seg> segs;
+  bool on_host = false;           // the device had no room to grow: everything is in `spill` from then on
+  std::vector<kr::KeyRank> spill;
+};
+
+namespace {
+uint64_t pool_start_pairs()
+{
+  const char* e = getenv("KR_BUILD_POOL_PAIRS");
+  const uint64_t v = e ? strtoull(e, nullptr, 10) : 0;
+  return v ? v : 64ull << 20;
+}
+// the pool's pairs as host (key, rank) records behind what `spill` holds; the device block is given back
+int pool_to_host(kr::KeyPool* p)
+{
+  std::vector<uint64_t> tmp(p->used);
+  if (p->used) HIP_TRY(hipMemcpy(tmp.data(), p->keys.get(), p->used * 8, hipMemcpyDeviceToHost));
+  p->keys.reset();
+  p->spill.reserve(p->spill.size() + p->used);
+  for (const auto& s : p->segs)
+    for (uint64_t q = 0; q < s.count; ++q) p->spill.push_back(kr::KeyRank{tmp[s.off + q], s.rank});
+  p->segs.clear();
+  p->used = 0, p->on_host = true;
+  return KR_OK;
+}
+// room for n more pairs: doubling, with a device-to-device copy; false: no room to be had (the pool is as it was)
+bool pool_room(kr::KeyPool* p, uint64_t n)
+{
+  if (p->used + n <= p->keys.size()) return true;
+  uint64_t cap = std::max<uint64_t>(p->keys.size(), 1);
+  const bool first = p->keys.size() == 0;
+  if (first) cap = pool_start_pairs();
+  while (cap < p->used + n) cap *= 2;
+  DevBuf<uint64_t> bigger;
+  if (!bigger.reserve(cap)) {
+    (void)hipGetLastError();
+    return false;
+  }
+  if (p->used && hipMemcpy(bigger.get(), p->keys.get(), p->used * 8, hipMemcpyDeviceToDevice) != hipSuccess) return false;
+  p->keys = std::move(bigger);
+  if (!first) p->growths++;
+  return true;
+}
+int pool_append(kr::KeyPool* p, const uint64_t* src, uint64_t n, uint32_t rank, bool src_on_device)
+{
+  if (!p) return kr::fail(KR_ERR_ARG, "key pool: null");
+  if (n == 0) return KR_OK;
+  if (!p->on_host && !pool_room(p, n)) {
+    if (int rc = pool_to_host(p)) return rc;
+  }
+  if (p->on_host) {
+    std::vector<uint64_t> tmp;
+    if (src_on_device) {
+      tmp.resize(n);
+      HIP_TRY(hipMemcpy(tmp.data(), src, n * 8, hipMemcpyDeviceToHost));
+      src = tmp.data();
+    }
+    for (uint64_t q = 0; q < n; ++q) p->spill.push_back(kr::KeyRank{src[q], rank});
+    return KR_OK;
+  }
+  HIP_TRY(hipMemcpy(p->keys.get() + p->used, src, n * 8, src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+  p->segs.push_back(kr::KeyPool::Seg{p->used, n, rank});
+  p->used += n;
+  return KR_OK;
+}
+} // namespace
+
+int kr::key_pool_create(int device, KeyPool** out)
+{
+  if (int rc = set_device(device, "key pool")) return rc;
+  *out = new KeyPool();
+  (*out)->device = device;
+  return KR_OK;
+}
+void kr::key_pool_free(KeyPool* p)
+{
+  if (!p) return;
+  if (p->keys.get()) (void)hipSetDevice(p->device);
+  delete p;
+}
+int kr::key_pool_append_device(KeyPool* p, const uint64_t* d_keys, uint64_t n, uint32_t rank) { return pool_append(p, d_keys, n, rank, true); }
+int kr::key_pool_append_host(KeyPool* p, const uint64_t* keys, uint64_t n, uint32_t rank) { return pool_append(p, keys, n, rank, false); }
+void kr::key_stage_note_path(uint64_t path) { note(0, 0, 0, 0, 0, path); }
+
+namespace {
+// the pool's segments expanded into a rank array, and the stage on both, in place
+int pool_on_device(kr::KeyPool* p, uint32_t nrows, uint32_t nleaves, kr_key_groups* out, uint64_t* npasses)
+{
+  const uint64_t n = p->used;
+  const uint32_t nseg = (uint32_t)p->segs.size();
+  std::vector<uint64_t> seg_off(nseg + 1);
+  std::vector<uint32_t> seg_rank(nseg);
+  for (uint32_t q = 0; q < nseg; ++q) seg_off[q] = p->segs[q].off, seg_rank[q] = p->segs[q].rank;
+  seg_off[nseg] = n;
+  DevBuf<uint64_t> b_off;
+  DevBuf<uint32_t> b_rank, b_ra;
+  if (!b_off.reserve(nseg + 1) || !b_rank.reserve(nseg) || !b_ra.reserve(n)) {
+    (void)hipGetLastError();
+    return kr::fail(KR_ERR_NOMEM, "key pool: out of device memory");
+  }
+  HIP_TRY(hipMemcpy(b_off.get(), seg_off.data(), (nseg + 1) * 8ull, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(b_rank.get(), seg_rank.data(), nseg * 4ull, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(kr_keys_expand_kernel, dim3(grid_for((n + 255) / 256)), dim3(256), 0, 0, (const uint64_t*)b_off.get(), (const uint32_t*)b_rank.get(), nseg, n,
+                     b_ra.get());
+  HIP_TRY(hipGetLastError());
+  return run_stage(p->keys.get(), b_ra.get(), n, nrows, nleaves, out, npasses);
+}
+} // namespace
+
+int kr::key_pool_finish(KeyPool* p, uint32_t nrows, uint32_t nleaves, kr_key_groups* out)
+{
+  if (!p || !out) return kr::fail(KR_ERR_ARG, "key pool: null");
+  if (int rc = set_device(p->device, "key pool")) return rc;
+  const uint64_t n = p->on_host ? p->spill.size() : p->used;
+  if (!p->on_host && n) {
+    uint64_t npasses = 0;
+    int rc = stage_fits(n, nrows, n * 8) ? pool_on_device(p, nrows, nleaves, out, &npasses) : KR_ERR_NOMEM;
+    if (rc != KR_ERR_NOMEM) {
+      if (rc == KR_OK) note(n, out->npairs, out->nkeys, npasses, p->growths, 1);
+      p->keys.reset();
+      p->used = 0, p->segs.clear();
+      return rc;
+    }
+    kr::clear_error(); // no room on the device: the pool is as it was, and the host can finish
+    if ((rc = pool_to_host(p))) return rc;
+  }
+  int rc = kr::key_groups_host(p->spill, nrows, nleaves, out);
+  if (rc == KR_OK) note(n, out->npairs, out->nkeys, 0, p->growths, n ? 2 : 1);
+  return rc;
+}
+
+extern "C" int kr_key_groups_device(int device, const uint64_t* keys, const uint32_t* ranks, uint64_t n, uint32_t nrows, uint32_t nleaves, kr_key_groups* out)
+{
+  kr::clear_error();
+  if (!out || (n && (!keys || !ranks))) return kr::fail(KR_ERR_ARG, "kr_key_groups_device: null argument");
+  memset(out, 0, sizeof(*out));
+  if (nleaves > 65536u) return kr::fail(KR_ERR_ARG, "kr_key_groups_device: more than 65536 leaves");
+  if (int rc = set_device(device, "kr_key_groups_device")) return rc;
+  if (n == 0) {
+    int rc = kr::key_groups_alloc(out, 0, 0, nrows);
+    if (rc == KR_OK) note(0, 0, 0, 0, 0, 1);
+    return rc;
+  }
+  int rc = KR_ERR_NOMEM;
+  if (stage_fits(n, nrows, 0)) {
+    DevBuf<uint64_t> b_ka; // (freed where the block is left)
+    DevBuf<uint32_t> b_ra;
+    uint64_t npasses = 0;
+    if (b_ka.reserve(n) && b_ra.reserve(n)) {
+      HIP_TRY(hipMemcpy(b_ka.get(), keys, n * 8, hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(b_ra.get(), ranks, n * 4, hipMemcpyHostToDevice));
+      rc = run_stage(b_ka.get(), b_ra.get(), n, nrows, nleaves, out, &npasses);
+    } else {
+      (void)hipGetLastError();
+    }
+    if (rc == KR_OK) note(n, out->npairs, out->nkeys, npasses, 0, 1);
+  }
+  if (rc != KR_ERR_NOMEM) return rc;
+  kr::clear_error(); // no room on the device: the twin, with the same result
+  rc = kr_key_groups_cpu(keys, ranks, n, nrows, nleaves, out);
+  if (rc == KR_OK) note(n, out->npairs, out->nkeys, 0, 0, 2);
+  return rc;
+}
+
+extern "C" void kr_debug_build_keys(uint64_t out[8])
+{
+  if (!out) return;
+  for (int q = 0; q < 8; ++q) out[q] = g_stat[q].load();
+  out[6] = kTile; // (also before the first call)
+}

@@ -169,9 +169,38 @@ int sdust_lists_host(const uint8_t* bases, const uint64_t* offsets, uint32_t nco
 int finish_sdust(const std::vector<uint64_t>& iv, const std::vector<uint64_t>& ioff, kr_sdust_result* out);
 void resolve_mask(const uint8_t* seq, uint64_t len, uint32_t k, const uint64_t* rgs, size_t mn, std::vector<uint64_t>& skip,
                   std::vector<uint64_t>& brk);
+// ---- the key stage (kr_key_groups_cpu / _device; kr_build.cpp, kr_build_keys.hip) ----
+struct KeyRank {
+  uint64_t key;
+  uint32_t rank;
+};
+// The builder's host path: `all` sorted by (key, rank) in one comparison sort, then one walk over the runs of equal keys.  Takes `all`
+// apart (it is empty afterwards); any number of leaves.  kr_key_groups_cpu is this behind the public checks.
+int key_groups_host(std::vector<KeyRank>& all, uint32_t nrows, uint32_t nleaves, kr_key_groups* out);
+// malloc'd arrays of a kr_key_groups for nkeys / npairs / nrows (inc zeroed, goff[0] = 0), or KR_ERR_NOMEM with nothing held
+int key_groups_alloc(kr_key_groups* out, uint64_t nkeys, uint64_t npairs, uint32_t nrows);
+// The raw keys of all genomes on the device, with a segment table (offset, count, leaf rank): filled genome by genome by
+// minimizers_device (under the builder's lock around the device), then sorted and grouped in place by key_pool_finish -- or copied
+// back and finished by key_groups_host when the stage's buffers do not fit (same result).
+struct KeyPool;
+int key_pool_create(int device, KeyPool** out);
+int key_pool_append_device(KeyPool* p, const uint64_t* d_keys, uint64_t n, uint32_t rank); // device-to-device
+int key_pool_append_host(KeyPool* p, const uint64_t* keys, uint64_t n, uint32_t rank);
+int key_pool_finish(KeyPool* p, uint32_t nrows, uint32_t nleaves, kr_key_groups* out);
+void key_pool_free(KeyPool* p);
+void key_stage_note_path(uint64_t path); // kr_debug_build_keys: a build that could not use the device's key stage at all (3)
+// Where minimizers_device leaves a genome's keys and from which sums it counts on: pool == null: the keys come back in `out` as
+// ever; else they stay in the pool under leaf rank `rank` (the contig-end keys the host computes are appended by a small copy) and
+// `out` has none.  n1 / n2: the sums to add the contigs' estimates to, in order (a sketch's batches of records).
+struct MinSink {
+  KeyPool* pool;
+  uint32_t rank;
+  double n1, n2;
+};
 // kr_minimizers_device with the contigs' sdust lists given (iv / ioff as kr_sdust_result lays them out), or null: made inside
 int minimizers_device(int device, const kr_build_params* bp, const uint8_t* bases, const uint64_t* offsets, uint32_t ncontigs,
-                      const std::vector<uint64_t>* iv, const std::vector<uint64_t>* ioff, kr_minimizer_result* out);
+                      const std::vector<uint64_t>* iv, const std::vector<uint64_t>* ioff, kr_minimizer_result* out,
+                      const MinSink* sink = nullptr);
 
 // ---- `place` back end on the device (kr_device.hip), driven by kr_place.cpp ----
 // The placement tree as flat arrays over its nodes q = 1..pn (q = post-order number, so the subtree of q is the

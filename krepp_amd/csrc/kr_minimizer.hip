@@ -221,7 +221,8 @@ int pick_device(int device, const char* who)
 } // namespace
 
 int kr::minimizers_device(int device, const kr_build_params* bp, const uint8_t* bases, const uint64_t* offsets, uint32_t ncontigs,
-                          const std::vector<uint64_t>* iv_in, const std::vector<uint64_t>* ioff_in, kr_minimizer_result* out)
+                          const std::vector<uint64_t>* iv_in, const std::vector<uint64_t>* ioff_in, kr_minimizer_result* out,
+                          const kr::MinSink* sink)
 {
   kr::BuildCfg c;
   kr::LshPositions lsh;
@@ -247,7 +248,8 @@ int kr::minimizers_device(int device, const kr_build_params* bp, const uint8_t* 
     for (uint64_t p0 = 0; p0 < len; p0 += kTile) tiles.push_back(make_uint2(q, (uint32_t)p0));
   }
   std::vector<uint64_t> keys;
-  double n1 = 0, n2 = 0;
+  double n1 = sink ? sink->n1 : 0, n2 = sink ? sink->n2 : 0;
+  kr::KeyPool* pool = sink ? sink->pool : nullptr;
   std::vector<uint64_t> skip, brk, mwoff; // sdust: the interval walks of all contigs as bit strings
   if (!tiles.empty()) {
     std::vector<uint32_t> regs((size_t)ncontigs * 8192);
@@ -305,8 +307,12 @@ int kr::minimizers_device(int device, const kr_build_params* bp, const uint8_t* 
     unsigned long long nk = 0;
     HIP_TRY(hipMemcpy(&nk, d_n, 8, hipMemcpyDeviceToHost));
     if (nk > cap) return kr::fail(KR_ERR_CAPACITY, "kr_minimizers_device: key buffer overflow");
-    keys.resize(nk);
-    if (nk) HIP_TRY(hipMemcpy(keys.data(), d_keys, nk * 8, hipMemcpyDeviceToHost));
+    if (pool) { // the keys stay on the device: no copy back, no sort here (the key stage drops duplicates after its global sort)
+      if ((rc = kr::key_pool_append_device(pool, d_keys, nk, sink->rank))) return rc;
+    } else {
+      keys.resize(nk);
+      if (nk) HIP_TRY(hipMemcpy(keys.data(), d_keys, nk * 8, hipMemcpyDeviceToHost));
+    }
     HIP_TRY(hipMemcpy(regs.data(), d_hll, regs.size() * 4, hipMemcpyDeviceToHost));
     }
     // contig ends + HyperLogLog estimates, contig by contig as the reference adds them
@@ -330,6 +336,10 @@ int kr::minimizers_device(int device, const kr_build_params* bp, const uint8_t* 
       for (int i = 0; i < 4096; ++i) r8[i] = (uint8_t)r2[i];
       n2 += kr::hll12_estimate(r8.data());
     }
+  }
+  if (pool) { // `keys` holds the contig-end keys alone
+    if ((rc = kr::key_pool_append_host(pool, keys.data(), keys.size(), sink->rank))) return rc;
+    keys.clear();
   }
   return kr::finish_minimizers(keys, n1, n2, out);
 }

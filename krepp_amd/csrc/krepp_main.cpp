@@ -56,7 +56,7 @@ static const std::map<std::string, std::string> kAlias = {
   {"-i", "--index-dir"}, {"-q", "--query"}, {"-o", "--output-path"}, {"-t", "--nwk-file"}, {"-k", "--kmer-len"},
   {"-w", "--win-len"}, {"-h", "--num-positions"}, {"-m", "--modulo-lsh"}, {"-r", "--residue-lsh"}, {"-l", "--lineage-file"},
 };
-static const char* kFlags[] = {"--multi", "--filter", "--summarize", "--frac", "--verbose", "--gpu-minimizers", "--tabular", "--gpu-parse", "--gpu-seek"};
+static const char* kFlags[] = {"--multi", "--filter", "--summarize", "--frac", "--verbose", "--gpu-minimizers", "--gpu-keys", "--tabular", "--gpu-parse", "--gpu-seek"};
 
 // options as in the reference's CLI (src/krepp.cpp:516-675); the texts are this build's own
 static void print_help(const std::string& sub)
@@ -107,10 +107,16 @@ static void print_help(const std::string& sub)
     printf("\nkrepp index -i MAP.tsv -o DIR: build an index (reference ID <tab> FASTA path per line)\n"
            "  -t, --nwk-file PATH        rooted guide tree (default: a balanced tree over the IDs)\n%s"
            "      --num-threads N        CPU threads of the builder [1]\n"
-           "      --gpu-minimizers       window minimizers of the genomes on the GPU (identical output)\n",
+           "      --gpu-minimizers       window minimizers of the genomes on the GPU (identical output)\n"
+           "      --gpu-keys             also sort and group all genomes' keys on the GPU (implies --gpu-minimizers; identical output)\n"
+           "      --device D             the GPU of --gpu-minimizers / --gpu-keys [0]\n",
            build_opts);
   if (sub.empty() || sub == "sketch")
-    printf("\nkrepp sketch -i GENOME.fa -o SKETCH: sketch of a single FASTA/FASTQ file (default k 26)\n%s", build_opts);
+    printf("\nkrepp sketch -i GENOME.fa -o SKETCH: sketch of a single FASTA/FASTQ file (default k 26)\n%s"
+           "      --gpu-minimizers       window minimizers on the GPU (identical output)\n"
+           "      --gpu-keys             also sort the keys and count the rows on the GPU (implies --gpu-minimizers; identical output)\n"
+           "      --device D             the GPU of --gpu-minimizers / --gpu-keys [0]\n",
+           build_opts);
   printf("\nEnvironment knobs and what differs from the reference: INTEGRATION.md\n");
 }
 
@@ -1282,6 +1288,15 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
   return r.finish();
 }
 
+// --gpu-minimizers / --gpu-keys / --device of `index` and `sketch`: kr_build_params::gpu_minimizers is a bit set, the key stage implies the leaf stage
+static void gpu_build_options(const Args& a, kr_build_params& bp)
+{
+  auto on = [&](const char* f) { return a.flag.count(f) && a.flag.at(f); };
+  bp.gpu_minimizers = on("--gpu-minimizers") ? KR_BUILD_GPU_MINIMIZERS : 0u;
+  if (on("--gpu-keys")) bp.gpu_minimizers |= KR_BUILD_GPU_MINIMIZERS | KR_BUILD_GPU_KEYS;
+  bp.device = a.has("--device") ? atoi(a.get("--device").c_str()) : 0;
+}
+
 // --sdust-t / --sdust-w (src/krepp.cpp:530-531,576-577): non-negative integers, masking on when both are positive, and then the
 // two lines of validate_configuration (src/krepp.hpp:80-83)
 static void sdust_options(const Args& a, kr_build_params& bp)
@@ -1331,8 +1346,7 @@ static int run_index(const Args& a)
   if (a.flag.count("--frac")) bp.frac = a.flag.at("--frac");
   bp.num_threads = a.has("--num-threads") ? (uint32_t)atoi(a.get("--num-threads").c_str()) : 1;
   bp.seed = a.has("--seed") ? (uint32_t)atoi(a.get("--seed").c_str()) : 0;
-  bp.gpu_minimizers = a.flag.count("--gpu-minimizers") && a.flag.at("--gpu-minimizers");
-  bp.device = a.has("--device") ? atoi(a.get("--device").c_str()) : 0;
+  gpu_build_options(a, bp);
   sdust_options(a, bp);
   fprintf(stderr, "Building the index...\n");
   std::string nwk = a.get("--nwk-file");
@@ -1359,6 +1373,7 @@ static int run_sketch(const Args& a)
   if (a.has("--residue-lsh")) bp.r = (uint32_t)atoi(a.get("--residue-lsh").c_str());
   if (a.flag.count("--frac")) bp.frac = a.flag.at("--frac");
   bp.seed = a.has("--seed") ? (uint32_t)atoi(a.get("--seed").c_str()) : 0;
+  gpu_build_options(a, bp);
   sdust_options(a, bp);
   fprintf(stderr, "Initializing the sketch...\n");
   if (kr_build_sketch(input.c_str(), outp.c_str(), &bp)) error_exit(kr_last_error());
