@@ -826,16 +826,20 @@ KR_API int kr_place_frame(const kr_place_tree*, int which, int tabular, const ch
  * the reference.  `gpu_minimizers` is a bit set that moves stages to the GPU `device`, with identical files:
  *   KR_BUILD_GPU_MINIMIZERS  the leaf stage (window minimizers of every genome; kr_minimizers_device)
  *   KR_BUILD_GPU_KEYS        also the key stage: all genomes' keys stay in a device pool and are sorted and grouped there
- *                            (kr_key_groups_device); implies the leaf stage.  The colours of the groups stay on the host. */
+ *                            (kr_key_groups_device); implies the leaf stage.  The colours of the groups stay on the host.
+ *   KR_BUILD_GPU_COLOURS     also the colour classes: the distinct leaf sets among the groups are found on the device while the
+ *                            groups are still there (kr_colour_classes_device), and the host folds each set into a colour once
+ *                            instead of once per key; implies the key and the leaf stage. */
 #define KR_BUILD_GPU_MINIMIZERS 1u
 #define KR_BUILD_GPU_KEYS 2u
+#define KR_BUILD_GPU_COLOURS 4u          /* implies KR_BUILD_GPU_KEYS and KR_BUILD_GPU_MINIMIZERS */
 typedef struct kr_build_params {
   uint32_t k, w, h, m, r, frac; /* defaults 29, 35, 13, 4, 1, 1 (src/krepp.hpp:47-58) */
   uint32_t num_threads;
   uint32_t seed;
   const uint8_t* ppos;          /* optional explicit LSH positions [h] (descending)    */
-  uint32_t gpu_minimizers;      /* bit set KR_BUILD_GPU_*: 1 leaf stage, 2 key stage too, on the GPU `device`;     */
-  int32_t device;               /*    identical output, checked by tests/test_minimizers.py, test_gpu_build_keys.py */
+  uint32_t gpu_minimizers;      /* bit set KR_BUILD_GPU_*: 1 leaf stage, 2 key stage too, 4 colour classes too, on the GPU `device`; */
+  int32_t device;               /*    identical output, checked by tests/test_minimizers.py, test_gpu_build_keys.py, test_gpu_build_colours.py */
   uint32_t sdust_t, sdust_w;    /* --sdust-t / --sdust-w (src/krepp.cpp:530-531,576-577): both > 0 keeps the sdust intervals  */
                                 /* of every contig out of the minimizer windows (src/rqseq.cpp:71-107); either 0: off    */
 } kr_build_params;
@@ -884,6 +888,31 @@ KR_API void kr_key_groups_free(kr_key_groups*);
  * radix passes run, pool growths, path taken (1 device, 2 fell back to the host for memory, 3 fell back for more than 65,536
  * leaves), pairs per tile of the sort, 0}. */
 KR_API void kr_debug_build_keys(uint64_t out[8]);
+
+/* The colour classes of key groups (goff / ranks as kr_key_groups lays them out; goff[0] = 0, goff ascending): a class is one
+ * distinct rank sequence among the groups of two or more ranks.  Both functions hold these invariants:
+ *   every group of a class has exactly the ranks of group rep[class];
+ *   rep[c] is the smallest group index in class c and rep ascends, so that classes are numbered in order of first appearance;
+ *   a group of fewer than two ranks has KR_NO_CLASS.
+ * _cpu is the canonical form, exactly one class per distinct set (a hash map on the host).  _device sorts 64-bit fingerprints of the
+ * sets (a wrapping sum of hashed ranks plus a hashed length, from one scan over all ranks) and compares every group's ranks with
+ * those of its predecessor in that order; it gives the canonical form unless two different sets share a fingerprint, in which case
+ * a set may be split over several classes, each led by its own smallest group index.  When the device has no room the classes
+ * come from _cpu (never an error).  KR_BUILD_COLOUR_HASH_BITS=N (environment, read at each call, default 64) keeps only the low N
+ * bits of every fingerprint: a knob for tests of the content compare. */
+#define KR_NO_CLASS 0xFFFFFFFFu
+typedef struct kr_colour_classes {
+  uint32_t* class_of;  /* [nkeys]    class of group i; KR_NO_CLASS for a group of one rank                    */
+  uint64_t* rep;       /* [nclasses] a group index per class, strictly ascending: the class's FIRST group      */
+  uint64_t nkeys, nclasses;
+} kr_colour_classes;
+KR_API int kr_colour_classes_cpu(const uint64_t* goff, const uint32_t* ranks, uint64_t nkeys, kr_colour_classes* out);
+KR_API int kr_colour_classes_device(int device, const uint64_t* goff, const uint32_t* ranks, uint64_t nkeys, kr_colour_classes* out);
+KR_API void kr_colour_classes_free(kr_colour_classes*);
+/* Tests: the calling process's last kr_colour_classes_device or index build: {groups, groups of >= 2 ranks, classes, classes whose
+ * fingerprint equals their predecessor's in the sorted list (raised by the content compare alone), path (0 not asked, 1 device,
+ * 2 host), sort passes, 0, 0}. */
+KR_API void kr_debug_build_colours(uint64_t out[8]);
 
 /* The masker on its own: per contig the list that the reference's sdust(0, seq, -1, T, W, &n) (src/sdust.h) returns, element for
  * element: intervals[offsets[c] .. offsets[c+1]) = (start << 32 | finish), finish exclusive.  Its alphabet is sdust's own (bytes

@@ -103,6 +103,10 @@ class KrKeyGroups(C.Structure):
                 ("nrows", C.c_uint32)]
 
 
+class KrColourClasses(C.Structure):
+    _fields_ = [("class_of", u32p), ("rep", u64p), ("nkeys", C.c_uint64), ("nclasses", C.c_uint64)]
+
+
 class KrSdustResult(C.Structure):
     _fields_ = [("intervals", u64p), ("offsets", u64p), ("ncontigs", C.c_uint32)]
 
@@ -135,6 +139,7 @@ EXPORTS = [
     "kr_build_index", "kr_minimizers_cpu", "kr_minimizers_device", "kr_minimizers_free", "kr_last_error", "kr_version",
     "kr_sdust_cpu", "kr_sdust_free",
     "kr_key_groups_cpu", "kr_key_groups_device", "kr_key_groups_free", "kr_debug_build_keys",
+    "kr_colour_classes_cpu", "kr_colour_classes_device", "kr_colour_classes_free", "kr_debug_build_colours",
     "kr_stream_seek_enable", "kr_batch_collect_seek", "kr_debug_seek_layout", "kr_debug_seek_ms",
     "kr_stream_bgzf_enable", "kr_batch_submit_bgzf", "kr_debug_bgzf_inflate", "kr_debug_bgzf_inflate_host", "kr_debug_bgzf_ms",
     "kr_bgzf_member_size", "kr_bgzf_walk", "kr_bgzf_chunk_cut", "kr_fastx_open_at_bgzf",
@@ -1117,11 +1122,13 @@ def place_heavy_reads():
     return int(c.value)
 
 
-KR_BUILD_GPU_MINIMIZERS, KR_BUILD_GPU_KEYS = 1, 2  # bits of kr_build_params.gpu_minimizers
+KR_BUILD_GPU_MINIMIZERS, KR_BUILD_GPU_KEYS, KR_BUILD_GPU_COLOURS = 1, 2, 4  # bits of kr_build_params.gpu_minimizers
+KR_NO_CLASS = 0xFFFFFFFF
 
 
-def _gpu_build_bits(gpu_minimizers, gpu_keys):
-    return (KR_BUILD_GPU_MINIMIZERS if gpu_minimizers else 0) | (KR_BUILD_GPU_MINIMIZERS | KR_BUILD_GPU_KEYS if gpu_keys else 0)
+def _gpu_build_bits(gpu_minimizers, gpu_keys, gpu_colours=False):
+    return ((KR_BUILD_GPU_MINIMIZERS if gpu_minimizers else 0) | (KR_BUILD_GPU_MINIMIZERS | KR_BUILD_GPU_KEYS if gpu_keys else 0)
+            | (KR_BUILD_GPU_MINIMIZERS | KR_BUILD_GPU_KEYS | KR_BUILD_GPU_COLOURS if gpu_colours else 0))
 
 
 def key_groups(keys, ranks, nrows, nleaves, device=None, copy=True):
@@ -1165,13 +1172,47 @@ def build_keys_stats():
             "path": int(v[5]), "tile": int(v[6])}
 
 
+def group_colour_classes(goff, ranks, device=None):
+    """The colour classes of key groups (goff / ranks as key_groups returns them): (class_of[nkeys], rep[nclasses]) from
+    kr_colour_classes_cpu (device=None) or _device.  (colour_classes, above, is the upload's pass over a colour table.)"""
+    lib = load()
+    goff = np.ascontiguousarray(goff, dtype=np.uint64)
+    ranks = np.ascontiguousarray(ranks, dtype=np.uint32)
+    assert len(goff) >= 1
+    res = KrColourClasses()
+    vp = C.c_void_p
+    lib.kr_colour_classes_cpu.argtypes = [vp, vp, C.c_uint64, C.POINTER(KrColourClasses)]
+    lib.kr_colour_classes_device.argtypes = [C.c_int, vp, vp, C.c_uint64, C.POINTER(KrColourClasses)]
+    lib.kr_colour_classes_free.argtypes = [C.POINTER(KrColourClasses)]
+    lib.kr_colour_classes_free.restype = None
+    rp = ranks.ctypes.data if len(ranks) else None
+    if device is None:
+        check(lib.kr_colour_classes_cpu(goff.ctypes.data, rp, len(goff) - 1, C.byref(res)))
+    else:
+        check(lib.kr_colour_classes_device(int(device), goff.ctypes.data, rp, len(goff) - 1, C.byref(res)))
+    out = _np(res.class_of, res.nkeys, np.uint32), _np(res.rep, res.nclasses, np.uint64)
+    lib.kr_colour_classes_free(C.byref(res))
+    return out
+
+
+def build_colours_stats():
+    """kr_debug_build_colours: the process's last kr_colour_classes_device or index build."""
+    v = (C.c_uint64 * 8)()
+    lib = load()
+    lib.kr_debug_build_colours.argtypes = [C.POINTER(C.c_uint64 * 8)]
+    lib.kr_debug_build_colours.restype = None
+    lib.kr_debug_build_colours(C.byref(v))
+    return {"groups": int(v[0]), "multi": int(v[1]), "classes": int(v[2]), "raised": int(v[3]), "path": int(v[4]), "passes": int(v[5])}
+
+
 def build_index(input_tsv, out_dir, nwk=None, k=29, w=35, h=13, m=4, r=1, frac=True, num_threads=1, seed=0, ppos=None,
-                gpu_minimizers=False, device=0, sdust_t=0, sdust_w=0, gpu_keys=False):
-    """`krepp index` (reference: src/krepp.cpp:131-303), on the CPU unless gpu_minimizers (the leaf stage on `device`) or gpu_keys
-    (the key sort and grouping there too; implies the leaf stage).  sdust_t, sdust_w both > 0: --sdust-t/-w masking."""
+                gpu_minimizers=False, device=0, sdust_t=0, sdust_w=0, gpu_keys=False, gpu_colours=False):
+    """`krepp index` (reference: src/krepp.cpp:131-303), on the CPU unless gpu_minimizers (the leaf stage on `device`), gpu_keys
+    (the key sort and grouping there too; implies the leaf stage) or gpu_colours (the groups' distinct leaf sets found there too,
+    each folded into a colour once; implies both).  sdust_t, sdust_w both > 0: --sdust-t/-w masking."""
     lib = load()
     p = KrBuildParams(k=k, w=w, h=h, m=m, r=r, frac=int(frac), num_threads=num_threads, seed=seed, ppos=None,
-                      gpu_minimizers=_gpu_build_bits(gpu_minimizers, gpu_keys), device=device, sdust_t=sdust_t, sdust_w=sdust_w)
+                      gpu_minimizers=_gpu_build_bits(gpu_minimizers, gpu_keys, gpu_colours), device=device, sdust_t=sdust_t, sdust_w=sdust_w)
     keep = None
     if ppos is not None:
         keep = (C.c_uint8 * len(ppos))(*ppos)

@@ -1,5 +1,6 @@
 // kr_build.cpp — index construction (`krepp index`, `krepp sketch`).  On the CPU by default; the leaf stage and the key stage
-// can run on the GPU (kr_build_params::gpu_minimizers, kr_minimizer.hip, kr_build_keys.hip) with identical files.  It exists
+// can run on the GPU, and the groups' colour classes be found there (kr_build_params::gpu_minimizers, kr_minimizer.hip,
+// kr_build_keys.hip), with identical files.  It exists
 // because no index can be obtained any other way (the reference ships none).  Output files follow the reference's on-disk format
 // byte for byte (src/krepp.cpp:18-29,206-246; src/table.cpp:77-83;
 // src/record.cpp:213-219).
@@ -22,6 +23,7 @@
 #include "kr_sdust.h"
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -408,7 +410,96 @@ int key_groups_host(std::vector<KeyRank>& all, uint32_t nrows, uint32_t nleaves,
   return KR_OK;
 }
 
+// ---- the colour classes on the host ----
+int colour_classes_alloc(kr_colour_classes* out, uint64_t nkeys, uint64_t cap)
+{
+  memset(out, 0, sizeof(*out));
+  out->class_of = (uint32_t*)malloc(std::max<uint64_t>(1, nkeys) * 4);
+  out->rep = (uint64_t*)malloc(std::max<uint64_t>(1, cap) * 8);
+  if (!out->class_of || !out->rep) {
+    kr_colour_classes_free(out);
+    return fail(KR_ERR_NOMEM, "colour classes: out of memory");
+  }
+  memset(out->class_of, 0xFF, nkeys * 4);
+  out->nkeys = nkeys;
+  return KR_OK;
+}
+
+// One class per distinct rank sequence: a hash map from the sequence's hash to the newest class with it, classes of one hash chained
+// through `next`; a group joins the class whose first group has its very ranks, or opens one.
+int colour_classes_host(const uint64_t* goff, const uint32_t* ranks, uint64_t nkeys, kr_colour_classes* out)
+{
+  uint64_t multi = 0;
+  for (uint64_t i = 0; i < nkeys; ++i) multi += goff[i + 1] - goff[i] >= 2;
+  if (multi >= KR_NO_CLASS) return fail(KR_ERR_CAPACITY, "colour classes: 2^32 - 1 groups of several ranks or more");
+  std::vector<uint64_t> rep;
+  std::vector<uint32_t> next;
+  std::unordered_map<uint64_t, uint32_t> newest;
+  int rc = colour_classes_alloc(out, nkeys, 0);
+  if (rc) return rc;
+  for (uint64_t i = 0; i < nkeys; ++i) {
+    const uint64_t a = goff[i], len = goff[i + 1] - a;
+    if (len < 2) continue;
+    uint64_t h = fmix64(len);
+    for (uint64_t q = 0; q < len; ++q) h = fmix64(h ^ ranks[a + q]) + q;
+    auto ins = newest.emplace(h, (uint32_t)rep.size());
+    uint32_t c = ins.second ? KR_NO_CLASS : ins.first->second;
+    for (; c != KR_NO_CLASS; c = next[c]) {
+      const uint64_t b = goff[rep[c]];
+      if (goff[rep[c] + 1] - b == len && !memcmp(ranks + a, ranks + b, len * 4)) break;
+    }
+    if (c == KR_NO_CLASS) {
+      c = (uint32_t)rep.size();
+      next.push_back(ins.second ? KR_NO_CLASS : ins.first->second);
+      ins.first->second = c;
+      rep.push_back(i);
+    }
+    out->class_of[i] = c;
+  }
+  free(out->rep);
+  out->rep = (uint64_t*)malloc(std::max<size_t>(1, rep.size()) * 8);
+  if (!out->rep) {
+    kr_colour_classes_free(out);
+    return fail(KR_ERR_NOMEM, "colour classes: out of memory");
+  }
+  if (!rep.empty()) memcpy(out->rep, rep.data(), rep.size() * 8);
+  out->nclasses = rep.size();
+  return KR_OK;
+}
+
+namespace {
+std::atomic<uint64_t> g_colour_stat[8];
+}
+void colour_stats_note(uint64_t groups, uint64_t multi, uint64_t classes, uint64_t raised, uint64_t path, uint64_t passes)
+{
+  const uint64_t v[8] = {groups, multi, classes, raised, path, passes, 0, 0};
+  for (int q = 0; q < 8; ++q) g_colour_stat[q].store(v[q]);
+}
+
 } // namespace kr
+
+extern "C" int kr_colour_classes_cpu(const uint64_t* goff, const uint32_t* ranks, uint64_t nkeys, kr_colour_classes* out)
+{
+  kr::clear_error();
+  if (!out || !goff) return kr::fail(KR_ERR_ARG, "kr_colour_classes_cpu: null argument");
+  memset(out, 0, sizeof(*out));
+  if (goff[0] != 0 || !std::is_sorted(goff, goff + nkeys + 1)) return kr::fail(KR_ERR_ARG, "kr_colour_classes_cpu: goff must ascend from 0");
+  if (goff[nkeys] && !ranks) return kr::fail(KR_ERR_ARG, "kr_colour_classes_cpu: null argument");
+  return kr::colour_classes_host(goff, ranks, nkeys, out);
+}
+
+extern "C" void kr_colour_classes_free(kr_colour_classes* c)
+{
+  if (!c) return;
+  free(c->class_of), free(c->rep);
+  memset(c, 0, sizeof(*c));
+}
+
+extern "C" void kr_debug_build_colours(uint64_t out[8])
+{
+  if (!out) return;
+  for (int q = 0; q < 8; ++q) out[q] = kr::g_colour_stat[q].load();
+}
 
 extern "C" int kr_key_groups_cpu(const uint64_t* keys, const uint32_t* ranks, uint64_t n, uint32_t nrows, uint32_t nleaves, kr_key_groups* out)
 {
@@ -568,12 +659,26 @@ bool write_file(const std::string& path, const void* hdr, size_t hdr_bytes, cons
 struct PhaseClock {
   const bool on = getenv("KR_BUILD_TIMING") && atoi(getenv("KR_BUILD_TIMING")) != 0;
   std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now(), last = t0;
-  void done(const char* phase)
+  // less: seconds of the time since the last phase that belong to another phase (printed by span)
+  void done(const char* phase, double less = 0)
   {
     if (!on) return;
     const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "build timing: %-24s %10.3f s\n", phase, std::chrono::duration<double>(now - last).count());
+    fprintf(stderr, "build timing: %-24s %10.3f s\n", phase, std::chrono::duration<double>(now - last).count() - less);
     last = now;
+  }
+  void span(const char* phase, double seconds)
+  {
+    if (on) fprintf(stderr, "build timing: %-24s %10.3f s\n", phase, seconds);
+  }
+  void classes()
+  {
+    if (!on) return;
+    uint64_t st[8] = {0};
+    kr_debug_build_colours(st);
+    fprintf(stderr, "build colours: groups %llu multi_rank_groups %llu classes %llu raised_by_compare %llu path %llu passes %llu\n",
+            (unsigned long long)st[0], (unsigned long long)st[1], (unsigned long long)st[2], (unsigned long long)st[3], (unsigned long long)st[4],
+            (unsigned long long)st[5]);
   }
   // the key stage's counts; pairs_in / passes: what the device path saw (0: the host path, whose input is unique per genome already)
   void keys(const kr_key_groups& g, bool device_pool)
@@ -708,7 +813,7 @@ extern "C" int kr_build_index(const char* input_tsv, const char* nwk_path, const
   if (sdust_t && sdust_w < 4) return kr::fail(KR_ERR_ARG, "--sdust-w must be at least 4");
   // KR_BUILD_GPU_KEYS: the genomes' raw keys stay on the device, in a pool that the key stage sorts and groups after the last genome
   PoolOwner pool;
-  if (bp->gpu_minimizers & KR_BUILD_GPU_KEYS) {
+  if (bp->gpu_minimizers & (KR_BUILD_GPU_KEYS | KR_BUILD_GPU_COLOURS)) {
     if (nleaves > 65536u)
       kr::key_stage_note_path(3); // two rank digits at most: this build keeps its keys on the host
     else if (int prc = kr::key_pool_create(bp->device, &pool.p))
@@ -792,9 +897,16 @@ extern "C" int kr_build_index(const char* input_tsv, const char* nwk_path, const
     Groups() { memset(static_cast<kr_key_groups*>(this), 0, sizeof(kr_key_groups)); }
     ~Groups() { kr_key_groups_free(this); }
   } grp;
+  // KR_BUILD_GPU_COLOURS: the groups' colour classes with them, from the device while the groups are there or else from the host
+  struct Classes : kr_colour_classes {
+    Classes() { memset(static_cast<kr_colour_classes*>(this), 0, sizeof(kr_colour_classes)); }
+    ~Classes() { kr_colour_classes_free(this); }
+  } cls;
+  const bool classed = (bp->gpu_minimizers & KR_BUILD_GPU_COLOURS) != 0;
+  double cls_seconds = 0;
   const bool pooled = pool.p != nullptr;
   if (pooled) {
-    int krc = kr::key_pool_finish(pool.p, nrows, nleaves, &grp);
+    int krc = kr::key_pool_finish(pool.p, nrows, nleaves, &grp, classed ? &cls : nullptr, &cls_seconds);
     kr::key_pool_free(pool.p), pool.p = nullptr;
     if (krc) return krc;
   } else {
@@ -812,19 +924,40 @@ extern "C" int kr_build_index(const char* input_tsv, const char* nwk_path, const
     if (int krc = kr::key_groups_host(all, nrows, nleaves, &grp)) return krc;
   }
   if (grp.nkeys == 0) return kr::fail(KR_ERR_FORMAT, "No k-mers to index!");
-  clk.done("key sort + group");
+  clk.done("key sort + group", cls_seconds);
   clk.keys(grp, pooled);
+  if (classed) {
+    if (cls.class_of) {
+      clk.span("colour classes", cls_seconds);
+    } else { // the device did not make them: the canonical classes, from the host's copy of the groups
+      if (int crc = kr::colour_classes_host(grp.goff, grp.ranks, grp.nkeys, &cls)) return crc;
+      uint64_t multi = 0;
+      for (uint64_t i = 0; i < grp.nkeys; ++i) multi += cls.class_of[i] != KR_NO_CLASS;
+      kr::colour_stats_note(grp.nkeys, multi, cls.nclasses, 0, 2, 0);
+      clk.done("colour classes");
+    }
+    clk.classes();
+  } else {
+    kr::colour_stats_note(0, 0, 0, 0, 0, 0);
+  }
 
   // colours of the groups IN KEY ORDER: Colours::created's order fixes the ids of the colours that are no tree nodes
   std::vector<uint32_t> leaf_se(nleaves, 0);
   for (uint32_t se = 1; se <= nn; ++se)
     if (bt.t.nodes[se].kind == 1) leaf_se[bt.leaf_rank[se]] = se;
-  std::vector<uint64_t> out_sh(grp.nkeys);
+  std::vector<uint64_t> out_sh(classed ? 0 : grp.nkeys);
   uint32_t root_se = nn;
-  for (uint64_t i = 0; i < grp.nkeys; ++i) {
+  for (uint64_t i = 0; i < out_sh.size(); ++i) {
     const uint64_t a = grp.goff[i], b = grp.goff[i + 1];
     // one leaf: colour_of would walk down to it and create nothing on the way
     out_sh[i] = b - a == 1 ? bt.sh[leaf_se[grp.ranks[a]]] : colour_of(bt, col, root_se, grp.ranks, (size_t)a, (size_t)b);
+  }
+  // ... or of the classes in the order of their first groups, which is the order in which the loop above meets each leaf set for
+  // the first time; at every later group of a set colour_of finds what the first walk made and creates nothing
+  std::vector<uint64_t> class_sh(cls.nclasses);
+  for (uint64_t cc = 0; cc < cls.nclasses; ++cc) {
+    const uint64_t i = cls.rep[cc];
+    class_sh[cc] = colour_of(bt, col, root_se, grp.ranks, (size_t)grp.goff[i], (size_t)grp.goff[i + 1]);
   }
 
   // Record::make_compact + CRecord(record) (src/record.cpp:131-176)
@@ -843,10 +976,21 @@ extern "C" int kr_build_index(const char* input_tsv, const char* nwk_path, const
   std::vector<double> rho(nn + 1, 0.0);
   for (auto& g : genomes)
     if (g.present) rho[leaf_by_name[g.name]] = g.n1 > 0 ? g.n2 / g.n1 : 0.0; // RSeq::compute_rho, src/rqseq.hpp:79
-  std::vector<uint32_t> cmer(out_sh.size() * 2);
+  std::vector<uint32_t> cmer(grp.nkeys * 2);
   for (size_t i = 0; i < out_sh.size(); ++i) {
     cmer[2 * i] = (uint32_t)grp.keys[i];
     cmer[2 * i + 1] = col.by_sh[out_sh[i]].se;
+  }
+  if (classed) { // one look-up per class; a group of one leaf has the leaf's id, as bt.sh[leaf_se[rank]] looks up above
+    std::vector<uint32_t> class_se(cls.nclasses);
+    for (uint64_t cc = 0; cc < cls.nclasses; ++cc) class_se[cc] = col.by_sh.at(class_sh[cc]).se;
+#if defined(_OPENMP)
+#pragma omp parallel for schedule(static) num_threads(nthreads)
+#endif
+    for (int64_t i = 0; i < (int64_t)grp.nkeys; ++i) {
+      cmer[2 * i] = (uint32_t)grp.keys[i];
+      cmer[2 * i + 1] = cls.class_of[i] == KR_NO_CLASS ? leaf_se[grp.ranks[grp.goff[i]]] : class_se[cls.class_of[i]];
+    }
   }
   clk.done("colours");
 
@@ -854,7 +998,7 @@ extern "C" int kr_build_index(const char* input_tsv, const char* nwk_path, const
   mkdir(out_dir, 0777);
   std::string sfx = "-m" + std::to_string(c.m) + "r" + std::to_string(c.r) + (c.frac ? "-frac" : "-no_frac");
   std::string dir = out_dir;
-  uint64_t nk = out_sh.size();
+  uint64_t nk = grp.nkeys;
   uint32_t nn1 = nn + 1;
   bool ok = write_file(dir + "/cmer" + sfx, &nk, 8, cmer.data(), cmer.size() * 4);
   ok = ok && write_file(dir + "/inc" + sfx, &nrows, 4, grp.inc, (size_t)nrows * 8);
@@ -988,8 +1132,9 @@ extern "C" int kr_build_sketch(const char* input_path, const char* out_path, con
   if (sdust_t && sdust_w < 4) return kr::fail(KR_ERR_ARG, "--sdust-w must be at least 4");
   PhaseClock clk;
   // gpu_minimizers, as in kr_build_index: the leaf stage of every batch of records on the device; KR_BUILD_GPU_KEYS: the keys stay
-  // there, and the sort, the unique and the row counts are the key stage with one leaf
-  const bool gpu_leaf = bp->gpu_minimizers != 0;
+  // there, and the sort, the unique and the row counts are the key stage with one leaf.  One leaf has no colours to fold:
+  // KR_BUILD_GPU_COLOURS is ignored.
+  const bool gpu_leaf = (bp->gpu_minimizers & ~KR_BUILD_GPU_COLOURS) != 0;
   PoolOwner pool;
   if (bp->gpu_minimizers & KR_BUILD_GPU_KEYS)
     if (int prc = kr::key_pool_create(bp->device, &pool.p)) return prc;

@@ -18,12 +18,31 @@
 // writes ranks[kept position], keys / goff[head position], and adds 1 to inc[row] at a head (an ordinary vector atomic); a 64-bit
 // inclusive scan over the rows turns inc into the cumulative counts.
 //
+// Colour classes (kr_colour_classes_device; KR_BUILD_GPU_COLOURS), on the groups while they are on the device: the distinct rank
+// sequences among the groups of two or more ranks, numbered in the order of their first groups.
+//   kr_classes_term_kernel     a 64-bit term per kept rank, fmix64(rank + 1); ONE exclusive scan (wrapping sums) over all of them
+//   kr_classes_flag_kernel     1 per group of >= 2 ranks; its exclusive scan is the group's place in the multi-rank list
+//   kr_classes_list_kernel     list entry = (fingerprint, group index), fingerprint = S[goff[i+1]] - S[goff[i]] + fmix64(length):
+//                              work in proportion to the ranks, whatever the group lengths
+//   the sort above             key passes only, the group index in the rank slot; stable, and the list is in group order, so
+//                              equal fingerprints stay in ascending group index
+//   kr_classes_head_kernel     an entry is a head unless fingerprint, length AND ranks equal its predecessor's.  The hash only
+//                              brings candidates together; the ranks decide.  A lane compares up to kLaneCompare ranks alone,
+//                              longer groups are compared by the whole wave, one after the other
+//   two scans                  of the head flags over the sorted list (the entry's run) and of the heads' flags over the groups
+//                              (class numbers in group order = order of first appearance)
+//   kr_classes_rep_kernel      a head writes rep[class] and its run's leading group; kr_classes_member_kernel gives every entry
+//                              the class of its run's leading group
+// With A, B, A under one fingerprint the second A opens a class of its own: more work for the builder (a repeated fold creates
+// nothing), the same files.
+//
 // No per-lane private arrays, no dynamic LDS: the kernels hold scalars and statically sized LDS only.
 #include "kr_common.h"
 #include "kr_devutil.h"
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -231,7 +250,121 @@ __global__ __launch_bounds__(256) void kr_keys_group_kernel(const uint64_t* keys
   }
 }
 
-#define HIP_TRY(expr)                                                                                   \
+// ---- colour classes ----
+constexpr uint32_t kLaneCompare = 64; // a group of up to this many ranks is compared by one lane, a longer one by the wave
+
+__device__ __forceinline__ uint64_t mix64(uint64_t v)
+{ // kr::fmix64
+  v ^= v >> 33;
+  v *= 0xff51afd7ed558ccdull;
+  v ^= v >> 33;
+  v *= 0xc4ceb9fe1a85ec53ull;
+  v ^= v >> 33;
+  return v;
+}
+
+// term[0 .. npairs]: the rank's term, and 0 behind the last, so that the exclusive scan has the sum of all at [npairs]
+__global__ __launch_bounds__(256) void kr_classes_term_kernel(const uint32_t* ranks, uint64_t npairs, uint64_t* term)
+{
+  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i <= npairs; i += (uint64_t)gridDim.x * 256u)
+    term[i] = i < npairs ? mix64((uint64_t)ranks[i] + 1u) : 0;
+}
+
+__global__ __launch_bounds__(256) void kr_classes_flag_kernel(const uint64_t* goff, uint64_t nkeys, uint64_t* flag)
+{
+  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < nkeys; i += (uint64_t)gridDim.x * 256u) flag[i] = goff[i + 1] - goff[i] >= 2u;
+}
+
+// sums: the scanned terms, pos: the scanned flags, m: their total (the list's length)
+__global__ __launch_bounds__(256) void kr_classes_list_kernel(const uint64_t* goff, uint64_t nkeys, const uint64_t* sums, const uint64_t* pos, uint64_t m,
+                                                              uint64_t mask, uint64_t* fp, uint32_t* gi)
+{
+  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < nkeys; i += (uint64_t)gridDim.x * 256u) {
+    const uint64_t a = goff[i], b = goff[i + 1];
+    if (b - a < 2u) continue;
+    const uint64_t p = pos[i];
+    if (p < m) fp[p] = (sums[b] - sums[a] + mix64(b - a)) & mask, gi[p] = (uint32_t)i;
+  }
+}
+
+// fp / gi: the sorted list.  head[j] = 1 where entry j opens a class, is_rep[group] = 1 for its group (zeroed by the caller);
+// *raised counts the heads whose fingerprint equals the predecessor's.  A wave takes 64 entries at a time.
+__global__ __launch_bounds__(256) void kr_classes_head_kernel(const uint64_t* fp, const uint32_t* gi, uint64_t m, const uint64_t* goff, const uint32_t* ranks,
+                                                              uint64_t* head, uint64_t* is_rep, unsigned long long* raised)
+{
+  const uint32_t lane = threadIdx.x & 63u;
+  for (uint64_t w0 = ((uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6)) * 64u; w0 < m; w0 += (uint64_t)gridDim.x * 256u) { // (wave-uniform)
+    const uint64_t j = w0 + lane;
+    uint32_t h = 0, same_fp = 0; // h: 0 a member, 1 a head, 2 left to the wave
+    uint64_t a = 0, b = 0, len = 0;
+    if (j < m) {
+      h = 1;
+      if (j > 0 && fp[j] == fp[j - 1]) {
+        same_fp = 1;
+        const uint32_t g = gi[j], pg = gi[j - 1];
+        a = goff[g], len = goff[g + 1] - a, b = goff[pg];
+        if (goff[pg + 1] - b == len) {
+          if (len <= kLaneCompare) {
+            h = 0;
+            for (uint64_t q = 0; q < len; ++q)
+              if (ranks[a + q] != ranks[b + q]) {
+                h = 1;
+                break;
+              }
+          } else {
+            h = 2;
+          }
+        }
+      }
+    }
+    for (uint64_t todo = __ballot(h == 2u); todo; todo &= todo - 1) { // the long candidates of these 64, each by all lanes
+      const int src = __ffsll((unsigned long long)todo) - 1;
+      const uint64_t sa = __shfl(a, src), sb = __shfl(b, src), sl = __shfl(len, src);
+      uint32_t differs = 0;
+      for (uint64_t q0 = 0; q0 < sl; q0 += 64u) {
+        const uint64_t q = q0 + lane;
+        const bool d = q < sl && ranks[sa + q] != ranks[sb + q];
+        if (__ballot(d)) {
+          differs = 1;
+          break;
+        }
+      }
+      if (lane == (uint32_t)src) h = differs;
+    }
+    if (j < m) {
+      head[j] = h;
+      if (h) is_rep[gi[j]] = 1;
+    }
+    const uint64_t r = __ballot(h && same_fp);
+    if (lane == 0 && r) atomicAdd(raised, (unsigned long long)__popcll(r));
+  }
+}
+
+// run: the head flags scanned inclusively (entry j belongs to run run[j] - 1), cls: the is_rep flags scanned exclusively (a leading
+// group's class).  lead has room for the runs, rep for the classes: there are as many of either as heads.
+__global__ __launch_bounds__(256) void kr_classes_rep_kernel(const uint64_t* run, const uint32_t* gi, uint64_t m, const uint64_t* cls, uint32_t* lead,
+                                                             uint64_t* rep)
+{
+  for (uint64_t j = (uint64_t)blockIdx.x * 256u + threadIdx.x; j < m; j += (uint64_t)gridDim.x * 256u) {
+    const uint64_t r = run[j];
+    if (j > 0 && run[j - 1] == r) continue;
+    const uint32_t g = gi[j];
+    if (r - 1 < m) lead[r - 1] = g;
+    if (cls[g] < m) rep[cls[g]] = g;
+  }
+}
+__global__ __launch_bounds__(256) void kr_classes_member_kernel(const uint64_t* run, const uint32_t* gi, uint64_t m, const uint64_t* cls, uint64_t nkeys,
+                                                                const uint32_t* lead, uint32_t* class_of)
+{
+  for (uint64_t j = (uint64_t)blockIdx.x * 256u + threadIdx.x; j < m; j += (uint64_t)gridDim.x * 256u) {
+    const uint64_t r = run[j];
+    if (r - 1 >= m) continue;
+    const uint32_t g = lead[r - 1];
+    if (g < nkeys) class_of[gi[j]] = (uint32_t)cls[g];
+  }
+}
+
+#define HIP_TRY(expr)                                                                                \
   do {                                                                                                  \
     hipError_t e__ = (expr);                                                                            \
     if (e__ != hipSuccess)                                                                              \
@@ -306,9 +439,116 @@ void scan_u64(uint64_t* v, uint64_t m, uint64_t* bsum, uint64_t* d_total)
   hipLaunchKernelGGL(kr_keys_bwrite_kernel<INCL>, dim3(grid_for(nblk)), dim3(256), 0, 0, v, m, bsum);
 }
 
+// ---- colour classes ----
+// KR_BUILD_COLOUR_HASH_BITS: the low bits of a fingerprint that are kept (tests of the content compare)
+uint32_t colour_hash_bits()
+{
+  const char* e = getenv("KR_BUILD_COLOUR_HASH_BITS");
+  return e ? (uint32_t)std::min<unsigned long long>(strtoull(e, nullptr, 10), 64) : 64u;
+}
+// the list can have no more entries than there are groups, or pairs of ranks
+uint64_t classes_list_max(uint64_t nkeys, uint64_t npairs) { return std::min(nkeys, npairs / 2); }
+uint64_t classes_block_sums(uint64_t nkeys, uint64_t npairs)
+{
+  const uint64_t ntiles = (classes_list_max(nkeys, npairs) + kTile - 1) / kTile;
+  return std::max(std::max(scan_blocks(npairs + 1), scan_blocks(nkeys)), scan_blocks(256 * ntiles));
+}
+// Device bytes of the class stage: terms, flags, class_of, the list twice over (12 B an entry), digit counts, block sums
+uint64_t classes_bytes(uint64_t nkeys, uint64_t npairs)
+{
+  const uint64_t mmax = classes_list_max(nkeys, npairs), ntiles = (mmax + kTile - 1) / kTile;
+  return 8 * (npairs + 1) + 8 * nkeys + 4 * nkeys + 24 * mmax + 8 * 256 * ntiles + 8 * classes_block_sums(nkeys, npairs) + 4096;
+}
+bool classes_fit(uint64_t nkeys, uint64_t npairs)
+{
+  const uint64_t need = classes_bytes(nkeys, npairs);
+  if (const char* e = getenv("KR_BUILD_KEYS_MAX_MB"))
+    if (need > (uint64_t)strtoull(e, nullptr, 10) << 20) return false;
+  size_t fr = 0, tot = 0;
+  if (hipMemGetInfo(&fr, &tot) != hipSuccess) return false;
+  return need + (64ull << 20) <= (uint64_t)fr;
+}
+
+// The classes of nkeys > 0 groups that are on the device in effect (d_goff[nkeys + 1], d_ranks[npairs]).  Every buffer is had before
+// the first kernel runs.  KR_ERR_NOMEM: the stage is not for the device (no room, or group indices that do not fit the sort's rank
+// slot); `out` holds nothing, and the caller takes the classes from the host.
+int classes_on_device(const uint64_t* d_goff, const uint32_t* d_ranks, uint64_t nkeys, uint64_t npairs, kr_colour_classes* out)
+{
+  memset(out, 0, sizeof(*out));
+  if (nkeys >= KR_NO_CLASS) return kr::fail(KR_ERR_NOMEM, "colour classes: 2^32 - 1 groups or more");
+  const uint64_t mmax = classes_list_max(nkeys, npairs);
+  if (mmax == 0) { // fewer than two ranks in all
+    int rc = kr::colour_classes_alloc(out, nkeys, 0);
+    if (rc == KR_OK) kr::colour_stats_note(nkeys, 0, 0, 0, 1, 0);
+    return rc;
+  }
+  const uint64_t nblk = classes_block_sums(nkeys, npairs);
+  DevBuf<uint64_t> b_term, b_flag, b_fa, b_fb, b_counts, b_bsum, b_small; // (freed at every return)
+  DevBuf<uint32_t> b_ga, b_gb, b_class;
+  if (!b_term.reserve(npairs + 1) || !b_flag.reserve(nkeys) || !b_fa.reserve(mmax) || !b_fb.reserve(mmax) || !b_ga.reserve(mmax) || !b_gb.reserve(mmax) ||
+      !b_counts.reserve(256 * ((mmax + kTile - 1) / kTile)) || !b_bsum.reserve(nblk) || !b_small.reserve(4) || !b_class.reserve(nkeys)) {
+    (void)hipGetLastError();
+    return kr::fail(KR_ERR_NOMEM, "colour classes: out of device memory");
+  }
+  uint64_t* d_total = b_small.get(); // [0]: list entries, then classes; [1]: the other scans' totals; [2]: raised by the content compare
+  HIP_TRY(hipMemset(d_total, 0, 32));
+  HIP_TRY(hipMemset(b_class.get(), 0xFF, nkeys * 4));
+  hipLaunchKernelGGL(kr_classes_term_kernel, dim3(grid_for((npairs + 256) / 256)), dim3(256), 0, 0, d_ranks, npairs, b_term.get());
+  scan_u64<false>(b_term.get(), npairs + 1, b_bsum.get(), d_total + 1);
+  hipLaunchKernelGGL(kr_classes_flag_kernel, dim3(grid_for((nkeys + 255) / 256)), dim3(256), 0, 0, d_goff, nkeys, b_flag.get());
+  scan_u64<false>(b_flag.get(), nkeys, b_bsum.get(), d_total);
+  HIP_TRY(hipGetLastError());
+  uint64_t m = 0;
+  HIP_TRY(hipMemcpy(&m, d_total, 8, hipMemcpyDeviceToHost)); // (synchronises: null stream)
+  if (m > mmax) return kr::fail(KR_ERR_STATE, "colour classes: inconsistent group offsets");
+  uint64_t res[3] = {0, 0, 0}; // classes, -, raised
+  uint32_t npasses = 0;
+  uint64_t* d_rep = b_term.get(); // the sums are done with once the list is made: room for npairs + 1 > m classes
+  if (m) {
+    const uint32_t bits = colour_hash_bits();
+    hipLaunchKernelGGL(kr_classes_list_kernel, dim3(grid_for((nkeys + 255) / 256)), dim3(256), 0, 0, d_goff, nkeys, (const uint64_t*)b_term.get(),
+                       (const uint64_t*)b_flag.get(), m, bits >= 64 ? ~0ull : (1ull << bits) - 1ull, b_fa.get(), b_ga.get());
+    const uint32_t ntiles = (uint32_t)((m + kTile - 1) / kTile);
+    const uint64_t ncounts = 256ull * ntiles;
+    uint64_t *fin = b_fa.get(), *fout = b_fb.get();
+    uint32_t *gin = b_ga.get(), *gout = b_gb.get();
+    for (uint32_t shift = 0; shift < bits; shift += 8, ++npasses) {
+      hipLaunchKernelGGL(kr_keys_hist_kernel, dim3(ntiles), dim3(256), 0, 0, fin, gin, m, ntiles, 0u, shift, b_counts.get());
+      scan_u64<false>(b_counts.get(), ncounts, b_bsum.get(), d_total + 1);
+      hipLaunchKernelGGL(kr_keys_scatter_kernel, dim3(ntiles), dim3(256), 0, 0, fin, gin, fout, gout, m, ntiles, 0u, shift, b_counts.get());
+      std::swap(fin, fout), std::swap(gin, gout);
+    }
+    // fin / gin: sorted.  The other pair of buffers takes the head flags (then the runs) and the runs' leading groups.
+    HIP_TRY(hipMemset(b_flag.get(), 0, nkeys * 8));
+    hipLaunchKernelGGL(kr_classes_head_kernel, dim3(grid_for((m + 255) / 256)), dim3(256), 0, 0, fin, gin, m, d_goff, d_ranks, fout, b_flag.get(),
+                       (unsigned long long*)(d_total + 2));
+    scan_u64<true>(fout, m, b_bsum.get(), d_total + 1);
+    scan_u64<false>(b_flag.get(), nkeys, b_bsum.get(), d_total);
+    hipLaunchKernelGGL(kr_classes_rep_kernel, dim3(grid_for((m + 255) / 256)), dim3(256), 0, 0, fout, gin, m, (const uint64_t*)b_flag.get(), gout, d_rep);
+    hipLaunchKernelGGL(kr_classes_member_kernel, dim3(grid_for((m + 255) / 256)), dim3(256), 0, 0, fout, gin, m, (const uint64_t*)b_flag.get(), nkeys,
+                       (const uint32_t*)gout, b_class.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(res, d_total, 24, hipMemcpyDeviceToHost));
+    if (res[0] == 0 || res[0] > m) return kr::fail(KR_ERR_STATE, "colour classes: inconsistent class counts");
+  }
+  int rc = kr::colour_classes_alloc(out, nkeys, res[0]);
+  if (rc) return rc;
+  hipError_t e = hipMemcpy(out->class_of, b_class.get(), nkeys * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && res[0]) e = hipMemcpy(out->rep, d_rep, res[0] * 8, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) {
+    kr_colour_classes_free(out);
+    return kr::fail(KR_ERR_NO_DEVICE, std::string("colour classes: ") + hipGetErrorString(e));
+  }
+  out->nclasses = res[0];
+  kr::colour_stats_note(nkeys, m, res[0], res[2], 1, npasses);
+  return KR_OK;
+}
+
 // The stage on n > 0 pairs that are on the device: ka / ra are sorted between themselves and two buffers made here.  Every buffer
 // is had before the first kernel runs: KR_ERR_NOMEM means that ka / ra are as they were (the callers finish on the host then).
-int run_stage(uint64_t* ka, uint32_t* ra, uint64_t n, uint32_t nrows, uint32_t nleaves, kr_key_groups* out, uint64_t* npasses)
+// cls: the groups' colour classes too, while the groups are here (left empty where the device has no room for that stage).
+int run_stage(uint64_t* ka, uint32_t* ra, uint64_t n, uint32_t nrows, uint32_t nleaves, kr_key_groups* out, uint64_t* npasses,
+              kr_colour_classes* cls = nullptr, double* cls_seconds = nullptr)
 {
   const uint64_t ntiles64 = (n + kTile - 1) / kTile;
   if (ntiles64 >= (1ull << 31)) return kr::fail(KR_ERR_ARG, "key stage: too many pairs for one sort");
@@ -367,6 +607,18 @@ int run_stage(uint64_t* ka, uint32_t* ra, uint64_t n, uint32_t nrows, uint32_t n
   if (e != hipSuccess) {
     kr_key_groups_free(out);
     return kr::fail(KR_ERR_NO_DEVICE, std::string("key stage: ") + hipGetErrorString(e));
+  }
+  if (cls) { // on the groups where the group kernel left them
+    const auto t0 = std::chrono::steady_clock::now();
+    rc = classes_fit(nkeys, npairs) ? classes_on_device(b_goff.get(), rout, nkeys, npairs, cls) : KR_ERR_NOMEM;
+    if (rc == KR_ERR_NOMEM) {
+      kr::clear_error(); // the caller has the groups and takes their classes from the host
+    } else if (rc) {
+      kr_key_groups_free(out);
+      return rc;
+    } else if (cls_seconds) {
+      *cls_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    }
   }
   return KR_OK;
 }
@@ -470,7 +722,7 @@ void kr::key_stage_note_path(uint64_t path) { note(0, 0, 0, 0, 0, path); }
 
 namespace {
 // the pool's segments expanded into a rank array, and the stage on both, in place
-int pool_on_device(kr::KeyPool* p, uint32_t nrows, uint32_t nleaves, kr_key_groups* out, uint64_t* npasses)
+int pool_on_device(kr::KeyPool* p, uint32_t nrows, uint32_t nleaves, kr_key_groups* out, uint64_t* npasses, kr_colour_classes* cls, double* cls_seconds)
 {
   const uint64_t n = p->used;
   const uint32_t nseg = (uint32_t)p->segs.size();
@@ -489,18 +741,20 @@ int pool_on_device(kr::KeyPool* p, uint32_t nrows, uint32_t nleaves, kr_key_grou
   hipLaunchKernelGGL(kr_keys_expand_kernel, dim3(grid_for((n + 255) / 256)), dim3(256), 0, 0, (const uint64_t*)b_off.get(), (const uint32_t*)b_rank.get(), nseg, n,
                      b_ra.get());
   HIP_TRY(hipGetLastError());
-  return run_stage(p->keys.get(), b_ra.get(), n, nrows, nleaves, out, npasses);
+  return run_stage(p->keys.get(), b_ra.get(), n, nrows, nleaves, out, npasses, cls, cls_seconds);
 }
 } // namespace
 
-int kr::key_pool_finish(KeyPool* p, uint32_t nrows, uint32_t nleaves, kr_key_groups* out)
+int kr::key_pool_finish(KeyPool* p, uint32_t nrows, uint32_t nleaves, kr_key_groups* out, kr_colour_classes* cls, double* cls_seconds)
 {
   if (!p || !out) return kr::fail(KR_ERR_ARG, "key pool: null");
+  if (cls) memset(cls, 0, sizeof(*cls));
+  if (cls_seconds) *cls_seconds = 0;
   if (int rc = set_device(p->device, "key pool")) return rc;
   const uint64_t n = p->on_host ? p->spill.size() : p->used;
   if (!p->on_host && n) {
     uint64_t npasses = 0;
-    int rc = stage_fits(n, nrows, n * 8) ? pool_on_device(p, nrows, nleaves, out, &npasses) : KR_ERR_NOMEM;
+    int rc = stage_fits(n, nrows, n * 8) ? pool_on_device(p, nrows, nleaves, out, &npasses, cls, cls_seconds) : KR_ERR_NOMEM;
     if (rc != KR_ERR_NOMEM) {
       if (rc == KR_OK) note(n, out->npairs, out->nkeys, npasses, p->growths, 1);
       p->keys.reset();
@@ -545,6 +799,43 @@ extern "C" int kr_key_groups_device(int device, const uint64_t* keys, const uint
   kr::clear_error(); // no room on the device: the twin, with the same result
   rc = kr_key_groups_cpu(keys, ranks, n, nrows, nleaves, out);
   if (rc == KR_OK) note(n, out->npairs, out->nkeys, 0, 0, 2);
+  return rc;
+}
+
+extern "C" int kr_colour_classes_device(int device, const uint64_t* goff, const uint32_t* ranks, uint64_t nkeys, kr_colour_classes* out)
+{
+  kr::clear_error();
+  if (!out || !goff) return kr::fail(KR_ERR_ARG, "kr_colour_classes_device: null argument");
+  memset(out, 0, sizeof(*out));
+  if (goff[0] != 0 || !std::is_sorted(goff, goff + nkeys + 1)) return kr::fail(KR_ERR_ARG, "kr_colour_classes_device: goff must ascend from 0");
+  const uint64_t npairs = goff[nkeys];
+  if (npairs && !ranks) return kr::fail(KR_ERR_ARG, "kr_colour_classes_device: null argument");
+  if (int rc = set_device(device, "kr_colour_classes_device")) return rc;
+  if (nkeys == 0) {
+    int rc = kr::colour_classes_alloc(out, 0, 0);
+    if (rc == KR_OK) kr::colour_stats_note(0, 0, 0, 0, 1, 0);
+    return rc;
+  }
+  int rc = KR_ERR_NOMEM;
+  if (classes_fit(nkeys, npairs)) {
+    DevBuf<uint64_t> b_goff; // (freed where the block is left)
+    DevBuf<uint32_t> b_ranks;
+    if (b_goff.reserve(nkeys + 1) && b_ranks.reserve(std::max<uint64_t>(npairs, 1))) {
+      HIP_TRY(hipMemcpy(b_goff.get(), goff, (nkeys + 1) * 8, hipMemcpyHostToDevice));
+      if (npairs) HIP_TRY(hipMemcpy(b_ranks.get(), ranks, npairs * 4, hipMemcpyHostToDevice));
+      rc = classes_on_device(b_goff.get(), b_ranks.get(), nkeys, npairs, out);
+    } else {
+      (void)hipGetLastError();
+    }
+  }
+  if (rc != KR_ERR_NOMEM) return rc;
+  kr::clear_error(); // not for the device: the canonical classes from the host
+  rc = kr::colour_classes_host(goff, ranks, nkeys, out);
+  if (rc == KR_OK) {
+    uint64_t multi = 0;
+    for (uint64_t i = 0; i < nkeys; ++i) multi += out->class_of[i] != KR_NO_CLASS;
+    kr::colour_stats_note(nkeys, multi, out->nclasses, 0, 2, 0);
+  }
   return rc;
 }
 

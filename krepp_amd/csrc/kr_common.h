@@ -186,8 +186,19 @@ struct KeyPool;
 int key_pool_create(int device, KeyPool** out);
 int key_pool_append_device(KeyPool* p, const uint64_t* d_keys, uint64_t n, uint32_t rank); // device-to-device
 int key_pool_append_host(KeyPool* p, const uint64_t* keys, uint64_t n, uint32_t rank);
-int key_pool_finish(KeyPool* p, uint32_t nrows, uint32_t nleaves, kr_key_groups* out);
+// cls (KR_BUILD_GPU_COLOURS): the groups' colour classes too, found while the groups are on the device, and *cls_seconds what that
+// took; cls->class_of stays null where the device did not make them (no room, or the key stage itself fell back): the caller
+// takes them from colour_classes_host then.
+int key_pool_finish(KeyPool* p, uint32_t nrows, uint32_t nleaves, kr_key_groups* out, kr_colour_classes* cls = nullptr,
+                    double* cls_seconds = nullptr);
 void key_pool_free(KeyPool* p);
+// ---- the colour classes (kr_colour_classes_cpu / _device; kr_build.cpp, kr_build_keys.hip) ----
+// kr_colour_classes_cpu behind the public checks: npairs = goff[nkeys]
+int colour_classes_host(const uint64_t* goff, const uint32_t* ranks, uint64_t nkeys, kr_colour_classes* out);
+// malloc'd arrays of a kr_colour_classes (class_of all KR_NO_CLASS; rep has room for `cap` classes, nclasses = 0), or KR_ERR_NOMEM
+int colour_classes_alloc(kr_colour_classes* out, uint64_t nkeys, uint64_t cap);
+// kr_debug_build_colours: {groups, groups of >= 2 ranks, classes, raised by the content compare, path, sort passes}
+void colour_stats_note(uint64_t groups, uint64_t multi, uint64_t classes, uint64_t raised, uint64_t path, uint64_t passes);
 void key_stage_note_path(uint64_t path); // kr_debug_build_keys: a build that could not use the device's key stage at all (3)
 // Where minimizers_device leaves a genome's keys and from which sums it counts on: pool == null: the keys come back in `out` as
 // ever; else they stay in the pool under leaf rank `rank` (the contig-end keys the host computes are appended by a small copy) and

@@ -56,7 +56,7 @@ static const std::map<std::string, std::string> kAlias = {
   {"-i", "--index-dir"}, {"-q", "--query"}, {"-o", "--output-path"}, {"-t", "--nwk-file"}, {"-k", "--kmer-len"},
   {"-w", "--win-len"}, {"-h", "--num-positions"}, {"-m", "--modulo-lsh"}, {"-r", "--residue-lsh"}, {"-l", "--lineage-file"},
 };
-static const char* kFlags[] = {"--multi", "--filter", "--summarize", "--frac", "--verbose", "--gpu-minimizers", "--gpu-keys", "--tabular", "--gpu-parse", "--gpu-seek"};
+static const char* kFlags[] = {"--multi", "--filter", "--summarize", "--frac", "--verbose", "--gpu-minimizers", "--gpu-keys", "--gpu-colours", "--tabular", "--gpu-parse", "--gpu-seek"};
 
 // options as in the reference's CLI (src/krepp.cpp:516-675); the texts are this build's own
 static void print_help(const std::string& sub)
@@ -109,7 +109,8 @@ static void print_help(const std::string& sub)
            "      --num-threads N        CPU threads of the builder [1]\n"
            "      --gpu-minimizers       window minimizers of the genomes on the GPU (identical output)\n"
            "      --gpu-keys             also sort and group all genomes' keys on the GPU (implies --gpu-minimizers; identical output)\n"
-           "      --device D             the GPU of --gpu-minimizers / --gpu-keys [0]\n",
+           "      --gpu-colours          also find the distinct leaf sets of the keys on the GPU and fold each into a colour once (implies --gpu-keys; identical output)\n"
+           "      --device D             the GPU of --gpu-minimizers / --gpu-keys / --gpu-colours [0]\n",
            build_opts);
   if (sub.empty() || sub == "sketch")
     printf("\nkrepp sketch -i GENOME.fa -o SKETCH: sketch of a single FASTA/FASTQ file (default k 26)\n%s"
@@ -1289,6 +1290,7 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
 }
 
 // --gpu-minimizers / --gpu-keys / --device of `index` and `sketch`: kr_build_params::gpu_minimizers is a bit set, the key stage implies the leaf stage
+// (--gpu-colours, which implies both, is `index`'s alone: run_index)
 static void gpu_build_options(const Args& a, kr_build_params& bp)
 {
   auto on = [&](const char* f) { return a.flag.count(f) && a.flag.at(f); };
@@ -1347,6 +1349,8 @@ static int run_index(const Args& a)
   bp.num_threads = a.has("--num-threads") ? (uint32_t)atoi(a.get("--num-threads").c_str()) : 1;
   bp.seed = a.has("--seed") ? (uint32_t)atoi(a.get("--seed").c_str()) : 0;
   gpu_build_options(a, bp);
+  if (a.flag.count("--gpu-colours") && a.flag.at("--gpu-colours")) // (`index` only: a sketch has one leaf and no colours to fold)
+    bp.gpu_minimizers |= KR_BUILD_GPU_MINIMIZERS | KR_BUILD_GPU_KEYS | KR_BUILD_GPU_COLOURS;
   sdust_options(a, bp);
   fprintf(stderr, "Building the index...\n");
   std::string nwk = a.get("--nwk-file");
