@@ -926,6 +926,46 @@ typedef struct kr_sdust_result {
 KR_API int kr_sdust_cpu(const uint8_t* bases, const uint64_t* offsets, uint32_t ncontigs, uint32_t T, uint32_t W, kr_sdust_result* out);
 KR_API void kr_sdust_free(kr_sdust_result*);
 
+/* ------------------------------------------------------------------------- */
+/* `krepp inspect` (Index::display_info src/index.cpp:172-186, FlatHT::display_info src/table.cpp:262-270,
+ * CRecord::display_info src/record.cpp:257-276): per library the k-mers that carry each colour, the times each colour is named as
+ * a child in se_to_pse[1 ..], and how many of the colours 1 .. nsubsets-1 share each of those two figures.
+ * _cpu is the canonical form and needs no device.  _device counts on the GPU (kr_index_stats.hip; big arrays from host memory, or
+ * from device memory with KR_VIEW_DEVICE) and returns identical arrays; when the device has no room, it finishes through _cpu
+ * (never an error).  A colour id >= nsubsets in cmer or in a child of se_to_pse[1 ..] is KR_ERR_FORMAT on both: the message names the
+ * library's suffix, the array, the first offending position and the value; `out` holds nothing then.
+ * Environment, read at each _device call: KR_STATS_CHUNK_KMERS (cmer entries per chunk), KR_STATS_MAX_MB (cap on the device memory
+ * the call may ask for; above it: _cpu), KR_STATS_LDS_CAP (colour ids below it are counted in LDS; 0: global atomics only). */
+typedef struct kr_lib_stats {
+  uint64_t nkmers;
+  uint32_t nsubsets, r, frac;
+  uint64_t *mer_value, *mer_freq; /* [n_mer] ascending mer_value; sum(mer_freq) == nsubsets - 1 */
+  uint64_t n_mer;
+  uint64_t *deg_value, *deg_freq; /* [n_deg] ascending deg_value; sum(deg_freq) == nsubsets - 1 */
+  uint64_t n_deg;
+  uint64_t* se_count;  /* [nsubsets] k-mers per colour, only with KR_STATS_KEEP_COUNTS, else NULL */
+  uint64_t* se_outdeg; /* [nsubsets] likewise */
+} kr_lib_stats;
+typedef struct kr_index_stats {
+  uint32_t nlibs;
+  kr_lib_stats* libs;
+} kr_index_stats;
+#define KR_STATS_KEEP_COUNTS 4u /* beside KR_VIEW_HOST / KR_VIEW_DEVICE in `flags` */
+KR_API int kr_index_stats_cpu(const kr_index_view*, uint32_t flags, kr_index_stats* out);
+KR_API int kr_index_stats_device(const kr_index_view*, int device, uint32_t flags, kr_index_stats* out);
+KR_API void kr_index_stats_free(kr_index_stats*);
+/* The metadata text of library `lib` as `inspect` prints it: the content of metadata<suffix>.txt, or the reference's thirteen
+ * `name: value` lines (src/index.cpp:128-141) where the file is missing.  "" for a bad argument. */
+KR_API const char* kr_host_index_lib_info(const kr_host_index*, uint32_t lib);
+/* The text of `krepp inspect`: blocks by ascending residue key, rows by ascending value.  kr_free(*text). */
+KR_API int kr_format_inspect(const kr_host_index*, const kr_index_stats*, char** text, uint64_t* len);
+/* Tests: the calling process's last kr_index_stats_device: {path (1 device, 2 fell back to the host for memory), cmer chunks,
+ * increments served from LDS, increments sent as global atomics, LDS counter capacity in colours, sort passes of the MER_COUNT
+ * histogram, sort passes of the OUTDEGREE_COUNT histogram (both of the last library), cmer entries of one workgroup's run}.
+ * kr_debug_index_stats_ms: {H2D copies, count kernels, out-degrees and histograms, whole call} in milliseconds (events; the last wall). */
+KR_API void kr_debug_index_stats(uint64_t out[8]);
+KR_API void kr_debug_index_stats_ms(float out[4]);
+
 KR_API const char* kr_last_error(void);
 KR_API const char* kr_version(void);
 

@@ -103,6 +103,19 @@ class KrKeyGroups(C.Structure):
                 ("nrows", C.c_uint32)]
 
 
+class KrLibStats(C.Structure):
+    _fields_ = [("nkmers", C.c_uint64), ("nsubsets", C.c_uint32), ("r", C.c_uint32), ("frac", C.c_uint32),
+                ("mer_value", u64p), ("mer_freq", u64p), ("n_mer", C.c_uint64), ("deg_value", u64p), ("deg_freq", u64p), ("n_deg", C.c_uint64),
+                ("se_count", u64p), ("se_outdeg", u64p)]
+
+
+class KrIndexStats(C.Structure):
+    _fields_ = [("nlibs", C.c_uint32), ("libs", C.POINTER(KrLibStats))]
+
+
+KR_STATS_KEEP_COUNTS = 4
+
+
 class KrColourClasses(C.Structure):
     _fields_ = [("class_of", u32p), ("rep", u64p), ("nkeys", C.c_uint64), ("nclasses", C.c_uint64)]
 
@@ -140,6 +153,8 @@ EXPORTS = [
     "kr_sdust_cpu", "kr_sdust_free",
     "kr_key_groups_cpu", "kr_key_groups_device", "kr_key_groups_free", "kr_debug_build_keys",
     "kr_colour_classes_cpu", "kr_colour_classes_device", "kr_colour_classes_free", "kr_debug_build_colours",
+    "kr_index_stats_cpu", "kr_index_stats_device", "kr_index_stats_free", "kr_host_index_lib_info", "kr_format_inspect", "kr_debug_index_stats",
+    "kr_debug_index_stats_ms",
     "kr_stream_seek_enable", "kr_batch_collect_seek", "kr_debug_seek_layout", "kr_debug_seek_ms",
     "kr_stream_bgzf_enable", "kr_batch_submit_bgzf", "kr_debug_bgzf_inflate", "kr_debug_bgzf_inflate_host", "kr_debug_bgzf_ms",
     "kr_bgzf_member_size", "kr_bgzf_walk", "kr_bgzf_chunk_cut", "kr_fastx_open_at_bgzf",
@@ -1193,6 +1208,70 @@ def group_colour_classes(goff, ranks, device=None):
     out = _np(res.class_of, res.nkeys, np.uint32), _np(res.rep, res.nclasses, np.uint64)
     lib.kr_colour_classes_free(C.byref(res))
     return out
+
+
+def index_stats(view_or_hx, device=None, keep_counts=False, view_flags=KR_VIEW_HOST):
+    """The statistics of `krepp inspect`: a list with one dict per library (nkmers, nsubsets, r, frac, mer_value, mer_freq, deg_value,
+    deg_freq, and se_count / se_outdeg with keep_counts, else None) from kr_index_stats_cpu (device=None) or _device.
+    view_or_hx: a HostIndex or a KrIndexView; view_flags=KR_VIEW_DEVICE: the view's cmer / pse are device pointers."""
+    lib = load()
+    view = view_or_hx.view if isinstance(view_or_hx, HostIndex) else view_or_hx
+    lib.kr_index_stats_cpu.argtypes = [C.POINTER(KrIndexView), C.c_uint32, C.POINTER(KrIndexStats)]
+    lib.kr_index_stats_device.argtypes = [C.POINTER(KrIndexView), C.c_int, C.c_uint32, C.POINTER(KrIndexStats)]
+    lib.kr_index_stats_free.argtypes = [C.POINTER(KrIndexStats)]
+    lib.kr_index_stats_free.restype = None
+    flags = int(view_flags) | (KR_STATS_KEEP_COUNTS if keep_counts else 0)
+    res = KrIndexStats()
+    if device is None:
+        check(lib.kr_index_stats_cpu(C.byref(view), flags, C.byref(res)))
+    else:
+        check(lib.kr_index_stats_device(C.byref(view), int(device), flags, C.byref(res)))
+    out = []
+    for i in range(res.nlibs):
+        L = res.libs[i]
+        out.append({"nkmers": int(L.nkmers), "nsubsets": int(L.nsubsets), "r": int(L.r), "frac": int(L.frac),
+                    "mer_value": _np(L.mer_value, L.n_mer, np.uint64), "mer_freq": _np(L.mer_freq, L.n_mer, np.uint64),
+                    "deg_value": _np(L.deg_value, L.n_deg, np.uint64), "deg_freq": _np(L.deg_freq, L.n_deg, np.uint64),
+                    "se_count": _np(L.se_count, L.nsubsets, np.uint64) if L.se_count else None,
+                    "se_outdeg": _np(L.se_outdeg, L.nsubsets, np.uint64) if L.se_outdeg else None})
+    lib.kr_index_stats_free(C.byref(res))
+    return out
+
+
+def format_inspect(hx, stats):
+    """kr_format_inspect: the text of `krepp inspect` for the HostIndex `hx` and what index_stats returned for it (bytes)."""
+    lib = load()
+    lib.kr_format_inspect.argtypes = [C.c_void_p, C.POINTER(KrIndexStats), C.POINTER(C.c_void_p), u64p]
+    arr = (KrLibStats * max(1, len(stats)))()
+    keep = []
+    for i, d in enumerate(stats):
+        cols = [np.ascontiguousarray(d[k_], dtype=np.uint64) for k_ in ("mer_value", "mer_freq", "deg_value", "deg_freq")]
+        keep.append(cols)
+        arr[i].nkmers, arr[i].nsubsets, arr[i].r, arr[i].frac = d["nkmers"], d["nsubsets"], d["r"], d["frac"]
+        arr[i].mer_value, arr[i].mer_freq = C.cast(cols[0].ctypes.data, u64p), C.cast(cols[1].ctypes.data, u64p)
+        arr[i].deg_value, arr[i].deg_freq = C.cast(cols[2].ctypes.data, u64p), C.cast(cols[3].ctypes.data, u64p)
+        arr[i].n_mer, arr[i].n_deg = len(cols[0]), len(cols[2])
+    st = KrIndexStats(nlibs=len(stats), libs=arr)
+    text, n = C.c_void_p(), C.c_uint64(0)
+    check(lib.kr_format_inspect(hx.h, C.byref(st), C.byref(text), C.byref(n)))
+    out = C.string_at(text, n.value)
+    lib.kr_free(text)
+    return out
+
+
+def index_stats_debug():
+    """kr_debug_index_stats / _ms: the process's last kr_index_stats_device."""
+    v, ms = (C.c_uint64 * 8)(), (C.c_float * 4)()
+    lib = load()
+    lib.kr_debug_index_stats.argtypes = [C.POINTER(C.c_uint64 * 8)]
+    lib.kr_debug_index_stats.restype = None
+    lib.kr_debug_index_stats_ms.argtypes = [C.POINTER(C.c_float * 4)]
+    lib.kr_debug_index_stats_ms.restype = None
+    lib.kr_debug_index_stats(C.byref(v))
+    lib.kr_debug_index_stats_ms(C.byref(ms))
+    return {"path": int(v[0]), "chunks": int(v[1]), "lds": int(v[2]), "global": int(v[3]), "cap": int(v[4]), "passes_mer": int(v[5]),
+            "passes_deg": int(v[6]), "run": int(v[7]), "copy_ms": float(ms[0]), "kernel_ms": float(ms[1]), "rest_ms": float(ms[2]),
+            "total_ms": float(ms[3])}
 
 
 def build_colours_stats():

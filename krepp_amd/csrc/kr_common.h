@@ -200,6 +200,13 @@ int colour_classes_alloc(kr_colour_classes* out, uint64_t nkeys, uint64_t cap);
 // kr_debug_build_colours: {groups, groups of >= 2 ranks, classes, raised by the content compare, path, sort passes}
 void colour_stats_note(uint64_t groups, uint64_t multi, uint64_t classes, uint64_t raised, uint64_t path, uint64_t passes);
 void key_stage_note_path(uint64_t path); // kr_debug_build_keys: a build that could not use the device's key stage at all (3)
+// ---- index statistics (kr_index_stats_cpu: kr_inspect.cpp; kr_index_stats_device: kr_index_stats.hip) ----
+// KR_ERR_FORMAT with the one message both paths give for a colour id >= nsubsets: `array` is "cmer" or "se_to_pse", `pos` its entry
+int stats_bad_id(const kr_index_view* v, uint32_t lib, const char* array, uint64_t pos, uint32_t value);
+// calloc'd kr_lib_stats of a view's libraries with nkmers / nsubsets / r / frac set, or KR_ERR_NOMEM
+int index_stats_alloc(const kr_index_view* v, kr_index_stats* out);
+// malloc'd copies of n values and their frequencies into a library's mer (which = 0) or deg (1) lists; KR_ERR_NOMEM
+int lib_stats_set_list(kr_lib_stats* L, int which, const uint64_t* value, const uint64_t* freq, uint64_t n);
 // Where minimizers_device leaves a genome's keys and from which sums it counts on: pool == null: the keys come back in `out` as
 // ever; else they stay in the pool under leaf rank `rank` (the contig-end keys the host computes are appended by a small copy) and
 // `out` has none.  n1 / n2: the sums to add the contigs' estimates to, in order (a sketch's batches of records).

@@ -437,6 +437,7 @@ struct kr_host_lib {
   std::vector<uint32_t> pse;  // interleaved
   std::vector<double> rho;
   uint32_t nnodes = 0, nsubsets = 0, r = 0, frac = 0, w = 0, nrows_meta = 0;
+  std::string info; // what `inspect` prints for the library: metadata<suffix>.txt, or the reference's fallback lines
 };
 
 struct kr_host_index {
@@ -463,6 +464,24 @@ bool slurp(const std::string& path, std::string& out)
   size_t got = n > 0 ? fread(&out[0], 1, (size_t)n, f) : 0;
   fclose(f);
   return got == (size_t)std::max(0L, n);
+}
+
+// The metadata text of a library without a metadata<suffix>.txt (src/index.cpp:128-141): thirteen lines, `?` for what the binary
+// files do not say; nrows is the whole table's 4^h, not the library's share
+std::string fallback_info(uint32_t k, uint32_t w, uint32_t h, uint32_t m, bool frac, const std::vector<uint8_t>& ppos,
+                          const std::vector<uint8_t>& npos, uint64_t nkmers)
+{
+  auto list = [](const std::vector<uint8_t>& v) {
+    std::string o = "[";
+    for (size_t i = 0; i < v.size(); ++i) o += (i ? ", " : "") + std::to_string((unsigned)v[i]);
+    return o + "]";
+  };
+  std::string s = "krepp version: ?\ndate: ?\nseed: ?\n";
+  s += "k: " + std::to_string(k) + "\nw: " + std::to_string(w) + "\nh: " + std::to_string(h) + "\nm: " + std::to_string(m) + "\n";
+  s += frac ? "frac: true\n" : "frac: false\n";
+  s += "ppos_v: " + list(ppos) + "\nnpos_v: " + list(npos) + "\n";
+  s += "nrows: " + std::to_string((uint32_t)(h < 32 ? 1ull << (2 * h) : 0)) + "\ntotal_num_kmers: " + std::to_string(nkmers) + "\n";
+  return s + "sdust-t: ?\nsdust-w: ?\n";
 }
 
 template <typename T>
@@ -611,6 +630,8 @@ int kr_host_index_load(const char* index_dir, kr_host_index** out)
     }
     if (lib.nnodes != hx->tree.nnodes() + 1)
       return kr::fail(KR_ERR_FORMAT, "crecord" + sfx + " does not match the tree (nnodes)");
+    if (!slurp(dir + "/metadata" + sfx + ".txt", lib.info)) // src/index.cpp:121-142
+      lib.info = fallback_info(k8, w8, h8, m32, frac8 != 0, ppos, npos, nk);
     // residues served by this library (src/index.cpp:144-157)
     if (lib.frac) {
       for (uint32_t q = 0; q <= lib.r; ++q) residues.insert(q);
@@ -681,6 +702,7 @@ int kr_host_sketch_load(const char* sketch_path, kr_host_index** out)
   rho *= frac ? ((double)r + 1.0) / (double)m : 1.0 / (double)m;
   kr_host_lib lib;
   lib.r = r, lib.frac = frac, lib.w = w, lib.nrows_meta = nrows2;
+  lib.info = fallback_info(k, w, h, m, frac != 0, hx->ppos, hx->npos, nkmers);
   lib.inc.resize(nrows);
   memcpy(lib.inc.data(), buf.data() + inc_off, (size_t)nrows * 8);
   if (nrows && lib.inc.back() != nkmers) return kr::fail(KR_ERR_FORMAT, bad);
@@ -743,6 +765,11 @@ uint32_t kr_host_index_node_parent(const kr_host_index* h, uint32_t se)
 double kr_host_index_node_blen(const kr_host_index* h, uint32_t se)
 {
   return (h && se && se < h->tree.nodes.size()) ? h->tree.nodes[se].blen : NAN;
+}
+
+const char* kr_host_index_lib_info(const kr_host_index* h, uint32_t lib)
+{
+  return (h && lib < h->libs.size()) ? h->libs[lib].info.c_str() : "";
 }
 
 void kr_params_default(kr_params* p)

@@ -1,8 +1,6 @@
-// krepp_main.cpp — the `krepp` command line for the sub-commands this repository
-// implements: `dist` (MI355X) and `index` (CPU).  Option names, defaults, header lines
-// and error conventions follow the reference CLI (src/krepp.cpp:508-712,
-// src/krepp.hpp:206-221); everything else of the reference CLI (place, seek, sketch,
-// inspect) is out of scope here and reported as such.
+// krepp_main.cpp — the `krepp` command line: every sub-command of the reference CLI (dist, place, seek, index, sketch,
+// inspect).  Option names, defaults, header lines and error conventions follow the reference CLI (src/krepp.cpp:508-712,
+// src/krepp.hpp:206-221).
 //
 // Query pipeline (run_query): reader thread (gz/FASTX, src/rqseq.cpp:180-197) -> workers, each
 // GPU with its own replica of the index and each worker with its own kr_stream -> writer emitting
@@ -56,7 +54,7 @@ static const std::map<std::string, std::string> kAlias = {
   {"-i", "--index-dir"}, {"-q", "--query"}, {"-o", "--output-path"}, {"-t", "--nwk-file"}, {"-k", "--kmer-len"},
   {"-w", "--win-len"}, {"-h", "--num-positions"}, {"-m", "--modulo-lsh"}, {"-r", "--residue-lsh"}, {"-l", "--lineage-file"},
 };
-static const char* kFlags[] = {"--multi", "--filter", "--summarize", "--frac", "--verbose", "--gpu-minimizers", "--gpu-keys", "--gpu-colours", "--tabular", "--gpu-parse", "--gpu-seek"};
+static const char* kFlags[] = {"--multi", "--filter", "--summarize", "--frac", "--verbose", "--gpu-minimizers", "--gpu-keys", "--gpu-colours", "--tabular", "--gpu-parse", "--gpu-seek", "--gpu-stats"};
 
 // options as in the reference's CLI (src/krepp.cpp:516-675); the texts are this build's own
 static void print_help(const std::string& sub)
@@ -82,7 +80,7 @@ static void print_help(const std::string& sub)
     "      --seed N               seed of the random LSH positions\n"
     "      --sdust-t N            sdust score threshold; with --sdust-w > 0 low-complexity intervals stay out of the windows [0: off]\n"
     "      --sdust-w N            sdust window length, >= 4 [0: off]\n";
-  printf("krepp (MI355X build, mirrors krepp v0.8.3): dist | place | seek | index | sketch\n");
+  printf("krepp (MI355X build, mirrors krepp v0.8.3): dist | place | seek | index | sketch | inspect\n");
   if (sub.empty() || sub == "dist")
     printf("\nkrepp dist -i DIR -q READS: distances of every read to the references it matches\n%s%s"
            "      --filter / --no-filter keep only references not significantly worse than the closest [no-filter]\n"
@@ -118,6 +116,11 @@ static void print_help(const std::string& sub)
            "      --gpu-keys             also sort the keys and count the rows on the GPU (implies --gpu-minimizers; identical output)\n"
            "      --device D             the GPU of --gpu-minimizers / --gpu-keys [0]\n",
            build_opts);
+  if (sub.empty() || sub == "inspect")
+    printf("\nkrepp inspect -i DIR: the backbone tree, every partial library's metadata and its colour statistics, on stdout\n"
+           "  -i, --index-dir DIR        index directory\n"
+           "      --gpu-stats            count the k-mers per colour, the out-degrees and their histograms on the GPU (identical output)\n"
+           "      --device D             the GPU of --gpu-stats [0]\n");
   printf("\nEnvironment knobs and what differs from the reference: INTEGRATION.md\n");
 }
 
@@ -1385,6 +1388,44 @@ static int run_sketch(const Args& a)
   return 0;
 }
 
+// `inspect` (src/krepp.cpp:696-701, Index::display_info): the host index, its statistics -- on the host, or with --gpu-stats on the
+// device -- and the text, to stdout.  Without the flag no HIP call is made.
+static int run_inspect(const Args& a)
+{
+  const std::string dir = a.get("--index-dir");
+  if (dir.empty()) error_exit("inspect requires -i/--index-dir");
+  const bool gpu = a.flag.count("--gpu-stats") && a.flag.at("--gpu-stats");
+  const bool timing = getenv("KR_CLI_TIMING") != nullptr;
+  auto t0 = Clock::now();
+  kr_host_index* hx = nullptr;
+  if (kr_host_index_load(dir.c_str(), &hx)) error_exit(kr_last_error());
+  kr_index_view view;
+  kr_host_index_view(hx, &view);
+  const uint64_t t_load = since(t0);
+  t0 = Clock::now();
+  kr_index_stats st;
+  const int rc = gpu ? kr_index_stats_device(&view, a.has("--device") ? atoi(a.get("--device").c_str()) : 0, KR_VIEW_HOST, &st)
+                     : kr_index_stats_cpu(&view, KR_VIEW_HOST, &st);
+  if (rc) error_exit(kr_last_error());
+  const uint64_t t_stats = since(t0);
+  t0 = Clock::now();
+  char* text = nullptr;
+  uint64_t len = 0;
+  if (kr_format_inspect(hx, &st, &text, &len)) error_exit(kr_last_error());
+  if (fwrite(text, 1, len, stdout) != len || fflush(stdout) != 0) error_exit("Failed to write the report");
+  const uint64_t t_text = since(t0);
+  if (timing) {
+    uint64_t dbg[8] = {0};
+    if (gpu) kr_debug_index_stats(dbg);
+    fprintf(stderr, "[timing] inspect: load %.3f s, statistics %.3f s (%s), text %.3f s\n", t_load * 1e-9, t_stats * 1e-9,
+            !gpu ? "host" : dbg[0] == 1 ? "device" : "device asked, host for memory", t_text * 1e-9);
+  }
+  kr_free(text);
+  kr_index_stats_free(&st);
+  kr_host_index_free(hx);
+  return 0;
+}
+
 int main(int argc, char** argv)
 {
   // more hardware queues than the runtime's default of 4: with two workers per GPU (each a kr_stream with its own HIP
@@ -1415,9 +1456,9 @@ int main(int argc, char** argv)
   else if (a.sub == "sketch")
     rc = run_sketch(a);
   else if (a.sub == "inspect")
-    error_exit("sub-command `inspect` is outside the scope of this build (dist/place/seek/index/sketch)");
+    rc = run_inspect(a);
   else
-    error_exit("A subcommand is required (dist | place | seek | index | sketch)");
+    error_exit("A subcommand is required (dist | place | seek | index | sketch | inspect)");
   now = std::time(nullptr);
   fprintf(stderr, "%s", std::ctime(&now));
   return rc;
