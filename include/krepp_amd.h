@@ -667,6 +667,40 @@ KR_API int kr_bgzf_walk(const uint8_t* buf, uint64_t n, uint64_t max_inflated, u
 KR_API uint64_t kr_bgzf_chunk_cut(const uint8_t* buf, uint64_t comp_bytes, uint32_t skip, uint32_t fasta, uint64_t* member_off, uint32_t* uoff);
 KR_API int kr_fastx_open_at_bgzf(const char* path, uint64_t member_off, uint32_t uoff, kr_fastx** out);
 
+/* ---- report text written block-gzipped (csrc/kr_deflate.h, csrc/kr_dev_deflate.inc; docs/design/15_bgzf_out.md) ----
+ * The opposite direction: bytes deflated into BGZF members of at most 65,280 input bytes each (where bgzip cuts), one DEFLATE block
+ * a member -- greedy matches from a hash table, fixed Huffman codes, or one stored block when that is not smaller.  One encoder
+ * (csrc/kr_deflate.h) runs serially on the host and as one wave per member on the device, and both give THE SAME BYTES for the same
+ * input.  Members concatenate: the files of several calls, written one behind the other and ended with kr_bgzf_eof's member, are
+ * one BGZF file that zcat, bgzip -d, tabix and kr_batch_submit_bgzf read.
+ * No device:
+ *   kr_bgzf_deflate_bound   the most bytes kr_bgzf_deflate_host or the device produce for n bytes: n + 31 a member
+ *   kr_bgzf_deflate_host    text[0 .. n) as members into out[0 .. cap); n == 0 gives no member.  The members are spread over the host
+ *                           thread pool; the bytes do not depend on the thread count.  KR_ERR_CAPACITY when they need more than cap
+ *   kr_bgzf_eof             the standard 28-byte empty member that ends a BGZF file
+ *   kr_debug_bgzf_deflate_stats   (tests) what the host form did with text[0 .. n): stats[6] = members, stored members, literals,
+ *                           matches, longest match, farthest distance (the last four over the coded members)
+ * Device:
+ *   kr_stream_bgzf_out_enable   once per stream, after kr_stream_text_enable or kr_stream_seek_enable made text buffers (before them,
+ *                           or twice: KR_ERR_STATE): device buffers for the members of max_text_bytes of text
+ *   kr_batch_collect_text_bgzf  kr_batch_collect_text with the text deflated on the device: the same statuses for the same reasons
+ *                           (and KR_ERR_STATE before kr_stream_bgzf_out_enable).  *comp points into the stream's page-locked
+ *                           buffer and stays valid until the next submit on this stream; *len: its bytes, *text_len: the bytes
+ *                           it inflates to.  No end member is written.  The text stays on the device as it is:
+ *                           kr_batch_collect_text on the same batch still returns the plain bytes.  Serves `dist` and KR_SEEK text
+ *   kr_debug_bgzf_deflate   (tests) any host bytes through the kernels: out[0 .. cap) receives the members (KR_ERR_CAPACITY: more
+ *                           than cap).  Not while a batch is in flight on the stream's first lane (it is waited for)
+ *   kr_debug_bgzf_deflate_ms    (measurements) device time (ms) of the deflate, scan and copy kernels of the stream's last deflate;
+ *                           -1 before the first */
+KR_API uint64_t kr_bgzf_deflate_bound(uint64_t n);
+KR_API int kr_bgzf_deflate_host(const uint8_t* text, uint64_t n, uint8_t* out, uint64_t cap, uint64_t* len);
+KR_API void kr_bgzf_eof(uint8_t* out28);
+KR_API int kr_debug_bgzf_deflate_stats(const uint8_t* text, uint64_t n, uint64_t* stats);
+KR_API int kr_stream_bgzf_out_enable(kr_stream*);
+KR_API int kr_batch_collect_text_bgzf(kr_stream*, const uint8_t** comp, uint64_t* len, uint64_t* text_len);
+KR_API int kr_debug_bgzf_deflate(kr_stream*, const uint8_t* bytes, uint64_t n, uint8_t* out, uint64_t cap, uint64_t* len);
+KR_API int kr_debug_bgzf_deflate_ms(kr_stream*, float* ms);
+
 /* ---- `seek` on kernels of its own (csrc/kr_dev_seek.inc; docs/design/13_seek.md; INTEGRATION.md "A seek batch") ----
  * SBatch::seek_sequences (src/seek.cpp:22-126) on a SKETCH index (kr_host_sketch_load): per k-mer and strand the minimum Hamming
  * distance over one bucket, a histogram of hdist_th + 1 bins per strand, one minimisation per strand, the smaller d -- or NaN when

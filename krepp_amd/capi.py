@@ -158,6 +158,8 @@ EXPORTS = [
     "kr_stream_seek_enable", "kr_batch_collect_seek", "kr_debug_seek_layout", "kr_debug_seek_ms",
     "kr_stream_bgzf_enable", "kr_batch_submit_bgzf", "kr_debug_bgzf_inflate", "kr_debug_bgzf_inflate_host", "kr_debug_bgzf_ms",
     "kr_bgzf_member_size", "kr_bgzf_walk", "kr_bgzf_chunk_cut", "kr_fastx_open_at_bgzf",
+    "kr_bgzf_deflate_bound", "kr_bgzf_deflate_host", "kr_bgzf_eof", "kr_debug_bgzf_deflate_stats",
+    "kr_stream_bgzf_out_enable", "kr_batch_collect_text_bgzf", "kr_debug_bgzf_deflate", "kr_debug_bgzf_deflate_ms",
 ]
 
 # kr_debug_acc_paths: the accumulate kernel's path witnesses, in the order of CounterSlot (kr_dev_common.inc)
@@ -289,6 +291,16 @@ def load():
     lib.kr_bgzf_chunk_cut.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
     lib.kr_bgzf_chunk_cut.restype = C.c_uint64
     lib.kr_fastx_open_at_bgzf.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, C.POINTER(vp)]
+    lib.kr_bgzf_deflate_bound.argtypes = [C.c_uint64]
+    lib.kr_bgzf_deflate_bound.restype = C.c_uint64
+    lib.kr_bgzf_deflate_host.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+    lib.kr_bgzf_eof.argtypes = [vp]
+    lib.kr_bgzf_eof.restype = None
+    lib.kr_debug_bgzf_deflate_stats.argtypes = [vp, C.c_uint64, u64p]
+    lib.kr_stream_bgzf_out_enable.argtypes = [vp]
+    lib.kr_batch_collect_text_bgzf.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.kr_debug_bgzf_deflate.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+    lib.kr_debug_bgzf_deflate_ms.argtypes = [vp, C.POINTER(C.c_float)]
     lib.kr_debug_tile_layout.argtypes = [vp, u32p, u32p, vp, vp, vp, vp, vp]
     lib.kr_stream_seek_enable.argtypes = [vp, C.c_uint64, C.c_uint64]
     lib.kr_batch_collect_seek.argtypes = [vp, C.POINTER(KrSeekView)]
@@ -829,6 +841,33 @@ class Stream:
         check(self.lib.kr_batch_collect_text(self.h, C.byref(txt), C.byref(ln)))
         return C.string_at(txt, ln.value) if ln.value else b""
 
+    def bgzf_out_enable(self):
+        """kr_stream_bgzf_out_enable (after text_enable or seek_enable with text buffers): this stream can hand its report text out as
+        BGZF members deflated on the device (csrc/kr_dev_deflate.inc)"""
+        check(self.lib.kr_stream_bgzf_out_enable(self.h))
+
+    def collect_text_bgzf(self):
+        """kr_batch_collect_text_bgzf: (the batch's report text as BGZF members, the bytes they inflate to)"""
+        comp = C.c_void_p()
+        ln, tl = C.c_uint64(), C.c_uint64()
+        check(self.lib.kr_batch_collect_text_bgzf(self.h, C.byref(comp), C.byref(ln), C.byref(tl)))
+        return (C.string_at(comp, ln.value) if ln.value else b""), int(tl.value)
+
+    def bgzf_deflate(self, data, cap=None):
+        """(tests) kr_debug_bgzf_deflate: any bytes through the deflate kernels, the members back"""
+        data = bytes(data)
+        cap = bgzf_deflate_bound(len(data)) if cap is None else int(cap)
+        out = np.zeros(max(1, cap), np.uint8)
+        n = C.c_uint64(0)
+        check(self.lib.kr_debug_bgzf_deflate(self.h, data, len(data), out.ctypes.data, cap, C.byref(n)))
+        return out[: n.value].tobytes()
+
+    def bgzf_deflate_ms(self):
+        """(measurements) kr_debug_bgzf_deflate_ms: device time of the last deflate's kernels, -1 before the first measured one"""
+        ms = C.c_float(0)
+        check(self.lib.kr_debug_bgzf_deflate_ms(self.h, C.byref(ms)))
+        return float(ms.value)
+
     def seek_enable(self, max_text_bytes=0, max_id_bytes=0):
         """kr_stream_seek_enable: this stream takes batches flagged KR_SEEK (csrc/kr_dev_seek.inc); 0, 0: values only, no text"""
         check(self.lib.kr_stream_seek_enable(self.h, int(max_text_bytes), int(max_id_bytes)))
@@ -967,6 +1006,39 @@ def bgzf_walk(buf, max_inflated):
     k, c, u = C.c_uint32(0), C.c_uint64(0), C.c_uint64(0)
     check(load().kr_bgzf_walk(buf, len(buf), int(max_inflated), C.byref(k), C.byref(c), C.byref(u)))
     return int(k.value), int(c.value), int(u.value)
+
+
+BGZF_DEFLATE_STATS = ("members", "stored", "literals", "matches", "longest", "farthest")
+
+
+def bgzf_deflate_bound(n):
+    """kr_bgzf_deflate_bound: the most bytes the host form or the device produce for n bytes"""
+    return int(load().kr_bgzf_deflate_bound(int(n)))
+
+
+def bgzf_deflate_host(text, cap=None):
+    """kr_bgzf_deflate_host: `text` as BGZF members of 65,280 input bytes each (no device, no end member)"""
+    text = bytes(text)
+    cap = bgzf_deflate_bound(len(text)) if cap is None else int(cap)
+    out = np.zeros(max(1, cap), np.uint8)
+    n = C.c_uint64(0)
+    check(load().kr_bgzf_deflate_host(text, len(text), out.ctypes.data, cap, C.byref(n)))
+    return out[: n.value].tobytes()
+
+
+def bgzf_eof():
+    """kr_bgzf_eof: the 28-byte empty member that ends a BGZF file"""
+    out = C.create_string_buffer(28)
+    load().kr_bgzf_eof(out)
+    return out.raw
+
+
+def bgzf_deflate_stats(text):
+    """(tests) kr_debug_bgzf_deflate_stats: what the host form did with `text`, as a dict of BGZF_DEFLATE_STATS"""
+    text = bytes(text)
+    st = (C.c_uint64 * 6)()
+    check(load().kr_debug_bgzf_deflate_stats(text, len(text), st))
+    return dict(zip(BGZF_DEFLATE_STATS, [int(x) for x in st]))
 
 
 def bgzf_chunk_cut(buf, skip=0, fasta=False):

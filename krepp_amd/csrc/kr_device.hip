@@ -49,6 +49,7 @@
 //   kr_dev_fastq.inc       FASTQ records found in a chunk of raw file bytes (kr_batch_submit_fastq)
 //   kr_dev_fasta.inc       FASTA records found in a chunk of raw file bytes, every pass parallel over bytes (kr_batch_submit_fasta)
 //   kr_dev_bgzf.inc        the members of a block-gzipped chunk inflated into the record finders' buffer (kr_batch_submit_bgzf; decoder: kr_inflate.h)
+//   kr_dev_deflate.inc     report text deflated into BGZF members, one wave per member (kr_batch_collect_text_bgzf; encoder: kr_deflate.h)
 //   kr_dev_place.inc       back end of `place`: ancestor accumulation, candidates, their likelihoods (kr_place_kernel)
 //   kr_dev_place_parsed.inc  read lengths and ids of a batch the record finders queued, for the place kernels (kr_place_stream_parsed)
 //   kr_dev_debug.inc       debug / tap kernels and the re-layout kernels of kr_index_upload
@@ -58,6 +59,7 @@
 //   kr_host_fastq.inc      kr_stream_fastq_enable, kr_batch_submit_fastq, kr_batch_fastq_names
 //   kr_host_fasta.inc      kr_batch_submit_fasta
 //   kr_host_bgzf.inc       kr_stream_bgzf_enable, kr_batch_submit_bgzf, kr_debug_bgzf_inflate / _ms
+//   kr_host_deflate.inc    kr_stream_bgzf_out_enable, kr_batch_collect_text_bgzf, kr_debug_bgzf_deflate / _ms
 //   kr_host_place.inc      kr::place_on_device (launch of the place kernels for kr_place_stream and kr_place_stream_parsed)
 //   kr_host_seek.inc       kr_stream_seek_enable, a KR_SEEK batch's submit / wait, kr_batch_collect_seek, kr_debug_seek_layout / _ms
 //   (below, in this file)  kr_host_alloc, debug entry points, kr_llh_batch, kr_llh_eval_indexed
@@ -70,6 +72,7 @@
 #include "kr_common.h"
 #include "kr_devutil.h"
 #include "kr_inflate.h"
+#include "kr_deflate.h"
 
 #include <algorithm>
 #include <iterator>
@@ -100,6 +103,7 @@ namespace {
 #include "kr_dev_fastq.inc"
 #include "kr_dev_fasta.inc"
 #include "kr_dev_bgzf.inc"
+#include "kr_dev_deflate.inc"
 #include "kr_dev_place.inc"
 #include "kr_dev_place_parsed.inc"
 #include "kr_dev_debug.inc"
@@ -165,6 +169,7 @@ LlhConst make_llh_const(uint32_t k, uint32_t h, uint32_t th)
 #include "kr_host_fastq.inc"
 #include "kr_host_fasta.inc"
 #include "kr_host_bgzf.inc"
+#include "kr_host_deflate.inc"
 #include "kr_host_place.inc"
 #include "kr_host_seek.inc"
 

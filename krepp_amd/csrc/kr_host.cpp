@@ -12,6 +12,7 @@
 //   report text                      src/query.cpp:152-196, src/query.hpp:210
 #include "kr_common.h"
 #include "kr_inflate.h"
+#include "kr_deflate.h"
 
 #include <sched.h>
 
@@ -1610,6 +1611,58 @@ int kr_debug_bgzf_inflate_host(const uint8_t* comp, uint64_t ncomp, uint8_t* out
     total += m.isize, off += ms;
   }
   *len = total;
+  return KR_OK;
+}
+
+// ---- bytes deflated into BGZF members by the encoder's host instantiation (kr_deflate.h): what the device's kernel writes ------------
+uint64_t kr_bgzf_deflate_bound(uint64_t n) { return kr::bgzf_deflate_bound(n); }
+
+void kr_bgzf_eof(uint8_t* out28)
+{
+  if (out28) kr::bgzf_eof(out28);
+}
+
+// Every member into a slot of its own (the members' sizes are known only afterwards), on the thread pool in runs of members; then
+// the slots back to back.  A member's bytes depend on its input alone: neither on the thread that wrote it nor on how many there are.
+static int bgzf_deflate_slots(const uint8_t* text, uint64_t n, std::vector<uint8_t>& slots, std::vector<uint32_t>& sizes, kr::DefStats* st)
+{
+  const uint64_t nm = kr::bgzf_deflate_members(n);
+  slots.resize(nm * kr::kDefSlot), sizes.resize(nm);
+  const int nt = (int)std::max<uint64_t>(1, std::min<uint64_t>(st ? 1 : kr::parallel_width(), nm / 4)); // (stats: one thread, one counter)
+  kr::parallel_for(nt, [&](int t) {
+    std::unique_ptr<kr::DefState> S(new kr::DefState);
+    for (uint64_t m = nm * (uint64_t)t / nt; m < nm * (uint64_t)(t + 1) / nt; ++m)
+      sizes[m] = kr::bgzf_deflate_member_host(text, n, m, slots.data() + m * kr::kDefSlot, *S, st);
+  });
+  return KR_OK;
+}
+
+int kr_bgzf_deflate_host(const uint8_t* text, uint64_t n, uint8_t* out, uint64_t cap, uint64_t* len)
+{
+  kr::clear_error();
+  if (!len || (n && !text) || (cap && !out)) return kr::fail(KR_ERR_ARG, "kr_bgzf_deflate_host: null argument");
+  *len = 0;
+  std::vector<uint8_t> slots;
+  std::vector<uint32_t> sizes;
+  bgzf_deflate_slots(text, n, slots, sizes, nullptr);
+  uint64_t total = 0;
+  for (uint32_t sz : sizes) total += sz;
+  if (total > cap) return kr::fail(KR_ERR_CAPACITY, "kr_bgzf_deflate_host: the members take " + std::to_string(total) + " bytes, the buffer holds " + std::to_string(cap));
+  uint64_t off = 0;
+  for (size_t m = 0; m < sizes.size(); ++m) memcpy(out + off, slots.data() + m * kr::kDefSlot, sizes[m]), off += sizes[m];
+  *len = total;
+  return KR_OK;
+}
+
+int kr_debug_bgzf_deflate_stats(const uint8_t* text, uint64_t n, uint64_t* stats)
+{
+  kr::clear_error();
+  if (!stats || (n && !text)) return kr::fail(KR_ERR_ARG, "kr_debug_bgzf_deflate_stats: null argument");
+  std::vector<uint8_t> slots;
+  std::vector<uint32_t> sizes;
+  kr::DefStats st;
+  bgzf_deflate_slots(text, n, slots, sizes, &st);
+  stats[0] = st.members, stats[1] = st.stored, stats[2] = st.literals, stats[3] = st.matches, stats[4] = st.longest, stats[5] = st.farthest;
   return KR_OK;
 }
 

@@ -1,0 +1,132 @@
+// kr_host_deflate.inc -- part of kr_device.hip (host side): kr_stream_bgzf_out_enable, kr_batch_collect_text_bgzf,
+// kr_debug_bgzf_deflate, kr_debug_bgzf_deflate_ms.  Report text that lies in device memory is deflated into BGZF members there
+// (kernels: kr_dev_deflate.inc, encoder: kr_deflate.h) and only the members cross to the host.
+
+namespace {
+
+// Room for the members of n text bytes.  Every buffer is in hand before the first kernel is queued.
+int deflate_reserve(kr_stream* s, uint64_t n)
+{
+  kr_stream::BgzfOut& o = s->bgzf_out;
+  const uint64_t nm = kr::bgzf_deflate_members(n);
+  if (!o.d_slots.reserve(nm * kr::kDefSlot) || !o.d_off.reserve(nm + 1) || !o.d_out.reserve(kr::bgzf_deflate_bound(n)) || !o.h_total.reserve(1))
+    return alloc_failed("bgzf out: device buffers");
+  return KR_OK;
+}
+
+// d_text[0 .. n), n > 0, deflated on st; behind the wait *total is the members' bytes, back to back in d_out
+int deflate_run(kr_stream* s, hipStream_t st, const uint8_t* d_text, uint64_t n, uint64_t* total)
+{
+  kr_stream::BgzfOut& o = s->bgzf_out;
+  const uint64_t nm = kr::bgzf_deflate_members(n);
+  if (nm >= (1ull << 31)) return kr::fail(KR_ERR_ARG, "bgzf out: too many members");
+  DeflateIO io{d_text, n, (uint32_t)nm, o.d_slots.get(), o.d_off.get(), o.d_out.get()};
+  if (o.ev0) HIP_TRY(hipEventRecord(o.ev0, st));
+  hipLaunchKernelGGL(kr_bgzf_deflate_kernel, dim3((uint32_t)((nm + 3) / 4)), dim3(256), 0, st, io);
+  hipLaunchKernelGGL(kr_bgzf_deflate_scan_kernel, dim3(1), dim3(1024), 0, st, io.off, io.nmembers);
+  hipLaunchKernelGGL(kr_bgzf_deflate_copy_kernel, dim3(io.nmembers), dim3(256), 0, st, io);
+  HIP_TRY(hipGetLastError());
+  if (o.ev0) {
+    HIP_TRY(hipEventRecord(o.ev1, st));
+    o.ev_set = true;
+  }
+  HIP_TRY(hipMemcpyAsync(o.h_total.get(), io.off + nm, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  *total = *o.h_total.get();
+  if (*total < nm * 28 || *total > kr::bgzf_deflate_bound(n)) return kr::fail(KR_ERR_NO_DEVICE, "bgzf out: the deflate kernels left an impossible size");
+  return KR_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int kr_stream_bgzf_out_enable(kr_stream* s)
+{
+  kr::clear_error();
+  if (!s) return kr::fail(KR_ERR_ARG, "kr_stream_bgzf_out_enable: null argument");
+  if (!s->text.on) return kr::fail(KR_ERR_STATE, "kr_stream_bgzf_out_enable: kr_stream_text_enable or kr_stream_seek_enable (with text buffers) first");
+  if (s->bgzf_out.on) return kr::fail(KR_ERR_STATE, "kr_stream_bgzf_out_enable: already enabled");
+  HIP_TRY(hipSetDevice(s->ix->device));
+  if (int rc = deflate_reserve(s, s->text.text_cap)) return rc;
+  s->bgzf_out.on = true;
+  return KR_OK;
+}
+
+int kr_batch_collect_text_bgzf(kr_stream* s, const uint8_t** comp, uint64_t* len, uint64_t* text_len)
+{
+  kr::clear_error();
+  if (!s || !comp || !len || !text_len) return kr::fail(KR_ERR_ARG, "kr_batch_collect_text_bgzf: null argument");
+  *comp = (const uint8_t*)"", *len = 0, *text_len = 0;
+  if (!s->bgzf_out.on) return kr::fail(KR_ERR_STATE, "kr_batch_collect_text_bgzf: kr_stream_bgzf_out_enable first");
+  if (!s->batch.submitted || !s->batch.has_ids()) return kr::fail(KR_ERR_STATE, "kr_batch_collect_text_bgzf: no batch submitted with kr_batch_submit_text");
+  if (int rc = kr_batch_wait(s)) return rc;
+  kr_stream::Text& t = s->text;
+  kr_stream::BgzfOut& o = s->bgzf_out;
+  // (the statuses of kr_batch_collect_text, for the same reasons)
+  if (!s->batch.text_made) return kr::fail(KR_ERR_UNSUPPORTED, "kr_batch_collect_text_bgzf: the batch left the device as record slots (long sequences; submit with KR_TILE_ROWS for device text): kr_batch_collect + kr_format_dist");
+  if (t.h_total[1] & kTextOverCap) return kr::fail(KR_ERR_CAPACITY, "the batch's report text exceeds max_text_bytes: submit fewer reads per batch");
+  if (t.h_total[1] & kTextBadNum) return kr::fail(KR_ERR_UNSUPPORTED, "kr_batch_collect_text_bgzf: a DIST outside [0, 1000): kr_batch_collect + kr_format_dist");
+  HIP_TRY(hipSetDevice(s->ix->device));
+  const uint64_t n = t.h_total[0];
+  if (n == 0) return KR_OK;
+  if (n > t.text_cap) return kr::fail(KR_ERR_CAPACITY, "the batch's report text exceeds max_text_bytes: submit fewer reads per batch"); // (cannot be: the kernels flag it)
+  const uint64_t bound = kr::bgzf_deflate_bound(n);
+  if (int rc = deflate_reserve(s, n)) return rc; // (in hand since kr_stream_bgzf_out_enable: n <= max_text_bytes)
+  if (bound > o.h_comp.size() && !o.h_comp.reserve(std::min<uint64_t>(kr::bgzf_deflate_bound(t.text_cap), bound + bound / 4 + (1u << 20))))
+    return alloc_failed("kr_batch_collect_text_bgzf");
+  hipStream_t st = s->lanes[0].stream;
+  uint64_t total = 0;
+  if (int rc = deflate_run(s, st, (const uint8_t*)t.d_text, n, &total)) return rc;
+  HIP_TRY(hipMemcpyAsync(o.h_comp.get(), o.d_out.get(), total, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  *comp = o.h_comp.get(), *len = total, *text_len = n;
+  return KR_OK;
+}
+
+// (tests) any host bytes through the kernels
+int kr_debug_bgzf_deflate(kr_stream* s, const uint8_t* bytes, uint64_t n, uint8_t* out, uint64_t cap, uint64_t* len)
+{
+  kr::clear_error();
+  if (!s || !len || (n && !bytes) || (cap && !out)) return kr::fail(KR_ERR_ARG, "kr_debug_bgzf_deflate: null argument");
+  *len = 0;
+  if (!s->bgzf_out.on) return kr::fail(KR_ERR_STATE, "kr_debug_bgzf_deflate: kr_stream_bgzf_out_enable first");
+  if (n == 0) return KR_OK;
+  HIP_TRY(hipSetDevice(s->ix->device));
+  (void)hipGetLastError();
+  if (int rc = drain_batch(s)) return rc; // (growing a buffer frees the old one)
+  kr_stream::BgzfOut& o = s->bgzf_out;
+  if (int rc = deflate_reserve(s, n)) return rc;
+  if (!o.d_in.reserve(n)) return alloc_failed("kr_debug_bgzf_deflate");
+  hipStream_t st = s->lanes[0].stream;
+  HIP_TRY(hipMemcpyAsync(o.d_in.get(), bytes, n, hipMemcpyHostToDevice, st));
+  uint64_t total = 0;
+  if (int rc = deflate_run(s, st, o.d_in.get(), n, &total)) return rc;
+  if (total > cap) return kr::fail(KR_ERR_CAPACITY, "kr_debug_bgzf_deflate: the members take " + std::to_string(total) + " bytes, the buffer holds " + std::to_string(cap));
+  HIP_TRY(hipMemcpy(out, o.d_out.get(), total, hipMemcpyDeviceToHost));
+  *len = total;
+  return KR_OK;
+}
+
+// (measurements) the device time of the deflate, scan and copy kernels of the stream's last kr_batch_collect_text_bgzf /
+// kr_debug_bgzf_deflate.  The first call makes the events and gives *ms = -1: the next deflate is the first measured.
+int kr_debug_bgzf_deflate_ms(kr_stream* s, float* ms)
+{
+  kr::clear_error();
+  if (!s || !ms) return kr::fail(KR_ERR_ARG, "kr_debug_bgzf_deflate_ms: null argument");
+  if (!s->bgzf_out.on) return kr::fail(KR_ERR_STATE, "kr_debug_bgzf_deflate_ms: kr_stream_bgzf_out_enable first");
+  kr_stream::BgzfOut& o = s->bgzf_out;
+  *ms = -1.0f;
+  HIP_TRY(hipSetDevice(s->ix->device));
+  if (!o.ev0) {
+    HIP_TRY(hipEventCreate(&o.ev0));
+    HIP_TRY(hipEventCreate(&o.ev1));
+    return KR_OK;
+  }
+  if (!o.ev_set) return KR_OK;
+  HIP_TRY(hipEventSynchronize(o.ev1));
+  HIP_TRY(hipEventElapsedTime(ms, o.ev0, o.ev1));
+  return KR_OK;
+}
+
+} // extern "C"

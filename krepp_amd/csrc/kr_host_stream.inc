@@ -268,6 +268,16 @@ struct kr_stream {
     hipEvent_t ev0 = nullptr, ev1 = nullptr; // kr_debug_bgzf_ms: around the inflate kernel, once asked for
     bool ev_set = false;
   } bgzf;
+  // report text deflated into BGZF members on the device (kr_dev_deflate.inc, kr_host_deflate.inc; kr_stream_bgzf_out_enable)
+  struct BgzfOut {
+    bool on = false;
+    DevBuf<uint8_t> d_slots, d_out, d_in; // [members][kDefSlot], the members back to back, kr_debug_bgzf_deflate's bytes
+    DevBuf<uint64_t> d_off;               // [members + 1]
+    PinBuf<uint64_t> h_total;
+    PinBuf<uint8_t> h_comp; // (made by the first batch that needs it, as large as that batch's text can become)
+    hipEvent_t ev0 = nullptr, ev1 = nullptr; // kr_debug_bgzf_deflate_ms: around the three kernels, once asked for
+    bool ev_set = false;
+  } bgzf_out;
   Batch batch;     // the batch in flight
   LastParse parse; // the last record finder's call
   // state
@@ -1068,6 +1078,8 @@ void kr_stream_destroy(kr_stream* s)
   if (s->fq.ev_parse1) (void)hipEventDestroy(s->fq.ev_parse1);
   if (s->bgzf.ev0) (void)hipEventDestroy(s->bgzf.ev0);
   if (s->bgzf.ev1) (void)hipEventDestroy(s->bgzf.ev1);
+  if (s->bgzf_out.ev0) (void)hipEventDestroy(s->bgzf_out.ev0);
+  if (s->bgzf_out.ev1) (void)hipEventDestroy(s->bgzf_out.ev1);
   for (auto& e : s->seek.ev)
     if (e) (void)hipEventDestroy(e);
   delete s; // (every DevBuf / PinBuf of the stream frees itself here: the device is set, the lanes' streams have been waited for)

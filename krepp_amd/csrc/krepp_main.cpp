@@ -54,7 +54,7 @@ static const std::map<std::string, std::string> kAlias = {
   {"-i", "--index-dir"}, {"-q", "--query"}, {"-o", "--output-path"}, {"-t", "--nwk-file"}, {"-k", "--kmer-len"},
   {"-w", "--win-len"}, {"-h", "--num-positions"}, {"-m", "--modulo-lsh"}, {"-r", "--residue-lsh"}, {"-l", "--lineage-file"},
 };
-static const char* kFlags[] = {"--multi", "--filter", "--summarize", "--frac", "--verbose", "--gpu-minimizers", "--gpu-keys", "--gpu-colours", "--tabular", "--gpu-parse", "--gpu-seek", "--gpu-stats"};
+static const char* kFlags[] = {"--multi", "--filter", "--summarize", "--frac", "--verbose", "--gpu-minimizers", "--gpu-keys", "--gpu-colours", "--tabular", "--gpu-parse", "--gpu-seek", "--gpu-stats", "--bgzf-out"};
 
 // options as in the reference's CLI (src/krepp.cpp:516-675); the texts are this build's own
 static void print_help(const std::string& sub)
@@ -62,6 +62,7 @@ static void print_help(const std::string& sub)
   const char* query_opts =
     "  -q, --query PATH           query FASTA/FASTQ file (gzip accepted)\n"
     "  -o, --output-path PATH     write the report here [stdout]\n"
+    "      --bgzf-out             write the report block-gzipped (BGZF: zcat, bgzip -d, tabix read it; device text is deflated on the GPU)\n"
     "      --hdist-th N           largest Hamming distance at which a k-mer matches [4]\n";
   const char* index_query_opts =
     "  -i, --index-dir DIR        index directory (as written by `krepp index`, this build's or the reference's)\n"
@@ -171,6 +172,7 @@ struct Settings {
   std::string query, index_arg, invocation;
   bool gpu_parse = false; // --gpu-parse asked for (Run::open_input decides whether the file qualifies)
   bool gpu_seek = false;  // seek --gpu-seek: batches flagged KR_SEEK, the report as the device's text
+  bool bgzf_out = false;  // --bgzf-out: every byte of the report goes out as BGZF members (Run::put, Worker::collect)
   int ngpus = 1, dev0 = 0, wpg = 2, nworkers = 2, write_threads = 4;
   uint32_t max_reads = 0;
   uint64_t batch_bases = 0, max_bases = 0, chunk_bytes = 0, max_records = 0, text_bytes = 0;
@@ -215,6 +217,7 @@ static Settings resolve_settings(const Args& a, const std::string& invocation, i
   s.gpu_parse = a.flag.count("--gpu-parse") && a.flag.at("--gpu-parse");
   s.gpu_seek = a.flag.count("--gpu-seek") && a.flag.at("--gpu-seek");
   if (s.gpu_seek && !seek) error_exit("--gpu-seek is an option of `seek`");
+  s.bgzf_out = a.flag.count("--bgzf-out") && a.flag.at("--bgzf-out");
 
   // reads per batch: the kernels' efficiency grows with the batch (launch tails amortise, likelihood problems repeat): 262,144 reads
   // for `dist` on a large input, 65,536 for `place` / `seek` (more state per read) and for inputs of a few batches anyway
@@ -483,6 +486,10 @@ struct Run {
   std::atomic<uint64_t> ns_parse{0}, ns_job{0}, ns_dev{0}, ns_fmt{0}, ns_write{0};
   std::atomic<uint64_t> nb_dev_text{0}, nb_host_text{0}; // `dist` batches (pieces of them) written from device text / through kr_format_dist
   std::atomic<int> worker_ids{0};
+  // --bgzf-out: the report's bytes before and after deflation, and the pieces deflated on the device / by the host encoder
+  std::atomic<uint64_t> nb_plain{0}, nb_comp{0}, n_dev_deflate{0}, n_host_deflate{0};
+  std::string deflated(const char* p, size_t n);
+  void put(const char* p, size_t n);
   double at() const { return std::chrono::duration<double>(Clock::now() - t_init).count(); } // seconds since the query phase began
 
   void start_up(const Args& a);
@@ -556,18 +563,42 @@ void Run::start_up(const Args& a)
   }
   t_init = t_loop = Clock::now();
   if (s.seek) { // QuerySketch::header_dreport (src/krepp.cpp:305-309)
-    fprintf(out, "# software: krepp\tversion: " KREPP_VERSION "\tinvocation :%s\nSEQ_ID\tDIST\n", s.invocation.c_str());
+    const std::string h = "# software: krepp\tversion: " KREPP_VERSION "\tinvocation :" + s.invocation + "\nSEQ_ID\tDIST\n";
+    put(h.data(), h.size());
   } else if (!s.place) { // header (src/krepp.cpp:311-319)
-    fprintf(out, "# software: krepp\tversion: " KREPP_VERSION "\tinvocation :%s\n%s\n", s.invocation.c_str(),
-            s.summarize ? "REFERENCE_NAME\tWEIGHTED_COUNT\tSEQUENCE_ABUNDANCE" : "SEQ_ID\tREFERENCE_NAME\tDIST");
+    const std::string h = "# software: krepp\tversion: " KREPP_VERSION "\tinvocation :" + s.invocation + "\n" +
+                          (s.summarize ? "REFERENCE_NAME\tWEIGHTED_COUNT\tSEQUENCE_ABUNDANCE" : "SEQ_ID\tREFERENCE_NAME\tDIST") + "\n";
+    put(h.data(), h.size());
   } else { // jplace opening or tabular header (src/krepp.cpp:440-447)
     char* t = nullptr;
     uint64_t l = 0;
     if (kr_place_frame(ptree, 0, s.tabular, s.invocation.c_str(), 0, &t, &l)) error_exit(kr_last_error());
-    fwrite(t, 1, l, out);
+    put(t, l);
     kr_free(t);
   }
   order.open(out, s.dev_text && !s.serial_write);
+}
+
+// --bgzf-out: p[0 .. n) as BGZF members, deflated by the host encoder in the calling thread (what the device's kernel would write)
+std::string Run::deflated(const char* p, size_t n)
+{
+  std::string c((size_t)kr_bgzf_deflate_bound(n), '\0');
+  uint64_t len = 0;
+  if (kr_bgzf_deflate_host((const uint8_t*)p, n, (uint8_t*)&c[0], c.size(), &len)) error_exit(kr_last_error());
+  c.resize((size_t)len);
+  if (n) nb_plain += n, nb_comp += len, ++n_host_deflate;
+  return c;
+}
+
+// The one way bytes reach `out` from the threads that write in turn (start_up, the writer, finish): as they are, or as BGZF members
+void Run::put(const char* p, size_t n)
+{
+  if (!s.bgzf_out) {
+    fwrite(p, 1, n, out);
+    return;
+  }
+  const std::string c = deflated(p, n);
+  fwrite(c.data(), 1, c.size(), out);
 }
 
 // The first inflated byte of a block-gzipped file ('>': FASTA), from its first member that holds one, inflated on the host.
@@ -679,6 +710,7 @@ struct Worker {
   Worker(Run& r_, int g_) : r(r_), s(r_.s), g(g_) {}
   kr_stream* st = nullptr;
   bool text_on = false; // the stream formats `dist` rows on the device
+  bool bgzf_dev = false; // --bgzf-out: the stream deflates its device text (kr_batch_collect_text_bgzf)
   // reads per submit this worker currently trusts: halved when a submit overflows a device buffer, doubled again
   // after a run of successes -- data with hundreds of rows per read settle at a piece size instead of failing a
   // full-size submit (and every intermediate size) for every batch
@@ -700,6 +732,9 @@ struct Worker {
   int chunk_names(const uint8_t* raw, uint32_t n);
   void keep_placements(int rc, kr_placement* pp, uint64_t npp, uint64_t base);
   void emit(const char* p, size_t n, bool whole_job);
+  void emit_host(const char* p, size_t n); // rows a host formatter made: through the host encoder with --bgzf-out
+  void append(const char* p, size_t n);    // ... for the job's text
+  int collect_device_text(const char** dtext, uint64_t* dlen);
   int joins() const { return (!s.tabular && !text.empty()) ? 1 : 0; } // jplace: pieces of a job are joined by the worker, jobs by the writer (src/krepp.cpp:474-484)
   void succeeded() // (grow back after a run of successes)
   {
@@ -722,6 +757,10 @@ void Worker::loop()
       fprintf(stderr, "[krepp_amd] report text on the host: %s\n", kr_last_error());
   }
   if (s.gpu_seek && kr_stream_seek_enable(st, s.text_bytes, std::max<uint64_t>(1ull << 20, (uint64_t)s.max_reads * 64))) return r.worker_ready(kr_last_error());
+  if (s.bgzf_out && (text_on || s.gpu_seek)) {
+    if (kr_stream_bgzf_out_enable(st)) return r.worker_ready(kr_last_error());
+    bgzf_dev = true;
+  }
   if (r.gpu_parse && kr_stream_fastq_enable(st, r.chunk_cap())) return r.worker_ready(kr_last_error());
   if (r.bgzf && kr_stream_bgzf_enable(st, r.chunk_cap())) return r.worker_ready(kr_last_error());
   const double t_ready = r.at();
@@ -787,10 +826,35 @@ void Worker::emit(const char* p, size_t n, bool whole_job)
 int Worker::collect(kr_result_view* rv, const char** dtext, uint64_t* dlen, bool* on_device)
 {
   if (!text_on) return kr_batch_collect(st, rv);
-  int rc = kr_batch_collect_text(st, dtext, dlen);
+  int rc = collect_device_text(dtext, dlen);
   *on_device = rc == 0;
   if (rc == KR_ERR_UNSUPPORTED) rc = kr_batch_collect(st, rv);
   return rc;
+}
+
+// The batch's device text: the bytes the output takes -- plain, or deflated into BGZF members where they lie (--bgzf-out)
+int Worker::collect_device_text(const char** dtext, uint64_t* dlen)
+{
+  if (!bgzf_dev) return kr_batch_collect_text(st, dtext, dlen);
+  const uint8_t* comp = nullptr;
+  uint64_t text_len = 0;
+  const int rc = kr_batch_collect_text_bgzf(st, &comp, dlen, &text_len);
+  *dtext = (const char*)comp;
+  if (!rc && text_len) r.nb_plain += text_len, r.nb_comp += *dlen, ++r.n_dev_deflate;
+  return rc;
+}
+
+void Worker::emit_host(const char* p, size_t n)
+{
+  if (!s.bgzf_out) return emit(p, n, false);
+  const std::string c = r.deflated(p, n);
+  emit(c.data(), c.size(), false);
+}
+
+void Worker::append(const char* p, size_t n)
+{
+  if (s.bgzf_out) text += r.deflated(p, n);
+  else text.append(p, n);
 }
 
 // place --summarize: the piece's placements, `read` counted from `base`
@@ -832,7 +896,7 @@ int Worker::run_batch(size_t lo, size_t hi)
     for (size_t i = 0; i < n; ++i) id_off[i] = (uint32_t)(nm[i] - j->blob);
     id_off[n] = hi < j->n ? (uint32_t)(nm[n] - j->blob) : (uint32_t)j->blob_bytes;
     rc = kr_batch_submit_text(st, j->bases + j->offsets[lo], offs.data(), (uint32_t)n, KR_BASES_HOST | KR_SEEK, j->blob, id_off.data(), 1);
-    if (!rc) rc = kr_batch_collect_text(st, &dtext, &dlen);
+    if (!rc) rc = collect_device_text(&dtext, &dlen);
     r.ns_dev += since(t_dev);
     if (rc == KR_ERR_CAPACITY && n > 1) {
       piece = std::min(piece, (n + 1) / 2);
@@ -840,7 +904,7 @@ int Worker::run_batch(size_t lo, size_t hi)
       return run_halves(lo, hi);
     }
     if (rc) return rc;
-    text.append(dtext, dlen);
+    text.append(dtext, dlen); // (members, with --bgzf-out: they concatenate as their texts do)
     r.nreads_seek += n;
     succeeded();
     return 0;
@@ -882,9 +946,9 @@ int Worker::run_batch(size_t lo, size_t hi)
     keep_placements(rc, pp, npp, j->first_read + lo);
   }
   if (!rc && txt && s.dev_text)
-    emit(txt, len, false); // (in order with the pieces the device wrote)
+    emit_host(txt, len); // (in order with the pieces the device wrote)
   else if (!rc && txt)
-    text.append(txt, len);
+    append(txt, len);
   kr_free(txt);
   r.ns_fmt += since(t_fmt);
   if (!rc) succeeded();
@@ -938,7 +1002,7 @@ int Worker::run_chunk()
       const char* dtext = nullptr;
       bool on_device = false;
       if (s.gpu_seek)
-        rc = kr_batch_collect_text(st, &dtext, &dlen);
+        rc = collect_device_text(&dtext, &dlen);
       else if (!s.place)
         rc = collect(&rv, &dtext, &dlen, &on_device); // (place: kr_place_stream_parsed waits for the batch)
       r.ns_dev += since(t_dev);
@@ -963,9 +1027,9 @@ int Worker::run_chunk()
         keep_placements(rc, pp, npp, nr_job); // (`read`: the number within the chunk; the chunk's first read is known when its turn comes)
       }
       if (!rc && txt && s.plain_dist())
-        emit(txt, len, false);
+        emit_host(txt, len);
       else if (!rc && txt)
-        text.append(txt, len);
+        append(txt, len);
       kr_free(txt);
       r.ns_fmt += since(t_fmt);
       if (rc == KR_ERR_CAPACITY) { // more records or text than a batch holds: the host reader takes over at this batch's first record
@@ -1011,7 +1075,7 @@ void Run::write_loop()
       carry.erase(carry.begin(), carry.begin() + cut);
     } else if (s.place && !s.tabular) {
       if (!j->text.empty()) {
-        if (jplace_prev) fputs(",\n", out);
+        if (jplace_prev) put(",\n", 2);
         fwrite(j->text.data(), 1, j->text.size(), out);
         jplace_prev = true;
       }
@@ -1220,27 +1284,39 @@ int Run::finish()
 {
   const bool place = s.place, seek = s.seek;
   if (order.failed()) error_exit(order.error());
+  std::string rows;
   if (s.summarize && !place) // src/krepp.cpp:388-393 (ascending colour id instead of hash-map order)
     for (uint32_t se = 0; se < wcount.size(); ++se)
-      if (wcount[se] != 0) fprintf(out, "%s\t%.5f\t%.5f\n", kr_host_index_node_name(hx, se), wcount[se], wcount[se] / twcount);
+      if (wcount[se] != 0) {
+        char row[64];
+        std::string line = kr_host_index_node_name(hx, se);
+        snprintf(row, sizeof(row), "\t%.5f\t%.5f\n", wcount[se], wcount[se] / twcount);
+        rows += line + row;
+      }
   if (s.tabular == 2) { // src/krepp.cpp:493-497
     char* t = nullptr;
     uint64_t l = 0;
     if (kr_place_summary_add(ptree, carry.data(), carry.size(), pwcount.data(), &ptwcount) ||
         kr_place_summary_text(ptree, pwcount.data(), ptwcount, &t, &l))
       error_exit(kr_last_error());
-    fwrite(t, 1, l, out);
+    rows.append(t, l);
     kr_free(t);
   }
   if (place) {
     char* t = nullptr;
     uint64_t l = 0;
     if (kr_place_frame(ptree, 1, s.tabular, s.invocation.c_str(), nreads_total, &t, &l)) error_exit(kr_last_error());
-    fwrite(t, 1, l, out);
+    rows.append(t, l);
     kr_free(t);
     kr_place_tree_free(ptree);
   }
+  if (!rows.empty()) put(rows.data(), rows.size()); // (only where no worker wrote side by side: the stream's position is the file's end)
   order.rewind_to_end(out);
+  if (s.bgzf_out) { // the end member, once, last
+    uint8_t eof_member[28];
+    kr_bgzf_eof(eof_member);
+    fwrite(eof_member, 1, sizeof(eof_member), out);
+  }
   if (out != stdout) fclose(out);
   const double sec = at();
   fprintf(stderr, place ? "Done placing queries, elapsed: %g sec (%.0f reads/s on %d GPU(s))\n" : seek ? "Done seeking query sequences, elapsed: %g sec (%.0f reads/s on %d GPU(s))\n" : "Done estimating distances, elapsed: %g sec (%.0f reads/s on %d GPU(s))\n", sec,
@@ -1254,6 +1330,9 @@ int Run::finish()
   if (s.timing && s.plain_dist()) // (a batch split at capacity counts once per piece)
     fprintf(stderr, "[timing] report text: %llu batches written from device text, %llu through the host formatter\n", (unsigned long long)nb_dev_text.load(),
             (unsigned long long)nb_host_text.load());
+  if (s.timing && s.bgzf_out)
+    fprintf(stderr, "[timing] bgzf-out: %llu text bytes, %llu compressed bytes (without the end member); %llu pieces deflated on the device, %llu by the host encoder\n",
+            (unsigned long long)nb_plain.load(), (unsigned long long)nb_comp.load(), (unsigned long long)n_dev_deflate.load(), (unsigned long long)n_host_deflate.load());
   fprintf(stderr, "Total number of sequences queried: %llu\n", (unsigned long long)nreads_total);
   // Everything is written.  Unmapping 19 GB of index, 10 GB of host tables and the page-locked buffers one by one takes 0.8-1.2 s
   // that nobody is waiting for: the process ends here and the kernel reclaims the lot (KR_CLI_CLEAN_EXIT=1: free everything in

@@ -5,7 +5,9 @@ reader thread -> GPU workers -> ordered writer, plain FASTQ in, report text out 
 
 usage: scripts/time_cli_syn1000.py [reads, default 8,000,000] [index GB, default 10]
 Prints, per configuration, the CLI's own `elapsed` / `[timing]` lines (KR_CLI_TIMING=1) and reads/s from its elapsed time (query
-phase only: the index load -- 10 GB from disk, re-layout on the device -- is printed separately as wall time minus elapsed)."""
+phase only: the index load -- 10 GB from disk, re-layout on the device -- is printed separately as wall time minus elapsed).
+Environment: KR_TIME_CLI_CONFIGS (which configurations, "p" in front: with the binary of KR_TIME_CLI_PARENT_EXE), KR_TIME_CLI_OUT_DIR,
+KR_TIME_CLI_DEFLATE=1 (the deflate kernels on 100 MB of this workload's text), KR_TIME_CLI_TRACE=1: scripts/README.md."""
 import os
 import struct
 import subprocess
@@ -68,7 +70,6 @@ with open(fq, "wb") as f:
         done += m
 print(f"set-up {time.time() - t0:.0f} s: index {nk * 8 / 1e9:.1f} GB in {idx}, {n} reads in {os.path.getsize(fq) / 1e9:.2f} GB of FASTQ", flush=True)
 
-exe = os.path.join(root, "krepp_amd", "lib", "krepp")
 # KR_TIME_CLI_OUT_DIR: where the report goes (default: the work directory, i.e. the box's disk; /dev/shm takes the disk out of the
 # measurement -- 38 GB of rows for 50 M reads are written at the disk's 5 GB/s otherwise, profiles/round6_cli_syn1000_50m*.txt)
 out_file = os.path.join(os.environ.get("KR_TIME_CLI_OUT_DIR", work), "krepp_cli_out.txt")
@@ -86,10 +87,14 @@ configs = [
     ("dist", ["--summarize"], {"KR_CLI_WORKERS_PER_GPU": "3"}, out_file),  # 10
     ("dist", ["--no-multi"], {"KR_CLI_WORKERS_PER_GPU": "4"}, out_file),  # 11
     ("dist", ["--no-multi"], {"KR_CLI_BATCH_READS": "524288"}, out_file),  # 12
+    ("dist", ["--bgzf-out"], {}, out_file),  # 13: the report block-gzipped, the text deflated on the GPU (docs/design/15)
 ]
-if os.environ.get("KR_TIME_CLI_CONFIGS"):  # e.g. "0,5,7"
-    configs = [configs[int(i)] for i in os.environ["KR_TIME_CLI_CONFIGS"].split(",")]
-for sub, extra, env, outp in configs:
+# KR_TIME_CLI_CONFIGS, e.g. "0,5,7"; "p0": configuration 0 with the binary KR_TIME_CLI_PARENT_EXE names (a build of another commit, as
+# the yardstick of the same session: "p0,0,13,p0,0,13,p0,0,13")
+picked = os.environ.get("KR_TIME_CLI_CONFIGS", ",".join(str(i) for i in range(len(configs)))).split(",")
+for tok in picked:
+    sub, extra, env, outp = configs[int(tok.lstrip("p"))]
+    exe = os.environ["KR_TIME_CLI_PARENT_EXE"] if tok.startswith("p") else os.path.join(root, "krepp_amd", "lib", "krepp")
     # a fresh output file every time: closing a file that was truncated and rewritten makes ext4 allocate its blocks at close()
     # (0.6 s for 6 GB, inside the CLI's elapsed time as inside the reference's) -- every configuration after the first paid that
     # in the earlier runs of this script (profiles/round5_cli_syn1000.txt: the gap between a worker's last batch and `elapsed`)
@@ -101,7 +106,7 @@ for sub, extra, env, outp in configs:
     lines = [l for l in r.stderr.strip().splitlines() if "timing" in l or "elapsed" in l]
     el = [float(l.split("elapsed:")[1].split()[0]) for l in lines if "elapsed:" in l]
     size = os.path.getsize(outp) / 1e9 if outp != "/dev/null" and os.path.exists(outp) else 0.0
-    print(f"{sub} {' '.join(extra)} {env} -> {outp if outp == '/dev/null' else 'file'}: rc {r.returncode}, wall {dt:.2f} s, query phase "
+    print(f"{'[parent binary] ' if tok.startswith('p') else ''}{sub} {' '.join(extra)} {env} -> {outp if outp == '/dev/null' else 'file'}: rc {r.returncode}, wall {dt:.2f} s, query phase "
           f"{el[0] if el else float('nan'):.2f} s = {n / el[0] / 1e6 if el else float('nan'):.1f} M reads/s, index load + start-up {dt - (el[0] if el else 0):.1f} s, "
           f"output {size:.2f} GB ({size / el[0] if el else 0:.2f} GB/s of text)", flush=True)
     for l in lines:
@@ -109,12 +114,44 @@ for sub, extra, env, outp in configs:
     if r.returncode:
         print(r.stderr[-1500:])
 
+# ---- KR_TIME_CLI_DEFLATE=1: ~100 MB of this workload's report text in one batch: the plain copy back (kr_batch_collect_text) beside
+#      the deflate on the device and the copy back of the members (kr_batch_collect_text_bgzf); kr_debug_bgzf_deflate_ms is the three
+#      kernels alone.  The text stays on the device, so both calls are repeated on the same batch.
+if os.environ.get("KR_TIME_CLI_DEFLATE"):
+    import ctypes as C
+
+    nr = 115_000
+    b, o, names = synth.sample_reads(genomes, nr, seed=77)
+    hx = capi.HostIndex(idx)
+    dx = hx.upload(0)
+    st = dx.stream(max_reads=nr, max_bases=len(b) + 64, max_records=64 * nr)
+    st.text_enable(hx, 160 << 20, 64 * nr)
+    st.bgzf_out_enable()
+    st.bgzf_deflate_ms()  # (makes the events)
+    st.submit_text(b, o, names, capi.KR_TILE_ROWS)
+    st.wait()
+    lib, p, ln, tl = capi.load(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+    for rep in range(4):
+        t = time.perf_counter()
+        capi.check(lib.kr_batch_collect_text(st.h, C.byref(p), C.byref(ln)))
+        t_plain = time.perf_counter() - t
+        nbytes = ln.value
+        t = time.perf_counter()
+        capi.check(lib.kr_batch_collect_text_bgzf(st.h, C.byref(p), C.byref(ln), C.byref(tl)))
+        t_bgzf = time.perf_counter() - t
+        ms = st.bgzf_deflate_ms()
+        print(f"deflate, repetition {rep}: {nbytes / 1e6:.1f} MB of text from {nr} reads; plain copy back {t_plain * 1e3:.2f} ms "
+              f"({nbytes / t_plain / 1e9:.1f} GB/s); deflate + copy back of {ln.value / 1e6:.1f} MB ({ln.value / nbytes:.4f} of the text) "
+              f"{t_bgzf * 1e3:.2f} ms, of which the kernels {ms:.2f} ms ({nbytes / ms / 1e6:.1f} GB/s of text)", flush=True)
+    st.close(), dx.close(), hx.close()
+
 # ---- KR_TIME_CLI_TRACE=1: the default configuration once more under rocprofv3 --kernel-trace (the binary itself after `--`): the
 #      kernels of a CLI batch by name -- what the text kernels (kr_text_*) and the row compaction cost beside the rest
 if os.environ.get("KR_TIME_CLI_TRACE"):
     import collections, csv, glob, re, statistics
     td = os.path.join(work, "trace")
     env = dict(os.environ, TMPDIR="/tmp", GPU_MAX_HW_QUEUES="8", KR_CLI_CLEAN_EXIT="1")  # (the tool writes its files when the process exits in order)
+    exe = os.path.join(root, "krepp_amd", "lib", "krepp")
     r = subprocess.run(["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", td, "--", exe, "dist", "-i", idx, "-q", fq, "-o", out_file],
                        capture_output=True, text=True, env=env)
     d = collections.defaultdict(list)
