@@ -311,7 +311,8 @@ KR_API int kr_debug_indexed_list(kr_stream*, uint64_t* extent, uint64_t* fallbac
 /* Tests: crafted records through the production select and row kernels (tests/select_craft.py, tests/test_gpu_select_forms.py).
  * `kr_select_tables` is what the stages before the selection leave behind for one lane: the reads' record ranges, the records in key
  * order, and the values of the distinct likelihood problems, reached through the list (rec_rep = position) or through a direct place
- * (rec_rep = 0x80000000 | place, dd_direct[place] = position, dd_dv[place] = the value). */
+ * (rec_rep = 0x80000000 | place, dd_direct[place] = position, dd_dv[place] = the value).  What the likelihood stage guarantees of them
+ * is "The de-duplication's contract" in docs/design/05_likelihood_select_rows_text.md, tested through kr_debug_dedup below. */
 typedef struct kr_select_tables {
   uint32_t nreads, nrecs;       /* reads; record slots in use (slots between two reads' ranges belong to nobody) */
   const uint32_t* rd_off;       /* [nreads] ascending, the ranges [rd_off, rd_off + rd_cnt) disjoint and within nrecs */
@@ -362,6 +363,53 @@ KR_API int kr_debug_select_check(const kr_select_tables* in, uint32_t max_reads,
  * (KR_SELECT_GL), most records the big form keeps in registers (256), records per step of its second pass in memory (128), reads per
  * block of the row kernels (kRowBlock), reads the row kernel's workgroup takes per round (16)}. */
 KR_API int kr_debug_select_layout(uint32_t* out8);
+/* Tests: crafted records through the production likelihood de-duplication and minimisations (tests/dedup_craft.py,
+ * tests/test_gpu_dedup_routes.py): the stage that leaves behind what kr_select_tables takes as given -- rec_rep, the list of distinct
+ * problems, the direct places and their values; its contract is "The de-duplication's contract" in
+ * docs/design/05_likelihood_select_rows_text.md.  `kr_dedup_tables` is what the accumulate stage leaves for one lane. */
+typedef struct kr_dedup_tables {
+  uint32_t nreads, nrecs;       /* reads; record slots handed out (counters[kCtRecSlots]) */
+  const uint32_t* rd_off;       /* [nreads] ascending, the ranges [rd_off, rd_off + rd_cnt) disjoint and within nrecs */
+  const uint32_t* rd_cnt;       /* [nreads] */
+  const uint32_t* rd_onmers;    /* [nreads] k-mers of the read */
+  const uint32_t* rec_key;      /* [nrecs] se << 1 | strand, se below the index's node count; 0 (a hole) at every slot outside the reads' ranges and nowhere else */
+  const uint64_t* rec_w0;       /* [nrecs] the packed problem (hdist_th 4 only: counts in bits 0..39, the read's k-mers in 40..55, bit 63), or 0 */
+  const uint32_t* rec_hist;     /* [nrecs][hdist_th + 1] row-major, read for records with rec_w0 == 0; NULL if there is none */
+  const uint32_t* rec_read;     /* [nrecs] the record's read, likewise */
+} kr_dedup_tables;
+/* What the kernels wrote; every array is the caller's, any may be NULL.  rep_room, table_room and places_room are set by the caller: the
+ * entries its rep_list / rep_dv, the slots its dd_table and the places its dd_direct / dd_dv hold; everything below them is set by the call. */
+typedef struct kr_dedup_result {
+  uint32_t* rec_rep;    /* [nrecs] list position, 0x80000000 | direct place, or 0xFFFFFFFF for a hole */
+  uint32_t* rep_list;   /* [rep_room] the first rep_n entries: record index or 0xFFFFFFFF (hole) below `problems`, 0xA5 bytes beyond */
+  double* rep_dv;       /* [rep_room][2] (d, v) of the listed problems; 0xA5 bytes at holes and beyond `problems` */
+  uint32_t* dd_direct;  /* [places_room] list position of the place, 0xFFFFFFFF for a place no record names */
+  double* dd_dv;        /* [places_room][2] the named places' values; 0xA5 bytes elsewhere */
+  uint8_t* dd_oslot;    /* [256] k-mer count -> slot of the direct part, 0xFF none (untouched without a direct part) */
+  uint64_t* dd_table;   /* [table_room][2] the first table_n slots of the lane's table: word, leaf | (position + 1) << 32; slots above `mask`
+                         * are not this batch's (they hold what earlier batches left) */
+  uint32_t rep_room, table_room, places_room;
+  uint32_t rep_n, table_n;        /* entries copied: min(rep_room, rep_cap), min(table_room, dd_slots); of dd_direct / dd_dv: min(places_room, places) */
+  uint32_t problems, err;         /* counters[kCtProblems], counters[kCtErr] */
+  uint32_t rep_cap, places, dd_nodes, mask, dd_slots, dd_shift; /* the lane's list capacity, direct places (440 * dd_nodes), BatchOut::dd_nodes,
+                                                                 * this batch's table mask, the table's slots, KR_DD_SHIFT as the stream read it */
+} kr_dedup_result;
+/* Sets lane 0 of an idle one-lane stream up as kr_batch_submit(0) would, fills every output of the stage with 0xA5 bytes (rec_rep, rep_list
+ * and rep_dv up to the lane's capacity, dd_direct, dd_dv, dd_oslot; not the table), sets counters[kCtRecSlots] = nrecs and the other
+ * counters 0, uploads `in` and queues the launches of a batch's likelihood stage.  KR_ERR_ARG for tables the kernels could not be given
+ * safely, KR_ERR_STATE for a stream with a batch in flight or several lanes. */
+KR_API int kr_debug_dedup(kr_stream*, const kr_dedup_tables* in, kr_dedup_result* out);
+/* Tests (no device needed): the checks kr_debug_dedup makes of `in`, against limits given as numbers: reads and records the stream holds,
+ * nodes of the index (rho entries) and hdist_th.  KR_OK, or KR_ERR_ARG with the reason in kr_last_error(): read ranges that overlap or
+ * leave the records, a key beyond the nodes, a hole inside a read or a record outside every read, a packed word at another threshold,
+ * without bit 63 or with a k-mer count that is not its read's, a record without word and histogram, a rec_read naming another read. */
+KR_API int kr_debug_dedup_check(const kr_dedup_tables* in, uint32_t max_reads, uint64_t max_records, uint32_t nnodes, uint32_t hdist_th);
+/* Tests (no device needed): the constants of the de-duplication kernels: out12 = {k-mer-count slots of the direct part (kDdOslots),
+ * its classes (kDdClasses), most events of a direct problem (kDdMaxEvents), fewest table slots of a batch (kDdMinSlots), probe rounds
+ * (kDdProbeRounds), list positions a wave takes at a time and at most (kRepChunk, kRepChunkMax), blocks of kr_dedup_kernel
+ * (kDedupBlocks), reads per block of kr_dedup_oslot_kernel's grid (kDdOslotReads), low and high half of the word's hash multiplier
+ * (kDdHashWord), the leaf's multiplier (kDdHashLeaf)}. */
+KR_API int kr_debug_dedup_layout(uint32_t* out12);
 /* Tests: path witnesses of the accumulate kernel for the batch last waited for, counted only by a stream created under
  * KR_DEBUG_SKIP=512 (0 otherwise): the first min(n, 21) into `out`, in this order -- finalize_events_fast: calls, returned false before
  * the compaction, compaction entered, returned false after it, finish_big_read, finished in one key batch, in several, key batches

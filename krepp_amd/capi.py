@@ -137,6 +137,18 @@ class KrSelectResult(C.Structure):
                 ("nrows", C.c_uint64), ("rows_mode", C.c_uint32), ("rows_indexed", C.c_uint32), ("keep_v", C.c_uint32)]
 
 
+class KrDedupTables(C.Structure):
+    _fields_ = [("nreads", C.c_uint32), ("nrecs", C.c_uint32), ("rd_off", u32p), ("rd_cnt", u32p), ("rd_onmers", u32p),
+                ("rec_key", u32p), ("rec_w0", u64p), ("rec_hist", u32p), ("rec_read", u32p)]
+
+
+class KrDedupResult(C.Structure):
+    _fields_ = [("rec_rep", u32p), ("rep_list", u32p), ("rep_dv", f64p), ("dd_direct", u32p), ("dd_dv", f64p), ("dd_oslot", u8p),
+                ("dd_table", u64p), ("rep_room", C.c_uint32), ("table_room", C.c_uint32), ("places_room", C.c_uint32), ("rep_n", C.c_uint32), ("table_n", C.c_uint32),
+                ("problems", C.c_uint32), ("err", C.c_uint32), ("rep_cap", C.c_uint32), ("places", C.c_uint32), ("dd_nodes", C.c_uint32),
+                ("mask", C.c_uint32), ("dd_slots", C.c_uint32), ("dd_shift", C.c_uint32)]
+
+
 # every symbol include/krepp_amd.h declares (tests check that the library exports them all)
 EXPORTS = [
     "kr_host_index_load", "kr_host_sketch_load", "kr_format_seek", "kr_build_sketch", "kr_host_index_free", "kr_host_index_view", "kr_host_index_node_name",
@@ -148,7 +160,7 @@ EXPORTS = [
     "kr_debug_front_end", "kr_debug_stream_move", "kr_debug_stream_addrs", "kr_debug_item_placement", "kr_debug_brent", "kr_debug_prefix", "kr_debug_colour_classes", "kr_llh_batch", "kr_llh_eval_indexed", "kr_batch_timing",
     "kr_place_tree_create", "kr_place_tree_create_lineage", "kr_place_tree_nnodes", "kr_place_summary_add",
     "kr_place_summary_text", "kr_place_tree_free", "kr_place_tree_kinds", "kr_place_batch", "kr_place_stream", "kr_place_stream_parsed", "kr_debug_place_ids", "kr_place_frame", "kr_place_counters",
-    "kr_debug_last_d2h_bytes", "kr_debug_indexed_list", "kr_debug_select", "kr_debug_select_check", "kr_debug_select_layout", "kr_debug_acc_paths", "kr_debug_acc_layout", "kr_debug_scan_layout", "kr_debug_scan_stream", "kr_debug_place_fixed5", "kr_place_text_counters", "kr_place_path_counters", "kr_debug_place_layout", "kr_debug_place_paths", "kr_fastx_open", "kr_fastx_open_at", "kr_fastx_next", "kr_fastx_detach", "kr_fastx_release", "kr_fastx_close", "kr_fastx_parallel_chunks", "kr_fastx_pgz_stats", "kr_format_dist", "kr_debug_fixed5", "kr_free", "kr_host_alloc", "kr_host_free",
+    "kr_debug_last_d2h_bytes", "kr_debug_indexed_list", "kr_debug_select", "kr_debug_select_check", "kr_debug_select_layout", "kr_debug_dedup", "kr_debug_dedup_check", "kr_debug_dedup_layout", "kr_debug_acc_paths", "kr_debug_acc_layout", "kr_debug_scan_layout", "kr_debug_scan_stream", "kr_debug_place_fixed5", "kr_place_text_counters", "kr_place_path_counters", "kr_debug_place_layout", "kr_debug_place_paths", "kr_fastx_open", "kr_fastx_open_at", "kr_fastx_next", "kr_fastx_detach", "kr_fastx_release", "kr_fastx_close", "kr_fastx_parallel_chunks", "kr_fastx_pgz_stats", "kr_format_dist", "kr_debug_fixed5", "kr_free", "kr_host_alloc", "kr_host_free",
     "kr_build_index", "kr_minimizers_cpu", "kr_minimizers_device", "kr_minimizers_free", "kr_last_error", "kr_version",
     "kr_sdust_cpu", "kr_sdust_free",
     "kr_key_groups_cpu", "kr_key_groups_device", "kr_key_groups_free", "kr_debug_build_keys",
@@ -224,6 +236,9 @@ def load():
     lib.kr_debug_select.argtypes = [vp, C.POINTER(KrSelectTables), C.c_uint32, C.c_uint32, C.POINTER(KrSelectResult)]
     lib.kr_debug_select_check.argtypes = [C.POINTER(KrSelectTables), C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32]
     lib.kr_debug_select_layout.argtypes = [u32p]
+    lib.kr_debug_dedup.argtypes = [vp, C.POINTER(KrDedupTables), C.POINTER(KrDedupResult)]
+    lib.kr_debug_dedup_check.argtypes = [C.POINTER(KrDedupTables), C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32]
+    lib.kr_debug_dedup_layout.argtypes = [u32p]
     lib.kr_debug_acc_layout.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, u32p]
     lib.kr_index_slot_words.restype = C.c_uint32
     lib.kr_params_default.argtypes = [C.POINTER(KrParams)]
@@ -629,6 +644,34 @@ class Stream:
         out.update(nrows=int(r.nrows), rows_mode=int(r.rows_mode), rows_indexed=int(r.rows_indexed), keep_v=int(r.keep_v))
         return out
 
+    def debug_dedup(self, tables, places=0, rep_room=None, table_room=None):
+        """(tests) kr_debug_dedup: crafted records (a dict as dedup_tables takes it) through the likelihood de-duplication and the
+        minimisations of this idle one-lane stream; what they wrote, as a dict of numpy arrays and the numbers of kr_dedup_result.
+        places: the direct places the caller expects (dd_direct / dd_dv hold that many; the stream's own count comes back as
+        "places"); rep_list / rep_dv: the first rep_room entries, by default room for every record, a largest chunk per wave and 4,160
+        more, so that the poison behind the list shows; dd_table: [slots, 2], by default every slot a batch of this size can use"""
+        t, keep = dedup_tables(tables)
+        nrecs = t.nrecs
+        lay = dedup_layout()
+        if rep_room is None:
+            rep_room = nrecs + lay["rep_chunk_max"] * ((nrecs + 63) // 64) + 4096 + 64
+        if table_room is None:
+            table_room = lay["min_slots"]
+            while table_room < nrecs:
+                table_room *= 2
+        r = KrDedupResult()
+        r.rep_room, r.table_room, r.places_room = int(rep_room), int(table_room), int(places)
+        out = dict(rec_rep=np.full(nrecs, 0x5A5A5A5A, np.uint32), rep_list=np.full(rep_room, 0x5A5A5A5A, np.uint32),  # (0x5A: not copied back)
+                   rep_dv=np.full((rep_room, 2), np.nan), dd_direct=np.full(places, 0x5A5A5A5A, np.uint32), dd_dv=np.full((places, 2), np.nan),
+                   dd_oslot=np.full(256, 0x5A, np.uint8), dd_table=np.full((table_room, 2), 0x5A5A5A5A5A5A5A5A, np.uint64))
+        for k, a in out.items():
+            setattr(r, k, a.ctypes.data_as(dict(KrDedupResult._fields_)[k]) if a.size else None)
+        check(self.lib.kr_debug_dedup(self.h, C.byref(t), C.byref(r)))
+        out["rep_list"], out["rep_dv"], out["dd_table"] = out["rep_list"][:r.rep_n], out["rep_dv"][:r.rep_n], out["dd_table"][:r.table_n]
+        for k in ("problems", "err", "rep_cap", "places", "dd_nodes", "mask", "dd_slots", "dd_shift"):
+            out[k] = int(getattr(r, k))
+        return out
+
     def scan_info(self):
         """(tests) kr_debug_scan_stream: which scan kernel this stream launches, the item slots a lane's scan may use, and the item
         slots the batch last waited for asked for"""
@@ -954,6 +997,38 @@ def select_check(t, max_reads, max_records, nnodes, hdist_th=4, direct_nodes=0):
     """(tests, no device) kr_debug_select_check: the return code.  direct_nodes: the nodes the stream's direct part is laid out for"""
     s, keep = select_tables(t)
     return load().kr_debug_select_check(C.byref(s), int(max_reads), int(max_records), int(nnodes), int(hdist_th), int(direct_nodes))
+
+
+DEDUP_LAYOUT = ("oslots", "classes", "max_events", "min_slots", "probe_rounds", "rep_chunk", "rep_chunk_max", "dedup_blocks", "oslot_reads",
+                "hash_word_lo", "hash_word_hi", "hash_leaf")
+
+
+def dedup_layout():
+    """(tests) kr_debug_dedup_layout: the constants of the de-duplication kernels, by name; hash_word: the 64-bit multiplier"""
+    a = (C.c_uint32 * 12)()
+    check(load().kr_debug_dedup_layout(a))
+    d = dict(zip(DEDUP_LAYOUT, [int(x) for x in a]))
+    d["hash_word"] = d.pop("hash_word_hi") << 32 | d.pop("hash_word_lo")
+    return d
+
+
+def dedup_tables(t):
+    """KrDedupTables over the arrays of dict `t` (keys as the structure's fields; rec_hist [nrecs, th + 1] and rec_read optional, counts
+    taken from the arrays unless given); returns it with the arrays that must outlive it"""
+    spec = dict(rd_off=np.uint32, rd_cnt=np.uint32, rd_onmers=np.uint32, rec_key=np.uint32, rec_w0=np.uint64, rec_hist=np.uint32, rec_read=np.uint32)
+    keep = {k: np.ascontiguousarray(t[k], dtype=dt) for k, dt in spec.items() if t.get(k) is not None}
+    s = KrDedupTables()
+    for k, a in keep.items():
+        setattr(s, k, a.ctypes.data_as(dict(KrDedupTables._fields_)[k]) if a.size else None)
+    s.nreads = int(t.get("nreads", len(keep["rd_off"]) if "rd_off" in keep else 0))
+    s.nrecs = int(t.get("nrecs", len(keep["rec_key"]) if "rec_key" in keep else 0))
+    return s, keep
+
+
+def dedup_check(t, max_reads, max_records, nnodes, hdist_th=4):
+    """(tests, no device) kr_debug_dedup_check: the return code"""
+    s, keep = dedup_tables(t)
+    return load().kr_debug_dedup_check(C.byref(s), int(max_reads), int(max_records), int(nnodes), int(hdist_th))
 
 
 def seek_layout():

@@ -311,13 +311,18 @@ __device__ __forceinline__ uint32_t record_matches(const LlhConst& C, const Batc
 constexpr uint32_t kRepChunk = 16, kRepChunkMax = KR_REP_CHUNK;
 constexpr uint32_t kDedupBlocks = 4096;                      // grid of kr_dedup_kernel (256 threads a block)
 constexpr uint32_t kRepSlack = kDedupBlocks * 4u * kRepChunkMax; // list positions its waves may leave unused
+constexpr uint32_t kDdMinSlots = 1024;    // the fewest table slots a batch uses (dd_mask)
+constexpr int kDdProbeRounds = 48;        // rounds of kr_dedup_kernel's retry loop; a record still unresolved then stands alone
+constexpr uint32_t kDdOslotReads = 4096;  // reads per block of kr_dedup_oslot_kernel's grid (launch_likelihood)
+constexpr uint64_t kDdHashWord = 0x9E3779B97F4A7C15ull; // first slot = (word * kDdHashWord) >> 32 ^ leaf * kDdHashLeaf, masked
+constexpr uint32_t kDdHashLeaf = 0x85EBCA6Bu;
 #ifndef KR_DEDUP_PROBE16
 #define KR_DEDUP_PROBE16 1
 #endif
 __device__ __forceinline__ uint32_t dd_mask(const BatchOut& out)
 { // table slots used for this batch: a power of two >= (number of record slots) >> dd_shift, at most dd_slots
   const uint32_t n = min(out.counters[kCtRecSlots], out.rec_cap);
-  uint32_t m = 1024;
+  uint32_t m = kDdMinSlots;
   while (m < out.dd_slots && m < (n >> out.dd_shift)) m <<= 1;
   return m - 1u;
 }
@@ -443,11 +448,11 @@ __global__ __launch_bounds__(256) void kr_dedup_kernel(BatchOut out)
         }
       }
     }
-    uint32_t slot = (uint32_t)((w0 * 0x9E3779B97F4A7C15ull) >> 32) ^ (se * 0x85EBCA6Bu);
+    uint32_t slot = (uint32_t)((w0 * kDdHashWord) >> 32) ^ (se * kDdHashLeaf);
     // Retry loop without an inner spin: a lane that finds its histogram word in a slot whose second word is not
     // published yet simply comes round again (the publishing lane may be in this very wave).
     const uint64_t lt = (1ull << lane_id()) - 1ull;
-    for (int it = 0; it < 48 && __ballot(todo && !own) != 0; ++it) {
+    for (int it = 0; it < kDdProbeRounds && __ballot(todo && !own) != 0; ++it) {
       bool won = false;
       unsigned long long old = 1ull, w1p = 0ull;
       if (todo && !own) {

@@ -595,7 +595,7 @@ void launch_likelihood(kr_stream* s, Lane& L)
   const bool np5 = s->llh.th == 4, direct = np5 && o.dd_nodes; // (the direct-mapped part: five planes only)
   const uint32_t places = kDdOslots * kDdClasses * o.dd_nodes;
   hipLaunchKernelGGL(kr_dedup_clear_kernel, dim3(4096), dim3(256), 0, st, o);
-  if (o.dd_nodes) hipLaunchKernelGGL(kr_dedup_oslot_kernel, dim3(std::min<uint32_t>((L.nreads + 4095) / 4096, 1024u)), dim3(256), 0, st, o, L.nreads);
+  if (o.dd_nodes) hipLaunchKernelGGL(kr_dedup_oslot_kernel, dim3(std::min<uint32_t>((L.nreads + kDdOslotReads - 1u) / kDdOslotReads, 1024u)), dim3(256), 0, st, o, L.nreads);
   hipLaunchKernelGGL(kr_dedup_kernel, dim3(kDedupBlocks), dim3(256), 0, st, o);
   if (direct) hipLaunchKernelGGL(kr_dedup_direct_kernel, dim3(std::min<uint32_t>((places + 4095u) / 4096u, 4096u)), dim3(256), 0, st, o);
   with_bools([&](auto NP5) {
@@ -1919,6 +1919,140 @@ int kr_debug_select(kr_stream* s, const kr_select_tables* in, uint32_t flags, ui
     out->nrows = nrows;
   }
   HIP_TRY(back(out->rd_roff, o.rd_roff, (uint64_t)nreads * 4));
+  HIP_TRY(hipStreamSynchronize(st));
+  return KR_OK;
+}
+
+// (tests, no device needed) The constants the designs of tests/dedup_craft.py depend on, all of them the kernels' own names
+// (kr_dev_likelihood.inc): a changed table floor, probe limit, chunk or hash moves the designs or fails tests/test_dedup_craft_cpu.py.
+int kr_debug_dedup_layout(uint32_t* out12)
+{
+  kr::clear_error();
+  if (!out12) return kr::fail(KR_ERR_ARG, "kr_debug_dedup_layout: null argument");
+  out12[0] = kDdOslots, out12[1] = kDdClasses, out12[2] = kDdMaxEvents, out12[3] = kDdMinSlots, out12[4] = (uint32_t)kDdProbeRounds;
+  out12[5] = kRepChunk, out12[6] = kRepChunkMax, out12[7] = kDedupBlocks, out12[8] = kDdOslotReads;
+  out12[9] = (uint32_t)kDdHashWord, out12[10] = (uint32_t)(kDdHashWord >> 32), out12[11] = kDdHashLeaf;
+  return KR_OK;
+}
+
+// what kr_debug_dedup requires of its tables, given the limits of a stream (kr_debug_dedup_check: the same without one).  Every record
+// slot is looked at: kr_dedup_kernel walks the slots, not the reads, so a slot outside the reads' ranges must be a hole (key 0)
+static int dedup_check(const kr_dedup_tables* in, uint32_t max_reads, uint64_t max_records, uint32_t nnodes, uint32_t hdist_th)
+{
+  auto bad = [](const char* what) { return kr::fail(KR_ERR_ARG, std::string("kr_debug_dedup: ") + what); };
+  const uint32_t nreads = in->nreads, nrecs = in->nrecs;
+  if (nreads == 0 || nreads > max_reads) return bad("nreads out of range for this stream");
+  if (nrecs > max_records) return bad("more records than the stream's max_records");
+  if (!in->rd_off || !in->rd_cnt || !in->rd_onmers) return bad("null read table");
+  if (nrecs && (!in->rec_key || !in->rec_w0)) return bad("null record table");
+  if ((in->rec_hist == nullptr) != (in->rec_read == nullptr)) return bad("rec_hist and rec_read come together");
+  uint64_t end = 0;
+  for (uint32_t r = 0; r < nreads; ++r) {
+    const uint64_t o = in->rd_off[r], n = in->rd_cnt[r];
+    if (o < end || o + n > nrecs) return bad("read ranges overlap, descend or leave the records");
+    end = o + n;
+  }
+  end = 0;
+  for (uint32_t r = 0; r < nreads; ++r) {
+    const uint64_t o = in->rd_off[r], n = in->rd_cnt[r];
+    for (uint64_t i = end; i < o; ++i)
+      if (in->rec_key[i] != 0) return bad("record outside the reads' ranges");
+    end = o + n;
+    for (uint64_t i = o; i < o + n; ++i) {
+      const uint32_t key = in->rec_key[i];
+      const uint64_t w0 = in->rec_w0[i];
+      if (key == 0) return bad("hole (key 0) inside a read");
+      if ((key >> 1) >= nnodes) return bad("key beyond the index's nodes");
+      if (w0 != 0) {
+        if (hdist_th != 4) return bad("packed word at a threshold other than 4");
+        if (!(w0 >> 63)) return bad("packed word without bit 63");
+        if (((w0 >> 40) & 0xFFFFu) != in->rd_onmers[r]) return bad("packed word whose k-mer count is not its read's");
+      } else {
+        if (!in->rec_hist) return bad("record without a word and without a histogram");
+        if (in->rec_read[i] != r) return bad("rec_read names another read");
+      }
+    }
+  }
+  for (uint64_t i = end; i < nrecs; ++i)
+    if (in->rec_key[i] != 0) return bad("record outside the reads' ranges");
+  return KR_OK;
+}
+int kr_debug_dedup_check(const kr_dedup_tables* in, uint32_t max_reads, uint64_t max_records, uint32_t nnodes, uint32_t hdist_th)
+{
+  kr::clear_error();
+  if (!in) return kr::fail(KR_ERR_ARG, "kr_debug_dedup_check: null argument");
+  return dedup_check(in, max_reads, max_records, nnodes, hdist_th);
+}
+// (tests) Crafted records through the likelihood de-duplication and the minimisations as a one-lane batch would run them: the lane's
+// view is set_lane_view's, the launches are launch_likelihood's.  Everything the kernels may read is checked first: a table that passes
+// cannot send them outside the stream's buffers (keys index rho and, below dd_nodes, the direct part; rec_read indexes rd_onmers; the
+// k-mer count of a packed word indexes dd_oslot below 256 only; list positions are bounded by rep_cap in the kernels themselves).
+// The table is NOT poisoned: what an earlier batch of the stream left beyond this batch's mask stays there, for the kernels to ignore.
+int kr_debug_dedup(kr_stream* s, const kr_dedup_tables* in, kr_dedup_result* out)
+{
+  kr::clear_error();
+  if (!s || !in || !out) return kr::fail(KR_ERR_ARG, "kr_debug_dedup: null argument");
+  if (s->max_lanes != 1 || (s->batch.submitted && !s->batch.waited)) return kr::fail(KR_ERR_STATE, "kr_debug_dedup: needs an idle one-lane stream");
+  if (int rc = dedup_check(in, s->max_reads, std::min<uint64_t>(s->rec_user_cap, s->rec_cap), s->ix->dix.libs[0].nnodes, s->llh.th)) return rc;
+  const uint32_t nreads = in->nreads, nrecs = in->nrecs, np = s->dp.np;
+  HIP_TRY(hipSetDevice(s->device));
+  Lane& L = s->lanes[0];
+  hipStream_t st = L.stream;
+  begin_batch(s, nullptr, nullptr, nreads, 0, BatchOrigin{}, false); // (a crafted batch: neither tiled nor text, nothing to wait for)
+  set_lanes_and_row_modes(s, 1);
+  L.read0 = 0, L.nreads = nreads, L.rec_base = 0, L.rec_cap = s->rec_cap, L.nrecs = nrecs;
+  set_lane_view(s, L, 0, 0, 0, s->rec_cap, s->item_cap, s->item_cap, debug_list_caps());
+  BatchOut& o = L.out;
+  const uint64_t nr = nrecs, places = (uint64_t)kDdOslots * kDdClasses * o.dd_nodes, places4 = (places + 3) & ~3ull;
+  // ---- poison every output, then the tables
+  if (nr) HIP_TRY(hipMemsetAsync(o.rec_rep, 0xA5, nr * 4, st));
+  HIP_TRY(hipMemsetAsync(o.rep_list, 0xA5, (uint64_t)o.rep_cap * 4, st));
+  HIP_TRY(hipMemsetAsync(o.rep_dv, 0xA5, (uint64_t)o.rep_cap * 16, st));
+  if (o.dd_nodes) {
+    HIP_TRY(hipMemsetAsync(o.dd_direct, 0xA5, places4 * 4, st));
+    HIP_TRY(hipMemsetAsync(o.dd_dv, 0xA5, places4 * 16, st));
+    HIP_TRY(hipMemsetAsync(o.dd_ohist, 0xA5, 260 * 4, st));
+    HIP_TRY(hipMemsetAsync(o.dd_oslot, 0xA5, 256, st));
+  }
+  HIP_TRY(hipMemsetAsync(o.counters, 0, kCounterWords * 4, st));
+  HIP_TRY(hipMemcpyAsync(o.counters + kCtRecSlots, &in->nrecs, 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(o.rd_off, in->rd_off, (uint64_t)nreads * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(o.rd_cnt, in->rd_cnt, (uint64_t)nreads * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(o.rd_onmers, in->rd_onmers, (uint64_t)nreads * 4, hipMemcpyHostToDevice, st));
+  std::vector<uint32_t> planes;
+  if (nr) {
+    HIP_TRY(hipMemcpyAsync(o.rec_key, in->rec_key, nr * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(o.rec_w0, in->rec_w0, nr * 8, hipMemcpyHostToDevice, st));
+    if (in->rec_hist) {
+      planes.resize(nr * np);
+      for (uint64_t i = 0; i < nr; ++i)
+        for (uint32_t x = 0; x < np; ++x) planes[x * nr + i] = in->rec_hist[i * np + x];
+      for (uint32_t x = 0; x < np; ++x) HIP_TRY(hipMemcpyAsync(o.rec_hist + x * o.rec_stride, planes.data() + x * nr, nr * 4, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(o.rec_read, in->rec_read, nr * 4, hipMemcpyHostToDevice, st));
+    }
+  }
+  // ---- the stage
+  launch_likelihood(s, L);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(L.h_counters, o.counters, kCounterWords * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st)); // (the uploads above come from pageable memory: `planes` may go only now)
+  const uint32_t problems = L.h_counters[kCtProblems];
+  uint32_t mask = kDdMinSlots; // dd_mask, on the host
+  while (mask < o.dd_slots && mask < (std::min(nrecs, o.rec_cap) >> o.dd_shift)) mask <<= 1;
+  mask -= 1u;
+  out->problems = problems, out->err = L.h_counters[kCtErr], out->rep_cap = o.rep_cap;
+  out->places = (uint32_t)places, out->dd_nodes = o.dd_nodes, out->mask = mask, out->dd_slots = o.dd_slots, out->dd_shift = o.dd_shift;
+  const uint64_t nlist = std::min<uint64_t>(out->rep_room, o.rep_cap), ntab = std::min<uint64_t>(out->table_room, o.dd_slots);
+  out->rep_n = (uint32_t)nlist, out->table_n = (uint32_t)ntab;
+  auto back = [&](void* dst, const void* src, uint64_t bytes) -> hipError_t { return (dst && src && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) : hipSuccess; };
+  HIP_TRY(back(out->rec_rep, o.rec_rep, nr * 4));
+  HIP_TRY(back(out->rep_list, o.rep_list, nlist * 4));
+  HIP_TRY(back(out->rep_dv, o.rep_dv, nlist * 16));
+  const uint64_t npl = std::min<uint64_t>(out->places_room, places);
+  HIP_TRY(back(out->dd_direct, o.dd_direct, npl * 4));
+  HIP_TRY(back(out->dd_dv, o.dd_dv, npl * 16));
+  HIP_TRY(back(out->dd_oslot, o.dd_nodes ? o.dd_oslot : nullptr, 256));
+  HIP_TRY(back(out->dd_table, o.dd_table, ntab * 16));
   HIP_TRY(hipStreamSynchronize(st));
   return KR_OK;
 }
