@@ -739,7 +739,22 @@ KR_API int kr_fastx_open_at_bgzf(const char* path, uint64_t member_off, uint32_t
  *   kr_debug_bgzf_deflate   (tests) any host bytes through the kernels: out[0 .. cap) receives the members (KR_ERR_CAPACITY: more
  *                           than cap).  Not while a batch is in flight on the stream's first lane (it is waited for)
  *   kr_debug_bgzf_deflate_ms    (measurements) device time (ms) of the deflate, scan and copy kernels of the stream's last deflate;
- *                           -1 before the first */
+ *                           -1 before the first
+ * Levels.  Level 1 is the encoder above and the default of every call without a level.  Level 2 codes the SAME tokens in a
+ * second pass under dynamic Huffman codes built from the member's own counts (BTYPE 10), and keeps level 1's fixed-code or stored
+ * block -- the same bytes -- for a member that those make smaller: a level-2 member is never larger than the level-1 member.
+ *   kr_bgzf_deflate_host_level     kr_bgzf_deflate_host at a level; KR_ERR_ARG for a level other than 1 or 2
+ *   kr_stream_bgzf_out_level       the level of the stream's later kr_batch_collect_text_bgzf and kr_debug_bgzf_deflate calls; after
+ *                           kr_stream_bgzf_out_enable (before it: KR_ERR_STATE); KR_ERR_ARG for a level other than 1 or 2, the
+ *                           level in force stays.  Level 2 takes a token buffer of 4 bytes per byte of max_text_bytes, made by
+ *                           the first call that asks for it.  The level may change between batches
+ *   kr_debug_bgzf_deflate_stats_level  (tests) kr_debug_bgzf_deflate_stats at a level: stats[10] = the six figures, then members
+ *                           coded with fixed codes, members coded with dynamic codes, members for which one of the three codes
+ *                           had to be limited (15 / 15 / 7 bits), dynamic header bits in total
+ *   kr_debug_huffman_lengths       (tests) the level-2 code-length builder on the host: lens[0 .. nsym) for the counts
+ *                           freq[0 .. nsym) with no code longer than maxbits, *limited = 1 when the limit was needed.  1 <= nsym
+ *                           <= 286, 1 <= maxbits <= 15, counts below 2^22, at most 2^maxbits of them non-zero (else KR_ERR_ARG)
+ *   kr_debug_huffman_lengths_device  (tests) the same through a kernel of one wave on the stream's device */
 KR_API uint64_t kr_bgzf_deflate_bound(uint64_t n);
 KR_API int kr_bgzf_deflate_host(const uint8_t* text, uint64_t n, uint8_t* out, uint64_t cap, uint64_t* len);
 KR_API void kr_bgzf_eof(uint8_t* out28);
@@ -748,6 +763,11 @@ KR_API int kr_stream_bgzf_out_enable(kr_stream*);
 KR_API int kr_batch_collect_text_bgzf(kr_stream*, const uint8_t** comp, uint64_t* len, uint64_t* text_len);
 KR_API int kr_debug_bgzf_deflate(kr_stream*, const uint8_t* bytes, uint64_t n, uint8_t* out, uint64_t cap, uint64_t* len);
 KR_API int kr_debug_bgzf_deflate_ms(kr_stream*, float* ms);
+KR_API int kr_bgzf_deflate_host_level(const uint8_t* text, uint64_t n, uint32_t level, uint8_t* out, uint64_t cap, uint64_t* len);
+KR_API int kr_stream_bgzf_out_level(kr_stream*, uint32_t level);
+KR_API int kr_debug_bgzf_deflate_stats_level(const uint8_t* text, uint64_t n, uint32_t level, uint64_t* stats);
+KR_API int kr_debug_huffman_lengths(const uint32_t* freq, uint32_t nsym, uint32_t maxbits, uint8_t* lens, uint32_t* limited);
+KR_API int kr_debug_huffman_lengths_device(kr_stream*, const uint32_t* freq, uint32_t nsym, uint32_t maxbits, uint8_t* lens, uint32_t* limited);
 
 /* ---- `seek` on kernels of its own (csrc/kr_dev_seek.inc; docs/design/13_seek.md; INTEGRATION.md "A seek batch") ----
  * SBatch::seek_sequences (src/seek.cpp:22-126) on a SKETCH index (kr_host_sketch_load): per k-mer and strand the minimum Hamming

@@ -172,6 +172,8 @@ EXPORTS = [
     "kr_bgzf_member_size", "kr_bgzf_walk", "kr_bgzf_chunk_cut", "kr_fastx_open_at_bgzf",
     "kr_bgzf_deflate_bound", "kr_bgzf_deflate_host", "kr_bgzf_eof", "kr_debug_bgzf_deflate_stats",
     "kr_stream_bgzf_out_enable", "kr_batch_collect_text_bgzf", "kr_debug_bgzf_deflate", "kr_debug_bgzf_deflate_ms",
+    "kr_bgzf_deflate_host_level", "kr_stream_bgzf_out_level", "kr_debug_bgzf_deflate_stats_level", "kr_debug_huffman_lengths",
+    "kr_debug_huffman_lengths_device",
 ]
 
 # kr_debug_acc_paths: the accumulate kernel's path witnesses, in the order of CounterSlot (kr_dev_common.inc)
@@ -316,6 +318,11 @@ def load():
     lib.kr_batch_collect_text_bgzf.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.kr_debug_bgzf_deflate.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.kr_debug_bgzf_deflate_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    lib.kr_bgzf_deflate_host_level.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+    lib.kr_stream_bgzf_out_level.argtypes = [vp, C.c_uint32]
+    lib.kr_debug_bgzf_deflate_stats_level.argtypes = [vp, C.c_uint64, C.c_uint32, u64p]
+    lib.kr_debug_huffman_lengths.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.POINTER(C.c_uint32)]
+    lib.kr_debug_huffman_lengths_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, C.POINTER(C.c_uint32)]
     lib.kr_debug_tile_layout.argtypes = [vp, u32p, u32p, vp, vp, vp, vp, vp]
     lib.kr_stream_seek_enable.argtypes = [vp, C.c_uint64, C.c_uint64]
     lib.kr_batch_collect_seek.argtypes = [vp, C.POINTER(KrSeekView)]
@@ -889,21 +896,33 @@ class Stream:
         BGZF members deflated on the device (csrc/kr_dev_deflate.inc)"""
         check(self.lib.kr_stream_bgzf_out_enable(self.h))
 
-    def collect_text_bgzf(self):
-        """kr_batch_collect_text_bgzf: (the batch's report text as BGZF members, the bytes they inflate to)"""
+    def bgzf_out_level(self, level):
+        """kr_stream_bgzf_out_level: the level of this stream's later collect_text_bgzf / bgzf_deflate (1: fixed codes, 2: dynamic)"""
+        check(self.lib.kr_stream_bgzf_out_level(self.h, int(level)))
+
+    def collect_text_bgzf(self, level=None):
+        """kr_batch_collect_text_bgzf: (the batch's report text as BGZF members, the bytes they inflate to); level: bgzf_out_level first"""
+        if level is not None:
+            self.bgzf_out_level(level)
         comp = C.c_void_p()
         ln, tl = C.c_uint64(), C.c_uint64()
         check(self.lib.kr_batch_collect_text_bgzf(self.h, C.byref(comp), C.byref(ln), C.byref(tl)))
         return (C.string_at(comp, ln.value) if ln.value else b""), int(tl.value)
 
-    def bgzf_deflate(self, data, cap=None):
-        """(tests) kr_debug_bgzf_deflate: any bytes through the deflate kernels, the members back"""
+    def bgzf_deflate(self, data, cap=None, level=None):
+        """(tests) kr_debug_bgzf_deflate: any bytes through the deflate kernels, the members back; level: bgzf_out_level first"""
+        if level is not None:
+            self.bgzf_out_level(level)
         data = bytes(data)
         cap = bgzf_deflate_bound(len(data)) if cap is None else int(cap)
         out = np.zeros(max(1, cap), np.uint8)
         n = C.c_uint64(0)
         check(self.lib.kr_debug_bgzf_deflate(self.h, data, len(data), out.ctypes.data, cap, C.byref(n)))
         return out[: n.value].tobytes()
+
+    def huffman_lengths(self, freq, maxbits, level=2):
+        """(tests) kr_debug_huffman_lengths_device: as capi.huffman_lengths, through the builder kernel on this stream's device"""
+        return _huffman_lengths(lambda *a: self.lib.kr_debug_huffman_lengths_device(self.h, *a), freq, maxbits, level)
 
     def bgzf_deflate_ms(self):
         """(measurements) kr_debug_bgzf_deflate_ms: device time of the last deflate's kernels, -1 before the first measured one"""
@@ -1084,6 +1103,7 @@ def bgzf_walk(buf, max_inflated):
 
 
 BGZF_DEFLATE_STATS = ("members", "stored", "literals", "matches", "longest", "farthest")
+BGZF_DEFLATE_STATS_LEVEL = BGZF_DEFLATE_STATS + ("fixed", "dynamic", "limited", "header_bits")
 
 
 def bgzf_deflate_bound(n):
@@ -1091,13 +1111,17 @@ def bgzf_deflate_bound(n):
     return int(load().kr_bgzf_deflate_bound(int(n)))
 
 
-def bgzf_deflate_host(text, cap=None):
-    """kr_bgzf_deflate_host: `text` as BGZF members of 65,280 input bytes each (no device, no end member)"""
+def bgzf_deflate_host(text, cap=None, level=None):
+    """kr_bgzf_deflate_host: `text` as BGZF members of 65,280 input bytes each (no device, no end member); with a level:
+    kr_bgzf_deflate_host_level (1: fixed codes, 2: dynamic codes)"""
     text = bytes(text)
     cap = bgzf_deflate_bound(len(text)) if cap is None else int(cap)
     out = np.zeros(max(1, cap), np.uint8)
     n = C.c_uint64(0)
-    check(load().kr_bgzf_deflate_host(text, len(text), out.ctypes.data, cap, C.byref(n)))
+    if level is None:
+        check(load().kr_bgzf_deflate_host(text, len(text), out.ctypes.data, cap, C.byref(n)))
+    else:
+        check(load().kr_bgzf_deflate_host_level(text, len(text), int(level), out.ctypes.data, cap, C.byref(n)))
     return out[: n.value].tobytes()
 
 
@@ -1108,12 +1132,33 @@ def bgzf_eof():
     return out.raw
 
 
-def bgzf_deflate_stats(text):
-    """(tests) kr_debug_bgzf_deflate_stats: what the host form did with `text`, as a dict of BGZF_DEFLATE_STATS"""
+def bgzf_deflate_stats(text, level=None):
+    """(tests) kr_debug_bgzf_deflate_stats: what the host form did with `text`, as a dict of BGZF_DEFLATE_STATS; with a level:
+    kr_debug_bgzf_deflate_stats_level, a dict of BGZF_DEFLATE_STATS_LEVEL"""
     text = bytes(text)
-    st = (C.c_uint64 * 6)()
-    check(load().kr_debug_bgzf_deflate_stats(text, len(text), st))
-    return dict(zip(BGZF_DEFLATE_STATS, [int(x) for x in st]))
+    if level is None:
+        st = (C.c_uint64 * 6)()
+        check(load().kr_debug_bgzf_deflate_stats(text, len(text), st))
+        return dict(zip(BGZF_DEFLATE_STATS, [int(x) for x in st]))
+    st = (C.c_uint64 * 10)()
+    check(load().kr_debug_bgzf_deflate_stats_level(text, len(text), int(level), st))
+    return dict(zip(BGZF_DEFLATE_STATS_LEVEL, [int(x) for x in st]))
+
+
+def _huffman_lengths(call, freq, maxbits, level):
+    if int(level) != 2:
+        raise ValueError("the code-length builder belongs to level 2")
+    freq = np.ascontiguousarray(freq, dtype=np.uint32)
+    lens = np.zeros(max(1, len(freq)), np.uint8)
+    limited = C.c_uint32(0)
+    check(call(freq.ctypes.data, len(freq), int(maxbits), lens.ctypes.data, C.byref(limited)))
+    return lens[: len(freq)].copy(), bool(limited.value)
+
+
+def huffman_lengths(freq, maxbits, level=2):
+    """(tests) kr_debug_huffman_lengths: (code lengths for the counts `freq` with none longer than maxbits, whether the limit was
+    needed), from the level-2 encoder's builder on the host"""
+    return _huffman_lengths(load().kr_debug_huffman_lengths, freq, maxbits, level)
 
 
 def bgzf_chunk_cut(buf, skip=0, fasta=False):

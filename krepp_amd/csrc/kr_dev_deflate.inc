@@ -1,16 +1,20 @@
 // kr_dev_deflate.inc -- part of kr_device.hip (device side): report text deflated into BGZF members where it was written
-// (kr_batch_collect_text_bgzf, kr_debug_bgzf_deflate; kr_host_deflate.inc).  Three kernels:
+// (kr_batch_collect_text_bgzf, kr_debug_bgzf_deflate; kr_host_deflate.inc).  The kernels:
 //   kr_bgzf_deflate_kernel   one wave per member of 65,280 text bytes, four waves a workgroup, the grid sized from the member count.
 //                            The encoder is kr_deflate.h's deflate_member, the code the host runs serially, and gives the same bytes:
 //                            a lane owns one position of every tile of 64 (lookup, verify, enter, its token's bits), the parse is the
 //                            same walk in every lane; head table, match lengths and the bit window live in LDS (8.7 KB a wave: four
 //                            workgroups a CU).  Member m goes to slot m (stride kDefSlot), one lane writes its size.
+//   kr_bgzf_deflate_dyn_kernel   the same launch at level 2 (kr_stream_bgzf_out_level): kr_deflate.h's deflate_member_dyn, the tokens
+//                            of pass 1 in a global list (kDefTokStride a member), the codes built by lane 0 between the passes,
+//                            a lane per token in pass 2; 10.1 KB of LDS a wave: three workgroups a CU
+//   kr_huffman_lengths_kernel    (tests) the code-length builder alone, one wave
 //   kr_bgzf_deflate_scan_kernel   ONE workgroup of 1024: the sizes become the members' positions (scan_block_sums, kr_dev_prefix.inc:
 //                            a member is a "block"), the total behind them
 //   kr_bgzf_deflate_copy_kernel   a workgroup per member: its slot's bytes to its position, in words aligned to the destination
 //
 // Bounds (the host sized the buffers, deflate_reserve): text[0 .. n); nmembers = ceil(n / 65,280) slots; off[nmembers + 1]; the
-// output holds n + 31 * nmembers bytes.  deflate_member never reads outside its member's input nor writes outside [slot, slot +
+// output holds n + 31 * nmembers bytes; at level 2, nmembers * kDefTokStride tokens.  deflate_member (and _dyn) never reads outside its member's input nor writes outside [slot, slot +
 // len + 31), whatever the bytes are, and len + 31 <= kDefSlot.  The kernels keep scalars and statically sized LDS only.
 
 struct DeflateIO {
@@ -22,13 +26,16 @@ struct DeflateIO {
   uint8_t* out;    // [n + 31 * nmembers]
 };
 
-struct DefWave {
+// (a type per level: each kernel has lanes of its own, so that what the compiler makes of one does not depend on the other)
+template <int LEVEL>
+struct DefWaveT {
   uint32_t l, total;
   __device__ uint32_t lane() const { return l; }
   __device__ uint32_t nlanes() const { return 64; }
   __device__ void sync() const { WAVE_SYNC(); } // (what other lanes of this wave wrote is read behind this: InfWave::sync)
   __device__ void head_max(uint32_t* p, uint32_t v) const { __hip_atomic_fetch_max((lds_u32*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
   __device__ void or_bits(uint32_t* p, uint32_t v) const { lds_or((lds_u32*)p, v); }
+  __device__ void add(uint32_t* p, uint32_t v) const { __hip_atomic_fetch_add((lds_u32*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
   __device__ void scan_begin() {}
   __device__ uint32_t scan_excl(uint32_t v) // every lane of the wave calls it once a tile
   {
@@ -52,6 +59,7 @@ struct DefWave {
     return ~(kr::crc_mulmod(kr::crc_xpow8(n), 0xFFFFFFFFu) ^ __shfl(part, 0));
   }
 };
+typedef DefWaveT<1> DefWave;
 
 __global__ __launch_bounds__(256) void kr_bgzf_deflate_kernel(DeflateIO io)
 {
@@ -68,6 +76,40 @@ __global__ __launch_bounds__(256) void kr_bgzf_deflate_kernel(DeflateIO io)
   L.l = lane, L.total = 0;
   const uint32_t size = kr::deflate_member(io.text + a, len, io.slots + (uint64_t)m * kr::kDefSlot, state[wave], crc_tab, L);
   if (lane == 0) io.off[m] = size;
+}
+
+// Level 2 (dynamic codes): the same launch; member m's tokens lie in tokens[m * kDefTokStride ..), written in pass 1 and read in
+// pass 2 by the same wave (a wave's memory instructions execute in order: DefWave::sync).  10,128 bytes of LDS a wave.
+__global__ __launch_bounds__(256) void kr_bgzf_deflate_dyn_kernel(DeflateIO io, uint32_t* tokens)
+{
+  __shared__ kr::DefDynState state[4];
+  __shared__ uint32_t crc_tab[256];
+  crc_tab[threadIdx.x] = kr::crc_table_entry(threadIdx.x);
+  __syncthreads(); // (the only workgroup barrier: every wave passes it before any leaves)
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint32_t m = blockIdx.x * 4u + wave;
+  if (m >= io.nmembers) return;
+  const uint64_t a = (uint64_t)m * kr::kDefMemberIn;
+  const uint32_t len = (uint32_t)std::min<uint64_t>(io.n - a, kr::kDefMemberIn);
+  DefWaveT<2> L;
+  L.l = lane, L.total = 0;
+  const uint32_t size = kr::deflate_member_dyn(io.text + a, len, io.slots + (uint64_t)m * kr::kDefSlot, tokens + (uint64_t)m * kr::kDefTokStride,
+                                               state[wave], crc_tab, L);
+  if (lane == 0) io.off[m] = size;
+}
+
+// (tests) def_build_lengths as the level-2 kernel's lane 0 runs it: one wave, the counts and the scratch in LDS
+__global__ __launch_bounds__(64) void kr_huffman_lengths_kernel(const uint32_t* freq, uint32_t nsym, uint32_t maxbits, uint8_t* lens, uint32_t* limited)
+{
+  __shared__ kr::DefBuild build;
+  __shared__ uint32_t cnt[kr::kDefLL];
+  __shared__ uint8_t out[kr::kDefLL];
+  if (nsym > kr::kDefLL) return; // (the host checked)
+  for (uint32_t i = threadIdx.x; i < nsym; i += 64u) cnt[i] = freq[i];
+  WAVE_SYNC();
+  if (threadIdx.x == 0) *limited = kr::def_build_lengths(cnt, nsym, maxbits, out, build) ? 1u : 0u;
+  WAVE_SYNC();
+  for (uint32_t i = threadIdx.x; i < nsym; i += 64u) lens[i] = out[i];
 }
 
 __global__ __launch_bounds__(1024) void kr_bgzf_deflate_scan_kernel(uint64_t* off, uint32_t nmembers)

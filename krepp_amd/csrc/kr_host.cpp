@@ -1624,45 +1624,85 @@ void kr_bgzf_eof(uint8_t* out28)
 
 // Every member into a slot of its own (the members' sizes are known only afterwards), on the thread pool in runs of members; then
 // the slots back to back.  A member's bytes depend on its input alone: neither on the thread that wrote it nor on how many there are.
-static int bgzf_deflate_slots(const uint8_t* text, uint64_t n, std::vector<uint8_t>& slots, std::vector<uint32_t>& sizes, kr::DefStats* st)
+static int bgzf_deflate_slots(const uint8_t* text, uint64_t n, uint32_t level, std::vector<uint8_t>& slots, std::vector<uint32_t>& sizes, kr::DefStats* st)
 {
   const uint64_t nm = kr::bgzf_deflate_members(n);
   slots.resize(nm * kr::kDefSlot), sizes.resize(nm);
   const int nt = (int)std::max<uint64_t>(1, std::min<uint64_t>(st ? 1 : kr::parallel_width(), nm / 4)); // (stats: one thread, one counter)
   kr::parallel_for(nt, [&](int t) {
+    const uint64_t m0 = nm * (uint64_t)t / nt, m1 = nm * (uint64_t)(t + 1) / nt;
+    if (level == 2) { // dynamic codes: the member's token list between the two passes
+      std::unique_ptr<kr::DefDynState> S(new kr::DefDynState);
+      std::vector<uint32_t> tok(kr::kDefTokStride);
+      for (uint64_t m = m0; m < m1; ++m) sizes[m] = kr::bgzf_deflate_member_host_dyn(text, n, m, slots.data() + m * kr::kDefSlot, *S, tok.data(), st);
+      return;
+    }
     std::unique_ptr<kr::DefState> S(new kr::DefState);
-    for (uint64_t m = nm * (uint64_t)t / nt; m < nm * (uint64_t)(t + 1) / nt; ++m)
-      sizes[m] = kr::bgzf_deflate_member_host(text, n, m, slots.data() + m * kr::kDefSlot, *S, st);
+    for (uint64_t m = m0; m < m1; ++m) sizes[m] = kr::bgzf_deflate_member_host(text, n, m, slots.data() + m * kr::kDefSlot, *S, st);
   });
   return KR_OK;
 }
 
-int kr_bgzf_deflate_host(const uint8_t* text, uint64_t n, uint8_t* out, uint64_t cap, uint64_t* len)
+static int bgzf_deflate_host_at(const char* who, const uint8_t* text, uint64_t n, uint32_t level, uint8_t* out, uint64_t cap, uint64_t* len)
 {
   kr::clear_error();
-  if (!len || (n && !text) || (cap && !out)) return kr::fail(KR_ERR_ARG, "kr_bgzf_deflate_host: null argument");
+  if (!len || (n && !text) || (cap && !out)) return kr::fail(KR_ERR_ARG, std::string(who) + ": null argument");
   *len = 0;
+  if (level != 1 && level != 2) return kr::fail(KR_ERR_ARG, std::string(who) + ": level " + std::to_string(level) + " (1: fixed codes, 2: dynamic codes)");
   std::vector<uint8_t> slots;
   std::vector<uint32_t> sizes;
-  bgzf_deflate_slots(text, n, slots, sizes, nullptr);
+  bgzf_deflate_slots(text, n, level, slots, sizes, nullptr);
   uint64_t total = 0;
   for (uint32_t sz : sizes) total += sz;
-  if (total > cap) return kr::fail(KR_ERR_CAPACITY, "kr_bgzf_deflate_host: the members take " + std::to_string(total) + " bytes, the buffer holds " + std::to_string(cap));
+  if (total > cap) return kr::fail(KR_ERR_CAPACITY, std::string(who) + ": the members take " + std::to_string(total) + " bytes, the buffer holds " + std::to_string(cap));
   uint64_t off = 0;
   for (size_t m = 0; m < sizes.size(); ++m) memcpy(out + off, slots.data() + m * kr::kDefSlot, sizes[m]), off += sizes[m];
   *len = total;
   return KR_OK;
 }
 
-int kr_debug_bgzf_deflate_stats(const uint8_t* text, uint64_t n, uint64_t* stats)
+int kr_bgzf_deflate_host(const uint8_t* text, uint64_t n, uint8_t* out, uint64_t cap, uint64_t* len)
+{
+  return bgzf_deflate_host_at("kr_bgzf_deflate_host", text, n, 1, out, cap, len);
+}
+
+int kr_bgzf_deflate_host_level(const uint8_t* text, uint64_t n, uint32_t level, uint8_t* out, uint64_t cap, uint64_t* len)
+{
+  return bgzf_deflate_host_at("kr_bgzf_deflate_host_level", text, n, level, out, cap, len);
+}
+
+int kr_debug_bgzf_deflate_stats_level(const uint8_t* text, uint64_t n, uint32_t level, uint64_t* stats)
 {
   kr::clear_error();
-  if (!stats || (n && !text)) return kr::fail(KR_ERR_ARG, "kr_debug_bgzf_deflate_stats: null argument");
+  if (!stats || (n && !text)) return kr::fail(KR_ERR_ARG, "kr_debug_bgzf_deflate_stats_level: null argument");
+  if (level != 1 && level != 2) return kr::fail(KR_ERR_ARG, "kr_debug_bgzf_deflate_stats_level: level " + std::to_string(level) + " (1: fixed codes, 2: dynamic codes)");
   std::vector<uint8_t> slots;
   std::vector<uint32_t> sizes;
   kr::DefStats st;
-  bgzf_deflate_slots(text, n, slots, sizes, &st);
+  bgzf_deflate_slots(text, n, level, slots, sizes, &st);
   stats[0] = st.members, stats[1] = st.stored, stats[2] = st.literals, stats[3] = st.matches, stats[4] = st.longest, stats[5] = st.farthest;
+  stats[6] = st.fixed, stats[7] = st.dynamic, stats[8] = st.limited, stats[9] = st.header_bits;
+  return KR_OK;
+}
+
+int kr_debug_bgzf_deflate_stats(const uint8_t* text, uint64_t n, uint64_t* stats)
+{
+  uint64_t all[10];
+  if (!stats) return kr::fail(KR_ERR_ARG, "kr_debug_bgzf_deflate_stats: null argument");
+  if (int rc = kr_debug_bgzf_deflate_stats_level(text, n, 1, all)) return rc;
+  for (int i = 0; i < 6; ++i) stats[i] = all[i];
+  return KR_OK;
+}
+
+// (tests) the code-length builder of the encoder's level 2 (kr_deflate.h's def_build_lengths) on the host
+int kr_debug_huffman_lengths(const uint32_t* freq, uint32_t nsym, uint32_t maxbits, uint8_t* lens, uint32_t* limited)
+{
+  kr::clear_error();
+  if (!freq || !lens || !limited) return kr::fail(KR_ERR_ARG, "kr_debug_huffman_lengths: null argument");
+  if (!kr::def_build_args_ok(freq, nsym, maxbits))
+    return kr::fail(KR_ERR_ARG, "kr_debug_huffman_lengths: 1 to 286 symbols, 1 to 15 bits with room for every counted symbol, counts below 2^22");
+  std::unique_ptr<kr::DefBuild> B(new kr::DefBuild);
+  *limited = kr::def_build_lengths(freq, nsym, maxbits, lens, *B) ? 1u : 0u;
   return KR_OK;
 }
 

@@ -1,5 +1,5 @@
-// kr_host_deflate.inc -- part of kr_device.hip (host side): kr_stream_bgzf_out_enable, kr_batch_collect_text_bgzf,
-// kr_debug_bgzf_deflate, kr_debug_bgzf_deflate_ms.  Report text that lies in device memory is deflated into BGZF members there
+// kr_host_deflate.inc -- part of kr_device.hip (host side): kr_stream_bgzf_out_enable, kr_stream_bgzf_out_level,
+// kr_batch_collect_text_bgzf, kr_debug_bgzf_deflate, kr_debug_bgzf_deflate_ms, kr_debug_huffman_lengths_device.  Report text that lies in device memory is deflated into BGZF members there
 // (kernels: kr_dev_deflate.inc, encoder: kr_deflate.h) and only the members cross to the host.
 
 namespace {
@@ -11,6 +11,7 @@ int deflate_reserve(kr_stream* s, uint64_t n)
   const uint64_t nm = kr::bgzf_deflate_members(n);
   if (!o.d_slots.reserve(nm * kr::kDefSlot) || !o.d_off.reserve(nm + 1) || !o.d_out.reserve(kr::bgzf_deflate_bound(n)) || !o.h_total.reserve(1))
     return alloc_failed("bgzf out: device buffers");
+  if (o.level == 2 && !o.d_tokens.reserve(nm * kr::kDefTokStride)) return alloc_failed("bgzf out: the token buffer of level 2");
   return KR_OK;
 }
 
@@ -22,7 +23,8 @@ int deflate_run(kr_stream* s, hipStream_t st, const uint8_t* d_text, uint64_t n,
   if (nm >= (1ull << 31)) return kr::fail(KR_ERR_ARG, "bgzf out: too many members");
   DeflateIO io{d_text, n, (uint32_t)nm, o.d_slots.get(), o.d_off.get(), o.d_out.get()};
   if (o.ev0) HIP_TRY(hipEventRecord(o.ev0, st));
-  hipLaunchKernelGGL(kr_bgzf_deflate_kernel, dim3((uint32_t)((nm + 3) / 4)), dim3(256), 0, st, io);
+  if (o.level == 2) hipLaunchKernelGGL(kr_bgzf_deflate_dyn_kernel, dim3((uint32_t)((nm + 3) / 4)), dim3(256), 0, st, io, o.d_tokens.get());
+  else hipLaunchKernelGGL(kr_bgzf_deflate_kernel, dim3((uint32_t)((nm + 3) / 4)), dim3(256), 0, st, io);
   hipLaunchKernelGGL(kr_bgzf_deflate_scan_kernel, dim3(1), dim3(1024), 0, st, io.off, io.nmembers);
   hipLaunchKernelGGL(kr_bgzf_deflate_copy_kernel, dim3(io.nmembers), dim3(256), 0, st, io);
   HIP_TRY(hipGetLastError());
@@ -50,6 +52,22 @@ int kr_stream_bgzf_out_enable(kr_stream* s)
   HIP_TRY(hipSetDevice(s->ix->device));
   if (int rc = deflate_reserve(s, s->text.text_cap)) return rc;
   s->bgzf_out.on = true;
+  return KR_OK;
+}
+
+int kr_stream_bgzf_out_level(kr_stream* s, uint32_t level)
+{
+  kr::clear_error();
+  if (!s) return kr::fail(KR_ERR_ARG, "kr_stream_bgzf_out_level: null argument");
+  if (!s->bgzf_out.on) return kr::fail(KR_ERR_STATE, "kr_stream_bgzf_out_level: kr_stream_bgzf_out_enable first");
+  if (level != 1 && level != 2) return kr::fail(KR_ERR_ARG, "kr_stream_bgzf_out_level: level " + std::to_string(level) + " (1: fixed codes, 2: dynamic codes)");
+  HIP_TRY(hipSetDevice(s->ix->device));
+  const uint32_t before = s->bgzf_out.level;
+  s->bgzf_out.level = level;
+  if (int rc = deflate_reserve(s, s->text.text_cap)) { // (level 2: the token buffer, in hand before a kernel is queued)
+    s->bgzf_out.level = before;
+    return rc;
+  }
   return KR_OK;
 }
 
@@ -126,6 +144,29 @@ int kr_debug_bgzf_deflate_ms(kr_stream* s, float* ms)
   if (!o.ev_set) return KR_OK;
   HIP_TRY(hipEventSynchronize(o.ev1));
   HIP_TRY(hipEventElapsedTime(ms, o.ev0, o.ev1));
+  return KR_OK;
+}
+
+// (tests) def_build_lengths through kr_huffman_lengths_kernel
+int kr_debug_huffman_lengths_device(kr_stream* s, const uint32_t* freq, uint32_t nsym, uint32_t maxbits, uint8_t* lens, uint32_t* limited)
+{
+  kr::clear_error();
+  if (!s || !freq || !lens || !limited) return kr::fail(KR_ERR_ARG, "kr_debug_huffman_lengths_device: null argument");
+  if (!kr::def_build_args_ok(freq, nsym, maxbits))
+    return kr::fail(KR_ERR_ARG, "kr_debug_huffman_lengths_device: 1 to 286 symbols, 1 to 15 bits with room for every counted symbol, counts below 2^22");
+  HIP_TRY(hipSetDevice(s->ix->device));
+  (void)hipGetLastError();
+  kr_stream::BgzfOut& o = s->bgzf_out;
+  const uint32_t lens_at = kr::kDefLL, flag_at = lens_at + (kr::kDefLL + 3u) / 4u; // in words: counts | lengths | the flag
+  if (!o.d_huff.reserve(flag_at + 1u)) return alloc_failed("kr_debug_huffman_lengths_device");
+  uint32_t* d = o.d_huff.get();
+  hipStream_t st = s->lanes[0].stream;
+  HIP_TRY(hipMemcpyAsync(d, freq, nsym * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(kr_huffman_lengths_kernel, dim3(1), dim3(64), 0, st, d, nsym, maxbits, (uint8_t*)(d + lens_at), d + flag_at);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(lens, d + lens_at, nsym, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(limited, d + flag_at, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
   return KR_OK;
 }
 

@@ -273,6 +273,9 @@ struct kr_stream {
     bool on = false;
     DevBuf<uint8_t> d_slots, d_out, d_in; // [members][kDefSlot], the members back to back, kr_debug_bgzf_deflate's bytes
     DevBuf<uint64_t> d_off;               // [members + 1]
+    uint32_t level = 1;                   // kr_stream_bgzf_out_level: 1 fixed codes, 2 dynamic codes
+    DevBuf<uint32_t> d_tokens;            // level 2: [members][kDefTokStride], made when level 2 is first asked for
+    DevBuf<uint32_t> d_huff;              // kr_debug_huffman_lengths_device: counts, lengths, the flag
     PinBuf<uint64_t> h_total;
     PinBuf<uint8_t> h_comp; // (made by the first batch that needs it, as large as that batch's text can become)
     hipEvent_t ev0 = nullptr, ev1 = nullptr; // kr_debug_bgzf_deflate_ms: around the three kernels, once asked for

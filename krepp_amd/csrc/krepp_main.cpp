@@ -63,6 +63,7 @@ static void print_help(const std::string& sub)
     "  -q, --query PATH           query FASTA/FASTQ file (gzip accepted)\n"
     "  -o, --output-path PATH     write the report here [stdout]\n"
     "      --bgzf-out             write the report block-gzipped (BGZF: zcat, bgzip -d, tabix read it; device text is deflated on the GPU)\n"
+    "      --bgzf-level N         with --bgzf-out: 1 fixed Huffman codes, 2 dynamic codes, a smaller file for a second coding pass [1]\n"
     "      --hdist-th N           largest Hamming distance at which a k-mer matches [4]\n";
   const char* index_query_opts =
     "  -i, --index-dir DIR        index directory (as written by `krepp index`, this build's or the reference's)\n"
@@ -172,6 +173,7 @@ struct Settings {
   std::string query, index_arg, invocation;
   bool gpu_parse = false; // --gpu-parse asked for (Run::open_input decides whether the file qualifies)
   bool gpu_seek = false;  // seek --gpu-seek: batches flagged KR_SEEK, the report as the device's text
+  uint32_t bgzf_level = 1; // --bgzf-level: the encoder's level, on the workers' streams and in Run::deflated
   bool bgzf_out = false;  // --bgzf-out: every byte of the report goes out as BGZF members (Run::put, Worker::collect)
   int ngpus = 1, dev0 = 0, wpg = 2, nworkers = 2, write_threads = 4;
   uint32_t max_reads = 0;
@@ -218,6 +220,12 @@ static Settings resolve_settings(const Args& a, const std::string& invocation, i
   s.gpu_seek = a.flag.count("--gpu-seek") && a.flag.at("--gpu-seek");
   if (s.gpu_seek && !seek) error_exit("--gpu-seek is an option of `seek`");
   s.bgzf_out = a.flag.count("--bgzf-out") && a.flag.at("--bgzf-out");
+  if (a.has("--bgzf-level")) {
+    if (!s.bgzf_out) error_exit("--bgzf-level needs --bgzf-out");
+    const std::string v = a.get("--bgzf-level");
+    if (v != "1" && v != "2") error_exit("--bgzf-level: 1 (fixed Huffman codes) or 2 (dynamic codes), not " + v);
+    s.bgzf_level = (uint32_t)(v[0] - '0');
+  }
 
   // reads per batch: the kernels' efficiency grows with the batch (launch tails amortise, likelihood problems repeat): 262,144 reads
   // for `dist` on a large input, 65,536 for `place` / `seek` (more state per read) and for inputs of a few batches anyway
@@ -584,7 +592,7 @@ std::string Run::deflated(const char* p, size_t n)
 {
   std::string c((size_t)kr_bgzf_deflate_bound(n), '\0');
   uint64_t len = 0;
-  if (kr_bgzf_deflate_host((const uint8_t*)p, n, (uint8_t*)&c[0], c.size(), &len)) error_exit(kr_last_error());
+  if (kr_bgzf_deflate_host_level((const uint8_t*)p, n, s.bgzf_level, (uint8_t*)&c[0], c.size(), &len)) error_exit(kr_last_error());
   c.resize((size_t)len);
   if (n) nb_plain += n, nb_comp += len, ++n_host_deflate;
   return c;
@@ -759,6 +767,7 @@ void Worker::loop()
   if (s.gpu_seek && kr_stream_seek_enable(st, s.text_bytes, std::max<uint64_t>(1ull << 20, (uint64_t)s.max_reads * 64))) return r.worker_ready(kr_last_error());
   if (s.bgzf_out && (text_on || s.gpu_seek)) {
     if (kr_stream_bgzf_out_enable(st)) return r.worker_ready(kr_last_error());
+    if (s.bgzf_level != 1 && kr_stream_bgzf_out_level(st, s.bgzf_level)) return r.worker_ready(kr_last_error());
     bgzf_dev = true;
   }
   if (r.gpu_parse && kr_stream_fastq_enable(st, r.chunk_cap())) return r.worker_ready(kr_last_error());
@@ -1331,8 +1340,8 @@ int Run::finish()
     fprintf(stderr, "[timing] report text: %llu batches written from device text, %llu through the host formatter\n", (unsigned long long)nb_dev_text.load(),
             (unsigned long long)nb_host_text.load());
   if (s.timing && s.bgzf_out)
-    fprintf(stderr, "[timing] bgzf-out: %llu text bytes, %llu compressed bytes (without the end member); %llu pieces deflated on the device, %llu by the host encoder\n",
-            (unsigned long long)nb_plain.load(), (unsigned long long)nb_comp.load(), (unsigned long long)n_dev_deflate.load(), (unsigned long long)n_host_deflate.load());
+    fprintf(stderr, "[timing] bgzf-out: %llu text bytes, %llu compressed bytes (without the end member); %llu pieces deflated on the device, %llu by the host encoder; level %u\n",
+            (unsigned long long)nb_plain.load(), (unsigned long long)nb_comp.load(), (unsigned long long)n_dev_deflate.load(), (unsigned long long)n_host_deflate.load(), s.bgzf_level);
   fprintf(stderr, "Total number of sequences queried: %llu\n", (unsigned long long)nreads_total);
   // Everything is written.  Unmapping 19 GB of index, 10 GB of host tables and the page-locked buffers one by one takes 0.8-1.2 s
   // that nobody is waiting for: the process ends here and the kernel reclaims the lot (KR_CLI_CLEAN_EXIT=1: free everything in

@@ -88,6 +88,7 @@ configs = [
     ("dist", ["--no-multi"], {"KR_CLI_WORKERS_PER_GPU": "4"}, out_file),  # 11
     ("dist", ["--no-multi"], {"KR_CLI_BATCH_READS": "524288"}, out_file),  # 12
     ("dist", ["--bgzf-out"], {}, out_file),  # 13: the report block-gzipped, the text deflated on the GPU (docs/design/15)
+    ("dist", ["--bgzf-out", "--bgzf-level", "2"], {}, out_file),  # 14: the same with dynamic Huffman codes (docs/design/15.6)
 ]
 # KR_TIME_CLI_CONFIGS, e.g. "0,5,7"; "p0": configuration 0 with the binary KR_TIME_CLI_PARENT_EXE names (a build of another commit, as
 # the yardstick of the same session: "p0,0,13,p0,0,13,p0,0,13")
@@ -143,6 +144,14 @@ if os.environ.get("KR_TIME_CLI_DEFLATE"):
         print(f"deflate, repetition {rep}: {nbytes / 1e6:.1f} MB of text from {nr} reads; plain copy back {t_plain * 1e3:.2f} ms "
               f"({nbytes / t_plain / 1e9:.1f} GB/s); deflate + copy back of {ln.value / 1e6:.1f} MB ({ln.value / nbytes:.4f} of the text) "
               f"{t_bgzf * 1e3:.2f} ms, of which the kernels {ms:.2f} ms ({nbytes / ms / 1e6:.1f} GB/s of text)", flush=True)
+    st.bgzf_out_level(2)  # the same batch under dynamic codes (docs/design/15.6)
+    for rep in range(4):
+        t = time.perf_counter()
+        capi.check(lib.kr_batch_collect_text_bgzf(st.h, C.byref(p), C.byref(ln), C.byref(tl)))
+        t_bgzf = time.perf_counter() - t
+        ms = st.bgzf_deflate_ms()
+        print(f"deflate at level 2, repetition {rep}: deflate + copy back of {ln.value / 1e6:.1f} MB ({ln.value / tl.value:.4f} of the text) "
+              f"{t_bgzf * 1e3:.2f} ms, of which the kernels {ms:.2f} ms ({tl.value / ms / 1e6:.1f} GB/s of text)", flush=True)
     st.close(), dx.close(), hx.close()
 
 # ---- KR_TIME_CLI_TRACE=1: the default configuration once more under rocprofv3 --kernel-trace (the binary itself after `--`): the
