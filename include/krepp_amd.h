@@ -754,7 +754,29 @@ KR_API int kr_fastx_open_at_bgzf(const char* path, uint64_t member_off, uint32_t
  *   kr_debug_huffman_lengths       (tests) the level-2 code-length builder on the host: lens[0 .. nsym) for the counts
  *                           freq[0 .. nsym) with no code longer than maxbits, *limited = 1 when the limit was needed.  1 <= nsym
  *                           <= 286, 1 <= maxbits <= 15, counts below 2^22, at most 2^maxbits of them non-zero (else KR_ERR_ARG)
- *   kr_debug_huffman_lengths_device  (tests) the same through a kernel of one wave on the stream's device */
+ *   kr_debug_huffman_lengths_device  (tests) the same through a kernel of one wave on the stream's device
+ * Member length.  A member takes 65,280 input bytes unless the caller says otherwise: any length from 256 to 65,280 is BGZF.  One
+ * wave codes one member, so shorter members are more and shorter waves, at a small price in ratio (docs/design/15 section 15.7).
+ *   kr_bgzf_deflate_bound_member   kr_bgzf_deflate_bound for members of member_bytes input bytes; 0 for a length outside
+ *                           256 .. 65,280
+ *   kr_bgzf_deflate_host_member    kr_bgzf_deflate_host_level with members of member_bytes input bytes (the last one shorter);
+ *                           65,280 gives kr_bgzf_deflate_host_level's bytes.  KR_ERR_ARG for a length outside 256 .. 65,280
+ *   kr_stream_bgzf_member          the member length of the stream's later device deflates (kr_batch_collect_text_bgzf,
+ *                           kr_debug_bgzf_deflate, kr_place_stream under kr_stream_place_bgzf) and of the host encoder where
+ *                           kr_place_stream uses it.  KR_ERR_ARG outside 256 .. 65,280, the length in force stays.  After
+ *                           kr_stream_bgzf_out_enable the buffers are reserved again for the members of max_text_bytes before
+ *                           any kernel is queued (a batch in flight is waited for)
+ *   kr_debug_bgzf_deflate_at       (tests) kr_debug_bgzf_deflate for a text that starts at any byte: bytes[0 .. n) go to the
+ *                           device, [skip, n) is deflated from the device address of byte `skip`
+ * `place`.  kr_stream_place_bgzf(stream, level): 0 off (the default), 1 or 2 the encoder's level, anything else KR_ERR_ARG.  It
+ * needs neither kr_stream_text_enable nor kr_stream_bgzf_out_enable: the buffers grow with the text.  While it is on,
+ * kr_place_stream and kr_place_stream_parsed return BGZF members in *text / *len (no end member) that inflate to exactly the
+ * bytes the same call returns with it off; tabular == 2 and an empty text give *len == 0; has_previous, the placement records
+ * and every status are unchanged.  A range of reads whose rows were written on the device is deflated there, behind the text
+ * kernels, and only the members come back; a range the host formats goes through kr_bgzf_deflate_host_member at the same level
+ * and member length.  With one range a call the result is byte for byte kr_bgzf_deflate_host_member of the plain call's text;
+ * with several it is the ranges' encodings one behind the other.
+ *   kr_place_bgzf_counters         ranges of this process deflated on the device / by the host encoder (either may be null) */
 KR_API uint64_t kr_bgzf_deflate_bound(uint64_t n);
 KR_API int kr_bgzf_deflate_host(const uint8_t* text, uint64_t n, uint8_t* out, uint64_t cap, uint64_t* len);
 KR_API void kr_bgzf_eof(uint8_t* out28);
@@ -768,6 +790,12 @@ KR_API int kr_stream_bgzf_out_level(kr_stream*, uint32_t level);
 KR_API int kr_debug_bgzf_deflate_stats_level(const uint8_t* text, uint64_t n, uint32_t level, uint64_t* stats);
 KR_API int kr_debug_huffman_lengths(const uint32_t* freq, uint32_t nsym, uint32_t maxbits, uint8_t* lens, uint32_t* limited);
 KR_API int kr_debug_huffman_lengths_device(kr_stream*, const uint32_t* freq, uint32_t nsym, uint32_t maxbits, uint8_t* lens, uint32_t* limited);
+KR_API uint64_t kr_bgzf_deflate_bound_member(uint64_t n, uint32_t member_bytes);
+KR_API int kr_bgzf_deflate_host_member(const uint8_t* text, uint64_t n, uint32_t level, uint32_t member_bytes, uint8_t* out, uint64_t cap, uint64_t* len);
+KR_API int kr_stream_bgzf_member(kr_stream*, uint32_t member_bytes);
+KR_API int kr_debug_bgzf_deflate_at(kr_stream*, const uint8_t* bytes, uint64_t n, uint64_t skip, uint8_t* out, uint64_t cap, uint64_t* len);
+KR_API int kr_stream_place_bgzf(kr_stream*, uint32_t level);
+KR_API void kr_place_bgzf_counters(uint64_t* device_ranges, uint64_t* host_ranges);
 
 /* ---- `seek` on kernels of its own (csrc/kr_dev_seek.inc; docs/design/13_seek.md; INTEGRATION.md "A seek batch") ----
  * SBatch::seek_sequences (src/seek.cpp:22-126) on a SKETCH index (kr_host_sketch_load): per k-mer and strand the minimum Hamming

@@ -174,6 +174,8 @@ EXPORTS = [
     "kr_stream_bgzf_out_enable", "kr_batch_collect_text_bgzf", "kr_debug_bgzf_deflate", "kr_debug_bgzf_deflate_ms",
     "kr_bgzf_deflate_host_level", "kr_stream_bgzf_out_level", "kr_debug_bgzf_deflate_stats_level", "kr_debug_huffman_lengths",
     "kr_debug_huffman_lengths_device",
+    "kr_bgzf_deflate_bound_member", "kr_bgzf_deflate_host_member", "kr_stream_bgzf_member", "kr_debug_bgzf_deflate_at",
+    "kr_stream_place_bgzf", "kr_place_bgzf_counters",
 ]
 
 # kr_debug_acc_paths: the accumulate kernel's path witnesses, in the order of CounterSlot (kr_dev_common.inc)
@@ -321,6 +323,14 @@ def load():
     lib.kr_bgzf_deflate_host_level.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.kr_stream_bgzf_out_level.argtypes = [vp, C.c_uint32]
     lib.kr_debug_bgzf_deflate_stats_level.argtypes = [vp, C.c_uint64, C.c_uint32, u64p]
+    lib.kr_bgzf_deflate_bound_member.argtypes = [C.c_uint64, C.c_uint32]
+    lib.kr_bgzf_deflate_bound_member.restype = C.c_uint64
+    lib.kr_bgzf_deflate_host_member.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+    lib.kr_stream_bgzf_member.argtypes = [vp, C.c_uint32]
+    lib.kr_debug_bgzf_deflate_at.argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+    lib.kr_stream_place_bgzf.argtypes = [vp, C.c_uint32]
+    lib.kr_place_bgzf_counters.argtypes = [u64p, u64p]
+    lib.kr_place_bgzf_counters.restype = None
     lib.kr_debug_huffman_lengths.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.POINTER(C.c_uint32)]
     lib.kr_debug_huffman_lengths_device.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, C.POINTER(C.c_uint32)]
     lib.kr_debug_tile_layout.argtypes = [vp, u32p, u32p, vp, vp, vp, vp, vp]
@@ -900,6 +910,23 @@ class Stream:
         """kr_stream_bgzf_out_level: the level of this stream's later collect_text_bgzf / bgzf_deflate (1: fixed codes, 2: dynamic)"""
         check(self.lib.kr_stream_bgzf_out_level(self.h, int(level)))
 
+    def bgzf_member(self, member_bytes):
+        """kr_stream_bgzf_member: input bytes of a member (256 .. 65,280) of this stream's later device deflates"""
+        check(self.lib.kr_stream_bgzf_member(self.h, int(member_bytes)))
+
+    def place_bgzf(self, level):
+        """kr_stream_place_bgzf: kr_place_stream's text comes back as BGZF members (0: off, 1 / 2: the encoder's level)"""
+        check(self.lib.kr_stream_place_bgzf(self.h, int(level)))
+
+    def bgzf_deflate_at(self, data, skip, cap=None):
+        """(tests) kr_debug_bgzf_deflate_at: `data` goes to the device, data[skip:] is deflated from the device address of byte skip"""
+        data = bytes(data)
+        cap = bgzf_deflate_bound(len(data)) * 2 + 4096 if cap is None else int(cap)
+        out = np.zeros(max(1, cap), np.uint8)
+        n = C.c_uint64(0)
+        check(self.lib.kr_debug_bgzf_deflate_at(self.h, data, len(data), int(skip), out.ctypes.data, cap, C.byref(n)))
+        return out[: n.value].tobytes()
+
     def collect_text_bgzf(self, level=None):
         """kr_batch_collect_text_bgzf: (the batch's report text as BGZF members, the bytes they inflate to); level: bgzf_out_level first"""
         if level is not None:
@@ -1123,6 +1150,28 @@ def bgzf_deflate_host(text, cap=None, level=None):
     else:
         check(load().kr_bgzf_deflate_host_level(text, len(text), int(level), out.ctypes.data, cap, C.byref(n)))
     return out[: n.value].tobytes()
+
+
+def bgzf_deflate_bound_member(n, member_bytes):
+    """kr_bgzf_deflate_bound_member: kr_bgzf_deflate_bound for members of member_bytes input bytes (0: no such member length)"""
+    return int(load().kr_bgzf_deflate_bound_member(int(n), int(member_bytes)))
+
+
+def bgzf_deflate_host_member(text, level, member_bytes, cap=None):
+    """kr_bgzf_deflate_host_member: `text` as BGZF members of member_bytes input bytes each, at a level (no device, no end member)"""
+    text = bytes(text)
+    cap = bgzf_deflate_bound_member(len(text), member_bytes) if cap is None else int(cap)
+    out = np.zeros(max(1, cap), np.uint8)
+    n = C.c_uint64(0)
+    check(load().kr_bgzf_deflate_host_member(text, len(text), int(level), int(member_bytes), out.ctypes.data, cap, C.byref(n)))
+    return out[: n.value].tobytes()
+
+
+def place_bgzf_counters():
+    """kr_place_bgzf_counters: (ranges deflated on the device, ranges deflated by the host encoder) of this process"""
+    d, h = C.c_uint64(0), C.c_uint64(0)
+    load().kr_place_bgzf_counters(C.byref(d), C.byref(h))
+    return int(d.value), int(h.value)
 
 
 def bgzf_eof():
@@ -1586,11 +1635,12 @@ class Placer:
         self.lib.kr_free(txt)
         return s
 
-    def place(self, bases, offsets, names, host=False, c_names=None, want_placements=True, keep_text=True):
+    def place(self, bases, offsets, names, host=False, c_names=None, want_placements=True, keep_text=True, raw_text=False):
         """One batch.  host=False: kr_place_stream (tree aggregation and likelihoods on the device);
         host=True: kr_batch_collect + kr_place_batch (aggregation on the host).  Same output.
         keep_text=False (timing): the library's text and placements are not copied into Python objects -- copying and decoding 70 MB
-        of jplace text takes Python longer than the library takes to make it; returns (bytes of text, number of placements)."""
+        of jplace text takes Python longer than the library takes to make it; returns (bytes of text, number of placements).
+        raw_text=True: the text as bytes, not decoded (Stream.place_bgzf: BGZF members)."""
         bases = np.ascontiguousarray(bases, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         self.st.submit(bases, offsets, KR_TAP_ACCS)
@@ -1612,7 +1662,8 @@ class Placer:
             self.lib.kr_free(txt)
             self.lib.kr_free(pls)
             return int(ln.value), int(npl.value)
-        text = C.string_at(txt, ln.value).decode()
+        text = C.string_at(txt, ln.value)
+        text = text if raw_text else text.decode()
         pl = (np.frombuffer(C.string_at(pls, npl.value * PLACEMENT_DT.itemsize), dtype=PLACEMENT_DT).copy()
               if npl.value else np.zeros(0, PLACEMENT_DT))
         if int(self.tabular) == 2:
@@ -1621,7 +1672,7 @@ class Placer:
         self.lib.kr_free(pls)
         return text, pl
 
-    def place_parsed(self, raw, fasta=False, flags=0, want_placements=True, at_eof=1, bgzf=None):
+    def place_parsed(self, raw, fasta=False, flags=0, want_placements=True, at_eof=1, bgzf=None, raw_text=False):
         """One batch given as raw FASTQ (fasta=True: FASTA) bytes: kr_batch_submit_fastq / _fasta with KR_TAP_ACCS | flags on a
         page-locked copy of `raw`, then kr_place_stream_parsed.  The first call runs kr_stream_fastq_enable for chunks of up to
         max(len(raw), 1 MB) bytes.  Returns (text, placements, summary): the accepted prefix of the chunk is placed, and
@@ -1643,7 +1694,8 @@ class Placer:
         check(self.lib.kr_place_stream_parsed(self.hx.h, self.dx.h, self.pt, self.st.h, raw_ptr, C.byref(self.popts), int(self.tabular),
                                               C.byref(self.prev), C.byref(txt), C.byref(ln), C.byref(pls) if want_placements else None,
                                               C.byref(npl) if want_placements else None))
-        text = C.string_at(txt, ln.value).decode()
+        text = C.string_at(txt, ln.value)
+        text = text if raw_text else text.decode()
         pl = (np.frombuffer(C.string_at(pls, npl.value * PLACEMENT_DT.itemsize), dtype=PLACEMENT_DT).copy()
               if npl.value else np.zeros(0, PLACEMENT_DT))
         if int(self.tabular) == 2:

@@ -252,6 +252,10 @@ struct PlaceDeviceResult { // page-locked host arrays owned by the stream, valid
   const char* text = nullptr;
   uint64_t text_len = 0;
   uint64_t text_flags = 0;
+  // kr_stream_place_bgzf: `text` holds BGZF members, deflated on the device from the rows behind `text_skip` of them (0 or 2);
+  // text_plain: the rows' own length, the skipped bytes included (text_bgzf false: the same as text_len)
+  bool text_bgzf = false;
+  uint64_t text_plain = 0;
 };
 } // namespace kr
 struct kr_stream;
@@ -266,8 +270,15 @@ int place_on_device(kr_stream* s, const void* tree_tag, const PlaceTreeArrays& T
 // host arrays) -- the host's last phase of one range runs beside the kernels of the next (kr_place_stream).
 int place_device_begin(kr_stream* s, const void* tree_tag, const PlaceTreeArrays& T, const uint32_t* read_len);
 int place_device_launch(kr_stream* s, const PlaceTreeArrays& T, uint32_t r0, uint32_t n, uint32_t tau, bool no_filter, double chisq);
+// first_of_file: the caller will drop the ",\n" that opens the range's jplace text (it matters only while kr_stream_place_bgzf is
+// on: the device deflates the text from its third byte then).
 int place_device_finish(kr_stream* s, const PlaceTreeArrays& T, uint32_t r0, uint32_t n, uint32_t tau, bool no_filter, double chisq,
-                        uint64_t kept_base, PlaceDeviceResult* out);
+                        uint64_t kept_base, PlaceDeviceResult* out, bool first_of_file = false);
+// kr_stream_place_bgzf / kr_stream_bgzf_member as the stream holds them (0: off), and a range's rows in device memory deflated
+// into members on lane 0's stream, back in the stream's page-locked buffer (kr_host_deflate.inc)
+uint32_t place_bgzf_level(const kr_stream* s);
+uint32_t place_bgzf_member(const kr_stream* s);
+int place_text_deflate(kr_stream* s, const uint8_t* d_text, uint64_t n, const char** comp, uint64_t* len);
 uint32_t place_stream_nreads(const kr_stream* s);
 // Large host buffers the library hands to its caller (report text: tens of megabytes a batch) and its large temporaries: a block
 // given back (kr_free / big_free) is kept -- up to a bound -- and handed out again, pages already touched.  glibc maps a block of

@@ -718,9 +718,16 @@ KR_INF_HD inline uint32_t deflate_member_dyn(const uint8_t* in, uint32_t n, uint
   return size;
 }
 
+// The member length (input bytes a member takes) is the caller's: the cut is made outside deflate_member.  kDefMemberIn is the
+// default and the most; kDefMinMemberIn the least (kr_bgzf_deflate_host_member, kr_stream_bgzf_member, `--bgzf-member`).
+constexpr uint32_t kDefMinMemberIn = 256u;
+inline bool bgzf_member_in_ok(uint64_t member_in) { return member_in >= kDefMinMemberIn && member_in <= kDefMemberIn; }
+// the stride of the members' slots for a member length: room for member_in + 31 bytes, a multiple of 32 (kDefSlot at the default)
+KR_INF_HD inline uint32_t bgzf_slot_stride(uint32_t member_in) { return (member_in + 32u + 31u) & ~31u; }
+
 // members of n input bytes, and the most bytes they take
-inline uint64_t bgzf_deflate_members(uint64_t n) { return (n + kDefMemberIn - 1) / kDefMemberIn; }
-inline uint64_t bgzf_deflate_bound(uint64_t n) { return n + bgzf_deflate_members(n) * kDefOverhead; }
+inline uint64_t bgzf_deflate_members(uint64_t n, uint32_t member_in = kDefMemberIn) { return (n + member_in - 1) / member_in; }
+inline uint64_t bgzf_deflate_bound(uint64_t n, uint32_t member_in = kDefMemberIn) { return n + bgzf_deflate_members(n, member_in) * kDefOverhead; }
 
 // the empty member that ends a BGZF file
 inline void bgzf_eof(uint8_t* out28)
@@ -729,11 +736,12 @@ inline void bgzf_eof(uint8_t* out28)
   memcpy(out28, e, 28);
 }
 
-// Host form: member m of text[0 .. n) into its slot; `st` (optional) is added to.  Returns the member's size.
-inline uint32_t bgzf_deflate_member_host(const uint8_t* text, uint64_t n, uint64_t m, uint8_t* slot, DefState& S, DefStats* st)
+// Host form: member m (of member_in input bytes) of text[0 .. n) into its slot; `st` (optional) is added to.  Returns the member's size.
+inline uint32_t bgzf_deflate_member_host(const uint8_t* text, uint64_t n, uint64_t m, uint8_t* slot, DefState& S, DefStats* st,
+                                         uint32_t member_in = kDefMemberIn)
 {
-  const uint64_t a = m * kDefMemberIn;
-  const uint32_t len = (uint32_t)(n - a < kDefMemberIn ? n - a : kDefMemberIn);
+  const uint64_t a = m * member_in;
+  const uint32_t len = (uint32_t)(n - a < member_in ? n - a : member_in);
   DefSerial L;
   const uint32_t size = deflate_member(text + a, len, slot, S, crc_host_table(), L);
   if (st) {
@@ -749,11 +757,12 @@ inline uint32_t bgzf_deflate_member_host(const uint8_t* text, uint64_t n, uint64
   return size;
 }
 
-// The same at level 2.  tok: room for kDefTokStride tokens.
-inline uint32_t bgzf_deflate_member_host_dyn(const uint8_t* text, uint64_t n, uint64_t m, uint8_t* slot, DefDynState& S, uint32_t* tok, DefStats* st)
+// The same at level 2.  tok: room for member_in tokens (kDefTokStride at the most).
+inline uint32_t bgzf_deflate_member_host_dyn(const uint8_t* text, uint64_t n, uint64_t m, uint8_t* slot, DefDynState& S, uint32_t* tok, DefStats* st,
+                                             uint32_t member_in = kDefMemberIn)
 {
-  const uint64_t a = m * kDefMemberIn;
-  const uint32_t len = (uint32_t)(n - a < kDefMemberIn ? n - a : kDefMemberIn);
+  const uint64_t a = m * member_in;
+  const uint32_t len = (uint32_t)(n - a < member_in ? n - a : member_in);
   DefSerial L;
   const uint32_t size = deflate_member_dyn(text + a, len, slot, tok, S, crc_host_table(), L);
   if (st) {

@@ -1,29 +1,38 @@
 // kr_dev_deflate.inc -- part of kr_device.hip (device side): report text deflated into BGZF members where it was written
 // (kr_batch_collect_text_bgzf, kr_debug_bgzf_deflate; kr_host_deflate.inc).  The kernels:
-//   kr_bgzf_deflate_kernel   one wave per member of 65,280 text bytes, four waves a workgroup, the grid sized from the member count.
+//   kr_bgzf_deflate_kernel   one wave per member of io.member_in text bytes (65,280 unless kr_stream_bgzf_member says otherwise), four
+//                            waves a workgroup, the grid sized from the member count.
 //                            The encoder is kr_deflate.h's deflate_member, the code the host runs serially, and gives the same bytes:
 //                            a lane owns one position of every tile of 64 (lookup, verify, enter, its token's bits), the parse is the
 //                            same walk in every lane; head table, match lengths and the bit window live in LDS (8.7 KB a wave: four
-//                            workgroups a CU).  Member m goes to slot m (stride kDefSlot), one lane writes its size.
+//                            workgroups a CU).  Member m goes to slot m (stride io.slot_stride), one lane writes its size.
 //   kr_bgzf_deflate_dyn_kernel   the same launch at level 2 (kr_stream_bgzf_out_level): kr_deflate.h's deflate_member_dyn, the tokens
-//                            of pass 1 in a global list (kDefTokStride a member), the codes built by lane 0 between the passes,
+//                            of pass 1 in a global list (io.member_in a member), the codes built by lane 0 between the passes,
 //                            a lane per token in pass 2; 10.1 KB of LDS a wave: three workgroups a CU
 //   kr_huffman_lengths_kernel    (tests) the code-length builder alone, one wave
 //   kr_bgzf_deflate_scan_kernel   ONE workgroup of 1024: the sizes become the members' positions (scan_block_sums, kr_dev_prefix.inc:
 //                            a member is a "block"), the total behind them
 //   kr_bgzf_deflate_copy_kernel   a workgroup per member: its slot's bytes to its position, in words aligned to the destination
 //
-// Bounds (the host sized the buffers, deflate_reserve): text[0 .. n); nmembers = ceil(n / 65,280) slots; off[nmembers + 1]; the
-// output holds n + 31 * nmembers bytes; at level 2, nmembers * kDefTokStride tokens.  deflate_member (and _dyn) never reads outside its member's input nor writes outside [slot, slot +
-// len + 31), whatever the bytes are, and len + 31 <= kDefSlot.  The kernels keep scalars and statically sized LDS only.
+// Bounds (the host sized the buffers, deflate_reserve): text[0 .. n); nmembers = ceil(n / member_in) slots of slot_stride =
+// bgzf_slot_stride(member_in) bytes; off[nmembers + 1]; the output holds n + 31 * nmembers bytes; at level 2, nmembers * member_in
+// tokens.  deflate_member (and _dyn) never reads outside its member's input nor writes outside [slot, slot + len + 31), whatever
+// the bytes are, and len + 31 <= member_in + 31 < slot_stride <= kDefSlot.  The kernels keep scalars and statically sized LDS only
+// (kDefMemberIn bounds the state whatever member_in is).
+// Alignment of the input: a member starts at ANY byte (text + m * member_in with an odd member_in; a text that itself starts at an
+// odd address: place's d_text + 2).  Every load of the input in deflate_member / _dyn, def_tile_parse and DefWaveT::crc goes through
+// a const uint8_t* one byte at a time (def_hash assembles its word from four bytes); none is a cast to a wider type, so the
+// compiler may merge them only into loads the hardware takes at any address.  The slots stay 32-byte aligned (the copy kernel
+// reads them in words): slot_stride is a multiple of 32.
 
 struct DeflateIO {
   const uint8_t* text;
   uint64_t n;
   uint32_t nmembers;
-  uint8_t* slots;  // [nmembers][kDefSlot]
+  uint8_t* slots;  // [nmembers][slot_stride]
   uint64_t* off;   // [nmembers + 1]: the members' sizes, then (scan) their positions and the total
   uint8_t* out;    // [n + 31 * nmembers]
+  uint32_t member_in, slot_stride; // input bytes of a member (256 .. kDefMemberIn); bgzf_slot_stride(member_in)
 };
 
 // (a type per level: each kernel has lanes of its own, so that what the compiler makes of one does not depend on the other)
@@ -70,15 +79,15 @@ __global__ __launch_bounds__(256) void kr_bgzf_deflate_kernel(DeflateIO io)
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   const uint32_t m = blockIdx.x * 4u + wave;
   if (m >= io.nmembers) return;
-  const uint64_t a = (uint64_t)m * kr::kDefMemberIn;
-  const uint32_t len = (uint32_t)std::min<uint64_t>(io.n - a, kr::kDefMemberIn);
+  const uint64_t a = (uint64_t)m * io.member_in;
+  const uint32_t len = (uint32_t)std::min<uint64_t>(io.n - a, io.member_in);
   DefWave L;
   L.l = lane, L.total = 0;
-  const uint32_t size = kr::deflate_member(io.text + a, len, io.slots + (uint64_t)m * kr::kDefSlot, state[wave], crc_tab, L);
+  const uint32_t size = kr::deflate_member(io.text + a, len, io.slots + (uint64_t)m * io.slot_stride, state[wave], crc_tab, L);
   if (lane == 0) io.off[m] = size;
 }
 
-// Level 2 (dynamic codes): the same launch; member m's tokens lie in tokens[m * kDefTokStride ..), written in pass 1 and read in
+// Level 2 (dynamic codes): the same launch; member m's tokens lie in tokens[m * member_in ..), written in pass 1 and read in
 // pass 2 by the same wave (a wave's memory instructions execute in order: DefWave::sync).  10,128 bytes of LDS a wave.
 __global__ __launch_bounds__(256) void kr_bgzf_deflate_dyn_kernel(DeflateIO io, uint32_t* tokens)
 {
@@ -89,11 +98,11 @@ __global__ __launch_bounds__(256) void kr_bgzf_deflate_dyn_kernel(DeflateIO io, 
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   const uint32_t m = blockIdx.x * 4u + wave;
   if (m >= io.nmembers) return;
-  const uint64_t a = (uint64_t)m * kr::kDefMemberIn;
-  const uint32_t len = (uint32_t)std::min<uint64_t>(io.n - a, kr::kDefMemberIn);
+  const uint64_t a = (uint64_t)m * io.member_in;
+  const uint32_t len = (uint32_t)std::min<uint64_t>(io.n - a, io.member_in);
   DefWaveT<2> L;
   L.l = lane, L.total = 0;
-  const uint32_t size = kr::deflate_member_dyn(io.text + a, len, io.slots + (uint64_t)m * kr::kDefSlot, tokens + (uint64_t)m * kr::kDefTokStride,
+  const uint32_t size = kr::deflate_member_dyn(io.text + a, len, io.slots + (uint64_t)m * io.slot_stride, tokens + (uint64_t)m * io.member_in,
                                                state[wave], crc_tab, L);
   if (lane == 0) io.off[m] = size;
 }
@@ -124,8 +133,8 @@ __global__ __launch_bounds__(256) void kr_bgzf_deflate_copy_kernel(DeflateIO io)
   if (m >= io.nmembers) return;
   const uint64_t a = io.off[m];
   const uint32_t sz = (uint32_t)(io.off[m + 1] - a);
-  if (sz > kr::kDefSlot) return; // (cannot be: a member is at most 65,311 bytes)
-  const uint8_t* src = io.slots + (uint64_t)m * kr::kDefSlot; // 32-byte aligned
+  if (sz > io.slot_stride) return; // (cannot be: a member is at most member_in + 31 bytes)
+  const uint8_t* src = io.slots + (uint64_t)m * io.slot_stride; // 32-byte aligned
   uint8_t* dst = io.out + a;
   const uint32_t head = std::min<uint32_t>(sz, (4u - (uint32_t)((uintptr_t)dst & 3u)) & 3u); // bytes in front of dst's first whole word
   if (t < head) dst[t] = src[t];

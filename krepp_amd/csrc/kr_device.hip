@@ -59,7 +59,7 @@
 //   kr_host_fastq.inc      kr_stream_fastq_enable, kr_batch_submit_fastq, kr_batch_fastq_names
 //   kr_host_fasta.inc      kr_batch_submit_fasta
 //   kr_host_bgzf.inc       kr_stream_bgzf_enable, kr_batch_submit_bgzf, kr_debug_bgzf_inflate / _ms
-//   kr_host_deflate.inc    kr_stream_bgzf_out_enable, kr_batch_collect_text_bgzf, kr_debug_bgzf_deflate / _ms
+//   kr_host_deflate.inc    kr_stream_bgzf_out_enable, kr_stream_bgzf_member, kr_stream_place_bgzf, kr_batch_collect_text_bgzf, kr_debug_bgzf_deflate / _at / _ms
 //   kr_host_place.inc      kr::place_on_device (launch of the place kernels for kr_place_stream and kr_place_stream_parsed)
 //   kr_host_seek.inc       kr_stream_seek_enable, a KR_SEEK batch's submit / wait, kr_batch_collect_seek, kr_debug_seek_layout / _ms
 //   (below, in this file)  kr_host_alloc, debug entry points, kr_llh_batch, kr_llh_eval_indexed

@@ -1616,6 +1616,10 @@ int kr_debug_bgzf_inflate_host(const uint8_t* comp, uint64_t ncomp, uint8_t* out
 
 // ---- bytes deflated into BGZF members by the encoder's host instantiation (kr_deflate.h): what the device's kernel writes ------------
 uint64_t kr_bgzf_deflate_bound(uint64_t n) { return kr::bgzf_deflate_bound(n); }
+uint64_t kr_bgzf_deflate_bound_member(uint64_t n, uint32_t member_bytes)
+{ // (a member length outside 256 .. 65,280 is no length: 0)
+  return kr::bgzf_member_in_ok(member_bytes) ? kr::bgzf_deflate_bound(n, member_bytes) : 0;
+}
 
 void kr_bgzf_eof(uint8_t* out28)
 {
@@ -1624,26 +1628,29 @@ void kr_bgzf_eof(uint8_t* out28)
 
 // Every member into a slot of its own (the members' sizes are known only afterwards), on the thread pool in runs of members; then
 // the slots back to back.  A member's bytes depend on its input alone: neither on the thread that wrote it nor on how many there are.
-static int bgzf_deflate_slots(const uint8_t* text, uint64_t n, uint32_t level, std::vector<uint8_t>& slots, std::vector<uint32_t>& sizes, kr::DefStats* st)
+// member_in: the input bytes of a member; a slot is bgzf_slot_stride(member_in) bytes.
+static int bgzf_deflate_slots(const uint8_t* text, uint64_t n, uint32_t level, std::vector<uint8_t>& slots, std::vector<uint32_t>& sizes, kr::DefStats* st,
+                              uint32_t member_in = kr::kDefMemberIn)
 {
-  const uint64_t nm = kr::bgzf_deflate_members(n);
-  slots.resize(nm * kr::kDefSlot), sizes.resize(nm);
+  const uint64_t nm = kr::bgzf_deflate_members(n, member_in), stride = kr::bgzf_slot_stride(member_in);
+  slots.resize(nm * stride), sizes.resize(nm);
   const int nt = (int)std::max<uint64_t>(1, std::min<uint64_t>(st ? 1 : kr::parallel_width(), nm / 4)); // (stats: one thread, one counter)
   kr::parallel_for(nt, [&](int t) {
     const uint64_t m0 = nm * (uint64_t)t / nt, m1 = nm * (uint64_t)(t + 1) / nt;
     if (level == 2) { // dynamic codes: the member's token list between the two passes
       std::unique_ptr<kr::DefDynState> S(new kr::DefDynState);
-      std::vector<uint32_t> tok(kr::kDefTokStride);
-      for (uint64_t m = m0; m < m1; ++m) sizes[m] = kr::bgzf_deflate_member_host_dyn(text, n, m, slots.data() + m * kr::kDefSlot, *S, tok.data(), st);
+      std::vector<uint32_t> tok(member_in);
+      for (uint64_t m = m0; m < m1; ++m) sizes[m] = kr::bgzf_deflate_member_host_dyn(text, n, m, slots.data() + m * stride, *S, tok.data(), st, member_in);
       return;
     }
     std::unique_ptr<kr::DefState> S(new kr::DefState);
-    for (uint64_t m = m0; m < m1; ++m) sizes[m] = kr::bgzf_deflate_member_host(text, n, m, slots.data() + m * kr::kDefSlot, *S, st);
+    for (uint64_t m = m0; m < m1; ++m) sizes[m] = kr::bgzf_deflate_member_host(text, n, m, slots.data() + m * stride, *S, st, member_in);
   });
   return KR_OK;
 }
 
-static int bgzf_deflate_host_at(const char* who, const uint8_t* text, uint64_t n, uint32_t level, uint8_t* out, uint64_t cap, uint64_t* len)
+static int bgzf_deflate_host_at(const char* who, const uint8_t* text, uint64_t n, uint32_t level, uint8_t* out, uint64_t cap, uint64_t* len,
+                                uint32_t member_in = kr::kDefMemberIn)
 {
   kr::clear_error();
   if (!len || (n && !text) || (cap && !out)) return kr::fail(KR_ERR_ARG, std::string(who) + ": null argument");
@@ -1651,12 +1658,14 @@ static int bgzf_deflate_host_at(const char* who, const uint8_t* text, uint64_t n
   if (level != 1 && level != 2) return kr::fail(KR_ERR_ARG, std::string(who) + ": level " + std::to_string(level) + " (1: fixed codes, 2: dynamic codes)");
   std::vector<uint8_t> slots;
   std::vector<uint32_t> sizes;
-  bgzf_deflate_slots(text, n, level, slots, sizes, nullptr);
+  if (!kr::bgzf_member_in_ok(member_in)) return kr::fail(KR_ERR_ARG, std::string(who) + ": " + std::to_string(member_in) + " bytes a member (256 to 65280)");
+  bgzf_deflate_slots(text, n, level, slots, sizes, nullptr, member_in);
   uint64_t total = 0;
   for (uint32_t sz : sizes) total += sz;
   if (total > cap) return kr::fail(KR_ERR_CAPACITY, std::string(who) + ": the members take " + std::to_string(total) + " bytes, the buffer holds " + std::to_string(cap));
   uint64_t off = 0;
-  for (size_t m = 0; m < sizes.size(); ++m) memcpy(out + off, slots.data() + m * kr::kDefSlot, sizes[m]), off += sizes[m];
+  const uint64_t stride = kr::bgzf_slot_stride(member_in);
+  for (size_t m = 0; m < sizes.size(); ++m) memcpy(out + off, slots.data() + m * stride, sizes[m]), off += sizes[m];
   *len = total;
   return KR_OK;
 }
@@ -1669,6 +1678,11 @@ int kr_bgzf_deflate_host(const uint8_t* text, uint64_t n, uint8_t* out, uint64_t
 int kr_bgzf_deflate_host_level(const uint8_t* text, uint64_t n, uint32_t level, uint8_t* out, uint64_t cap, uint64_t* len)
 {
   return bgzf_deflate_host_at("kr_bgzf_deflate_host_level", text, n, level, out, cap, len);
+}
+
+int kr_bgzf_deflate_host_member(const uint8_t* text, uint64_t n, uint32_t level, uint32_t member_bytes, uint8_t* out, uint64_t cap, uint64_t* len)
+{
+  return bgzf_deflate_host_at("kr_bgzf_deflate_host_member", text, n, level, out, cap, len, member_bytes);
 }
 
 int kr_debug_bgzf_deflate_stats_level(const uint8_t* text, uint64_t n, uint32_t level, uint64_t* stats)

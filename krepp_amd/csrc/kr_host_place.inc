@@ -304,7 +304,7 @@ int kr::place_device_launch(kr_stream* s, const kr::PlaceTreeArrays& T, uint32_t
 // per-read results (at their places in the batch's arrays) and its kept candidates come back -- the candidates behind the
 // `kept_base` entries earlier ranges of this batch left in the host arrays (their reads' rd_c0 are moved accordingly).
 int kr::place_device_finish(kr_stream* s, const kr::PlaceTreeArrays& T, uint32_t r0, uint32_t n, uint32_t tau, bool no_filter, double chisq,
-                            uint64_t kept_base, kr::PlaceDeviceResult* out)
+                            uint64_t kept_base, kr::PlaceDeviceResult* out, bool first_of_file)
 {
   if (!out) return kr::fail(KR_ERR_ARG, "place_device_finish: null argument");
   kr_stream::PlaceWs& w = s->pw;
@@ -366,13 +366,26 @@ int kr::place_device_finish(kr_stream* s, const kr::PlaceTreeArrays& T, uint32_t
   out->overflow = (pl_cnt(w.h_cnt.get(), kPlFlags) & ~kPlFlagListCut) != 0; // (kPlFlagListCut: the internal candidates' list was incomplete -- the likelihood kernel did their minimisations itself)
   out->heavy_reads = pl_cnt(w.h_cnt.get(), kPlHeavySlots) + pl_cnt(w.h_cnt.get(), kPlInlineReads); // (list slots handed out, in chunks of 8: an upper bound, 0 when there was none; + reads done in global scratch by the first launch)
   if (out->overflow) return KR_OK;
-  out->text = nullptr, out->text_len = 0, out->text_flags = 0;
+  out->text = nullptr, out->text_len = 0, out->text_flags = 0, out->text_bgzf = false, out->text_plain = 0;
   if (w.text_on) {
     out->text_flags = w.h_ttotal.get()[1];
     const uint64_t tcap = place_text_bytes(w); // (what the kernels were told)
     if (w.h_ttotal.get()[0] > tcap) w.text_want_min = w.h_ttotal.get()[0] + w.h_ttotal.get()[0] / 4; // (this range goes to the host; the next batch gets the room)
     if (w.h_ttotal.get()[1] == 0 && w.h_ttotal.get()[0] <= tcap) { // the range's text is complete: it comes back, the candidates stay
       const uint64_t tl = w.h_ttotal.get()[0];
+      if (s->bgzf_out.place_level) { // kr_stream_place_bgzf: deflated behind the text kernels, only the members come back
+        // (jplace: every reported read begins with ",\n"; the first one of a file loses it -- kr_place_stream's rule, applied here
+        //  to where the deflate starts)
+        const uint64_t skip = (first_of_file && w.text_tabular == 0 && tl >= 2) ? 2 : 0;
+        const char* comp = "";
+        uint64_t clen = 0;
+        if (tl > skip && (rc = kr::place_text_deflate(s, (const uint8_t*)w.d_text.get() + skip, tl - skip, &comp, &clen))) return rc;
+        out->text = comp, out->text_len = clen, out->text_bgzf = true, out->text_plain = tl;
+        out->kept = 0;
+        out->rd_c0 = w.h_c0.get(), out->rd_info = w.h_info.get();
+        lap("the range's rows as BGZF members, back on the host");
+        return KR_OK;
+      }
       if (tl > w.h_text.size() && (rc = place_grow(w.h_text, tl + tl / 4 + (1u << 20)))) return rc;
       if (tl) {
         HIP_TRY(hipMemcpyAsync(w.h_text.get(), w.d_text.get(), tl, hipMemcpyDeviceToHost, st));

@@ -271,10 +271,12 @@ struct kr_stream {
   // report text deflated into BGZF members on the device (kr_dev_deflate.inc, kr_host_deflate.inc; kr_stream_bgzf_out_enable)
   struct BgzfOut {
     bool on = false;
-    DevBuf<uint8_t> d_slots, d_out, d_in; // [members][kDefSlot], the members back to back, kr_debug_bgzf_deflate's bytes
+    DevBuf<uint8_t> d_slots, d_out, d_in; // [members][bgzf_slot_stride(member_in)], the members back to back, kr_debug_bgzf_deflate's bytes
     DevBuf<uint64_t> d_off;               // [members + 1]
     uint32_t level = 1;                   // kr_stream_bgzf_out_level: 1 fixed codes, 2 dynamic codes
-    DevBuf<uint32_t> d_tokens;            // level 2: [members][kDefTokStride], made when level 2 is first asked for
+    uint32_t member_in = kr::kDefMemberIn; // kr_stream_bgzf_member: input bytes of a member
+    uint32_t place_level = 0;             // kr_stream_place_bgzf: 0 off; 1 / 2: kr_place_stream's text comes back as members
+    DevBuf<uint32_t> d_tokens;            // level 2: [members][member_in], made when level 2 is first asked for
     DevBuf<uint32_t> d_huff;              // kr_debug_huffman_lengths_device: counts, lengths, the flag
     PinBuf<uint64_t> h_total;
     PinBuf<uint8_t> h_comp; // (made by the first batch that needs it, as large as that batch's text can become)

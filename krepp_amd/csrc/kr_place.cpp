@@ -125,6 +125,8 @@ char* dup_text(const std::string& s, uint64_t* len)
 // kr_place_stream batches of this process by back end (kr_place_counters): on the device, or sent whole to the host path
 static std::atomic<uint64_t> g_place_device_batches{0}, g_place_host_batches{0}, g_place_heavy_reads{0};
 std::atomic<uint64_t> g_place_text_device{0}, g_place_text_fallback{0};
+// kr_stream_place_bgzf: ranges whose text was deflated on the device / by the host encoder (kr_place_bgzf_counters)
+static std::atomic<uint64_t> g_place_bgzf_device{0}, g_place_bgzf_host{0};
 std::atomic<uint64_t> kr::g_place_paths[kr::kPathCount] = {};
 std::atomic<uint64_t> kr::g_place_wit[kr::kPlaceWitCount] = {};
 
@@ -977,6 +979,26 @@ struct StreamBatch {
   }
 };
 
+// kr_stream_place_bgzf, a range the host formatted: its text through the host encoder at the stream's level and member length, in
+// place of the text.  An empty text stays empty: no member.
+int place_bgzf_host_piece(const std::string& who, uint32_t level, uint32_t member, char** text, uint64_t* len)
+{
+  if (!level || !*text || !*len) return KR_OK;
+  const uint64_t cap = kr_bgzf_deflate_bound_member(*len, member);
+  char* c = (char*)kr::big_alloc(cap + 1);
+  if (!c) return kr::fail(KR_ERR_NOMEM, who + ": out of memory");
+  uint64_t clen = 0;
+  if (const int rc = kr_bgzf_deflate_host_member((const uint8_t*)*text, *len, level, member, (uint8_t*)c, cap, &clen)) {
+    kr::big_free(c);
+    return rc;
+  }
+  c[clen] = 0;
+  kr::big_free(*text);
+  *text = c, *len = clen;
+  g_place_bgzf_host.fetch_add(1, std::memory_order_relaxed);
+  return KR_OK;
+}
+
 // The body of kr_place_stream and kr_place_stream_parsed: the entry points check their arguments and say where the batch's read
 // lengths, ids and host-side names come from (StreamBatch); everything else is one code.
 int place_stream_run(const kr_host_index* hx, const kr_index* dix, const kr_place_tree* pt, kr_stream* s, StreamBatch& B, const kr_params* p,
@@ -985,6 +1007,9 @@ int place_stream_run(const kr_host_index* hx, const kr_index* dix, const kr_plac
   const uint32_t nreads = B.nreads;
   const std::string who = B.who;
   kr::place_call_begin(s);
+  // kr_stream_place_bgzf: *text comes back as BGZF members -- a range whose rows the device wrote is deflated there
+  // (place_device_finish), a range the host formats goes through the host encoder; members concatenate as their texts do
+  const uint32_t bz_level = kr::place_bgzf_level(s), bz_member = kr::place_bgzf_member(s);
   auto host_path = [&]() -> int {
     g_place_host_batches.fetch_add(1, std::memory_order_relaxed);
     kr_result_view rv;
@@ -992,7 +1017,13 @@ int place_stream_run(const kr_host_index* hx, const kr_index* dix, const kr_plac
     if (rc) return rc;
     if (rv.nreads != nreads) return kr::fail(KR_ERR_ARG, who + ": nreads does not match the submitted batch");
     if ((rc = B.need_offsets()) || (rc = B.need_names())) return rc;
-    return kr_place_batch(hx, dix, pt, &rv, B.offsets, B.names, p, tabular, has_previous, text, len, placements, nplacements);
+    if ((rc = kr_place_batch(hx, dix, pt, &rv, B.offsets, B.names, p, tabular, has_previous, text, len, placements, nplacements))) return rc;
+    if ((rc = place_bgzf_host_piece(who, bz_level, bz_member, text, len))) {
+      kr::big_free(*text);
+      *text = nullptr, *len = 0;
+      if (placements && nplacements) kr::big_free(*placements), *placements = nullptr, *nplacements = 0;
+    }
+    return rc;
   };
   if (!pt->postorder || getenv("KR_PLACE_HOST")) return host_path();
   const bool timing = getenv("KR_PLACE_TIMING") != nullptr;
@@ -1044,7 +1075,7 @@ int place_stream_run(const kr_host_index* hx, const kr_index* dix, const kr_plac
   for (uint32_t k = 0; k < nranges && !rc; ++k) {
     const uint32_t r0 = r_of(k), r1 = r_of(k + 1);
     kr::PlaceDeviceResult res;
-    rc = kr::place_device_finish(s, T, r0, r1 - r0, p->tau, p->no_filter != 0, p->chisq, kept_base, &res);
+    rc = kr::place_device_finish(s, T, r0, r1 - r0, p->tau, p->no_filter != 0, p->chisq, kept_base, &res, tabular == 0 && !prev);
     if (rc) break;
     lap("A-C of a range: aggregation, Brent, chi-square on the device + copy back");
     if (res.overflow) {
@@ -1064,7 +1095,10 @@ int place_stream_run(const kr_host_index* hx, const kr_index* dix, const kr_plac
     if (res.text) { // the range's rows, written on the device
       const char* tp = res.text;
       uint64_t tl = res.text_len;
-      if (tabular == 0 && tl >= 2) { // jplace: every reported read begins with ",\n"; the first one of a file loses it
+      if (res.text_bgzf) { // members, deflated from where the text starts for this `prev` (place_device_finish)
+        if (tabular == 0 && res.text_plain >= 2) prev = 1;
+        if (tl) g_place_bgzf_device.fetch_add(1, std::memory_order_relaxed);
+      } else if (tabular == 0 && tl >= 2) { // jplace: every reported read begins with ",\n"; the first one of a file loses it
         if (!prev) tp += 2, tl -= 2;
         prev = 1;
       }
@@ -1103,6 +1137,7 @@ int place_stream_run(const kr_host_index* hx, const kr_index* dix, const kr_plac
     Piece& pc = pieces[k];
     if (tabular != 2 && (rc = B.need_names())) break; // (a parsed batch: the names the host formats with, made here and only here)
     rc = emit_placements(pt, r1 - r0, src, B.names, p, tabular, &prev, &pc.text, &pc.len, placements ? &pc.pl : nullptr, nplacements ? &pc.npl : nullptr, lap, r0);
+    if (!rc) rc = place_bgzf_host_piece(who, bz_level, bz_member, &pc.text, &pc.len);
   }
   if (rc) {
     drop();
@@ -1191,6 +1226,12 @@ void kr_place_text_counters(uint64_t* device_ranges, uint64_t* fallback_ranges)
 { // ranges of reads whose rows were written on the device / that were formatted by the host although device text was asked for
   if (device_ranges) *device_ranges = g_place_text_device.load(std::memory_order_relaxed);
   if (fallback_ranges) *fallback_ranges = g_place_text_fallback.load(std::memory_order_relaxed);
+}
+
+void kr_place_bgzf_counters(uint64_t* device_ranges, uint64_t* host_ranges)
+{ // kr_stream_place_bgzf: ranges whose text was deflated on the device / by the host encoder
+  if (device_ranges) *device_ranges = g_place_bgzf_device.load(std::memory_order_relaxed);
+  if (host_ranges) *host_ranges = g_place_bgzf_host.load(std::memory_order_relaxed);
 }
 
 void kr_place_path_counters(uint64_t* out, uint32_t n)

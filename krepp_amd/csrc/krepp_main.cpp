@@ -54,7 +54,7 @@ static const std::map<std::string, std::string> kAlias = {
   {"-i", "--index-dir"}, {"-q", "--query"}, {"-o", "--output-path"}, {"-t", "--nwk-file"}, {"-k", "--kmer-len"},
   {"-w", "--win-len"}, {"-h", "--num-positions"}, {"-m", "--modulo-lsh"}, {"-r", "--residue-lsh"}, {"-l", "--lineage-file"},
 };
-static const char* kFlags[] = {"--multi", "--filter", "--summarize", "--frac", "--verbose", "--gpu-minimizers", "--gpu-keys", "--gpu-colours", "--tabular", "--gpu-parse", "--gpu-seek", "--gpu-stats", "--bgzf-out"};
+static const char* kFlags[] = {"--multi", "--filter", "--summarize", "--frac", "--verbose", "--gpu-minimizers", "--gpu-keys", "--gpu-colours", "--tabular", "--gpu-parse", "--gpu-seek", "--gpu-stats", "--bgzf-out", "--gpu-deflate"};
 
 // options as in the reference's CLI (src/krepp.cpp:516-675); the texts are this build's own
 static void print_help(const std::string& sub)
@@ -64,6 +64,7 @@ static void print_help(const std::string& sub)
     "  -o, --output-path PATH     write the report here [stdout]\n"
     "      --bgzf-out             write the report block-gzipped (BGZF: zcat, bgzip -d, tabix read it; device text is deflated on the GPU)\n"
     "      --bgzf-level N         with --bgzf-out: 1 fixed Huffman codes, 2 dynamic codes, a smaller file for a second coding pass [1]\n"
+    "      --bgzf-member N        with --bgzf-out: text bytes a BGZF member takes, 256..65280; shorter members are more and shorter waves on the GPU and a slightly larger file [65280]\n"
     "      --hdist-th N           largest Hamming distance at which a k-mer matches [4]\n";
   const char* index_query_opts =
     "  -i, --index-dir DIR        index directory (as written by `krepp index`, this build's or the reference's)\n"
@@ -95,6 +96,7 @@ static void print_help(const std::string& sub)
            "      --tau N                highest Hamming distance counted by the placement threshold [2]\n"
            "      --filter / --no-filter [filter]\n"
            "      --tabular              tab-separated rows instead of jplace\n"
+           "      --gpu-deflate          with --bgzf-out: rows written on the GPU are deflated there, only BGZF members come back (the same text)\n"
            "      --gpu-parse            FASTA/FASTQ records found on the GPU (identical output; plain files, and BGZF files, inflated on the GPU; others keep the host reader)\n",
            query_opts, index_query_opts);
   if (sub.empty() || sub == "seek")
@@ -174,6 +176,8 @@ struct Settings {
   bool gpu_parse = false; // --gpu-parse asked for (Run::open_input decides whether the file qualifies)
   bool gpu_seek = false;  // seek --gpu-seek: batches flagged KR_SEEK, the report as the device's text
   uint32_t bgzf_level = 1; // --bgzf-level: the encoder's level, on the workers' streams and in Run::deflated
+  uint32_t bgzf_member = 65280; // --bgzf-member: text bytes a member takes, on the workers' streams and in Run::deflated
+  bool gpu_deflate = false; // place --bgzf-out --gpu-deflate: kr_stream_place_bgzf on the workers' streams
   bool bgzf_out = false;  // --bgzf-out: every byte of the report goes out as BGZF members (Run::put, Worker::collect)
   int ngpus = 1, dev0 = 0, wpg = 2, nworkers = 2, write_threads = 4;
   uint32_t max_reads = 0;
@@ -225,6 +229,19 @@ static Settings resolve_settings(const Args& a, const std::string& invocation, i
     const std::string v = a.get("--bgzf-level");
     if (v != "1" && v != "2") error_exit("--bgzf-level: 1 (fixed Huffman codes) or 2 (dynamic codes), not " + v);
     s.bgzf_level = (uint32_t)(v[0] - '0');
+  }
+  if (a.has("--bgzf-member")) {
+    if (!s.bgzf_out) error_exit("--bgzf-member needs --bgzf-out");
+    const std::string v = a.get("--bgzf-member");
+    char* end = nullptr;
+    const long m = strtol(v.c_str(), &end, 10);
+    if (v.empty() || *end || m < 256 || m > 65280) error_exit("--bgzf-member: 256 to 65280 text bytes a member, not " + v);
+    s.bgzf_member = (uint32_t)m;
+  }
+  if (a.flag.count("--gpu-deflate") && a.flag.at("--gpu-deflate")) {
+    if (!place) error_exit("--gpu-deflate is an option of `place`");
+    if (!s.bgzf_out) error_exit("--gpu-deflate needs --bgzf-out");
+    s.gpu_deflate = !s.summarize; // (--summarize: no rows, nothing to deflate)
   }
 
   // reads per batch: the kernels' efficiency grows with the batch (launch tails amortise, likelihood problems repeat): 262,144 reads
@@ -590,9 +607,9 @@ void Run::start_up(const Args& a)
 // --bgzf-out: p[0 .. n) as BGZF members, deflated by the host encoder in the calling thread (what the device's kernel would write)
 std::string Run::deflated(const char* p, size_t n)
 {
-  std::string c((size_t)kr_bgzf_deflate_bound(n), '\0');
+  std::string c((size_t)kr_bgzf_deflate_bound_member(n, s.bgzf_member), '\0');
   uint64_t len = 0;
-  if (kr_bgzf_deflate_host_level((const uint8_t*)p, n, s.bgzf_level, (uint8_t*)&c[0], c.size(), &len)) error_exit(kr_last_error());
+  if (kr_bgzf_deflate_host_member((const uint8_t*)p, n, s.bgzf_level, s.bgzf_member, (uint8_t*)&c[0], c.size(), &len)) error_exit(kr_last_error());
   c.resize((size_t)len);
   if (n) nb_plain += n, nb_comp += len, ++n_host_deflate;
   return c;
@@ -719,6 +736,7 @@ struct Worker {
   kr_stream* st = nullptr;
   bool text_on = false; // the stream formats `dist` rows on the device
   bool bgzf_dev = false; // --bgzf-out: the stream deflates its device text (kr_batch_collect_text_bgzf)
+  bool bgzf_place = false; // place --bgzf-out --gpu-deflate: kr_place_stream hands back members (kr_stream_place_bgzf)
   // reads per submit this worker currently trusts: halved when a submit overflows a device buffer, doubled again
   // after a run of successes -- data with hundreds of rows per read settle at a piece size instead of failing a
   // full-size submit (and every intermediate size) for every batch
@@ -769,6 +787,11 @@ void Worker::loop()
     if (kr_stream_bgzf_out_enable(st)) return r.worker_ready(kr_last_error());
     if (s.bgzf_level != 1 && kr_stream_bgzf_out_level(st, s.bgzf_level)) return r.worker_ready(kr_last_error());
     bgzf_dev = true;
+  }
+  if (s.bgzf_out && s.bgzf_member != 65280 && kr_stream_bgzf_member(st, s.bgzf_member)) return r.worker_ready(kr_last_error());
+  if (s.gpu_deflate) {
+    if (kr_stream_place_bgzf(st, s.bgzf_level)) return r.worker_ready(kr_last_error());
+    bgzf_place = true;
   }
   if (r.gpu_parse && kr_stream_fastq_enable(st, r.chunk_cap())) return r.worker_ready(kr_last_error());
   if (r.bgzf && kr_stream_bgzf_enable(st, r.chunk_cap())) return r.worker_ready(kr_last_error());
@@ -862,7 +885,12 @@ void Worker::emit_host(const char* p, size_t n)
 
 void Worker::append(const char* p, size_t n)
 {
-  if (s.bgzf_out) text += r.deflated(p, n);
+  if (bgzf_place) { // members already (kr_stream_place_bgzf): what they inflate to is in their trailers
+    uint32_t nm = 0;
+    uint64_t cb = 0, ub = 0;
+    if (n && kr_bgzf_walk((const uint8_t*)p, n, UINT64_MAX, &nm, &cb, &ub) == 0) r.nb_plain += ub, r.nb_comp += n;
+    text.append(p, n);
+  } else if (s.bgzf_out) text += r.deflated(p, n);
   else text.append(p, n);
 }
 
@@ -1339,6 +1367,11 @@ int Run::finish()
   if (s.timing && s.plain_dist()) // (a batch split at capacity counts once per piece)
     fprintf(stderr, "[timing] report text: %llu batches written from device text, %llu through the host formatter\n", (unsigned long long)nb_dev_text.load(),
             (unsigned long long)nb_host_text.load());
+  if (s.gpu_deflate) { // place pieces: the ranges the library deflated on the device / by its host encoder
+    uint64_t dev_ranges = 0, host_ranges = 0;
+    kr_place_bgzf_counters(&dev_ranges, &host_ranges);
+    n_dev_deflate += dev_ranges, n_host_deflate += host_ranges;
+  }
   if (s.timing && s.bgzf_out)
     fprintf(stderr, "[timing] bgzf-out: %llu text bytes, %llu compressed bytes (without the end member); %llu pieces deflated on the device, %llu by the host encoder; level %u\n",
             (unsigned long long)nb_plain.load(), (unsigned long long)nb_comp.load(), (unsigned long long)n_dev_deflate.load(), (unsigned long long)n_host_deflate.load(), s.bgzf_level);
