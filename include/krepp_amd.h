@@ -715,6 +715,61 @@ KR_API int kr_bgzf_walk(const uint8_t* buf, uint64_t n, uint64_t max_inflated, u
 KR_API uint64_t kr_bgzf_chunk_cut(const uint8_t* buf, uint64_t comp_bytes, uint32_t skip, uint32_t fasta, uint64_t* member_off, uint32_t* uoff);
 KR_API int kr_fastx_open_at_bgzf(const char* path, uint64_t member_off, uint32_t uoff, kr_fastx** out);
 
+/* ---- ordinary gzip inflated on the device (csrc/kr_inflate_sym.h, csrc/kr_gzip_super.h, csrc/kr_dev_gzip.inc; docs/design/08
+ * "Ordinary gzip on the device") ----
+ * An ordinary gzip member is ONE dependent deflate stream.  The inflater takes a SUPER-CHUNK of at most max_comp_bytes compressed
+ * bytes from where the verified stream stands, cuts it into sub-chunks of sub_bytes (one wave each) and runs four kernels: search (the
+ * first dynamic block start in every sub-chunk), decode (symbolically, against an unknown 32 KB window, into a slot of ratio_cap
+ * symbols per compressed byte), chain (the sub-chunks the stream passes through, and the window behind each), resolve (symbols to
+ * bytes, CRC-32).  The host compares every member's CRC-32 and length with its trailer, as gzread would.  It is independent of
+ * kr_stream: its own HIP stream on one device, buffers sized at creation (about 3 * ratio_cap * max_comp_bytes device bytes).
+ *   kr_gzdev_open      a regular file that starts with a gzip member.  sub_bytes >= 64, 1 <= ratio_cap <= 1024, max_comp_bytes >=
+ *                      sub_bytes, below 512 MB, ratio_cap * max_comp_bytes < 2^31 (else KR_ERR_ARG); keep_points >= 4 (fewer: 4)
+ *   kr_gzdev_read      the next inflated bytes in file order into dst[0 .. cap) (page-locked for the copy to be asynchronous); *n == 0:
+ *                      the end.  KR_ERR_IO ("damaged gzip file PATH: ... (at compressed offset N)") for a broken stream, a wrong CRC-32
+ *                      or length -- AFTER the bytes in front of the damage were handed out, as on every host path.  Bytes behind the
+ *                      last member that are no gzip member are ignored
+ *   kr_gzdev_point     the restart point at or in front of inflated_off among the starts of the last keep_points super-chunks
+ *                      (KR_ERR_ARG: none is kept that far back)
+ *   kr_gzdev_counters  c[11] = super-chunks, sub-chunks linked, sub-chunks without a start, sub-chunks dropped, host ranges (stretches
+ *                      zlib inflated because the first sub-chunk could not finish: a ratio above ratio_cap, a block larger than the
+ *                      super-chunk; inflated and handed out in pieces of about 64 MB, whatever they inflate to), redone bytes
+ *                      (compressed bytes that super-chunks took in behind their verified end -- a member's end, an overflow, a start
+ *                      nobody linked to -- and the next super-chunk copies, searches and decodes again: a file of many small members
+ *                      concatenated pays max_comp_bytes of work per member, and this counter says so), device time (us, by events) of
+ *                      the search, decode, chain and resolve kernels, time (us) of the copies
+ *   kr_fastx_open_at_gzip   the host reader so that it yields exactly the records from inflated_off on: zlib primed at the point
+ *                      (NULL: from the file's start), the members' trailers checked from the point's CRC state
+ *   kr_debug_gzdev_inflate       (tests) a whole gzip buffer through the kernels: its bytes, the rows of every super-chunk's sub-chunks one
+ *                      after the other (start bit S or 0xFFFFFFFF, end bit, status 0 idle / 1 linked / 2 member end / 3 input end /
+ *                      4 overflow / 5 bad, link, symbols, CRC-32 of a chain chunk), counters[6] as the first six above
+ *   kr_debug_gzdev_inflate_host  the same pipeline through the stages' serial instantiation: no device; the same bytes, rows, counters,
+ *                      codes and messages
+ *   kr_debug_gzdev_point_host    (tests) the restart point the serial twin keeps at or in front of inflated_off once it has read that far */
+typedef struct kr_gzdev kr_gzdev;
+typedef struct kr_gzip_point {
+  uint64_t bit;          /* compressed bit position in the file */
+  uint64_t inflated_off; /* of the first byte inflated from there */
+  uint64_t member_len;   /* the member's length in front of the point */
+  uint32_t member_crc;   /* ... and its CRC-32 */
+  uint32_t window_len;   /* bytes of window[] in use: its LAST window_len bytes */
+  uint8_t window[32768];
+} kr_gzip_point;
+KR_API int kr_gzdev_open(const char* path, int device, uint64_t max_comp_bytes, uint32_t sub_bytes, uint32_t ratio_cap, uint32_t keep_points, kr_gzdev** out);
+KR_API void kr_gzdev_close(kr_gzdev*);
+KR_API int kr_gzdev_read(kr_gzdev*, uint8_t* dst, uint64_t cap, uint64_t* n);
+KR_API int kr_gzdev_point(const kr_gzdev*, uint64_t inflated_off, kr_gzip_point* out);
+KR_API int kr_gzdev_counters(const kr_gzdev*, uint64_t* c11);
+KR_API int kr_fastx_open_at_gzip(const char* path, uint64_t inflated_off, const kr_gzip_point* from, kr_fastx** out);
+KR_API int kr_debug_gzdev_inflate(int device, const uint8_t* comp, uint64_t n, uint32_t sub_bytes, uint32_t ratio_cap, uint64_t max_comp_bytes, uint8_t* out,
+                                  uint64_t cap, uint64_t* len, uint64_t tab_cap, uint32_t* S, uint32_t* end, uint32_t* status, uint32_t* link,
+                                  uint32_t* length, uint32_t* crc, uint64_t* ntab, uint64_t* counters);
+KR_API int kr_debug_gzdev_point_host(const uint8_t* comp, uint64_t n, uint32_t sub_bytes, uint32_t ratio_cap, uint64_t max_comp_bytes, uint64_t inflated_off,
+                                     kr_gzip_point* out);
+KR_API int kr_debug_gzdev_inflate_host(const uint8_t* comp, uint64_t n, uint32_t sub_bytes, uint32_t ratio_cap, uint64_t max_comp_bytes, uint8_t* out,
+                                       uint64_t cap, uint64_t* len, uint64_t tab_cap, uint32_t* S, uint32_t* end, uint32_t* status, uint32_t* link,
+                                       uint32_t* length, uint32_t* crc, uint64_t* ntab, uint64_t* counters);
+
 /* ---- report text written block-gzipped (csrc/kr_deflate.h, csrc/kr_dev_deflate.inc; docs/design/15_bgzf_out.md) ----
  * The opposite direction: bytes deflated into BGZF members of at most 65,280 input bytes each (where bgzip cuts), one DEFLATE block
  * a member -- greedy matches from a hash table, fixed Huffman codes, or one stored block when that is not smaller.  One encoder

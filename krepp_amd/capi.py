@@ -149,6 +149,12 @@ class KrDedupResult(C.Structure):
                 ("mask", C.c_uint32), ("dd_slots", C.c_uint32), ("dd_shift", C.c_uint32)]
 
 
+class KrGzipPoint(C.Structure):
+    """kr_gzip_point: where an ordinary gzip stream can be taken up again"""
+    _fields_ = [("bit", C.c_uint64), ("inflated_off", C.c_uint64), ("member_len", C.c_uint64), ("member_crc", C.c_uint32),
+                ("window_len", C.c_uint32), ("window", C.c_uint8 * 32768)]
+
+
 # every symbol include/krepp_amd.h declares (tests check that the library exports them all)
 EXPORTS = [
     "kr_host_index_load", "kr_host_sketch_load", "kr_format_seek", "kr_build_sketch", "kr_host_index_free", "kr_host_index_view", "kr_host_index_node_name",
@@ -176,6 +182,8 @@ EXPORTS = [
     "kr_debug_huffman_lengths_device",
     "kr_bgzf_deflate_bound_member", "kr_bgzf_deflate_host_member", "kr_stream_bgzf_member", "kr_debug_bgzf_deflate_at",
     "kr_stream_place_bgzf", "kr_place_bgzf_counters",
+    "kr_gzdev_open", "kr_gzdev_close", "kr_gzdev_read", "kr_gzdev_point", "kr_gzdev_counters", "kr_fastx_open_at_gzip",
+    "kr_debug_gzdev_inflate", "kr_debug_gzdev_inflate_host", "kr_debug_gzdev_point_host",
 ]
 
 # kr_debug_acc_paths: the accumulate kernel's path witnesses, in the order of CounterSlot (kr_dev_common.inc)
@@ -310,6 +318,17 @@ def load():
     lib.kr_bgzf_chunk_cut.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
     lib.kr_bgzf_chunk_cut.restype = C.c_uint64
     lib.kr_fastx_open_at_bgzf.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, C.POINTER(vp)]
+    lib.kr_gzdev_open.argtypes = [C.c_char_p, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(vp)]
+    lib.kr_gzdev_close.argtypes = [vp]
+    lib.kr_gzdev_close.restype = None
+    lib.kr_gzdev_read.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+    lib.kr_gzdev_point.argtypes = [vp, C.c_uint64, C.POINTER(KrGzipPoint)]
+    lib.kr_gzdev_counters.argtypes = [vp, u64p]
+    lib.kr_fastx_open_at_gzip.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(KrGzipPoint), C.POINTER(vp)]
+    _gz_tabs = [C.c_uint64, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_uint64), u64p]
+    lib.kr_debug_gzdev_inflate.argtypes = [C.c_int, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64)] + _gz_tabs
+    lib.kr_debug_gzdev_inflate_host.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64)] + _gz_tabs
+    lib.kr_debug_gzdev_point_host.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(KrGzipPoint)]
     lib.kr_bgzf_deflate_bound.argtypes = [C.c_uint64]
     lib.kr_bgzf_deflate_bound.restype = C.c_uint64
     lib.kr_bgzf_deflate_host.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -1115,6 +1134,90 @@ def bgzf_inflate_host(comp, cap=None):
     return out[: n.value].tobytes()
 
 
+GZDEV_COUNTERS = ("super_chunks", "linked", "without_start", "dropped", "host_ranges", "redone_bytes")
+GZDEV_STATUS = ("idle", "linked", "member_end", "input_end", "overflow", "bad")
+
+
+class GzdevResult:
+    """What kr_debug_gzdev_inflate(_host) returns: the bytes handed out, the error (None, or the KrError raised behind the bytes), the
+    rows of every super-chunk's sub-chunks one after the other, the counters"""
+
+    def __init__(self, data, error, tables, counters):
+        self.data, self.error, self.tables, self.counters = data, error, tables, counters
+
+    def same_tables(self, other):
+        return all(np.array_equal(self.tables[k], other.tables[k]) for k in self.tables) and self.counters == other.counters
+
+
+def gzdev_inflate(comp, sub=32768, ratio=16, max_comp=64 << 20, cap=None, device=None):
+    """kr_debug_gzdev_inflate (device = an ordinal) / kr_debug_gzdev_inflate_host (device = None): a whole ordinary gzip buffer through
+    the inflater's four stages.  A damaged buffer gives the bytes in front of the damage and `.error`."""
+    comp = bytes(comp)
+    cap = max(1 << 16, 40 * len(comp)) if cap is None else int(cap)
+    out = np.zeros(max(1, cap), np.uint8)
+    tab_cap = (len(comp) // int(sub) + 2) * 64 + 64
+    tabs = {k: np.zeros(tab_cap, np.uint32) for k in ("S", "end", "status", "link", "length", "crc")}
+    ctr = np.zeros(6, np.uint64)
+    n, nt = C.c_uint64(0), C.c_uint64(0)
+    tail = [int(sub), int(ratio), int(max_comp), out.ctypes.data, cap, C.byref(n), tab_cap] + [tabs[k].ctypes.data for k in tabs] + [
+        C.byref(nt), ctr.ctypes.data_as(C.POINTER(C.c_uint64))]
+    if device is None:
+        rc = load().kr_debug_gzdev_inflate_host(comp, len(comp), *tail)
+    else:
+        rc = load().kr_debug_gzdev_inflate(int(device), comp, len(comp), *tail)
+    err = None
+    if rc == KR_ERR_IO:
+        err = KrError(rc, load().kr_last_error().decode(errors="replace"))
+    else:
+        check(rc)
+    return GzdevResult(out[: n.value].tobytes(), err, {k: v[: nt.value].copy() for k, v in tabs.items()},
+                       dict(zip(GZDEV_COUNTERS, (int(x) for x in ctr))))
+
+
+def gzdev_point_host(comp, inflated_off, sub=32768, ratio=16, max_comp=64 << 20):
+    """kr_debug_gzdev_point_host: the restart point the serial twin keeps at or in front of inflated_off"""
+    comp = bytes(comp)
+    pt = KrGzipPoint()
+    check(load().kr_debug_gzdev_point_host(comp, len(comp), int(sub), int(ratio), int(max_comp), int(inflated_off), C.byref(pt)))
+    return pt
+
+
+class Gzdev:
+    """kr_gzdev: an ordinary gzip file inflated on a device, super-chunk by super-chunk"""
+
+    def __init__(self, path, device=0, max_comp=64 << 20, sub=32768, ratio=16, keep_points=4):
+        self.lib = load()
+        self.h = C.c_void_p()
+        check(self.lib.kr_gzdev_open(os.fsencode(str(path)), int(device), int(max_comp), int(sub), int(ratio), int(keep_points), C.byref(self.h)))
+
+    def read(self, cap=1 << 20):
+        """the next inflated bytes (at most cap); b"" at the end"""
+        buf = np.zeros(int(cap), np.uint8)
+        n = C.c_uint64(0)
+        check(self.lib.kr_gzdev_read(self.h, buf.ctypes.data, int(cap), C.byref(n)))
+        return buf[: n.value].tobytes()
+
+    def point(self, inflated_off):
+        pt = KrGzipPoint()
+        check(self.lib.kr_gzdev_point(self.h, int(inflated_off), C.byref(pt)))
+        return pt
+
+    def counters(self):
+        c = np.zeros(11, np.uint64)
+        check(self.lib.kr_gzdev_counters(self.h, c.ctypes.data_as(C.POINTER(C.c_uint64))))
+        d = dict(zip(GZDEV_COUNTERS, (int(x) for x in c[:6])))
+        d.update(us_search=int(c[6]), us_decode=int(c[7]), us_chain=int(c[8]), us_resolve=int(c[9]), us_copy=int(c[10]))
+        return d
+
+    def close(self):
+        if self.h:
+            self.lib.kr_gzdev_close(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        self.close()
+
+
 def bgzf_member_size(buf):
     """kr_bgzf_member_size: the size of the BGZF member that `buf` starts with, 0 when it does not start with one"""
     buf = bytes(buf)
@@ -1253,17 +1356,20 @@ def colour_classes(pse, node_kind):
     return cls, out, lists[: nl.value]
 
 
-def read_fastx(path, min_bases=76800, stats=None, detach=0, offset=None, bgzf_at=None):
+def read_fastx(path, min_bases=76800, stats=None, detach=0, offset=None, bgzf_at=None, gzip_at=None):
     """All records of a FASTA/FASTQ(.gz) file via the library's reader: (names, bases, offsets).
     detach = K > 0: every batch is taken over (kr_fastx_detach), read only when K further batches have been parsed, then handed
     back (kr_fastx_release) -- the way the CLI's workers hold batches in flight.
     offset: the sequential reader from that record start of a plain file on (kr_fastx_open_at).
-    bgzf_at = (member_off, uoff): the same for a block-gzipped file (kr_fastx_open_at_bgzf)."""
+    bgzf_at = (member_off, uoff): the same for a block-gzipped file (kr_fastx_open_at_bgzf).
+    gzip_at = (inflated_off, KrGzipPoint or None): the same for an ordinary gzip file (kr_fastx_open_at_gzip)."""
     lib = load()
     lib.kr_fastx_parallel_chunks.restype = C.c_uint64
     lib.kr_fastx_parallel_chunks.argtypes = [C.c_void_p]
     h = C.c_void_p()
-    if bgzf_at is not None:
+    if gzip_at is not None:
+        check(lib.kr_fastx_open_at_gzip(os.fsencode(str(path)), int(gzip_at[0]), C.byref(gzip_at[1]) if gzip_at[1] is not None else None, C.byref(h)))
+    elif bgzf_at is not None:
         check(lib.kr_fastx_open_at_bgzf(os.fsencode(str(path)), int(bgzf_at[0]), int(bgzf_at[1]), C.byref(h)))
     elif offset is None:
         check(lib.kr_fastx_open(os.fsencode(str(path)), C.byref(h)))

@@ -49,6 +49,7 @@
 //   kr_dev_fastq.inc       FASTQ records found in a chunk of raw file bytes (kr_batch_submit_fastq)
 //   kr_dev_fasta.inc       FASTA records found in a chunk of raw file bytes, every pass parallel over bytes (kr_batch_submit_fasta)
 //   kr_dev_bgzf.inc        the members of a block-gzipped chunk inflated into the record finders' buffer (kr_batch_submit_bgzf; decoder: kr_inflate.h)
+//   kr_dev_gzip.inc        a super-chunk of an ORDINARY gzip stream inflated by four kernels: search, symbolic decode, chain, resolve (kr_gzdev_read; stages: kr_inflate_sym.h)
 //   kr_dev_deflate.inc     report text deflated into BGZF members, one wave per member (kr_batch_collect_text_bgzf; encoder: kr_deflate.h)
 //   kr_dev_place.inc       back end of `place`: ancestor accumulation, candidates, their likelihoods (kr_place_kernel)
 //   kr_dev_place_parsed.inc  read lengths and ids of a batch the record finders queued, for the place kernels (kr_place_stream_parsed)
@@ -59,6 +60,7 @@
 //   kr_host_fastq.inc      kr_stream_fastq_enable, kr_batch_submit_fastq, kr_batch_fastq_names
 //   kr_host_fasta.inc      kr_batch_submit_fasta
 //   kr_host_bgzf.inc       kr_stream_bgzf_enable, kr_batch_submit_bgzf, kr_debug_bgzf_inflate / _ms
+//   kr_host_gzip.inc       kr_gzdev_open / _read / _point / _counters / _close, kr_debug_gzdev_inflate (the driver between the kernels: kr_gzip_super.h)
 //   kr_host_deflate.inc    kr_stream_bgzf_out_enable, kr_stream_bgzf_member, kr_stream_place_bgzf, kr_batch_collect_text_bgzf, kr_debug_bgzf_deflate / _at / _ms
 //   kr_host_place.inc      kr::place_on_device (launch of the place kernels for kr_place_stream and kr_place_stream_parsed)
 //   kr_host_seek.inc       kr_stream_seek_enable, a KR_SEEK batch's submit / wait, kr_batch_collect_seek, kr_debug_seek_layout / _ms
@@ -67,11 +69,16 @@
 #include <rccl/rccl.h>
 #include <dlfcn.h>
 #include <unistd.h>
+#include <fcntl.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
 #include <type_traits>
 
 #include "kr_common.h"
 #include "kr_devutil.h"
 #include "kr_inflate.h"
+#include "kr_inflate_sym.h"
+#include "kr_gzip_super.h"
 #include "kr_deflate.h"
 
 #include <algorithm>
@@ -103,6 +110,7 @@ namespace {
 #include "kr_dev_fastq.inc"
 #include "kr_dev_fasta.inc"
 #include "kr_dev_bgzf.inc"
+#include "kr_dev_gzip.inc"
 #include "kr_dev_deflate.inc"
 #include "kr_dev_place.inc"
 #include "kr_dev_place_parsed.inc"
@@ -169,6 +177,7 @@ LlhConst make_llh_const(uint32_t k, uint32_t h, uint32_t th)
 #include "kr_host_fastq.inc"
 #include "kr_host_fasta.inc"
 #include "kr_host_bgzf.inc"
+#include "kr_host_gzip.inc"
 #include "kr_host_deflate.inc"
 #include "kr_host_place.inc"
 #include "kr_host_seek.inc"

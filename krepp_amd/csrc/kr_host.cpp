@@ -12,6 +12,7 @@
 //   report text                      src/query.cpp:152-196, src/query.hpp:210
 #include "kr_common.h"
 #include "kr_inflate.h"
+#include "kr_gzip_super.h"
 #include "kr_deflate.h"
 
 #include <sched.h>
@@ -1247,6 +1248,59 @@ struct BgzfSource {
   }
 };
 
+// Ordinary gzip read sequentially from a restart point (kr_fastx_open_at_gzip): zlib primed at the point's bit with its window
+// (kr::GzZlib, pgz::ZSeq's way), the members' trailers checked from the point's CRC state, the first `skip` bytes dropped.
+struct GzSeqSource {
+  int fd = -1;
+  const uint8_t* map = nullptr;
+  uint64_t size = 0, mlen = 0, skip = 0;
+  uint32_t crc = 0;
+  kr::GzZlib z;
+  bool done = false, failed = false;
+  std::vector<uint8_t> q;
+  size_t qpos = 0;
+  ~GzSeqSource()
+  {
+    if (map) munmap(const_cast<uint8_t*>(map), size);
+    if (fd >= 0) close(fd);
+  }
+  // like gzread: up to n bytes, 0 at the end, -1 on a damaged file (after the bytes in front of the damage)
+  int read(unsigned char* dst, unsigned n)
+  {
+    for (;;) {
+      if (qpos < q.size()) {
+        const unsigned k = (unsigned)std::min<size_t>(n, q.size() - qpos);
+        memcpy(dst, q.data() + qpos, k);
+        qpos += k;
+        return (int)k;
+      }
+      if (failed) return -1;
+      if (done) return 0;
+      q.clear(), qpos = 0;
+      const int r = z.run(q, z.bitpos() + (8ull << 20), 1ull << 32); // to the first block boundary a megabyte on
+      if (!q.empty()) crc = (uint32_t)crc32(crc, q.data(), (uInt)q.size()), mlen += q.size();
+      if (r == 0 || r == 3) failed = true;
+      else if (r == 2) { // the member has ended: its trailer, then the next member or the end (as gzread)
+        const uint64_t t = (z.bitpos() + 7) >> 3;
+        if (t + 8 > size || kr::bgzf_le32(map + t) != crc || kr::bgzf_le32(map + t + 4) != (uint32_t)mlen) failed = true;
+        else {
+          crc = 0, mlen = 0;
+          const uint64_t h = t + 8;
+          if (h + 2 > size || map[h] != 0x1f || map[h + 1] != 0x8b) done = true;
+          else {
+            const uint64_t d = kr::gz_member_header(map, size, h);
+            if (!d || !z.start(map, size, d * 8, nullptr, 0)) failed = true;
+          }
+        }
+      }
+      if (skip) {
+        const size_t k = (size_t)std::min<uint64_t>(skip, q.size());
+        qpos = k, skip -= k;
+      }
+    }
+  }
+};
+
 struct kr_fastx_held { // the buffers of one batch, owned by the caller between kr_fastx_detach and kr_fastx_release
   std::vector<uint8_t> bases;
   std::vector<uint64_t> offsets;
@@ -1259,6 +1313,7 @@ struct kr_fastx {
   gzFile f = nullptr;
   std::unique_ptr<BgzfSource> bgzf; // block-gzipped input: members inflated in parallel
   std::unique_ptr<pgz::Source> pgz; // ordinary gzip input: chunks of the one deflate stream inflated in parallel (kr_pgz.inc)
+  std::unique_ptr<GzSeqSource> gzseq; // ordinary gzip input from a restart point (kr_fastx_open_at_gzip)
   bool bgzf_error = false, pgz_error = false;
   std::string path;
   std::unique_ptr<FqPool> pool; // plain files: chunks parsed in parallel while this is set
@@ -1310,7 +1365,7 @@ struct kr_fastx {
   // there, src/kseq.h:92-101; a query file that lost its tail is reported instead, like a damaged block-gzipped one)
   void note_zlib_error()
   {
-    if (pgz || bgzf || !f) return;
+    if (pgz || bgzf || gzseq || !f) return;
     int en = Z_OK;
     (void)gzerror(f, &en);
     if (en != Z_OK && en != Z_STREAM_END) pgz_error = true;
@@ -1320,9 +1375,10 @@ struct kr_fastx {
   {
     if (pos >= end) {
       if (eof) return -1;
-      int n = pgz ? pgz->read(buf.data(), (unsigned)buf.size())
-                  : (bgzf ? bgzf->read(buf.data(), (unsigned)buf.size()) : gzread(f, buf.data(), (unsigned)buf.size()));
-      if (pgz && n < 0) pgz_error = true;
+      int n = gzseq ? gzseq->read(buf.data(), (unsigned)buf.size())
+              : pgz ? pgz->read(buf.data(), (unsigned)buf.size())
+                    : (bgzf ? bgzf->read(buf.data(), (unsigned)buf.size()) : gzread(f, buf.data(), (unsigned)buf.size()));
+      if ((pgz || gzseq) && n < 0) pgz_error = true;
       if (bgzf && n == -2) {
         if (leave_bgzf()) n = gzread(f, buf.data(), (unsigned)buf.size());
         else n = -1, bgzf_error = true;
@@ -1349,9 +1405,10 @@ struct kr_fastx {
       pos = 0;
     }
     while (end < buf.size()) {
-      int n = pgz ? pgz->read(buf.data() + end, (unsigned)(buf.size() - end))
-                  : (bgzf ? bgzf->read(buf.data() + end, (unsigned)(buf.size() - end)) : gzread(f, buf.data() + end, (unsigned)(buf.size() - end)));
-      if (pgz && n < 0) pgz_error = true;
+      int n = gzseq ? gzseq->read(buf.data() + end, (unsigned)(buf.size() - end))
+              : pgz ? pgz->read(buf.data() + end, (unsigned)(buf.size() - end))
+                    : (bgzf ? bgzf->read(buf.data() + end, (unsigned)(buf.size() - end)) : gzread(f, buf.data() + end, (unsigned)(buf.size() - end)));
+      if ((pgz || gzseq) && n < 0) pgz_error = true;
       if (bgzf && n == -2) {
         if (leave_bgzf()) n = gzread(f, buf.data() + end, (unsigned)(buf.size() - end));
         else n = -1, bgzf_error = true;
@@ -1614,6 +1671,39 @@ int kr_debug_bgzf_inflate_host(const uint8_t* comp, uint64_t ncomp, uint8_t* out
   return KR_OK;
 }
 
+// ---- an ordinary gzip buffer through the serial twin of the device inflater's stages (kr_inflate_sym.h, kr_gzip_super.h) -----------
+int kr_debug_gzdev_inflate_host(const uint8_t* comp, uint64_t n, uint32_t sub_bytes, uint32_t ratio_cap, uint64_t max_comp_bytes, uint8_t* out, uint64_t cap,
+                                uint64_t* len, uint64_t tab_cap, uint32_t* S, uint32_t* end, uint32_t* status, uint32_t* link, uint32_t* length, uint32_t* crc,
+                                uint64_t* ntab, uint64_t* counters)
+{
+  kr::clear_error();
+  if (!comp || !out || !len || !S || !end || !status || !link || !length || !crc || !ntab || !counters) return kr::fail(KR_ERR_ARG, "kr_debug_gzdev_inflate_host: null argument");
+  kr::GzParams prm;
+  prm.sub = sub_bytes, prm.ratio = ratio_cap, prm.max_comp = max_comp_bytes;
+  if (const char* why = kr::gz_params_check(prm)) return kr::fail(KR_ERR_ARG, std::string("kr_debug_gzdev_inflate_host: ") + why);
+  kr::GzHostBackend be;
+  std::string msg;
+  const int rc = kr::gz_debug_run(be, comp, n, prm, out, cap, len, tab_cap, S, end, status, link, length, crc, ntab, counters, msg);
+  return rc ? kr::fail(rc, msg) : KR_OK;
+}
+
+// (tests) the restart point the serial twin keeps at or in front of inflated_off: what kr_gzdev_point gives on the device
+int kr_debug_gzdev_point_host(const uint8_t* comp, uint64_t n, uint32_t sub_bytes, uint32_t ratio_cap, uint64_t max_comp_bytes, uint64_t inflated_off, kr_gzip_point* out)
+{
+  kr::clear_error();
+  if (!comp || !out) return kr::fail(KR_ERR_ARG, "kr_debug_gzdev_point_host: null argument");
+  kr::GzParams prm;
+  prm.sub = sub_bytes, prm.ratio = ratio_cap, prm.max_comp = max_comp_bytes;
+  if (const char* why = kr::gz_params_check(prm)) return kr::fail(KR_ERR_ARG, std::string("kr_debug_gzdev_point_host: ") + why);
+  kr::GzHostBackend be;
+  std::unique_ptr<kr::GzPoint> pt(new kr::GzPoint());
+  std::string msg;
+  if (int rc = kr::gz_debug_point(be, comp, n, prm, inflated_off, pt.get(), msg)) return kr::fail(rc, msg);
+  out->bit = pt->bit, out->inflated_off = pt->inflated_off, out->member_len = pt->mlen, out->member_crc = pt->crc, out->window_len = pt->wlen;
+  memcpy(out->window, pt->win, kr::kGzWin);
+  return KR_OK;
+}
+
 // ---- bytes deflated into BGZF members by the encoder's host instantiation (kr_deflate.h): what the device's kernel writes ------------
 uint64_t kr_bgzf_deflate_bound(uint64_t n) { return kr::bgzf_deflate_bound(n); }
 uint64_t kr_bgzf_deflate_bound_member(uint64_t n, uint32_t member_bytes)
@@ -1812,6 +1902,40 @@ int kr_fastx_open_at_bgzf(const char* path, uint64_t member_off, uint32_t uoff, 
     }
     left -= (uint32_t)n;
   }
+  *out = r;
+  return KR_OK;
+}
+
+// The host reader of an ordinary gzip file from inflated offset `inflated_off` on, a record start: zlib primed at the restart point
+// `from` (kr_gzdev_point; null: the file's start), in kseq's "look for the next marker" state (as kr_fastx_open_at).  Not the parallel
+// reader: it is the hand-over behind the device inflater.
+int kr_fastx_open_at_gzip(const char* path, uint64_t inflated_off, const kr_gzip_point* from, kr_fastx** out)
+{
+  kr::clear_error();
+  if (!path || !out) return kr::fail(KR_ERR_ARG, "kr_fastx_open_at_gzip: null argument");
+  if (from && (from->inflated_off > inflated_off || from->window_len > kr::kGzWin)) return kr::fail(KR_ERR_ARG, "kr_fastx_open_at_gzip: the point lies behind the offset");
+  std::unique_ptr<GzSeqSource> g(new GzSeqSource());
+  g->fd = open(path, O_RDONLY);
+  struct stat sb;
+  if (g->fd < 0 || fstat(g->fd, &sb) != 0) return kr::fail(KR_ERR_IO, std::string("Failed to open the file at ") + path);
+  if (!S_ISREG(sb.st_mode) || sb.st_size < 18) return kr::fail(KR_ERR_UNSUPPORTED, std::string("kr_fastx_open_at_gzip: not a regular gzip file: ") + path);
+  g->size = (uint64_t)sb.st_size;
+  void* m = mmap(nullptr, g->size, PROT_READ, MAP_PRIVATE, g->fd, 0);
+  if (m == MAP_FAILED) return kr::fail(KR_ERR_IO, std::string("kr_fastx_open_at_gzip: cannot map ") + path);
+  g->map = (const uint8_t*)m;
+  uint64_t bit = 0;
+  if (from) {
+    bit = from->bit, g->crc = from->member_crc, g->mlen = from->member_len, g->skip = inflated_off - from->inflated_off;
+  } else {
+    bit = kr::gz_member_header(g->map, g->size, 0) * 8, g->skip = inflated_off;
+    if (!bit) return kr::fail(KR_ERR_FORMAT, std::string("kr_fastx_open_at_gzip: not a gzip file: ") + path);
+  }
+  if (!g->z.start(g->map, g->size, bit, from ? from->window + (kr::kGzWin - from->window_len) : nullptr, from ? from->window_len : 0))
+    return kr::fail(KR_ERR_ARG, "kr_fastx_open_at_gzip: the point is no place in the file");
+  kr_fastx* r = new kr_fastx();
+  r->path = path;
+  r->buf.resize(4 << 20);
+  r->gzseq = std::move(g);
   *out = r;
   return KR_OK;
 }

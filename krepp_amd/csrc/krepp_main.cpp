@@ -54,7 +54,7 @@ static const std::map<std::string, std::string> kAlias = {
   {"-i", "--index-dir"}, {"-q", "--query"}, {"-o", "--output-path"}, {"-t", "--nwk-file"}, {"-k", "--kmer-len"},
   {"-w", "--win-len"}, {"-h", "--num-positions"}, {"-m", "--modulo-lsh"}, {"-r", "--residue-lsh"}, {"-l", "--lineage-file"},
 };
-static const char* kFlags[] = {"--multi", "--filter", "--summarize", "--frac", "--verbose", "--gpu-minimizers", "--gpu-keys", "--gpu-colours", "--tabular", "--gpu-parse", "--gpu-seek", "--gpu-stats", "--bgzf-out", "--gpu-deflate"};
+static const char* kFlags[] = {"--multi", "--filter", "--summarize", "--frac", "--verbose", "--gpu-minimizers", "--gpu-keys", "--gpu-colours", "--tabular", "--gpu-parse", "--gpu-seek", "--gpu-stats", "--bgzf-out", "--gpu-deflate", "--gpu-inflate"};
 
 // options as in the reference's CLI (src/krepp.cpp:516-675); the texts are this build's own
 static void print_help(const std::string& sub)
@@ -87,7 +87,8 @@ static void print_help(const std::string& sub)
   if (sub.empty() || sub == "dist")
     printf("\nkrepp dist -i DIR -q READS: distances of every read to the references it matches\n%s%s"
            "      --filter / --no-filter keep only references not significantly worse than the closest [no-filter]\n"
-           "      --gpu-parse            FASTA/FASTQ records found on the GPU (identical output; plain files, and BGZF files, inflated on the GPU; others keep the host reader)\n",
+           "      --gpu-parse            FASTA/FASTQ records found on the GPU (identical output; plain files, and BGZF files, inflated on the GPU; others keep the host reader)\n"
+           "      --gpu-inflate          with --gpu-parse: ordinary gzip files are inflated on the GPU too (identical output; without it they keep the host reader)\n",
            query_opts, index_query_opts);
   if (sub.empty() || sub == "place")
     printf("\nkrepp place -i DIR -q READS: placements on the backbone tree (jplace)\n%s%s"
@@ -97,12 +98,14 @@ static void print_help(const std::string& sub)
            "      --filter / --no-filter [filter]\n"
            "      --tabular              tab-separated rows instead of jplace\n"
            "      --gpu-deflate          with --bgzf-out: rows written on the GPU are deflated there, only BGZF members come back (the same text)\n"
-           "      --gpu-parse            FASTA/FASTQ records found on the GPU (identical output; plain files, and BGZF files, inflated on the GPU; others keep the host reader)\n",
+           "      --gpu-parse            FASTA/FASTQ records found on the GPU (identical output; plain files, and BGZF files, inflated on the GPU; others keep the host reader)\n"
+           "      --gpu-inflate          with --gpu-parse: ordinary gzip files are inflated on the GPU too (identical output; without it they keep the host reader)\n",
            query_opts, index_query_opts);
   if (sub.empty() || sub == "seek")
     printf("\nkrepp seek -i SKETCH -q READS: distance of every read to the one sketched reference\n"
            "  -i, --sketch-path PATH     sketch file (as written by `krepp sketch`)\n%s"
            "      --gpu-parse            FASTA/FASTQ records found on the GPU (identical output; plain files, and BGZF files, inflated on the GPU; others keep the host reader)\n"
+           "      --gpu-inflate          with --gpu-parse: ordinary gzip files are inflated on the GPU too (identical output; without it they keep the host reader)\n"
            "      --gpu-seek             seek kernels and report text on the GPU (identical output)\n",
            query_opts);
   if (sub.empty() || sub == "index")
@@ -175,6 +178,9 @@ struct Settings {
   std::string query, index_arg, invocation;
   bool gpu_parse = false; // --gpu-parse asked for (Run::open_input decides whether the file qualifies)
   bool gpu_seek = false;  // seek --gpu-seek: batches flagged KR_SEEK, the report as the device's text
+  bool gpu_inflate = false; // --gpu-parse --gpu-inflate: an ordinary gzip file is inflated on the device (kr_gzdev), its records found there
+  uint64_t gz_super = 64ull << 20; // KR_GZDEV_SUPER: compressed bytes a super-chunk takes
+  uint32_t gz_sub = 32768, gz_ratio = 16; // KR_GZDEV_SUB: bytes a wave searches and decodes from (zlib's blocks are 17-21 KB of FASTQ-like text); KR_GZDEV_RATIO: symbols a compressed byte may inflate to
   uint32_t bgzf_level = 1; // --bgzf-level: the encoder's level, on the workers' streams and in Run::deflated
   uint32_t bgzf_member = 65280; // --bgzf-member: text bytes a member takes, on the workers' streams and in Run::deflated
   bool gpu_deflate = false; // place --bgzf-out --gpu-deflate: kr_stream_place_bgzf on the workers' streams
@@ -223,6 +229,11 @@ static Settings resolve_settings(const Args& a, const std::string& invocation, i
   s.gpu_parse = a.flag.count("--gpu-parse") && a.flag.at("--gpu-parse");
   s.gpu_seek = a.flag.count("--gpu-seek") && a.flag.at("--gpu-seek");
   if (s.gpu_seek && !seek) error_exit("--gpu-seek is an option of `seek`");
+  s.gpu_inflate = a.flag.count("--gpu-inflate") && a.flag.at("--gpu-inflate");
+  if (s.gpu_inflate && !s.gpu_parse) error_exit("--gpu-inflate needs --gpu-parse");
+  if (const char* e = getenv("KR_GZDEV_SUPER")) s.gz_super = strtoull(e, nullptr, 10);
+  if (const char* e = getenv("KR_GZDEV_SUB")) s.gz_sub = (uint32_t)strtoul(e, nullptr, 10);
+  if (const char* e = getenv("KR_GZDEV_RATIO")) s.gz_ratio = (uint32_t)strtoul(e, nullptr, 10);
   s.bgzf_out = a.flag.count("--bgzf-out") && a.flag.at("--bgzf-out");
   if (a.has("--bgzf-level")) {
     if (!s.bgzf_out) error_exit("--bgzf-level needs --bgzf-out");
@@ -475,6 +486,9 @@ struct Run {
   // stop is a BGZF virtual offset and kr_fastx_open_at_bgzf takes over there.  Every `raw` buffer has a buffer for the members.
   bool bgzf = false;
   std::map<uint8_t*, uint8_t*> comp_of;
+  // --gpu-inflate, an ordinary gzip file: the reader's bytes come from the device inflater (kr_gzdev_read) in place of pread; offsets
+  // are inflated offsets, and an early stop hands over through kr_fastx_open_at_gzip from the inflater's restart point (kr_gzdev_point)
+  kr_gzdev* gz = nullptr;
   uint64_t chunk_cap() const { return s.chunk_bytes + (bgzf ? 2 * 65536 : 0); } // (a chunk may begin and end inside a member)
 
   OutputOrder order;
@@ -525,6 +539,7 @@ struct Run {
   void enqueue(std::unique_ptr<Job> j);
   void read_chunks();
   void read_chunks_bgzf();
+  void read_chunks_gzip();
   void chunks_done(uint64_t foreign_at);
   void read_host();
   void end_of_input();
@@ -661,6 +676,10 @@ void Run::open_input()
       gpu_parse = bgzf = true;
       qsize = (uint64_t)sb.st_size;
       fasta_parse = first == '>';
+    } else if (regular && gz && s.gpu_inflate) { // ordinary gzip, inflated on the first GPU (FASTA or FASTQ: read_chunks_gzip, from the first inflated byte)
+      if (kr_gzdev_open(s.query.c_str(), s.dev0, s.gz_super, s.gz_sub, s.gz_ratio, 8, &this->gz)) error_exit(kr_last_error());
+      gpu_parse = true;
+      qsize = (uint64_t)sb.st_size;
     } else if (!regular || gz) {
       if (qfd >= 0) close(qfd);
       qfd = -1; // ordinary gzip / not a regular file: the host reader
@@ -1163,6 +1182,58 @@ void Run::read_chunks()
   chunks_done(UINT64_MAX);
 }
 
+// --gpu-parse --gpu-inflate on an ordinary gzip file: read_chunks with kr_gzdev_read in place of pread.  The bytes behind a chunk's cut
+// are carried to the front of the next chunk's buffer; raw_off is an inflated offset.
+void Run::read_chunks_gzip()
+{
+  auto t_parse = Clock::now();
+  std::vector<uint8_t> carry_bytes;
+  uint64_t off = 0; // inflated offset of the next chunk's first byte
+  bool at_end = false, first = true;
+  while (!at_end) {
+    uint8_t* buf = nullptr;
+    {
+      std::unique_lock<std::mutex> lk(order.mu);
+      order.cv_work.wait(lk, [&] { return !raw_free.empty() || order.stopped_locked() || order.failed_locked(); });
+      if (order.stopped_locked() || order.failed_locked()) break; // (an early stop: nothing behind it will be used)
+      buf = raw_free.back();
+      raw_free.pop_back();
+    }
+    uint64_t got = carry_bytes.size();
+    if (got) memcpy(buf, carry_bytes.data(), got);
+    carry_bytes.clear();
+    while (got < s.chunk_bytes) {
+      uint64_t k = 0;
+      if (kr_gzdev_read(gz, buf + got, s.chunk_bytes - got, &k)) { // damage (the inflater hands out what lies in front of it first): the run fails here, with the chunk being filled
+        order.fail(kr_last_error());
+        at_end = true;
+        break;
+      }
+      if (k == 0) {
+        at_end = true;
+        break;
+      }
+      got += k;
+    }
+    if (order.failed() || got == 0) { // (the buffer goes back unused)
+      std::lock_guard<std::mutex> lk(order.mu);
+      raw_free.push_back(buf);
+      break;
+    }
+    if (first) fasta_parse = buf[0] == '>', first = false;
+    const uint64_t c = at_end ? 0 : fasta_parse ? kr_fasta_chunk_cut(buf, got) : kr_fastq_chunk_cut(buf, got);
+    const uint64_t cut = c ? c : got;
+    carry_bytes.assign(buf + cut, buf + got);
+    std::unique_ptr<Job> j(new Job());
+    j->raw = buf, j->raw_len = cut, j->raw_off = off, j->at_eof = at_end && cut == got;
+    j->fasta = fasta_parse, j->closed = at_end || (fasta_parse && c);
+    off += cut;
+    enqueue(std::move(j));
+  }
+  ns_parse += since(t_parse);
+  chunks_done(UINT64_MAX);
+}
+
 // Every chunk handed out is done (an earlier one may still stop early): then the first stop, if any, is final, and the host reader
 // takes over there.  foreign_at: where a block-gzipped file goes on with bytes that are no BGZF member (UINT64_MAX: nowhere) -- the
 // host reader's from that offset when no chunk stopped in front of it.
@@ -1177,6 +1248,12 @@ void Run::chunks_done(uint64_t foreign_at)
   uint64_t fb_off = 0;
   const bool stopped = order.stopped(&fb_off);
   if (order.failed()) return;
+  if (stopped && gz) { // zlib primed at the inflater's restart point in front of the stop (none kept that far back: from the file's start)
+    std::unique_ptr<kr_gzip_point> pt(new kr_gzip_point());
+    const bool have = kr_gzdev_point(gz, fb_off, pt.get()) == 0;
+    if (kr_fastx_open_at_gzip(s.query.c_str(), fb_off, have ? pt.get() : nullptr, &fx)) error_exit(kr_last_error());
+    return;
+  }
   if (stopped && (bgzf ? kr_fastx_open_at_bgzf(s.query.c_str(), fb_off >> 16, (uint32_t)(fb_off & 0xFFFFu), &fx) : kr_fastx_open_at(s.query.c_str(), fb_off, &fx)))
     error_exit(kr_last_error());
   if (!stopped && foreign_at != UINT64_MAX && kr_fastx_open_at_bgzf(s.query.c_str(), foreign_at, 0, &fx)) error_exit(kr_last_error());
@@ -1364,6 +1441,12 @@ int Run::finish()
   if (s.timing && s.gpu_seek) fprintf(stderr, "[timing] gpu-seek: %llu reads through the seek kernels\n", (unsigned long long)nreads_seek.load());
   if (s.timing && gpu_parse)
     fprintf(stderr, "[timing] gpu-parse: %llu %s records found on the device\n", (unsigned long long)nreads_dev.load(), fasta_parse ? "FASTA" : "FASTQ");
+  if (s.timing && gz) {
+    uint64_t c[11] = {0};
+    (void)kr_gzdev_counters(gz, c);
+    fprintf(stderr, "[timing] gpu-inflate: %llu super-chunks, %llu sub-chunks linked, %llu without a start, %llu dropped, host ranges %llu; kernels: search %.1f ms, decode %.1f ms, chain %.1f ms, resolve %.1f ms; copies %.1f ms; %llu compressed bytes taken in twice\n",
+            (unsigned long long)c[0], (unsigned long long)c[1], (unsigned long long)c[2], (unsigned long long)c[3], (unsigned long long)c[4], c[6] / 1e3, c[7] / 1e3, c[8] / 1e3, c[9] / 1e3, c[10] / 1e3, (unsigned long long)c[5]);
+  }
   if (s.timing && s.plain_dist()) // (a batch split at capacity counts once per piece)
     fprintf(stderr, "[timing] report text: %llu batches written from device text, %llu through the host formatter\n", (unsigned long long)nb_dev_text.load(),
             (unsigned long long)nb_host_text.load());
@@ -1386,6 +1469,7 @@ int Run::finish()
   }
   auto t_down = Clock::now();
   kr_fastx_close(fx); // (the reader's thread pool and chunk buffers)
+  kr_gzdev_close(gz);
   for (kr_stream* st : streams_to_free) kr_stream_destroy(st);
   for (auto* d : dix) kr_index_free(d);
   kr_host_index_free(hx);
@@ -1405,7 +1489,7 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
   std::thread writer([&r] { r.write_loop(); });
   if (s.seek) fprintf(stderr, "Seeking query sequences in the sketch...\n");
   if (!s.place && !s.seek) fprintf(stderr, "Estimating distances between given sequences and references...\n");
-  if (r.gpu_parse) r.bgzf ? r.read_chunks_bgzf() : r.read_chunks();
+  if (r.gpu_parse) r.gz ? r.read_chunks_gzip() : r.bgzf ? r.read_chunks_bgzf() : r.read_chunks();
   if (r.fx) r.read_host();
   r.end_of_input();
   for (auto& w : workers) w.join();
