@@ -886,6 +886,44 @@ KR_API int kr_stream_seek_enable(kr_stream*, uint64_t max_text_bytes, uint64_t m
 KR_API int kr_batch_collect_seek(kr_stream*, kr_seek_view* out);
 KR_API int kr_debug_seek_layout(uint32_t* out4);   /* [0] = T (positions per unit), [1] positions per segment, [2] waves per workgroup of the hist kernel, [3] reads per prefix block; no device needed */
 KR_API int kr_debug_seek_ms(kr_stream*, float* ms3); /* hist (with the unit count), solve, text of the last seek batch (HIP events) */
+
+/* ---- the reads of a seek batch split by their DIST, on the device (csrc/kr_dev_extract.inc; docs/design/13_seek.md 13.6;
+ *      INTEGRATION.md "Reads split by a seek batch") ----
+ * A seek batch that a record finder queued (kr_batch_submit_fastq / _fasta / _bgzf with KR_SEEK) has its chunk in device memory, and
+ * its accepted records tile the bytes [0, consumed) without a gap.  On a stream with extract enabled those bytes are partitioned
+ * behind the solve kernel: a read is MATCHED when its DIST is not NaN and, with a threshold, DIST <= max_dist (compared in double on
+ * the value the report text is formatted from).  Every record moves as the exact bytes it has in the chunk -- header comments,
+ * qualities, line wrapping, CRLF --, the matched records to the front, the unmatched ones behind them, both in input order; the
+ * host only copies and writes.  Nothing else of the batch changes: kr_batch_collect_text / kr_batch_collect_seek give what they give
+ * on a stream without extract, and a seek batch from host arrays (kr_batch_submit / _text with KR_SEEK) runs as before and has
+ * nothing to extract.
+ *   kr_stream_extract_enable   once per stream, after kr_stream_seek_enable and kr_stream_fastq_enable (else, or twice: KR_ERR_STATE);
+ *                           max_dist NaN: every read with a DIST is matched; negative or infinite: KR_ERR_ARG.  Allocates the record
+ *                           starts, the prefix arrays, one output buffer of the chunk's size and its page-locked mirror
+ *   kr_stream_extract_max   another threshold for the batches submitted from now on (KR_ERR_ARG leaves the rule in force as it is)
+ *   kr_batch_collect_extract       waits for the batch; copies back the parts named in `which` (KR_EXTRACT_MATCHED | _UNMATCHED;
+ *                           0 or an unknown bit: KR_ERR_ARG); a part not asked for has a NULL pointer and length 0, the four counts
+ *                           are always filled
+ *   kr_batch_collect_extract_bgzf  the same with each non-empty part deflated into BGZF members by the stream's deflate kernels, at
+ *                           `level` (1 or 2, else KR_ERR_ARG) and the stream's member length (kr_stream_bgzf_member): byte for byte
+ *                           kr_bgzf_deflate_host_member(part, n, level, member_bytes, ...).  An empty part has length 0: no member.
+ *                           kr_stream_bgzf_out_enable is not needed; the deflate buffers grow with the parts
+ * KR_ERR_STATE from the collect calls: extract not enabled; the last submit was not a raw-bytes seek submit; it accepted no record;
+ * the batch was a dist batch.  The pointers are page-locked and stay valid until the stream's next submit (the members' also
+ * until a later kr_batch_collect_extract_bgzf call on the same batch overwrites them). */
+#define KR_EXTRACT_MATCHED   1u
+#define KR_EXTRACT_UNMATCHED 2u
+typedef struct kr_extract_view {
+  uint32_t nreads, nmatched;
+  uint64_t matched_bytes, unmatched_bytes;   /* record bytes of each part (plain) */
+  const uint8_t *matched, *unmatched;        /* page-locked, valid until the stream's next submit; NULL when not asked for */
+  uint64_t matched_len, unmatched_len;       /* bytes at the pointers: == *_bytes plain, the members' bytes for _bgzf */
+} kr_extract_view;
+KR_API int kr_stream_extract_enable(kr_stream*, double max_dist);   /* NaN: every read with a finite DIST is matched */
+KR_API int kr_stream_extract_max(kr_stream*, double max_dist);      /* between batches */
+KR_API int kr_batch_collect_extract(kr_stream*, uint32_t which, kr_extract_view* out);
+KR_API int kr_batch_collect_extract_bgzf(kr_stream*, uint32_t which, uint32_t level, kr_extract_view* out);
+KR_API int kr_debug_extract_ms(kr_stream*, float* ms);              /* the extract kernels of the last batch, HIP events */
 /* tests: the tiled form of the batch last submitted on the stream as it lies on the device, laid out by the host (a host batch)
  * or by kernels (KR_TILE_DEVICE): reads of the tiled batch and long sequences; voff [nv + 1] where every read of the tiled batch
  * starts in its bases, vtile [nv] 1 = a tile of a long sequence, rfirst [nreads] the caller's read's first read of the tiled batch,

@@ -64,6 +64,14 @@ class KrSeekView(C.Structure):
                 ("hist", u32p), ("onmers", u32p)]
 
 
+KR_EXTRACT_MATCHED, KR_EXTRACT_UNMATCHED = 1, 2
+
+
+class KrExtractView(C.Structure):
+    _fields_ = [("nreads", C.c_uint32), ("nmatched", C.c_uint32), ("matched_bytes", C.c_uint64), ("unmatched_bytes", C.c_uint64),
+                ("matched", C.c_void_p), ("unmatched", C.c_void_p), ("matched_len", C.c_uint64), ("unmatched_len", C.c_uint64)]
+
+
 class KrHit(C.Structure):
     _fields_ = [("read", C.c_uint32), ("kpos", C.c_uint32), ("strand", C.c_uint32), ("lib", C.c_uint32),
                 ("cmer_index", C.c_uint64), ("hd", C.c_uint32), ("se", C.c_uint32)]
@@ -174,6 +182,7 @@ EXPORTS = [
     "kr_index_stats_cpu", "kr_index_stats_device", "kr_index_stats_free", "kr_host_index_lib_info", "kr_format_inspect", "kr_debug_index_stats",
     "kr_debug_index_stats_ms",
     "kr_stream_seek_enable", "kr_batch_collect_seek", "kr_debug_seek_layout", "kr_debug_seek_ms",
+    "kr_stream_extract_enable", "kr_stream_extract_max", "kr_batch_collect_extract", "kr_batch_collect_extract_bgzf", "kr_debug_extract_ms",
     "kr_stream_bgzf_enable", "kr_batch_submit_bgzf", "kr_debug_bgzf_inflate", "kr_debug_bgzf_inflate_host", "kr_debug_bgzf_ms",
     "kr_bgzf_member_size", "kr_bgzf_walk", "kr_bgzf_chunk_cut", "kr_fastx_open_at_bgzf",
     "kr_bgzf_deflate_bound", "kr_bgzf_deflate_host", "kr_bgzf_eof", "kr_debug_bgzf_deflate_stats",
@@ -357,6 +366,11 @@ def load():
     lib.kr_batch_collect_seek.argtypes = [vp, C.POINTER(KrSeekView)]
     lib.kr_debug_seek_layout.argtypes = [u32p]
     lib.kr_debug_seek_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    lib.kr_stream_extract_enable.argtypes = [vp, C.c_double]
+    lib.kr_stream_extract_max.argtypes = [vp, C.c_double]
+    lib.kr_batch_collect_extract.argtypes = [vp, C.c_uint32, C.POINTER(KrExtractView)]
+    lib.kr_batch_collect_extract_bgzf.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(KrExtractView)]
+    lib.kr_debug_extract_ms.argtypes = [vp, C.POINTER(C.c_float)]
     lib.kr_debug_tile_shape.argtypes = [C.c_uint64, C.c_uint32, u64p, u64p, u64p]
     lib.kr_fastx_next.argtypes = [vp, C.c_uint64, C.POINTER(KrFastxBatch)]
     lib.kr_fastx_detach.argtypes = [vp, C.POINTER(vp)]
@@ -994,6 +1008,39 @@ class Stream:
         ms = (C.c_float * 3)()
         check(self.lib.kr_debug_seek_ms(self.h, ms))
         return tuple(float(x) for x in ms)
+
+    def extract_enable(self, max_dist=float("nan")):
+        """kr_stream_extract_enable (after seek_enable and fastq_enable): the reads of this stream's raw-bytes seek batches are split into
+        matched and unmatched bytes on the device (csrc/kr_dev_extract.inc); NaN: every read with a DIST is matched"""
+        check(self.lib.kr_stream_extract_enable(self.h, float(max_dist)))
+
+    def extract_max(self, max_dist):
+        """kr_stream_extract_max: the threshold of the batches submitted from now on (NaN: none)"""
+        check(self.lib.kr_stream_extract_max(self.h, float(max_dist)))
+
+    @staticmethod
+    def _extract_dict(v):
+        return {"nreads": int(v.nreads), "nmatched": int(v.nmatched), "matched_bytes": int(v.matched_bytes), "unmatched_bytes": int(v.unmatched_bytes),
+                "matched": None if not v.matched else C.string_at(v.matched, v.matched_len),
+                "unmatched": None if not v.unmatched else C.string_at(v.unmatched, v.unmatched_len)}
+
+    def collect_extract(self, which=KR_EXTRACT_MATCHED | KR_EXTRACT_UNMATCHED):
+        """kr_batch_collect_extract: the counts and copies of the parts named in `which` (a part not asked for is None)"""
+        v = KrExtractView()
+        check(self.lib.kr_batch_collect_extract(self.h, int(which), C.byref(v)))
+        return self._extract_dict(v)
+
+    def collect_extract_bgzf(self, level, which=KR_EXTRACT_MATCHED | KR_EXTRACT_UNMATCHED):
+        """kr_batch_collect_extract_bgzf: as collect_extract with each part as BGZF members deflated on the device (an empty part: b"")"""
+        v = KrExtractView()
+        check(self.lib.kr_batch_collect_extract_bgzf(self.h, int(which), int(level), C.byref(v)))
+        return self._extract_dict(v)
+
+    def extract_ms(self):
+        """kr_debug_extract_ms: device milliseconds of the last batch's extract kernels"""
+        ms = C.c_float(0)
+        check(self.lib.kr_debug_extract_ms(self.h, C.byref(ms)))
+        return float(ms.value)
 
     def format_dist(self, host_index, names):
         arr = (C.c_char_p * len(names))(*[n.encode() for n in names])

@@ -48,6 +48,7 @@
 //   kr_dev_seek.inc        `seek` on kernels of its own (a batch flagged KR_SEEK): unit split, histograms per strand, solver, report text
 //   kr_dev_fastq.inc       FASTQ records found in a chunk of raw file bytes (kr_batch_submit_fastq)
 //   kr_dev_fasta.inc       FASTA records found in a chunk of raw file bytes, every pass parallel over bytes (kr_batch_submit_fasta)
+//   kr_dev_extract.inc     the reads of a seek batch split into matched and unmatched bytes: a stable partition of the chunk by a per-record verdict (kr_stream_extract_enable)
 //   kr_dev_bgzf.inc        the members of a block-gzipped chunk inflated into the record finders' buffer (kr_batch_submit_bgzf; decoder: kr_inflate.h)
 //   kr_dev_gzip.inc        a super-chunk of an ORDINARY gzip stream inflated by four kernels: search, symbolic decode, chain, resolve (kr_gzdev_read; stages: kr_inflate_sym.h)
 //   kr_dev_deflate.inc     report text deflated into BGZF members, one wave per member (kr_batch_collect_text_bgzf; encoder: kr_deflate.h)
@@ -63,6 +64,7 @@
 //   kr_host_gzip.inc       kr_gzdev_open / _read / _point / _counters / _close, kr_debug_gzdev_inflate (the driver between the kernels: kr_gzip_super.h)
 //   kr_host_deflate.inc    kr_stream_bgzf_out_enable, kr_stream_bgzf_member, kr_stream_place_bgzf, kr_batch_collect_text_bgzf, kr_debug_bgzf_deflate / _at / _ms
 //   kr_host_place.inc      kr::place_on_device (launch of the place kernels for kr_place_stream and kr_place_stream_parsed)
+//   kr_host_extract.inc    kr_stream_extract_enable / _max, kr_batch_collect_extract / _bgzf, kr_debug_extract_ms
 //   kr_host_seek.inc       kr_stream_seek_enable, a KR_SEEK batch's submit / wait, kr_batch_collect_seek, kr_debug_seek_layout / _ms
 //   (below, in this file)  kr_host_alloc, debug entry points, kr_llh_batch, kr_llh_eval_indexed
 #include <hip/hip_runtime.h>
@@ -109,6 +111,7 @@ namespace {
 #include "kr_dev_seek.inc"
 #include "kr_dev_fastq.inc"
 #include "kr_dev_fasta.inc"
+#include "kr_dev_extract.inc"
 #include "kr_dev_bgzf.inc"
 #include "kr_dev_gzip.inc"
 #include "kr_dev_deflate.inc"
@@ -180,6 +183,7 @@ LlhConst make_llh_const(uint32_t k, uint32_t h, uint32_t th)
 #include "kr_host_gzip.inc"
 #include "kr_host_deflate.inc"
 #include "kr_host_place.inc"
+#include "kr_host_extract.inc"
 #include "kr_host_seek.inc"
 
 // Room for `need` doubles in the index's likelihood workspace, device and page-locked (under ix->llh_mu); grown with 25 % to spare

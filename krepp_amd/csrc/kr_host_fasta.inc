@@ -25,6 +25,7 @@ int submit_fasta(kr_stream* s, const char* fn, const uint8_t* raw, uint64_t nbyt
   hipStream_t st = s->lanes[0].stream;
   io.tile_st = f.d_tile_st, io.tile_gr = f.d_tile_gr, io.hs = f.d_hs, io.ga = f.d_ga, io.rec_hg = f.d_hg, io.rec_he = f.d_he;
   io.closed = closed ? 1u : 0u;
+  f.last_fasta = true;
   const uint32_t tgrid = std::min<uint32_t>((uint32_t)((nbytes + kFqTile - 1) / kFqTile), 16384u);
   const uint32_t rgrid = std::min<uint32_t>((s->max_reads + 3) / 4, 8192u), bgrid = std::min<uint32_t>(s->max_reads / kFqRecBlock + 1, 4096u);
   if ((rc = fq_mark(s))) return rc;

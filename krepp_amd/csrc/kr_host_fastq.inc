@@ -104,6 +104,7 @@ int submit_fastq(kr_stream* s, const char* fn, const uint8_t* raw, uint64_t nbyt
   kr_stream::Fastq& f = s->fq;
   hipStream_t st = s->lanes[0].stream;
   io.nl = f.d_nl, io.nl_cap = 4u * s->max_reads, io.rec_lines = 4;
+  f.last_fasta = false;
   const uint32_t ntiles = (uint32_t)((nbytes + kFqTile - 1) / kFqTile);
   const uint32_t rgrid = std::min<uint32_t>((s->max_reads + 3) / 4, 8192u), bgrid = std::min<uint32_t>(s->max_reads / kFqRecBlock + 1, 4096u);
   if ((rc = fq_mark(s))) return rc;

@@ -70,6 +70,8 @@ struct Batch {
   bool text_made = false;    // submitted with ids, and its text kernels were queued
   bool seek = false;         // a seek batch (kr_host_seek.inc)
   bool seek_view = false;    // ... whose values are in the page-locked mirrors
+  bool extract = false;      // ... whose reads the extract kernels split (kr_host_extract.inc): a record finder queued it on an extract stream
+  uint32_t extract_have = 0; // ... and the parts (KR_EXTRACT_*) that are in the page-locked mirror
   uint32_t nrecs = 0;
   uint64_t nhits = 0;
   uint64_t ndist = 0, h_ndist = 0; // entries of the batch's list of distinct values (set by kr_batch_wait: a device view shows it too), of its host copy
@@ -254,6 +256,7 @@ struct kr_stream {
     uint32_t *d_tile_st = nullptr, *d_tile_gr = nullptr; // [tiles of raw_cap + 1]
     uint32_t *d_hs = nullptr, *d_ga = nullptr;           // [max_reads + 2]
     uint32_t *d_hg = nullptr, *d_he = nullptr;           // [max_reads]
+    bool last_fasta = false; // the last chunk's records were found by the FASTA kernels (hs), not the FASTQ ones (nl)
   } fq;
   // block-gzipped chunks inflated into fq.d_raw (kr_dev_bgzf.inc; kr_stream_bgzf_enable)
   struct Bgzf {
@@ -283,6 +286,18 @@ struct kr_stream {
     hipEvent_t ev0 = nullptr, ev1 = nullptr; // kr_debug_bgzf_deflate_ms: around the three kernels, once asked for
     bool ev_set = false;
   } bgzf_out;
+  // the reads of a seek batch split by their DIST on the device (kr_dev_extract.inc, kr_host_extract.inc; kr_stream_extract_enable)
+  struct Extract {
+    bool on = false;
+    double max_dist = 0; // NaN: every read with a finite DIST is matched
+    uint32_t *d_start = nullptr, *d_mpre = nullptr; // [max_reads + 1]
+    uint64_t* d_bsum = nullptr;                     // [max_reads / kRowBlock + 2]
+    uint8_t *d_out = nullptr, *h_out = nullptr;     // [raw_cap rounded up to 16, + 16]: matched bytes, then unmatched bytes
+    unsigned long long *d_res = nullptr, *h_res = nullptr; // [4] matched bytes, matched records, records, consumed
+    PinBuf<uint8_t> h_members; // kr_batch_collect_extract_bgzf: the matched part's members, then the unmatched part's
+    hipEvent_t ev[2] = {};     // around the extract kernels
+    bool timed = false;
+  } extract;
   Batch batch;     // the batch in flight
   LastParse parse; // the last record finder's call
   // state
@@ -1086,6 +1101,8 @@ void kr_stream_destroy(kr_stream* s)
   if (s->bgzf_out.ev0) (void)hipEventDestroy(s->bgzf_out.ev0);
   if (s->bgzf_out.ev1) (void)hipEventDestroy(s->bgzf_out.ev1);
   for (auto& e : s->seek.ev)
+    if (e) (void)hipEventDestroy(e);
+  for (auto& e : s->extract.ev)
     if (e) (void)hipEventDestroy(e);
   delete s; // (every DevBuf / PinBuf of the stream frees itself here: the device is set, the lanes' streams have been waited for)
 }

@@ -12,6 +12,7 @@
 #include <cerrno>
 #include <chrono>
 #include <cmath>
+#include <limits>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
@@ -54,7 +55,7 @@ static const std::map<std::string, std::string> kAlias = {
   {"-i", "--index-dir"}, {"-q", "--query"}, {"-o", "--output-path"}, {"-t", "--nwk-file"}, {"-k", "--kmer-len"},
   {"-w", "--win-len"}, {"-h", "--num-positions"}, {"-m", "--modulo-lsh"}, {"-r", "--residue-lsh"}, {"-l", "--lineage-file"},
 };
-static const char* kFlags[] = {"--multi", "--filter", "--summarize", "--frac", "--verbose", "--gpu-minimizers", "--gpu-keys", "--gpu-colours", "--tabular", "--gpu-parse", "--gpu-seek", "--gpu-stats", "--bgzf-out", "--gpu-deflate", "--gpu-inflate"};
+static const char* kFlags[] = {"--multi", "--filter", "--summarize", "--frac", "--verbose", "--gpu-minimizers", "--gpu-keys", "--gpu-colours", "--tabular", "--gpu-parse", "--gpu-seek", "--gpu-stats", "--bgzf-out", "--gpu-deflate", "--gpu-inflate", "--extract-bgzf"};
 
 // options as in the reference's CLI (src/krepp.cpp:516-675); the texts are this build's own
 static void print_help(const std::string& sub)
@@ -106,7 +107,11 @@ static void print_help(const std::string& sub)
            "  -i, --sketch-path PATH     sketch file (as written by `krepp sketch`)\n%s"
            "      --gpu-parse            FASTA/FASTQ records found on the GPU (identical output; plain files, and BGZF files, inflated on the GPU; others keep the host reader)\n"
            "      --gpu-inflate          with --gpu-parse: ordinary gzip files are inflated on the GPU too (identical output; without it they keep the host reader)\n"
-           "      --gpu-seek             seek kernels and report text on the GPU (identical output)\n",
+           "      --gpu-seek             seek kernels and report text on the GPU (identical output)\n"
+           "      --extract-matched FILE   with --gpu-parse --gpu-seek: the reads whose row carries a DIST, as the exact bytes they have in the input, split on the GPU\n"
+           "      --extract-unmatched FILE the other reads (rows with NaN, or above --extract-max); either file or both\n"
+           "      --extract-max D        a read is matched only when its DIST is at most D, 0..1 [no limit]\n"
+           "      --extract-bgzf         the extract files are BGZF, deflated on the GPU (--bgzf-level and --bgzf-member apply)\n",
            query_opts);
   if (sub.empty() || sub == "index")
     printf("\nkrepp index -i MAP.tsv -o DIR: build an index (reference ID <tab> FASTA path per line)\n"
@@ -185,6 +190,12 @@ struct Settings {
   uint32_t bgzf_member = 65280; // --bgzf-member: text bytes a member takes, on the workers' streams and in Run::deflated
   bool gpu_deflate = false; // place --bgzf-out --gpu-deflate: kr_stream_place_bgzf on the workers' streams
   bool bgzf_out = false;  // --bgzf-out: every byte of the report goes out as BGZF members (Run::put, Worker::collect)
+  // seek --gpu-parse --gpu-seek --extract-matched / --extract-unmatched: the reads split on the device (kr_stream_extract_enable)
+  std::string extract_matched, extract_unmatched;
+  double extract_max = std::numeric_limits<double>::quiet_NaN(); // --extract-max: NaN = every read with a DIST
+  bool extract_bgzf = false;                                     // --extract-bgzf: the two files as BGZF members, deflated on the device
+  bool extract() const { return !extract_matched.empty() || !extract_unmatched.empty(); }
+  uint32_t extract_which() const { return (extract_matched.empty() ? 0u : KR_EXTRACT_MATCHED) | (extract_unmatched.empty() ? 0u : KR_EXTRACT_UNMATCHED); }
   int ngpus = 1, dev0 = 0, wpg = 2, nworkers = 2, write_threads = 4;
   uint32_t max_reads = 0;
   uint64_t batch_bases = 0, max_bases = 0, chunk_bytes = 0, max_records = 0, text_bytes = 0;
@@ -235,14 +246,30 @@ static Settings resolve_settings(const Args& a, const std::string& invocation, i
   if (const char* e = getenv("KR_GZDEV_SUB")) s.gz_sub = (uint32_t)strtoul(e, nullptr, 10);
   if (const char* e = getenv("KR_GZDEV_RATIO")) s.gz_ratio = (uint32_t)strtoul(e, nullptr, 10);
   s.bgzf_out = a.flag.count("--bgzf-out") && a.flag.at("--bgzf-out");
+  s.extract_matched = a.get("--extract-matched"), s.extract_unmatched = a.get("--extract-unmatched");
+  s.extract_bgzf = a.flag.count("--extract-bgzf") && a.flag.at("--extract-bgzf");
+  if (s.extract() || a.has("--extract-matched") || a.has("--extract-unmatched") || a.has("--extract-max") || s.extract_bgzf) {
+    if (!seek) error_exit("--extract-matched, --extract-unmatched, --extract-max and --extract-bgzf are options of `seek`");
+    if (!s.gpu_parse || !s.gpu_seek) error_exit("--extract-* needs --gpu-parse and --gpu-seek: the reads are split on the GPU, from the bytes the record finder holds there");
+    if (!s.extract()) error_exit("--extract-max and --extract-bgzf need --extract-matched or --extract-unmatched");
+    if (a.has("--extract-max")) {
+      const std::string v = a.get("--extract-max");
+      char* end = nullptr;
+      s.extract_max = strtod(v.c_str(), &end);
+      if (v.empty() || *end || !(s.extract_max >= 0.0 && s.extract_max <= 1.0)) error_exit("--extract-max: a distance in [0, 1], not " + v);
+    }
+    if (s.extract_matched == s.extract_unmatched) error_exit("--extract-matched and --extract-unmatched name the same file: " + s.extract_matched);
+    if (a.has("--output-path") && (a.get("--output-path") == s.extract_matched || a.get("--output-path") == s.extract_unmatched))
+      error_exit("an --extract-* file is also the report's (-o): " + a.get("--output-path"));
+  }
   if (a.has("--bgzf-level")) {
-    if (!s.bgzf_out) error_exit("--bgzf-level needs --bgzf-out");
+    if (!s.bgzf_out && !s.extract_bgzf) error_exit("--bgzf-level needs --bgzf-out");
     const std::string v = a.get("--bgzf-level");
     if (v != "1" && v != "2") error_exit("--bgzf-level: 1 (fixed Huffman codes) or 2 (dynamic codes), not " + v);
     s.bgzf_level = (uint32_t)(v[0] - '0');
   }
   if (a.has("--bgzf-member")) {
-    if (!s.bgzf_out) error_exit("--bgzf-member needs --bgzf-out");
+    if (!s.bgzf_out && !s.extract_bgzf) error_exit("--bgzf-member needs --bgzf-out");
     const std::string v = a.get("--bgzf-member");
     char* end = nullptr;
     const long m = strtol(v.c_str(), &end, 10);
@@ -309,6 +336,7 @@ struct Job {
   std::string own_blob;
   std::vector<const char*> own_names;
   std::string text;
+  std::string ex_matched, ex_unmatched; // seek --extract-*: the bytes the two files take from this job, plain or BGZF members
   std::vector<kr_placement> pls; // place --summarize: the placements, `read` = global read number
   uint64_t first_read = 0;
   // --gpu-parse: a chunk of the file's raw bytes (page-locked), cut at a guessed record start; its records are found on the device
@@ -507,6 +535,9 @@ struct Run {
 
   std::atomic<uint64_t> nreads_dev{0}; // records found on the device so far, in the output's order (advanced in a chunk's turn)
   std::atomic<uint64_t> nreads_seek{0}; // seek --gpu-seek: reads whose rows the seek kernels wrote ([timing] only)
+  // seek --extract-*: the two files (the writer's, in the report's order), and for [timing] the reads, record bytes and kernel time
+  FILE *ex_matched = nullptr, *ex_unmatched = nullptr;
+  std::atomic<uint64_t> ex_reads{0}, ex_nmatched{0}, ex_bytes_m{0}, ex_bytes_u{0}, ex_kernel_us{0};
   uint64_t nbatches = 0, nreads_total = 0; // the reader's
   // the writer's.  place --summarize: counts per placement-tree node, summed in input order; placements of a 512-read group that
   // straddles two jobs wait in `carry` (the groups are the reference's batches)
@@ -554,6 +585,8 @@ void Run::start_up(const Args& a)
     out = fopen(a.get("--output-path").c_str(), "w");
     if (!out) error_exit("Failed to open " + a.get("--output-path"));
   }
+  if (!s.extract_matched.empty() && !(ex_matched = fopen(s.extract_matched.c_str(), "wb"))) error_exit("Failed to open " + s.extract_matched);
+  if (!s.extract_unmatched.empty() && !(ex_unmatched = fopen(s.extract_unmatched.c_str(), "wb"))) error_exit("Failed to open " + s.extract_unmatched);
   fprintf(stderr, "Loading the index and initializing...\n");
   if (s.seek ? kr_host_sketch_load(s.index_arg.c_str(), &hx) : kr_host_index_load(s.index_arg.c_str(), &hx)) error_exit(kr_last_error());
   kr_host_index_view(hx, &view);
@@ -681,6 +714,9 @@ void Run::open_input()
       gpu_parse = true;
       qsize = (uint64_t)sb.st_size;
     } else if (!regular || gz) {
+      if (s.extract()) // (no host fallback: the host reader keeps neither qualities nor byte spans)
+        error_exit(std::string("--extract-*: ") + (regular ? "an ordinary gzip file needs --gpu-inflate" : "not a regular file") +
+                   " at input offset 0: the records must be ones the GPU record finder accepts (include/krepp_amd.h)");
       if (qfd >= 0) close(qfd);
       qfd = -1; // ordinary gzip / not a regular file: the host reader
     } else {
@@ -775,6 +811,8 @@ struct Worker {
   int run_chunk();
   int collect(kr_result_view* rv, const char** dtext, uint64_t* dlen, bool* on_device);
   int chunk_names(const uint8_t* raw, uint32_t n);
+  int collect_extract();
+  int extract_stop(const char* reason, uint64_t pos);
   void keep_placements(int rc, kr_placement* pp, uint64_t npp, uint64_t base);
   void emit(const char* p, size_t n, bool whole_job);
   void emit_host(const char* p, size_t n); // rows a host formatter made: through the host encoder with --bgzf-out
@@ -807,13 +845,14 @@ void Worker::loop()
     if (s.bgzf_level != 1 && kr_stream_bgzf_out_level(st, s.bgzf_level)) return r.worker_ready(kr_last_error());
     bgzf_dev = true;
   }
-  if (s.bgzf_out && s.bgzf_member != 65280 && kr_stream_bgzf_member(st, s.bgzf_member)) return r.worker_ready(kr_last_error());
+  if ((s.bgzf_out || s.extract_bgzf) && s.bgzf_member != 65280 && kr_stream_bgzf_member(st, s.bgzf_member)) return r.worker_ready(kr_last_error());
   if (s.gpu_deflate) {
     if (kr_stream_place_bgzf(st, s.bgzf_level)) return r.worker_ready(kr_last_error());
     bgzf_place = true;
   }
   if (r.gpu_parse && kr_stream_fastq_enable(st, r.chunk_cap())) return r.worker_ready(kr_last_error());
   if (r.bgzf && kr_stream_bgzf_enable(st, r.chunk_cap())) return r.worker_ready(kr_last_error());
+  if (s.extract() && kr_stream_extract_enable(st, s.extract_max)) return r.worker_ready(kr_last_error());
   const double t_ready = r.at();
   r.worker_ready(nullptr);
   while ((j = r.next_job())) {
@@ -1065,6 +1104,7 @@ int Worker::run_chunk()
       auto t_fmt = Clock::now();
       if (s.gpu_seek) {
         if (!rc) text.append(dtext, dlen);
+        if (!rc && s.extract()) rc = collect_extract();
       } else if (!rc && on_device) {
         ++r.nb_dev_text;
         emit(dtext, dlen, false);
@@ -1089,6 +1129,7 @@ int Worker::run_chunk()
       kr_free(txt);
       r.ns_fmt += since(t_fmt);
       if (rc == KR_ERR_CAPACITY) { // more records or text than a batch holds: the host reader takes over at this batch's first record
+        if (s.extract()) return extract_stop("more report text than a batch holds", pos);
         fell = true;
         break;
       }
@@ -1098,12 +1139,18 @@ int Worker::run_chunk()
     pos += fp.consumed;
     if (fp.status == KR_FASTQ_OK) break;
     if (fp.status == KR_FASTQ_CAPACITY && fp.nreads) continue;
+    if (s.extract()) // (no host fallback: nothing is silently left out of either file)
+      return extract_stop(fp.status == KR_FASTQ_NOT_CLEAN ? "a record that is not clean (CRLF in a FASTQ, a stray '>' '+' '@', a quality line of another length)"
+                          : fp.status == KR_FASTQ_INCOMPLETE ? "an incomplete record (cut short, or a last line without '\\n')"
+                                                             : "a record that does not fit a batch",
+                          pos);
     fell = true; // not clean, a record cut by the end of the chunk or the file: the host reader from here
     break;
   }
   // in the output's order: only a chunk that no earlier chunk's stop has dropped counts
   if (!r.order.wait_turn(*j)) {
     text.clear(), pls.clear(); // (`place` / `seek`: rows made before the earlier chunk's stop was known)
+    j->ex_matched.clear(), j->ex_unmatched.clear();
     return 0;
   }
   for (size_t q = 0; q < wc_job.size(); ++q) wc[q] += wc_job[q];
@@ -1115,6 +1162,38 @@ int Worker::run_chunk()
   if (s.gpu_seek) r.nreads_seek += nr_job;
   if (fell) r.order.stop_at(*j, j->comp ? j->voffset(pos) : j->raw_off + pos);
   return 0;
+}
+
+// seek --extract-*: the parts of the batch just collected, appended to the job's two byte strings (plain, or as BGZF members)
+int Worker::collect_extract()
+{
+  kr_extract_view v;
+  const int rc = s.extract_bgzf ? kr_batch_collect_extract_bgzf(st, s.extract_which(), s.bgzf_level, &v) : kr_batch_collect_extract(st, s.extract_which(), &v);
+  if (rc) return rc;
+  if (v.matched) j->ex_matched.append((const char*)v.matched, (size_t)v.matched_len);
+  if (v.unmatched) j->ex_unmatched.append((const char*)v.unmatched, (size_t)v.unmatched_len);
+  r.ex_reads += v.nreads, r.ex_nmatched += v.nmatched, r.ex_bytes_m += v.matched_bytes, r.ex_bytes_u += v.unmatched_bytes;
+  float ms = 0;
+  if (s.timing && kr_debug_extract_ms(st, &ms) == 0) r.ex_kernel_us += (uint64_t)(ms * 1000.0f);
+  return 0;
+}
+
+// seek --extract-*: a chunk the device cannot take whole ends the run (the host reader keeps neither qualities nor byte spans)
+int Worker::extract_stop(const char* reason, uint64_t pos)
+{
+  // N is a byte of the file where it can be: a plain file's offset; for a block-gzipped chunk the file offset of the BGZF member that
+  // holds the record's first byte, with the inflated byte inside it named beside the reason (together the virtual offset the host
+  // reader is handed at such a stop); for ordinary gzip (--gpu-inflate) only the inflated offset exists
+  std::string why = reason;
+  uint64_t at = j->raw_off + pos;
+  if (j->comp) {
+    const uint64_t v = j->voffset(pos);
+    at = v >> 16, why += " (inflated byte " + std::to_string(v & 0xFFFFu) + " of the BGZF member)";
+  } else if (r.gz)
+    why += " (offset in the inflated stream)";
+  r.order.fail("--extract-*: " + why + " at input offset " + std::to_string(at) +
+               ": the records must be ones the GPU record finder accepts (include/krepp_amd.h)");
+  return KR_ERR_FORMAT;
 }
 
 // the writer thread: the jobs' texts in input order (jobs whose rows a worker wrote pass through empty)
@@ -1138,6 +1217,8 @@ void Run::write_loop()
     } else {
       auto t_w = Clock::now();
       fwrite(j->text.data(), 1, j->text.size(), out);
+      if (ex_matched) fwrite(j->ex_matched.data(), 1, j->ex_matched.size(), ex_matched);
+      if (ex_unmatched) fwrite(j->ex_unmatched.data(), 1, j->ex_unmatched.size(), ex_unmatched);
       ns_write += since(t_w);
     }
     j.reset();
@@ -1432,6 +1513,15 @@ int Run::finish()
     fwrite(eof_member, 1, sizeof(eof_member), out);
   }
   if (out != stdout) fclose(out);
+  for (FILE* f : {ex_matched, ex_unmatched}) {
+    if (!f) continue;
+    if (s.extract_bgzf) { // the end member, once, last
+      uint8_t eof_member[28];
+      kr_bgzf_eof(eof_member);
+      fwrite(eof_member, 1, sizeof(eof_member), f);
+    }
+    if (fclose(f) != 0) error_exit("Failed to write an --extract-* file");
+  }
   const double sec = at();
   fprintf(stderr, place ? "Done placing queries, elapsed: %g sec (%.0f reads/s on %d GPU(s))\n" : seek ? "Done seeking query sequences, elapsed: %g sec (%.0f reads/s on %d GPU(s))\n" : "Done estimating distances, elapsed: %g sec (%.0f reads/s on %d GPU(s))\n", sec,
           sec > 0 ? nreads_total / sec : 0.0, s.ngpus);
@@ -1439,6 +1529,9 @@ int Run::finish()
     fprintf(stderr, "[timing] parse %.3f s, job hand-over (incl. waiting for queue space) %.3f s, device %.3f s, format %.3f s, write %.3f s; of the elapsed time, until the last worker had its stream and page-locked buffers: %.3f s (the reader parses meanwhile)\n",
             ns_parse / 1e9, ns_job / 1e9, ns_dev / 1e9, ns_fmt / 1e9, ns_write / 1e9, std::chrono::duration<double>(t_loop - t_init).count());
   if (s.timing && s.gpu_seek) fprintf(stderr, "[timing] gpu-seek: %llu reads through the seek kernels\n", (unsigned long long)nreads_seek.load());
+  if (s.timing && s.extract())
+    fprintf(stderr, "[timing] extract: %llu matched of %llu reads, %llu + %llu bytes, %.3f ms of kernels\n", (unsigned long long)ex_nmatched.load(), (unsigned long long)ex_reads.load(),
+            (unsigned long long)ex_bytes_m.load(), (unsigned long long)ex_bytes_u.load(), ex_kernel_us.load() / 1e3);
   if (s.timing && gpu_parse)
     fprintf(stderr, "[timing] gpu-parse: %llu %s records found on the device\n", (unsigned long long)nreads_dev.load(), fasta_parse ? "FASTA" : "FASTQ");
   if (s.timing && gz) {
