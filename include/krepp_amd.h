@@ -673,6 +673,12 @@ KR_API int kr_debug_fastq_parse_ms(kr_stream*, float* ms);
 KR_API int kr_batch_submit_fasta(kr_stream*, const uint8_t* raw, uint64_t nbytes, uint32_t flags, uint32_t closed, kr_fastq_parse* out);
 KR_API uint64_t kr_fasta_chunk_cut(const uint8_t* buf, uint64_t n);
 KR_API uint64_t kr_fastq_chunk_cut(const uint8_t* buf, uint64_t n);
+/* kr_fastq_pair_cut (no device): the cut of a reader of PAIRED four-line FASTQ (`krepp seek --query2 / --interleaved`).  a and b each
+ * begin at a record start; *nrec is the largest n <= max_records such that both hold 4n complete lines, *cut_a / *cut_b the byte
+ * behind the 4n-th '\n' of each (0 when n is 0).  b == NULL (nb ignored, cut_b may be NULL): one buffer with the mates as
+ * neighbours -- the largest EVEN n.  Only newlines are counted: whether the records are clean is the device record finder's to say.
+ * KR_ERR_ARG: a, cut_a or nrec is NULL, or b without cut_b. */
+KR_API int kr_fastq_pair_cut(const uint8_t* a, uint64_t na, const uint8_t* b, uint64_t nb, uint32_t max_records, uint64_t* cut_a, uint64_t* cut_b, uint32_t* nrec);
 
 /* ---- block-gzipped bytes inflated on the device (csrc/kr_inflate.h, csrc/kr_dev_bgzf.inc; docs/design/08 "BGZF on the device") ----
  * A BGZF file is a run of independent gzip members of at most 64 KB of inflated bytes; each announces its compressed size ("BC"
@@ -910,9 +916,30 @@ KR_API int kr_debug_seek_ms(kr_stream*, float* ms3); /* hist (with the unit coun
  *                           kr_stream_bgzf_out_enable is not needed; the deflate buffers grow with the parts
  * KR_ERR_STATE from the collect calls: extract not enabled; the last submit was not a raw-bytes seek submit; it accepted no record;
  * the batch was a dist batch.  The pointers are page-locked and stay valid until the stream's next submit (the members' also
- * until a later kr_batch_collect_extract_bgzf call on the same batch overwrites them). */
+ * until a later kr_batch_collect_extract_bgzf call on the same batch overwrites them).
+ *
+ * PAIRED READS (docs/design/13_seek.md 13.7): the mates of a pair are split together, so that record i of the matched part of file 1
+ * is the mate of record i of the matched part of file 2, and the same for the unmatched parts.
+ *   kr_stream_extract_defer  between batches, after kr_stream_extract_enable (else KR_ERR_STATE).  on != 0: a raw-bytes seek submit
+ *                           queues no extract kernels; the collect calls answer KR_ERR_STATE (naming kr_batch_extract_pair) until
+ *                           the pair call.  0: every batch is split by its own reads again (the default)
+ *   kr_batch_extract_pair   a and b hold the mates: record r of a's batch and record r of b's; a == b: one interleaved batch, the
+ *                           mate of record r is record r ^ 1.  A pair is matched under KR_PAIR_ANY when either mate is matched by
+ *                           the rule above, under KR_PAIR_BOTH when both are.  One kernel writes a pair value per record (ANY: the
+ *                           smaller distance that is not NaN; BOTH: NaN when either is, else the larger), and the extract kernels
+ *                           run on it for each stream; all of it is queued on a's lane, between two events that order it behind
+ *                           b's batch and in front of b's next wait.  Afterwards the collect calls work on each stream as ever
+ *                           (nmatched: the matched PAIRS).  Calling it again on the same batches, with the other rule for
+ *                           instance, overwrites the parts.  kr_batch_collect_text / _seek of both batches are untouched, and
+ *                           kr_debug_extract_ms of either stream times all kernels of the call.
+ *                           KR_ERR_ARG: a NULL stream, an unknown rule.  KR_ERR_STATE: streams of different kr_index objects; a
+ *                           stream without extract or without defer; the last submit of one was not a raw-bytes seek batch, or
+ *                           it failed, or accepted no record; different record counts (the message names both); an odd count
+ *                           with a == b; different thresholds (they must be bitwise equal, or both NaN). */
 #define KR_EXTRACT_MATCHED   1u
 #define KR_EXTRACT_UNMATCHED 2u
+#define KR_PAIR_ANY  1u
+#define KR_PAIR_BOTH 2u
 typedef struct kr_extract_view {
   uint32_t nreads, nmatched;
   uint64_t matched_bytes, unmatched_bytes;   /* record bytes of each part (plain) */
@@ -924,6 +951,8 @@ KR_API int kr_stream_extract_max(kr_stream*, double max_dist);      /* between b
 KR_API int kr_batch_collect_extract(kr_stream*, uint32_t which, kr_extract_view* out);
 KR_API int kr_batch_collect_extract_bgzf(kr_stream*, uint32_t which, uint32_t level, kr_extract_view* out);
 KR_API int kr_debug_extract_ms(kr_stream*, float* ms);              /* the extract kernels of the last batch, HIP events */
+KR_API int kr_stream_extract_defer(kr_stream*, uint32_t on);        /* between batches */
+KR_API int kr_batch_extract_pair(kr_stream* a, kr_stream* b, uint32_t rule);
 /* tests: the tiled form of the batch last submitted on the stream as it lies on the device, laid out by the host (a host batch)
  * or by kernels (KR_TILE_DEVICE): reads of the tiled batch and long sequences; voff [nv + 1] where every read of the tiled batch
  * starts in its bases, vtile [nv] 1 = a tile of a long sequence, rfirst [nreads] the caller's read's first read of the tiled batch,

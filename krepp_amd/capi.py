@@ -65,6 +65,7 @@ class KrSeekView(C.Structure):
 
 
 KR_EXTRACT_MATCHED, KR_EXTRACT_UNMATCHED = 1, 2
+KR_PAIR_ANY, KR_PAIR_BOTH = 1, 2
 
 
 class KrExtractView(C.Structure):
@@ -183,6 +184,7 @@ EXPORTS = [
     "kr_debug_index_stats_ms",
     "kr_stream_seek_enable", "kr_batch_collect_seek", "kr_debug_seek_layout", "kr_debug_seek_ms",
     "kr_stream_extract_enable", "kr_stream_extract_max", "kr_batch_collect_extract", "kr_batch_collect_extract_bgzf", "kr_debug_extract_ms",
+    "kr_stream_extract_defer", "kr_batch_extract_pair", "kr_fastq_pair_cut",
     "kr_stream_bgzf_enable", "kr_batch_submit_bgzf", "kr_debug_bgzf_inflate", "kr_debug_bgzf_inflate_host", "kr_debug_bgzf_ms",
     "kr_bgzf_member_size", "kr_bgzf_walk", "kr_bgzf_chunk_cut", "kr_fastx_open_at_bgzf",
     "kr_bgzf_deflate_bound", "kr_bgzf_deflate_host", "kr_bgzf_eof", "kr_debug_bgzf_deflate_stats",
@@ -371,6 +373,9 @@ def load():
     lib.kr_batch_collect_extract.argtypes = [vp, C.c_uint32, C.POINTER(KrExtractView)]
     lib.kr_batch_collect_extract_bgzf.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(KrExtractView)]
     lib.kr_debug_extract_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    lib.kr_stream_extract_defer.argtypes = [vp, C.c_uint32]
+    lib.kr_batch_extract_pair.argtypes = [vp, vp, C.c_uint32]
+    lib.kr_fastq_pair_cut.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
     lib.kr_debug_tile_shape.argtypes = [C.c_uint64, C.c_uint32, u64p, u64p, u64p]
     lib.kr_fastx_next.argtypes = [vp, C.c_uint64, C.POINTER(KrFastxBatch)]
     lib.kr_fastx_detach.argtypes = [vp, C.POINTER(vp)]
@@ -1036,6 +1041,15 @@ class Stream:
         check(self.lib.kr_batch_collect_extract_bgzf(self.h, int(which), int(level), C.byref(v)))
         return self._extract_dict(v)
 
+    def extract_defer(self, on=True):
+        """kr_stream_extract_defer: a raw-bytes seek submit leaves the split to extract_pair (paired reads); False: as before"""
+        check(self.lib.kr_stream_extract_defer(self.h, 1 if on else 0))
+
+    def extract_pair(self, other, rule=KR_PAIR_ANY):
+        """kr_batch_extract_pair: this stream's batch and `other`'s hold the mates (other is self: one interleaved batch); both are split
+        by the pair's verdict (KR_PAIR_ANY / KR_PAIR_BOTH), then collect_extract / collect_extract_bgzf on each stream"""
+        check(self.lib.kr_batch_extract_pair(self.h, other.h, int(rule)))
+
     def extract_ms(self):
         """kr_debug_extract_ms: device milliseconds of the last batch's extract kernels"""
         ms = C.c_float(0)
@@ -1162,6 +1176,16 @@ def fasta_chunk_cut(buf):
     """kr_fasta_chunk_cut: the position of the last record start ('>' behind a newline) in buf[1:], 0 when there is none"""
     buf = bytes(buf)
     return int(load().kr_fasta_chunk_cut(buf, len(buf)))
+
+
+def fastq_pair_cut(a, b=None, max_records=0xFFFFFFFF):
+    """kr_fastq_pair_cut: (cut_a, cut_b, n) -- the largest n <= max_records such that a and b both hold 4n complete lines, and the byte
+    behind the 4n-th newline of each; b None: the interleaved form, the largest even n of a (cut_b is 0)"""
+    ca, cb, n = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+    a = bytes(a)
+    b = None if b is None else bytes(b)
+    check(load().kr_fastq_pair_cut(a, len(a), b, 0 if b is None else len(b), int(max_records), C.byref(ca), C.byref(cb), C.byref(n)))
+    return int(ca.value), int(cb.value), int(n.value)
 
 
 def fastq_chunk_cut(buf):

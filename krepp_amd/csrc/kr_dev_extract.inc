@@ -22,6 +22,8 @@
 // The record count n comes from the record finder's device summary; every index is bounded by it and by the list capacities before
 // it indexes anything, every load of the chunk starts in front of `consumed` (d_raw is padded for 16 bytes), and every store is
 // checked against `consumed`, the size of what `out` holds.
+// Paired reads (the end of this file): kr_ex_pair_kernel writes one value per pair, the four kernels take it through ExIO::d in place
+// of the read's own distance and run unchanged -- both mates of a pair land in the same part.
 struct ExIO {
   const uint8_t* raw;
   const kr_fastq_parse* sum; // the record finder's summary on the device: nreads, consumed
@@ -174,5 +176,54 @@ __global__ __launch_bounds__(256) void kr_ex_copy_kernel(ExIO x)
       }
       p = re;
     }
+  }
+}
+
+// ---- paired reads: one verdict per PAIR in front of the partition (kr_batch_extract_pair; docs/design/13_seek.md section 13.7) ----
+// Two seek batches hold the mates of the same pairs -- record r of stream A and record r of stream B -- or one batch holds them as
+// neighbours (interleaved: the mate of record r is record r ^ 1).  kr_ex_pair_kernel writes, per record and per stream, one PAIR VALUE
+// that the four kernels above take in place of the read's own distance (ExIO::d):
+//   KR_PAIR_ANY    the smaller of the two distances that are not NaN; NaN when both are
+//   KR_PAIR_BOTH   NaN when either is NaN, otherwise the larger
+// so that ex_matched(pair value, max_dist) == matched(d1) || matched(d2), respectively matched(d1) && matched(d2): d <= max_dist holds
+// for the smaller of two numbers iff it holds for one of them, for the larger iff for both.  Both mates carry the same value, so both
+// land in the same part, and record i of A's matched part is the mate of record i of B's matched part (the partition is stable).
+// The pair count is the smaller of the two record finders' device counts, each clamped to its stream's max_reads; a record of either
+// stream behind it (the host refuses unequal counts: never) has no mate and takes the value a NaN mate gives.  Nothing is indexed
+// before it is compared with its stream's own clamped count.
+struct ExPairIO {
+  const kr_fastq_parse *sum_a, *sum_b; // the record finders' device summaries (interleaved: the same)
+  uint32_t max_a, max_b;               // the streams' max_reads: what d_* and pv_* hold
+  const double *d_a, *d_b;             // the seek batches' reported distances
+  double *pv_a, *pv_b;                 // [max_reads] the pair values (interleaved: pv_b == pv_a)
+  uint32_t rule;                       // KR_PAIR_ANY, KR_PAIR_BOTH
+  uint32_t interleaved;
+};
+
+__device__ __forceinline__ double ex_pair_value(double x, double y, uint32_t rule)
+{
+  const bool nx = x != x, ny = y != y;
+  if (rule == KR_PAIR_BOTH) return (nx || ny) ? __builtin_nan("") : (x > y ? x : y);
+  if (nx) return y; // (NaN when both are)
+  if (ny) return x;
+  return x < y ? x : y;
+}
+
+__global__ __launch_bounds__(256) void kr_ex_pair_kernel(ExPairIO p)
+{
+  const uint32_t na = min(p.sum_a->nreads, p.max_a), nb = min(p.sum_b->nreads, p.max_b);
+  const uint32_t n = min(na, nb), top = max(na, nb);
+  const double none = __builtin_nan("");
+  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < top; i += (uint64_t)gridDim.x * 256u) {
+    const uint32_t r = (uint32_t)i;
+    if (p.interleaved) { // (na == nb == n)
+      const uint32_t m = r ^ 1u;
+      p.pv_a[r] = ex_pair_value(p.d_a[r], m < n ? p.d_a[m] : none, p.rule);
+      continue;
+    }
+    const double x = r < na ? p.d_a[r] : none, y = r < nb ? p.d_b[r] : none;
+    const double v = ex_pair_value(x, y, p.rule);
+    if (r < na) p.pv_a[r] = v;
+    if (r < nb) p.pv_b[r] = v;
   }
 }

@@ -64,7 +64,7 @@
 //   kr_host_gzip.inc       kr_gzdev_open / _read / _point / _counters / _close, kr_debug_gzdev_inflate (the driver between the kernels: kr_gzip_super.h)
 //   kr_host_deflate.inc    kr_stream_bgzf_out_enable, kr_stream_bgzf_member, kr_stream_place_bgzf, kr_batch_collect_text_bgzf, kr_debug_bgzf_deflate / _at / _ms
 //   kr_host_place.inc      kr::place_on_device (launch of the place kernels for kr_place_stream and kr_place_stream_parsed)
-//   kr_host_extract.inc    kr_stream_extract_enable / _max, kr_batch_collect_extract / _bgzf, kr_debug_extract_ms
+//   kr_host_extract.inc    kr_stream_extract_enable / _max / _defer, kr_batch_extract_pair, kr_batch_collect_extract / _bgzf, kr_debug_extract_ms
 //   kr_host_seek.inc       kr_stream_seek_enable, a KR_SEEK batch's submit / wait, kr_batch_collect_seek, kr_debug_seek_layout / _ms
 //   (below, in this file)  kr_host_alloc, debug entry points, kr_llh_batch, kr_llh_eval_indexed
 #include <hip/hip_runtime.h>

@@ -1625,6 +1625,41 @@ uint64_t kr_fastq_chunk_cut(const uint8_t* buf, uint64_t n)
   return cut;
 }
 
+// the records of four lines that buf[0 .. n) holds whole, at most max_records: their number, and the byte behind the last one's last '\n'
+static uint32_t fastq_whole_records(const uint8_t* buf, uint64_t n, uint32_t max_records, uint64_t* end)
+{
+  uint32_t rec = 0, lines = 0;
+  uint64_t pos = 0;
+  *end = 0;
+  while (rec < max_records && pos < n) {
+    const uint8_t* nl = (const uint8_t*)memchr(buf + pos, '\n', n - pos);
+    if (!nl) break;
+    pos = (uint64_t)(nl - buf) + 1;
+    if (++lines == 4) lines = 0, ++rec, *end = pos;
+  }
+  return rec;
+}
+
+// Paired reads (`krepp seek --query2 / --interleaved`): two buffers that each begin at a record start of four-line FASTQ are cut
+// behind the same number of records -- the largest n <= max_records such that both hold 4n complete lines; b == nullptr: one buffer
+// with the mates as neighbours, the largest EVEN n.  Newlines are counted and nothing else: whether the records are clean is for the
+// device's record finder to say.
+int kr_fastq_pair_cut(const uint8_t* a, uint64_t na, const uint8_t* b, uint64_t nb, uint32_t max_records, uint64_t* cut_a, uint64_t* cut_b, uint32_t* nrec)
+{
+  kr::clear_error();
+  if (!a || !cut_a || !nrec || (b && !cut_b)) return kr::fail(KR_ERR_ARG, "kr_fastq_pair_cut: null argument");
+  uint64_t ea = 0, eb = 0;
+  uint32_t n = fastq_whole_records(a, na, b ? max_records : max_records & ~1u, &ea);
+  if (b) {
+    const uint32_t nb_rec = fastq_whole_records(b, nb, n, &eb); // (<= n)
+    if (nb_rec < n) n = fastq_whole_records(a, na, nb_rec, &ea);
+  } else if (n & 1u)
+    n = fastq_whole_records(a, na, n - 1u, &ea);
+  *cut_a = ea, *nrec = n;
+  if (cut_b) *cut_b = b ? eb : 0;
+  return KR_OK;
+}
+
 // ---- block-gzipped bytes for the device's inflate (kr_batch_submit_bgzf): the walk over members, the chunk cut, the hand-over -------
 uint32_t kr_bgzf_member_size(const uint8_t* h, uint64_t avail) { return h ? kr::bgzf_member_size(h, avail) : 0u; }
 

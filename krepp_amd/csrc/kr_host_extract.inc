@@ -1,5 +1,5 @@
-// kr_host_extract.inc -- part of kr_device.hip (host side): kr_stream_extract_enable, kr_stream_extract_max,
-// kr_batch_collect_extract, kr_batch_collect_extract_bgzf, kr_debug_extract_ms.  Kernels: kr_dev_extract.inc.
+// kr_host_extract.inc -- part of kr_device.hip (host side): kr_stream_extract_enable, kr_stream_extract_max, kr_stream_extract_defer,
+// kr_batch_extract_pair, kr_batch_collect_extract, kr_batch_collect_extract_bgzf, kr_debug_extract_ms.  Kernels: kr_dev_extract.inc.
 // A seek batch that a record finder queued (kr_batch_submit_fastq / _fasta / _bgzf with KR_SEEK) on a stream with extract enabled
 // has the extract kernels queued behind its solve and text kernels, on the same stream and inside the same link of the index's
 // kernel chain (seek_queue, kr_host_seek.inc): the chunk's accepted bytes [0, consumed) land in d_out as the matched reads followed
@@ -8,8 +8,9 @@
 
 namespace {
 
-// queued by seek_queue behind the batch's last kernel; the chunk is the stream's last record finder call's
-int extract_queue(kr_stream* s, hipStream_t st)
+// the four extract kernels on `st` with the verdict taken from d[0 .. n): the reads' own distances (extract_queue) or the pair
+// values (kr_batch_extract_pair); the chunk is the stream's last record finder call's
+int extract_launch(kr_stream* s, hipStream_t st, const double* d)
 {
   kr_stream::Extract& e = s->extract;
   const kr_stream::Fastq& f = s->fq;
@@ -18,7 +19,7 @@ int extract_queue(kr_stream* s, hipStream_t st)
   x.nl = f.last_fasta ? nullptr : f.d_nl, x.nl_cap = 4u * s->max_reads;
   x.hs = f.d_hs, x.max_reads = s->max_reads, x.raw_cap = f.raw_cap;
   if (f.last_fasta && !f.d_hs) return kr::fail(KR_ERR_STATE, "extract: the FASTA record finder's start list is missing");
-  x.d = s->seek.d_d, x.max_dist = e.max_dist;
+  x.d = d, x.max_dist = e.max_dist;
   x.rec_start = e.d_start, x.mpre = e.d_mpre, x.bsum = e.d_bsum, x.out = e.d_out, x.res = e.d_res;
   static const bool bytes_only = getenv("KR_EXTRACT_STORE") && atoi(getenv("KR_EXTRACT_STORE")) == 1; // (measurements: byte stores only)
   x.wide = bytes_only ? 0u : 1u;
@@ -28,11 +29,19 @@ int extract_queue(kr_stream* s, hipStream_t st)
   // the work is shared out, never what is computed.
   const uint32_t bgrid = std::min<uint32_t>(s->batch.nreads / kRowBlock + 1u, 4096u);
   const uint32_t tgrid = std::min<uint32_t>((uint32_t)((f.h_sum->consumed + kFqTile - 1) / kFqTile) + 1u, 65536u);
-  HIP_TRY(hipEventRecord(e.ev[0], st));
   hipLaunchKernelGGL(kr_ex_len_kernel, dim3(bgrid), dim3(256), 0, st, x);
   hipLaunchKernelGGL(kr_ex_scan_kernel, dim3(1), dim3(1024), 0, st, x);
   hipLaunchKernelGGL(kr_ex_pre_kernel, dim3(bgrid), dim3(256), 0, st, x);
   hipLaunchKernelGGL(kr_ex_copy_kernel, dim3(tgrid), dim3(256), 0, st, x);
+  return KR_OK;
+}
+
+// queued by seek_queue behind the batch's last kernel
+int extract_queue(kr_stream* s, hipStream_t st)
+{
+  kr_stream::Extract& e = s->extract;
+  HIP_TRY(hipEventRecord(e.ev[0], st));
+  if (int rc = extract_launch(s, st, s->seek.d_d)) return rc;
   HIP_TRY(hipEventRecord(e.ev[1], st));
   e.timed = true;
   HIP_TRY(hipMemcpyAsync(e.h_res, e.d_res, 32, hipMemcpyDeviceToHost, st));
@@ -48,6 +57,8 @@ int extract_ready(kr_stream* s, uint32_t which, kr_extract_view* out, const char
   memset(out, 0, sizeof(*out));
   if (!s->extract.on) return kr::fail(KR_ERR_STATE, w + "kr_stream_extract_enable first");
   if (!s->batch.submitted || !s->batch.seek) return kr::fail(KR_ERR_STATE, w + "the last batch was not submitted with KR_SEEK");
+  if (s->parse.parsed && s->batch.extract_deferred && !s->batch.extract)
+    return kr::fail(KR_ERR_STATE, w + "the stream defers its split (kr_stream_extract_defer): kr_batch_extract_pair first");
   if (!s->parse.parsed || !s->batch.extract)
     return kr::fail(KR_ERR_STATE, w + "the last submit was not a seek batch of raw bytes (kr_batch_submit_fastq / _fasta / _bgzf with KR_SEEK)");
   if (s->parse.nreads == 0) return kr::fail(KR_ERR_STATE, w + "the last submit accepted no record");
@@ -90,6 +101,88 @@ int kr_stream_extract_max(kr_stream* s, double max_dist)
   if (max_dist == max_dist && (max_dist < 0 || std::isinf(max_dist))) return kr::fail(KR_ERR_ARG, "kr_stream_extract_max: max_dist is negative or infinite (NaN: no threshold)");
   if (!s->extract.on) return kr::fail(KR_ERR_STATE, "kr_stream_extract_max: kr_stream_extract_enable first");
   s->extract.max_dist = max_dist; // (read when the next batch is queued: the batch in flight keeps its rule)
+  return KR_OK;
+}
+
+int kr_stream_extract_defer(kr_stream* s, uint32_t on)
+{
+  kr::clear_error();
+  if (!s) return kr::fail(KR_ERR_ARG, "kr_stream_extract_defer: null argument");
+  if (!s->extract.on) return kr::fail(KR_ERR_STATE, "kr_stream_extract_defer: kr_stream_extract_enable first");
+  kr_stream::Extract& e = s->extract;
+  if (on && !e.ev_x[0]) {
+    HIP_TRY(hipSetDevice(s->ix->device));
+    for (auto& ev : e.ev_x) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  }
+  e.defer = on != 0; // (read when the next batch is queued: the batch in flight stays what it is)
+  return KR_OK;
+}
+
+// The mates of a pair are split together.  Everything is queued on A's lane: it waits for B's lane as it stands now (B's solve and
+// text kernels are behind that event), runs the pair kernel, the four extract kernels of A, those of B, and both summary copies; B's
+// lane then waits for the event behind them, so kr_batch_wait(b) and B's next drain_batch cover the lot.  Every event is recorded
+// before the wait on it is queued -- there is no cycle --, and the order holds without the index's kernel chain (chain_off): the
+// ChainLink only keeps other batches' kernels out from between these.
+int kr_batch_extract_pair(kr_stream* a, kr_stream* b, uint32_t rule)
+{
+  kr::clear_error();
+  const std::string w = "kr_batch_extract_pair: ";
+  if (!a || !b) return kr::fail(KR_ERR_ARG, w + "null argument");
+  if (rule != KR_PAIR_ANY && rule != KR_PAIR_BOTH) return kr::fail(KR_ERR_ARG, w + "rule " + std::to_string(rule) + " (KR_PAIR_ANY or KR_PAIR_BOTH)");
+  const bool inter = a == b;
+  if (a->ix != b->ix) return kr::fail(KR_ERR_STATE, w + "the two streams are on different indexes");
+  for (kr_stream* s : {a, b}) {
+    if (!s->extract.on) return kr::fail(KR_ERR_STATE, w + "kr_stream_extract_enable first");
+    if (!s->extract.defer) return kr::fail(KR_ERR_STATE, w + "kr_stream_extract_defer first: the stream splits every batch by its own reads");
+    const Batch& q = s->batch;
+    if (!q.submitted || !q.seek || !s->parse.parsed || !q.from.parsed || !q.extract_deferred) // (deferred: also a batch that a pair call has split)
+      return kr::fail(KR_ERR_STATE, w + "the last submit was not a seek batch of raw bytes (kr_batch_submit_fastq / _fasta / _bgzf with KR_SEEK) on a deferring stream");
+    if (q.rc) return kr::fail(KR_ERR_STATE, w + "the batch failed: " + q.msg);
+    if (s->parse.nreads == 0) return kr::fail(KR_ERR_STATE, w + "the last submit accepted no record");
+  }
+  const uint32_t n = a->parse.nreads;
+  if (b->parse.nreads != n)
+    return kr::fail(KR_ERR_STATE, w + "the two batches hold " + std::to_string(n) + " and " + std::to_string(b->parse.nreads) + " records: mates must be the same records of both");
+  if (inter && (n & 1u)) return kr::fail(KR_ERR_STATE, w + "an interleaved batch of " + std::to_string(n) + " records: the last one has no mate");
+  const double ta = a->extract.max_dist, tb = b->extract.max_dist;
+  if (!((ta != ta && tb != tb) || memcmp(&ta, &tb, sizeof(ta)) == 0)) return kr::fail(KR_ERR_STATE, w + "the two streams have different thresholds (kr_stream_extract_max)");
+  HIP_TRY(hipSetDevice(a->ix->device));
+  (void)hipGetLastError();
+  for (kr_stream* s : {a, b})
+    if (!s->extract.d_pair)
+      if (int rc = salloc(s, &s->extract.d_pair, (uint64_t)s->max_reads)) return rc;
+  kr_stream::Extract &ea = a->extract, &eb = b->extract;
+  hipStream_t sa = a->lanes[0].stream, sb = b->lanes[0].stream;
+  if (!inter) {
+    HIP_TRY(hipEventRecord(eb.ev_x[0], sb));
+    HIP_TRY(hipStreamWaitEvent(sa, eb.ev_x[0], 0));
+  }
+  ChainLink chain(a->ix, sa);
+  HIP_TRY(chain.opened);
+  HIP_TRY(hipEventRecord(ea.ev[0], sa));
+  if (!inter) HIP_TRY(hipEventRecord(eb.ev[0], sa));
+  ExPairIO p;
+  p.sum_a = a->fq.d_sum, p.sum_b = b->fq.d_sum, p.max_a = a->max_reads, p.max_b = b->max_reads;
+  p.d_a = a->seek.d_d, p.d_b = b->seek.d_d, p.pv_a = ea.d_pair, p.pv_b = eb.d_pair;
+  p.rule = rule, p.interleaved = inter ? 1u : 0u;
+  hipLaunchKernelGGL(kr_ex_pair_kernel, dim3(std::min<uint32_t>(n / 256u + 1u, 4096u)), dim3(256), 0, sa, p);
+  if (int rc = extract_launch(a, sa, ea.d_pair)) return rc;
+  if (!inter)
+    if (int rc = extract_launch(b, sa, eb.d_pair)) return rc;
+  HIP_TRY(hipEventRecord(ea.ev[1], sa));
+  if (!inter) HIP_TRY(hipEventRecord(eb.ev[1], sa));
+  HIP_TRY(hipMemcpyAsync(ea.h_res, ea.d_res, 32, hipMemcpyDeviceToHost, sa));
+  if (!inter) HIP_TRY(hipMemcpyAsync(eb.h_res, eb.d_res, 32, hipMemcpyDeviceToHost, sa));
+  HIP_TRY(chain.close(sa));
+  if (!inter) {
+    HIP_TRY(hipEventRecord(ea.ev_x[1], sa));
+    HIP_TRY(hipStreamWaitEvent(sb, ea.ev_x[1], 0));
+  }
+  HIP_TRY(hipGetLastError());
+  for (kr_stream* s : {a, b}) { // the parts are new: the batches are waited for again, nothing of the split is in the mirrors
+    s->extract.timed = true;
+    s->batch.extract = true, s->batch.extract_have = 0, s->batch.waited = false;
+  }
   return KR_OK;
 }
 

@@ -83,8 +83,12 @@ static int seek_queue(kr_stream* s, const uint8_t* bases, const uint64_t* offset
   HIP_TRY(hipEventRecord(k.ev[3], st));
   k.timed = true;
   if (s->extract.on && b.from.parsed) { // the chunk is in fq.d_raw, the record finder's lists beside it: split it by d
-    if (int rc = extract_queue(s, st)) return rc;
-    s->batch.extract = true;
+    if (s->extract.defer) // (paired reads: kr_batch_extract_pair splits it, by the pair's verdict)
+      s->batch.extract_deferred = true;
+    else {
+      if (int rc = extract_queue(s, st)) return rc;
+      s->batch.extract = true;
+    }
   }
   HIP_TRY(chain.close(st));
   HIP_TRY(hipGetLastError());

@@ -72,6 +72,7 @@ struct Batch {
   bool seek_view = false;    // ... whose values are in the page-locked mirrors
   bool extract = false;      // ... whose reads the extract kernels split (kr_host_extract.inc): a record finder queued it on an extract stream
   uint32_t extract_have = 0; // ... and the parts (KR_EXTRACT_*) that are in the page-locked mirror
+  bool extract_deferred = false; // ... or would have, on a stream with kr_stream_extract_defer: kr_batch_extract_pair queues the kernels
   uint32_t nrecs = 0;
   uint64_t nhits = 0;
   uint64_t ndist = 0, h_ndist = 0; // entries of the batch's list of distinct values (set by kr_batch_wait: a device view shows it too), of its host copy
@@ -297,6 +298,10 @@ struct kr_stream {
     PinBuf<uint8_t> h_members; // kr_batch_collect_extract_bgzf: the matched part's members, then the unmatched part's
     hipEvent_t ev[2] = {};     // around the extract kernels
     bool timed = false;
+    // paired reads (kr_stream_extract_defer, kr_batch_extract_pair): a seek submit leaves the split to the pair call
+    bool defer = false;
+    double* d_pair = nullptr;   // [max_reads] the pair values of the batch in flight, made by the first pair call
+    hipEvent_t ev_x[2] = {};    // this stream's lane at the pair call (the other stream's lane waits for it); behind the pair call's last copy
   } extract;
   Batch batch;     // the batch in flight
   LastParse parse; // the last record finder's call
@@ -1103,6 +1108,8 @@ void kr_stream_destroy(kr_stream* s)
   for (auto& e : s->seek.ev)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : s->extract.ev)
+    if (e) (void)hipEventDestroy(e);
+  for (auto& e : s->extract.ev_x)
     if (e) (void)hipEventDestroy(e);
   delete s; // (every DevBuf / PinBuf of the stream frees itself here: the device is set, the lanes' streams have been waited for)
 }

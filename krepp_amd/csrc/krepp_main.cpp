@@ -55,7 +55,7 @@ static const std::map<std::string, std::string> kAlias = {
   {"-i", "--index-dir"}, {"-q", "--query"}, {"-o", "--output-path"}, {"-t", "--nwk-file"}, {"-k", "--kmer-len"},
   {"-w", "--win-len"}, {"-h", "--num-positions"}, {"-m", "--modulo-lsh"}, {"-r", "--residue-lsh"}, {"-l", "--lineage-file"},
 };
-static const char* kFlags[] = {"--multi", "--filter", "--summarize", "--frac", "--verbose", "--gpu-minimizers", "--gpu-keys", "--gpu-colours", "--tabular", "--gpu-parse", "--gpu-seek", "--gpu-stats", "--bgzf-out", "--gpu-deflate", "--gpu-inflate", "--extract-bgzf"};
+static const char* kFlags[] = {"--multi", "--filter", "--summarize", "--frac", "--verbose", "--gpu-minimizers", "--gpu-keys", "--gpu-colours", "--tabular", "--gpu-parse", "--gpu-seek", "--gpu-stats", "--bgzf-out", "--gpu-deflate", "--gpu-inflate", "--extract-bgzf", "--interleaved"};
 
 // options as in the reference's CLI (src/krepp.cpp:516-675); the texts are this build's own
 static void print_help(const std::string& sub)
@@ -111,7 +111,13 @@ static void print_help(const std::string& sub)
            "      --extract-matched FILE   with --gpu-parse --gpu-seek: the reads whose row carries a DIST, as the exact bytes they have in the input, split on the GPU\n"
            "      --extract-unmatched FILE the other reads (rows with NaN, or above --extract-max); either file or both\n"
            "      --extract-max D        a read is matched only when its DIST is at most D, 0..1 [no limit]\n"
-           "      --extract-bgzf         the extract files are BGZF, deflated on the GPU (--bgzf-level and --bgzf-member apply)\n",
+           "      --extract-bgzf         the extract files are BGZF, deflated on the GPU (--bgzf-level and --bgzf-member apply)\n"
+           "      --query2 FILE          paired reads: the mates' file (plain FASTQ, record for record with -q); both mates of a pair go to the same part\n"
+           "      --output-path2 FILE    with --query2: the report of the mates [not written]\n"
+           "      --extract-matched2 FILE   with --query2 and --extract-matched: the matched pairs' mates, record for record with --extract-matched\n"
+           "      --extract-unmatched2 FILE with --query2 and --extract-unmatched: the other pairs' mates\n"
+           "      --interleaved          paired reads in one file: every pair as two neighbouring records of -q (not with --query2)\n"
+           "      --pair-rule any|both   a pair is matched when either mate is, or only when both are [any]\n",
            query_opts);
   if (sub.empty() || sub == "index")
     printf("\nkrepp index -i MAP.tsv -o DIR: build an index (reference ID <tab> FASTA path per line)\n"
@@ -196,6 +202,11 @@ struct Settings {
   bool extract_bgzf = false;                                     // --extract-bgzf: the two files as BGZF members, deflated on the device
   bool extract() const { return !extract_matched.empty() || !extract_unmatched.empty(); }
   uint32_t extract_which() const { return (extract_matched.empty() ? 0u : KR_EXTRACT_MATCHED) | (extract_unmatched.empty() ? 0u : KR_EXTRACT_UNMATCHED); }
+  // paired reads (--query2 FILE or --interleaved): both mates of a pair go to the same part (kr_batch_extract_pair)
+  std::string query2, output2, extract_matched2, extract_unmatched2;
+  bool interleaved = false;
+  uint32_t pair_rule = KR_PAIR_ANY;
+  bool paired() const { return !query2.empty() || interleaved; }
   int ngpus = 1, dev0 = 0, wpg = 2, nworkers = 2, write_threads = 4;
   uint32_t max_reads = 0;
   uint64_t batch_bases = 0, max_bases = 0, chunk_bytes = 0, max_records = 0, text_bytes = 0;
@@ -261,6 +272,40 @@ static Settings resolve_settings(const Args& a, const std::string& invocation, i
     if (s.extract_matched == s.extract_unmatched) error_exit("--extract-matched and --extract-unmatched name the same file: " + s.extract_matched);
     if (a.has("--output-path") && (a.get("--output-path") == s.extract_matched || a.get("--output-path") == s.extract_unmatched))
       error_exit("an --extract-* file is also the report's (-o): " + a.get("--output-path"));
+  }
+  s.query2 = a.get("--query2"), s.output2 = a.get("--output-path2");
+  s.extract_matched2 = a.get("--extract-matched2"), s.extract_unmatched2 = a.get("--extract-unmatched2");
+  s.interleaved = a.flag.count("--interleaved") && a.flag.at("--interleaved");
+  if (a.has("--query2") || a.has("--output-path2") || a.has("--extract-matched2") || a.has("--extract-unmatched2") || a.flag.count("--interleaved") || a.has("--pair-rule")) {
+    if (!seek) error_exit("--query2, --output-path2, --extract-matched2, --extract-unmatched2, --interleaved and --pair-rule are options of `seek`");
+    if (!s.gpu_parse || !s.gpu_seek || !s.extract())
+      error_exit("paired reads (--query2, --interleaved) need --gpu-parse, --gpu-seek and --extract-matched or --extract-unmatched: the pairs are split on the GPU");
+    if (a.has("--query2") && s.interleaved) error_exit("--interleaved and --query2 exclude each other: the mates are in a second file or in the same one");
+    if (a.has("--query2") && s.query2.empty()) error_exit("--query2: an empty file name");
+    for (const char* o : {"--output-path2", "--extract-matched2", "--extract-unmatched2"})
+      if (a.has(o) && !a.has("--query2")) error_exit(std::string(o) + " needs --query2");
+    if (!s.paired()) error_exit("--pair-rule needs --query2 or --interleaved");
+    if (a.has("--pair-rule")) {
+      const std::string v = a.get("--pair-rule");
+      if (v != "any" && v != "both") error_exit("--pair-rule: any or both, not " + v);
+      s.pair_rule = v == "any" ? KR_PAIR_ANY : KR_PAIR_BOTH;
+    }
+    if (!s.query2.empty()) {
+      if (s.extract_matched.empty() != s.extract_matched2.empty())
+        error_exit(s.extract_matched2.empty() ? "--extract-matched with --query2 needs --extract-matched2: the mates' file" : "--extract-matched2 needs --extract-matched");
+      if (s.extract_unmatched.empty() != s.extract_unmatched2.empty())
+        error_exit(s.extract_unmatched2.empty() ? "--extract-unmatched with --query2 needs --extract-unmatched2: the mates' file" : "--extract-unmatched2 needs --extract-unmatched");
+      if (s.query2 == s.query) error_exit("--query2 names the same file as -q: " + s.query2);
+      const std::string others[] = {a.get("--output-path"), s.extract_matched, s.extract_unmatched};
+      const std::string twos[] = {s.output2, s.extract_matched2, s.extract_unmatched2};
+      for (size_t x = 0; x < 3; ++x) {
+        if (twos[x].empty()) continue;
+        bool twice = false;
+        for (const std::string& o : others) twice = twice || o == twos[x];
+        for (size_t y = 0; y < x; ++y) twice = twice || twos[y] == twos[x];
+        if (twice) error_exit("an output file is named twice: " + twos[x]);
+      }
+    }
   }
   if (a.has("--bgzf-level")) {
     if (!s.bgzf_out && !s.extract_bgzf) error_exit("--bgzf-level needs --bgzf-out");
@@ -337,6 +382,11 @@ struct Job {
   std::vector<const char*> own_names;
   std::string text;
   std::string ex_matched, ex_unmatched; // seek --extract-*: the bytes the two files take from this job, plain or BGZF members
+  // paired reads: the mates' chunk (page-locked, --query2), their report rows and their two byte strings
+  uint8_t* raw2 = nullptr;
+  uint64_t raw2_len = 0, raw2_off = 0;
+  bool at_eof2 = false;
+  std::string text2, ex_matched2, ex_unmatched2;
   std::vector<kr_placement> pls; // place --summarize: the placements, `read` = global read number
   uint64_t first_read = 0;
   // --gpu-parse: a chunk of the file's raw bytes (page-locked), cut at a guessed record start; its records are found on the device
@@ -538,6 +588,11 @@ struct Run {
   // seek --extract-*: the two files (the writer's, in the report's order), and for [timing] the reads, record bytes and kernel time
   FILE *ex_matched = nullptr, *ex_unmatched = nullptr;
   std::atomic<uint64_t> ex_reads{0}, ex_nmatched{0}, ex_bytes_m{0}, ex_bytes_u{0}, ex_kernel_us{0};
+  // paired reads: the mates' file, their report (--output-path2) and extract files, and for [timing] the pairs
+  int qfd2 = -1;
+  uint64_t qsize2 = 0;
+  FILE *out2 = nullptr, *ex_matched2 = nullptr, *ex_unmatched2 = nullptr;
+  std::atomic<uint64_t> ex_pairs{0}, ex_pairs_matched{0}, ex_pair_bytes{0}, ex_pair_kernel_us{0};
   uint64_t nbatches = 0, nreads_total = 0; // the reader's
   // the writer's.  place --summarize: counts per placement-tree node, summed in input order; placements of a 512-read group that
   // straddles two jobs wait in `carry` (the groups are the reference's batches)
@@ -566,7 +621,9 @@ struct Run {
   void open_input();
   void worker_ready(const char* err);
   std::unique_ptr<Job> next_job();
-  void chunk_done(uint8_t* raw);
+  void chunk_done(uint8_t* raw, uint8_t* raw2 = nullptr);
+  void check_pair_inputs();
+  void read_pairs();
   void enqueue(std::unique_ptr<Job> j);
   void read_chunks();
   void read_chunks_bgzf();
@@ -581,12 +638,16 @@ struct Run {
 // the output file, the index on the host and on every GPU, the placement tree, the report's first lines
 void Run::start_up(const Args& a)
 {
+  if (s.paired()) check_pair_inputs(); // (refused before anything is loaded or created)
   if (a.has("--output-path")) {
     out = fopen(a.get("--output-path").c_str(), "w");
     if (!out) error_exit("Failed to open " + a.get("--output-path"));
   }
   if (!s.extract_matched.empty() && !(ex_matched = fopen(s.extract_matched.c_str(), "wb"))) error_exit("Failed to open " + s.extract_matched);
   if (!s.extract_unmatched.empty() && !(ex_unmatched = fopen(s.extract_unmatched.c_str(), "wb"))) error_exit("Failed to open " + s.extract_unmatched);
+  if (!s.output2.empty() && !(out2 = fopen(s.output2.c_str(), "w"))) error_exit("Failed to open " + s.output2);
+  if (!s.extract_matched2.empty() && !(ex_matched2 = fopen(s.extract_matched2.c_str(), "wb"))) error_exit("Failed to open " + s.extract_matched2);
+  if (!s.extract_unmatched2.empty() && !(ex_unmatched2 = fopen(s.extract_unmatched2.c_str(), "wb"))) error_exit("Failed to open " + s.extract_unmatched2);
   fprintf(stderr, "Loading the index and initializing...\n");
   if (s.seek ? kr_host_sketch_load(s.index_arg.c_str(), &hx) : kr_host_index_load(s.index_arg.c_str(), &hx)) error_exit(kr_last_error());
   kr_host_index_view(hx, &view);
@@ -638,6 +699,10 @@ void Run::start_up(const Args& a)
   if (s.seek) { // QuerySketch::header_dreport (src/krepp.cpp:305-309)
     const std::string h = "# software: krepp\tversion: " KREPP_VERSION "\tinvocation :" + s.invocation + "\nSEQ_ID\tDIST\n";
     put(h.data(), h.size());
+    if (out2) { // (the mates' report: the same first lines)
+      const std::string c = s.bgzf_out ? deflated(h.data(), h.size()) : h;
+      fwrite(c.data(), 1, c.size(), out2);
+    }
   } else if (!s.place) { // header (src/krepp.cpp:311-319)
     const std::string h = "# software: krepp\tversion: " KREPP_VERSION "\tinvocation :" + s.invocation + "\n" +
                           (s.summarize ? "REFERENCE_NAME\tWEIGHTED_COUNT\tSEQUENCE_ABUNDANCE" : "SEQ_ID\tREFERENCE_NAME\tDIST") + "\n";
@@ -698,6 +763,15 @@ static bool bgzf_first_byte(int fd, uint64_t size, uint8_t* first)
 // gzip, a pipe): the host reader
 void Run::open_input()
 {
+  if (s.paired()) { // (check_pair_inputs opened the files: plain FASTQ, read by pread)
+    gpu_parse = true;
+    for (int q = 0; q < 2 * (2 * s.nworkers + 1); ++q) { // (a job carries two chunks: the pool doubles)
+      uint8_t* b_ = (uint8_t*)kr_host_alloc(chunk_cap() + 16);
+      if (!b_) error_exit("cannot allocate page-locked chunk buffers for --gpu-parse");
+      raw_free.push_back(b_);
+    }
+    return;
+  }
   if (s.gpu_parse) {
     struct stat sb;
     unsigned char mg[2] = {0, 0};
@@ -758,11 +832,12 @@ std::unique_ptr<Job> Run::next_job()
   return j;
 }
 
-void Run::chunk_done(uint8_t* raw)
+void Run::chunk_done(uint8_t* raw, uint8_t* raw2)
 {
   {
     std::lock_guard<std::mutex> lk(order.mu);
     raw_free.push_back(raw);
+    if (raw2) raw_free.push_back(raw2);
     ++gpu_done;
   }
   order.cv_work.notify_all();
@@ -789,6 +864,7 @@ struct Worker {
   const int g;
   Worker(Run& r_, int g_) : r(r_), s(r_.s), g(g_) {}
   kr_stream* st = nullptr;
+  kr_stream* st2 = nullptr; // paired reads: the mates' stream on the same GPU (--interleaved: none, the pairs are in st's batch)
   bool text_on = false; // the stream formats `dist` rows on the device
   bool bgzf_dev = false; // --bgzf-out: the stream deflates its device text (kr_batch_collect_text_bgzf)
   bool bgzf_place = false; // place --bgzf-out --gpu-deflate: kr_place_stream hands back members (kr_stream_place_bgzf)
@@ -813,11 +889,16 @@ struct Worker {
   int chunk_names(const uint8_t* raw, uint32_t n);
   int collect_extract();
   int extract_stop(const char* reason, uint64_t pos);
+  const char* make_stream(kr_stream** out);
+  int run_pair_chunk();
+  int pair_stop(const std::string& reason, bool mates, uint64_t pos);
+  int collect_pair_side(kr_stream* q, std::string* rows, std::string& m, std::string& u, kr_extract_view* v);
   void keep_placements(int rc, kr_placement* pp, uint64_t npp, uint64_t base);
   void emit(const char* p, size_t n, bool whole_job);
   void emit_host(const char* p, size_t n); // rows a host formatter made: through the host encoder with --bgzf-out
   void append(const char* p, size_t n);    // ... for the job's text
-  int collect_device_text(const char** dtext, uint64_t* dlen);
+  int collect_device_text(const char** dtext, uint64_t* dlen) { return collect_device_text(st, dtext, dlen); }
+  int collect_device_text(kr_stream* q, const char** dtext, uint64_t* dlen);
   int joins() const { return (!s.tabular && !text.empty()) ? 1 : 0; } // jplace: pieces of a job are joined by the worker, jobs by the writer (src/krepp.cpp:474-484)
   void succeeded() // (grow back after a run of successes)
   {
@@ -825,41 +906,56 @@ struct Worker {
   }
 };
 
-void Worker::loop()
+// A stream of this worker's on its GPU with everything the run asked for enabled; the reason it could not be made, or null
+const char* Worker::make_stream(kr_stream** out)
 {
-  const int wid = r.worker_ids++;
-  double t_first = -1, t_last = 0;
-  uint64_t njobs = 0;
+  kr_stream* st = nullptr; // (the one being made)
   // (four times the reads of a batch: a batch of contigs is submitted as tiles of 128 k-mer positions, include/krepp_amd.h)
-  if (kr_stream_create(r.dix[g], (s.place || s.seek) ? &s.pfront : &s.p, 4 * s.max_reads, s.max_bases, s.max_records, &st)) return r.worker_ready(kr_last_error());
-  wc.assign(r.wcount.size(), 0.0);
+  if (kr_stream_create(r.dix[g], (s.place || s.seek) ? &s.pfront : &s.p, 4 * s.max_reads, s.max_bases, s.max_records, &st)) return kr_last_error();
   if (s.dev_text) { // (and 64 bytes of id per read)
     if (kr_stream_text_enable(st, r.hx, s.text_bytes, std::max<uint64_t>(1ull << 20, (uint64_t)s.max_reads * 64)) == 0)
       text_on = true;
     else
       fprintf(stderr, "[krepp_amd] report text on the host: %s\n", kr_last_error());
   }
-  if (s.gpu_seek && kr_stream_seek_enable(st, s.text_bytes, std::max<uint64_t>(1ull << 20, (uint64_t)s.max_reads * 64))) return r.worker_ready(kr_last_error());
+  if (s.gpu_seek && kr_stream_seek_enable(st, s.text_bytes, std::max<uint64_t>(1ull << 20, (uint64_t)s.max_reads * 64))) return kr_last_error();
   if (s.bgzf_out && (text_on || s.gpu_seek)) {
-    if (kr_stream_bgzf_out_enable(st)) return r.worker_ready(kr_last_error());
-    if (s.bgzf_level != 1 && kr_stream_bgzf_out_level(st, s.bgzf_level)) return r.worker_ready(kr_last_error());
+    if (kr_stream_bgzf_out_enable(st)) return kr_last_error();
+    if (s.bgzf_level != 1 && kr_stream_bgzf_out_level(st, s.bgzf_level)) return kr_last_error();
     bgzf_dev = true;
   }
-  if ((s.bgzf_out || s.extract_bgzf) && s.bgzf_member != 65280 && kr_stream_bgzf_member(st, s.bgzf_member)) return r.worker_ready(kr_last_error());
+  if ((s.bgzf_out || s.extract_bgzf) && s.bgzf_member != 65280 && kr_stream_bgzf_member(st, s.bgzf_member)) return kr_last_error();
   if (s.gpu_deflate) {
-    if (kr_stream_place_bgzf(st, s.bgzf_level)) return r.worker_ready(kr_last_error());
+    if (kr_stream_place_bgzf(st, s.bgzf_level)) return kr_last_error();
     bgzf_place = true;
   }
-  if (r.gpu_parse && kr_stream_fastq_enable(st, r.chunk_cap())) return r.worker_ready(kr_last_error());
-  if (r.bgzf && kr_stream_bgzf_enable(st, r.chunk_cap())) return r.worker_ready(kr_last_error());
-  if (s.extract() && kr_stream_extract_enable(st, s.extract_max)) return r.worker_ready(kr_last_error());
+  if (r.gpu_parse && kr_stream_fastq_enable(st, r.chunk_cap())) return kr_last_error();
+  if (r.bgzf && kr_stream_bgzf_enable(st, r.chunk_cap())) return kr_last_error();
+  if (s.extract() && kr_stream_extract_enable(st, s.extract_max)) return kr_last_error();
+  *out = st;
+  return nullptr;
+}
+
+void Worker::loop()
+{
+  const int wid = r.worker_ids++;
+  double t_first = -1, t_last = 0;
+  uint64_t njobs = 0;
+  wc.assign(r.wcount.size(), 0.0);
+  if (const char* err = make_stream(&st)) return r.worker_ready(err);
+  if (s.paired()) { // both streams leave the split to kr_batch_extract_pair
+    if (!s.interleaved)
+      if (const char* err = make_stream(&st2)) return r.worker_ready(err);
+    if (kr_stream_extract_defer(st, 1) || (st2 && kr_stream_extract_defer(st2, 1))) return r.worker_ready(kr_last_error());
+  }
   const double t_ready = r.at();
   r.worker_ready(nullptr);
   while ((j = r.next_job())) {
     kr_fastx_held* const held = j->held; // (what outlives a job that is handed over: the reader's buffers, the chunk's)
     uint8_t* const raw = j->raw;
-    const int rc = raw ? run_chunk() : run_batch(0, j->n);
-    if (raw) r.chunk_done(raw);
+    uint8_t* const raw2 = j->raw2;
+    const int rc = s.paired() ? run_pair_chunk() : raw ? run_chunk() : run_batch(0, j->n);
+    if (raw) r.chunk_done(raw, raw2);
     if (held) kr_fastx_release(r.fx, held); // (the batch's buffers go back to the reader)
     t_last = r.at(), ++njobs;
     if (t_first < 0) t_first = t_last;
@@ -874,6 +970,7 @@ void Worker::loop()
   for (size_t q = 0; q < wc.size(); ++q) r.wcount[q] += wc[q];
   r.twcount += tw;
   r.streams_to_free.push_back(st); // (torn down with the index, after the elapsed time has been taken)
+  if (st2) r.streams_to_free.push_back(st2);
 }
 
 // Rows in the job's turn: into their place in the file, or written now.
@@ -923,12 +1020,12 @@ int Worker::collect(kr_result_view* rv, const char** dtext, uint64_t* dlen, bool
 }
 
 // The batch's device text: the bytes the output takes -- plain, or deflated into BGZF members where they lie (--bgzf-out)
-int Worker::collect_device_text(const char** dtext, uint64_t* dlen)
+int Worker::collect_device_text(kr_stream* q, const char** dtext, uint64_t* dlen)
 {
-  if (!bgzf_dev) return kr_batch_collect_text(st, dtext, dlen);
+  if (!bgzf_dev) return kr_batch_collect_text(q, dtext, dlen);
   const uint8_t* comp = nullptr;
   uint64_t text_len = 0;
-  const int rc = kr_batch_collect_text_bgzf(st, &comp, dlen, &text_len);
+  const int rc = kr_batch_collect_text_bgzf(q, &comp, dlen, &text_len);
   *dtext = (const char*)comp;
   if (!rc && text_len) r.nb_plain += text_len, r.nb_comp += *dlen, ++r.n_dev_deflate;
   return rc;
@@ -1196,6 +1293,103 @@ int Worker::extract_stop(const char* reason, uint64_t pos)
   return KR_ERR_FORMAT;
 }
 
+// paired reads: a chunk the device cannot take whole ends the run, naming the file (mates: --query2's) and the byte
+int Worker::pair_stop(const std::string& reason, bool mates, uint64_t pos)
+{
+  r.order.fail("--extract-*: " + reason + " at input offset " + std::to_string((mates ? j->raw2_off : j->raw_off) + pos) + " of " + (mates ? s.query2 : s.query) +
+               ": the records must be ones the GPU record finder accepts (include/krepp_amd.h)");
+  return KR_ERR_FORMAT;
+}
+
+// paired reads: one stream's rows (rows == nullptr: not asked for) and its two parts behind the pair call
+int Worker::collect_pair_side(kr_stream* q, std::string* rows, std::string& m, std::string& u, kr_extract_view* v)
+{
+  if (rows) {
+    const char* dtext = nullptr;
+    uint64_t dlen = 0;
+    if (int rc = collect_device_text(q, &dtext, &dlen)) return rc;
+    rows->append(dtext, dlen);
+  }
+  const int rc = s.extract_bgzf ? kr_batch_collect_extract_bgzf(q, s.extract_which(), s.bgzf_level, v) : kr_batch_collect_extract(q, s.extract_which(), v);
+  if (rc) return rc;
+  if (v->matched) m.append((const char*)v->matched, (size_t)v->matched_len);
+  if (v->unmatched) u.append((const char*)v->unmatched, (size_t)v->unmatched_len);
+  return 0;
+}
+
+// paired reads (--query2 / --interleaved): the job's two chunks hold the same records (kr_fastq_pair_cut).  Each goes to its own
+// stream, kr_batch_extract_pair splits both by the pair's verdict, and both reports and all parts are collected.  A batch that stops
+// at capacity on one side leaves the two accepted prefixes of different lengths: the longer chunk is submitted once more, cut at the
+// start of the first record the other side did not take, and the loop goes on behind both prefixes.  Every other stop ends the run.
+int Worker::run_pair_chunk()
+{
+  const bool inter = s.interleaved;
+  const uint32_t flags = KR_SEEK | KR_TILE_DEVICE;
+  uint64_t pos[2] = {0, 0}, nr_job = 0;
+  kr_stream* const q[2] = {st, st2};
+  const uint8_t* const raw[2] = {j->raw, j->raw2};
+  const uint64_t len[2] = {j->raw_len, j->raw2_len};
+  const bool eof[2] = {j->at_eof, j->at_eof2};
+  const int nside = inter ? 1 : 2;
+  auto stop_reason = [](const kr_fastq_parse& fp) -> const char* {
+    if (fp.status == KR_FASTQ_OK || (fp.status == KR_FASTQ_CAPACITY && fp.nreads)) return nullptr;
+    return fp.status == KR_FASTQ_NOT_CLEAN ? "a record that is not clean (CRLF in a FASTQ, a stray '>' '+' '@', a quality line of another length)"
+           : fp.status == KR_FASTQ_INCOMPLETE ? "an incomplete record (cut short, or a last line without '\\n')"
+                                               : "a record that does not fit a batch";
+  };
+  while (pos[0] < len[0]) {
+    if (!inter && pos[1] >= len[1]) return pair_stop("mates out of step: the mates' chunk ends in front of this record", false, pos[0]);
+    kr_fastq_parse fp[2];
+    auto t_dev = Clock::now();
+    for (int k = 0; k < nside; ++k) {
+      if (int rc = kr_batch_submit_fastq(q[k], raw[k] + pos[k], len[k] - pos[k], flags, eof[k] ? 1u : 0u, &fp[k])) return rc;
+      if (const char* why = stop_reason(fp[k])) return pair_stop(why, k == 1, pos[k] + fp[k].consumed);
+    }
+    // the pairs both sides took: the shorter prefix (one file: an even number of records)
+    const uint32_t n = inter ? fp[0].nreads & ~1u : std::min(fp[0].nreads, fp[1].nreads);
+    if (n == 0) return pair_stop("a pair that does not fit a batch", false, pos[0]);
+    for (int k = 0; k < nside; ++k) {
+      if (fp[k].nreads == n) continue;
+      const uint64_t* np = nullptr;
+      const uint32_t* nl = nullptr;
+      if (int rc = kr_batch_fastq_names(q[k], &np, &nl)) return rc;
+      const uint64_t cut = np[n] - 1; // (the '@' of the first record the other side did not take)
+      if (int rc = kr_batch_submit_fastq(q[k], raw[k] + pos[k], cut, flags, 0u, &fp[k])) return rc;
+      if (fp[k].status != KR_FASTQ_OK || fp[k].nreads != n) return pair_stop("mates out of step: the two files' records do not pair up", k == 1, pos[k]);
+    }
+    if (int rc = kr_batch_extract_pair(st, inter ? st : st2, s.pair_rule)) return rc;
+    kr_extract_view v[2];
+    int rc = collect_pair_side(st, &text, j->ex_matched, j->ex_unmatched, &v[0]);
+    if (!rc && !inter) rc = collect_pair_side(st2, r.out2 ? &j->text2 : nullptr, j->ex_matched2, j->ex_unmatched2, &v[1]);
+    r.ns_dev += since(t_dev);
+    if (rc == KR_ERR_CAPACITY) return pair_stop("more report text than a batch holds", false, pos[0]);
+    if (rc) return rc;
+    if (!inter && (v[0].nmatched != v[1].nmatched || v[0].nreads != v[1].nreads)) {
+      r.order.fail("--extract-*: the two parts of a pair batch differ in their record counts");
+      return KR_ERR_FORMAT;
+    }
+    const uint64_t div = inter ? 2 : 1;
+    r.ex_pairs += v[0].nreads / div, r.ex_pairs_matched += v[0].nmatched / div;
+    for (int k = 0; k < nside; ++k) {
+      r.ex_reads += v[k].nreads, r.ex_nmatched += v[k].nmatched, r.ex_bytes_m += v[k].matched_bytes, r.ex_bytes_u += v[k].unmatched_bytes;
+      r.ex_pair_bytes += v[k].matched_bytes + v[k].unmatched_bytes;
+      pos[k] += fp[k].consumed;
+      nr_job += fp[k].nreads;
+    }
+    float ms = 0;
+    if (s.timing && kr_debug_extract_ms(st, &ms) == 0) r.ex_kernel_us += (uint64_t)(ms * 1000.0f), r.ex_pair_kernel_us += (uint64_t)(ms * 1000.0f);
+  }
+  if (!inter && pos[1] < len[1]) return pair_stop("mates out of step: this record has no mate in the first file's chunk", true, pos[1]);
+  if (!r.order.wait_turn(*j)) {
+    text.clear();
+    j->text2.clear(), j->ex_matched.clear(), j->ex_unmatched.clear(), j->ex_matched2.clear(), j->ex_unmatched2.clear();
+    return 0;
+  }
+  j->first_read = r.nreads_dev, j->n = (size_t)nr_job;
+  r.nreads_dev += nr_job, r.nreads_seek += nr_job;
+  return 0;
+}
+
 // the writer thread: the jobs' texts in input order (jobs whose rows a worker wrote pass through empty)
 void Run::write_loop()
 {
@@ -1219,6 +1413,9 @@ void Run::write_loop()
       fwrite(j->text.data(), 1, j->text.size(), out);
       if (ex_matched) fwrite(j->ex_matched.data(), 1, j->ex_matched.size(), ex_matched);
       if (ex_unmatched) fwrite(j->ex_unmatched.data(), 1, j->ex_unmatched.size(), ex_unmatched);
+      if (out2) fwrite(j->text2.data(), 1, j->text2.size(), out2);
+      if (ex_matched2) fwrite(j->ex_matched2.data(), 1, j->ex_matched2.size(), ex_matched2);
+      if (ex_unmatched2) fwrite(j->ex_unmatched2.data(), 1, j->ex_unmatched2.size(), ex_unmatched2);
       ns_write += since(t_w);
     }
     j.reset();
@@ -1261,6 +1458,100 @@ void Run::read_chunks()
   }
   ns_parse += since(t_parse);
   chunks_done(UINT64_MAX);
+}
+
+// paired reads: both files must be plain FASTQ (gzip, BGZF and FASTA pairs are not built); settled before anything is loaded
+void Run::check_pair_inputs()
+{
+  auto open_plain = [&](const std::string& path, int* fd, uint64_t* size) {
+    struct stat sb;
+    unsigned char mg[2] = {0, 0};
+    *fd = open(path.c_str(), O_RDONLY);
+    if (*fd < 0) error_exit("Failed to open the file at " + path);
+    if (fstat(*fd, &sb) != 0 || !S_ISREG(sb.st_mode)) error_exit("paired reads: not a regular file: " + path);
+    *size = (uint64_t)sb.st_size;
+    const ssize_t k = pread(*fd, mg, 2, 0);
+    if (k == 2 && mg[0] == 0x1f && mg[1] == 0x8b)
+      error_exit("paired reads: only plain FASTQ files are accepted so far, not gzip or BGZF (with or without --gpu-inflate): " + path);
+    if (k >= 1 && mg[0] != '@') error_exit(std::string("paired reads: only plain FASTQ files are accepted so far, not ") + (mg[0] == '>' ? "FASTA" : "this file") + ": " + path);
+  };
+  open_plain(s.query, &qfd, &qsize);
+  if (!s.interleaved) open_plain(s.query2, &qfd2, &qsize2);
+}
+
+// paired reads: both files by pread in chunks, cut behind the same number of whole records (kr_fastq_pair_cut counts newlines);
+// each offset advances by its own cut.  --interleaved: one file, cut behind an even number of records
+void Run::read_pairs()
+{
+  auto t_parse = Clock::now();
+  const bool inter = s.interleaved;
+  uint64_t off[2] = {0, 0};
+  const uint64_t size[2] = {qsize, inter ? 0 : qsize2};
+  const int fd[2] = {qfd, qfd2};
+  const int nside = inter ? 1 : 2;
+  auto uneven = [&] {
+    order.fail(inter ? "--interleaved: " + s.query + " (offset " + std::to_string(off[0]) + "): the mates do not hold the same number of records -- an odd or incomplete record is left"
+                     : "paired reads: " + s.query + " (offset " + std::to_string(off[0]) + ") and " + s.query2 + " (offset " + std::to_string(off[1]) +
+                         ") do not hold the same number of records");
+  };
+  while (off[0] < size[0] || off[1] < size[1]) {
+    if (!inter && (off[0] >= size[0] || off[1] >= size[1])) { // bytes left in one file only
+      uneven();
+      break;
+    }
+    uint8_t* buf[2] = {nullptr, nullptr};
+    {
+      std::unique_lock<std::mutex> lk(order.mu);
+      order.cv_work.wait(lk, [&] { return raw_free.size() >= (size_t)nside || order.failed_locked(); });
+      if (order.failed_locked()) break;
+      for (int k = 0; k < nside; ++k) buf[k] = raw_free.back(), raw_free.pop_back();
+    }
+    uint64_t want[2] = {0, 0};
+    bool read_ok = true;
+    for (int k = 0; k < nside && read_ok; ++k) {
+      want[k] = std::min<uint64_t>(s.chunk_bytes, size[k] - off[k]);
+      uint64_t got = 0;
+      while (got < want[k]) {
+        const ssize_t n = pread(fd[k], buf[k] + got, want[k] - got, (off_t)(off[k] + got));
+        if (n <= 0) {
+          order.fail("cannot read " + (k ? s.query2 : s.query));
+          read_ok = false;
+          break;
+        }
+        got += (uint64_t)n;
+      }
+    }
+    uint64_t cut[2] = {0, 0};
+    uint32_t n = 0;
+    if (read_ok && kr_fastq_pair_cut(buf[0], want[0], inter ? nullptr : buf[1], want[1], s.max_reads, &cut[0], &cut[1], &n)) order.fail(kr_last_error()), read_ok = false;
+    if (read_ok && n == 0) {
+      const bool end0 = off[0] + want[0] >= size[0], end1 = inter || off[1] + want[1] >= size[1];
+      if (end0 || end1)
+        uneven(); // (what is left of a file is no whole record, or no whole pair)
+      else
+        order.fail("paired reads: a record longer than a chunk (" + std::to_string(s.chunk_bytes) + " bytes) at offset " + std::to_string(off[0]) + " of " + s.query + " or offset " +
+                   std::to_string(off[1]) + " of " + s.query2);
+      read_ok = false;
+    }
+    if (!read_ok) {
+      std::lock_guard<std::mutex> lk(order.mu);
+      for (int k = 0; k < nside; ++k) raw_free.push_back(buf[k]);
+      break;
+    }
+    std::unique_ptr<Job> j(new Job());
+    j->raw = buf[0], j->raw_len = cut[0], j->raw_off = off[0], j->at_eof = off[0] + cut[0] >= size[0];
+    if (!inter) j->raw2 = buf[1], j->raw2_len = cut[1], j->raw2_off = off[1], j->at_eof2 = off[1] + cut[1] >= size[1];
+    off[0] += cut[0], off[1] += cut[1];
+    enqueue(std::move(j));
+  }
+  ns_parse += since(t_parse);
+  {
+    std::unique_lock<std::mutex> lk(order.mu);
+    order.cv_done.wait(lk, [&] { return gpu_done == gpu_issued || order.failed_locked(); });
+  }
+  close(qfd);
+  if (qfd2 >= 0) close(qfd2);
+  nreads_total = nreads_dev;
 }
 
 // --gpu-parse --gpu-inflate on an ordinary gzip file: read_chunks with kr_gzdev_read in place of pread.  The bytes behind a chunk's cut
@@ -1513,7 +1804,15 @@ int Run::finish()
     fwrite(eof_member, 1, sizeof(eof_member), out);
   }
   if (out != stdout) fclose(out);
-  for (FILE* f : {ex_matched, ex_unmatched}) {
+  if (out2) {
+    if (s.bgzf_out) {
+      uint8_t eof_member[28];
+      kr_bgzf_eof(eof_member);
+      fwrite(eof_member, 1, sizeof(eof_member), out2);
+    }
+    if (fclose(out2) != 0) error_exit("Failed to write " + s.output2);
+  }
+  for (FILE* f : {ex_matched, ex_unmatched, ex_matched2, ex_unmatched2}) {
     if (!f) continue;
     if (s.extract_bgzf) { // the end member, once, last
       uint8_t eof_member[28];
@@ -1532,6 +1831,9 @@ int Run::finish()
   if (s.timing && s.extract())
     fprintf(stderr, "[timing] extract: %llu matched of %llu reads, %llu + %llu bytes, %.3f ms of kernels\n", (unsigned long long)ex_nmatched.load(), (unsigned long long)ex_reads.load(),
             (unsigned long long)ex_bytes_m.load(), (unsigned long long)ex_bytes_u.load(), ex_kernel_us.load() / 1e3);
+  if (s.timing && s.paired())
+    fprintf(stderr, "[timing] extract pairs: %llu matched of %llu pairs (rule %s), %llu bytes, %.3f ms of kernels\n", (unsigned long long)ex_pairs_matched.load(),
+            (unsigned long long)ex_pairs.load(), s.pair_rule == KR_PAIR_ANY ? "any" : "both", (unsigned long long)ex_pair_bytes.load(), ex_pair_kernel_us.load() / 1e3);
   if (s.timing && gpu_parse)
     fprintf(stderr, "[timing] gpu-parse: %llu %s records found on the device\n", (unsigned long long)nreads_dev.load(), fasta_parse ? "FASTA" : "FASTQ");
   if (s.timing && gz) {
@@ -1582,7 +1884,10 @@ static int run_query(const Args& a, const std::string& invocation, int mode)
   std::thread writer([&r] { r.write_loop(); });
   if (s.seek) fprintf(stderr, "Seeking query sequences in the sketch...\n");
   if (!s.place && !s.seek) fprintf(stderr, "Estimating distances between given sequences and references...\n");
-  if (r.gpu_parse) r.gz ? r.read_chunks_gzip() : r.bgzf ? r.read_chunks_bgzf() : r.read_chunks();
+  if (s.paired())
+    r.read_pairs();
+  else if (r.gpu_parse)
+    r.gz ? r.read_chunks_gzip() : r.bgzf ? r.read_chunks_bgzf() : r.read_chunks();
   if (r.fx) r.read_host();
   r.end_of_input();
   for (auto& w : workers) w.join();
